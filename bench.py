@@ -82,6 +82,27 @@ def _log(msg):
     print(f"[bench {time.strftime('%H:%M:%S')}] {msg}", file=sys.stderr, flush=True)
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays, seed=0):
+    """--dump-outputs: {name: (device tensor, hypothesis axis)} -> path/<name>.npy in float32.  Over DUMP_MAX_BYTES in all, every
+    array keeps the same fraction of its hypotheses, chosen by a generator seeded with `seed` (so the same rows for the same
+    arguments); -> {name: shape written}"""
+    host = {k: (t.detach().float().cpu().numpy(), ax) for k, (t, ax) in arrays.items()}
+    total = sum(a.nbytes for a, _ in host.values())
+    os.makedirs(path, exist_ok=True)
+    shapes = {}
+    for name, (a, ax) in host.items():
+        if total > DUMP_MAX_BYTES:
+            n = a.shape[ax]
+            keep = np.sort(np.random.default_rng(seed).choice(n, max(1, n * DUMP_MAX_BYTES // total), replace=False))
+            a = np.take(a, keep, axis=ax)
+        np.save(os.path.join(path, f"{name}.npy"), a)
+        shapes[name] = list(a.shape)
+    return shapes
+
+
 def cpu_baseline(n_hyp=16, iters=5, reps=3):
     """BASELINE configs[0] (16 hypotheses, one frame, 5 refine iterations + 1 score pass, no GPU) on the oracle -- C
     rasteriser/warp with OpenMP + torch-CPU fp32 networks -- repeated `reps` times; checker, not product"""
@@ -423,7 +444,13 @@ def main():
                     "mode (BASELINE configs[4] at 64 hypotheses per frame, and the reference's track_one: 1 hypothesis x 2 iterations)")
     ap.add_argument("--track-frames", type=int, default=1000)
     ap.add_argument("--no-kernel-table", action="store_true", help="skip the second (instrumented) pass")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step returned as DIR/<name>.npy (float32): "
+                    "poses (N,4,4) and scores (N,) in hypothesis order, records (ranks,N,17) = [score | pose] as the step returns "
+                    "them; every input is seeded, so the same arguments give the same inputs and two builds can be compared "
+                    "output for output")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         _respawn(args)
@@ -477,17 +504,18 @@ def main():
     from foundationpose_amd.dist import gather_object_records, register_hypothesis_parallel
 
     def step():
+        """-> (records, poses, scores): the step's result and the predictors' outputs it was made from (for --dump-outputs)"""
         if hyp_mode:
             p, s, _ = register_hypothesis_parallel(refiner, scorer, rgb_t, depth_t, sc["K"], poses0, xyz_t, mesh=sc["mesh"],
                                                    mesh_tensors=sc["gm"], mesh_diameter=sc["diameter"], iteration=R,
                                                    shared_translation=args.shared_crop)
-            return torch.cat([s.reshape(-1, 1), p.reshape(-1, 16)], dim=1)[None]   # replicated on every rank
+            return torch.cat([s.reshape(-1, 1), p.reshape(-1, 16)], dim=1)[None], p, s   # replicated on every rank
         p, _ = refiner.predict(rgb_t, depth_t, sc["K"], poses0, xyz_t, mesh=sc["mesh"], mesh_tensors=sc["gm"],
                                mesh_diameter=sc["diameter"], iteration=R, shared_translation=args.shared_crop)
         s, _ = scorer.predict(rgb_t, depth_t, sc["K"], p, mesh=sc["mesh"], mesh_tensors=sc["gm"],
                               mesh_diameter=sc["diameter"])
         ids = s.argsort(descending=True)
-        return gather_object_records(s[ids], p[ids])  # ONE RCCL all-gather of [score|pose] per register()
+        return gather_object_records(s[ids], p[ids]), p, s  # ONE RCCL all-gather of [score|pose] per register() (SURVEY 8(e))
 
     def sync():
         if use_dist:
@@ -512,7 +540,7 @@ def main():
     with clock:
         t0 = time.perf_counter()
         for _ in range(args.steps):
-            rec = step()
+            rec, p_last, s_last = step()
         sync()
         dt = time.perf_counter() - t0
     marker()
@@ -521,6 +549,9 @@ def main():
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
     dt = float(tmax.item())
     assert torch.isfinite(rec).all()
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(args.dump_outputs, {"poses": (p_last, 0), "scores": (s_last, 0), "records": (rec, 1)})
     # not the headline: the same step the way estimater.register() issues it -- every hypothesis of the rotation grid starts at ONE
     # translation (estimater.py:132-133), so the observed crop of the first refine iteration is warped and stem-encoded once per
     # sub-batch (bit-identical poses; PoseRefinePredictor.predict(shared_translation=True)).  Reported next to the headline so that a
@@ -632,6 +663,8 @@ def main():
             "network_mfma": {"algorithmic_TFLOP_per_step": flops / 1e3, "achieved_TFLOPs": flops / 1e3 / (dt / args.steps),
                              "frac_of_mfma_peak": flops / 1e3 / (dt / args.steps) / (MFMA_PEAK_TFLOPS * world)},
         }
+        if dumped is not None:
+            out["dumped_outputs"] = {"dir": os.path.abspath(args.dump_outputs), "shapes": dumped}
         pw = out["clock"].get("power_W_mean")
         if pw and out["clock"].get("source_matches_torch_device_pci"):
             # the step is power-limited: energy is the number a faster schedule has to move, not only time

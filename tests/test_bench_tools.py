@@ -132,3 +132,31 @@ def test_bench_refuses_more_ranks_than_gpus():
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2"], capture_output=True, text=True, timeout=300,
                        env=dict(os.environ, WORLD_SIZE="4", RANK="0", LOCAL_RANK="0"))
     assert r.returncode != 0 and "--gpus 2 but WORLD_SIZE=4" in r.stderr
+
+
+def test_dump_outputs_writes_float32_and_keeps_a_fixed_sample_under_the_cap(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: one float32 .npy per array, whole when small; over the cap the same seeded rows of the hypothesis axis
+    of every array, the same from call to call, within the cap"""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    p = torch.arange(40 * 16, dtype=torch.float32).reshape(40, 4, 4)
+    s = torch.arange(40, dtype=torch.float16)
+    rec = torch.cat([s.float().reshape(-1, 1), p.reshape(-1, 16)], 1)[None]
+    arrays = {"poses": (p, 0), "scores": (s, 0), "records": (rec, 1)}
+    shapes = bench.dump_outputs(str(tmp_path / "whole"), arrays)
+    assert shapes == {"poses": [40, 4, 4], "scores": [40], "records": [1, 40, 17]}
+    for name, (t, _) in arrays.items():
+        a = np.load(tmp_path / "whole" / f"{name}.npy")
+        assert a.dtype == np.float32 and np.array_equal(a, t.float().numpy())
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 2000)          # the three arrays hold 5440 bytes
+    bench.dump_outputs(str(tmp_path / "a"), arrays)
+    bench.dump_outputs(str(tmp_path / "b"), arrays)
+    got = {n: np.load(tmp_path / "a" / f"{n}.npy") for n in arrays}
+    assert sum(a.nbytes for a in got.values()) <= 2000
+    rows = got["scores"].astype(np.int64)                        # scores[i] == i: the kept hypotheses
+    assert len(rows) > 0 and np.all(np.diff(rows) > 0)
+    assert np.array_equal(got["poses"], p.numpy()[rows]) and np.array_equal(got["records"], rec.numpy()[:, rows])
+    for n in arrays:
+        assert np.array_equal(got[n], np.load(tmp_path / "b" / f"{n}.npy"))

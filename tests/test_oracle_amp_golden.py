@@ -3,8 +3,15 @@ torch.autocast(fp16) -- tests/golden/nets_amp_golden.npz, minted by tests/golden
 container.  The first conv block must agree BIT FOR BIT (same cast points, and the 6x7x7 reduction is short enough
 that both sides round the same fp32 sums); deeper layers differ only by fp32 summation order, which flips an fp16
 rounding in ~0.3 % of the outputs of every convolution (measured: the reference's own CPU kernels against an fp64
-accumulation of the same fp16 operands do the same), so they are held to a relative RMS bound instead."""
+accumulation of the same fp16 operands do the same), so they are held to a relative RMS bound instead.
+
+The fp32 summation order is the CPU kernels' choice (ISA code path, blocking, thread partitioning): on an AMD EPYC host's
+default path (MKL's AVX2 GEMM) one score logit lands 4 fp16 ulps from the golden, 2 on the machine that minted it.  Every
+test therefore runs in a child process with ATen, oneDNN and MKL held to their AVX2 code paths on 8 threads (PINNED_CPU),
+where the bounds below hold on Intel and AMD hosts alike (at most 2 ulps on both)."""
 import os
+import subprocess
+import sys
 
 import numpy as np
 import pytest
@@ -14,6 +21,19 @@ from conftest import ROOT
 
 GOLD = os.path.join(ROOT, "tests", "golden", "nets_amp_golden.npz")
 STRIDE = 61
+# read by the libraries when they load, hence a child process
+PINNED_CPU = {"ATEN_CPU_CAPABILITY": "avx2", "ONEDNN_MAX_CPU_ISA": "AVX2", "MKL_ENABLE_INSTRUCTIONS": "AVX2", "OMP_NUM_THREADS": "8"}
+
+
+def _ran_pinned(request):
+    """False in the pinned child (the test body runs here); otherwise runs this test in a pinned child, asserts it passed, True"""
+    if all(os.environ.get(k) == v for k, v in PINNED_CPU.items()):
+        return False
+    cmd = [sys.executable] + (["-s"] if sys.flags.no_user_site else []) + ["-m", "pytest", "-q", "-p", "no:cacheprovider",
+                                                                            request.node.nodeid]
+    r = subprocess.run(cmd, cwd=ROOT, env=dict(os.environ, **PINNED_CPU), capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout[-6000:] + r.stderr[-2000:]
+    return True
 
 
 def _inputs(n, seed):
@@ -47,7 +67,9 @@ def amp():
 
 
 @pytest.mark.parametrize("use_bn", [True, False])
-def test_refine_amp_oracle_matches_reference_under_autocast(amp, use_bn):
+def test_refine_amp_oracle_matches_reference_under_autocast(amp, use_bn, request):
+    if _ran_pinned(request):
+        return
     from foundationpose_amd.weights import DEFAULT_REFINE_CFG, random_state_dict
     g = np.load(GOLD)
     cfg = dict(DEFAULT_REFINE_CFG, use_BN=use_bn)
@@ -77,7 +99,9 @@ def test_refine_amp_oracle_matches_reference_under_autocast(amp, use_bn):
 
 
 @pytest.mark.parametrize("use_bn", [True, False])
-def test_score_amp_oracle_matches_reference_under_autocast(amp, use_bn):
+def test_score_amp_oracle_matches_reference_under_autocast(amp, use_bn, request):
+    if _ran_pinned(request):
+        return
     from foundationpose_amd.weights import DEFAULT_SCORE_CFG, random_state_dict
     g = np.load(GOLD)
     cfg = dict(DEFAULT_SCORE_CFG, use_BN=use_bn)
@@ -97,11 +121,13 @@ def test_score_amp_oracle_matches_reference_under_autocast(amp, use_bn):
     assert np.all(np.abs(out - ref) <= 3 * _ulp16(ref)), (out, ref)
 
 
-def test_policy_deviations_are_at_the_summation_order_floor(amp):
+def test_policy_deviations_are_at_the_summation_order_floor(amp, request):
     """What the deployed HIP plan does differently from the autocast op sequence, measured on the oracle itself against
     the reference-under-autocast goldens: (a) the token mean commuted with the output Linear (engine.py), (b) flash-order
     attention in the scorer instead of the fp16-rounded score matrix of the need_weights=True branch.  Both stay at
     the floor that fp32 summation order alone produces (the `fused` oracle against the golden)."""
+    if _ran_pinned(request):
+        return
     import torch.nn.functional as F
     from foundationpose_amd.weights import DEFAULT_REFINE_CFG, DEFAULT_SCORE_CFG, random_state_dict
     g = np.load(GOLD)
