@@ -37,6 +37,48 @@ extern "C" int fp_mesh_create(const float* pos, const float* nrm, const int32_t*
 
 extern "C" void fp_mesh_destroy(fp_mesh* mesh) { free(mesh); }
 
+extern "C" int fp_mesh_set_create(const fp_mesh* const* meshes, int M, fp_mesh_set** out) {
+  FP_REQUIRE(out != nullptr, "fp_mesh_set_create: out is NULL");
+  *out = nullptr;
+  FP_REQUIRE(M >= 1, "fp_mesh_set_create: empty set (M=%d)", M);
+  FP_REQUIRE(meshes != nullptr, "fp_mesh_set_create: meshes is NULL");
+  int maxV = 0, maxT = 0;
+  for (int i = 0; i < M; ++i) {
+    FP_REQUIRE(meshes[i] != nullptr, "fp_mesh_set_create: mesh %d is NULL", i);
+    const int V = meshes[i]->V, T = meshes[i]->T;
+    FP_REQUIRE(V > 0 && T > 0 && V <= FP_MESH_SET_MAX_ELEMS && T <= FP_MESH_SET_MAX_ELEMS,
+               "fp_mesh_set_create: mesh %d has V=%d, T=%d (each must be in 1..%d)", i, V, T, FP_MESH_SET_MAX_ELEMS);
+    maxV = V > maxV ? V : maxV;
+    maxT = T > maxT ? T : maxT;
+  }
+  fp_mesh* host = (fp_mesh*)malloc(sizeof(fp_mesh) * (size_t)M);
+  if (!host) {
+    fp_set_error("fp_mesh_set_create: out of host memory");
+    return FP_ERR_INVALID_ARG;
+  }
+  for (int i = 0; i < M; ++i) host[i] = *meshes[i];
+  fp_mesh* dev = nullptr;
+  hipError_t e = hipMalloc((void**)&dev, sizeof(fp_mesh) * (size_t)M);
+  if (e == hipSuccess) e = hipMemcpy(dev, host, sizeof(fp_mesh) * (size_t)M, hipMemcpyHostToDevice);
+  free(host);
+  if (e != hipSuccess) {
+    if (dev) (void)hipFree(dev);
+    fp_set_error("fp_mesh_set_create: device table of %d meshes: %s", M, hipGetErrorString(e));
+    return FP_ERR_LAUNCH;
+  }
+  fp_mesh_set* s = (fp_mesh_set*)calloc(1, sizeof(fp_mesh_set));
+  s->meshes = dev;
+  s->M = M; s->maxV = maxV; s->maxT = maxT;
+  *out = s;
+  return FP_OK;
+}
+
+extern "C" void fp_mesh_set_destroy(fp_mesh_set* set) {
+  if (!set) return;
+  if (set->meshes) (void)hipFree(set->meshes);
+  free(set);
+}
+
 // Greedy symmetry-aware pose clustering (reference: mycpp/src/app/pybind_api.cpp:24-68,
 // geodesic distance mycpp/src/Utils.cpp:21-26).  Init-time, O(N^2 S), host only.
 extern "C" int fp_cluster_poses(float angle_diff_deg, float dist_diff, const float* poses, int N,

@@ -36,6 +36,13 @@ struct fp_mesh {
   int V, T, Ht, Wt;
 };
 
+// fp_mesh_set_create: the descriptors of M meshes in one device table (copied once, at setup) + the largest V / T, which size
+// the grids and the workspace of fp_render_crops_multi
+struct fp_mesh_set {
+  fp_mesh* meshes;   // [dev M]
+  int M, maxV, maxT;
+};
+
 struct fp_k9 { float v[9]; };
 struct fp_k9d { double v[9]; };
 

@@ -91,10 +91,21 @@ __global__ void k_depth_to_xyz(const float* __restrict__ depth, fp_k9d K, float 
 }
 
 // ---------------------------------------------------------------- a5+a6 (Utils.py:577-621, float64 internals)
-__global__ void k_crop_windows(const float* __restrict__ poses, fp_k9d K, double radius, int out_w, int out_h,
+// per-object diameters (the *_multi entry points): diam[obj[n]] (obj NULL: diam[0]); an index outside 0..M-1 reads as NaN
+__device__ __forceinline__ double diameter_of(const double* __restrict__ diam, const int32_t* __restrict__ obj, int M, int n) {
+  const int o = obj ? obj[n] : 0;
+  return (unsigned)o < (unsigned)M ? diam[o] : __builtin_nan("");
+}
+
+// MULTI: the radius of hypothesis n is diam[obj[n]] * crop_ratio / 2, the expression fp_crop_windows evaluates on the host (f64,
+// no contraction: the same bits); otherwise `radius`
+template <bool MULTI>
+__global__ void k_crop_windows(const float* __restrict__ poses, fp_k9d K, double radius1, const double* __restrict__ diam,
+                               const int32_t* __restrict__ obj, int M, double crop_ratio, int out_w, int out_h,
                                int N, float* __restrict__ tfs, float* __restrict__ bbox) {
   const int n = blockIdx.x * blockDim.x + threadIdx.x;
   if (n >= N) return;
+  const double radius = MULTI ? diameter_of(diam, obj, M, n) * crop_ratio / 2.0 : radius1;
   const float* P = poses + (size_t)n * 16;
   const double tx = (double)P[3], ty = (double)P[7], tz = (double)P[11];
   double u0 = 0.0, v0 = 0.0, rad = 0.0;
@@ -133,13 +144,17 @@ __global__ void k_crop_windows(const float* __restrict__ poses, fp_k9d K, double
 // ---------------------------------------------------------------- a13 (predict_pose_refine.py:195-234)
 struct fp_f3 { float v[3]; };
 
+// MULTI: the diameter of hypothesis n is diam[obj[n]] rounded to float (as the scalar entry point's caller rounds it)
+template <bool MULTI>
 __global__ void k_pose_update(const float* __restrict__ trans, const float* __restrict__ rot,
                               const float* __restrict__ poses_in, int rot_rep, int normalize_xyz, fp_f3 tn,
-                              float rot_normalizer, float mesh_diameter, int N, float* __restrict__ poses_out,
+                              float rot_normalizer, float mesh_diameter1, const double* __restrict__ diam,
+                              const int32_t* __restrict__ obj, int M, int N, float* __restrict__ poses_out,
                               float* __restrict__ trans_delta_out, float* __restrict__ rot_delta_out, int trans_rep, fp_k9 K,
                               const float* __restrict__ tf_to_crops, float input_w) {
   const int n = blockIdx.x * blockDim.x + threadIdx.x;
   if (n >= N) return;
+  const float mesh_diameter = MULTI ? (float)diameter_of(diam, obj, M, n) : mesh_diameter1;
   float dt[3];
   if (trans_rep == FP_TRANS_DEEPIM) {
     // predict_pose_refine.py:201-215: (trans.x, trans.y) = shift of the projected object centre in crop pixels / crop
@@ -268,9 +283,47 @@ extern "C" int fp_crop_windows(const float* poses, const double* K, double mesh_
   fp_k9d Kd;
   for (int i = 0; i < 9; ++i) Kd.v[i] = K[i];
   const double radius = mesh_diameter * crop_ratio / 2.0;
-  hipLaunchKernelGGL(k_crop_windows, dim3(fp_cdiv(N, 64)), dim3(64), 0, (hipStream_t)stream, poses, Kd, radius,
-                     out_w, out_h, N, tf_to_crops, bbox2d);
+  hipLaunchKernelGGL(k_crop_windows<false>, dim3(fp_cdiv(N, 64)), dim3(64), 0, (hipStream_t)stream, poses, Kd, radius,
+                     nullptr, nullptr, 0, 0.0, out_w, out_h, N, tf_to_crops, bbox2d);
   FP_CHECK_LAUNCH("fp_crop_windows");
+  return FP_OK;
+}
+
+extern "C" int fp_crop_windows_multi(const float* poses, const double* K, const double* diameters, const int32_t* obj, int M,
+                                     double crop_ratio, int out_w, int out_h, int N, float* tf_to_crops, float* bbox2d,
+                                     void* stream) {
+  FP_REQUIRE(N >= 0, "fp_crop_windows_multi: N < 0");
+  FP_REQUIRE(M >= 1 && diameters, "fp_crop_windows_multi: need the diameters of M >= 1 objects (M=%d)", M);
+  FP_REQUIRE(obj || M == 1, "fp_crop_windows_multi: obj is NULL but there are %d objects", M);
+  if (N == 0) return FP_OK;
+  FP_REQUIRE(poses && K && tf_to_crops && bbox2d && out_w > 1 && out_h > 1, "fp_crop_windows_multi: bad arguments");
+  fp_k9d Kd;
+  for (int i = 0; i < 9; ++i) Kd.v[i] = K[i];
+  hipLaunchKernelGGL(k_crop_windows<true>, dim3(fp_cdiv(N, 64)), dim3(64), 0, (hipStream_t)stream, poses, Kd, 0.0, diameters,
+                     obj, M, crop_ratio, out_w, out_h, N, tf_to_crops, bbox2d);
+  FP_CHECK_LAUNCH("fp_crop_windows_multi");
+  return FP_OK;
+}
+
+template <bool MULTI>
+static int pose_update_launch(const char* name, const float* trans, const float* rot, const float* poses_in, int rot_rep,
+                              int normalize_xyz, const float* trans_normalizer, float rot_normalizer, float mesh_diameter,
+                              const double* diam, const int32_t* obj, int M, int N, float* poses_out, float* trans_delta_out,
+                              float* rot_delta_out, int trans_rep, const float* K9, const float* tf_to_crops, float input_w,
+                              void* stream) {
+  FP_REQUIRE(trans && rot && poses_in && poses_out, "%s: NULL tensor", name);
+  FP_REQUIRE(rot_rep == FP_ROT_AXIS_ANGLE || rot_rep == FP_ROT_6D, "%s: unknown rot_rep %d", name, rot_rep);
+  FP_REQUIRE(trans_rep == FP_TRANS_TRACKNET || trans_rep == FP_TRANS_DEEPIM || trans_rep == FP_TRANS_RAW, "%s: unknown trans_rep %d", name, trans_rep);
+  FP_REQUIRE(trans_rep != FP_TRANS_DEEPIM || (K9 && tf_to_crops && input_w > 0.f),
+             "%s: trans_rep deepim needs K, tf_to_crops and the crop width", name);
+  fp_k9 Kk = {{1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 1.f}};
+  if (K9) for (int i = 0; i < 9; ++i) Kk.v[i] = K9[i];
+  fp_f3 tn = {{1.f, 1.f, 1.f}};
+  if (trans_normalizer) { tn.v[0] = trans_normalizer[0]; tn.v[1] = trans_normalizer[1]; tn.v[2] = trans_normalizer[2]; }
+  hipLaunchKernelGGL(k_pose_update<MULTI>, dim3(fp_cdiv(N, 64)), dim3(64), 0, (hipStream_t)stream, trans, rot, poses_in,
+                     rot_rep, normalize_xyz, tn, rot_normalizer, mesh_diameter, diam, obj, M, N, poses_out, trans_delta_out,
+                     rot_delta_out, trans_rep, Kk, tf_to_crops, input_w);
+  FP_CHECK_LAUNCH(name);
   return FP_OK;
 }
 
@@ -280,18 +333,21 @@ extern "C" int fp_pose_update(const float* trans, const float* rot, const float*
                               int trans_rep, const float* K9, const float* tf_to_crops, float input_w, void* stream) {
   FP_REQUIRE(N >= 0, "fp_pose_update: N < 0");
   if (N == 0) return FP_OK;
-  FP_REQUIRE(trans && rot && poses_in && poses_out, "fp_pose_update: NULL tensor");
-  FP_REQUIRE(rot_rep == FP_ROT_AXIS_ANGLE || rot_rep == FP_ROT_6D, "fp_pose_update: unknown rot_rep %d", rot_rep);
-  FP_REQUIRE(trans_rep == FP_TRANS_TRACKNET || trans_rep == FP_TRANS_DEEPIM || trans_rep == FP_TRANS_RAW, "fp_pose_update: unknown trans_rep %d", trans_rep);
-  FP_REQUIRE(trans_rep != FP_TRANS_DEEPIM || (K9 && tf_to_crops && input_w > 0.f),
-             "fp_pose_update: trans_rep deepim needs K, tf_to_crops and the crop width");
-  fp_k9 Kk = {{1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 1.f}};
-  if (K9) for (int i = 0; i < 9; ++i) Kk.v[i] = K9[i];
-  fp_f3 tn = {{1.f, 1.f, 1.f}};
-  if (trans_normalizer) { tn.v[0] = trans_normalizer[0]; tn.v[1] = trans_normalizer[1]; tn.v[2] = trans_normalizer[2]; }
-  hipLaunchKernelGGL(k_pose_update, dim3(fp_cdiv(N, 64)), dim3(64), 0, (hipStream_t)stream, trans, rot, poses_in,
-                     rot_rep, normalize_xyz, tn, rot_normalizer, mesh_diameter, N, poses_out, trans_delta_out, rot_delta_out,
-                     trans_rep, Kk, tf_to_crops, input_w);
-  FP_CHECK_LAUNCH("fp_pose_update");
-  return FP_OK;
+  return pose_update_launch<false>("fp_pose_update", trans, rot, poses_in, rot_rep, normalize_xyz, trans_normalizer,
+                                   rot_normalizer, mesh_diameter, nullptr, nullptr, 0, N, poses_out, trans_delta_out,
+                                   rot_delta_out, trans_rep, K9, tf_to_crops, input_w, stream);
+}
+
+extern "C" int fp_pose_update_multi(const float* trans, const float* rot, const float* poses_in, int rot_rep,
+                                    int normalize_xyz, const float* trans_normalizer, float rot_normalizer,
+                                    const double* diameters, const int32_t* obj, int M, int N, float* poses_out,
+                                    float* trans_delta_out, float* rot_delta_out, int trans_rep, const float* K9,
+                                    const float* tf_to_crops, float input_w, void* stream) {
+  FP_REQUIRE(N >= 0, "fp_pose_update_multi: N < 0");
+  FP_REQUIRE(M >= 1 && diameters, "fp_pose_update_multi: need the diameters of M >= 1 objects (M=%d)", M);
+  FP_REQUIRE(obj || M == 1, "fp_pose_update_multi: obj is NULL but there are %d objects", M);
+  if (N == 0) return FP_OK;
+  return pose_update_launch<true>("fp_pose_update_multi", trans, rot, poses_in, rot_rep, normalize_xyz, trans_normalizer,
+                                  rot_normalizer, 0.f, diameters, obj, M, N, poses_out, trans_delta_out, rot_delta_out,
+                                  trans_rep, K9, tf_to_crops, input_w, stream);
 }

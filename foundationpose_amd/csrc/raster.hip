@@ -223,14 +223,55 @@ struct RenderWs {
   int* counts;             // [N][strips]
   unsigned short* lists16; // [N][strips][T]   (T <= 65535)
   int* lists32;            // same with 32-bit ids for larger meshes
+  int vstride, tstride;    // mesh set: the V / T of a hypothesis' rows above = the set's largest (one mesh: its own V / T)
 };
 
-__global__ __launch_bounds__(256) void k_vertex(fp_mesh m, const float* __restrict__ poses,
+// Where a kernel finds the mesh of hypothesis n.  MULTI = false (fp_render_crops): the one mesh, passed by value; the table is
+// unused and the instantiation is the single-mesh kernel.  MULTI = true (fp_render_crops_multi): entry obj[n] of the set's device
+// table (obj NULL: entry 0).  n = blockIdx.y, so the address is wave-uniform and the 72-byte descriptor comes in with scalar loads,
+// once per workgroup.  An index outside 0..M-1 reads as an empty mesh (nothing drawn) with a NaN diameter.
+struct MeshTable {
+  const fp_mesh* meshes;   // [dev M]
+  const int32_t* obj;      // [dev N] | NULL
+  const double* diam;      // [dev M] | NULL: diameters for FP_FLAG_NORMALIZE_XYZ
+  int M;
+};
+
+__device__ __forceinline__ int obj_of(const MeshTable& tab, int n) {
+  const int o = tab.obj ? tab.obj[n] : 0;
+  return (unsigned)o < (unsigned)tab.M ? o : -1;
+}
+
+template <bool MULTI>
+__device__ __forceinline__ fp_mesh mesh_of(const fp_mesh& one, const MeshTable& tab, int n) {
+  if (!MULTI) return one;
+  const int o = obj_of(tab, n);
+  if (o < 0) {
+    fp_mesh e = {};
+    return e;
+  }
+  return tab.meshes[o];
+}
+
+// 1 / (d / 2) of hypothesis n: the expression fp_render_crops evaluates on the host for its one mesh (IEEE division, no
+// contraction: the same bits), d rounded to float as the scalar entry point's caller rounds it
+template <bool MULTI>
+__device__ __forceinline__ float inv_radius_of(float one, const MeshTable& tab, int n) {
+  if (!MULTI) return one;
+  const int o = obj_of(tab, n);
+  const float d = (o >= 0 && tab.diam) ? (float)tab.diam[o] : __builtin_nanf("");
+  return 1.0f / (d * 0.5f);
+}
+
+template <bool MULTI>
+__global__ __launch_bounds__(256) void k_vertex(fp_mesh m1, MeshTable tab, const float* __restrict__ poses,
                                                 const float* __restrict__ bbox2d, fp_k9 K, int H, int W, int oh, int ow,
                                                 int nstrips, RenderWs ws) {
   const int n = blockIdx.y;
   const int v = blockIdx.x * blockDim.x + threadIdx.x;
   if (blockIdx.x == 0 && threadIdx.x < nstrips) ws.counts[n * nstrips + threadIdx.x] = 0;
+  const fp_mesh m = mesh_of<MULTI>(m1, tab, n);
+  const int vstride = MULTI ? ws.vstride : m.V;
   if (v >= m.V) return;
   const HypConst h = load_hyp(poses, bbox2d, K, n, H, W, oh, ow);
   const float vx = m.pos[v * 3], vy = m.pos[v * 3 + 1], vz = m.pos[v * 3 + 2];
@@ -243,17 +284,21 @@ __global__ __launch_bounds__(256) void k_vertex(fp_mesh m, const float* __restri
   const float n2 = fmaf(h.P[10], vn[2], fmaf(h.P[9], vn[1], h.P[8] * vn[0]));
   const float len = sqrtf(fmaf(n2, n2, fmaf(n1, n1, n0 * n0)));
   a.dk = clamp01((-n2) / fmaxf(len, 1e-12f));
-  const size_t o = (size_t)n * m.V + v;
+  const size_t o = (size_t)n * vstride + v;
   ws.va[o] = a;
   ws.vr[o] = project_vertex(h, vx, vy, vz);
 }
 
-__global__ __launch_bounds__(256) void k_bin(fp_mesh m, int oh, int ow, int nstrips, RenderWs ws) {
+template <bool MULTI>
+__global__ __launch_bounds__(256) void k_bin(fp_mesh m1, MeshTable tab, int oh, int ow, int nstrips, RenderWs ws) {
   const int n = blockIdx.y;
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  const fp_mesh m = mesh_of<MULTI>(m1, tab, n);
+  const int vstride = MULTI ? ws.vstride : m.V, tstride = MULTI ? ws.tstride : m.T;
+  if (MULTI && (int)(blockIdx.x * blockDim.x) >= m.T) return;   // grid sized for the set's largest mesh; uniform per workgroup
   int s0 = 1, s1 = 0;   // empty range
   if (t < m.T) {
-    const VtxRec* vr = ws.vr + (size_t)n * m.V;
+    const VtxRec* vr = ws.vr + (size_t)n * vstride;
     const VtxRec r0 = vr[m.faces[t * 3]], r1 = vr[m.faces[t * 3 + 1]], r2 = vr[m.faces[t * 3 + 2]];
     TriSetup tr;
     if (tri_setup(r0, r1, r2, tr)) {
@@ -282,19 +327,22 @@ __global__ __launch_bounds__(256) void k_bin(fp_mesh m, int oh, int ow, int nstr
     const int base = __shfl(mybase, s, 64);
     if (s >= s0 && s <= s1) {
       const int pos = base + __popcll(mask & ((1ull << lane) - 1ull));
-      const size_t li = ((size_t)n * nstrips + s) * m.T + pos;
+      const size_t li = ((size_t)n * nstrips + s) * tstride + pos;
       if (ws.lists16) ws.lists16[li] = (unsigned short)t;
       else ws.lists32[li] = t;
     }
   }
 }
 
+template <bool MULTI>
 __global__ __launch_bounds__(FP_RASTER_THREADS) void k_raster(
-    fp_mesh m, const float* __restrict__ poses, const float* __restrict__ bbox2d, fp_k9 K, int H, int W, int oh,
-    int ow, int nstrips, float w_ambient, float w_diffuse, float inv_r, float xyz_thr, int flags, RenderOut out,
+    fp_mesh m1, MeshTable tab, const float* __restrict__ poses, const float* __restrict__ bbox2d, fp_k9 K, int H, int W, int oh,
+    int ow, int nstrips, float w_ambient, float w_diffuse, float inv_r1, float xyz_thr, int flags, RenderOut out,
     RenderWs ws) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int n = blockIdx.y, strip = blockIdx.x;
+  const fp_mesh m = mesh_of<MULTI>(m1, tab, n);
+  const int vstride = MULTI ? ws.vstride : m.V, tstride = MULTI ? ws.tstride : m.T;
   const int row0 = strip * FP_STRIP_ROWS;
   const int rows = min(FP_STRIP_ROWS, oh - row0);
   const int npix = rows * ow;
@@ -303,8 +351,8 @@ __global__ __launch_bounds__(FP_RASTER_THREADS) void k_raster(
   BigTri* big = reinterpret_cast<BigTri*>(nbig + 4);
   const int tid = threadIdx.x;
   if (tid == 0) *nbig = 0;
-  const VtxRec* vr = ws.vr + (size_t)n * m.V;
-  const VtxAttr* va = ws.va + (size_t)n * m.V;
+  const VtxRec* vr = ws.vr + (size_t)n * vstride;
+  const VtxAttr* va = ws.va + (size_t)n * vstride;
 
   for (int p = tid; p < npix; p += FP_RASTER_THREADS) zb[p] = FP_KEY_EMPTY;
   __syncthreads();
@@ -313,7 +361,7 @@ __global__ __launch_bounds__(FP_RASTER_THREADS) void k_raster(
   // box exceeds FP_BIG_CELLS pixels (the fan triangles of a cap span 50 x 16 of them) would stall its whole wave in
   // the per-lane pixel loop, so it is queued and rasterised afterwards by all lanes together (pixel-parallel).
   const int cnt = FP_PROF_FLAG(flags, 0x20000) ? 0 : ws.counts[n * nstrips + strip];   // 0x20000: profiling aid, skip phase 1
-  const size_t lbase = ((size_t)n * nstrips + strip) * m.T;
+  const size_t lbase = ((size_t)n * nstrips + strip) * tstride;
   // edge functions are affine in the pixel index: w_k(i+1, j) = w_k(i, j) + 16*dwx_k, so a row costs three integer adds
   // per cell after one evaluation at its first cell (`first`/`step` stride the cells of a row-major walk over lanes)
   auto raster_cells = [&](const TriSetup& tr, float iw0, float iw1, float iw2, int t, int i0, int i1, int j0, int j1,
@@ -406,6 +454,7 @@ __global__ __launch_bounds__(FP_RASTER_THREADS) void k_raster(
 
   // ---- phase 2: resolve + shade + write
   const HypConst h = load_hyp(poses, bbox2d, K, n, H, W, oh, ow);
+  const float inv_r = inv_radius_of<MULTI>(inv_r1, tab, n);
   const size_t plane = (size_t)oh * ow;
   const float t0 = h.P[3], t1 = h.P[7], t2 = h.P[11];
   const bool normalize = (flags & FP_FLAG_NORMALIZE_XYZ) != 0;
@@ -540,21 +589,24 @@ extern "C" size_t fp_workspace_bytes(int N, int V, int T, int oh, int ow) {
   return ws_layout(N, V, T, oh).total;
 }
 
-extern "C" int fp_render_crops(const fp_mesh* mesh, const float* poses, const float* bbox2d, const float* K9, int H,
-                               int W, int N, int oh, int ow, float w_ambient, float w_diffuse, float mesh_diameter,
-                               float xyz_thr, int flags, void* A, float* color, float* depth, float* xyz,
-                               float* normal, uint32_t* zbuf, int32_t* tri_id, void* workspace,
-                               size_t workspace_bytes, void* stream) {
-  FP_REQUIRE(N >= 0, "fp_render_crops: N < 0");
-  FP_REQUIRE((flags & ~FP_RENDER_FLAG_MASK) == 0, "fp_render_crops: unknown flag bits 0x%x", flags & ~FP_RENDER_FLAG_MASK);
-  if (N == 0) return FP_OK;
-  FP_REQUIRE(mesh && poses && K9, "fp_render_crops: NULL mesh/poses/K");
-  FP_REQUIRE(oh > 0 && ow > 0 && oh <= 1024 && ow <= 1024, "fp_render_crops: output size %dx%d unsupported (max 1024)", oh, ow);
-  FP_REQUIRE(bbox2d || (oh == H && ow == W), "fp_render_crops: full-frame render needs oh==H and ow==W");
-  FP_REQUIRE(N <= 65535, "fp_render_crops: N=%d exceeds the grid limit; chunk the batch", N);
-  const WsLayout L = ws_layout(N, mesh->V, mesh->T, oh);
+extern "C" size_t fp_mesh_set_workspace_bytes(const fp_mesh_set* set, int N, int oh, int ow) {
+  if (!set) return 0;
+  return fp_workspace_bytes(N, set->maxV, set->maxT, oh, ow);
+}
+
+// the three launches of one render, shared by fp_render_crops (MULTI = false: `one`, maxV = V, maxT = T) and
+// fp_render_crops_multi (MULTI = true: the set's table, grids sized by its largest mesh)
+template <bool MULTI>
+static int render_launch(const char* name, const fp_mesh& one, const MeshTable& tab, int maxV, int maxT, const float* poses,
+                         const float* bbox2d, const float* K9, int H, int W, int N, int oh, int ow, float w_ambient,
+                         float w_diffuse, float inv_r, float xyz_thr, int flags, const RenderOut& out, void* workspace,
+                         size_t workspace_bytes, hipStream_t st) {
+  FP_REQUIRE(oh > 0 && ow > 0 && oh <= 1024 && ow <= 1024, "%s: output size %dx%d unsupported (max 1024)", name, oh, ow);
+  FP_REQUIRE(bbox2d || (oh == H && ow == W), "%s: full-frame render needs oh==H and ow==W", name);
+  FP_REQUIRE(N <= 65535, "%s: N=%d exceeds the grid limit; chunk the batch", name, N);
+  const WsLayout L = ws_layout(N, maxV, maxT, oh);
   if (!workspace || workspace_bytes < L.total) {
-    fp_set_error("fp_render_crops: workspace too small (%zu < %zu bytes, see fp_workspace_bytes)", workspace_bytes, L.total);
+    fp_set_error("%s: workspace too small (%zu < %zu bytes, see fp_workspace_bytes)", name, workspace_bytes, L.total);
     return FP_ERR_WORKSPACE;
   }
   fp_k9 K;
@@ -564,18 +616,51 @@ extern "C" int fp_render_crops(const fp_mesh* mesh, const float* poses, const fl
   ws.vr = (VtxRec*)(w8 + L.vr); ws.va = (VtxAttr*)(w8 + L.va); ws.counts = (int*)(w8 + L.counts);
   ws.lists16 = L.ids16 ? (unsigned short*)(w8 + L.lists) : nullptr;
   ws.lists32 = L.ids16 ? nullptr : (int*)(w8 + L.lists);
-  const float inv_r = 1.0f / (mesh_diameter * 0.5f);
-  RenderOut out = {A, color, depth, xyz, normal, zbuf, tri_id};
-  hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(k_vertex, dim3(fp_cdiv(mesh->V, 256), N), dim3(256), 0, st, *mesh, poses, bbox2d, K, H, W, oh, ow,
+  ws.vstride = maxV; ws.tstride = maxT;
+  hipLaunchKernelGGL(k_vertex<MULTI>, dim3(fp_cdiv(maxV, 256), N), dim3(256), 0, st, one, tab, poses, bbox2d, K, H, W, oh, ow,
                      L.nstrips, ws);
-  FP_CHECK_LAUNCH("fp_render_crops(vertex)");
-  hipLaunchKernelGGL(k_bin, dim3(fp_cdiv(mesh->T, 256), N), dim3(256), 0, st, *mesh, oh, ow, L.nstrips, ws);
-  FP_CHECK_LAUNCH("fp_render_crops(bin)");
+  FP_CHECK_LAUNCH(MULTI ? "fp_render_crops_multi(vertex)" : "fp_render_crops(vertex)");
+  hipLaunchKernelGGL(k_bin<MULTI>, dim3(fp_cdiv(maxT, 256), N), dim3(256), 0, st, one, tab, oh, ow, L.nstrips, ws);
+  FP_CHECK_LAUNCH(MULTI ? "fp_render_crops_multi(bin)" : "fp_render_crops(bin)");
   const size_t lds = (size_t)FP_STRIP_ROWS * ow * sizeof(unsigned long long) + 16 + FP_BIG_MAX * sizeof(BigTri);
-  FP_SET_MAX_LDS(k_raster, 160 * 1024);
-  hipLaunchKernelGGL(k_raster, dim3(L.nstrips, N), dim3(FP_RASTER_THREADS), lds, st, *mesh, poses, bbox2d, K, H, W, oh, ow,
-                     L.nstrips, w_ambient, w_diffuse, inv_r, xyz_thr, flags, out, ws);
-  FP_CHECK_LAUNCH("fp_render_crops");
+  FP_SET_MAX_LDS(k_raster<MULTI>, 160 * 1024);
+  hipLaunchKernelGGL(k_raster<MULTI>, dim3(L.nstrips, N), dim3(FP_RASTER_THREADS), lds, st, one, tab, poses, bbox2d, K, H, W, oh,
+                     ow, L.nstrips, w_ambient, w_diffuse, inv_r, xyz_thr, flags, out, ws);
+  FP_CHECK_LAUNCH(name);
   return FP_OK;
+}
+
+extern "C" int fp_render_crops(const fp_mesh* mesh, const float* poses, const float* bbox2d, const float* K9, int H,
+                               int W, int N, int oh, int ow, float w_ambient, float w_diffuse, float mesh_diameter,
+                               float xyz_thr, int flags, void* A, float* color, float* depth, float* xyz,
+                               float* normal, uint32_t* zbuf, int32_t* tri_id, void* workspace,
+                               size_t workspace_bytes, void* stream) {
+  FP_REQUIRE(N >= 0, "fp_render_crops: N < 0");
+  FP_REQUIRE((flags & ~FP_RENDER_FLAG_MASK) == 0, "fp_render_crops: unknown flag bits 0x%x", flags & ~FP_RENDER_FLAG_MASK);
+  if (N == 0) return FP_OK;
+  FP_REQUIRE(mesh && poses && K9, "fp_render_crops: NULL mesh/poses/K");
+  const float inv_r = 1.0f / (mesh_diameter * 0.5f);
+  const MeshTable none = {nullptr, nullptr, nullptr, 0};
+  const RenderOut out = {A, color, depth, xyz, normal, zbuf, tri_id};
+  return render_launch<false>("fp_render_crops", *mesh, none, mesh->V, mesh->T, poses, bbox2d, K9, H, W, N, oh, ow, w_ambient,
+                              w_diffuse, inv_r, xyz_thr, flags, out, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+extern "C" int fp_render_crops_multi(const fp_mesh_set* set, const int32_t* obj, const double* diameters, const float* poses,
+                                     const float* bbox2d, const float* K9, int H, int W, int N, int oh, int ow, float w_ambient,
+                                     float w_diffuse, float xyz_thr, int flags, void* A, float* color, float* depth, float* xyz,
+                                     float* normal, uint32_t* zbuf, int32_t* tri_id, void* workspace, size_t workspace_bytes,
+                                     void* stream) {
+  FP_REQUIRE(N >= 0, "fp_render_crops_multi: N < 0");
+  FP_REQUIRE((flags & ~FP_RENDER_FLAG_MASK) == 0, "fp_render_crops_multi: unknown flag bits 0x%x", flags & ~FP_RENDER_FLAG_MASK);
+  FP_REQUIRE(set, "fp_render_crops_multi: NULL mesh set");
+  FP_REQUIRE(obj || set->M == 1, "fp_render_crops_multi: obj is NULL but the set has %d meshes", set->M);
+  FP_REQUIRE(diameters || !(flags & FP_FLAG_NORMALIZE_XYZ), "fp_render_crops_multi: FP_FLAG_NORMALIZE_XYZ needs the diameters");
+  if (N == 0) return FP_OK;
+  FP_REQUIRE(poses && K9, "fp_render_crops_multi: NULL poses/K");
+  const fp_mesh none = {};
+  const MeshTable tab = {set->meshes, obj, diameters, set->M};
+  const RenderOut out = {A, color, depth, xyz, normal, zbuf, tri_id};
+  return render_launch<true>("fp_render_crops_multi", none, tab, set->maxV, set->maxT, poses, bbox2d, K9, H, W, N, oh, ow,
+                             w_ambient, w_diffuse, 0.f, xyz_thr, flags, out, workspace, workspace_bytes, (hipStream_t)stream);
 }

@@ -103,12 +103,17 @@ __device__ __forceinline__ void warp_pixel(const float* __restrict__ rgb, const 
 // operation, the integer division a multiply-shift.
 struct WarpConst { float cW, cH; unsigned mul_ow, shr_ow; };
 
-template <int MODE>
+// Per-object diameters (fp_warp_crops_multi, MULTI = true): the same lane also computes 1 / (d / 2) of the hypothesis' object,
+// d = diam[obj[n]] rounded to float -- the host expression of fp_warp_crops (IEEE division, no contraction: the same bits).
+struct WarpObjects { const double* diam; const int32_t* obj; int M; };
+
+template <int MODE, bool MULTI>
 __global__ __launch_bounds__(256) void k_warp(const float* __restrict__ rgb, const float* __restrict__ xyz_map,
                                               const float* __restrict__ depthf, const float* __restrict__ tfs,
-                                              fp_k9 K, const float* __restrict__ poses, float inv_r, int flags,
-                                              int H, int W, int oh, int ow, void* __restrict__ Bout, WarpConst wc) {
-  __shared__ float inv_tf[4];
+                                              fp_k9 K, const float* __restrict__ poses, float inv_r1, int flags,
+                                              int H, int W, int oh, int ow, void* __restrict__ Bout, WarpConst wc,
+                                              WarpObjects objs) {
+  __shared__ float inv_tf[5];   // [4]: 1 / radius (MULTI)
   const int n = blockIdx.y;
   const float* tf = tfs + (size_t)n * 9;
   const float sx = tf[0], tx = tf[2], sy = tf[4], ty = tf[5];
@@ -117,8 +122,14 @@ __global__ __launch_bounds__(256) void k_warp(const float* __restrict__ rgb, con
     inv_tf[1] = 1.0f / sy;
     inv_tf[2] = (-tx) / sx;
     inv_tf[3] = (-ty) / sy;
+    if (MULTI) {
+      const int o = objs.obj ? objs.obj[n] : 0;
+      const float d = (unsigned)o < (unsigned)objs.M ? (float)objs.diam[o] : __builtin_nanf("");
+      inv_tf[4] = 1.0f / (d * 0.5f);
+    }
   }
   __syncthreads();
+  const float inv_r = MULTI ? inv_tf[4] : inv_r1;
   const int p = blockIdx.x * blockDim.x + threadIdx.x;
   const int npx = oh * ow;
   if (p >= npx) return;
@@ -142,20 +153,18 @@ __global__ __launch_bounds__(256) void k_warp(const float* __restrict__ rgb, con
   }
 }
 
-extern "C" int fp_warp_crops(const float* rgb, const float* xyz_map, const float* depth, const float* tf_to_crops,
-                             const float* K9, const float* poses, float mesh_diameter, int flags, int mode, int H,
-                             int W, int N, int oh, int ow, void* B, void* stream) {
-  FP_REQUIRE(N >= 0, "fp_warp_crops: N < 0");
-  if (N == 0) return FP_OK;
-  FP_REQUIRE(rgb && tf_to_crops && K9 && poses && B, "fp_warp_crops: NULL tensor");
-  FP_REQUIRE(H > 1 && W > 1 && oh > 1 && ow > 1, "fp_warp_crops: degenerate sizes");
-  FP_REQUIRE(N <= 65535, "fp_warp_crops: N=%d exceeds the grid limit; chunk the batch", N);
-  FP_REQUIRE(mode == FP_MODE_REFINE || mode == FP_MODE_SCORE, "fp_warp_crops: unknown mode %d", mode);
-  FP_REQUIRE(mode != FP_MODE_REFINE || xyz_map, "fp_warp_crops: REFINE mode needs xyz_map");
-  FP_REQUIRE(mode != FP_MODE_SCORE || depth, "fp_warp_crops: SCORE mode needs depth");
+template <bool MULTI>
+static int warp_launch(const char* name, const float* rgb, const float* xyz_map, const float* depth, const float* tf_to_crops,
+                       const float* K9, const float* poses, float inv_r, const WarpObjects& objs, int flags, int mode, int H,
+                       int W, int N, int oh, int ow, void* B, void* stream) {
+  FP_REQUIRE(rgb && tf_to_crops && K9 && poses && B, "%s: NULL tensor", name);
+  FP_REQUIRE(H > 1 && W > 1 && oh > 1 && ow > 1, "%s: degenerate sizes", name);
+  FP_REQUIRE(N <= 65535, "%s: N=%d exceeds the grid limit; chunk the batch", name, N);
+  FP_REQUIRE(mode == FP_MODE_REFINE || mode == FP_MODE_SCORE, "%s: unknown mode %d", name, mode);
+  FP_REQUIRE(mode != FP_MODE_REFINE || xyz_map, "%s: REFINE mode needs xyz_map", name);
+  FP_REQUIRE(mode != FP_MODE_SCORE || depth, "%s: SCORE mode needs depth", name);
   fp_k9 K;
   for (int i = 0; i < 9; ++i) K.v[i] = K9[i];
-  const float inv_r = 1.0f / (mesh_diameter * 0.5f);
   dim3 grid(fp_cdiv(oh * ow, 256), N), block(256);
   WarpConst wc;
   wc.cW = (float)W / (float)(W - 1);
@@ -171,11 +180,34 @@ extern "C" int fp_warp_crops(const float* rgb, const float* xyz_map, const float
     }
   }
   if (mode == FP_MODE_REFINE)
-    hipLaunchKernelGGL(k_warp<FP_MODE_REFINE>, grid, block, 0, (hipStream_t)stream, rgb, xyz_map, depth, tf_to_crops,
-                       K, poses, inv_r, flags, H, W, oh, ow, B, wc);
+    hipLaunchKernelGGL((k_warp<FP_MODE_REFINE, MULTI>), grid, block, 0, (hipStream_t)stream, rgb, xyz_map, depth, tf_to_crops,
+                       K, poses, inv_r, flags, H, W, oh, ow, B, wc, objs);
   else
-    hipLaunchKernelGGL(k_warp<FP_MODE_SCORE>, grid, block, 0, (hipStream_t)stream, rgb, xyz_map, depth, tf_to_crops,
-                       K, poses, inv_r, flags, H, W, oh, ow, B, wc);
-  FP_CHECK_LAUNCH("fp_warp_crops");
+    hipLaunchKernelGGL((k_warp<FP_MODE_SCORE, MULTI>), grid, block, 0, (hipStream_t)stream, rgb, xyz_map, depth, tf_to_crops,
+                       K, poses, inv_r, flags, H, W, oh, ow, B, wc, objs);
+  FP_CHECK_LAUNCH(name);
   return FP_OK;
+}
+
+extern "C" int fp_warp_crops(const float* rgb, const float* xyz_map, const float* depth, const float* tf_to_crops,
+                             const float* K9, const float* poses, float mesh_diameter, int flags, int mode, int H,
+                             int W, int N, int oh, int ow, void* B, void* stream) {
+  FP_REQUIRE(N >= 0, "fp_warp_crops: N < 0");
+  if (N == 0) return FP_OK;
+  const float inv_r = 1.0f / (mesh_diameter * 0.5f);
+  const WarpObjects none = {nullptr, nullptr, 0};
+  return warp_launch<false>("fp_warp_crops", rgb, xyz_map, depth, tf_to_crops, K9, poses, inv_r, none, flags, mode, H, W, N,
+                            oh, ow, B, stream);
+}
+
+extern "C" int fp_warp_crops_multi(const float* rgb, const float* xyz_map, const float* depth, const float* tf_to_crops,
+                                   const float* K9, const float* poses, const double* diameters, const int32_t* obj, int M,
+                                   int flags, int mode, int H, int W, int N, int oh, int ow, void* B, void* stream) {
+  FP_REQUIRE(N >= 0, "fp_warp_crops_multi: N < 0");
+  FP_REQUIRE(M >= 1 && diameters, "fp_warp_crops_multi: need the diameters of M >= 1 objects (M=%d)", M);
+  FP_REQUIRE(obj || M == 1, "fp_warp_crops_multi: obj is NULL but there are %d objects", M);
+  if (N == 0) return FP_OK;
+  const WarpObjects objs = {diameters, obj, M};
+  return warp_launch<true>("fp_warp_crops_multi", rgb, xyz_map, depth, tf_to_crops, K9, poses, 0.f, objs, flags, mode, H, W,
+                           N, oh, ow, B, stream);
 }

@@ -216,3 +216,42 @@ class FoundationPose:
         return (pose @ self.get_tf_to_centered_mesh()).data.cpu().numpy().reshape(4, 4)
 
     track = track_one  # the north-star calls it track(); the reference method is track_one
+
+
+def track_objects(estimators, rgb, depth, K, iteration=2):
+    """track_one for several objects in one frame: ONE batched refine loop over the objects' hypotheses (one each, from every
+    estimator's pose_last), replayed as captured hipGraphs (graphs.GraphedTracker over the objects' meshes) on one shared depth
+    ingest, instead of len(estimators) separate calls.  Per object the result is what its own track_one computes (the hypotheses of
+    a call never mix; each one draws its own mesh and uses its own diameter).  Every estimator must be registered and all must share
+    ONE refiner object (its network and configuration are the loop's).  The captured tracker is cached on that refiner under
+    (estimators, frame size, K, iteration), like track_one's.  -> [4x4 np.ndarray] per estimator, in its original mesh frame;
+    updates each pose_last.  register() stays per object."""
+    ests = list(estimators)
+    if not ests:
+        raise ValueError("track_objects: no estimators")
+    for i, e in enumerate(ests):
+        if e.pose_last is None:
+            raise RuntimeError(f"track_objects: estimator {i} is not registered (call register first)")
+    refiner = ests[0].refiner
+    if any(e.refiner is not refiner for e in ests):
+        raise ValueError("track_objects: the estimators must share one refiner object (FoundationPose(..., refiner=shared))")
+    if len({id(e) for e in ests}) != len(ests):
+        raise ValueError("track_objects: an estimator is listed twice")
+    dev = ests[0].device
+    hw = tuple(np.asarray(depth).shape[:2]) if not torch.is_tensor(depth) else tuple(depth.shape[:2])
+    key = (tuple((id(e), id(e.mesh_tensors)) for e in ests), hw, np.asarray(K, dtype=np.float64).tobytes(), int(iteration))
+    cached = getattr(refiner, "_objects_tracker", None)
+    if cached is None or cached[0] != key:
+        from .graphs import GraphedTracker
+        trk = GraphedTracker(refiner, [e.mesh_tensors for e in ests], [e.diameter for e in ests], K, hw[0], hw[1], n_hyp=1,
+                             iteration=iteration, device=dev).capture()
+        # the entry keeps the estimators and their mesh dicts alive, so the ids of its key cannot be reused while it is cached
+        cached = refiner._objects_tracker = (key, trk, ests, [e.mesh_tensors for e in ests])
+    trk = cached[1]
+    start = torch.stack([e.pose_last.reshape(4, 4).to(dev, torch.float32) for e in ests])
+    out = trk.step(rgb, depth, start).clone()
+    poses = []
+    for k, e in enumerate(ests):
+        e.pose_last = out[k:k + 1]
+        poses.append((out[k] @ e.get_tf_to_centered_mesh()).data.cpu().numpy().reshape(4, 4))
+    return poses

@@ -123,15 +123,35 @@ class GraphedTracker:
     The frame is captured as 1 + k LINEAR graphs: the depth pre-processing, and the whole refine loop of each of the k
     hypothesis sub-batches of the refiner (overlap.py).  A replay launches the first on the caller's stream and the k part
     graphs on k streams forked from / joined into it, so the overlap between sub-batches is ordinary stream semantics and
-    every graph stays a simple chain."""
+    every graph stays a simple chain.
+
+    Several objects per frame: mesh_tensors and mesh_diameter are lists (one entry per object) and every object has `n_hyp`
+    hypotheses, so a frame refines N = M x n_hyp poses in ONE batched loop -- rows [k n_hyp, (k+1) n_hyp) of poses_in / poses_out
+    are object k's -- on one shared depth ingest (ops.MeshSet, predict_pose_refine.ObjectIndex).  A list of one mesh is the same
+    loop for one object."""
 
     def __init__(self, refiner, mesh_tensors, mesh_diameter, K, H, W, n_hyp=1, iteration=2, device=None):
         self.refiner = refiner
-        self.handle = get_mesh_handle(mesh_tensors)
+        self.multi = isinstance(mesh_tensors, (list, tuple))
+        if self.multi:
+            from .predict_pose_refine import ObjectIndex
+            if len(mesh_tensors) < 1 or len(mesh_diameter) != len(mesh_tensors):
+                raise ValueError(f"GraphedTracker: {len(mesh_tensors)} meshes and {len(mesh_diameter)} diameters")
+            self.M = len(mesh_tensors)
+            self.handle = ops.MeshSet([get_mesh_handle(m) for m in mesh_tensors])
+        else:
+            self.M = 1
+            self.handle = get_mesh_handle(mesh_tensors)
         self.dev = torch.device(device) if device is not None else self.handle.device
         self.K = np.asarray(K, dtype=np.float64).copy()
-        self.H, self.W, self.N, self.R = int(H), int(W), int(n_hyp), int(iteration)
-        self.diameter = float(mesh_diameter)
+        self.H, self.W, self.N, self.R = int(H), int(W), int(n_hyp) * self.M, int(iteration)
+        self.n_hyp = int(n_hyp)
+        if self.multi:
+            self.diameter = ops.object_diameters(mesh_diameter, self.dev)
+            self.obj = ObjectIndex(np.repeat(np.arange(self.M), self.n_hyp), self.dev)
+        else:
+            self.diameter = float(mesh_diameter)
+            self.obj = None
         self.rgb = torch.zeros((H, W, 3), dtype=torch.float32, device=self.dev)
         self.depth = torch.zeros((H, W), dtype=torch.float32, device=self.dev)
         self.poses_in = torch.eye(4, device=self.dev).repeat(self.N, 1, 1).contiguous()
@@ -140,6 +160,9 @@ class GraphedTracker:
         # (batch, H, W, slot) in the plan (never dropped)
         oh, ow = int(refiner.cfg["input_resize"][0]), int(refiner.cfg["input_resize"][1])
         self.parts = refiner.sub.parts(self.N, self.dev)
+        if self.obj is not None:
+            from .predict_pose_refine import parts_for_pairs
+            self.parts = parts_for_pairs(self.parts, self.obj.pairs)
         self.workspace = [torch.empty(max(16, ops.workspace_bytes(b - a, self.handle.V, self.handle.T, oh, ow)),
                                       dtype=torch.uint8, device=self.dev) for a, b in self.parts]
         self.outs = refiner.alloc_outputs(self.N, self.dev) + (self.R,)
@@ -154,7 +177,7 @@ class GraphedTracker:
 
     def _part(self, h, xyz):
         self.refiner.refine_part(h, self.parts[h], self.rgb, xyz, self.poses_in, self.K, self.H, self.W, self.handle,
-                                 self.diameter, range(self.R), self.outs, self.workspace[h])
+                                 self.diameter, range(self.R), self.outs, self.workspace[h], obj=self.obj)
 
     def _body(self, xyz=None):
         """the frame without graphs: same launches, same streams (xyz given: the refine loop alone, on that map)"""

@@ -85,6 +85,63 @@ class MeshHandle:
             pass
 
 
+class MeshSet:
+    """Several objects' meshes for one call (fp_mesh_set): the descriptors of `handles` (MeshHandle) in one device table, built
+    once.  Where render_crops takes a MeshHandle it takes a MeshSet with a per-hypothesis object index `obj` (int32 device tensor,
+    values 0..M-1) and the per-object diameters (object_diameters).  V / T are the largest of the set: what sizes the grids and the
+    rasteriser scratch (workspace_bytes(N, set.V, set.T, ...))."""
+
+    def __init__(self, handles):
+        self.meshes = list(handles)           # the set points at their tensors: keep them alive
+        if not self.meshes:
+            raise _lib.FpAmdError("MeshSet: empty list of meshes")
+        devs = {h.device for h in self.meshes}
+        if len(devs) != 1:
+            raise _lib.FpAmdError(f"MeshSet: meshes on several devices {sorted(map(str, devs))}")
+        self.device = self.meshes[0].device
+        self.M = len(self.meshes)
+        self.V = max(h.V for h in self.meshes)
+        self.T = max(h.T for h in self.meshes)
+        arr = (C.c_void_p * self.M)(*[h.handle.value for h in self.meshes])
+        h = C.c_void_p()
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().fp_mesh_set_create(arr, self.M, C.byref(h)), "fp_mesh_set_create")
+        self.handle = h
+
+    def workspace_bytes(self, N, oh=160, ow=160):
+        return int(_lib.lib().fp_mesh_set_workspace_bytes(self.handle, int(N), int(oh), int(ow)))
+
+    def __del__(self):
+        try:
+            if getattr(self, "handle", None):
+                _lib.lib().fp_mesh_set_destroy(self.handle)
+                self.handle = None
+        except Exception:
+            pass
+
+
+def object_diameters(diameters, device):
+    """the per-object diameter table of the multi-object entry points: (M,) float64 on `device`, the values exactly as the scalar
+    entry points receive them (fp_crop_windows takes the double, the others round it to float on the device as ops does here)"""
+    return torch.tensor([float(d) for d in diameters], dtype=torch.float64, device=device)
+
+
+def _objects(mesh_diameter, obj, what):
+    """the multi-object form of an entry point: (diameter table, obj or None, M), or None for the scalar form"""
+    if not torch.is_tensor(mesh_diameter):
+        if obj is not None:
+            raise _lib.FpAmdError(f"{what}: an object index needs the per-object diameters (object_diameters), not a scalar")
+        return None
+    d = _dev(mesh_diameter, torch.float64, f"{what}: diameters")
+    if d.dim() != 1 or d.numel() < 1:
+        raise _lib.FpAmdError(f"{what}: diameters must be a (M,) float64 tensor")
+    M = int(d.numel())
+    o = _dev(obj, torch.int32, f"{what}: obj")
+    if o is None and M > 1:
+        raise _lib.FpAmdError(f"{what}: {M} objects need a per-hypothesis object index obj")
+    return d, o, M
+
+
 def erode_depth(depth, radius=2, depth_diff_thres=0.001, ratio_thres=0.8, zfar=100.0):
     d = _dev(depth, torch.float32, "depth")
     out = torch.empty_like(d)
@@ -113,16 +170,24 @@ def depth_to_xyz(depth, K, zfar=float("inf"), f64_internal=False):
     return out
 
 
-def crop_windows(poses, K, mesh_diameter, crop_ratio, out_size=(160, 160)):
-    """-> tf_to_crops (N,3,3) f32, bbox2d (N,4) f32.  out_size = (width, height)."""
+def crop_windows(poses, K, mesh_diameter, crop_ratio, out_size=(160, 160), obj=None):
+    """-> tf_to_crops (N,3,3) f32, bbox2d (N,4) f32.  out_size = (width, height).  Several objects: mesh_diameter = the (M,)
+    table of object_diameters, obj = the per-hypothesis object index (fp_crop_windows_multi)."""
     P = _dev(poses, torch.float32, "poses")
     N = int(P.shape[0])
     tf = torch.empty((N, 3, 3), dtype=torch.float32, device=P.device)
     bb = torch.empty((N, 4), dtype=torch.float32, device=P.device)
     Kd = _hostK64(K)
-    _lib.check(_lib.lib().fp_crop_windows(_ptr(P), Kd.ctypes.data_as(C.c_void_p), float(mesh_diameter),
-                                          float(crop_ratio), int(out_size[0]), int(out_size[1]), N, _ptr(tf), _ptr(bb),
-                                          _stream(P)), "fp_crop_windows")
+    objs = _objects(mesh_diameter, obj, "crop_windows")
+    if objs is None:
+        _lib.check(_lib.lib().fp_crop_windows(_ptr(P), Kd.ctypes.data_as(C.c_void_p), float(mesh_diameter),
+                                              float(crop_ratio), int(out_size[0]), int(out_size[1]), N, _ptr(tf), _ptr(bb),
+                                              _stream(P)), "fp_crop_windows")
+    else:
+        d, o, M = objs
+        _lib.check(_lib.lib().fp_crop_windows_multi(_ptr(P), Kd.ctypes.data_as(C.c_void_p), _ptr(d), _ptr(o), M, float(crop_ratio),
+                                                    int(out_size[0]), int(out_size[1]), N, _ptr(tf), _ptr(bb), _stream(P)),
+                   "fp_crop_windows_multi")
     return tf, bb
 
 
@@ -155,10 +220,18 @@ def _workspace(nbytes, device):
 
 def render_crops(mesh, poses, bbox2d, K, H, W, out_hw=(160, 160), mesh_diameter=1.0, xyz_thr=0.001,
                  normalize_xyz=True, out_f16=False, w_ambient=0.8, w_diffuse=0.5,
-                 want=("A",), A_out=None, workspace=None):
+                 want=("A",), A_out=None, workspace=None, obj=None):
     """Fused render of N hypotheses (see fp_render_crops).  Returns dict of requested outputs.  workspace: caller-owned
     uint8 scratch of at least workspace_bytes(...) bytes (a captured hipGraph must own its scratch); default: a
-    per-device scratch that grows on demand."""
+    per-device scratch that grows on demand.  Several objects: mesh = a MeshSet, obj = the per-hypothesis object index, mesh_diameter =
+    the (M,) table of object_diameters (fp_render_crops_multi: hypothesis n draws mesh obj[n])."""
+    multi = isinstance(mesh, MeshSet)
+    if multi:
+        d, o, M = _objects(mesh_diameter, obj, "render_crops") or (None, None, 0)
+        if d is None or M != mesh.M:
+            raise _lib.FpAmdError(f"render_crops: a MeshSet of {mesh.M} meshes needs a ({mesh.M},) diameter table")
+    elif obj is not None:
+        raise _lib.FpAmdError("render_crops: an object index needs a MeshSet")
     P = _dev(poses, torch.float32, "poses")
     N = int(P.shape[0])
     bb = _dev(bbox2d, torch.float32, "bbox2d")
@@ -184,7 +257,7 @@ def render_crops(mesh, poses, bbox2d, K, H, W, out_hw=(160, 160), mesh_diameter=
     zbuf = alloc("zbuf", (N, oh, ow), torch.int32)  # u32 payload, viewed as int32 by torch
     tri = alloc("tri_id", (N, oh, ow), torch.int32)
     L = _lib.lib()
-    need = L.fp_workspace_bytes(N, mesh.V, mesh.T, oh, ow)
+    need = mesh.workspace_bytes(N, oh, ow) if multi else L.fp_workspace_bytes(N, mesh.V, mesh.T, oh, ow)
     if workspace is not None:
         ws = _dev(workspace, torch.uint8, "workspace")
         if ws.numel() < need:
@@ -193,6 +266,12 @@ def render_crops(mesh, poses, bbox2d, K, H, W, out_hw=(160, 160), mesh_diameter=
         ws = _workspace(need, dev)
     K9 = _hostK32(K)
     flags = (FLAG_NORMALIZE_XYZ if normalize_xyz else 0) | (FLAG_OUT_F16 if (A is not None and A.dtype == torch.float16) else 0)
+    if multi:
+        st = L.fp_render_crops_multi(mesh.handle, _ptr(o), _ptr(d), _ptr(P), _ptr(bb), K9.ctypes.data_as(C.c_void_p), int(H), int(W),
+                                     N, oh, ow, w_ambient, w_diffuse, xyz_thr, flags, _ptr(A), _ptr(color), _ptr(depth), _ptr(xyz),
+                                     _ptr(normal), _ptr(zbuf), _ptr(tri), _ptr(ws), 0 if ws is None else ws.numel(), _stream(P))
+        _lib.check(st, "fp_render_crops_multi")
+        return outs
     st = L.fp_render_crops(mesh.handle, _ptr(P), _ptr(bb), K9.ctypes.data_as(C.c_void_p), int(H), int(W), N, oh, ow,
                            w_ambient, w_diffuse, float(np.float32(mesh_diameter)), xyz_thr, flags, _ptr(A), _ptr(color),
                            _ptr(depth), _ptr(xyz), _ptr(normal), _ptr(zbuf), _ptr(tri), _ptr(ws),
@@ -202,7 +281,9 @@ def render_crops(mesh, poses, bbox2d, K, H, W, out_hw=(160, 160), mesh_diameter=
 
 
 def warp_crops(rgb, xyz_map, depth, tf_to_crops, K, poses, mesh_diameter, mode, normalize_xyz=True, out_f16=False,
-               out_hw=(160, 160), B_out=None):
+               out_hw=(160, 160), B_out=None, obj=None):
+    """fp_warp_crops.  Several objects: mesh_diameter = the (M,) table of object_diameters, obj = the per-hypothesis object
+    index (fp_warp_crops_multi)."""
     rgbf = _dev(rgb, torch.float32, "rgb")
     H, W = int(rgbf.shape[0]), int(rgbf.shape[1])
     xm = _dev(xyz_map, torch.float32, "xyz_map")
@@ -215,6 +296,13 @@ def warp_crops(rgb, xyz_map, depth, tf_to_crops, K, poses, mesh_diameter, mode, 
                                                     device=P.device)
     flags = (FLAG_NORMALIZE_XYZ if normalize_xyz else 0) | (FLAG_OUT_F16 if B.dtype == torch.float16 else 0)
     K9 = _hostK32(K)
+    objs = _objects(mesh_diameter, obj, "warp_crops")
+    if objs is not None:
+        d, o, M = objs
+        st = _lib.lib().fp_warp_crops_multi(_ptr(rgbf), _ptr(xm), _ptr(dp), _ptr(tf), K9.ctypes.data_as(C.c_void_p), _ptr(P), _ptr(d),
+                                            _ptr(o), M, flags, int(mode), H, W, N, oh, ow, _ptr(B), _stream(P))
+        _lib.check(st, "fp_warp_crops_multi")
+        return B
     st = _lib.lib().fp_warp_crops(_ptr(rgbf), _ptr(xm), _ptr(dp), _ptr(tf), K9.ctypes.data_as(C.c_void_p), _ptr(P),
                                   float(np.float32(mesh_diameter)), flags, int(mode), H, W, N, oh, ow, _ptr(B), _stream(P))
     _lib.check(st, "fp_warp_crops")
@@ -223,9 +311,10 @@ def warp_crops(rgb, xyz_map, depth, tf_to_crops, K, poses, mesh_diameter, mode, 
 
 def pose_update(trans, rot, poses, rot_rep="axis_angle", normalize_xyz=True, trans_normalizer=(1.0, 1.0, 1.0),
                 rot_normalizer=1.0, mesh_diameter=1.0, out=None, trans_delta_out=None, rot_delta_out=None, trans_rep="tracknet",
-                K=None, tf_to_crops=None, input_w=0):
+                K=None, tf_to_crops=None, input_w=0, obj=None):
     """fp_pose_update.  trans_rep='deepim' needs K, tf_to_crops (N,3,3) and the crop width (predict_pose_refine.py:201-215);
-    any trans_rep other than 'tracknet' / 'deepim' is the reference's plain `else` branch (:217-218): the raw output"""
+    any trans_rep other than 'tracknet' / 'deepim' is the reference's plain `else` branch (:217-218): the raw output.  Several
+    objects: mesh_diameter = the (M,) table of object_diameters, obj = the per-hypothesis object index (fp_pose_update_multi)"""
     tr = _dev(trans, torch.float32, "trans")
     ro = _dev(rot, torch.float32, "rot")
     P = _dev(poses, torch.float32, "poses")
@@ -241,11 +330,21 @@ def pose_update(trans, rot, poses, rot_rep="axis_angle", normalize_xyz=True, tra
     deepim = trans_rep == "deepim"
     K9 = _hostK32(K) if deepim else None
     tf = _dev(tf_to_crops, torch.float32, "tf_to_crops") if deepim else None
+    tro = TRANS_DEEPIM if deepim else (TRANS_TRACKNET if trans_rep == "tracknet" else TRANS_RAW)
+    objs = _objects(mesh_diameter, obj, "pose_update")
+    if objs is not None:
+        d, o, M = objs
+        st = _lib.lib().fp_pose_update_multi(_ptr(tr), _ptr(ro), _ptr(P), rr, int(bool(normalize_xyz)), tn.ctypes.data_as(C.c_void_p),
+                                             float(rot_normalizer), _ptr(d), _ptr(o), M, N, _ptr(O),
+                                             _ptr(_dev(trans_delta_out, torch.float32, "trans_delta_out")),
+                                             _ptr(_dev(rot_delta_out, torch.float32, "rot_delta_out")), tro,
+                                             K9.ctypes.data_as(C.c_void_p) if deepim else None, _ptr(tf), float(input_w), _stream(P))
+        _lib.check(st, "fp_pose_update_multi")
+        return O
     st = _lib.lib().fp_pose_update(_ptr(tr), _ptr(ro), _ptr(P), rr, int(bool(normalize_xyz)),
                                    tn.ctypes.data_as(C.c_void_p), float(rot_normalizer), float(np.float32(mesh_diameter)),
                                    N, _ptr(O), _ptr(_dev(trans_delta_out, torch.float32, "trans_delta_out")),
-                                   _ptr(_dev(rot_delta_out, torch.float32, "rot_delta_out")),
-                                   TRANS_DEEPIM if deepim else (TRANS_TRACKNET if trans_rep == "tracknet" else TRANS_RAW),
+                                   _ptr(_dev(rot_delta_out, torch.float32, "rot_delta_out")), tro,
                                    K9.ctypes.data_as(C.c_void_p) if deepim else None, _ptr(tf), float(input_w), _stream(P))
     _lib.check(st, "fp_pose_update")
     return O

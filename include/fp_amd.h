@@ -54,6 +54,7 @@ typedef enum {
 #define FP_ZBUF_EMPTY 0xFFFFFFFFu
 
 typedef struct fp_mesh fp_mesh; /* opaque: device pointers + sizes of one object's mesh tensors */
+typedef struct fp_mesh_set fp_mesh_set; /* opaque: M mesh descriptors in one device table (several objects per call) */
 
 const char* fp_last_error(void);
 /* ABI version of the library = FP_AMD_ABI_VERSION of the header it was built from; a binding compares the two at load time
@@ -65,8 +66,10 @@ const char* fp_last_error(void);
  *   212 -> 213 (round 6): w_tiles is read only when flags has FP_IGEMM_HAS_W_TILES (a 212 caller that sets w_tiles without the bit
  *                         gets the plain weight path: correct, slower); fp_igemm_f16_splitk_fwd refuses w_tiles instead of ignoring it;
  *                         fp_linear_layernorm_fwd takes the row stride of x16 (new argument before the stream);
- *                         + fp_encoder_tail_mean_fwd / fp_encoder_tail_workspace_bytes. */
-#define FP_AMD_ABI_VERSION 213
+ *                         + fp_encoder_tail_mean_fwd / fp_encoder_tail_workspace_bytes.
+ *   213 -> 214: several objects per call (additions only): + fp_mesh_set_create / fp_mesh_set_destroy /
+ *               fp_mesh_set_workspace_bytes, fp_render_crops_multi, fp_crop_windows_multi, fp_warp_crops_multi, fp_pose_update_multi. */
+#define FP_AMD_ABI_VERSION 214
 int fp_version(void);
 
 /* Utils.py:104-130 make_mesh_tensors: records caller-owned device tensors.
@@ -77,6 +80,20 @@ int fp_mesh_create(const float* pos /*dev*/, const float* nrm /*dev*/, const int
                    const float* tex /*dev|NULL*/, const float* vcol /*dev|NULL*/, int V, int T, int Ht,
                    int Wt, fp_mesh** out);
 void fp_mesh_destroy(fp_mesh* mesh);
+
+/* Several objects per call.  A mesh set holds M mesh descriptors (fp_mesh_create) in one device table; every *_multi entry point
+ * takes a per-hypothesis object index obj (dev N int32, values 0..M-1, any order; NULL allowed only for M == 1: all 0) and the
+ * per-object diameters (dev M f64).  Hypothesis n then sees exactly what the scalar entry point sees for the mesh meshes[obj[n]]
+ * and the diameter diameters[obj[n]] (passed as that double to fp_crop_windows and rounded to float for the others): the outputs
+ * are bit-identical.  An index outside 0..M-1 renders nothing and yields NaN-scaled values, never a memory access out of the set.
+ * fp_mesh_set_create is a SETUP call: it allocates the device table and copies the descriptors synchronously (the per-frame
+ * entry points below copy nothing, so they can be captured in a hipGraph).  The set refers to the meshes' tensors, it does not own
+ * them; the fp_mesh handles themselves may be destroyed after the call.  V and T of every mesh: 1..FP_MESH_SET_MAX_ELEMS. */
+#define FP_MESH_SET_MAX_ELEMS (1 << 26)
+int fp_mesh_set_create(const fp_mesh* const* meshes /*host M*/, int M, fp_mesh_set** out);
+void fp_mesh_set_destroy(fp_mesh_set* set);
+/* fp_workspace_bytes for the set's largest V and largest T (so the lists are 32-bit when any mesh has T > 65535) */
+size_t fp_mesh_set_workspace_bytes(const fp_mesh_set* set, int N, int oh, int ow);
 
 /* Utils.py:359-395 erode_depth (+ kernel) */
 int fp_depth_erode(const float* depth /*dev H,W*/, float* out /*dev*/, int H, int W, int radius,
@@ -93,6 +110,10 @@ int fp_depth_to_xyz(const float* depth /*dev H,W*/, const double* K /*host 9*/, 
 int fp_crop_windows(const float* poses /*dev N,16*/, const double* K /*host 9*/, double mesh_diameter,
                     double crop_ratio, int out_w, int out_h, int N, float* tf_to_crops /*dev N,9*/,
                     float* bbox2d /*dev N,4*/, void* stream);
+/* fp_crop_windows with the diameter of hypothesis n = diameters[obj[n]] */
+int fp_crop_windows_multi(const float* poses /*dev N,16*/, const double* K /*host 9*/, const double* diameters /*dev M*/,
+                          const int32_t* obj /*dev N|NULL*/, int M, double crop_ratio, int out_w, int out_h, int N,
+                          float* tf_to_crops /*dev N,9*/, float* bbox2d /*dev N,4*/, void* stream);
 
 /* bytes of scratch fp_render_crops needs for (N hypotheses, V vertices, T triangles, oh x ow crops): per-hypothesis
  * vertex records (32 B/vertex) and per-strip triangle lists; caller-owned device memory, no alignment beyond 256 B */
@@ -111,6 +132,15 @@ int fp_render_crops(const fp_mesh* mesh, const float* poses /*dev N,16*/, const 
                     uint32_t* zbuf /*dev*/, int32_t* tri_id /*dev*/, void* workspace /*dev*/,
                     size_t workspace_bytes, void* stream);
 
+/* fp_render_crops with hypothesis n drawing mesh obj[n] of the set (meshes may differ in V, T and texture / vertex colour);
+ * diameters may be NULL without FP_FLAG_NORMALIZE_XYZ.  workspace: fp_mesh_set_workspace_bytes(set, N, oh, ow). */
+int fp_render_crops_multi(const fp_mesh_set* set, const int32_t* obj /*dev N|NULL*/, const double* diameters /*dev M|NULL*/,
+                          const float* poses /*dev N,16*/, const float* bbox2d /*dev N,4|NULL*/, const float* K9 /*host 9 f32*/,
+                          int H, int W, int N, int oh, int ow, float w_ambient, float w_diffuse, float xyz_thr, int flags,
+                          void* A /*dev*/, float* color /*dev*/, float* depth /*dev*/, float* xyz /*dev*/, float* normal /*dev*/,
+                          uint32_t* zbuf /*dev*/, int32_t* tri_id /*dev*/, void* workspace /*dev*/, size_t workspace_bytes,
+                          void* stream);
+
 /* kornia warp_perspective call sites predict_pose_refine.py:63,72 / predict_score.py:89,90 fused with
  * h5_dataset.py:79-114 (refine) or :137-170 (score: depth crop -> frame -> back-projection -> crop) and
  * the concat of predict_pose_refine.py:188 (B = [rgb, xyz]).
@@ -119,6 +149,12 @@ int fp_warp_crops(const float* rgb /*dev*/, const float* xyz_map /*dev|NULL*/, c
                   const float* tf_to_crops /*dev N,9*/, const float* K9 /*host 9 f32*/,
                   const float* poses /*dev N,16*/, float mesh_diameter, int flags, int mode, int H, int W,
                   int N, int oh, int ow, void* B /*dev N,6,oh,ow*/, void* stream);
+
+/* fp_warp_crops with the diameter of hypothesis n = diameters[obj[n]] */
+int fp_warp_crops_multi(const float* rgb /*dev*/, const float* xyz_map /*dev|NULL*/, const float* depth /*dev|NULL*/,
+                        const float* tf_to_crops /*dev N,9*/, const float* K9 /*host 9 f32*/, const float* poses /*dev N,16*/,
+                        const double* diameters /*dev M*/, const int32_t* obj /*dev N|NULL*/, int M, int flags, int mode, int H,
+                        int W, int N, int oh, int ow, void* B /*dev N,6,oh,ow*/, void* stream);
 
 /* predict_pose_refine.py:195-234 + Utils.py:848-855 + pytorch3d so3_exp_map / rotation_6d_to_matrix.
  * trans_delta_out / rot_delta_out (optional): the metric translation delta and the applied rotation matrix
@@ -129,6 +165,13 @@ int fp_pose_update(const float* trans /*dev N,3*/, const float* rot /*dev N,3|6*
                    float* poses_out /*dev N,16*/, float* trans_delta_out /*dev N,3|NULL*/,
                    float* rot_delta_out /*dev N,9|NULL*/, int trans_rep, const float* K9 /*host 9 f32|NULL (deepim)*/,
                    const float* tf_to_crops /*dev N,9|NULL (deepim)*/, float input_w /*crop width (deepim)*/, void* stream);
+/* fp_pose_update with the diameter of hypothesis n = diameters[obj[n]] */
+int fp_pose_update_multi(const float* trans /*dev N,3*/, const float* rot /*dev N,3|6*/, const float* poses_in /*dev N,16*/,
+                         int rot_rep, int normalize_xyz, const float* trans_normalizer /*host 3*/, float rot_normalizer,
+                         const double* diameters /*dev M*/, const int32_t* obj /*dev N|NULL*/, int M, int N,
+                         float* poses_out /*dev N,16*/, float* trans_delta_out /*dev N,3|NULL*/, float* rot_delta_out /*dev N,9|NULL*/,
+                         int trans_rep, const float* K9 /*host 9 f32|NULL (deepim)*/, const float* tf_to_crops /*dev N,9|NULL*/,
+                         float input_w, void* stream);
 
 /* ---- network stage.  Arithmetic policy of every entry point below = the op sequence torch.cuda.amp.autocast(fp16)
  * produces for the reference's modules (predict_pose_refine.py:190-191, predict_score.py:193-194): fp16 operands,

@@ -1,0 +1,111 @@
+"""CPU: the multi-object entry points (several objects per refine call) -- argument errors of the C ABI, reported without a GPU,
+and the per-object grouping of the two-pose quirk on hand-made object indices."""
+import ctypes as C
+
+import pytest
+
+
+def _fake_mesh(lib, V, T):
+    """an fp_mesh descriptor over made-up device addresses (fp_mesh_create only records them)"""
+    h = C.c_void_p()
+    assert lib.fp_mesh_create(C.c_void_p(16), C.c_void_p(32), C.c_void_p(48), None, None, None, C.c_void_p(64), V, T, 0, 0,
+                              C.byref(h)) == 0
+    return h
+
+
+def test_mesh_set_argument_errors_are_reported_without_gpu():
+    from foundationpose_amd import _lib
+    lib = _lib.lib()
+    s = C.c_void_p()
+    m1, m2 = _fake_mesh(lib, 100, 200), _fake_mesh(lib, 40000, 70000)
+    try:
+        arr = (C.c_void_p * 2)(m1.value, m2.value)
+        assert lib.fp_mesh_set_create(arr, 0, C.byref(s)) == -1 and b"empty set" in lib.fp_last_error()
+        assert not s.value
+        assert lib.fp_mesh_set_create(None, 2, C.byref(s)) == -1 and b"meshes is NULL" in lib.fp_last_error()
+        assert lib.fp_mesh_set_create(arr, 2, None) == -1 and b"out is NULL" in lib.fp_last_error()
+        holes = (C.c_void_p * 2)(m1.value, None)
+        assert lib.fp_mesh_set_create(holes, 2, C.byref(s)) == -1 and b"mesh 1 is NULL" in lib.fp_last_error()
+        huge = _fake_mesh(lib, 10, (1 << 26) + 1)
+        try:
+            assert lib.fp_mesh_set_create((C.c_void_p * 1)(huge.value), 1, C.byref(s)) == -1
+            assert b"mesh 0 has V=10, T=67108865" in lib.fp_last_error()
+        finally:
+            lib.fp_mesh_destroy(huge)
+        # a NULL set is refused by the render and sized as nothing
+        assert lib.fp_render_crops_multi(None, None, None, C.c_void_p(16), None, C.c_void_p(16), 480, 640, 4, 160, 160, 0.8, 0.5,
+                                         0.001, 1, None, None, None, None, None, None, None, None, 0, None) == -1
+        assert b"NULL mesh set" in lib.fp_last_error()
+        assert lib.fp_mesh_set_workspace_bytes(None, 4, 160, 160) == 0
+        # the per-object diameter entry points: no diameters, no objects, obj NULL with several objects, unknown flags
+        assert lib.fp_crop_windows_multi(C.c_void_p(16), None, None, C.c_void_p(16), 2, 1.2, 160, 160, 4, C.c_void_p(16),
+                                         C.c_void_p(16), None) == -1
+        assert b"fp_crop_windows_multi: need the diameters" in lib.fp_last_error()
+        assert lib.fp_crop_windows_multi(C.c_void_p(16), None, C.c_void_p(16), None, 3, 1.2, 160, 160, 4, C.c_void_p(16),
+                                         C.c_void_p(16), None) == -1
+        assert b"obj is NULL but there are 3 objects" in lib.fp_last_error()
+        assert lib.fp_warp_crops_multi(None, None, None, None, None, None, C.c_void_p(16), None, 2, 1, 0, 480, 640, 4, 160, 160,
+                                       None, None) == -1
+        assert b"fp_warp_crops_multi: obj is NULL" in lib.fp_last_error()
+        assert lib.fp_warp_crops_multi(None, None, None, None, None, None, C.c_void_p(16), None, 0, 1, 0, 480, 640, 4, 160, 160,
+                                       None, None) == -1
+        assert lib.fp_warp_crops_multi(C.c_void_p(16), C.c_void_p(16), None, C.c_void_p(16), C.c_void_p(16), C.c_void_p(16),
+                                       C.c_void_p(16), C.c_void_p(16), 2, 1, 7, 480, 640, 4, 160, 160, C.c_void_p(16), None) == -1
+        assert b"fp_warp_crops_multi: unknown mode 7" in lib.fp_last_error()
+        assert lib.fp_pose_update_multi(C.c_void_p(16), C.c_void_p(16), C.c_void_p(16), 0, 1, None, 0.35, C.c_void_p(16), None, 4,
+                                        8, C.c_void_p(16), None, None, 0, None, None, 0.0, None) == -1
+        assert b"fp_pose_update_multi: obj is NULL but there are 4 objects" in lib.fp_last_error()
+        assert lib.fp_pose_update_multi(C.c_void_p(16), C.c_void_p(16), C.c_void_p(16), 5, 1, None, 0.35, C.c_void_p(16),
+                                        C.c_void_p(16), 4, 8, C.c_void_p(16), None, None, 0, None, None, 0.0, None) == -1
+        assert b"fp_pose_update_multi: unknown rot_rep 5" in lib.fp_last_error()
+        # nothing to do
+        assert lib.fp_pose_update_multi(None, None, None, 0, 1, None, 0.35, C.c_void_p(16), None, 1, 0, None, None, None, 0, None,
+                                        None, 0.0, None) == 0
+        # a real set needs the device table; without a GPU its creation fails loudly, with one the render checks obj
+        st = lib.fp_mesh_set_create(arr, 2, C.byref(s))
+        if st != 0:
+            assert b"fp_mesh_set_create: device table of 2 meshes" in lib.fp_last_error() and not s.value
+        else:
+            try:
+                # sized by the largest V and T of the set; T > 65535: 32-bit triangle lists
+                assert lib.fp_mesh_set_workspace_bytes(s, 4, 160, 160) == lib.fp_workspace_bytes(4, 40000, 70000, 160, 160)
+                assert lib.fp_render_crops_multi(s, None, C.c_void_p(16), C.c_void_p(16), None, C.c_void_p(16), 480, 640, 4, 160,
+                                                 160, 0.8, 0.5, 0.001, 1, None, None, None, None, None, None, None, None, 0, None) == -1
+                assert b"obj is NULL but the set has 2 meshes" in lib.fp_last_error()
+                assert lib.fp_render_crops_multi(s, C.c_void_p(16), None, C.c_void_p(16), None, C.c_void_p(16), 480, 640, 4, 160,
+                                                 160, 0.8, 0.5, 0.001, 1, None, None, None, None, None, None, None, None, 0, None) == -1
+                assert b"FP_FLAG_NORMALIZE_XYZ needs the diameters" in lib.fp_last_error()
+                assert lib.fp_render_crops_multi(s, C.c_void_p(16), None, C.c_void_p(16), None, C.c_void_p(16), 480, 640, 4, 160,
+                                                 160, 0.8, 0.5, 0.001, 0x10000, None, None, None, None, None, None, None, None, 0,
+                                                 None) == -1
+                assert b"unknown flag bits" in lib.fp_last_error()
+            finally:
+                lib.fp_mesh_set_destroy(s)
+    finally:
+        lib.fp_mesh_destroy(m1)
+        lib.fp_mesh_destroy(m2)
+
+
+@pytest.mark.parametrize("obj,pairs", [
+    ([0, 1, 2, 0, 1, 2], [(0, 3), (1, 4), (2, 5)]),    # three objects interleaved, two hypotheses each
+    ([0, 0], [(0, 1)]),                                # the single-object quirk: one object, exactly two poses
+    ([0, 1], []),                                      # two objects x one hypothesis: never paired across objects
+    ([3, 1, 3, 2, 2, 2], [(0, 2)]),                    # interleaved; object 2 has three hypotheses, object 1 one
+    ([1, 0, 0, 1, 2], [(0, 3), (1, 2)]),
+    ([], []),
+])
+def test_two_pose_pairs(obj, pairs):
+    from foundationpose_amd.predict_pose_refine import two_pose_pairs
+    assert two_pose_pairs(obj) == pairs
+
+
+def test_parts_keep_quirk_pairs_together():
+    from foundationpose_amd.predict_pose_refine import parts_for_pairs, two_pose_pairs
+    parts = [(0, 32), (32, 64)]
+    assert parts_for_pairs(parts, []) == parts
+    assert parts_for_pairs(parts, [(0, 1), (32, 33)]) == parts
+    assert parts_for_pairs(parts, [(31, 32)]) == [(0, 64)]         # a pair across the boundary: one part
+    obj = [k for k in range(32) for _ in range(2)]                  # 32 objects x 2 hypotheses, object-major
+    assert parts_for_pairs(parts, two_pose_pairs(obj)) == parts
+    obj = list(range(32)) * 2                                       # the same interleaved: every pair straddles
+    assert parts_for_pairs(parts, two_pose_pairs(obj)) == [(0, 64)]
