@@ -76,21 +76,47 @@ struct AtShape {
   static constexpr int ROWS = 32 * QT * WAVES;     // query rows per workgroup
 };
 
+// Where a sequence lies in qkv / out (the kernel's SEQ parameter):
+//   AtUniform  (fp_attention_f16_fwd): B sequences of S rows each, sequence b = rows b S .. b S + S - 1;
+//   AtSegments (fp_attention_segments_f16_fwd): sequence b = rows offs[b] .. offs[b + 1] - 1 (device table, ragged lengths); the
+//       grid is sized for max_S rows per sequence, and a workgroup whose query group lies past its own sequence's end returns
+//       as a whole before the first barrier.
+// `grid_S` is the length that sizes the grid; `seq(b, S, row0)` gives the length and first row of sequence b.
+struct AtUniform {
+  int S;
+  __device__ __forceinline__ int grid_S() const { return S; }
+  __device__ __forceinline__ void seq(int b, int& S_b, size_t& row0) const { S_b = S; row0 = (size_t)b * S; }
+};
+struct AtSegments {
+  const int32_t* offs;
+  int max_S;
+  __device__ __forceinline__ int grid_S() const { return max_S; }
+  __device__ __forceinline__ void seq(int b, int& S_b, size_t& row0) const {
+    const int r0 = offs[b];
+    S_b = offs[b + 1] - r0;
+    row0 = (size_t)r0;
+  }
+};
+
 // qscale > 0 selects the fp16-score policy of the need_weights=True branch of F.multi_head_attention_forward under
 // autocast (score_network.py:73,86): q is multiplied by qscale = sqrt(1/d) and rounded to fp16, the q.k products are
 // rounded to fp16 before the fp32 softmax (c is then log2(e) alone).  qscale == 0: scaled_dot_product_attention.
-template <int QT, int WAVES>
+template <int QT, int WAVES, typename SEQ>
 __global__ __launch_bounds__(WAVES * 64, QT == 1 ? 2 : 1) void k_attention_f16(const _Float16* __restrict__ qkv, _Float16* __restrict__ out,
-                                                                            int S, int H, float c /* log2(e)/sqrt(d) | log2(e) */, float qscale) {
+                                                                            SEQ seqs, int H, float c /* log2(e)/sqrt(d) | log2(e) */, float qscale) {
   constexpr int THREADS = WAVES * 64;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int lq = lane & 31, hi = lane >> 5;
-  const int nqg = (S + 32 * QT * WAVES - 1) / (32 * QT * WAVES);   // query groups per (sequence, head)
+  const int nqg = (seqs.grid_S() + 32 * QT * WAVES - 1) / (32 * QT * WAVES);   // query groups per (sequence, head)
   const int qg = blockIdx.x % nqg, bh = blockIdx.x / nqg;
   const int h = bh % H, b = bh / H;
+  int S;
+  size_t row0;
+  seqs.seq(b, S, row0);
+  if (!std::is_same<SEQ, AtUniform>::value && qg * (32 * QT * WAVES) >= S) return;   // past the end of this segment (or an empty one)
   const int ld = 3 * H * AT_D, ldo = H * AT_D;
-  const _Float16* qp = qkv + (size_t)b * S * ld + h * AT_D;
+  const _Float16* qp = qkv + row0 * ld + h * AT_D;
   const _Float16* kp = qp + H * AT_D;
   const _Float16* vp = kp + H * AT_D;
   const int q0 = (qg * WAVES + wid) * (32 * QT);   // first query row of this wave
@@ -366,7 +392,7 @@ __global__ __launch_bounds__(WAVES * 64, QT == 1 ? 2 : 1) void k_attention_f16(c
       const int q = q0 + r;
       if (q < S) {
         const uint4_ v = *reinterpret_cast<const uint4_*>(tile + r * 256 + ((ch ^ (r & 15)) << 4));
-        *reinterpret_cast<uint4_*>(out + ((size_t)b * S + q) * ldo + h * AT_D + ch * 8) = v;
+        *reinterpret_cast<uint4_*>(out + (row0 + q) * ldo + h * AT_D + ch * 8) = v;
       }
     }
   }
@@ -380,15 +406,15 @@ __global__ __launch_bounds__(WAVES * 64, QT == 1 ? 2 : 1) void k_attention_f16(c
 #endif
 }
 
-template <int QT, int WAVES>
-int at_launch(const void* qkv, void* out, int B, int S, int H, float c, float qscale, hipStream_t stream) {
+template <int QT, int WAVES, typename SEQ>
+int at_launch(const char* name, const void* qkv, void* out, int B, SEQ seqs, int grid_S, int H, float c, float qscale, hipStream_t stream) {
   static_assert(WAVES * 32 * QT * 256 <= AT_LDS, "the output tiles reuse the K / V buffers");
-  const long long wgs = (long long)B * H * ((S + 32 * QT * WAVES - 1) / (32 * QT * WAVES));
-  FP_REQUIRE(wgs < (1ll << 31), "fp_attention_f16_fwd: too many workgroups");
-  FP_SET_MAX_LDS((k_attention_f16<QT, WAVES>), AT_LDS);
-  hipLaunchKernelGGL((k_attention_f16<QT, WAVES>), dim3((unsigned)wgs), dim3(WAVES * 64), AT_LDS, stream,
-                     (const _Float16*)qkv, (_Float16*)out, S, H, c, qscale);
-  FP_CHECK_LAUNCH("fp_attention_f16_fwd");
+  const long long wgs = (long long)B * H * ((grid_S + 32 * QT * WAVES - 1) / (32 * QT * WAVES));
+  FP_REQUIRE(wgs < (1ll << 31), "%s: too many workgroups", name);
+  FP_SET_MAX_LDS((k_attention_f16<QT, WAVES, SEQ>), AT_LDS);
+  hipLaunchKernelGGL((k_attention_f16<QT, WAVES, SEQ>), dim3((unsigned)wgs), dim3(WAVES * 64), AT_LDS, stream,
+                     (const _Float16*)qkv, (_Float16*)out, seqs, H, c, qscale);
+  FP_CHECK_LAUNCH(name);
   return FP_OK;
 }
 
@@ -412,7 +438,24 @@ extern "C" int fp_attention_f16_fwd(const void* qkv, void* out, int B, int S, in
   // profiling build only: FP_ATT_QT=2 selects the measured-and-rejected 64-queries-per-wave shape
   static int forced = -1;
   if (forced < 0) { const char* e = getenv("FP_ATT_QT"); forced = e ? atoi(e) : 0; }
-  if ((forced == 2 || (forced == 0 && AT_DEFAULT_QT == 2)) && S > 32) return at_launch<2, 4>(qkv, out, B, S, H, c, qscale, (hipStream_t)stream);
+  if ((forced == 2 || (forced == 0 && AT_DEFAULT_QT == 2)) && S > 32)
+    return at_launch<2, 4>("fp_attention_f16_fwd", qkv, out, B, AtUniform{S}, S, H, c, qscale, (hipStream_t)stream);
 #endif
-  return at_launch<1, 8>(qkv, out, B, S, H, c, qscale, (hipStream_t)stream);
+  return at_launch<1, 8>("fp_attention_f16_fwd", qkv, out, B, AtUniform{S}, S, H, c, qscale, (hipStream_t)stream);
+}
+
+extern "C" int fp_attention_segments_f16_fwd(const void* qkv, void* out, const int32_t* seg_offsets, int B, int max_S, int H,
+                                             int head_dim, int flags, void* stream) {
+  FP_REQUIRE(B >= 0 && max_S >= 0, "fp_attention_segments_f16_fwd: negative size (B=%d, max_S=%d)", B, max_S);
+  FP_REQUIRE(qkv && out && seg_offsets, "fp_attention_segments_f16_fwd: NULL tensor");
+  FP_REQUIRE(head_dim == AT_D, "fp_attention_segments_f16_fwd: head_dim=%d (only 128 is built)", head_dim);
+  FP_REQUIRE(H > 0 && ((((size_t)qkv | (size_t)out) & 15) == 0) && ((size_t)seg_offsets & 3) == 0,
+             "fp_attention_segments_f16_fwd: bad head count / unaligned tensors");
+  FP_REQUIRE((flags & ~FP_ATT_FP16_SCORES) == 0, "fp_attention_segments_f16_fwd: unknown flags 0x%x", flags);
+  if (B == 0 || max_S == 0) return FP_OK;
+  const bool f16s = (flags & FP_ATT_FP16_SCORES) != 0;
+  const float qscale = f16s ? (float)sqrt(1.0 / (double)head_dim) : 0.f;
+  const float c = f16s ? 1.4426950408889634f : 1.4426950408889634f / sqrtf((float)head_dim);
+  return at_launch<1, 8>("fp_attention_segments_f16_fwd", qkv, out, B, AtSegments{seg_offsets, max_S}, max_S, H, c, qscale,
+                         (hipStream_t)stream);
 }

@@ -402,6 +402,12 @@ class _HipMHA:
         """softmax(q k^T / sqrt(d)) v with heads merged, before the output projection: (Bn, L, D) fp16.  slot: as for the encoder's
         activation sets -- callers that overlap on different streams must not share the split-K slab"""
         Bn, L, D = x16.shape
+        qkv = self.in_proj(x16, slot, small_calls)
+        return ops.attention_f16(qkv.reshape(Bn, L, 3 * D), self.nhead, fp16_scores=self.fp16_scores)
+
+    def in_proj(self, x16, slot=0, small_calls=True):
+        """the in_proj of context(): (Bn, L, D) fp16 -> [q | k | v] rows (Bn * L, 3 D) (or (Bn, L, 3 D)) fp16"""
+        Bn, L, D = x16.shape
         if ROWS_QKV and self.qkv_p is not None and Bn * L >= ROWS_QKV_MIN_ROWS:
             qkv = ops.linear512(x16, self.qkv_p, self.qkv.b)
         elif self.small_calls and small_calls and small_call(Bn, SPLITK_MAX_HYPS) and D % 64 == 0 and D // 64 >= 4:
@@ -416,7 +422,7 @@ class _HipMHA:
             ops.igemm_f16_splitk(x16.reshape(M, D), Gm(D), self.qkv.w, self.qkv.b, qkv, Gm(No), M, No, D, 1, pieces, ws)
         else:
             qkv = self.qkv(x16)
-        return ops.attention_f16(qkv.reshape(Bn, L, 3 * D), self.nhead, fp16_scores=self.fp16_scores)
+        return qkv
 
     def __call__(self, x16, slot=0, small_calls=True):
         return self.out(self.context(x16, slot, small_calls))
@@ -635,6 +641,32 @@ class ScorePlan:
             return self.lin(o16.reshape(-1, o16.shape[-1]), round_f16=True).reshape(-1, L)
         x = self.att_cross(x.to(self.dtype))
         return F.linear(x, self.lin_w, self.lin_b).float().reshape(-1, L)
+
+    @torch.inference_mode()
+    def head_segments(self, feats, segments):
+        """head() for several objects in one call: feats (Ntot,512) packed as `segments` (ops.Segments; segment k = object k's
+        hypotheses) -> logits (Ntot,) fp32, each segment's the bits of head(feats[segment], L=its length): the cross-hypothesis
+        attention stays inside a segment (a common L, or attention over all rows, would change every score).  HIP plan: the
+        in_proj, out_proj and final Linear treat rows independently and run once over all rows, the attention is
+        fp_attention_segments_f16_fwd; the torch plans run head() per segment."""
+        if feats.shape[0] != segments.total:
+            raise ValueError(f"head_segments: {feats.shape[0]} feature rows but the segments cover {segments.total}")
+        if segments.total == 0:
+            return torch.empty((0,), dtype=torch.float32, device=feats.device)
+        if self.hip and self.module is None:
+            x = feats if feats.dtype == torch.float16 else feats.to(torch.float16)
+            x = x.contiguous()
+            mha = self.att_cross
+            qkv = mha.in_proj(x[None]).reshape(segments.total, -1)       # one "sequence" of all rows: rows are independent here
+            ctx = ops.attention_f16_segments(qkv, segments, mha.nhead, fp16_scores=mha.fp16_scores)
+            o16 = mha.out(ctx)
+            return self.lin(o16, round_f16=True).reshape(-1)
+        out = torch.empty((segments.total,), dtype=torch.float32, device=feats.device)
+        for k in range(len(segments)):
+            a, b = segments.rows(k)
+            if b > a:
+                out[a:b] = self.head(feats[a:b], L=b - a).reshape(-1)
+        return out
 
     def __call__(self, AB, L):
         return {"score_logit": self.head(self.features(AB), L)}

@@ -225,7 +225,7 @@ def track_objects(estimators, rgb, depth, K, iteration=2):
     a call never mix; each one draws its own mesh and uses its own diameter).  Every estimator must be registered and all must share
     ONE refiner object (its network and configuration are the loop's).  The captured tracker is cached on that refiner under
     (estimators, frame size, K, iteration), like track_one's.  -> [4x4 np.ndarray] per estimator, in its original mesh frame;
-    updates each pose_last.  register() stays per object."""
+    updates each pose_last.  register_objects is the batched register()."""
     ests = list(estimators)
     if not ests:
         raise ValueError("track_objects: no estimators")
@@ -255,3 +255,96 @@ def track_objects(estimators, rgb, depth, K, iteration=2):
         e.pose_last = out[k:k + 1]
         poses.append((out[k] @ e.get_tf_to_centered_mesh()).data.cpu().numpy().reshape(4, 4))
     return poses
+
+
+def _object_tables(refiner, ests):
+    """the MeshSet and diameter table of `ests`' objects, cached on the shared refiner like track_objects' tracker, under the
+    estimators and their mesh tensors"""
+    key = tuple((id(e), id(e.mesh_tensors)) for e in ests)
+    cached = getattr(refiner, "_objects_tables", None)
+    if cached is None or cached[0] != key:
+        from .Utils import get_mesh_handle
+        dev = ests[0].device
+        mset = ops.MeshSet([get_mesh_handle(e.mesh_tensors) for e in ests])
+        # the entry keeps the estimators and their mesh dicts alive, so the ids of its key cannot be reused while it is cached
+        cached = refiner._objects_tables = (key, mset, ops.object_diameters([e.diameter for e in ests], dev), ests,
+                                            [e.mesh_tensors for e in ests])
+    return cached[1], cached[2]
+
+
+def register_objects(estimators, K, rgb, depth, ob_masks, ob_ids=None, iteration=5):
+    """register() for several objects in one frame: ONE depth ingest, ONE batched refine loop over all objects' hypotheses
+    (refine_device with a MeshSet and an ObjectIndex) and ONE scorer call (ScorePredictor.predict_objects, whose cross-hypothesis
+    attention stays inside each object) instead of len(estimators) register() calls.  ob_masks[k] is estimator k's object mask,
+    ob_ids[k] its id.  Per object the result, and the state set on the estimator (H, W, K, ob_id, ob_mask, pose_last, best_id,
+    poses, scores), is what its own register() computes; an object whose mask holds fewer than 4 valid depths gets register()'s
+    guess-translation pose and keeps its state, as there.  All estimators must share ONE refiner and ONE scorer object.
+    -> [4x4 np.ndarray] per estimator, in its original mesh frame."""
+    ests = list(estimators)
+    if not ests:
+        raise ValueError("register_objects: no estimators")
+    masks = list(ob_masks)
+    if len(masks) != len(ests):
+        raise ValueError(f"register_objects: {len(ests)} estimators but {len(masks)} masks")
+    ob_ids = [None] * len(ests) if ob_ids is None else list(ob_ids)
+    if len(ob_ids) != len(ests):
+        raise ValueError(f"register_objects: {len(ests)} estimators but {len(ob_ids)} object ids")
+    refiner, scorer = ests[0].refiner, ests[0].scorer
+    if any(e.refiner is not refiner for e in ests):
+        raise ValueError("register_objects: the estimators must share one refiner object (FoundationPose(..., refiner=shared))")
+    if any(e.scorer is not scorer for e in ests):
+        raise ValueError("register_objects: the estimators must share one scorer object (FoundationPose(..., scorer=shared))")
+    if len({id(e) for e in ests}) != len(ests):
+        raise ValueError("register_objects: an estimator is listed twice")
+    set_seed(0)
+    dev = ests[0].device
+    for e in ests:
+        if e.glctx is None:
+            e.glctx = dr.RasterizeCudaContext(e.device)
+    # register()'s depth ingest, once for all objects
+    depth_t = torch.as_tensor(depth, device=dev, dtype=torch.float).contiguous()
+    depth_t = ops.erode_depth(depth_t, radius=2)
+    depth_t = ops.bilateral_filter_depth(depth_t, radius=2)
+    out, hyps, lengths, masks_np = [None] * len(ests), [], [], []
+    for k, (e, m) in enumerate(zip(ests, masks)):
+        m = np.asarray(m.data.cpu().numpy() if torch.is_tensor(m) else m)
+        masks_np.append(m)
+        mask_t = torch.as_tensor(m, device=dev) > 0
+        if int(((depth_t >= 0.001) & mask_t).sum()) < 4:
+            logging.info(f"object {k}: valid too small, return")
+            pose = np.eye(4)
+            pose[:3, 3] = e.guess_translation(depth=depth_t, mask=mask_t, K=K)
+            out[k] = pose
+            lengths.append(0)
+            continue
+        P = e.generate_random_pose_hypo(K=K, rgb=rgb, depth=depth_t, mask=mask_t, scene_pts=None)
+        hyps.append(P)
+        lengths.append(int(P.shape[0]))
+    if not hyps:
+        return out
+    from .predict_pose_refine import ObjectIndex
+    seg = ops.Segments(lengths, dev)
+    mset, diam = _object_tables(refiner, ests)
+    with torch.inference_mode():
+        xyz_t = ops.depth_to_xyz(depth_t, K, zfar=float("inf"), f64_internal=True).contiguous()   # depth2xyzmap (numpy variant)
+        rgb_t = torch.as_tensor(rgb, device=dev).to(torch.float).contiguous()
+        H, W = int(rgb_t.shape[0]), int(rgb_t.shape[1])
+        poses, trans, rot = refiner.refine_device(rgb_t, xyz_t, torch.cat(hyps).contiguous(), K, H, W, mset, diam, iteration,
+                                                  shared_translation=False, obj=ObjectIndex(np.repeat(np.arange(len(ests)), lengths), dev))
+        refiner.last_trans_update, refiner.last_rot_update = trans, rot
+        scores = scorer.predict_objects(rgb, depth_t, K, poses, mset, diam, seg)
+    for k, e in enumerate(ests):
+        a, b = seg.rows(k)
+        if b == a:
+            continue
+        ids = scores[a:b].argsort(descending=True)
+        e.H, e.W = int(depth_t.shape[0]), int(depth_t.shape[1])
+        e.K = K
+        e.ob_id = ob_ids[k]
+        e.ob_mask = masks_np[k]
+        e.scores = scores[a:b][ids]
+        e.poses = poses[a:b][ids]
+        e.pose_last = e.poses[0]
+        e.best_id = ids[0]
+        out[k] = (e.poses[0] @ e.get_tf_to_centered_mesh()).data.cpu().numpy()
+    return out

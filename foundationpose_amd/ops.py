@@ -697,6 +697,62 @@ def attention_f16(qkv, n_heads, fp16_scores=False):
     return out
 
 
+class Segments:
+    """Ragged sequences packed row after row (several objects' hypotheses in one call): segment k is rows offsets[k] ..
+    offsets[k + 1] - 1.  Built once from host lengths, like predict_pose_refine.ObjectIndex: the host offsets, the int32 device
+    offset table the kernels read (so a captured graph copies nothing), the longest segment max_S and the row total."""
+
+    def __init__(self, lengths, device):
+        L = np.asarray(lengths).reshape(-1)
+        if L.size == 0:
+            raise ValueError("Segments: no segments")
+        if L.dtype.kind not in "iu":
+            raise ValueError(f"Segments: lengths must be integers, got {L.dtype}")
+        L = L.astype(np.int64)
+        if L.min() < 0:
+            raise ValueError(f"Segments: negative length {int(L.min())}")
+        self.lengths = L
+        self.offsets = np.concatenate([[0], np.cumsum(L)]).astype(np.int64)
+        self.total = int(self.offsets[-1])
+        if self.total > np.iinfo(np.int32).max:
+            raise ValueError(f"Segments: {self.total} rows do not fit the int32 offset table")
+        self.max_S = int(L.max())
+        self.B = int(L.size)
+        self.dev = torch.as_tensor(self.offsets.astype(np.int32), device=device)
+
+    def __len__(self):
+        return self.B
+
+    def rows(self, k):
+        """the row range (a, b) of segment k"""
+        return int(self.offsets[k]), int(self.offsets[k + 1])
+
+    def row_ids(self):
+        """(total,) int32 device tensor: the segment of every row (the per-hypothesis object index of a multi-object call); built
+        at the first use and kept"""
+        if getattr(self, "_row_ids", None) is None:
+            self._row_ids = torch.as_tensor(np.repeat(np.arange(self.B), self.lengths).astype(np.int32), device=self.dev.device)
+        return self._row_ids
+
+
+def attention_f16_segments(qkv, segments, n_heads, fp16_scores=False):
+    """qkv (Ntot, 3*D) fp16 packed as `segments` (Segments) -> (Ntot, D) fp16: attention_f16 over every segment on its own rows,
+    never across segments (fp_attention_segments_f16_fwd; each segment gets the bits of attention_f16 on its slice)"""
+    qkv = _dev(qkv, torch.float16, "qkv")
+    if qkv.dim() != 2 or qkv.shape[1] % 3:
+        raise _lib.FpAmdError(f"attention_f16_segments: qkv must be (Ntot, 3*D), got {tuple(qkv.shape)}")
+    Ntot, D = int(qkv.shape[0]), int(qkv.shape[1]) // 3
+    if Ntot != segments.total:
+        raise _lib.FpAmdError(f"attention_f16_segments: {Ntot} rows but the segments cover {segments.total}")
+    if segments.dev.device != qkv.device:
+        raise _lib.FpAmdError(f"attention_f16_segments: offsets on {segments.dev.device}, qkv on {qkv.device}")
+    out = torch.empty((Ntot, D), dtype=torch.float16, device=qkv.device)
+    st = _lib.lib().fp_attention_segments_f16_fwd(_ptr(qkv), _ptr(out), _ptr(segments.dev), segments.B, segments.max_S, int(n_heads),
+                                                  D // int(n_heads), ATT_FP16_SCORES if fp16_scores else 0, _stream(qkv))
+    _lib.check(st, "fp_attention_segments_f16_fwd")
+    return out
+
+
 def cluster_poses(angle_diff, dist_diff, poses, symmetry_tfs):
     """Host op (init-time): returns indices of the kept poses (mycpp.cluster_poses semantics)."""
     P = np.ascontiguousarray(np.asarray(poses, dtype=np.float32).reshape(-1, 16))
@@ -833,3 +889,6 @@ colmean_f16 = _timed("fp_colmean_f16_fwd", colmean_f16,
 rows_linear = _timed("fp_rows_linear_fwd", rows_linear)
 attention_f16 = _timed("fp_attention_f16_fwd", attention_f16,
                        lambda qkv, n_heads, **k: (2.0 * qkv.numel() * 4.0 / 3.0, 4.0 * qkv.shape[0] * qkv.shape[1] ** 2 * (qkv.shape[2] // 3)))
+attention_f16_segments = _timed("fp_attention_segments_f16_fwd", attention_f16_segments,
+                                lambda qkv, seg, n_heads, **k: (2.0 * qkv.numel() * 4.0 / 3.0,
+                                                                4.0 * float((seg.lengths ** 2).sum()) * (qkv.shape[1] // 3)))

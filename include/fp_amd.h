@@ -68,8 +68,9 @@ const char* fp_last_error(void);
  *                         fp_linear_layernorm_fwd takes the row stride of x16 (new argument before the stream);
  *                         + fp_encoder_tail_mean_fwd / fp_encoder_tail_workspace_bytes.
  *   213 -> 214: several objects per call (additions only): + fp_mesh_set_create / fp_mesh_set_destroy /
- *               fp_mesh_set_workspace_bytes, fp_render_crops_multi, fp_crop_windows_multi, fp_warp_crops_multi, fp_pose_update_multi. */
-#define FP_AMD_ABI_VERSION 214
+ *               fp_mesh_set_workspace_bytes, fp_render_crops_multi, fp_crop_windows_multi, fp_warp_crops_multi, fp_pose_update_multi.
+ *   214 -> 215: + fp_attention_segments_f16_fwd (addition only): attention over ragged sequences (several objects' hypotheses). */
+#define FP_AMD_ABI_VERSION 215
 int fp_version(void);
 
 /* Utils.py:104-130 make_mesh_tensors: records caller-owned device tensors.
@@ -366,6 +367,16 @@ int fp_rows_linear_fwd(const void* x /*dev*/, const void* w /*dev*/, const float
  * after it (flash-attention order); the (B*H, S, S) probability tensor is never formed. */
 int fp_attention_f16_fwd(const void* qkv /*dev*/, void* out /*dev*/, int B, int S, int H, int head_dim, int flags,
                          void* stream);
+
+/* fp_attention_f16_fwd over B sequences of DIFFERENT lengths packed row after row (the scorer's cross-hypothesis attention of
+ * several objects in one call, score_network.py:83-88 per object): sequence b is rows seg_offsets[b] .. seg_offsets[b+1] - 1 of qkv
+ * (Ntot, 3*H*hd) and of out (Ntot, H*hd); no attention crosses a segment boundary.  seg_offsets (B+1) int32 stays on the device
+ * (non-decreasing, seg_offsets[0] = 0 -- the caller's to guarantee); max_S is a host bound on every segment's length that only
+ * sizes the grid.  Segments of length 0 write nothing.  Arithmetic and flags as fp_attention_f16_fwd: every segment gets the bits
+ * of fp_attention_f16_fwd(B=1, S=its length) on its rows. */
+int fp_attention_segments_f16_fwd(const void* qkv /*dev Ntot,3*H*hd*/, void* out /*dev Ntot,H*hd*/,
+                                  const int32_t* seg_offsets /*dev B+1*/, int B, int max_S, int H, int head_dim, int flags,
+                                  void* stream);
 
 /* mycpp/src/app/pybind_api.cpp:24-68 cluster_poses (host, init-time). Returns #kept, indices in keep_idx. */
 int fp_cluster_poses(float angle_diff_deg, float dist_diff, const float* poses /*host N,16*/, int N,
