@@ -46,6 +46,35 @@ struct fp_mesh_set {
 struct fp_k9 { float v[9]; };
 struct fp_k9d { double v[9]; };
 
+// Several views per call (the *_views entry points): hypothesis n reads frame view[n] of a (V, H, W, C) stack and the intrinsics
+// Ks[view[n]] of a (V, 9) device table (view NULL: all 0, allowed only for V == 1).  -1 = an index outside 0..V-1: the caller
+// then reads nothing from the stack or the table.
+struct fp_views {
+  const void* Ks;          // [dev V,9] f32 (render, warp, pose update) | f64 (crop windows, back-projection)
+  const int32_t* view;     // [dev N] | NULL
+  int V;
+};
+
+__device__ __forceinline__ int fp_view_of(const fp_views& vt, int n) {
+  const int v = vt.view ? vt.view[n] : 0;
+  return (unsigned)v < (unsigned)vt.V ? v : -1;
+}
+
+// The kernels take the table as a trailing parameter pack: empty for the single-view instantiations, whose signatures (and so their
+// kernel-argument layouts and instruction sequences) stay what they were; one fp_views for the *_views ones.
+__device__ __forceinline__ fp_views fp_views_of() { return fp_views{nullptr, nullptr, 0}; }
+__device__ __forceinline__ fp_views fp_views_of(const fp_views& vt) { return vt; }
+
+// K of view v (v >= 0), or all NaN (v < 0)
+template <typename KT, typename T>
+__device__ __forceinline__ KT fp_view_K(const fp_views& vt, int v) {
+  KT K;
+  const T* src = reinterpret_cast<const T*>(vt.Ks) + (size_t)(v < 0 ? 0 : v) * 9;
+#pragma unroll
+  for (int i = 0; i < 9; ++i) K.v[i] = v < 0 ? (T)__builtin_nan("") : src[i];
+  return K;
+}
+
 static inline int fp_cdiv(int a, int b) { return (a + b - 1) / b; }
 
 // hipFuncAttributeMaxDynamicSharedMemorySize is a per-device property of a kernel: set it once per (kernel, device).

@@ -4,11 +4,17 @@
 #include "fp_common.h"
 
 // ---------------------------------------------------------------- a1 (Utils.py:359-384)
+// FRAMES (the *_frames entry points): frame blockIdx.z of a (V, H, W) stack, the same arithmetic per frame
+template <bool FRAMES>
 __global__ void k_erode(const float* __restrict__ depth, float* __restrict__ out, int H, int W, int radius,
                         float diff_thres, float ratio_thres, float zfar) {
   const int w = blockIdx.x * blockDim.x + threadIdx.x;
   const int h = blockIdx.y * blockDim.y + threadIdx.y;
   if (w >= W || h >= H) return;
+  if (FRAMES) {
+    depth += (size_t)blockIdx.z * H * W;
+    out += (size_t)blockIdx.z * H * W;
+  }
   const float d0 = depth[h * W + w];
   float bad = 0.f, total = 0.f;
   for (int u = w - radius; u <= w + radius; ++u) {
@@ -24,11 +30,16 @@ __global__ void k_erode(const float* __restrict__ depth, float* __restrict__ out
 }
 
 // ---------------------------------------------------------------- a2 (Utils.py:304-343)
+template <bool FRAMES>
 __global__ void k_bilateral(const float* __restrict__ depth, float* __restrict__ out, int H, int W, int radius,
                             float zfar, float sigmaD, float sigmaR) {
   const int w = blockIdx.x * blockDim.x + threadIdx.x;
   const int h = blockIdx.y * blockDim.y + threadIdx.y;
   if (w >= W || h >= H) return;
+  if (FRAMES) {
+    depth += (size_t)blockIdx.z * H * W;
+    out += (size_t)blockIdx.z * H * W;
+  }
   float res = 0.f, mean = 0.f;
   int nvalid = 0;
   for (int u = w - radius; u <= w + radius; ++u) {
@@ -64,11 +75,23 @@ __global__ void k_bilateral(const float* __restrict__ depth, float* __restrict__
 }
 
 // ---------------------------------------------------------------- a3 (Utils.py:399-438)
-__global__ void k_depth_to_xyz(const float* __restrict__ depth, fp_k9d K, float zfar, int f64_internal,
-                               float* __restrict__ xyz, int H, int W) {
+// FRAMES (a view table in the pack, its Ks the dev (V, 9) f64 table): frame blockIdx.z with K = Ks[blockIdx.z] (a uniform
+// address: scalar loads)
+template <typename... VT>
+__global__ void k_depth_to_xyz(const float* __restrict__ depth, fp_k9d K1, float zfar, int f64_internal,
+                               float* __restrict__ xyz, int H, int W, VT... vts) {
+  constexpr bool FRAMES = sizeof...(VT) > 0;
   const int u = blockIdx.x * blockDim.x + threadIdx.x;
   const int v = blockIdx.y * blockDim.y + threadIdx.y;
   if (u >= W || v >= H) return;
+  fp_k9d K = K1;
+  if (FRAMES) {
+    const double* Ks = reinterpret_cast<const double*>(fp_views_of(vts...).Ks);
+    depth += (size_t)blockIdx.z * H * W;
+    xyz += (size_t)blockIdx.z * H * W * 3;
+#pragma unroll
+    for (int i = 0; i < 9; ++i) K.v[i] = Ks[(size_t)blockIdx.z * 9 + i];
+  }
   const float z = depth[v * W + u];
   float x = 0.f, y = 0.f, zz = 0.f;
   if (f64_internal) {
@@ -98,13 +121,17 @@ __device__ __forceinline__ double diameter_of(const double* __restrict__ diam, c
 }
 
 // MULTI: the radius of hypothesis n is diam[obj[n]] * crop_ratio / 2, the expression fp_crop_windows evaluates on the host (f64,
-// no contraction: the same bits); otherwise `radius`
-template <bool MULTI>
-__global__ void k_crop_windows(const float* __restrict__ poses, fp_k9d K, double radius1, const double* __restrict__ diam,
+// no contraction: the same bits); otherwise `radius`.  VIEWS: K of hypothesis n = the f64 table entry of view[n] (one lane per
+// hypothesis: a per-lane read); an index outside 0..V-1 gives NaN K, so NaN windows
+template <bool MULTI, typename... VT>
+__global__ void k_crop_windows(const float* __restrict__ poses, fp_k9d K1, double radius1, const double* __restrict__ diam,
                                const int32_t* __restrict__ obj, int M, double crop_ratio, int out_w, int out_h,
-                               int N, float* __restrict__ tfs, float* __restrict__ bbox) {
+                               int N, float* __restrict__ tfs, float* __restrict__ bbox, VT... vts) {
+  constexpr bool VIEWS = sizeof...(VT) > 0;
   const int n = blockIdx.x * blockDim.x + threadIdx.x;
   if (n >= N) return;
+  const fp_views vt = fp_views_of(vts...);
+  const fp_k9d K = VIEWS ? fp_view_K<fp_k9d, double>(vt, fp_view_of(vt, n)) : K1;
   const double radius = MULTI ? diameter_of(diam, obj, M, n) * crop_ratio / 2.0 : radius1;
   const float* P = poses + (size_t)n * 16;
   const double tx = (double)P[3], ty = (double)P[7], tz = (double)P[11];
@@ -144,16 +171,38 @@ __global__ void k_crop_windows(const float* __restrict__ poses, fp_k9d K, double
 // ---------------------------------------------------------------- a13 (predict_pose_refine.py:195-234)
 struct fp_f3 { float v[3]; };
 
-// MULTI: the diameter of hypothesis n is diam[obj[n]] rounded to float (as the scalar entry point's caller rounds it)
-template <bool MULTI>
+// MULTI: the diameter of hypothesis n is diam[obj[n]] rounded to float (as the scalar entry point's caller rounds it).
+// VIEWS: K (deepim) of hypothesis n = the f32 table entry of view[n]; an index outside 0..V-1 writes NaN to every output row
+template <bool MULTI, typename... VT>
 __global__ void k_pose_update(const float* __restrict__ trans, const float* __restrict__ rot,
                               const float* __restrict__ poses_in, int rot_rep, int normalize_xyz, fp_f3 tn,
                               float rot_normalizer, float mesh_diameter1, const double* __restrict__ diam,
                               const int32_t* __restrict__ obj, int M, int N, float* __restrict__ poses_out,
-                              float* __restrict__ trans_delta_out, float* __restrict__ rot_delta_out, int trans_rep, fp_k9 K,
-                              const float* __restrict__ tf_to_crops, float input_w) {
+                              float* __restrict__ trans_delta_out, float* __restrict__ rot_delta_out, int trans_rep, fp_k9 K1,
+                              const float* __restrict__ tf_to_crops, float input_w, VT... vts) {
+  constexpr bool VIEWS = sizeof...(VT) > 0;
   const int n = blockIdx.x * blockDim.x + threadIdx.x;
   if (n >= N) return;
+  const fp_views vt = fp_views_of(vts...);
+  fp_k9 K = K1;
+  if (VIEWS) {
+    const int v = fp_view_of(vt, n);
+    if (v < 0) {
+      const float nan = __builtin_nanf("");
+#pragma unroll
+      for (int k = 0; k < 16; ++k) poses_out[(size_t)n * 16 + k] = nan;
+      if (trans_delta_out) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) trans_delta_out[n * 3 + c] = nan;
+      }
+      if (rot_delta_out) {
+#pragma unroll
+        for (int c = 0; c < 9; ++c) rot_delta_out[(size_t)n * 9 + c] = nan;
+      }
+      return;
+    }
+    if (trans_rep == FP_TRANS_DEEPIM) K = fp_view_K<fp_k9, float>(vt, v);
+  }
   const float mesh_diameter = MULTI ? (float)diameter_of(diam, obj, M, n) : mesh_diameter1;
   float dt[3];
   if (trans_rep == FP_TRANS_DEEPIM) {
@@ -250,7 +299,7 @@ extern "C" int fp_depth_erode(const float* depth, float* out, int H, int W, int 
                               float ratio_thres, float zfar, void* stream) {
   FP_REQUIRE(depth && out && H > 0 && W > 0 && radius >= 0, "fp_depth_erode: bad arguments");
   dim3 b(64, 4), g(fp_cdiv(W, 64), fp_cdiv(H, 4));
-  hipLaunchKernelGGL(k_erode, g, b, 0, (hipStream_t)stream, depth, out, H, W, radius, diff_thres, ratio_thres, zfar);
+  hipLaunchKernelGGL(k_erode<false>, g, b, 0, (hipStream_t)stream, depth, out, H, W, radius, diff_thres, ratio_thres, zfar);
   FP_CHECK_LAUNCH("fp_depth_erode");
   return FP_OK;
 }
@@ -259,7 +308,7 @@ extern "C" int fp_depth_bilateral(const float* depth, float* out, int H, int W, 
                                   float sigmaD, float sigmaR, void* stream) {
   FP_REQUIRE(depth && out && H > 0 && W > 0 && radius >= 0, "fp_depth_bilateral: bad arguments");
   dim3 b(64, 4), g(fp_cdiv(W, 64), fp_cdiv(H, 4));
-  hipLaunchKernelGGL(k_bilateral, g, b, 0, (hipStream_t)stream, depth, out, H, W, radius, zfar, sigmaD, sigmaR);
+  hipLaunchKernelGGL(k_bilateral<false>, g, b, 0, (hipStream_t)stream, depth, out, H, W, radius, zfar, sigmaD, sigmaR);
   FP_CHECK_LAUNCH("fp_depth_bilateral");
   return FP_OK;
 }
@@ -270,8 +319,42 @@ extern "C" int fp_depth_to_xyz(const float* depth, const double* K, float zfar, 
   fp_k9d Kd;
   for (int i = 0; i < 9; ++i) Kd.v[i] = K[i];
   dim3 b(64, 4), g(fp_cdiv(W, 64), fp_cdiv(H, 4));
-  hipLaunchKernelGGL(k_depth_to_xyz, g, b, 0, (hipStream_t)stream, depth, Kd, zfar, f64_internal, xyz, H, W);
+  hipLaunchKernelGGL(k_depth_to_xyz<>, g, b, 0, (hipStream_t)stream, depth, Kd, zfar, f64_internal, xyz, H, W);
   FP_CHECK_LAUNCH("fp_depth_to_xyz");
+  return FP_OK;
+}
+
+// the batched ingest: one launch per stage over a (V, H, W) stack, frame f = blockIdx.z
+extern "C" int fp_depth_erode_frames(const float* depth, float* out, int H, int W, int V, int radius, float diff_thres,
+                                     float ratio_thres, float zfar, void* stream) {
+  FP_REQUIRE(V >= 1 && V <= 65535, "fp_depth_erode_frames: V=%d outside 1..65535", V);
+  FP_REQUIRE(depth && out && H > 0 && W > 0 && radius >= 0, "fp_depth_erode_frames: bad arguments");
+  dim3 b(64, 4), g(fp_cdiv(W, 64), fp_cdiv(H, 4), V);
+  hipLaunchKernelGGL(k_erode<true>, g, b, 0, (hipStream_t)stream, depth, out, H, W, radius, diff_thres, ratio_thres, zfar);
+  FP_CHECK_LAUNCH("fp_depth_erode_frames");
+  return FP_OK;
+}
+
+extern "C" int fp_depth_bilateral_frames(const float* depth, float* out, int H, int W, int V, int radius, float zfar,
+                                         float sigmaD, float sigmaR, void* stream) {
+  FP_REQUIRE(V >= 1 && V <= 65535, "fp_depth_bilateral_frames: V=%d outside 1..65535", V);
+  FP_REQUIRE(depth && out && H > 0 && W > 0 && radius >= 0, "fp_depth_bilateral_frames: bad arguments");
+  dim3 b(64, 4), g(fp_cdiv(W, 64), fp_cdiv(H, 4), V);
+  hipLaunchKernelGGL(k_bilateral<true>, g, b, 0, (hipStream_t)stream, depth, out, H, W, radius, zfar, sigmaD, sigmaR);
+  FP_CHECK_LAUNCH("fp_depth_bilateral_frames");
+  return FP_OK;
+}
+
+extern "C" int fp_depth_to_xyz_frames(const float* depth, const double* Ks, float zfar, int f64_internal, float* xyz, int H,
+                                      int W, int V, void* stream) {
+  FP_REQUIRE(V >= 1 && V <= 65535, "fp_depth_to_xyz_frames: V=%d outside 1..65535", V);
+  FP_REQUIRE(Ks, "fp_depth_to_xyz_frames: NULL K table");
+  FP_REQUIRE(depth && xyz && H > 0 && W > 0, "fp_depth_to_xyz_frames: bad arguments");
+  const fp_k9d unused = {};
+  const fp_views vt = {Ks, nullptr, V};
+  dim3 b(64, 4), g(fp_cdiv(W, 64), fp_cdiv(H, 4), V);
+  hipLaunchKernelGGL(k_depth_to_xyz<fp_views>, g, b, 0, (hipStream_t)stream, depth, unused, zfar, f64_internal, xyz, H, W, vt);
+  FP_CHECK_LAUNCH("fp_depth_to_xyz_frames");
   return FP_OK;
 }
 
@@ -305,24 +388,47 @@ extern "C" int fp_crop_windows_multi(const float* poses, const double* K, const 
   return FP_OK;
 }
 
-template <bool MULTI>
+extern "C" int fp_crop_windows_views(const float* poses, const double* Ks, const int32_t* view, int V, const double* diameters,
+                                     const int32_t* obj, int M, double crop_ratio, int out_w, int out_h, int N, float* tf_to_crops,
+                                     float* bbox2d, void* stream) {
+  FP_REQUIRE(N >= 0, "fp_crop_windows_views: N < 0");
+  FP_REQUIRE(V >= 1 && Ks, "fp_crop_windows_views: need the K table of V >= 1 views (V=%d)", V);
+  FP_REQUIRE(view || V == 1, "fp_crop_windows_views: view is NULL but there are %d views", V);
+  FP_REQUIRE(M >= 1 && diameters, "fp_crop_windows_views: need the diameters of M >= 1 objects (M=%d)", M);
+  FP_REQUIRE(obj || M == 1, "fp_crop_windows_views: obj is NULL but there are %d objects", M);
+  if (N == 0) return FP_OK;
+  FP_REQUIRE(poses && tf_to_crops && bbox2d && out_w > 1 && out_h > 1, "fp_crop_windows_views: bad arguments");
+  const fp_k9d unused = {};
+  const fp_views vt = {Ks, view, V};
+  hipLaunchKernelGGL((k_crop_windows<true, fp_views>), dim3(fp_cdiv(N, 64)), dim3(64), 0, (hipStream_t)stream, poses, unused, 0.0,
+                     diameters, obj, M, crop_ratio, out_w, out_h, N, tf_to_crops, bbox2d, vt);
+  FP_CHECK_LAUNCH("fp_crop_windows_views");
+  return FP_OK;
+}
+
+template <bool MULTI, bool VIEWS = false>
 static int pose_update_launch(const char* name, const float* trans, const float* rot, const float* poses_in, int rot_rep,
                               int normalize_xyz, const float* trans_normalizer, float rot_normalizer, float mesh_diameter,
                               const double* diam, const int32_t* obj, int M, int N, float* poses_out, float* trans_delta_out,
                               float* rot_delta_out, int trans_rep, const float* K9, const float* tf_to_crops, float input_w,
-                              void* stream) {
+                              void* stream, const fp_views& vt = fp_views{nullptr, nullptr, 0}) {
   FP_REQUIRE(trans && rot && poses_in && poses_out, "%s: NULL tensor", name);
   FP_REQUIRE(rot_rep == FP_ROT_AXIS_ANGLE || rot_rep == FP_ROT_6D, "%s: unknown rot_rep %d", name, rot_rep);
   FP_REQUIRE(trans_rep == FP_TRANS_TRACKNET || trans_rep == FP_TRANS_DEEPIM || trans_rep == FP_TRANS_RAW, "%s: unknown trans_rep %d", name, trans_rep);
-  FP_REQUIRE(trans_rep != FP_TRANS_DEEPIM || (K9 && tf_to_crops && input_w > 0.f),
+  FP_REQUIRE(trans_rep != FP_TRANS_DEEPIM || ((K9 || VIEWS) && tf_to_crops && input_w > 0.f),
              "%s: trans_rep deepim needs K, tf_to_crops and the crop width", name);
   fp_k9 Kk = {{1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 1.f}};
   if (K9) for (int i = 0; i < 9; ++i) Kk.v[i] = K9[i];
   fp_f3 tn = {{1.f, 1.f, 1.f}};
   if (trans_normalizer) { tn.v[0] = trans_normalizer[0]; tn.v[1] = trans_normalizer[1]; tn.v[2] = trans_normalizer[2]; }
-  hipLaunchKernelGGL(k_pose_update<MULTI>, dim3(fp_cdiv(N, 64)), dim3(64), 0, (hipStream_t)stream, trans, rot, poses_in,
-                     rot_rep, normalize_xyz, tn, rot_normalizer, mesh_diameter, diam, obj, M, N, poses_out, trans_delta_out,
-                     rot_delta_out, trans_rep, Kk, tf_to_crops, input_w);
+  if constexpr (VIEWS)
+    hipLaunchKernelGGL((k_pose_update<MULTI, fp_views>), dim3(fp_cdiv(N, 64)), dim3(64), 0, (hipStream_t)stream, trans, rot,
+                       poses_in, rot_rep, normalize_xyz, tn, rot_normalizer, mesh_diameter, diam, obj, M, N, poses_out,
+                       trans_delta_out, rot_delta_out, trans_rep, Kk, tf_to_crops, input_w, vt);
+  else
+    hipLaunchKernelGGL(k_pose_update<MULTI>, dim3(fp_cdiv(N, 64)), dim3(64), 0, (hipStream_t)stream, trans, rot, poses_in,
+                       rot_rep, normalize_xyz, tn, rot_normalizer, mesh_diameter, diam, obj, M, N, poses_out, trans_delta_out,
+                       rot_delta_out, trans_rep, Kk, tf_to_crops, input_w);
   FP_CHECK_LAUNCH(name);
   return FP_OK;
 }
@@ -350,4 +456,21 @@ extern "C" int fp_pose_update_multi(const float* trans, const float* rot, const 
   return pose_update_launch<true>("fp_pose_update_multi", trans, rot, poses_in, rot_rep, normalize_xyz, trans_normalizer,
                                   rot_normalizer, 0.f, diameters, obj, M, N, poses_out, trans_delta_out, rot_delta_out,
                                   trans_rep, K9, tf_to_crops, input_w, stream);
+}
+
+extern "C" int fp_pose_update_views(const float* trans, const float* rot, const float* poses_in, int rot_rep,
+                                    int normalize_xyz, const float* trans_normalizer, float rot_normalizer,
+                                    const double* diameters, const int32_t* obj, int M, int N, float* poses_out,
+                                    float* trans_delta_out, float* rot_delta_out, int trans_rep, const float* Ks,
+                                    const int32_t* view, int V, const float* tf_to_crops, float input_w, void* stream) {
+  FP_REQUIRE(N >= 0, "fp_pose_update_views: N < 0");
+  FP_REQUIRE(V >= 1 && Ks, "fp_pose_update_views: need the K table of V >= 1 views (V=%d)", V);
+  FP_REQUIRE(view || V == 1, "fp_pose_update_views: view is NULL but there are %d views", V);
+  FP_REQUIRE(M >= 1 && diameters, "fp_pose_update_views: need the diameters of M >= 1 objects (M=%d)", M);
+  FP_REQUIRE(obj || M == 1, "fp_pose_update_views: obj is NULL but there are %d objects", M);
+  if (N == 0) return FP_OK;
+  const fp_views vt = {Ks, view, V};
+  return pose_update_launch<true, true>("fp_pose_update_views", trans, rot, poses_in, rot_rep, normalize_xyz, trans_normalizer,
+                                        rot_normalizer, 0.f, diameters, obj, M, N, poses_out, trans_delta_out, rot_delta_out,
+                                        trans_rep, nullptr, tf_to_crops, input_w, stream, vt);
 }

@@ -242,11 +242,13 @@ __device__ __forceinline__ int obj_of(const MeshTable& tab, int n) {
   return (unsigned)o < (unsigned)tab.M ? o : -1;
 }
 
-template <bool MULTI>
-__device__ __forceinline__ fp_mesh mesh_of(const fp_mesh& one, const MeshTable& tab, int n) {
+// VIEWS (fp_render_crops_views, always with MULTI): hypothesis n also reads its K from entry view[n] of the (V, 9) table, with the
+// same uniform scalar loads as the descriptor; a view index outside 0..V-1 reads as an empty mesh too (nothing drawn)
+template <bool MULTI, bool VIEWS = false>
+__device__ __forceinline__ fp_mesh mesh_of(const fp_mesh& one, const MeshTable& tab, int n, const fp_views& vt = fp_views{}) {
   if (!MULTI) return one;
   const int o = obj_of(tab, n);
-  if (o < 0) {
+  if (o < 0 || (VIEWS && fp_view_of(vt, n) < 0)) {
     fp_mesh e = {};
     return e;
   }
@@ -263,16 +265,21 @@ __device__ __forceinline__ float inv_radius_of(float one, const MeshTable& tab, 
   return 1.0f / (d * 0.5f);
 }
 
-template <bool MULTI>
+template <bool MULTI, typename... VT>
 __global__ __launch_bounds__(256) void k_vertex(fp_mesh m1, MeshTable tab, const float* __restrict__ poses,
-                                                const float* __restrict__ bbox2d, fp_k9 K, int H, int W, int oh, int ow,
-                                                int nstrips, RenderWs ws) {
+                                                const float* __restrict__ bbox2d, fp_k9 K1, int H, int W, int oh, int ow,
+                                                int nstrips, RenderWs ws, VT... vts) {
+  constexpr bool VIEWS = sizeof...(VT) > 0;
+  const fp_views vt = fp_views_of(vts...);
   const int n = blockIdx.y;
   const int v = blockIdx.x * blockDim.x + threadIdx.x;
   if (blockIdx.x == 0 && threadIdx.x < nstrips) ws.counts[n * nstrips + threadIdx.x] = 0;
-  const fp_mesh m = mesh_of<MULTI>(m1, tab, n);
+  const fp_mesh m = mesh_of<MULTI, VIEWS>(m1, tab, n, vt);
   const int vstride = MULTI ? ws.vstride : m.V;
   if (v >= m.V) return;
+  fp_k9 Kv;
+  if (VIEWS) Kv = fp_view_K<fp_k9, float>(vt, fp_view_of(vt, n));
+  const fp_k9& K = VIEWS ? Kv : K1;   // single view: the kernel argument itself, as before
   const HypConst h = load_hyp(poses, bbox2d, K, n, H, W, oh, ow);
   const float vx = m.pos[v * 3], vy = m.pos[v * 3 + 1], vz = m.pos[v * 3 + 2];
   VtxAttr a;
@@ -289,11 +296,13 @@ __global__ __launch_bounds__(256) void k_vertex(fp_mesh m1, MeshTable tab, const
   ws.vr[o] = project_vertex(h, vx, vy, vz);
 }
 
-template <bool MULTI>
-__global__ __launch_bounds__(256) void k_bin(fp_mesh m1, MeshTable tab, int oh, int ow, int nstrips, RenderWs ws) {
+template <bool MULTI, typename... VT>
+__global__ __launch_bounds__(256) void k_bin(fp_mesh m1, MeshTable tab, int oh, int ow, int nstrips, RenderWs ws, VT... vts) {
+  constexpr bool VIEWS = sizeof...(VT) > 0;
+  const fp_views vt = fp_views_of(vts...);
   const int n = blockIdx.y;
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
-  const fp_mesh m = mesh_of<MULTI>(m1, tab, n);
+  const fp_mesh m = mesh_of<MULTI, VIEWS>(m1, tab, n, vt);
   const int vstride = MULTI ? ws.vstride : m.V, tstride = MULTI ? ws.tstride : m.T;
   if (MULTI && (int)(blockIdx.x * blockDim.x) >= m.T) return;   // grid sized for the set's largest mesh; uniform per workgroup
   int s0 = 1, s1 = 0;   // empty range
@@ -334,14 +343,16 @@ __global__ __launch_bounds__(256) void k_bin(fp_mesh m1, MeshTable tab, int oh, 
   }
 }
 
-template <bool MULTI>
+template <bool MULTI, typename... VT>
 __global__ __launch_bounds__(FP_RASTER_THREADS) void k_raster(
-    fp_mesh m1, MeshTable tab, const float* __restrict__ poses, const float* __restrict__ bbox2d, fp_k9 K, int H, int W, int oh,
+    fp_mesh m1, MeshTable tab, const float* __restrict__ poses, const float* __restrict__ bbox2d, fp_k9 K1, int H, int W, int oh,
     int ow, int nstrips, float w_ambient, float w_diffuse, float inv_r1, float xyz_thr, int flags, RenderOut out,
-    RenderWs ws) {
+    RenderWs ws, VT... vts) {
+  constexpr bool VIEWS = sizeof...(VT) > 0;
+  const fp_views vt = fp_views_of(vts...);
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int n = blockIdx.y, strip = blockIdx.x;
-  const fp_mesh m = mesh_of<MULTI>(m1, tab, n);
+  const fp_mesh m = mesh_of<MULTI, VIEWS>(m1, tab, n, vt);
   const int vstride = MULTI ? ws.vstride : m.V, tstride = MULTI ? ws.tstride : m.T;
   const int row0 = strip * FP_STRIP_ROWS;
   const int rows = min(FP_STRIP_ROWS, oh - row0);
@@ -453,6 +464,7 @@ __global__ __launch_bounds__(FP_RASTER_THREADS) void k_raster(
   __syncthreads();
 
   // ---- phase 2: resolve + shade + write
+  const fp_k9 K = VIEWS ? fp_view_K<fp_k9, float>(vt, fp_view_of(vt, n)) : K1;
   const HypConst h = load_hyp(poses, bbox2d, K, n, H, W, oh, ow);
   const float inv_r = inv_radius_of<MULTI>(inv_r1, tab, n);
   const size_t plane = (size_t)oh * ow;
@@ -594,13 +606,14 @@ extern "C" size_t fp_mesh_set_workspace_bytes(const fp_mesh_set* set, int N, int
   return fp_workspace_bytes(N, set->maxV, set->maxT, oh, ow);
 }
 
-// the three launches of one render, shared by fp_render_crops (MULTI = false: `one`, maxV = V, maxT = T) and
-// fp_render_crops_multi (MULTI = true: the set's table, grids sized by its largest mesh)
-template <bool MULTI>
+// the three launches of one render, shared by fp_render_crops (MULTI = false: `one`, maxV = V, maxT = T),
+// fp_render_crops_multi (MULTI = true: the set's table, grids sized by its largest mesh) and fp_render_crops_views (VIEWS = true:
+// K from the view table `vt`, K9 unused)
+template <bool MULTI, bool VIEWS = false>
 static int render_launch(const char* name, const fp_mesh& one, const MeshTable& tab, int maxV, int maxT, const float* poses,
                          const float* bbox2d, const float* K9, int H, int W, int N, int oh, int ow, float w_ambient,
                          float w_diffuse, float inv_r, float xyz_thr, int flags, const RenderOut& out, void* workspace,
-                         size_t workspace_bytes, hipStream_t st) {
+                         size_t workspace_bytes, hipStream_t st, const fp_views& vt = fp_views{nullptr, nullptr, 0}) {
   FP_REQUIRE(oh > 0 && ow > 0 && oh <= 1024 && ow <= 1024, "%s: output size %dx%d unsupported (max 1024)", name, oh, ow);
   FP_REQUIRE(bbox2d || (oh == H && ow == W), "%s: full-frame render needs oh==H and ow==W", name);
   FP_REQUIRE(N <= 65535, "%s: N=%d exceeds the grid limit; chunk the batch", name, N);
@@ -609,23 +622,34 @@ static int render_launch(const char* name, const fp_mesh& one, const MeshTable& 
     fp_set_error("%s: workspace too small (%zu < %zu bytes, see fp_workspace_bytes)", name, workspace_bytes, L.total);
     return FP_ERR_WORKSPACE;
   }
-  fp_k9 K;
-  for (int i = 0; i < 9; ++i) K.v[i] = K9[i];
+  fp_k9 K = {};
+  if (!VIEWS)
+    for (int i = 0; i < 9; ++i) K.v[i] = K9[i];
   unsigned char* w8 = (unsigned char*)workspace;
   RenderWs ws;
   ws.vr = (VtxRec*)(w8 + L.vr); ws.va = (VtxAttr*)(w8 + L.va); ws.counts = (int*)(w8 + L.counts);
   ws.lists16 = L.ids16 ? (unsigned short*)(w8 + L.lists) : nullptr;
   ws.lists32 = L.ids16 ? nullptr : (int*)(w8 + L.lists);
   ws.vstride = maxV; ws.tstride = maxT;
-  hipLaunchKernelGGL(k_vertex<MULTI>, dim3(fp_cdiv(maxV, 256), N), dim3(256), 0, st, one, tab, poses, bbox2d, K, H, W, oh, ow,
-                     L.nstrips, ws);
-  FP_CHECK_LAUNCH(MULTI ? "fp_render_crops_multi(vertex)" : "fp_render_crops(vertex)");
-  hipLaunchKernelGGL(k_bin<MULTI>, dim3(fp_cdiv(maxT, 256), N), dim3(256), 0, st, one, tab, oh, ow, L.nstrips, ws);
-  FP_CHECK_LAUNCH(MULTI ? "fp_render_crops_multi(bin)" : "fp_render_crops(bin)");
+  const dim3 gv(fp_cdiv(maxV, 256), N), gb(fp_cdiv(maxT, 256), N), gr(L.nstrips, N);
   const size_t lds = (size_t)FP_STRIP_ROWS * ow * sizeof(unsigned long long) + 16 + FP_BIG_MAX * sizeof(BigTri);
-  FP_SET_MAX_LDS(k_raster<MULTI>, 160 * 1024);
-  hipLaunchKernelGGL(k_raster<MULTI>, dim3(L.nstrips, N), dim3(FP_RASTER_THREADS), lds, st, one, tab, poses, bbox2d, K, H, W, oh,
-                     ow, L.nstrips, w_ambient, w_diffuse, inv_r, xyz_thr, flags, out, ws);
+  if constexpr (VIEWS) {
+    hipLaunchKernelGGL((k_vertex<MULTI, fp_views>), gv, dim3(256), 0, st, one, tab, poses, bbox2d, K, H, W, oh, ow, L.nstrips, ws, vt);
+    FP_CHECK_LAUNCH("fp_render_crops_views(vertex)");
+    hipLaunchKernelGGL((k_bin<MULTI, fp_views>), gb, dim3(256), 0, st, one, tab, oh, ow, L.nstrips, ws, vt);
+    FP_CHECK_LAUNCH("fp_render_crops_views(bin)");
+    FP_SET_MAX_LDS((k_raster<MULTI, fp_views>), 160 * 1024);
+    hipLaunchKernelGGL((k_raster<MULTI, fp_views>), gr, dim3(FP_RASTER_THREADS), lds, st, one, tab, poses, bbox2d, K, H, W, oh, ow,
+                       L.nstrips, w_ambient, w_diffuse, inv_r, xyz_thr, flags, out, ws, vt);
+  } else {
+    hipLaunchKernelGGL(k_vertex<MULTI>, gv, dim3(256), 0, st, one, tab, poses, bbox2d, K, H, W, oh, ow, L.nstrips, ws);
+    FP_CHECK_LAUNCH(MULTI ? "fp_render_crops_multi(vertex)" : "fp_render_crops(vertex)");
+    hipLaunchKernelGGL(k_bin<MULTI>, gb, dim3(256), 0, st, one, tab, oh, ow, L.nstrips, ws);
+    FP_CHECK_LAUNCH(MULTI ? "fp_render_crops_multi(bin)" : "fp_render_crops(bin)");
+    FP_SET_MAX_LDS(k_raster<MULTI>, 160 * 1024);
+    hipLaunchKernelGGL(k_raster<MULTI>, gr, dim3(FP_RASTER_THREADS), lds, st, one, tab, poses, bbox2d, K, H, W, oh, ow, L.nstrips,
+                       w_ambient, w_diffuse, inv_r, xyz_thr, flags, out, ws);
+  }
   FP_CHECK_LAUNCH(name);
   return FP_OK;
 }
@@ -663,4 +687,27 @@ extern "C" int fp_render_crops_multi(const fp_mesh_set* set, const int32_t* obj,
   const RenderOut out = {A, color, depth, xyz, normal, zbuf, tri_id};
   return render_launch<true>("fp_render_crops_multi", none, tab, set->maxV, set->maxT, poses, bbox2d, K9, H, W, N, oh, ow,
                              w_ambient, w_diffuse, 0.f, xyz_thr, flags, out, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+extern "C" int fp_render_crops_views(const fp_mesh_set* set, const int32_t* obj, const double* diameters, const float* Ks,
+                                     const int32_t* view, int V, const float* poses, const float* bbox2d, int H, int W, int N, int oh,
+                                     int ow, float w_ambient, float w_diffuse, float xyz_thr, int flags, void* A, float* color,
+                                     float* depth, float* xyz, float* normal, uint32_t* zbuf, int32_t* tri_id, void* workspace,
+                                     size_t workspace_bytes, void* stream) {
+  FP_REQUIRE(N >= 0, "fp_render_crops_views: N < 0");
+  FP_REQUIRE((flags & ~FP_RENDER_FLAG_MASK) == 0, "fp_render_crops_views: unknown flag bits 0x%x", flags & ~FP_RENDER_FLAG_MASK);
+  FP_REQUIRE(set, "fp_render_crops_views: NULL mesh set");
+  FP_REQUIRE(obj || set->M == 1, "fp_render_crops_views: obj is NULL but the set has %d meshes", set->M);
+  FP_REQUIRE(diameters || !(flags & FP_FLAG_NORMALIZE_XYZ), "fp_render_crops_views: FP_FLAG_NORMALIZE_XYZ needs the diameters");
+  FP_REQUIRE(V >= 1 && Ks, "fp_render_crops_views: need the K table of V >= 1 views (V=%d)", V);
+  FP_REQUIRE(view || V == 1, "fp_render_crops_views: view is NULL but there are %d views", V);
+  if (N == 0) return FP_OK;
+  FP_REQUIRE(poses, "fp_render_crops_views: NULL poses");
+  const fp_mesh none = {};
+  const MeshTable tab = {set->meshes, obj, diameters, set->M};
+  const RenderOut out = {A, color, depth, xyz, normal, zbuf, tri_id};
+  const fp_views vt = {Ks, view, V};
+  return render_launch<true, true>("fp_render_crops_views", none, tab, set->maxV, set->maxT, poses, bbox2d, nullptr, H, W, N, oh,
+                                   ow, w_ambient, w_diffuse, 0.f, xyz_thr, flags, out, workspace, workspace_bytes,
+                                   (hipStream_t)stream, vt);
 }

@@ -107,12 +107,17 @@ struct WarpConst { float cW, cH; unsigned mul_ow, shr_ow; };
 // d = diam[obj[n]] rounded to float -- the host expression of fp_warp_crops (IEEE division, no contraction: the same bits).
 struct WarpObjects { const double* diam; const int32_t* obj; int M; };
 
-template <int MODE, bool MULTI>
+// Several views (fp_warp_crops_views, VIEWS = true, always with MULTI): hypothesis n reads frame view[n] of the (V, H, W, C) stacks
+// and K = Ks[view[n]].  n = blockIdx.y, so the index and the 9 floats come in with uniform scalar loads, once per wave.  An index
+// outside 0..V-1 reads nothing: the bounds of the frame become 0 x 0, so every pixel gets what a pixel outside the frame gets.
+template <int MODE, bool MULTI, typename... VT>
 __global__ __launch_bounds__(256) void k_warp(const float* __restrict__ rgb, const float* __restrict__ xyz_map,
                                               const float* __restrict__ depthf, const float* __restrict__ tfs,
-                                              fp_k9 K, const float* __restrict__ poses, float inv_r1, int flags,
+                                              fp_k9 K1, const float* __restrict__ poses, float inv_r1, int flags,
                                               int H, int W, int oh, int ow, void* __restrict__ Bout, WarpConst wc,
-                                              WarpObjects objs) {
+                                              WarpObjects objs, VT... vts) {
+  constexpr bool VIEWS = sizeof...(VT) > 0;
+  const fp_views vt = fp_views_of(vts...);
   __shared__ float inv_tf[5];   // [4]: 1 / radius (MULTI)
   const int n = blockIdx.y;
   const float* tf = tfs + (size_t)n * 9;
@@ -138,9 +143,24 @@ __global__ __launch_bounds__(256) void k_warp(const float* __restrict__ rgb, con
   const float i00 = inv_tf[0], i11 = inv_tf[1], i02 = inv_tf[2], i12 = inv_tf[3];
   const float cW = wc.cW, cH = wc.cH;
   const float* P = poses + (size_t)n * 16;
+  fp_k9 Kv;
+  int Hv = H, Wv = W;
+  if (VIEWS) {
+    const int v = fp_view_of(vt, n);
+    Kv = fp_view_K<fp_k9, float>(vt, v);
+    if (v < 0) {
+      Hv = 0; Wv = 0;
+    } else {
+      const size_t px = (size_t)v * H * W;
+      rgb += px * 3;
+      if (MODE == FP_MODE_REFINE) xyz_map += px * 3;
+      else depthf += px;
+    }
+  }
+  const fp_k9& K = VIEWS ? Kv : K1;   // single view: the kernel argument itself, as before
   float a[6];
   warp_pixel<MODE>(rgb, xyz_map, depthf, sx, tx, sy, ty, i00, i02, i11, i12, cW, cH, K, P[3], P[7], P[11], inv_r,
-                   (flags & FP_FLAG_NORMALIZE_XYZ) != 0, H, W, oh, ow, i, j, a);
+                   (flags & FP_FLAG_NORMALIZE_XYZ) != 0, Hv, Wv, oh, ow, i, j, a);
   const size_t o = (size_t)n * 6 * npx + p;
   if (flags & FP_FLAG_OUT_F16) {
     __half* B = reinterpret_cast<__half*>(Bout);
@@ -153,18 +173,19 @@ __global__ __launch_bounds__(256) void k_warp(const float* __restrict__ rgb, con
   }
 }
 
-template <bool MULTI>
+template <bool MULTI, bool VIEWS = false>
 static int warp_launch(const char* name, const float* rgb, const float* xyz_map, const float* depth, const float* tf_to_crops,
                        const float* K9, const float* poses, float inv_r, const WarpObjects& objs, int flags, int mode, int H,
-                       int W, int N, int oh, int ow, void* B, void* stream) {
-  FP_REQUIRE(rgb && tf_to_crops && K9 && poses && B, "%s: NULL tensor", name);
+                       int W, int N, int oh, int ow, void* B, void* stream, const fp_views& vt = fp_views{nullptr, nullptr, 0}) {
+  FP_REQUIRE(rgb && tf_to_crops && (K9 || VIEWS) && poses && B, "%s: NULL tensor", name);
   FP_REQUIRE(H > 1 && W > 1 && oh > 1 && ow > 1, "%s: degenerate sizes", name);
   FP_REQUIRE(N <= 65535, "%s: N=%d exceeds the grid limit; chunk the batch", name, N);
   FP_REQUIRE(mode == FP_MODE_REFINE || mode == FP_MODE_SCORE, "%s: unknown mode %d", name, mode);
   FP_REQUIRE(mode != FP_MODE_REFINE || xyz_map, "%s: REFINE mode needs xyz_map", name);
   FP_REQUIRE(mode != FP_MODE_SCORE || depth, "%s: SCORE mode needs depth", name);
-  fp_k9 K;
-  for (int i = 0; i < 9; ++i) K.v[i] = K9[i];
+  fp_k9 K = {};
+  if (!VIEWS)
+    for (int i = 0; i < 9; ++i) K.v[i] = K9[i];
   dim3 grid(fp_cdiv(oh * ow, 256), N), block(256);
   WarpConst wc;
   wc.cW = (float)W / (float)(W - 1);
@@ -179,12 +200,20 @@ static int warp_launch(const char* name, const float* rgb, const float* xyz_map,
       wc.shr_ow = (unsigned)(sh - 32);
     }
   }
-  if (mode == FP_MODE_REFINE)
+  if constexpr (VIEWS) {
+    if (mode == FP_MODE_REFINE)
+      hipLaunchKernelGGL((k_warp<FP_MODE_REFINE, MULTI, fp_views>), grid, block, 0, (hipStream_t)stream, rgb, xyz_map, depth,
+                         tf_to_crops, K, poses, inv_r, flags, H, W, oh, ow, B, wc, objs, vt);
+    else
+      hipLaunchKernelGGL((k_warp<FP_MODE_SCORE, MULTI, fp_views>), grid, block, 0, (hipStream_t)stream, rgb, xyz_map, depth,
+                         tf_to_crops, K, poses, inv_r, flags, H, W, oh, ow, B, wc, objs, vt);
+  } else if (mode == FP_MODE_REFINE) {
     hipLaunchKernelGGL((k_warp<FP_MODE_REFINE, MULTI>), grid, block, 0, (hipStream_t)stream, rgb, xyz_map, depth, tf_to_crops,
                        K, poses, inv_r, flags, H, W, oh, ow, B, wc, objs);
-  else
+  } else {
     hipLaunchKernelGGL((k_warp<FP_MODE_SCORE, MULTI>), grid, block, 0, (hipStream_t)stream, rgb, xyz_map, depth, tf_to_crops,
                        K, poses, inv_r, flags, H, W, oh, ow, B, wc, objs);
+  }
   FP_CHECK_LAUNCH(name);
   return FP_OK;
 }
@@ -210,4 +239,22 @@ extern "C" int fp_warp_crops_multi(const float* rgb, const float* xyz_map, const
   const WarpObjects objs = {diameters, obj, M};
   return warp_launch<true>("fp_warp_crops_multi", rgb, xyz_map, depth, tf_to_crops, K9, poses, 0.f, objs, flags, mode, H, W,
                            N, oh, ow, B, stream);
+}
+
+extern "C" int fp_warp_crops_views(const float* rgb, const float* xyz_map, const float* depth, const float* tf_to_crops,
+                                   const float* Ks, const int32_t* view, int V, const float* poses, const double* diameters,
+                                   const int32_t* obj, int M, int flags, int mode, int H, int W, int N, int oh, int ow, void* B,
+                                   void* stream) {
+  FP_REQUIRE(N >= 0, "fp_warp_crops_views: N < 0");
+  FP_REQUIRE((flags & ~(FP_FLAG_NORMALIZE_XYZ | FP_FLAG_OUT_F16)) == 0, "fp_warp_crops_views: unknown flag bits 0x%x",
+             flags & ~(FP_FLAG_NORMALIZE_XYZ | FP_FLAG_OUT_F16));
+  FP_REQUIRE(V >= 1 && Ks, "fp_warp_crops_views: need the K table of V >= 1 views (V=%d)", V);
+  FP_REQUIRE(view || V == 1, "fp_warp_crops_views: view is NULL but there are %d views", V);
+  FP_REQUIRE(M >= 1 && diameters, "fp_warp_crops_views: need the diameters of M >= 1 objects (M=%d)", M);
+  FP_REQUIRE(obj || M == 1, "fp_warp_crops_views: obj is NULL but there are %d objects", M);
+  if (N == 0) return FP_OK;
+  const WarpObjects objs = {diameters, obj, M};
+  const fp_views vt = {Ks, view, V};
+  return warp_launch<true, true>("fp_warp_crops_views", rgb, xyz_map, depth, tf_to_crops, nullptr, poses, 0.f, objs, flags, mode,
+                                 H, W, N, oh, ow, B, stream, vt);
 }

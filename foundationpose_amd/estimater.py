@@ -257,6 +257,63 @@ def track_objects(estimators, rgb, depth, K, iteration=2):
     return poses
 
 
+def _frame_hw(f):
+    return tuple(f.shape[:2]) if torch.is_tensor(f) else tuple(np.asarray(f).shape[:2])
+
+
+def track_views(estimators, views, rgbs, depths, Ks, iteration=2):
+    """track_one for objects in several camera frames at once: estimator k is tracked on frame views[k] (rgbs[v], depths[v] with
+    intrinsics Ks[v]), all in ONE batched refine loop over one hypothesis per estimator, replayed as captured hipGraphs
+    (graphs.GraphedTracker with views) on one batched depth ingest of all frames.  Per estimator the result is what its own track_one
+    on its frame computes; two estimators may share a mesh (one object seen by two cameras, each pose in its own camera's frame).
+    Every estimator must be registered, listed once, and all must share ONE refiner object; the frames must have one size.  The
+    captured tracker is cached on that refiner, like track_objects'.  -> [4x4 np.ndarray] per estimator, in its original mesh
+    frame; updates each pose_last."""
+    ests = list(estimators)
+    if not ests:
+        raise ValueError("track_views: no estimators")
+    views = [int(v) for v in views]
+    if len(views) != len(ests):
+        raise ValueError(f"track_views: {len(ests)} estimators but {len(views)} view indices")
+    rgbs, depths, Ks = list(rgbs), list(depths), list(Ks)
+    V = len(depths)
+    if V < 1 or len(rgbs) != V or len(Ks) != V:
+        raise ValueError(f"track_views: {len(rgbs)} rgb frames, {V} depth frames and {len(Ks)} intrinsics: need one of each per view")
+    for i, v in enumerate(views):
+        if not 0 <= v < V:
+            raise ValueError(f"track_views: estimator {i} views frame {v}, outside 0..{V - 1}")
+    hws = {_frame_hw(f) for f in rgbs + depths}
+    if len(hws) != 1:
+        raise ValueError(f"track_views: the frames differ in size {sorted(hws)}; all views must have one H x W")
+    for i, e in enumerate(ests):
+        if e.pose_last is None:
+            raise RuntimeError(f"track_views: estimator {i} is not registered (call register first)")
+    refiner = ests[0].refiner
+    if any(e.refiner is not refiner for e in ests):
+        raise ValueError("track_views: the estimators must share one refiner object (FoundationPose(..., refiner=shared))")
+    if len({id(e) for e in ests}) != len(ests):
+        raise ValueError("track_views: an estimator is listed twice")
+    dev = ests[0].device
+    hw = hws.pop()
+    Kb = b"".join(np.asarray(K, dtype=np.float64).reshape(9).tobytes() for K in Ks)
+    key = (tuple((id(e), id(e.mesh_tensors)) for e in ests), tuple(views), hw, Kb, int(iteration))
+    cached = getattr(refiner, "_views_tracker", None)
+    if cached is None or cached[0] != key:
+        from .graphs import GraphedTracker
+        trk = GraphedTracker(refiner, [e.mesh_tensors for e in ests], [e.diameter for e in ests], Ks, hw[0], hw[1], n_hyp=1,
+                             iteration=iteration, device=dev, views=views).capture()
+        # the entry keeps the estimators and their mesh dicts alive, so the ids of its key cannot be reused while it is cached
+        cached = refiner._views_tracker = (key, trk, ests, [e.mesh_tensors for e in ests])
+    trk = cached[1]
+    start = torch.stack([e.pose_last.reshape(4, 4).to(dev, torch.float32) for e in ests])
+    out = trk.step(rgbs, depths, start).clone()
+    poses = []
+    for k, e in enumerate(ests):
+        e.pose_last = out[k:k + 1]
+        poses.append((out[k] @ e.get_tf_to_centered_mesh()).data.cpu().numpy().reshape(4, 4))
+    return poses
+
+
 def _object_tables(refiner, ests):
     """the MeshSet and diameter table of `ests`' objects, cached on the shared refiner like track_objects' tracker, under the
     estimators and their mesh tensors"""

@@ -128,32 +128,51 @@ class GraphedTracker:
     Several objects per frame: mesh_tensors and mesh_diameter are lists (one entry per object) and every object has `n_hyp`
     hypotheses, so a frame refines N = M x n_hyp poses in ONE batched loop -- rows [k n_hyp, (k+1) n_hyp) of poses_in / poses_out
     are object k's -- on one shared depth ingest (ops.MeshSet, predict_pose_refine.ObjectIndex).  A list of one mesh is the same
-    loop for one object."""
+    loop for one object.
 
-    def __init__(self, refiner, mesh_tensors, mesh_diameter, K, H, W, n_hyp=1, iteration=2, device=None):
+    Several camera frames per step: K = [K_0 .. K_{V-1}] (one intrinsics matrix per view, all frames H x W) and views = [v_0 ..
+    v_{M-1}] (object k lives in view views[k]; the meshes are a list).  The static inputs are then (V,H,W,3) / (V,H,W) frame stacks,
+    the pre-graph is the batched ingest (three launches for all views, ops.ingest_frames) and the refine loop reads hypothesis n's
+    frame and K through an ops.Views; step() takes the V frames as lists or stacked tensors.  Without views nothing changes."""
+
+    def __init__(self, refiner, mesh_tensors, mesh_diameter, K, H, W, n_hyp=1, iteration=2, device=None, views=None):
         self.refiner = refiner
         self.multi = isinstance(mesh_tensors, (list, tuple))
+        if views is not None and not self.multi:
+            raise ValueError("GraphedTracker: views need a list of meshes (one per object)")
         if self.multi:
             from .predict_pose_refine import ObjectIndex
             if len(mesh_tensors) < 1 or len(mesh_diameter) != len(mesh_tensors):
                 raise ValueError(f"GraphedTracker: {len(mesh_tensors)} meshes and {len(mesh_diameter)} diameters")
+            if views is not None and len(views) != len(mesh_tensors):
+                raise ValueError(f"GraphedTracker: {len(mesh_tensors)} meshes and {len(views)} view indices")
             self.M = len(mesh_tensors)
             self.handle = ops.MeshSet([get_mesh_handle(m) for m in mesh_tensors])
         else:
             self.M = 1
             self.handle = get_mesh_handle(mesh_tensors)
         self.dev = torch.device(device) if device is not None else self.handle.device
-        self.K = np.asarray(K, dtype=np.float64).copy()
         self.H, self.W, self.N, self.R = int(H), int(W), int(n_hyp) * self.M, int(iteration)
         self.n_hyp = int(n_hyp)
+        self.views = None
+        if views is not None:
+            self.K = [np.asarray(k, dtype=np.float64).reshape(3, 3).copy() for k in K]
+            self.V = len(self.K)
+            vh = np.repeat(np.asarray(views, dtype=np.int64).reshape(-1), self.n_hyp)
+            self.views = ops.Views(self.K, vh, self.dev)       # refuses an index outside 0..V-1
+        else:
+            self.K = np.asarray(K, dtype=np.float64).copy()
+            self.V = 1
         if self.multi:
             self.diameter = ops.object_diameters(mesh_diameter, self.dev)
-            self.obj = ObjectIndex(np.repeat(np.arange(self.M), self.n_hyp), self.dev)
+            self.obj = ObjectIndex(np.repeat(np.arange(self.M), self.n_hyp), self.dev,
+                                   view=None if self.views is None else self.views.host)
         else:
             self.diameter = float(mesh_diameter)
             self.obj = None
-        self.rgb = torch.zeros((H, W, 3), dtype=torch.float32, device=self.dev)
-        self.depth = torch.zeros((H, W), dtype=torch.float32, device=self.dev)
+        fr = () if self.views is None else (self.V,)
+        self.rgb = torch.zeros(fr + (H, W, 3), dtype=torch.float32, device=self.dev)
+        self.depth = torch.zeros(fr + (H, W), dtype=torch.float32, device=self.dev)
         self.poses_in = torch.eye(4, device=self.dev).repeat(self.N, 1, 1).contiguous()
         # everything the captured kernels address by raw pointer and that is not allocated inside a capture belongs to
         # the tracker: the outputs and one rasteriser scratch per part here, the encoder's activation sets by
@@ -172,12 +191,14 @@ class GraphedTracker:
         self._have_output = False
 
     def _pre(self):
+        if self.views is not None:
+            return ops.ingest_frames(self.depth, self.views, f64_internal=False)
         d = ops.bilateral_filter_depth(ops.erode_depth(self.depth, radius=2), radius=2)
         return ops.depth_to_xyz(d, self.K, zfar=float("inf"), f64_internal=False)     # depth2xyzmap_batch variant
 
     def _part(self, h, xyz):
         self.refiner.refine_part(h, self.parts[h], self.rgb, xyz, self.poses_in, self.K, self.H, self.W, self.handle,
-                                 self.diameter, range(self.R), self.outs, self.workspace[h], obj=self.obj)
+                                 self.diameter, range(self.R), self.outs, self.workspace[h], obj=self.obj, views=self.views)
 
     def _body(self, xyz=None):
         """the frame without graphs: same launches, same streams (xyz given: the refine loop alone, on that map)"""
@@ -231,12 +252,23 @@ class GraphedTracker:
             self.poses_out.copy_(self.poses_in)
         return self.poses_out
 
+    def _upload(self, dst, frames, what, non_blocking):
+        """one frame, or with views the V frames as a list / a stacked tensor or array, into the static input `dst`"""
+        if self.views is not None and isinstance(frames, (list, tuple)):
+            if len(frames) != self.V:
+                raise ValueError(f"GraphedTracker: {self.V} views but {len(frames)} {what} frames")
+            for v, f in enumerate(frames):
+                dst[v].copy_(torch.as_tensor(f, device=self.dev), non_blocking=non_blocking)
+        else:
+            dst.copy_(torch.as_tensor(frames, device=self.dev), non_blocking=non_blocking)
+
     @torch.inference_mode()
     def step(self, rgb, depth, poses=None):
+        """rgb / depth: the frame, or with views the V frames (lists or stacked (V,H,W,3) / (V,H,W))"""
         if self.g_pre is None:
             self.capture()
-        self.rgb.copy_(torch.as_tensor(rgb, device=self.dev), non_blocking=True)
-        self.depth.copy_(torch.as_tensor(depth, device=self.dev), non_blocking=True)
+        self._upload(self.rgb, rgb, "rgb", True)
+        self._upload(self.depth, depth, "depth", True)
         if poses is not None:
             self.poses_in.copy_(torch.as_tensor(poses, device=self.dev, dtype=torch.float32).reshape(self.N, 4, 4))
         elif self._have_output:
@@ -249,8 +281,8 @@ class GraphedTracker:
     @torch.inference_mode()
     def step_eager(self, rgb, depth, poses):
         """the same frame without the graphs (for A/B timing and the equality test)"""
-        self.rgb.copy_(torch.as_tensor(rgb, device=self.dev))
-        self.depth.copy_(torch.as_tensor(depth, device=self.dev))
+        self._upload(self.rgb, rgb, "rgb", False)
+        self._upload(self.depth, depth, "depth", False)
         self.poses_in.copy_(torch.as_tensor(poses, device=self.dev, dtype=torch.float32).reshape(self.N, 4, 4))
         return self._body()
 
@@ -269,6 +301,8 @@ class FramePipeline:
     never starts before frame f is complete (one compute stream order): a tracker's hypotheses depend on the previous pose."""
 
     def __init__(self, tracker, slots=2):
+        if getattr(tracker, "views", None) is not None:
+            raise ValueError("FramePipeline: the tracker spans several views; pipelining views is not supported (use its step())")
         if tracker.g_pre is None:
             tracker.capture()
         t = self.trk = tracker

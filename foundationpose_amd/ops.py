@@ -142,6 +142,91 @@ def _objects(mesh_diameter, obj, what):
     return d, o, M
 
 
+class PairRows:
+    """The rows of the reference's two-pose quirk in one call (predict_pose_refine.two_pose_pairs) as a device table, built once from
+    host data so a captured refine loop copies nothing.  pairs: sorted [(i, j)]"""
+
+    def __init__(self, pairs, device):
+        self.pairs = list(pairs)
+        self._pairs_dev = torch.as_tensor(np.asarray(self.pairs, dtype=np.int64).reshape(-1, 2), device=device)
+        self._first = np.asarray([i for i, _ in self.pairs], dtype=np.int64)
+
+    def pair_rows(self, a, b):
+        """(P, 2) device rows of the quirk pairs inside rows a..b, relative to a; None when there are none (parts_for_pairs keeps a
+        pair from straddling two parts)"""
+        k0, k1 = int(np.searchsorted(self._first, a)), int(np.searchsorted(self._first, b))
+        if k0 == k1:
+            return None
+        return self._pairs_dev[k0:k1] - a
+
+
+class Views:
+    """The view table of a call over several camera frames of one size (the *_views entry points): hypothesis n reads frame view[n]
+    of the frame stacks and the intrinsics Ks[view[n]].  Built once from host data, like predict_pose_refine.ObjectIndex and Segments:
+    the (V, 9) K tables in float64 (crop windows, back-projection) and float32 (render, warp, pose update) -- exactly the values the
+    single-view paths pass from the host -- and the int32 device index (None for one view without an index: all hypotheses view 0).
+    `pairs` / pair_rows: the two-pose quirk grouped per view (every hypothesis one object; with several objects the ObjectIndex built
+    with view=... carries the (view, object) grouping)."""
+
+    def __init__(self, Ks, view, device):
+        Ks = [np.asarray(K, dtype=np.float64).reshape(-1) for K in Ks]
+        if not Ks:
+            raise _lib.FpAmdError("Views: no intrinsics (need V >= 1)")
+        if any(K.size != 9 for K in Ks):
+            raise _lib.FpAmdError("Views: every K must be a 3x3 matrix")
+        self.V = len(Ks)
+        if view is None:
+            if self.V > 1:
+                raise _lib.FpAmdError(f"Views: {self.V} views need a per-hypothesis view index")
+            self.host = None
+        else:
+            self.host = np.asarray(view, dtype=np.int64).reshape(-1)
+            if self.host.size and (self.host.min() < 0 or self.host.max() >= self.V):
+                raise _lib.FpAmdError(f"Views: view index outside 0..{self.V - 1}")
+        self.device = torch.device(device)
+        self.K64 = torch.as_tensor(np.stack([_hostK64(K) for K in Ks]), device=self.device)
+        self.K32 = torch.as_tensor(np.stack([_hostK32(K) for K in Ks]), device=self.device)
+        self.dev = None if self.host is None else torch.as_tensor(self.host.astype(np.int32), device=self.device)
+        self._rows = None
+        if self.host is not None:
+            from .predict_pose_refine import two_pose_pairs
+            self._rows = PairRows(two_pose_pairs(np.zeros_like(self.host), self.host), self.device)
+
+    def __len__(self):
+        return 0 if self.host is None else int(self.host.size)
+
+    @property
+    def pairs(self):
+        return [] if self._rows is None else self._rows.pairs
+
+    def pair_rows(self, a, b):
+        return None if self._rows is None else self._rows.pair_rows(a, b)
+
+    def rows(self, a, b):
+        """the table for hypotheses a..b of the call (shares the K tables; the index is a slice: nothing is copied)"""
+        v = object.__new__(Views)
+        v.__dict__.update(self.__dict__)
+        v.host = None if self.host is None else self.host[a:b]
+        v.dev = None if self.dev is None else self.dev[a:b]
+        v._rows = None
+        return v
+
+
+def _views(views, what, N=None):
+    if not isinstance(views, Views):
+        raise _lib.FpAmdError(f"{what}: views must be an ops.Views")
+    if N is not None and views.dev is not None and int(views.dev.numel()) != N:
+        raise _lib.FpAmdError(f"{what}: {N} hypotheses but a view index of {views.dev.numel()}")
+    return views
+
+
+def _objects_views(mesh_diameter, obj, what):
+    objs = _objects(mesh_diameter, obj, what)
+    if objs is None:
+        raise _lib.FpAmdError(f"{what}: views need the per-object diameter table (object_diameters), not a scalar")
+    return objs
+
+
 def erode_depth(depth, radius=2, depth_diff_thres=0.001, ratio_thres=0.8, zfar=100.0):
     d = _dev(depth, torch.float32, "depth")
     out = torch.empty_like(d)
@@ -170,13 +255,68 @@ def depth_to_xyz(depth, K, zfar=float("inf"), f64_internal=False):
     return out
 
 
-def crop_windows(poses, K, mesh_diameter, crop_ratio, out_size=(160, 160), obj=None):
+def _frames(t, what, ndim):
+    d = _dev(t, torch.float32, what)
+    if d.dim() != ndim:
+        raise _lib.FpAmdError(f"{what}: expected a {ndim}-d frame stack, got shape {tuple(d.shape)}")
+    return d
+
+
+def erode_depth_frames(depth, radius=2, depth_diff_thres=0.001, ratio_thres=0.8, zfar=100.0):
+    """erode_depth on every frame of a (V,H,W) stack, one launch (fp_depth_erode_frames)"""
+    d = _frames(depth, "depth", 3)
+    out = torch.empty_like(d)
+    V, H, W = d.shape
+    _lib.check(_lib.lib().fp_depth_erode_frames(_ptr(d), _ptr(out), H, W, V, int(radius), depth_diff_thres, ratio_thres, zfar,
+                                                _stream(d)), "fp_depth_erode_frames")
+    return out
+
+
+def bilateral_filter_depth_frames(depth, radius=2, zfar=100.0, sigmaD=2.0, sigmaR=100000.0):
+    """bilateral_filter_depth on every frame of a (V,H,W) stack, one launch (fp_depth_bilateral_frames)"""
+    d = _frames(depth, "depth", 3)
+    out = torch.empty_like(d)
+    V, H, W = d.shape
+    _lib.check(_lib.lib().fp_depth_bilateral_frames(_ptr(d), _ptr(out), H, W, V, int(radius), zfar, sigmaD, sigmaR, _stream(d)),
+               "fp_depth_bilateral_frames")
+    return out
+
+
+def depth_to_xyz_frames(depth, views, zfar=float("inf"), f64_internal=False):
+    """depth_to_xyz of frame v of a (V,H,W) stack with K = views' K v (fp_depth_to_xyz_frames) -> (V,H,W,3)"""
+    d = _frames(depth, "depth", 3)
+    vt = _views(views, "depth_to_xyz_frames")
+    V, H, W = d.shape
+    if V != vt.V:
+        raise _lib.FpAmdError(f"depth_to_xyz_frames: {V} frames but {vt.V} views")
+    out = torch.empty((V, H, W, 3), dtype=torch.float32, device=d.device)
+    _lib.check(_lib.lib().fp_depth_to_xyz_frames(_ptr(d), _ptr(vt.K64), float(zfar), int(bool(f64_internal)), _ptr(out), H, W, V,
+                                                 _stream(d)), "fp_depth_to_xyz_frames")
+    return out
+
+
+def ingest_frames(depth, views, f64_internal=False):
+    """the tracking ingest (erode -> bilateral -> back-projection, estimater.py:255-257) of a (V,H,W) depth stack in three launches
+    -> xyz (V,H,W,3)"""
+    d = bilateral_filter_depth_frames(erode_depth_frames(depth, radius=2), radius=2)
+    return depth_to_xyz_frames(d, views, zfar=float("inf"), f64_internal=f64_internal)
+
+
+def crop_windows(poses, K, mesh_diameter, crop_ratio, out_size=(160, 160), obj=None, views=None):
     """-> tf_to_crops (N,3,3) f32, bbox2d (N,4) f32.  out_size = (width, height).  Several objects: mesh_diameter = the (M,)
-    table of object_diameters, obj = the per-hypothesis object index (fp_crop_windows_multi)."""
+    table of object_diameters, obj = the per-hypothesis object index (fp_crop_windows_multi).  Several views: views = an ops.Views
+    (K unused; fp_crop_windows_views)."""
     P = _dev(poses, torch.float32, "poses")
     N = int(P.shape[0])
     tf = torch.empty((N, 3, 3), dtype=torch.float32, device=P.device)
     bb = torch.empty((N, 4), dtype=torch.float32, device=P.device)
+    if views is not None:
+        vt = _views(views, "crop_windows", N)
+        d, o, M = _objects_views(mesh_diameter, obj, "crop_windows")
+        _lib.check(_lib.lib().fp_crop_windows_views(_ptr(P), _ptr(vt.K64), _ptr(vt.dev), vt.V, _ptr(d), _ptr(o), M, float(crop_ratio),
+                                                    int(out_size[0]), int(out_size[1]), N, _ptr(tf), _ptr(bb), _stream(P)),
+                   "fp_crop_windows_views")
+        return tf, bb
     Kd = _hostK64(K)
     objs = _objects(mesh_diameter, obj, "crop_windows")
     if objs is None:
@@ -220,12 +360,15 @@ def _workspace(nbytes, device):
 
 def render_crops(mesh, poses, bbox2d, K, H, W, out_hw=(160, 160), mesh_diameter=1.0, xyz_thr=0.001,
                  normalize_xyz=True, out_f16=False, w_ambient=0.8, w_diffuse=0.5,
-                 want=("A",), A_out=None, workspace=None, obj=None):
+                 want=("A",), A_out=None, workspace=None, obj=None, views=None):
     """Fused render of N hypotheses (see fp_render_crops).  Returns dict of requested outputs.  workspace: caller-owned
     uint8 scratch of at least workspace_bytes(...) bytes (a captured hipGraph must own its scratch); default: a
     per-device scratch that grows on demand.  Several objects: mesh = a MeshSet, obj = the per-hypothesis object index, mesh_diameter =
-    the (M,) table of object_diameters (fp_render_crops_multi: hypothesis n draws mesh obj[n])."""
+    the (M,) table of object_diameters (fp_render_crops_multi: hypothesis n draws mesh obj[n]).  Several views: views = an ops.Views
+    with a MeshSet (K unused; fp_render_crops_views: hypothesis n projects with K view[n])."""
     multi = isinstance(mesh, MeshSet)
+    if views is not None and not multi:
+        raise _lib.FpAmdError("render_crops: views need a MeshSet")
     if multi:
         d, o, M = _objects(mesh_diameter, obj, "render_crops") or (None, None, 0)
         if d is None or M != mesh.M:
@@ -264,8 +407,15 @@ def render_crops(mesh, poses, bbox2d, K, H, W, out_hw=(160, 160), mesh_diameter=
             raise _lib.FpAmdError(f"render_crops: workspace has {ws.numel()} bytes, {need} needed")
     else:
         ws = _workspace(need, dev)
-    K9 = _hostK32(K)
+    K9 = _hostK32(K) if views is None else None
     flags = (FLAG_NORMALIZE_XYZ if normalize_xyz else 0) | (FLAG_OUT_F16 if (A is not None and A.dtype == torch.float16) else 0)
+    if views is not None:
+        vt = _views(views, "render_crops", N)
+        st = L.fp_render_crops_views(mesh.handle, _ptr(o), _ptr(d), _ptr(vt.K32), _ptr(vt.dev), vt.V, _ptr(P), _ptr(bb), int(H), int(W),
+                                     N, oh, ow, w_ambient, w_diffuse, xyz_thr, flags, _ptr(A), _ptr(color), _ptr(depth), _ptr(xyz),
+                                     _ptr(normal), _ptr(zbuf), _ptr(tri), _ptr(ws), 0 if ws is None else ws.numel(), _stream(P))
+        _lib.check(st, "fp_render_crops_views")
+        return outs
     if multi:
         st = L.fp_render_crops_multi(mesh.handle, _ptr(o), _ptr(d), _ptr(P), _ptr(bb), K9.ctypes.data_as(C.c_void_p), int(H), int(W),
                                      N, oh, ow, w_ambient, w_diffuse, xyz_thr, flags, _ptr(A), _ptr(color), _ptr(depth), _ptr(xyz),
@@ -281,11 +431,12 @@ def render_crops(mesh, poses, bbox2d, K, H, W, out_hw=(160, 160), mesh_diameter=
 
 
 def warp_crops(rgb, xyz_map, depth, tf_to_crops, K, poses, mesh_diameter, mode, normalize_xyz=True, out_f16=False,
-               out_hw=(160, 160), B_out=None, obj=None):
+               out_hw=(160, 160), B_out=None, obj=None, views=None):
     """fp_warp_crops.  Several objects: mesh_diameter = the (M,) table of object_diameters, obj = the per-hypothesis object
-    index (fp_warp_crops_multi)."""
+    index (fp_warp_crops_multi).  Several views: views = an ops.Views, rgb / xyz_map / depth = (V,H,W,3) / (V,H,W,3) / (V,H,W) frame
+    stacks (K unused; fp_warp_crops_views)."""
     rgbf = _dev(rgb, torch.float32, "rgb")
-    H, W = int(rgbf.shape[0]), int(rgbf.shape[1])
+    H, W = (int(rgbf.shape[0]), int(rgbf.shape[1])) if views is None else (int(rgbf.shape[1]), int(rgbf.shape[2]))
     xm = _dev(xyz_map, torch.float32, "xyz_map")
     dp = _dev(depth, torch.float32, "depth")
     tf = _dev(tf_to_crops, torch.float32, "tf_to_crops")
@@ -295,6 +446,15 @@ def warp_crops(rgb, xyz_map, depth, tf_to_crops, K, poses, mesh_diameter, mode, 
     B = B_out if B_out is not None else torch.empty((N, 6, oh, ow), dtype=torch.float16 if out_f16 else torch.float32,
                                                     device=P.device)
     flags = (FLAG_NORMALIZE_XYZ if normalize_xyz else 0) | (FLAG_OUT_F16 if B.dtype == torch.float16 else 0)
+    if views is not None:
+        vt = _views(views, "warp_crops", N)
+        if rgbf.dim() != 4 or int(rgbf.shape[0]) != vt.V:
+            raise _lib.FpAmdError(f"warp_crops: views need a ({vt.V},H,W,3) rgb stack, got {tuple(rgbf.shape)}")
+        d, o, M = _objects_views(mesh_diameter, obj, "warp_crops")
+        st = _lib.lib().fp_warp_crops_views(_ptr(rgbf), _ptr(xm), _ptr(dp), _ptr(tf), _ptr(vt.K32), _ptr(vt.dev), vt.V, _ptr(P), _ptr(d),
+                                            _ptr(o), M, flags, int(mode), H, W, N, oh, ow, _ptr(B), _stream(P))
+        _lib.check(st, "fp_warp_crops_views")
+        return B
     K9 = _hostK32(K)
     objs = _objects(mesh_diameter, obj, "warp_crops")
     if objs is not None:
@@ -311,10 +471,11 @@ def warp_crops(rgb, xyz_map, depth, tf_to_crops, K, poses, mesh_diameter, mode, 
 
 def pose_update(trans, rot, poses, rot_rep="axis_angle", normalize_xyz=True, trans_normalizer=(1.0, 1.0, 1.0),
                 rot_normalizer=1.0, mesh_diameter=1.0, out=None, trans_delta_out=None, rot_delta_out=None, trans_rep="tracknet",
-                K=None, tf_to_crops=None, input_w=0, obj=None):
+                K=None, tf_to_crops=None, input_w=0, obj=None, views=None):
     """fp_pose_update.  trans_rep='deepim' needs K, tf_to_crops (N,3,3) and the crop width (predict_pose_refine.py:201-215);
     any trans_rep other than 'tracknet' / 'deepim' is the reference's plain `else` branch (:217-218): the raw output.  Several
-    objects: mesh_diameter = the (M,) table of object_diameters, obj = the per-hypothesis object index (fp_pose_update_multi)"""
+    objects: mesh_diameter = the (M,) table of object_diameters, obj = the per-hypothesis object index (fp_pose_update_multi).  Several
+    views: views = an ops.Views (K unused; fp_pose_update_views)"""
     tr = _dev(trans, torch.float32, "trans")
     ro = _dev(rot, torch.float32, "rot")
     P = _dev(poses, torch.float32, "poses")
@@ -328,9 +489,19 @@ def pose_update(trans, rot, poses, rot_rep="axis_angle", normalize_xyz=True, tra
     tn = np.ascontiguousarray(np.broadcast_to(np.asarray(trans_normalizer, dtype=np.float32).reshape(-1), (3,)))
     O = out if out is not None else torch.empty_like(P)
     deepim = trans_rep == "deepim"
-    K9 = _hostK32(K) if deepim else None
+    K9 = _hostK32(K) if deepim and views is None else None
     tf = _dev(tf_to_crops, torch.float32, "tf_to_crops") if deepim else None
     tro = TRANS_DEEPIM if deepim else (TRANS_TRACKNET if trans_rep == "tracknet" else TRANS_RAW)
+    if views is not None:
+        vt = _views(views, "pose_update", N)
+        d, o, M = _objects_views(mesh_diameter, obj, "pose_update")
+        st = _lib.lib().fp_pose_update_views(_ptr(tr), _ptr(ro), _ptr(P), rr, int(bool(normalize_xyz)), tn.ctypes.data_as(C.c_void_p),
+                                             float(rot_normalizer), _ptr(d), _ptr(o), M, N, _ptr(O),
+                                             _ptr(_dev(trans_delta_out, torch.float32, "trans_delta_out")),
+                                             _ptr(_dev(rot_delta_out, torch.float32, "rot_delta_out")), tro, _ptr(vt.K32), _ptr(vt.dev),
+                                             vt.V, _ptr(tf), float(input_w), _stream(P))
+        _lib.check(st, "fp_pose_update_views")
+        return O
     objs = _objects(mesh_diameter, obj, "pose_update")
     if objs is not None:
         d, o, M = objs

@@ -117,14 +117,20 @@ def resolve_shared_translation(ob_in_cams, flag):
     return same if flag is None else bool(flag) and same
 
 
-def two_pose_pairs(obj):
+def two_pose_pairs(obj, view=None):
     """The reference's two-pose broadcasting quirk in a call that refines several objects: a call of exactly two
     poses renders both with [umin_0, vmin_0, umax_1, vmax_1], and in a multi-object call the quirk belongs to each object's own
     call, so it applies to an object with exactly two hypotheses -- pairing them in call order -- and never across objects.
-    obj: per-hypothesis object index (host sequence).  -> sorted [(i, j)]: the rows of every object with exactly two hypotheses"""
+    obj: per-hypothesis object index (host sequence).  view: per-hypothesis view index (host sequence) or None: a reference call is
+    ONE frame of one object, so over several views the quirk is grouped per (view, object) and never pairs two frames.
+    -> sorted [(i, j)]: the rows of every group with exactly two hypotheses"""
+    obj = np.asarray(obj).reshape(-1).tolist()
+    view = [0] * len(obj) if view is None else np.asarray(view).reshape(-1).tolist()
+    if len(view) != len(obj):
+        raise ValueError(f"two_pose_pairs: {len(obj)} object indices but {len(view)} view indices")
     rows = {}
-    for n, o in enumerate(np.asarray(obj).reshape(-1).tolist()):
-        rows.setdefault(o, []).append(n)
+    for n, key in enumerate(zip(view, obj)):
+        rows.setdefault(key, []).append(n)
     return sorted(tuple(r) for r in rows.values() if len(r) == 2)
 
 
@@ -137,30 +143,23 @@ def parts_for_pairs(parts, pairs):
     return list(parts)
 
 
-class ObjectIndex:
+class ObjectIndex(ops.PairRows):
     """The per-hypothesis object index of a refine call over several objects: hypothesis n belongs to object obj[n] -- entry obj[n]
     of the MeshSet and of the diameter table (ops.object_diameters).  Built once from host data: the int32 device index the kernels
-    read, and the rows of the two-pose quirk (two_pose_pairs) as a device table, so a captured refine loop copies nothing."""
+    read, and the rows of the two-pose quirk (two_pose_pairs) as a device table, so a captured refine loop copies nothing.
+    view: the call's per-hypothesis view index (the host index of its ops.Views) when it spans several views: the quirk is then
+    grouped per (view, object)."""
 
-    def __init__(self, obj, device):
+    def __init__(self, obj, device, view=None):
         self.host = np.asarray(obj, dtype=np.int64).reshape(-1)
         if self.host.size and self.host.min() < 0:
             raise ValueError("ObjectIndex: negative object index")
+        self.view = None if view is None else np.asarray(view, dtype=np.int64).reshape(-1)
         self.dev = torch.as_tensor(self.host.astype(np.int32), device=device)
-        self.pairs = two_pose_pairs(self.host)
-        self._pairs_dev = torch.as_tensor(np.asarray(self.pairs, dtype=np.int64).reshape(-1, 2), device=device)
-        self._first = np.asarray([i for i, _ in self.pairs], dtype=np.int64)
+        super().__init__(two_pose_pairs(self.host, self.view), device)
 
     def __len__(self):
         return int(self.host.size)
-
-    def pair_rows(self, a, b):
-        """(P, 2) device rows of the quirk pairs inside rows a..b, relative to a; None when there are none (parts_for_pairs keeps a
-        pair from straddling two parts)"""
-        k0, k1 = int(np.searchsorted(self._first, a)), int(np.searchsorted(self._first, b))
-        if k0 == k1:
-            return None
-        return self._pairs_dev[k0:k1] - a
 
 
 def apply_two_pose_quirk(bbox2d, pairs):
@@ -240,7 +239,7 @@ class PoseRefinePredictor:
         return oh, ow, tn, bool(self.cfg["normalize_xyz"])
 
     def refine_part(self, slot, rows, rgb_t, xyz_t, poses, K, H, W, mesh_handle, mesh_diameter, iterations, outs, workspace=None,
-                    state=None, shared_translation=False, obj=None):
+                    state=None, shared_translation=False, obj=None, views=None):
         """Iterations `iterations` (a range) of the refine loop for the hypotheses rows=(a, b) of `poses`, on the CURRENT
         stream, with the activation-buffer set `slot`: per iteration fp_crop_windows -> fp_render_crops (A) +
         fp_warp_crops (B) -> RefineNet plan -> fp_pose_update.  outs = (poses_out (N,4,4), trans_delta (N,3), rot_delta
@@ -249,46 +248,51 @@ class PoseRefinePredictor:
         translation (register(): estimater.py:132-133 puts every rotation of the grid at the guessed centre), so in
         iteration 0 they share one crop window and one observed crop: it is warped once and the stem of the fp16 plan
         encodes it once (engine._HipEncoder, bit-identical to 252 copies).  Several objects: mesh_handle = an ops.MeshSet,
-        mesh_diameter = its ops.object_diameters table, obj = the call's ObjectIndex (rows a..b of it are this part's).  -> state"""
+        mesh_diameter = its ops.object_diameters table, obj = the call's ObjectIndex (rows a..b of it are this part's).  Several views:
+        views = the call's ops.Views, rgb_t / xyz_t = (V,H,W,3) frame stacks, mesh_handle an ops.MeshSet with its diameter table (K
+        unused).  -> state"""
         plan = self.plan()
         a, b = rows
         n = b - a
         oh, ow, tn, normalize = self._loop_constants()
         poses_out, trans_delta, rot_delta, total = outs
         o = obj.dev[a:b] if obj is not None else None
-        pairs = obj.pair_rows(a, b) if obj is not None else None
+        vw = views.rows(a, b) if views is not None else None
+        grouped = obj if obj is not None else views        # the quirk per object, per view, or per (view, object)
+        pairs = grouped.pair_rows(a, b) if grouped is not None else None
+        tables = obj is not None or views is not None
         if state is None:
             state = dict(P=poses[a:b], AB=torch.empty((2 * n, 6, oh, ow), dtype=plan.dtype, device=poses.device), raw=None)
         for it in iterations:
             last = it + 1 == total
             P, AB = state["P"], state["AB"]
-            tf_to_crops, bbox2d = ops.crop_windows(P, K, mesh_diameter, self.cfg["crop_ratio"], (ow, oh), obj=o)
-            if obj is not None:
-                if pairs is not None:       # the quirk below, per object (two_pose_pairs)
+            tf_to_crops, bbox2d = ops.crop_windows(P, K, mesh_diameter, self.cfg["crop_ratio"], (ow, oh), obj=o, views=vw)
+            if grouped is not None:
+                if pairs is not None:       # the quirk below, per object / view (two_pose_pairs)
                     apply_two_pose_quirk(bbox2d, pairs)
             elif poses.shape[0] == 2:
                 # reference broadcasting quirk (SURVEY App. D.5): with exactly two poses transform_pts pairs pose i with
                 # corner i, so both hypotheses are rendered with [umin_0, vmin_0, umax_1, vmax_1]
                 bbox2d = torch.stack([bbox2d[0, 0], bbox2d[0, 1], bbox2d[1, 2], bbox2d[1, 3]])[None].expand(2, 4).contiguous()
             ops.render_crops(mesh_handle, P, bbox2d, K, H, W, out_hw=(oh, ow), mesh_diameter=mesh_diameter, xyz_thr=0.001,
-                             normalize_xyz=normalize, A_out=AB[:n], workspace=workspace, obj=o)
+                             normalize_xyz=normalize, A_out=AB[:n], workspace=workspace, obj=o, views=vw)
             shared = bool(shared_translation) and it == 0 and n > 1 and plan.hip
             ops.warp_crops(rgb_t, xyz_t, None, tf_to_crops[:1] if shared else tf_to_crops, K, P[:1] if shared else P, mesh_diameter,
                            ops.MODE_REFINE, normalize_xyz=normalize, out_hw=(oh, ow), B_out=AB[n:n + 1] if shared else AB[n:],
-                           obj=None if o is None else (o[:1] if shared else o))
+                           obj=None if o is None else (o[:1] if shared else o), views=vw)
             raw = plan(AB[:n + 1], slot=slot, shared_b=True) if shared else plan(AB, slot=slot)
             state["raw"] = raw
             state["P"] = ops.pose_update(raw["trans"], raw["rot"], P, rot_rep=self.cfg["rot_rep"], normalize_xyz=normalize,
                                          trans_normalizer=tn, rot_normalizer=float(self.cfg["rot_normalizer"]),
-                                         mesh_diameter=mesh_diameter if obj is not None else float(mesh_diameter),
+                                         mesh_diameter=mesh_diameter if tables else float(mesh_diameter),
                                          out=poses_out[a:b] if last else None,
                                          trans_delta_out=trans_delta[a:b] if last else None,
                                          rot_delta_out=rot_delta[a:b] if last else None, trans_rep=str(self.cfg["trans_rep"]), K=K,
-                                         tf_to_crops=tf_to_crops, input_w=float(self.cfg["input_resize"][0]), obj=o)
+                                         tf_to_crops=tf_to_crops, input_w=float(self.cfg["input_resize"][0]), obj=o, views=vw)
         return state
 
     def refine_device(self, rgb_t, xyz_t, poses, K, H, W, mesh_handle, mesh_diameter, iteration, workspace=None,
-                      shared_translation=False, obj=None):
+                      shared_translation=False, obj=None, views=None):
         """The refine loop on device tensors only (predict_pose_refine.py:182-235).  No host round trip, no host-side
         tensor creation.  Hypotheses are independent through all iterations, so the parts of `self.sub.parts(N)` run the
         whole loop as independent launch sequences on concurrent streams (overlap.py), issued iteration by iteration and
@@ -296,15 +300,31 @@ class PoseRefinePredictor:
         -> (poses (N,4,4), trans_delta (N,3) in metres, rot_mat_delta (N,3,3)) of the last iteration, as the reference
         keeps them in last_trans_update / last_rot_update (predict_pose_refine.py:238-239).
         Several objects in one call: mesh_handle = an ops.MeshSet, mesh_diameter = its ops.object_diameters table, obj = an
-        ObjectIndex of the N hypotheses (any order of objects; the two-pose quirk per object, two_pose_pairs)"""
+        ObjectIndex of the N hypotheses (any order of objects; the two-pose quirk per object, two_pose_pairs).
+        Several views in one call: views = an ops.Views of the N hypotheses, rgb_t / xyz_t = (V,H,W,3) frame stacks, mesh_handle an
+        ops.MeshSet with its diameter table; with obj too, the ObjectIndex must be built with view=views.host (the quirk per (view,
+        object)).  shared_translation is a registration feature and is refused with views."""
         self.plan()
         N = poses.shape[0]
         dev = poses.device
         if obj is not None and len(obj) != N:
             raise ValueError(f"refine_device: {N} poses but an object index of {len(obj)}")
+        if views is not None:
+            if shared_translation:
+                raise ValueError("refine_device: shared_translation (registration) is not supported with views")
+            if not isinstance(views, ops.Views):
+                raise ValueError("refine_device: views must be an ops.Views")
+            if views.dev is not None and len(views) != N:
+                raise ValueError(f"refine_device: {N} poses but a view index of {len(views)}")
+            if obj is not None:
+                vh = np.zeros(N, dtype=np.int64) if views.host is None else views.host
+                if obj.view is None or not np.array_equal(obj.view, vh):
+                    raise ValueError("refine_device: with views, the ObjectIndex must be built with view=views.host "
+                                     "(the two-pose quirk is grouped per (view, object))")
         parts = self.sub.parts(N, dev)
-        if obj is not None:
-            parts = parts_for_pairs(parts, obj.pairs)
+        grouped = obj if obj is not None else views
+        if grouped is not None:
+            parts = parts_for_pairs(parts, grouped.pairs)
         if workspace is not None and torch.is_tensor(workspace):
             workspace = [workspace]
         if workspace is not None and len(workspace) != len(parts):
@@ -322,7 +342,7 @@ class PoseRefinePredictor:
                 with torch.cuda.stream(streams[h]):
                     state[h] = self.refine_part(h, rows, rgb_t, xyz_t, poses, K, H, W, mesh_handle, mesh_diameter, range(it, it + 1),
                                                 outs, None if workspace is None else workspace[h], state[h],
-                                                shared_translation=shared_translation, obj=obj)
+                                                shared_translation=shared_translation, obj=obj, views=views)
         self.sub.join(streams)
         self._raw_parts = [None if st is None else st["raw"] for st in state]   # last_raw_output
         return outs[:3]

@@ -69,8 +69,10 @@ const char* fp_last_error(void);
  *                         + fp_encoder_tail_mean_fwd / fp_encoder_tail_workspace_bytes.
  *   213 -> 214: several objects per call (additions only): + fp_mesh_set_create / fp_mesh_set_destroy /
  *               fp_mesh_set_workspace_bytes, fp_render_crops_multi, fp_crop_windows_multi, fp_warp_crops_multi, fp_pose_update_multi.
- *   214 -> 215: + fp_attention_segments_f16_fwd (addition only): attention over ragged sequences (several objects' hypotheses). */
-#define FP_AMD_ABI_VERSION 215
+ *   214 -> 215: + fp_attention_segments_f16_fwd (addition only): attention over ragged sequences (several objects' hypotheses).
+ *   215 -> 216: several views per call (additions only): + fp_crop_windows_views, fp_render_crops_views, fp_warp_crops_views,
+ *               fp_pose_update_views, fp_depth_erode_frames, fp_depth_bilateral_frames, fp_depth_to_xyz_frames. */
+#define FP_AMD_ABI_VERSION 216
 int fp_version(void);
 
 /* Utils.py:104-130 make_mesh_tensors: records caller-owned device tensors.
@@ -105,6 +107,49 @@ int fp_depth_bilateral(const float* depth /*dev*/, float* out /*dev*/, int H, in
 /* Utils.py:399-417 depth2xyzmap (f64_internal=1, numpy promotion) / :420-438 depth2xyzmap_batch (0) */
 int fp_depth_to_xyz(const float* depth /*dev H,W*/, const double* K /*host 9*/, float zfar,
                     int f64_internal, float* xyz /*dev H,W,3*/, int H, int W, void* stream);
+
+/* Several views per call: the batched ingest of V frames of one size, one launch per stage over a (V,H,W) stack (frame f of every
+ * output = what the single-frame entry point computes on frame f of the input, bit for bit).  1 <= V <= 65535.
+ * fp_depth_to_xyz_frames reads the intrinsics of frame f from Ks[f] (dev V,9 f64: the values fp_depth_to_xyz takes on the host). */
+int fp_depth_erode_frames(const float* depth /*dev V,H,W*/, float* out /*dev V,H,W*/, int H, int W, int V, int radius,
+                          float depth_diff_thres, float ratio_thres, float zfar, void* stream);
+int fp_depth_bilateral_frames(const float* depth /*dev V,H,W*/, float* out /*dev V,H,W*/, int H, int W, int V, int radius,
+                              float zfar, float sigmaD, float sigmaR, void* stream);
+int fp_depth_to_xyz_frames(const float* depth /*dev V,H,W*/, const double* Ks /*dev V,9*/, float zfar, int f64_internal,
+                           float* xyz /*dev V,H,W,3*/, int H, int W, int V, void* stream);
+
+/* Several views per call (the *_views entry points; estimater.py:250-268 track_one on several camera frames at once).  Each takes the
+ * arguments of its *_multi form with the one host K replaced by a VIEW TABLE: Ks (dev V,9: f64 for fp_crop_windows_views, f32 for the
+ * others -- the values the single-view entry points take on the host) and a per-hypothesis view index view (dev N int32, values
+ * 0..V-1, any order; NULL allowed only for V == 1: all 0).  Image inputs are FRAME STACKS of V frames of one H x W, frame v at
+ * element offset (size_t)v * H * W * C.  obj may be NULL for a one-mesh set / M == 1 as in the *_multi forms.  Hypothesis n then sees
+ * exactly what the *_multi entry point sees when it is called with frame view[n] and K Ks[view[n]]: the outputs are bit-identical.
+ * A view index outside 0..V-1 never reads outside the stack or the table: the render draws nothing, the warp writes what a pixel
+ * outside the frame gets, crop windows and pose update write NaN.  Argument errors (FP_ERR_INVALID_ARG, fp_last_error): a NULL K
+ * table, V < 1, view NULL with V > 1, unknown flag bits, and those of the *_multi form. */
+/* fp_crop_windows_multi with K = Ks[view[n]] (f64) */
+int fp_crop_windows_views(const float* poses /*dev N,16*/, const double* Ks /*dev V,9*/, const int32_t* view /*dev N|NULL*/, int V,
+                          const double* diameters /*dev M*/, const int32_t* obj /*dev N|NULL*/, int M, double crop_ratio, int out_w,
+                          int out_h, int N, float* tf_to_crops /*dev N,9*/, float* bbox2d /*dev N,4*/, void* stream);
+/* fp_render_crops_multi with K = Ks[view[n]] (f32); workspace: fp_mesh_set_workspace_bytes(set, N, oh, ow) */
+int fp_render_crops_views(const fp_mesh_set* set, const int32_t* obj /*dev N|NULL*/, const double* diameters /*dev M|NULL*/,
+                          const float* Ks /*dev V,9*/, const int32_t* view /*dev N|NULL*/, int V, const float* poses /*dev N,16*/,
+                          const float* bbox2d /*dev N,4|NULL*/, int H, int W, int N, int oh, int ow, float w_ambient, float w_diffuse,
+                          float xyz_thr, int flags, void* A /*dev*/, float* color /*dev*/, float* depth /*dev*/, float* xyz /*dev*/,
+                          float* normal /*dev*/, uint32_t* zbuf /*dev*/, int32_t* tri_id /*dev*/, void* workspace /*dev*/,
+                          size_t workspace_bytes, void* stream);
+/* fp_warp_crops_multi on frame view[n] of the stacks rgb (V,H,W,3), xyz_map (V,H,W,3; REFINE) / depth (V,H,W; SCORE), K = Ks[view[n]] */
+int fp_warp_crops_views(const float* rgb /*dev V,H,W,3*/, const float* xyz_map /*dev V,H,W,3|NULL*/, const float* depth /*dev V,H,W|NULL*/,
+                        const float* tf_to_crops /*dev N,9*/, const float* Ks /*dev V,9*/, const int32_t* view /*dev N|NULL*/, int V,
+                        const float* poses /*dev N,16*/, const double* diameters /*dev M*/, const int32_t* obj /*dev N|NULL*/, int M,
+                        int flags, int mode, int H, int W, int N, int oh, int ow, void* B /*dev N,6,oh,ow*/, void* stream);
+/* fp_pose_update_multi with K = Ks[view[n]] (read by trans_rep deepim only; Ks is required either way) */
+int fp_pose_update_views(const float* trans /*dev N,3*/, const float* rot /*dev N,3|6*/, const float* poses_in /*dev N,16*/,
+                         int rot_rep, int normalize_xyz, const float* trans_normalizer /*host 3*/, float rot_normalizer,
+                         const double* diameters /*dev M*/, const int32_t* obj /*dev N|NULL*/, int M, int N,
+                         float* poses_out /*dev N,16*/, float* trans_delta_out /*dev N,3|NULL*/, float* rot_delta_out /*dev N,9|NULL*/,
+                         int trans_rep, const float* Ks /*dev V,9*/, const int32_t* view /*dev N|NULL*/, int V,
+                         const float* tf_to_crops /*dev N,9|NULL*/, float input_w, void* stream);
 
 /* Utils.py:577-621 compute_crop_window_tf_batch(method='box_3d') and the bbox of
  * predict_pose_refine.py:44-45 / predict_score.py:74-75 (closed-form inverse). */
