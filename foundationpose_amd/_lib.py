@@ -10,7 +10,7 @@ import torch  # noqa: F401  (must precede CDLL: shares the HIP runtime with PyTo
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("FP_AMD_LIB") or os.path.join(_HERE, "csrc", "libfp_amd.so")   # FP_AMD_LIB: A/B builds
-ABI_VERSION = 216    # = FP_AMD_ABI_VERSION of include/fp_amd.h (tests/test_abi.py keeps the two in step)
+ABI_VERSION = 217    # = FP_AMD_ABI_VERSION of include/fp_amd.h (tests/test_abi.py keeps the two in step)
 _lib = None
 
 vp, ci, cf, cd, sz = C.c_void_p, C.c_int, C.c_float, C.c_double, C.c_size_t
@@ -32,6 +32,7 @@ SIGNATURES = {
     "fp_depth_erode_frames": (ci, [vp, vp, ci, ci, ci, ci, cf, cf, cf, vp]),
     "fp_depth_bilateral_frames": (ci, [vp, vp, ci, ci, ci, ci, cf, cf, cf, vp]),
     "fp_depth_to_xyz_frames": (ci, [vp, vp, cf, ci, vp, ci, ci, ci, vp]),
+    "fp_mask_depth_stats": (ci, [vp, vp, vp, ci, ci, ci, ci, cf, vp, vp]),
     "fp_crop_windows_views": (ci, [vp, vp, vp, ci, vp, vp, ci, cd, ci, ci, ci, vp, vp, vp]),
     "fp_render_crops_views": (ci, [vp, vp, vp, vp, vp, ci, vp, vp, ci, ci, ci, ci, ci, cf, cf, cf, ci, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]),
     "fp_warp_crops_views": (ci, [vp, vp, vp, vp, vp, vp, ci, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, ci, vp, vp]),
@@ -50,6 +51,7 @@ SIGNATURES = {
     "fp_igemm_f16_splitk_fwd": (ci, [vp, vp, vp, vp, vp, ci, ci, ci, ci, vp, ci, vp, sz, vp]),
     "fp_add_pe_f16_fwd": (ci, [vp, vp, vp, ci, ci, ci, vp]),
     "fp_replicate_rows_f16": (ci, [vp, vp, ci, ci, ci, ci, ci, C.c_longlong, vp]),
+    "fp_replicate_segments_f16": (ci, [vp, vp, ci, ci, ci, ci, ci, C.c_longlong, vp]),
     "fp_layernorm_res_fwd": (ci, [vp, vp, vp, ci, vp, vp, vp, cf, vp, vp, ci, ci, vp]),
     "fp_pack_linear512_f16": (ci, [vp, vp, vp]),
     "fp_linear512_f16_fwd": (ci, [vp, vp, vp, vp, ci, ci, ci, vp]),

@@ -1,6 +1,8 @@
 // Per-frame and per-hypothesis small ops: depth erosion / bilateral filter / back-projection,
 // crop windows, pose update.  All HBM-trivial; one thread per pixel or per pose.
 // Compiled with -ffp-contract=off so the operation order matches the definition in DESIGN.md.
+#include <climits>
+
 #include "fp_common.h"
 
 // ---------------------------------------------------------------- a1 (Utils.py:359-384)
@@ -294,6 +296,122 @@ __global__ void k_pose_update(const float* __restrict__ trans, const float* __re
   }
 }
 
+// ---------------------------------------------------------------- a14 (estimater.py:137-156 guess_translation, :164-166)
+// Per mask: the bounding box of its pixels, the count n of its valid depths (d >= min_depth) and the (n-1)//2-th and n//2-th
+// smallest of them, exactly the elements torch.sort puts there.  One workgroup per mask.  Pass 1 reads the whole mask for the box
+// and n; then an exact radix select (four 8-bit digits, most significant first) over the box: valid depths are positive floats, so
+// their bit patterns order as uint32 (+inf last), and both ranks are found in the same passes with one LDS histogram each.
+// out[m] = {v0, v1, u0, u1, n, bits(lo), bits(hi), 0}: -1 for the box of an empty mask, NaN for lo / hi when n == 0.  A view index
+// outside 0..V-1 reads nothing and reports an empty mask.
+#define MDS_THREADS 1024
+__device__ __forceinline__ void mds_visit(const uint8_t* __restrict__ mk, const float* __restrict__ dp, int i, float min_depth,
+                                          int W, int& rmin, int& rmax, int& cmin, int& cmax, int& cnt) {
+  if (!mk[i]) return;
+  const int r = i / W, c = i - r * W;
+  rmin = min(rmin, r); rmax = max(rmax, r); cmin = min(cmin, c); cmax = max(cmax, c);
+  cnt += dp[i] >= min_depth;
+}
+
+__global__ __launch_bounds__(MDS_THREADS) void k_mask_depth_stats(const float* __restrict__ depth, const uint8_t* __restrict__ masks,
+                                                                  const int32_t* __restrict__ view, int V, int H, int W,
+                                                                  float min_depth, int32_t* __restrict__ out) {
+  __shared__ int red[MDS_THREADS / 64][5];
+  __shared__ unsigned hist[2][256];
+  __shared__ unsigned sel[2][2];            // per rank: the digits found so far (prefix) and the rank left inside them
+  const int m = blockIdx.x, t = threadIdx.x, lane = t & 63, wid = t >> 6;
+  const int vv = view ? view[m] : 0;
+  const bool ok = (unsigned)vv < (unsigned)V;
+  const size_t HW = (size_t)H * W;
+  const uint8_t* mk = masks + (size_t)m * HW;
+  const float* dp = depth + (size_t)(ok ? vv : 0) * HW;
+  int rmin = INT_MAX, rmax = -1, cmin = INT_MAX, cmax = -1, cnt = 0;
+  if (ok) {
+    const int n = (int)HW;
+    if ((HW & 3) == 0) {                      // four mask bytes per load; rows of the masks stay 4-byte aligned
+      const uint32_t* mk4 = reinterpret_cast<const uint32_t*>(mk);
+      for (int q = t; q < n / 4; q += MDS_THREADS) {
+        const uint32_t w4 = mk4[q];
+        if (!w4) continue;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) mds_visit(mk, dp, 4 * q + e, min_depth, W, rmin, rmax, cmin, cmax, cnt);
+      }
+    } else {
+      for (int i = t; i < n; i += MDS_THREADS) mds_visit(mk, dp, i, min_depth, W, rmin, rmax, cmin, cmax, cnt);
+    }
+  }
+  for (int o = 32; o > 0; o >>= 1) {
+    rmin = min(rmin, __shfl_xor(rmin, o, 64)); rmax = max(rmax, __shfl_xor(rmax, o, 64));
+    cmin = min(cmin, __shfl_xor(cmin, o, 64)); cmax = max(cmax, __shfl_xor(cmax, o, 64));
+    cnt += __shfl_xor(cnt, o, 64);
+  }
+  if (lane == 0) { red[wid][0] = rmin; red[wid][1] = rmax; red[wid][2] = cmin; red[wid][3] = cmax; red[wid][4] = cnt; }
+  __syncthreads();
+  rmin = INT_MAX; rmax = -1; cmin = INT_MAX; cmax = -1; cnt = 0;
+  for (int w = 0; w < MDS_THREADS / 64; ++w) {       // every thread, in one order: all hold the same totals
+    rmin = min(rmin, red[w][0]); rmax = max(rmax, red[w][1]); cmin = min(cmin, red[w][2]); cmax = max(cmax, red[w][3]);
+    cnt += red[w][4];
+  }
+  int32_t* o = out + (size_t)m * 8;
+  if (cnt == 0) {                                     // no valid depth (or an empty mask: then no box either): lo = hi = NaN
+    const bool any = rmax >= 0;
+    const int32_t vals[8] = {any ? rmin : -1, any ? rmax : -1, any ? cmin : -1, any ? cmax : -1, 0, 0x7fc00000, 0x7fc00000, 0};
+    if (t < 8) o[t] = vals[t];
+    return;
+  }
+  if (t < 2) {
+    sel[t][0] = 0u;
+    sel[t][1] = t == 0 ? (unsigned)(cnt - 1) / 2 : (unsigned)cnt / 2;
+  }
+  const int bw = cmax - cmin + 1;
+  const int box = (rmax - rmin + 1) * bw;
+  unsigned known = 0u;                                // the bits of the digits found so far
+  for (int shift = 24; shift >= 0; shift -= 8) {
+    for (int i = t; i < 512; i += MDS_THREADS) (&hist[0][0])[i] = 0u;
+    __syncthreads();                                  // also publishes sel[] of the previous digit
+    const unsigned p0 = sel[0][0], p1 = sel[1][0];
+    for (int i = t; i < box; i += MDS_THREADS) {
+      const int r = rmin + i / bw, c = cmin + i % bw;
+      const size_t px = (size_t)r * W + c;
+      if (!mk[px]) continue;
+      const float d = dp[px];
+      if (!(d >= min_depth)) continue;
+      const unsigned b = __float_as_uint(d);
+      if ((b & known) == p0) atomicAdd(&hist[0][(b >> shift) & 255u], 1u);
+      if ((b & known) == p1) atomicAdd(&hist[1][(b >> shift) & 255u], 1u);
+    }
+    __syncthreads();
+    if (wid < 2) {                                    // wave k scans histogram k: four bins per lane, then an inclusive lane scan
+      unsigned h[4], sum = 0u;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) { h[e] = hist[wid][lane * 4 + e]; sum += h[e]; }
+      unsigned inc = sum;
+      for (int o2 = 1; o2 < 64; o2 <<= 1) {
+        const unsigned y = __shfl_up(inc, o2, 64);
+        if (lane >= o2) inc += y;
+      }
+      const unsigned k = sel[wid][1];
+      unsigned before = inc - sum;
+      if (k >= before && k < inc) {                   // exactly one lane holds the rank
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          if (k < before + h[e]) {
+            sel[wid][0] |= (unsigned)(lane * 4 + e) << shift;
+            sel[wid][1] = k - before;
+            break;
+          }
+          before += h[e];
+        }
+      }
+    }
+    known |= 255u << shift;
+    __syncthreads();                                  // the scan has read the histograms before the next digit clears them
+  }
+  if (t < 8) {
+    const int32_t vals[8] = {rmin, rmax, cmin, cmax, cnt, (int32_t)sel[0][0], (int32_t)sel[1][0], 0};
+    o[t] = vals[t];
+  }
+}
+
 // ---------------------------------------------------------------- C ABI
 extern "C" int fp_depth_erode(const float* depth, float* out, int H, int W, int radius, float diff_thres,
                               float ratio_thres, float zfar, void* stream) {
@@ -473,4 +591,20 @@ extern "C" int fp_pose_update_views(const float* trans, const float* rot, const 
   return pose_update_launch<true, true>("fp_pose_update_views", trans, rot, poses_in, rot_rep, normalize_xyz, trans_normalizer,
                                         rot_normalizer, 0.f, diameters, obj, M, N, poses_out, trans_delta_out, rot_delta_out,
                                         trans_rep, nullptr, tf_to_crops, input_w, stream, vt);
+}
+
+extern "C" int fp_mask_depth_stats(const float* depth, const uint8_t* masks, const int32_t* view, int V, int M, int H, int W,
+                                   float min_depth, int32_t* out, void* stream) {
+  FP_REQUIRE(M >= 0, "fp_mask_depth_stats: M < 0");
+  if (M == 0) return FP_OK;
+  FP_REQUIRE(depth && masks && out, "fp_mask_depth_stats: NULL tensor");
+  FP_REQUIRE(V >= 1 && H > 0 && W > 0, "fp_mask_depth_stats: bad frame size (V=%d, H=%d, W=%d)", V, H, W);
+  FP_REQUIRE(view || V == 1, "fp_mask_depth_stats: %d frames need a per-mask view index", V);
+  FP_REQUIRE((long long)H * W < (1ll << 31), "fp_mask_depth_stats: H * W too large");
+  FP_REQUIRE(min_depth > 0.f && min_depth < __builtin_inff(),
+             "fp_mask_depth_stats: min_depth must be positive and finite (the select orders valid depths by their bits)");
+  FP_REQUIRE(((size_t)H * W & 3) != 0 || ((size_t)masks & 3) == 0, "fp_mask_depth_stats: masks must be 4-byte aligned");
+  hipLaunchKernelGGL(k_mask_depth_stats, dim3(M), dim3(MDS_THREADS), 0, (hipStream_t)stream, depth, masks, view, V, H, W, min_depth, out);
+  FP_CHECK_LAUNCH("fp_mask_depth_stats");
+  return FP_OK;
 }

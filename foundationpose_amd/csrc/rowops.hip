@@ -191,6 +191,49 @@ extern "C" int fp_replicate_rows_f16(const void* src, void* dst, int copies, int
   return FP_OK;
 }
 
+// The segmented form: image i of segment s (off[s] <= i < off[s+1]) gets image s's vector, in place.  A lane owns one 16-byte
+// vector column through all images, so no other lane touches its addresses.  It walks the segments from the last to the first and
+// reads a segment's source before it writes that segment's images.  With non-empty segments off[s] >= s, so every image segment s
+// writes is >= s, while the sources still to be read are images < s: none is overwritten before it is read (and image s itself is
+// its own segment's source, read first).  Offsets outside 0..images are clamped: a bad table writes only inside the buffer.
+__global__ __launch_bounds__(64) void k_replicate_segments(uint4* __restrict__ buf, const int32_t* __restrict__ off, int segments,
+                                                           int images, int pixels, int vec_per_pixel, int pixel_stride_v,
+                                                           size_t image_stride_v) {
+  const int idx = blockIdx.x * 64 + threadIdx.x;
+  if (idx >= pixels * vec_per_pixel) return;
+  const int p = idx / vec_per_pixel, v = idx - p * vec_per_pixel;
+  uint4* col = buf + (size_t)p * pixel_stride_v + v;
+  int hi = min(max(off[segments], 0), images);
+  for (int s = segments - 1; s >= 0; --s) {
+    const int lo = min(max(off[s], 0), images);
+    if (lo < hi) {
+      const uint4 val = col[(size_t)s * image_stride_v];
+      for (int i = lo; i < hi; ++i)
+        if (i != s) col[(size_t)i * image_stride_v] = val;
+    }
+    hi = min(hi, lo);
+  }
+}
+
+extern "C" int fp_replicate_segments_f16(void* buf, const int32_t* seg_offsets, int segments, int images, int pixels, int channels,
+                                         int pixel_stride, long long image_stride, void* stream) {
+  FP_REQUIRE(segments >= 0 && images >= 0 && pixels >= 0, "fp_replicate_segments_f16: negative size");
+  if (segments == 0 || images == 0 || pixels == 0) return FP_OK;
+  FP_REQUIRE(buf && seg_offsets, "fp_replicate_segments_f16: NULL tensor");
+  FP_REQUIRE(segments <= images, "fp_replicate_segments_f16: %d segments but %d images (the sources are images 0..segments-1)",
+             segments, images);
+  FP_REQUIRE(channels > 0 && channels % 8 == 0 && pixel_stride % 8 == 0 && image_stride % 8 == 0,
+             "fp_replicate_segments_f16: channels and strides must be multiples of 8 fp16 values (16-byte vectors)");
+  FP_REQUIRE(pixel_stride >= channels && image_stride >= (long long)pixels * pixel_stride, "fp_replicate_segments_f16: bad strides");
+  FP_REQUIRE(((size_t)buf & 15) == 0, "fp_replicate_segments_f16: buf must be 16-byte aligned");
+  FP_REQUIRE((long long)pixels * (channels / 8) < (1ll << 31), "fp_replicate_segments_f16: pixels * channels too large");
+  const int vpp = channels / 8;
+  hipLaunchKernelGGL(k_replicate_segments, dim3(fp_cdiv(pixels * vpp, 64)), dim3(64), 0, (hipStream_t)stream, (uint4*)buf, seg_offsets,
+                     segments, images, pixels, vpp, pixel_stride / 8, (size_t)(image_stride / 8));
+  FP_CHECK_LAUNCH("fp_replicate_segments_f16");
+  return FP_OK;
+}
+
 extern "C" int fp_add_pe_f16_fwd(const void* tok, const float* pe, void* out, int M, int S, int D, void* stream) {
   FP_REQUIRE(M >= 0, "fp_add_pe_f16_fwd: M < 0");
   if (M == 0) return FP_OK;

@@ -325,9 +325,19 @@ class _HipEncoder:
         shared_b: AB is (n+1,6,H,W) -- n rendered crops and ONE observed crop that all n pairs share (the first refine
         iteration of register(): every hypothesis has the same translation, hence the same crop window).  The shared stem
         then runs on n+1 images instead of 2n and the B half of the concat is replicated; per element the same kernels in
-        the same order, so the result is bit-identical to feeding n copies."""
+        the same order, so the result is bit-identical to feeding n copies.
+        shared_b = an ops.Segments over the n pairs (the segmented form: a batched registration, one translation per (camera,
+        object)): AB is (n+S,6,H,W) -- n rendered crops and one observed crop per segment, image n+s for segment s.  The stem runs on
+        n+S images, its last conv puts observed crop s into CAT row s, and fp_replicate_segments_f16 copies it to every row of
+        segment s.  The split-K pieces still come from the plain form's image count (sk_rows), so the summation order is the same."""
         n2, _, H, W = AB.shape
-        n = n2 - 1 if shared_b else n2 // 2
+        segs = shared_b if isinstance(shared_b, ops.Segments) else None
+        if segs is not None:
+            n = n2 - len(segs)
+            if segs.total != n:
+                raise ValueError(f"shared_b: {n2} images and {len(segs)} segments, but the segments cover {segs.total} pairs")
+        else:
+            n = n2 - 1 if shared_b else n2 // 2
         b = self._buffers(n, H, W, slot, small_calls)
         h1, w1, h2, w2, h3, w3 = b["dims"]
         G = ops.IgemmGeom.image
@@ -339,7 +349,9 @@ class _HipEncoder:
         # stem output of image i (A) and image n+i (B) side by side along C: torch.cat((a, b), 1)
         self._conv("s3b", b["T"], n2, h2, w2, 128, 128, b["CAT"], res=b["P3"],
                    gout=G(h2, w2, 1, 256, bsplit=n, cgroup=128), gres=G(h2, w2, 1, 128), sk=b["SK"], sk_rows=2 * n * h2 * w2)
-        if shared_b and n > 1:
+        if segs is not None:
+            ops.replicate_segments(b["CAT"], segs, 128, 256)
+        elif shared_b and n > 1:
             ops.replicate_channels(b["CAT"], n, 128, 256)
         self._conv("j0a", b["CAT"], n, h2, w2, 256, 256, b["T2"], sk=b["SK"])
         self._conv("j0b", b["T2"], n, h2, w2, 256, 256, b["J0"], res=b["CAT"], sk=b["SK"])
@@ -531,9 +543,10 @@ class RefinePlan:
     def __call__(self, AB, slot=0, shared_b=False):
         """AB (2N,6,H,W) in the plan's dtype -> {'trans': (N,3) f32, 'rot': (N,3|6) f32}.  slot: activation-buffer set
         (callers that overlap on different streams use different slots).  shared_b (fp16 plan only): AB is (N+1,6,H,W),
-        the last image being the observed crop every pair shares (_HipEncoder.__call__)"""
+        the last image being the observed crop every pair shares; or an ops.Segments of the N pairs: AB is (N+S,6,H,W), one observed
+        crop per segment (_HipEncoder.__call__)"""
         out = {}
-        if shared_b and not self.hip:
+        if shared_b is not False and shared_b is not None and not self.hip:
             raise ValueError("shared_b is a property of the fp16 plan; expand the observed crop for the torch plans")
         if self.module is not None:
             n = AB.shape[0] // 2

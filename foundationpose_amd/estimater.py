@@ -405,3 +405,119 @@ def register_objects(estimators, K, rgb, depth, ob_masks, ob_ids=None, iteration
         e.best_id = ids[0]
         out[k] = (e.poses[0] @ e.get_tf_to_centered_mesh()).data.cpu().numpy()
     return out
+
+
+def translation_from_stats(K, box, n, lo, hi):
+    """guess_translation's centre (estimater.py:137-156) from the numbers fp_mask_depth_stats returns for one mask (the box
+    [v0, v1, u0, u1], the valid count n, the two middle valid depths lo / hi as float32), with guess_translation's own expression:
+    the same bits.  Zeros for an empty mask or an empty valid set, as there."""
+    if int(box[1]) < 0 or int(n) == 0:
+        return np.zeros((3))
+    v0, v1, u0, u1 = (float(x) for x in box)
+    lo, hi = float(lo), float(hi)
+    zc = float(np.float32(np.float32(lo) + np.float32(hi)) / np.float32(2.0)) if lo != hi else lo
+    center = (np.linalg.inv(K) @ np.asarray([(u0 + u1) / 2.0, (v0 + v1) / 2.0, 1]).reshape(3, 1)) * zc   # estimater.py:149
+    return center.reshape(3)
+
+
+def register_views(estimators, views, rgbs, depths, Ks, ob_masks, ob_ids=None, iteration=5):
+    """register() for objects in several camera frames at once: estimator k is registered on frame views[k] (rgbs[v], depths[v] with
+    intrinsics Ks[v]) with mask ob_masks[k], in ONE batched depth ingest of all frames, ONE fp_mask_depth_stats launch (every mask's
+    translation guess and valid-depth count, one copy back), ONE refine_device call over all hypotheses (views, an ObjectIndex, and
+    one shared translation per estimator: its first iteration warps one observed crop per estimator) and ONE scorer call
+    (predict_objects with views).  Per estimator the result, and the state set on it (H, W, K = Ks[views[k]], ob_id, ob_mask,
+    pose_last, best_id, poses, scores), is what its own register() on its frame computes; an estimator whose mask holds fewer than 4
+    valid depths gets register()'s guess-translation pose and keeps its state.  The argument rules are track_views': every estimator
+    listed once, all sharing ONE refiner and ONE scorer, the frames of one size; two estimators may share a mesh (one object seen by
+    two cameras).  -> [4x4 np.ndarray] per estimator, each in its own camera's frame and the original mesh frame.  track_views is the
+    batched track_one that follows."""
+    ests = list(estimators)
+    if not ests:
+        raise ValueError("register_views: no estimators")
+    views = [int(v) for v in views]
+    if len(views) != len(ests):
+        raise ValueError(f"register_views: {len(ests)} estimators but {len(views)} view indices")
+    masks = list(ob_masks)
+    if len(masks) != len(ests):
+        raise ValueError(f"register_views: {len(ests)} estimators but {len(masks)} masks")
+    ob_ids = [None] * len(ests) if ob_ids is None else list(ob_ids)
+    if len(ob_ids) != len(ests):
+        raise ValueError(f"register_views: {len(ests)} estimators but {len(ob_ids)} object ids")
+    rgbs, depths, Ks = list(rgbs), list(depths), list(Ks)
+    V = len(depths)
+    if V < 1 or len(rgbs) != V or len(Ks) != V:
+        raise ValueError(f"register_views: {len(rgbs)} rgb frames, {V} depth frames and {len(Ks)} intrinsics: need one of each per view")
+    for i, v in enumerate(views):
+        if not 0 <= v < V:
+            raise ValueError(f"register_views: estimator {i} views frame {v}, outside 0..{V - 1}")
+    hws = {_frame_hw(f) for f in rgbs + depths}
+    if len(hws) != 1:
+        raise ValueError(f"register_views: the frames differ in size {sorted(hws)}; all views must have one H x W")
+    hw = hws.pop()
+    masks_np = [np.asarray(m.data.cpu().numpy() if torch.is_tensor(m) else m) for m in masks]
+    for i, m in enumerate(masks_np):
+        if m.shape != hw:
+            raise ValueError(f"register_views: mask {i} has shape {m.shape}, the frames are {hw}")
+    refiner, scorer = ests[0].refiner, ests[0].scorer
+    if any(e.refiner is not refiner for e in ests):
+        raise ValueError("register_views: the estimators must share one refiner object (FoundationPose(..., refiner=shared))")
+    if any(e.scorer is not scorer for e in ests):
+        raise ValueError("register_views: the estimators must share one scorer object (FoundationPose(..., scorer=shared))")
+    if len({id(e) for e in ests}) != len(ests):
+        raise ValueError("register_views: an estimator is listed twice")
+    set_seed(0)
+    dev = ests[0].device
+    for e in ests:
+        if e.glctx is None:
+            e.glctx = dr.RasterizeCudaContext(e.device)
+    # register()'s depth ingest, once for all frames
+    depth_t = torch.stack([torch.as_tensor(d, device=dev, dtype=torch.float) for d in depths]).contiguous()
+    depth_t = ops.bilateral_filter_depth_frames(ops.erode_depth_frames(depth_t, radius=2), radius=2)
+    # every mask's translation guess and valid-depth count: one launch, one copy back
+    mk = torch.as_tensor(np.stack([m > 0 for m in masks_np]).astype(np.uint8), device=dev)
+    box, cnt, lo, hi = ops.mask_depth_stats_host(ops.mask_depth_stats(depth_t, mk, torch.as_tensor(np.asarray(views, np.int32), device=dev)))
+    out, hyps, lengths = [None] * len(ests), [], []
+    for k, e in enumerate(ests):
+        center = translation_from_stats(Ks[views[k]], box[k], cnt[k], lo[k], hi[k])
+        if cnt[k] < 4:
+            logging.info(f"estimator {k}: valid too small, return")
+            pose = np.eye(4)
+            pose[:3, 3] = center
+            out[k] = pose
+            lengths.append(0)
+            continue
+        P = e.rot_grid.clone()                           # generate_random_pose_hypo
+        P[:, :3, 3] = torch.as_tensor(center, device=dev, dtype=torch.float).reshape(1, 3)
+        hyps.append(P)
+        lengths.append(int(P.shape[0]))
+    if not hyps:
+        return out
+    from .predict_pose_refine import ObjectIndex
+    seg = ops.Segments(lengths, dev)
+    mset, diam = _object_tables(refiner, ests)
+    hyp_view = np.repeat(np.asarray(views, dtype=np.int64), lengths)
+    vt = ops.Views(Ks, hyp_view, dev)
+    with torch.inference_mode():
+        xyz_t = ops.depth_to_xyz_frames(depth_t, vt, zfar=float("inf"), f64_internal=True).contiguous()   # depth2xyzmap (numpy variant)
+        rgb_t = torch.stack([torch.as_tensor(r, device=dev) for r in rgbs]).to(torch.float).contiguous()
+        H, W = hw
+        poses, trans, rot = refiner.refine_device(rgb_t, xyz_t, torch.cat(hyps).contiguous(), None, H, W, mset, diam, iteration,
+                                                  shared_translation=seg, views=vt,
+                                                  obj=ObjectIndex(np.repeat(np.arange(len(ests)), lengths), dev, view=hyp_view))
+        refiner.last_trans_update, refiner.last_rot_update = trans, rot
+        scores = scorer.predict_objects(rgb_t, depth_t, None, poses, mset, diam, seg, views=vt)
+    for k, e in enumerate(ests):
+        a, b = seg.rows(k)
+        if b == a:
+            continue
+        ids = scores[a:b].argsort(descending=True)
+        e.H, e.W = int(H), int(W)
+        e.K = Ks[views[k]]
+        e.ob_id = ob_ids[k]
+        e.ob_mask = masks_np[k]
+        e.scores = scores[a:b][ids]
+        e.poses = poses[a:b][ids]
+        e.pose_last = e.poses[0]
+        e.best_id = ids[0]
+        out[k] = (e.poses[0] @ e.get_tf_to_centered_mesh()).data.cpu().numpy()
+    return out

@@ -211,6 +211,16 @@ class Views:
         v._rows = None
         return v
 
+    def take(self, idx):
+        """the table for the hypotheses idx (host indices into this table's rows; shares the K tables, uploads the gathered index)"""
+        v = object.__new__(Views)
+        v.__dict__.update(self.__dict__)
+        if self.host is not None:
+            v.host = self.host[np.asarray(idx, dtype=np.int64)]
+            v.dev = torch.as_tensor(v.host.astype(np.int32), device=self.device)
+        v._rows = None
+        return v
+
 
 def _views(views, what, N=None):
     if not isinstance(views, Views):
@@ -300,6 +310,33 @@ def ingest_frames(depth, views, f64_internal=False):
     -> xyz (V,H,W,3)"""
     d = bilateral_filter_depth_frames(erode_depth_frames(depth, radius=2), radius=2)
     return depth_to_xyz_frames(d, views, zfar=float("inf"), f64_internal=f64_internal)
+
+
+def mask_depth_stats(depth, masks, view=None, min_depth=0.001):
+    """the statistics of estimater.guess_translation and register()'s valid-depth count for M masks in one launch
+    (fp_mask_depth_stats): depth a (V,H,W) f32 stack, masks (M,H,W) uint8 (nonzero = inside), view the (M,) int32 device frame index of
+    every mask (None for one frame) -> (M, 8) int32 device tensor, per mask [v0, v1, u0, u1, n, lo, hi, 0]: the bounding box (-1 when
+    the mask is empty), the count n of depths >= min_depth inside, and as float32 bits the (n-1)//2-th and n//2-th smallest of them
+    (NaN when n == 0).  One device-to-host copy of it serves every mask (mask_depth_stats_host)."""
+    d = _frames(depth, "depth", 3)
+    mk = _dev(masks, torch.uint8, "masks")
+    if mk.dim() != 3 or tuple(mk.shape[1:]) != tuple(d.shape[1:]):
+        raise _lib.FpAmdError(f"mask_depth_stats: masks must be (M,{d.shape[1]},{d.shape[2]}), got {tuple(mk.shape)}")
+    V, H, W = (int(x) for x in d.shape)
+    M = int(mk.shape[0])
+    vw = _dev(view, torch.int32, "view")
+    if vw is not None and int(vw.numel()) != M:
+        raise _lib.FpAmdError(f"mask_depth_stats: {M} masks but a view index of {vw.numel()}")
+    out = torch.empty((M, 8), dtype=torch.int32, device=d.device)
+    _lib.check(_lib.lib().fp_mask_depth_stats(_ptr(d), _ptr(mk), _ptr(vw), V, M, H, W, float(min_depth), _ptr(out), _stream(d)),
+               "fp_mask_depth_stats")
+    return out
+
+
+def mask_depth_stats_host(stats):
+    """mask_depth_stats' table on the host (one copy) -> (box (M,4) int64 [v0, v1, u0, u1], n (M,) int64, lo (M,) f32, hi (M,) f32)"""
+    a = np.ascontiguousarray(stats.cpu().numpy() if torch.is_tensor(stats) else np.asarray(stats, dtype=np.int32))
+    return a[:, :4].astype(np.int64), a[:, 4].astype(np.int64), a[:, 5].view(np.float32).copy(), a[:, 6].view(np.float32).copy()
 
 
 def crop_windows(poses, K, mesh_diameter, crop_ratio, out_size=(160, 160), obj=None, views=None):
@@ -660,6 +697,25 @@ def replicate_channels(buf, n, c0, c1):
     st = _lib.lib().fp_replicate_rows_f16(C.c_void_p(src), C.c_void_p(src + 2 * Hp * Wp * Ct), int(n) - 1, Hp * Wp, int(c1) - int(c0), Ct, Ct,
                                           Hp * Wp * Ct, _stream(buf))
     _lib.check(st, "fp_replicate_rows_f16")
+    return buf
+
+
+def replicate_segments(buf, segments, c0, c1):
+    """buf (>= segments.total, Hp, Wp, C) fp16 NHWC, contiguous; segments an ops.Segments without empty segments: every image i of
+    segment s gets buf[i, :, :, c0:c1] = buf[s, :, :, c0:c1], in place -- the sources (images 0..S-1) are read before they are
+    overwritten (fp_replicate_segments_f16, one launch)"""
+    buf = _dev(buf, torch.float16, "buf")
+    n = int(segments.total)
+    if buf.dim() != 4 or not buf.is_contiguous() or buf.shape[0] < n:
+        raise _lib.FpAmdError(f"replicate_segments: buf must be a contiguous (>= {n}, Hp, Wp, C) tensor, got {tuple(buf.shape)}")
+    if int(segments.lengths.min()) < 1:
+        raise _lib.FpAmdError("replicate_segments: every segment must hold at least one image (its source)")
+    if segments.dev.device != buf.device:
+        raise _lib.FpAmdError(f"replicate_segments: offsets on {segments.dev.device}, buf on {buf.device}")
+    _, Hp, Wp, Ct = (int(v) for v in buf.shape)
+    st = _lib.lib().fp_replicate_segments_f16(C.c_void_p(buf.data_ptr() + 2 * int(c0)), _ptr(segments.dev), len(segments), n, Hp * Wp,
+                                              int(c1) - int(c0), Ct, Hp * Wp * Ct, _stream(buf))
+    _lib.check(st, "fp_replicate_segments_f16")
     return buf
 
 
@@ -1040,6 +1096,9 @@ igemm_f16_splitk = _timed("fp_igemm_f16_splitk_fwd", igemm_f16_splitk, _work_ige
 add_pe_f16 = _timed("fp_add_pe_f16_fwd", add_pe_f16, lambda tok, pe: (4.0 * tok.numel(), 0.0))
 replicate_channels = _timed("fp_replicate_rows_f16", replicate_channels,
                             lambda buf, n, c0, c1: (2.0 * n * buf.shape[1] * buf.shape[2] * (c1 - c0), 0.0))
+replicate_segments = _timed("fp_replicate_segments_f16", replicate_segments,
+                            lambda buf, seg, c0, c1: (2.0 * (seg.total - len(seg)) * buf.shape[1] * buf.shape[2] * (c1 - c0), 0.0))
+mask_depth_stats = _timed("fp_mask_depth_stats", mask_depth_stats)
 layernorm_res = _timed("fp_layernorm_res_fwd", layernorm_res,
                        lambda br, *a, **k: ((2.0 + (4.0 if k.get("x32") is not None else 2.0) + (4.0 if k.get("want32", True) else 0.0)
                                              + (2.0 if k.get("want16", True) else 0.0)) * br.numel(), 0.0))

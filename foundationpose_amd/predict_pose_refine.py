@@ -143,6 +143,17 @@ def parts_for_pairs(parts, pairs):
     return list(parts)
 
 
+def segment_pieces(offsets, a, b):
+    """the pieces of the segments (host offsets, ops.Segments.offsets) that fall into rows a..b of a call: [(start, end)] relative
+    to a, in order, empty pieces dropped.  A segment may straddle the part boundary (each part gets its piece of it) and a piece may
+    be a single row.  The first refine iteration warps one observed crop per piece (refine_part with a segmented
+    shared_translation)."""
+    off = np.asarray(offsets, dtype=np.int64).reshape(-1)
+    lo, hi = np.maximum(off[:-1], a), np.minimum(off[1:], b)
+    keep = hi > lo
+    return [(int(s) - a, int(e) - a) for s, e in zip(lo[keep], hi[keep])]
+
+
 class ObjectIndex(ops.PairRows):
     """The per-hypothesis object index of a refine call over several objects: hypothesis n belongs to object obj[n] -- entry obj[n]
     of the MeshSet and of the diameter table (ops.object_diameters).  Built once from host data: the int32 device index the kernels
@@ -250,7 +261,9 @@ class PoseRefinePredictor:
         encodes it once (engine._HipEncoder, bit-identical to 252 copies).  Several objects: mesh_handle = an ops.MeshSet,
         mesh_diameter = its ops.object_diameters table, obj = the call's ObjectIndex (rows a..b of it are this part's).  Several views:
         views = the call's ops.Views, rgb_t / xyz_t = (V,H,W,3) frame stacks, mesh_handle an ops.MeshSet with its diameter table (K
-        unused).  -> state"""
+        unused).  shared_translation may also be an ops.Segments of the call's rows (a batched registration): the rows of each segment
+        share one translation (the caller guarantees it, as with True), so iteration 0 warps one observed crop per piece of a segment
+        in this part (segment_pieces) and the plan replicates each into its rows (engine._HipEncoder, segmented shared_b).  -> state"""
         plan = self.plan()
         a, b = rows
         n = b - a
@@ -276,11 +289,23 @@ class PoseRefinePredictor:
                 bbox2d = torch.stack([bbox2d[0, 0], bbox2d[0, 1], bbox2d[1, 2], bbox2d[1, 3]])[None].expand(2, 4).contiguous()
             ops.render_crops(mesh_handle, P, bbox2d, K, H, W, out_hw=(oh, ow), mesh_diameter=mesh_diameter, xyz_thr=0.001,
                              normalize_xyz=normalize, A_out=AB[:n], workspace=workspace, obj=o, views=vw)
-            shared = bool(shared_translation) and it == 0 and n > 1 and plan.hip
-            ops.warp_crops(rgb_t, xyz_t, None, tf_to_crops[:1] if shared else tf_to_crops, K, P[:1] if shared else P, mesh_diameter,
-                           ops.MODE_REFINE, normalize_xyz=normalize, out_hw=(oh, ow), B_out=AB[n:n + 1] if shared else AB[n:],
-                           obj=None if o is None else (o[:1] if shared else o), views=vw)
-            raw = plan(AB[:n + 1], slot=slot, shared_b=True) if shared else plan(AB, slot=slot)
+            pieces = segment_pieces(shared_translation.offsets, a, b) \
+                if isinstance(shared_translation, ops.Segments) and it == 0 and plan.hip else None
+            if pieces is not None and len(pieces) < n:
+                # one observed crop per piece, from the piece's first row (its view, object and translation are the piece's)
+                S = len(pieces)
+                first_h = np.asarray([p0 for p0, _ in pieces], dtype=np.int64)
+                first = torch.as_tensor(first_h, device=poses.device)
+                ops.warp_crops(rgb_t, xyz_t, None, tf_to_crops.index_select(0, first), K, P.index_select(0, first), mesh_diameter,
+                               ops.MODE_REFINE, normalize_xyz=normalize, out_hw=(oh, ow), B_out=AB[n:n + S],
+                               obj=None if o is None else o.index_select(0, first), views=None if vw is None else vw.take(first_h))
+                raw = plan(AB[:n + S], slot=slot, shared_b=ops.Segments([e - p0 for p0, e in pieces], poses.device))
+            else:
+                shared = bool(shared_translation) and not isinstance(shared_translation, ops.Segments) and it == 0 and n > 1 and plan.hip
+                ops.warp_crops(rgb_t, xyz_t, None, tf_to_crops[:1] if shared else tf_to_crops, K, P[:1] if shared else P, mesh_diameter,
+                               ops.MODE_REFINE, normalize_xyz=normalize, out_hw=(oh, ow), B_out=AB[n:n + 1] if shared else AB[n:],
+                               obj=None if o is None else (o[:1] if shared else o), views=vw)
+                raw = plan(AB[:n + 1], slot=slot, shared_b=True) if shared else plan(AB, slot=slot)
             state["raw"] = raw
             state["P"] = ops.pose_update(raw["trans"], raw["rot"], P, rot_rep=self.cfg["rot_rep"], normalize_xyz=normalize,
                                          trans_normalizer=tn, rot_normalizer=float(self.cfg["rot_normalizer"]),
@@ -303,14 +328,18 @@ class PoseRefinePredictor:
         ObjectIndex of the N hypotheses (any order of objects; the two-pose quirk per object, two_pose_pairs).
         Several views in one call: views = an ops.Views of the N hypotheses, rgb_t / xyz_t = (V,H,W,3) frame stacks, mesh_handle an
         ops.MeshSet with its diameter table; with obj too, the ObjectIndex must be built with view=views.host (the quirk per (view,
-        object)).  shared_translation is a registration feature and is refused with views."""
+        object)).  shared_translation=True (one translation for the whole call) is refused with views; an ops.Segments of the N rows
+        (one translation per segment, e.g. per (camera, object) of a batched registration) works with obj, views or both."""
         self.plan()
         N = poses.shape[0]
         dev = poses.device
         if obj is not None and len(obj) != N:
             raise ValueError(f"refine_device: {N} poses but an object index of {len(obj)}")
+        segmented = isinstance(shared_translation, ops.Segments)
+        if segmented and shared_translation.total != N:
+            raise ValueError(f"refine_device: {N} poses but shared_translation segments cover {shared_translation.total}")
         if views is not None:
-            if shared_translation:
+            if shared_translation and not segmented:
                 raise ValueError("refine_device: shared_translation (registration) is not supported with views")
             if not isinstance(views, ops.Views):
                 raise ValueError("refine_device: views must be an ops.Views")

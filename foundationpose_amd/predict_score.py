@@ -186,14 +186,16 @@ class ScorePredictor:
         return scores, None
 
     @torch.inference_mode()
-    def predict_objects(self, rgb, depth, K, ob_in_cams, mesh_set, object_diameters, segments, get_vis=False, feature_exchange=None):
+    def predict_objects(self, rgb, depth, K, ob_in_cams, mesh_set, object_diameters, segments, get_vis=False, feature_exchange=None,
+                        views=None):
         """predict() for the hypotheses of several objects in ONE call.  ob_in_cams (N,4,4) grouped by object: segments
         (ops.Segments, total N) segment k = the hypotheses of object k = entry k of mesh_set (ops.MeshSet) and of object_diameters
         (ops.object_diameters).  The per-hypothesis half runs the multi-object kernels (fp_crop_windows_multi, fp_render_crops_multi,
         fp_warp_crops_multi) in predict()'s sub-batches on its streams; the cross-hypothesis attention runs per object
         (ScorePlan.head_segments), so no object's scores see another object's hypotheses.  Per object the scores are what
         predict() of that object's hypotheses alone returns.  -> scores (N,) f32 device tensor = logit + 100.  get_vis and
-        feature_exchange are not supported here."""
+        feature_exchange are not supported here.  Several camera frames: views = an ops.Views of the N hypotheses, rgb / depth =
+        (V,H,W,3) / (V,H,W) stacks (K unused): the crops come from the *_views kernels, each hypothesis from its own frame."""
         if get_vis or feature_exchange is not None:
             raise NotImplementedError("predict_objects: get_vis and feature_exchange are supported by predict() only")
         plan = self.plan()
@@ -205,9 +207,23 @@ class ScorePredictor:
         if len(segments) != mesh_set.M or int(object_diameters.numel()) != mesh_set.M:
             raise ValueError(f"predict_objects: {len(segments)} segments and {int(object_diameters.numel())} diameters for a set of "
                              f"{mesh_set.M} meshes")
-        rgb_t = torch.as_tensor(rgb, device=dev).to(torch.float).contiguous()
-        depth_t = torch.as_tensor(depth, device=dev, dtype=torch.float).contiguous()
-        H, W = int(depth_t.shape[0]), int(depth_t.shape[1])
+        if views is not None:
+            if not isinstance(views, ops.Views):
+                raise ValueError("predict_objects: views must be an ops.Views")
+            if views.dev is not None and len(views) != N:
+                raise ValueError(f"predict_objects: {N} poses but a view index of {len(views)}")
+            rgb_t = torch.stack([torch.as_tensor(r, device=dev) for r in rgb]).to(torch.float).contiguous() \
+                if isinstance(rgb, (list, tuple)) else torch.as_tensor(rgb, device=dev).to(torch.float).contiguous()
+            depth_t = torch.stack([torch.as_tensor(d, device=dev, dtype=torch.float) for d in depth]).contiguous() \
+                if isinstance(depth, (list, tuple)) else torch.as_tensor(depth, device=dev, dtype=torch.float).contiguous()
+            if rgb_t.dim() != 4 or depth_t.dim() != 3 or rgb_t.shape[0] != views.V or depth_t.shape[0] != views.V:
+                raise ValueError(f"predict_objects: {views.V} views need (V,H,W,3) / (V,H,W) stacks, got {tuple(rgb_t.shape)} / "
+                                 f"{tuple(depth_t.shape)}")
+            H, W = int(depth_t.shape[1]), int(depth_t.shape[2])
+        else:
+            rgb_t = torch.as_tensor(rgb, device=dev).to(torch.float).contiguous()
+            depth_t = torch.as_tensor(depth, device=dev, dtype=torch.float).contiguous()
+            H, W = int(depth_t.shape[0]), int(depth_t.shape[1])
         oh, ow = int(self.cfg["input_resize"][0]), int(self.cfg["input_resize"][1])
         normalize = bool(self.cfg["normalize_xyz"])
         obj = segments.row_ids()
@@ -221,14 +237,16 @@ class ScorePredictor:
                     # make_crop_data_batch's launches with the per-hypothesis object index
                     n = b - a
                     P, o = poses[a:b], obj[a:b]
+                    vw = None if views is None else views.rows(a, b)
                     AB = torch.empty((2 * n, 6, oh, ow), dtype=plan.dtype, device=dev)
-                    tf_to_crops, bbox2d = ops.crop_windows(P, K, object_diameters, self.cfg["crop_ratio"], (ow, oh), obj=o)
+                    tf_to_crops, bbox2d = ops.crop_windows(P, K, object_diameters, self.cfg["crop_ratio"], (ow, oh), obj=o, views=vw)
                     for c in range(0, n, 4096):
                         e = min(n, c + 4096)
+                        vc = None if vw is None else vw.rows(c, e)
                         ops.render_crops(mesh_set, P[c:e], bbox2d[c:e], K, H, W, out_hw=(oh, ow), mesh_diameter=object_diameters,
-                                         xyz_thr=0.1, normalize_xyz=normalize, A_out=AB[c:e], obj=o[c:e])
+                                         xyz_thr=0.1, normalize_xyz=normalize, A_out=AB[c:e], obj=o[c:e], views=vc)
                         ops.warp_crops(rgb_t, None, depth_t, tf_to_crops[c:e], K, P[c:e], object_diameters, ops.MODE_SCORE,
-                                       normalize_xyz=normalize, out_hw=(oh, ow), B_out=AB[n + c:n + e], obj=o[c:e])
+                                       normalize_xyz=normalize, out_hw=(oh, ow), B_out=AB[n + c:n + e], obj=o[c:e], views=vc)
                     plan.features(AB, slot=h, out=feats[a:b])
             self.sub.join(streams)
         return plan.head_segments(feats, segments) + 100  # predict_score.py:209

@@ -71,8 +71,9 @@ const char* fp_last_error(void);
  *               fp_mesh_set_workspace_bytes, fp_render_crops_multi, fp_crop_windows_multi, fp_warp_crops_multi, fp_pose_update_multi.
  *   214 -> 215: + fp_attention_segments_f16_fwd (addition only): attention over ragged sequences (several objects' hypotheses).
  *   215 -> 216: several views per call (additions only): + fp_crop_windows_views, fp_render_crops_views, fp_warp_crops_views,
- *               fp_pose_update_views, fp_depth_erode_frames, fp_depth_bilateral_frames, fp_depth_to_xyz_frames. */
-#define FP_AMD_ABI_VERSION 216
+ *               fp_pose_update_views, fp_depth_erode_frames, fp_depth_bilateral_frames, fp_depth_to_xyz_frames.
+ *   216 -> 217: registration in several views per call (additions only): + fp_mask_depth_stats, fp_replicate_segments_f16. */
+#define FP_AMD_ABI_VERSION 217
 int fp_version(void);
 
 /* Utils.py:104-130 make_mesh_tensors: records caller-owned device tensors.
@@ -117,6 +118,15 @@ int fp_depth_bilateral_frames(const float* depth /*dev V,H,W*/, float* out /*dev
                               float zfar, float sigmaD, float sigmaR, void* stream);
 int fp_depth_to_xyz_frames(const float* depth /*dev V,H,W*/, const double* Ks /*dev V,9*/, float zfar, int f64_internal,
                            float* xyz /*dev V,H,W,3*/, int H, int W, int V, void* stream);
+
+/* estimater.py:137-156 guess_translation and the "fewer than 4 valid depths" test of register() (estimater.py:164-166), for M masks
+ * over a (V,H,W) f32 depth stack in one launch: mask m ((M,H,W) uint8, nonzero = inside) lies on frame view[m] (dev M int32; NULL
+ * allowed only for V == 1).  out (dev M,8 int32) per mask: {v0, v1, u0, u1, n, lo, hi, 0} -- the mask's bounding box (rows v0..v1,
+ * columns u0..u1; all -1 for an empty mask), the count n of its valid depths (d >= min_depth), and lo / hi as float bits: the
+ * (n-1)//2-th and n//2-th smallest valid depths, the elements torch.sort puts there (exact; NaN when n == 0).  A view index outside
+ * 0..V-1 reads nothing and reports an empty mask.  min_depth must be positive and finite.  No allocation, no synchronisation. */
+int fp_mask_depth_stats(const float* depth /*dev V,H,W*/, const uint8_t* masks /*dev M,H,W*/, const int32_t* view /*dev M|NULL*/,
+                        int V, int M, int H, int W, float min_depth, int32_t* out /*dev M,8*/, void* stream);
 
 /* Several views per call (the *_views entry points; estimater.py:250-268 track_one on several camera frames at once).  Each takes the
  * arguments of its *_multi form with the one host K replaced by a VIEW TABLE: Ks (dev V,9: f64 for fp_crop_windows_views, f32 for the
@@ -308,6 +318,15 @@ int fp_add_pe_f16_fwd(const void* tok /*dev*/, const float* pe /*dev*/, void* ou
  * different images of one buffer as long as the source rows are not among the destination rows. */
 int fp_replicate_rows_f16(const void* src /*dev*/, void* dst /*dev*/, int copies, int rows, int channels, int src_row_stride,
                           int dst_row_stride, long long dst_copy_stride, void* stream);
+
+/* fp_replicate_rows_f16 per segment, in place: several (camera, object) groups in the first refine iteration of a batched
+ * registration, each with its own shared observed crop.  buf points at channel c0 of pixel 0 of image 0; image i, pixel p is at
+ * buf + i * image_stride + p * pixel_stride (fp16 values).  Segment s (images seg_offsets[s] .. seg_offsets[s+1]-1, dev int32
+ * S+1) gets `channels` values of image s at every pixel: the sources are images 0..S-1, which are destinations too, and each is
+ * read before it is overwritten.  Every segment must hold at least one image (offsets from 0, strictly increasing); offsets are
+ * clamped to 0..images.  channels and strides multiples of 8, buf 16-byte aligned, segments <= images. */
+int fp_replicate_segments_f16(void* buf /*dev*/, const int32_t* seg_offsets /*dev S+1*/, int segments, int images, int pixels,
+                              int channels, int pixel_stride, long long image_stride, void* stream);
 
 /* The LayerNorms of nn.TransformerEncoderLayer (refine_network.py:56-70; post-norm, eps 1e-5) on the fp32 residual
  * stream autocast keeps:  z = resid + f32(branch16);  y = LN(z)*gamma + beta  -> y32 (M,D) f32 and/or y16 (M,D) f16,
