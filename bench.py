@@ -15,9 +15,12 @@ Multi-GPU (one process per GPU, RCCL):
 127.0.0.1 and fails loudly when the node has fewer than N GPUs; under a launcher (WORLD_SIZE set) --gpus must equal
 the world size.  Rank 0 prints one JSON line.
 
-The headline (`value`, `ms_per_step`) is timed over --steps steps with nothing but the product on the stream; the
-per-kernel table (`kernels`, `roofline`) comes from a SECOND pass of the same length with two HIP events around every
-entry point (ops.KernelTimers), outside the timed region.
+The headline (`value`, `ms_per_step`) is timed over --steps steps with nothing but the product on the stream.  A plain run
+does only what the headline needs: set up, warm up, time the steps, write --dump-outputs, print the line.  `--full` adds,
+after the timed region: the register path (`register_path`), the per-kernel table (`kernels`, `roofline`, `stages`) from
+a SECOND pass of the same length with two HIP events around every entry point (ops.KernelTimers) and two more passes
+for the roofline, per-frame ingest and tracking mode (`ingest`, `tracking`), and the CPU baseline (`cpu_baseline`);
+--no-kernel-table / --no-extras / --no-cpu-baseline leave parts of it out.
 """
 import argparse
 import json
@@ -439,11 +442,15 @@ def main():
                     "hypothesis's full arithmetic")
     ap.add_argument("--no-graph", action="store_true", help="eager launches in the timed region instead of hipGraph replays of the "
                     "refine loop and of the scorer's per-hypothesis half (PoseRefinePredictor / ScorePredictor graph=False)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the records next to the headline: per-frame ingest (a1-a3) and tracking "
-                    "mode (BASELINE configs[4] at 64 hypotheses per frame, and the reference's track_one: 1 hypothesis x 2 iterations)")
+    ap.add_argument("--full", action="store_true", help="after the timed region, also measure what the headline does not need: the "
+                    "register path, the per-kernel table and roofline (instrumented passes of their own), per-frame ingest and "
+                    "tracking mode, the CPU baseline.  Off by default: a plain run prints the headline alone")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the records next to the headline: per-frame ingest (a1-a3) "
+                    "and tracking mode (BASELINE configs[4] at 64 hypotheses per frame, and the reference's track_one: 1 hypothesis x 2 "
+                    "iterations)")
     ap.add_argument("--track-frames", type=int, default=1000)
-    ap.add_argument("--no-kernel-table", action="store_true", help="skip the second (instrumented) pass")
+    ap.add_argument("--no-kernel-table", action="store_true", help="with --full: skip the instrumented passes")
     ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step returned as DIR/<name>.npy (float32): "
                     "poses (N,4,4) and scores (N,) in hypothesis order, records (ranks,N,17) = [score | pose] as the step returns "
                     "them; every input is seeded, so the same arguments give the same inputs and two builds can be compared "
@@ -451,6 +458,10 @@ def main():
     args = ap.parse_args()
     if args.steps < 1 or args.warmup < 0:
         ap.error("--steps must be >= 1 and --warmup >= 0")
+    # what runs after the timed region: nothing in a plain run
+    kernel_table = args.full and not args.no_kernel_table
+    extras = args.full and not args.no_extras
+    cpu_base = args.full and not args.no_cpu_baseline
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         _respawn(args)
@@ -555,9 +566,9 @@ def main():
     # not the headline: the same step the way estimater.register() issues it -- every hypothesis of the rotation grid starts at ONE
     # translation (estimater.py:132-133), so the observed crop of the first refine iteration is warped and stem-encoded once per
     # sub-batch (bit-identical poses; PoseRefinePredictor.predict(shared_translation=True)).  Reported next to the headline so that a
-    # driver-run record shows it; skipped when the headline already runs that way (--shared-crop) or in hypothesis mode.
+    # --full record shows it; skipped when the headline already runs that way (--shared-crop) or in hypothesis mode.
     dt_reg = None
-    if not args.shared_crop and not hyp_mode and args.precision == "fp16" and R > 0:
+    if args.full and not args.shared_crop and not hyp_mode and args.precision == "fp16" and R > 0:
         def step_register():
             p, _ = refiner.predict(rgb_t, depth_t, sc["K"], poses0, xyz_t, mesh=sc["mesh"], mesh_tensors=sc["gm"],
                                    mesh_diameter=sc["diameter"], iteration=R, shared_translation=True)
@@ -574,9 +585,9 @@ def main():
         dt_reg = time.perf_counter() - t0
     # second, instrumented pass (not part of the headline): per-entry-point HIP events on the launch stream
     timers = ops.KernelTimers()
-    if rank == 0 and not args.no_kernel_table:
+    if rank == 0 and kernel_table:
         _log("instrumented pass")
-    if not args.no_kernel_table:
+    if kernel_table:
         # the same launches (same sub-batches, same sizes), but issued on ONE stream: a HIP-event pair around a kernel that
         # shares the chip with another stream's kernels measures the mix, not the kernel
         refiner.sub.serial = scorer.sub.serial = True
@@ -592,11 +603,13 @@ def main():
     timers_full = ops.KernelTimers()
     # whether the step is split is decided per process by a stream-overlap probe + an exactness canary (overlap.py); every
     # extra pass below contains the step's collective, so under torch.distributed all ranks must take the same branch
-    split = torch.tensor([1 if len(refiner.sub.parts(N, dev)) > 1 else 0], device=dev, dtype=torch.int32)
-    if use_dist:
-        dist.all_reduce(split, op=dist.ReduceOp.MIN)
-    split = bool(split.item())
-    if not args.no_kernel_table and split:
+    split = False
+    if kernel_table:
+        split = torch.tensor([1 if len(refiner.sub.parts(N, dev)) > 1 else 0], device=dev, dtype=torch.int32)
+        if use_dist:
+            dist.all_reduce(split, op=dist.ReduceOp.MIN)
+        split = bool(split.item())
+    if kernel_table and split:
         ns = refiner.sub.n_streams
         refiner.sub.n_streams = scorer.sub.n_streams = 1
         step()
@@ -609,7 +622,7 @@ def main():
     # fourth pass: the launches of the TIMED mode (sub-batches on concurrent streams) with HIP events on their own streams:
     # busy time of the dominant kernel = union of its launch intervals, i.e. its roofline in the execution mode that is timed
     timers_conc, conc_ref, conc_wall = ops.KernelTimers(), None, None
-    if not args.no_kernel_table and not args.serialize and split:
+    if kernel_table and not args.serialize and split:
         step()
         sync()
         conc_ref = torch.cuda.Event(enable_timing=True)
@@ -672,7 +685,7 @@ def main():
             out["energy"] = {"socket_power_W_mean": pw, "J_per_step": j_step, "J_per_hypothesis": j_step / total_hyps,
                              "hypotheses_per_joule": total_hyps / j_step, "pJ_per_network_flop": j_step / (flops * 1e9) * 1e12,
                              "note": "amdgpu hwmon socket power sampled every 5 ms through the timed region x step time"}
-        if not args.no_kernel_table:
+        if kernel_table:
             ksum = timers.summary()
             kern = {}
             for name, k in ksum.items():
@@ -773,7 +786,7 @@ def main():
                 if ms > 0:
                     stages[g] = {"ms_per_step": ms, "hypothesis_passes_per_sec": passes / (ms * 1e-3)}
             out["stages"] = stages
-        if world == 1 and not args.no_extras and args.precision == "fp16":
+        if world == 1 and extras and args.precision == "fp16":
             # outside the headline's timed region, the same process and clock state: SURVEY 8(d) C5 + the per-frame ingest
             _log("extras: ingest, tracking")
             out["ingest"] = ingest_bench(dev, sc)
@@ -785,7 +798,7 @@ def main():
                 "sequence_generation_s": seq[3],
                 "config5_64hyp_2iter": tracking_bench(dev, sc, trk_ref, seq, 64, 2),
                 "track_one_1hyp_2iter": tracking_bench(dev, sc, trk_ref, seq, 1, 2)}
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and cpu_base:
             _log("cpu baseline (oracle on the host cores)")
             out["cpu_baseline"] = cpu_baseline()
         faulthandler.cancel_dump_traceback_later()

@@ -4,7 +4,7 @@ replayed per frame (foundationpose_amd/graphs.py: depth erosion + bilateral filt
 rasteriser, observed crop, RefineNet, pose update)).  Every frame is different: its own GT pose on a smooth trajectory,
 rendered by the product's rasteriser, with its own noise / dropout; per frame the uint8 colour image, the float depth
 map and the hypotheses are uploaded from pinned host memory (the H2D copies are inside the timed region).
-Round 5: the measurement itself lives in bench.py (`tracking_bench`, also part of the driver's `python bench.py` record,
+Round 5: the measurement itself lives in bench.py (`tracking_bench`, also part of the `python bench.py --full` record,
 key `tracking`); this is the stand-alone command line over it, also for the reference's own track_one (--hyps 1).
 
 Also measures the register() refine loop (252 hypotheses x 5 iterations) as ONE hipGraph against eager launches.

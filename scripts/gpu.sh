@@ -21,8 +21,8 @@ t_tests() {   # the whole GPU suite
 t_tests_fast() {   # everything but the three long parity chains
   timeout 900 python -m pytest tests/ -m gpu -q --timeout 600 -x -k "not teacher_forced and not fp32_matches_oracle and not scorer_252_vs_exact" > $O/${TAG}_pytest_gpu_fast.log 2>&1; tail -8 $O/${TAG}_pytest_gpu_fast.log | cut -c1-300
 }
-t_bench() {   # the driver's command
-  timeout 400 python bench.py --steps 20 --warmup 5 > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err; python scripts/show_bench_kernels.py $O/${TAG}_bench.json
+t_bench() {   # the full record: headline, per-kernel table, roofline, extras, CPU baseline
+  timeout 600 python bench.py --steps 20 --warmup 5 --full > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err; python scripts/show_bench_kernels.py $O/${TAG}_bench.json
 }
 bench_line() {  # name, env/lib, extra flags: one short line per variant (A/B runs on the same box)
   local name=$1 lib=$2; shift 2

@@ -1605,3 +1605,37 @@ def test_bench_under_the_launcher_with_rccl_matches_the_headline(dev):
     json.dump(rep, open(REPORT, "w"), indent=1)
     for mode, r in rep.items():
         assert abs(r["ratio"] - 1.0) <= tol[mode], rep
+
+
+def test_plain_bench_prints_the_headline_alone_and_full_adds_the_records(dev, tmp_path):
+    """`bench.py` without --full sets up, warms up, times the steps, dumps and prints the headline: none of the passes or records
+    that take runs of their own.  With --full the register path and the per-kernel table / roofline passes run after the timed
+    region (ingest / tracking and the CPU baseline are left out here for time); the headline keys mean the same in both."""
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT",
+                                                          "FP_BENCH_FORCE_DIST", "FP_BENCH_ENGINE")}
+
+    def run(*extra):
+        cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1"] + list(extra)
+        r = subprocess.run(cmd, env=env, cwd=root, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, (cmd, r.stderr[-2000:])
+        lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, r.stdout[-2000:]
+        return json.loads(lines[0]), r.stderr
+    moved = ("kernels", "roofline", "stages", "stage_raster_crop", "clock_instrumented_pass", "ingest", "tracking", "cpu_baseline")
+    plain, err = run("--dump-outputs", str(tmp_path / "plain"))
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in plain, k
+    assert plain["steps"] == 2 and plain["warmup"] == 1 and plain["higher_is_better"] is True and plain["dtype"] == "f16"
+    assert abs(plain["value"] - 252 / (plain["ms_per_step"] * 1e-3)) <= 1e-6 * plain["value"]
+    assert not [k for k in moved if k in plain] and plain["register_path"] is None, sorted(plain)
+    assert "] instrumented pass" not in err and "] extras:" not in err and "] cpu baseline" not in err, err[-2000:]
+    assert sorted(plain["dumped_outputs"]["shapes"]) == ["poses", "records", "scores"]
+    full, _ = run("--full", "--no-extras", "--no-cpu-baseline")
+    for k in ("kernels", "roofline", "stages", "stage_raster_crop"):
+        assert k in full, k
+    assert full["register_path"]["ms_per_step"] > 0 and full["roofline"]["launches_timed"] > 0
+    assert not [k for k in ("ingest", "tracking", "cpu_baseline") if k in full]
+    assert sorted(k for k in plain if k != "dumped_outputs") == sorted(k for k in full if k not in moved)
