@@ -418,6 +418,11 @@ int at_launch(const char* name, const void* qkv, void* out, int B, SEQ seqs, int
   return FP_OK;
 }
 
+// K and V of a sequence are read through buffer resources based at its first row, with 32-bit byte offsets (int arithmetic
+// in the kernel, num_records 0x7FFFFFFF): every row of a sequence, and the 64 rows of a key block before the tail clamp,
+// must lie within 2 GiB of that base, or the loads come back as zeros instead of failing
+bool at_span_ok(int S, int H) { return (long long)(S > AT_KB ? S : AT_KB) * (3ll * H * AT_D * 2) <= 0x7FFFFFFFll; }
+
 }  // namespace
 
 #ifndef AT_DEFAULT_QT
@@ -431,6 +436,7 @@ extern "C" int fp_attention_f16_fwd(const void* qkv, void* out, int B, int S, in
   FP_REQUIRE(head_dim == AT_D, "fp_attention_f16_fwd: head_dim=%d (only 128 is built)", head_dim);
   FP_REQUIRE(H > 0 && ((((size_t)qkv | (size_t)out) & 15) == 0), "fp_attention_f16_fwd: bad head count / unaligned tensors");
   FP_REQUIRE((flags & ~FP_ATT_FP16_SCORES) == 0, "fp_attention_f16_fwd: unknown flags 0x%x", flags);
+  FP_REQUIRE(at_span_ok(S, H), "fp_attention_f16_fwd: a sequence of S=%d rows of H=%d heads spans more than 2 GiB of qkv", S, H);
   const bool f16s = (flags & FP_ATT_FP16_SCORES) != 0;
   const float qscale = f16s ? (float)sqrt(1.0 / (double)head_dim) : 0.f;
   const float c = f16s ? 1.4426950408889634f : 1.4426950408889634f / sqrtf((float)head_dim);
@@ -452,6 +458,8 @@ extern "C" int fp_attention_segments_f16_fwd(const void* qkv, void* out, const i
   FP_REQUIRE(H > 0 && ((((size_t)qkv | (size_t)out) & 15) == 0) && ((size_t)seg_offsets & 3) == 0,
              "fp_attention_segments_f16_fwd: bad head count / unaligned tensors");
   FP_REQUIRE((flags & ~FP_ATT_FP16_SCORES) == 0, "fp_attention_segments_f16_fwd: unknown flags 0x%x", flags);
+  FP_REQUIRE(at_span_ok(max_S, H), "fp_attention_segments_f16_fwd: a sequence of max_S=%d rows of H=%d heads spans more than 2 GiB of qkv",
+             max_S, H);
   if (B == 0 || max_S == 0) return FP_OK;
   const bool f16s = (flags & FP_ATT_FP16_SCORES) != 0;
   const float qscale = f16s ? (float)sqrt(1.0 / (double)head_dim) : 0.f;

@@ -910,15 +910,27 @@ def rows_linear(x, w, bias=None, round_f16=False, out_f16=False, out=None):
 ATT_FP16_SCORES = 1
 
 
+def _att_head_dim(D3, n_heads, name):
+    """head size of a (.., 3*D) qkv row split into n_heads: the kernels derive the row stride from H and the head size, so a
+    row that is not exactly 3 * n_heads heads wide would be read with the wrong stride"""
+    n_heads = int(n_heads)
+    if n_heads <= 0 or D3 % (3 * n_heads):
+        raise _lib.FpAmdError(f"{name}: a qkv row of {D3} values is not [q | k | v] of {n_heads} equal heads")
+    return D3 // (3 * n_heads)
+
+
 def attention_f16(qkv, n_heads, fp16_scores=False):
     """qkv (B, S, 3*D) fp16 = in_proj output [q | k | v] -> (B, S, D) fp16 = softmax(q k^T / sqrt(hd)) v, heads merged
     (fp_attention_f16_fwd; head size D / n_heads must be 128).  fp16_scores: q * sqrt(1/hd) and the scores rounded to fp16
     (the need_weights=True branch of nn.MultiheadAttention under autocast, score_network.py:73,86)"""
+    if qkv.dim() != 3:
+        raise _lib.FpAmdError(f"attention_f16: qkv must be (B, S, 3*D), got {tuple(qkv.shape)}")
+    hd = _att_head_dim(int(qkv.shape[2]), n_heads, "attention_f16")
     qkv = _dev(qkv, torch.float16, "qkv")
     B, S, D3 = (int(v) for v in qkv.shape)
     D = D3 // 3
     out = torch.empty((B, S, D), dtype=torch.float16, device=qkv.device)
-    st = _lib.lib().fp_attention_f16_fwd(_ptr(qkv), _ptr(out), B, S, int(n_heads), D // int(n_heads),
+    st = _lib.lib().fp_attention_f16_fwd(_ptr(qkv), _ptr(out), B, S, int(n_heads), hd,
                                          ATT_FP16_SCORES if fp16_scores else 0, _stream(qkv))
     _lib.check(st, "fp_attention_f16_fwd")
     return out
@@ -965,9 +977,10 @@ class Segments:
 def attention_f16_segments(qkv, segments, n_heads, fp16_scores=False):
     """qkv (Ntot, 3*D) fp16 packed as `segments` (Segments) -> (Ntot, D) fp16: attention_f16 over every segment on its own rows,
     never across segments (fp_attention_segments_f16_fwd; each segment gets the bits of attention_f16 on its slice)"""
-    qkv = _dev(qkv, torch.float16, "qkv")
     if qkv.dim() != 2 or qkv.shape[1] % 3:
         raise _lib.FpAmdError(f"attention_f16_segments: qkv must be (Ntot, 3*D), got {tuple(qkv.shape)}")
+    hd = _att_head_dim(int(qkv.shape[1]), n_heads, "attention_f16_segments")
+    qkv = _dev(qkv, torch.float16, "qkv")
     Ntot, D = int(qkv.shape[0]), int(qkv.shape[1]) // 3
     if Ntot != segments.total:
         raise _lib.FpAmdError(f"attention_f16_segments: {Ntot} rows but the segments cover {segments.total}")
@@ -975,7 +988,7 @@ def attention_f16_segments(qkv, segments, n_heads, fp16_scores=False):
         raise _lib.FpAmdError(f"attention_f16_segments: offsets on {segments.dev.device}, qkv on {qkv.device}")
     out = torch.empty((Ntot, D), dtype=torch.float16, device=qkv.device)
     st = _lib.lib().fp_attention_segments_f16_fwd(_ptr(qkv), _ptr(out), _ptr(segments.dev), segments.B, segments.max_S, int(n_heads),
-                                                  D // int(n_heads), ATT_FP16_SCORES if fp16_scores else 0, _stream(qkv))
+                                                  hd, ATT_FP16_SCORES if fp16_scores else 0, _stream(qkv))
     _lib.check(st, "fp_attention_segments_f16_fwd")
     return out
 

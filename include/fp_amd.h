@@ -426,7 +426,8 @@ int fp_rows_linear_fwd(const void* x /*dev*/, const void* w /*dev*/, const float
  * score_network.py:52-53 (token attention) and :84-88 (attention across the hypotheses), i.e. what
  * torch.nn.functional.multi_head_attention_forward does between in_proj and out_proj:
  *   out[b, t, h*hd:(h+1)*hd] = softmax_t'(q[b,t,h,:] . k[b,t',h,:] / sqrt(hd)) v[b,t',h,:]
- * qkv (B*S, 3*H*hd) fp16 = the in_proj output [q | k | v]; out (B*S, H*hd) fp16 = the out_proj input.  hd must be 128.
+ * qkv (B*S, 3*H*hd) fp16 = the in_proj output [q | k | v]; out (B*S, H*hd) fp16 = the out_proj input.  hd must be 128, and
+ * the rows of one sequence must lie within 2 GiB of qkv: max(S, 64) * 3*H*hd * 2 bytes <= 2^31 - 1 (refused otherwise).
  * fp32 softmax statistics and accumulation, probabilities rounded to fp16 for the second product, normalisation
  * after it (flash-attention order); the (B*H, S, S) probability tensor is never formed. */
 int fp_attention_f16_fwd(const void* qkv /*dev*/, void* out /*dev*/, int B, int S, int H, int head_dim, int flags,
@@ -435,9 +436,9 @@ int fp_attention_f16_fwd(const void* qkv /*dev*/, void* out /*dev*/, int B, int 
 /* fp_attention_f16_fwd over B sequences of DIFFERENT lengths packed row after row (the scorer's cross-hypothesis attention of
  * several objects in one call, score_network.py:83-88 per object): sequence b is rows seg_offsets[b] .. seg_offsets[b+1] - 1 of qkv
  * (Ntot, 3*H*hd) and of out (Ntot, H*hd); no attention crosses a segment boundary.  seg_offsets (B+1) int32 stays on the device
- * (non-decreasing, seg_offsets[0] = 0 -- the caller's to guarantee); max_S is a host bound on every segment's length that only
- * sizes the grid.  Segments of length 0 write nothing.  Arithmetic and flags as fp_attention_f16_fwd: every segment gets the bits
- * of fp_attention_f16_fwd(B=1, S=its length) on its rows. */
+ * (non-decreasing, seg_offsets[0] = 0 -- the caller's to guarantee); max_S is a host bound on every segment's length that
+ * sizes the grid and is held to the 2 GiB span limit of S above.  Segments of length 0 write nothing.  Arithmetic and flags as
+ * fp_attention_f16_fwd: every segment gets the bits of fp_attention_f16_fwd(B=1, S=its length) on its rows. */
 int fp_attention_segments_f16_fwd(const void* qkv /*dev Ntot,3*H*hd*/, void* out /*dev Ntot,H*hd*/,
                                   const int32_t* seg_offsets /*dev B+1*/, int B, int max_S, int H, int head_dim, int flags,
                                   void* stream);

@@ -84,6 +84,13 @@ def test_argument_errors_are_reported_without_gpu():
     assert lib.fp_layernorm_res_fwd(C.c_void_p(16), C.c_void_p(16), C.c_void_p(16), 400, C.c_void_p(16), C.c_void_p(16), C.c_void_p(16), 1e-5,
                                     C.c_void_p(16), None, 4, 512, None) == -1     # residual given twice
     assert lib.fp_attention_f16_fwd(C.c_void_p(16), C.c_void_p(16), 1, 4, 4, 128, 2, None) == -1
+    # K / V are read with 32-bit offsets from a sequence's first row: a sequence spanning more than 2 GiB of qkv is refused
+    # (400 rows of 7000 heads; one row of 44000 heads, whose 64-row key block reaches past 2 GiB before the tail clamp)
+    for S, nh in ((400, 7000), (1, 44000)):
+        assert lib.fp_attention_f16_fwd(C.c_void_p(16), C.c_void_p(16), 1, S, nh, 128, 0, None) == -1
+        assert b"2 GiB" in lib.fp_last_error()
+        assert lib.fp_attention_segments_f16_fwd(C.c_void_p(16), C.c_void_p(16), C.c_void_p(16), 3, S, nh, 128, 0, None) == -1
+        assert b"2 GiB" in lib.fp_last_error()
     assert lib.fp_linear_layernorm_fwd(C.c_void_p(16), C.c_void_p(16), None, None, C.c_void_p(16), C.c_void_p(16), 400, C.c_void_p(16),
                                        C.c_void_p(16), 1e-5, C.c_void_p(16), None, 4, 256, 512, 0, None) == -1      # K != 512
     assert b"K=256" in lib.fp_last_error()
@@ -125,6 +132,19 @@ def test_ops_refuse_cpu_tensors():
     from foundationpose_amd import _lib, ops
     with pytest.raises(_lib.FpAmdError):
         ops.erode_depth(torch.zeros(4, 4))
+
+
+def test_attention_refuses_rows_that_are_not_whole_heads():
+    """D // n_heads == 128 with a row of 3 * 513 values would pass the entry point's head_dim check and be read with the stride of
+    3 * 4 heads: the wrappers refuse a qkv row that is not exactly [q | k | v] of n_heads equal heads"""
+    import pytest
+    import torch
+    from foundationpose_amd import _lib, ops
+    for width, nh in ((3 * 513, 4), (3 * 512 + 1, 4), (3 * 512, 3), (3 * 512, 0)):
+        with pytest.raises(_lib.FpAmdError, match="equal heads"):
+            ops.attention_f16(torch.zeros((1, 4, width), dtype=torch.float16), nh)
+        with pytest.raises(_lib.FpAmdError, match="equal heads|3\\*D"):
+            ops.attention_f16_segments(torch.zeros((4, width), dtype=torch.float16), ops.Segments([4], "cpu"), nh)
 
 
 def test_cluster_poses_host_op(scene):

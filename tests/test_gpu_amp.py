@@ -20,7 +20,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from amp_util import assert_equal_up_to_flips, conv_amp_ref, flip_report, geodesic, kendall_tau, r16, ulp16
+from amp_util import (ATT_GATE, assert_equal_up_to_flips, attention_blockwise_ref, attention_operands, conv_amp_ref, flip_report,
+                      geodesic, kendall_tau, r16, ulp16)
 from conftest import ROOT
 
 pytestmark = pytest.mark.gpu
@@ -321,6 +322,83 @@ def test_attention_fp16_score_policy(dev, B, S):
     assert e1 < 4e-3 and e0 < 4e-3, (e1, e0)
     if S >= 130:
         assert not torch.equal(out, plain)     # the score rounding is visible: the flag is not a no-op
+
+
+# every tail class of the kernel: half (1-32 keys) or partial or full last key block, idle waves of a 256-row query group, a
+# second / third query group
+ATT_S = [1, 2, 31, 32, 33, 63, 64, 65, 127, 128, 129, 255, 256, 257, 400, 513, 1000]
+ATT_DISTS = ("peaked", "diffuse", "late_max")
+
+
+def _attention_gate(out, S, H, fp16_scores, dist, qkv, what):
+    """out against the float64 model of the kernel's policy, recorded before it is asserted"""
+    ref, mag, slack = attention_blockwise_ref(qkv, H, fp16_scores=fp16_scores)
+    rep = flip_report(out.numpy(), ref.numpy(), mag.numpy(), slack.numpy())
+    REPORT.setdefault("kernel_flip_rates", {})[what] = rep
+    REPORT["attention_gate"] = dict(ATT_GATE)
+    assert_equal_up_to_flips(out.numpy(), ref.numpy(), mag.numpy(), slack=slack.numpy(), what=(what, S, H, dist), **ATT_GATE)
+
+
+def _arena(n, dev):
+    """(n,) fp16 view in the middle of a buffer poisoned with -7 (16-byte aligned both ends), and the buffer"""
+    pad = 4096
+    buf = torch.full((n + 2 * pad,), -7.0, dtype=torch.float16, device=dev)
+    return buf[pad:pad + n], buf, pad
+
+
+@pytest.mark.parametrize("fp16_scores", [False, True])
+@pytest.mark.parametrize("S", ATT_S)
+def test_attention_kernel_policy_vs_blockwise_model(dev, S, fp16_scores):
+    """fp_attention_f16_fwd against amp_util.attention_blockwise_ref (the running maximum per 64-key block, P rounded to fp16
+    against it, unrounded exponentials in l, 1/l at the end) up to fp32 summation-order flips, for three operand
+    distributions; H cycles through 1, 4 and 8 over the lengths"""
+    from foundationpose_amd import ops
+    i = ATT_S.index(S)
+    H = (1, 4, 8)[(i + int(fp16_scores)) % 3]
+    B = 2 if S <= 256 else 1
+    for dist in ATT_DISTS:
+        qkv = attention_operands(B, S, H, dist, seed=7919 * S + 31 * H + int(fp16_scores))
+        out = ops.attention_f16(qkv.half().to(dev), H, fp16_scores=fp16_scores).float().cpu()
+        _attention_gate(out, S, H, fp16_scores, dist, qkv, f"attention S{S} H{H} B{B} {dist}{' fp16-scores' if fp16_scores else ''}")
+
+
+@pytest.mark.parametrize("fp16_scores", [False, True])
+@pytest.mark.parametrize("H", [4, 8])
+def test_attention_segments_policy_vs_blockwise_model(dev, H, fp16_scores):
+    """fp_attention_segments_f16_fwd (the raw entry point, max_S above the longest segment, the output inside a poisoned
+    arena) against the float64 model segment by segment; then fp_attention_f16_fwd into an arena at a ragged length"""
+    import ctypes as C
+    from foundationpose_amd import _lib, ops
+    lengths = [33, 0, 1, 257, 2, 129, 0, 513, 64, 31, 1, 400, 255, 65, 128]
+    seg = ops.Segments(lengths, dev)
+    D = H * 128
+    for dist in ("peaked", "late_max"):
+        qkv = torch.cat([attention_operands(1, L, H, dist, seed=101 * j + H)[0] for j, L in enumerate(lengths) if L > 0])
+        q_dev = qkv.half().to(dev).contiguous()
+        out, buf, pad = _arena(seg.total * D, dev)
+        st = _lib.lib().fp_attention_segments_f16_fwd(C.c_void_p(q_dev.data_ptr()), C.c_void_p(out.data_ptr()), C.c_void_p(seg.dev.data_ptr()),
+                                                      seg.B, seg.max_S + 77, H, 128, ops.ATT_FP16_SCORES if fp16_scores else 0,
+                                                      ops._stream(q_dev))
+        _lib.check(st, "fp_attention_segments_f16_fwd")
+        got = buf.cpu()
+        assert bool((got[:pad] == -7).all()) and bool((got[pad + seg.total * D:] == -7).all()), "write outside the output"
+        got = got[pad:pad + seg.total * D].float().reshape(seg.total, D)
+        for k in range(len(seg)):
+            a, b = seg.rows(k)
+            if b > a:
+                _attention_gate(got[a:b][None], b - a, H, fp16_scores, dist, qkv[a:b][None],
+                                f"attention segments H{H} len {b - a} {dist}{' fp16-scores' if fp16_scores else ''}")
+    # the uniform kernel writes its (B, S, D) output and nothing around it
+    B, S = 3, 129
+    qkv = attention_operands(B, S, H, "peaked", seed=H)
+    q_dev = qkv.half().to(dev).contiguous()
+    out, buf, pad = _arena(B * S * D, dev)
+    st = _lib.lib().fp_attention_f16_fwd(C.c_void_p(q_dev.data_ptr()), C.c_void_p(out.data_ptr()), B, S, H, 128,
+                                         ops.ATT_FP16_SCORES if fp16_scores else 0, ops._stream(q_dev))
+    _lib.check(st, "fp_attention_f16_fwd")
+    got = buf.cpu()
+    assert bool((got[:pad] == -7).all()) and bool((got[pad + B * S * D:] == -7).all()), "write outside the output"
+    assert torch.equal(got[pad:pad + B * S * D].reshape(B, S, D), ops.attention_f16(q_dev, H, fp16_scores=fp16_scores).cpu())
 
 
 # ------------------------------------------------------------------ 2. encoder / plans vs the oracle
