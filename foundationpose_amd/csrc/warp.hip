@@ -12,6 +12,24 @@ struct __attribute__((aligned(4))) f3 { float x, y, z; };   // 12-byte texel, dw
 
 __device__ __forceinline__ int nn_index(float x) { return (int)rintf(x); }  // half-to-even like grid_sample nearest
 
+// The crop -> frame map, one definition for every kernel that reads the frame through a crop window (k_warp, k_depth_agreement).
+// crop_inverse: the per-hypothesis constants, the inverse of the scale + translate crop transform tf = [sx 0 tx; 0 sy ty; 0 0 1],
+// computed by ONE lane of a workgroup into LDS (inv[0..3] = 1/sx, 1/sy, -tx/sx, -ty/sy).  crop_to_frame: the frame coordinates of
+// crop pixel (i, j) as grid_sample(align_corners=False) sees them; nn_index of them is the texel a nearest read takes.
+__device__ __forceinline__ void crop_inverse(float sx, float tx, float sy, float ty, float* inv) {
+  inv[0] = 1.0f / sx;
+  inv[1] = 1.0f / sy;
+  inv[2] = (-tx) / sx;
+  inv[3] = (-ty) / sy;
+}
+
+__device__ __forceinline__ void crop_to_frame(int i, int j, float i00, float i02, float i11, float i12, float cW, float cH, float& ix,
+                                              float& iy) {
+  const float xs = fmaf((float)i, i00, i02), ys = fmaf((float)j, i11, i12);
+  ix = fmaf(xs, cW, -0.5f);
+  iy = fmaf(ys, cH, -0.5f);
+}
+
 // One output pixel: returns the 6 network channels (rgb/255 bilinear, xyz nearest + normalisation).
 template <int MODE>
 __device__ __forceinline__ void warp_pixel(const float* __restrict__ rgb, const float* __restrict__ xyz_map,
@@ -19,8 +37,8 @@ __device__ __forceinline__ void warp_pixel(const float* __restrict__ rgb, const 
                                            float i00, float i02, float i11, float i12, float cW, float cH, const fp_k9& K,
                                            float t0, float t1, float t2, float inv_r, bool normalize, int H, int W, int oh,
                                            int ow, int i, int j, float a[6]) {
-  const float xs = fmaf((float)i, i00, i02), ys = fmaf((float)j, i11, i12);
-  const float ix = fmaf(xs, cW, -0.5f), iy = fmaf(ys, cH, -0.5f);
+  float ix, iy;
+  crop_to_frame(i, j, i00, i02, i11, i12, cW, cH, ix, iy);
   // ---- rgb, bilinear with zero padding (tap order nw, ne, sw, se as torch grid_sample)
   {
     const float fx0 = floorf(ix), fy0 = floorf(iy);
@@ -123,10 +141,7 @@ __global__ __launch_bounds__(256) void k_warp(const float* __restrict__ rgb, con
   const float* tf = tfs + (size_t)n * 9;
   const float sx = tf[0], tx = tf[2], sy = tf[4], ty = tf[5];
   if (threadIdx.x == 0) {
-    inv_tf[0] = 1.0f / sx;
-    inv_tf[1] = 1.0f / sy;
-    inv_tf[2] = (-tx) / sx;
-    inv_tf[3] = (-ty) / sy;
+    crop_inverse(sx, tx, sy, ty, inv_tf);
     if (MULTI) {
       const int o = objs.obj ? objs.obj[n] : 0;
       const float d = (unsigned)o < (unsigned)objs.M ? (float)objs.diam[o] : __builtin_nanf("");
@@ -173,6 +188,23 @@ __global__ __launch_bounds__(256) void k_warp(const float* __restrict__ rgb, con
   }
 }
 
+static WarpConst warp_const(int H, int W, int ow) {
+  WarpConst wc;
+  wc.cW = (float)W / (float)(W - 1);
+  wc.cH = (float)H / (float)(H - 1);
+  {   // p / ow for p < oh * ow <= 2^20 as umulhi(p, mul) >> shr (exact: ceil(2^(31+lg) / ow) with lg = ceil(log2 ow)); 0 = divisor 1
+    wc.mul_ow = 0; wc.shr_ow = 0;
+    if (ow > 1) {
+      int lg = 0;
+      while ((1u << lg) < (unsigned)ow) ++lg;
+      const int sh = 31 + lg;
+      wc.mul_ow = (unsigned)(((1ull << sh) + (unsigned)ow - 1) / (unsigned)ow);
+      wc.shr_ow = (unsigned)(sh - 32);
+    }
+  }
+  return wc;
+}
+
 template <bool MULTI, bool VIEWS = false>
 static int warp_launch(const char* name, const float* rgb, const float* xyz_map, const float* depth, const float* tf_to_crops,
                        const float* K9, const float* poses, float inv_r, const WarpObjects& objs, int flags, int mode, int H,
@@ -187,19 +219,7 @@ static int warp_launch(const char* name, const float* rgb, const float* xyz_map,
   if (!VIEWS)
     for (int i = 0; i < 9; ++i) K.v[i] = K9[i];
   dim3 grid(fp_cdiv(oh * ow, 256), N), block(256);
-  WarpConst wc;
-  wc.cW = (float)W / (float)(W - 1);
-  wc.cH = (float)H / (float)(H - 1);
-  {   // p / ow for p < oh * ow <= 2^20 as umulhi(p, mul) >> shr (exact: ceil(2^(31+lg) / ow) with lg = ceil(log2 ow)); 0 = divisor 1
-    wc.mul_ow = 0; wc.shr_ow = 0;
-    if (ow > 1) {
-      int lg = 0;
-      while ((1u << lg) < (unsigned)ow) ++lg;
-      const int sh = 31 + lg;
-      wc.mul_ow = (unsigned)(((1ull << sh) + (unsigned)ow - 1) / (unsigned)ow);
-      wc.shr_ow = (unsigned)(sh - 32);
-    }
-  }
+  const WarpConst wc = warp_const(H, W, ow);
   if constexpr (VIEWS) {
     if (mode == FP_MODE_REFINE)
       hipLaunchKernelGGL((k_warp<FP_MODE_REFINE, MULTI, fp_views>), grid, block, 0, (hipStream_t)stream, rgb, xyz_map, depth,
@@ -257,4 +277,81 @@ extern "C" int fp_warp_crops_views(const float* rgb, const float* xyz_map, const
   const fp_views vt = {Ks, view, V};
   return warp_launch<true, true>("fp_warp_crops_views", rgb, xyz_map, depth, tf_to_crops, nullptr, poses, 0.f, objs, flags, mode,
                                  H, W, N, oh, ow, B, stream, vt);
+}
+
+// fp_depth_agreement: the render's depth of hypothesis n against the observed z the REFINE warp reads for the same crop pixel (the
+// nearest texel of frame view[n]'s xyz map through crop_inverse / crop_to_frame / nn_index, 0 outside the frame), classified per pixel
+// and counted per hypothesis: [model, valid, agree, behind] (include/fp_amd.h).  Grid and lanes as k_warp: one lane per crop pixel,
+// n = blockIdx.y.  Each wave counts its pixels with a ballot, the workgroup sums its waves through LDS, and four lanes add the sums
+// with one integer atomic each: integer addition is associative, so the counts are exact and the same on every replay whatever order
+// the workgroups finish in.  An index outside 0..V-1 reads nothing (z_o = 0 everywhere: only `model` counts).
+constexpr int kAgreeWaves = 256 / 64;
+
+__global__ __launch_bounds__(256) void k_depth_agreement(const float* __restrict__ depth_crops, const float* __restrict__ xyz_map,
+                                                         const float* __restrict__ tfs, fp_views vt, int H, int W, int oh, int ow,
+                                                         float tol, WarpConst wc, int32_t* __restrict__ counts) {
+  __shared__ float inv_tf[4];
+  __shared__ int part[4][kAgreeWaves];   // [count][wave]
+  const int n = blockIdx.y;
+  if (threadIdx.x == 0) {
+    const float* tf = tfs + (size_t)n * 9;
+    crop_inverse(tf[0], tf[2], tf[4], tf[5], inv_tf);
+  }
+  __syncthreads();
+  const int npx = oh * ow;
+  const int p = blockIdx.x * blockDim.x + threadIdx.x;
+  const int v = fp_view_of(vt, n);
+  bool model = false, valid = false, agree = false, behind = false;
+  if (p < npx) {   // no early return: every lane of the workgroup takes part in the ballots and the barrier below
+    const int j = wc.mul_ow ? (int)(__umulhi((unsigned)p, wc.mul_ow) >> wc.shr_ow) : p;
+    const int i = p - j * ow;
+    const float zr = depth_crops[(size_t)n * npx + p];
+    float ix, iy;
+    crop_to_frame(i, j, inv_tf[0], inv_tf[2], inv_tf[1], inv_tf[3], wc.cW, wc.cH, ix, iy);
+    const int qx = nn_index(ix), qy = nn_index(iy);
+    float zo = 0.f;
+    if (v >= 0 && qx >= 0 && qx < W && qy >= 0 && qy < H) zo = xyz_map[(((size_t)v * H + qy) * W + qx) * 3 + 2];
+    const float d = zo - zr;
+    model = zr > 0.f;
+    valid = model && zo >= 0.001f;
+    agree = valid && fabsf(d) <= tol;
+    behind = valid && d > tol;
+  }
+  const unsigned long long bm = __ballot(model), bv = __ballot(valid), ba = __ballot(agree), bb = __ballot(behind);
+  const int wave = threadIdx.x >> 6;
+  if ((threadIdx.x & 63) == 0) {
+    part[0][wave] = __popcll(bm);
+    part[1][wave] = __popcll(bv);
+    part[2][wave] = __popcll(ba);
+    part[3][wave] = __popcll(bb);
+  }
+  __syncthreads();
+  if (threadIdx.x < 4) {
+    int s = 0;
+#pragma unroll
+    for (int w = 0; w < kAgreeWaves; ++w) s += part[threadIdx.x][w];
+    if (s) atomicAdd(counts + (size_t)n * 4 + threadIdx.x, s);
+  }
+}
+
+extern "C" int fp_depth_agreement(const float* depth_crops, const float* xyz_map, const float* tf_to_crops, const int32_t* view, int V,
+                                  int H, int W, int N, int oh, int ow, float tol, int32_t* counts, void* stream) {
+  FP_REQUIRE(N >= 0 && N <= 65535, "fp_depth_agreement: N=%d outside 0..65535 (the grid limit; chunk the batch)", N);
+  FP_REQUIRE(oh >= 1 && ow >= 1 && H >= 1 && W >= 1 && V >= 1,
+             "fp_depth_agreement: sizes must be >= 1 (oh=%d, ow=%d, H=%d, W=%d, V=%d)", oh, ow, H, W, V);
+  FP_REQUIRE((long long)oh * ow <= (1 << 20), "fp_depth_agreement: crop %dx%d has more than 2^20 pixels", oh, ow);
+  FP_REQUIRE(view || V == 1, "fp_depth_agreement: view is NULL but there are %d views", V);
+  FP_REQUIRE(tol >= 0.f && __builtin_isfinite(tol), "fp_depth_agreement: tol=%g must be finite and >= 0", (double)tol);
+  FP_REQUIRE(xyz_map && ((depth_crops && tf_to_crops && counts) || N == 0), "fp_depth_agreement: NULL tensor");
+  if (N == 0) return FP_OK;
+  const hipError_t e = hipMemsetAsync(counts, 0, (size_t)N * 4 * sizeof(int32_t), (hipStream_t)stream);
+  if (e != hipSuccess) {
+    fp_set_error("fp_depth_agreement: zeroing the counts failed: %s", hipGetErrorString(e));
+    return FP_ERR_LAUNCH;
+  }
+  const fp_views vt = {nullptr, view, V};
+  hipLaunchKernelGGL(k_depth_agreement, dim3(fp_cdiv(oh * ow, 256), N), dim3(256), 0, (hipStream_t)stream, depth_crops, xyz_map,
+                     tf_to_crops, vt, H, W, oh, ow, tol, warp_const(H, W, ow), counts);
+  FP_CHECK_LAUNCH("fp_depth_agreement");
+  return FP_OK;
 }

@@ -45,6 +45,7 @@ class FoundationPose:
         self.scorer = scorer if scorer is not None else ScorePredictor(device=device)
         self.refiner = refiner if refiner is not None else PoseRefinePredictor(device=device)
         self.pose_last = None  # used for tracking; w.r.t. the centred mesh
+        self.depth_agreement = None   # ops.DepthAgreement of the last tracking call made with an agreement_tol (None without)
 
     # ------------------------------------------------------------------ estimater.py:44-78
     def reset_object(self, model_pts, model_normals, symmetry_tfs=None, mesh=None):
@@ -185,22 +186,29 @@ class FoundationPose:
         return -torch.ones(len(poses), device=self.device, dtype=torch.float)
 
     # ------------------------------------------------------------------ estimater.py:250-268
-    def track_one(self, rgb, depth, K, iteration, extra={}):
+    def track_one(self, rgb, depth, K, iteration, extra={}, agreement_tol=None):
+        """agreement_tol (metres; not in the reference's signature): also check the tracked pose against the observed depth
+        (PoseRefinePredictor.depth_check on the xyz map the refine loop read) into self.depth_agreement and extra["depth_agreement"]
+        (an ops.DepthAgreement); None: no check, self.depth_agreement = None.  The pose is the same either way."""
+        tol = None if agreement_tol is None else ops._check_tol(agreement_tol, "track_one")
         if self.pose_last is None:
             logging.info("Please init pose by register first")
             raise RuntimeError
+        self.depth_agreement = None
         if self.track_graph:
             # same arithmetic, one hipGraph launch per frame (foundationpose_amd/graphs.py); re-captured when the
-            # frame size, intrinsics or iteration count change
-            key = (tuple(np.asarray(depth).shape[:2]), np.asarray(K, dtype=np.float64).tobytes(), int(iteration))
+            # frame size, intrinsics, iteration count or agreement tolerance change
+            key = (tuple(np.asarray(depth).shape[:2]), np.asarray(K, dtype=np.float64).tobytes(), int(iteration), tol)
             if self._tracker is None or self._tracker_key != key:
                 from .graphs import GraphedTracker
                 H, W = key[0]
                 self._tracker = GraphedTracker(self.refiner, self.mesh_tensors, self.diameter, K, H, W, n_hyp=1,
-                                               iteration=iteration, device=self.device).capture()
+                                               iteration=iteration, device=self.device, agreement_tol=tol).capture()
                 self._tracker_key = key
             pose = self._tracker.step(rgb, depth, self.pose_last.reshape(1, 4, 4)).clone()
             self.pose_last = pose
+            if tol is not None:
+                self.depth_agreement = extra["depth_agreement"] = ops.DepthAgreement.rows(self._tracker.agreement)[0]
             return (pose @ self.get_tf_to_centered_mesh()).data.cpu().numpy().reshape(4, 4)
         depth_t = torch.as_tensor(depth, device=self.device, dtype=torch.float).contiguous()
         depth_t = ops.erode_depth(depth_t, radius=2)
@@ -213,19 +221,28 @@ class FoundationPose:
         if self.debug >= 2:
             extra["vis"] = vis
         self.pose_last = pose
+        if tol is not None:
+            from .Utils import get_mesh_handle
+            with torch.inference_mode():
+                H, W = int(depth_t.shape[0]), int(depth_t.shape[1])
+                table = self.refiner.depth_check(pose.reshape(-1, 4, 4).contiguous(), xyz_map, K, H, W, get_mesh_handle(self.mesh_tensors),
+                                                 self.diameter, tol)
+            self.depth_agreement = extra["depth_agreement"] = ops.DepthAgreement.rows(table)[0]
         return (pose @ self.get_tf_to_centered_mesh()).data.cpu().numpy().reshape(4, 4)
 
     track = track_one  # the north-star calls it track(); the reference method is track_one
 
 
-def track_objects(estimators, rgb, depth, K, iteration=2):
+def track_objects(estimators, rgb, depth, K, iteration=2, agreement_tol=None):
     """track_one for several objects in one frame: ONE batched refine loop over the objects' hypotheses (one each, from every
     estimator's pose_last), replayed as captured hipGraphs (graphs.GraphedTracker over the objects' meshes) on one shared depth
     ingest, instead of len(estimators) separate calls.  Per object the result is what its own track_one computes (the hypotheses of
     a call never mix; each one draws its own mesh and uses its own diameter).  Every estimator must be registered and all must share
     ONE refiner object (its network and configuration are the loop's).  The captured tracker is cached on that refiner under
     (estimators, frame size, K, iteration), like track_one's.  -> [4x4 np.ndarray] per estimator, in its original mesh frame;
-    updates each pose_last.  register_objects is the batched register()."""
+    updates each pose_last.  register_objects is the batched register().  agreement_tol (metres): also check every tracked pose against
+    the observed depth (GraphedTracker agreement_tol) and set each estimator's depth_agreement (an ops.DepthAgreement; None without)."""
+    tol = None if agreement_tol is None else ops._check_tol(agreement_tol, "track_objects")
     ests = list(estimators)
     if not ests:
         raise ValueError("track_objects: no estimators")
@@ -239,17 +256,18 @@ def track_objects(estimators, rgb, depth, K, iteration=2):
         raise ValueError("track_objects: an estimator is listed twice")
     dev = ests[0].device
     hw = tuple(np.asarray(depth).shape[:2]) if not torch.is_tensor(depth) else tuple(depth.shape[:2])
-    key = (tuple((id(e), id(e.mesh_tensors)) for e in ests), hw, np.asarray(K, dtype=np.float64).tobytes(), int(iteration))
+    key = (tuple((id(e), id(e.mesh_tensors)) for e in ests), hw, np.asarray(K, dtype=np.float64).tobytes(), int(iteration), tol)
     cached = getattr(refiner, "_objects_tracker", None)
     if cached is None or cached[0] != key:
         from .graphs import GraphedTracker
         trk = GraphedTracker(refiner, [e.mesh_tensors for e in ests], [e.diameter for e in ests], K, hw[0], hw[1], n_hyp=1,
-                             iteration=iteration, device=dev).capture()
+                             iteration=iteration, device=dev, agreement_tol=tol).capture()
         # the entry keeps the estimators and their mesh dicts alive, so the ids of its key cannot be reused while it is cached
         cached = refiner._objects_tracker = (key, trk, ests, [e.mesh_tensors for e in ests])
     trk = cached[1]
     start = torch.stack([e.pose_last.reshape(4, 4).to(dev, torch.float32) for e in ests])
     out = trk.step(rgb, depth, start).clone()
+    _set_agreement(ests, trk)
     poses = []
     for k, e in enumerate(ests):
         e.pose_last = out[k:k + 1]
@@ -257,18 +275,27 @@ def track_objects(estimators, rgb, depth, K, iteration=2):
     return poses
 
 
+def _set_agreement(ests, trk):
+    """each estimator's depth_agreement from a tracker's table (one copy; one hypothesis per estimator), or None without a check"""
+    rows = [None] * len(ests) if trk.agreement is None else ops.DepthAgreement.rows(trk.agreement)
+    for e, r in zip(ests, rows):
+        e.depth_agreement = r
+
+
 def _frame_hw(f):
     return tuple(f.shape[:2]) if torch.is_tensor(f) else tuple(np.asarray(f).shape[:2])
 
 
-def track_views(estimators, views, rgbs, depths, Ks, iteration=2):
+def track_views(estimators, views, rgbs, depths, Ks, iteration=2, agreement_tol=None):
     """track_one for objects in several camera frames at once: estimator k is tracked on frame views[k] (rgbs[v], depths[v] with
     intrinsics Ks[v]), all in ONE batched refine loop over one hypothesis per estimator, replayed as captured hipGraphs
     (graphs.GraphedTracker with views) on one batched depth ingest of all frames.  Per estimator the result is what its own track_one
     on its frame computes; two estimators may share a mesh (one object seen by two cameras, each pose in its own camera's frame).
     Every estimator must be registered, listed once, and all must share ONE refiner object; the frames must have one size.  The
     captured tracker is cached on that refiner, like track_objects'.  -> [4x4 np.ndarray] per estimator, in its original mesh
-    frame; updates each pose_last."""
+    frame; updates each pose_last.  agreement_tol (metres): also check every tracked pose against its frame's observed depth and set
+    each estimator's depth_agreement, as track_objects does."""
+    tol = None if agreement_tol is None else ops._check_tol(agreement_tol, "track_views")
     ests = list(estimators)
     if not ests:
         raise ValueError("track_views: no estimators")
@@ -296,22 +323,75 @@ def track_views(estimators, views, rgbs, depths, Ks, iteration=2):
     dev = ests[0].device
     hw = hws.pop()
     Kb = b"".join(np.asarray(K, dtype=np.float64).reshape(9).tobytes() for K in Ks)
-    key = (tuple((id(e), id(e.mesh_tensors)) for e in ests), tuple(views), hw, Kb, int(iteration))
+    key = (tuple((id(e), id(e.mesh_tensors)) for e in ests), tuple(views), hw, Kb, int(iteration), tol)
     cached = getattr(refiner, "_views_tracker", None)
     if cached is None or cached[0] != key:
         from .graphs import GraphedTracker
         trk = GraphedTracker(refiner, [e.mesh_tensors for e in ests], [e.diameter for e in ests], Ks, hw[0], hw[1], n_hyp=1,
-                             iteration=iteration, device=dev, views=views).capture()
+                             iteration=iteration, device=dev, views=views, agreement_tol=tol).capture()
         # the entry keeps the estimators and their mesh dicts alive, so the ids of its key cannot be reused while it is cached
         cached = refiner._views_tracker = (key, trk, ests, [e.mesh_tensors for e in ests])
     trk = cached[1]
     start = torch.stack([e.pose_last.reshape(4, 4).to(dev, torch.float32) for e in ests])
     out = trk.step(rgbs, depths, start).clone()
+    _set_agreement(ests, trk)
     poses = []
     for k, e in enumerate(ests):
         e.pose_last = out[k:k + 1]
         poses.append((out[k] @ e.get_tf_to_centered_mesh()).data.cpu().numpy().reshape(4, 4))
     return poses
+
+
+def depth_agreement(estimators, depths, Ks, views=None, tol=0.01):
+    """How well each estimator's current pose_last agrees with the observed depth: estimator k's pose on frame views[k] of depths
+    (intrinsics Ks[views[k]]), or with views=None on the one frame `depths` with the one K `Ks` -- the check the trackers run with
+    agreement_tol, on a registration or re-registration (register / register_objects / register_views) without changing them.  The
+    depth goes through the tracking ingest (erode, bilateral, back-projection in f32: ops.ingest_frames for several views); the crop
+    windows and crop size are those of the estimators' ONE shared refiner.  tol: absolute, in metres.
+    -> [ops.DepthAgreement] per estimator (one device-to-host copy)."""
+    t = ops._check_tol(tol, "depth_agreement")
+    ests = list(estimators)
+    if not ests:
+        raise ValueError("depth_agreement: no estimators")
+    refiner = ests[0].refiner
+    if any(e.refiner is not refiner for e in ests):
+        raise ValueError("depth_agreement: the estimators must share one refiner object (FoundationPose(..., refiner=shared))")
+    if len({id(e) for e in ests}) != len(ests):
+        raise ValueError("depth_agreement: an estimator is listed twice")
+    for i, e in enumerate(ests):
+        if e.pose_last is None:
+            raise RuntimeError(f"depth_agreement: estimator {i} is not registered (call register first)")
+    dev = ests[0].device
+    vt = None
+    with torch.inference_mode():
+        if views is None:
+            d = torch.as_tensor(depths, device=dev, dtype=torch.float).contiguous()
+            d = ops.bilateral_filter_depth(ops.erode_depth(d, radius=2), radius=2)
+            xyz = ops.depth_to_xyz(d, Ks, zfar=float("inf"), f64_internal=False)
+            H, W = int(d.shape[0]), int(d.shape[1])
+            K = Ks
+        else:
+            views = [int(v) for v in views]
+            depths, Ks = list(depths), list(Ks)
+            V = len(depths)
+            if len(views) != len(ests):
+                raise ValueError(f"depth_agreement: {len(ests)} estimators but {len(views)} view indices")
+            if V < 1 or len(Ks) != V:
+                raise ValueError(f"depth_agreement: {V} depth frames and {len(Ks)} intrinsics: need one of each per view")
+            if any(not 0 <= v < V for v in views):
+                raise ValueError(f"depth_agreement: a view index outside 0..{V - 1}")
+            if len({_frame_hw(f) for f in depths}) != 1:
+                raise ValueError("depth_agreement: the frames differ in size; all views must have one H x W")
+            stack = torch.stack([torch.as_tensor(f, device=dev, dtype=torch.float) for f in depths]).contiguous()
+            vt = ops.Views(Ks, views, dev)
+            xyz = ops.ingest_frames(stack, vt, f64_internal=False)
+            H, W = int(stack.shape[1]), int(stack.shape[2])
+            K = None
+        mset, diam = _object_tables(refiner, ests)
+        obj = torch.arange(len(ests), dtype=torch.int32, device=dev)
+        P = torch.stack([e.pose_last.reshape(4, 4).to(dev, torch.float32) for e in ests]).contiguous()
+        table = refiner.depth_check(P, xyz, K, H, W, mset, diam, t, obj=obj, views=vt)
+    return ops.DepthAgreement.rows(table)
 
 
 def _object_tables(refiner, ests):

@@ -133,9 +133,15 @@ class GraphedTracker:
     Several camera frames per step: K = [K_0 .. K_{V-1}] (one intrinsics matrix per view, all frames H x W) and views = [v_0 ..
     v_{M-1}] (object k lives in view views[k]; the meshes are a list).  The static inputs are then (V,H,W,3) / (V,H,W) frame stacks,
     the pre-graph is the batched ingest (three launches for all views, ops.ingest_frames) and the refine loop reads hypothesis n's
-    frame and K through an ops.Views; step() takes the V frames as lists or stacked tensors.  Without views nothing changes."""
+    frame and K through an ops.Views; step() takes the V frames as lists or stacked tensors.  Without views nothing changes.
 
-    def __init__(self, refiner, mesh_tensors, mesh_diameter, K, H, W, n_hyp=1, iteration=2, device=None, views=None):
+    agreement_tol (metres): every frame also checks the refined poses against the observed depth (PoseRefinePredictor.depth_check,
+    inside each part's graph after its last iteration, on the xyz map the loop read) into the static (N, 4) int32 table `agreement`
+    [model, valid, agree, behind] (ops.DepthAgreement).  The check only reads the poses: poses_out is bit-identical to a tracker built
+    without it.  None (default): no check, `agreement` is None."""
+
+    def __init__(self, refiner, mesh_tensors, mesh_diameter, K, H, W, n_hyp=1, iteration=2, device=None, views=None, agreement_tol=None):
+        self.agreement_tol = None if agreement_tol is None else ops._check_tol(agreement_tol, "GraphedTracker")
         self.refiner = refiner
         self.multi = isinstance(mesh_tensors, (list, tuple))
         if views is not None and not self.multi:
@@ -186,6 +192,7 @@ class GraphedTracker:
                                       dtype=torch.uint8, device=self.dev) for a, b in self.parts]
         self.outs = refiner.alloc_outputs(self.N, self.dev) + (self.R,)
         self.poses_out = self.outs[0]
+        self.agreement = None if self.agreement_tol is None else torch.zeros((self.N, 4), dtype=torch.int32, device=self.dev)
         self.xyz = None
         self.g_pre, self.g_part = None, []
         self._have_output = False
@@ -199,6 +206,13 @@ class GraphedTracker:
     def _part(self, h, xyz):
         self.refiner.refine_part(h, self.parts[h], self.rgb, xyz, self.poses_in, self.K, self.H, self.W, self.handle,
                                  self.diameter, range(self.R), self.outs, self.workspace[h], obj=self.obj, views=self.views)
+        if self.agreement_tol is not None:
+            a, b = self.parts[h]
+            P = self.poses_out if self.R > 0 else self.poses_in       # no iteration: the output is the input (copied after the join)
+            self.refiner.depth_check(P[a:b], xyz, self.K, self.H, self.W, self.handle, self.diameter, self.agreement_tol,
+                                     out=self.agreement[a:b], workspace=self.workspace[h],
+                                     obj=None if self.obj is None else self.obj.dev[a:b],
+                                     views=None if self.views is None else self.views.rows(a, b))
 
     def _body(self, xyz=None):
         """the frame without graphs: same launches, same streams (xyz given: the refine loop alone, on that map)"""

@@ -1,5 +1,6 @@
 """torch-tensor front-end of the C ABI (device pointers + current HIP stream).  Plumbing only."""
 import ctypes as C
+from typing import NamedTuple
 
 import numpy as np
 import torch
@@ -504,6 +505,90 @@ def warp_crops(rgb, xyz_map, depth, tf_to_crops, K, poses, mesh_diameter, mode, 
                                   float(np.float32(mesh_diameter)), flags, int(mode), H, W, N, oh, ow, _ptr(B), _stream(P))
     _lib.check(st, "fp_warp_crops")
     return B
+
+
+def _check_tol(tol, what):
+    """the tolerance of a depth-agreement check: a finite number >= 0 (metres), refused with ValueError before any device work"""
+    try:
+        t = float(tol)
+    except (TypeError, ValueError):
+        raise ValueError(f"{what}: agreement tolerance must be a number, got {tol!r}") from None
+    if not (np.isfinite(t) and t >= 0.0):
+        raise ValueError(f"{what}: agreement tolerance must be finite and >= 0 (metres), got {tol!r}")
+    return t
+
+
+def depth_agreement(depth_crops, xyz_map, tf_to_crops, tol, views=None, out=None):
+    """fp_depth_agreement: per hypothesis, how the render's depth crops (N,oh,ow) -- render_crops(want=("depth",)) at the pose through
+    the crop windows tf_to_crops (N,3,3) -- agree with the observed xyz map (H,W,3) through the same windows (the texel the REFINE warp
+    reads).  -> (N, 4) int32 device tensor [model, valid, agree, behind] (include/fp_amd.h); `tol` absolute, in metres.  out: a
+    caller-owned (N, 4) int32 tensor to fill (a captured graph owns its output).  Several views: views = an ops.Views and xyz_map the
+    (V,H,W,3) stack."""
+    t = _check_tol(tol, "depth_agreement")
+    dc = _dev(depth_crops, torch.float32, "depth_crops")
+    xm = _dev(xyz_map, torch.float32, "xyz_map")
+    tf = _dev(tf_to_crops, torch.float32, "tf_to_crops")
+    if dc.dim() != 3:
+        raise _lib.FpAmdError(f"depth_agreement: depth_crops must be (N,oh,ow), got {tuple(dc.shape)}")
+    N, oh, ow = (int(x) for x in dc.shape)
+    if tuple(tf.shape[-2:]) != (3, 3) or tf.numel() != 9 * N:
+        raise _lib.FpAmdError(f"depth_agreement: {N} depth crops but tf_to_crops of shape {tuple(tf.shape)}")
+    if views is not None:
+        vt = _views(views, "depth_agreement", N)
+        if xm.dim() != 4 or int(xm.shape[0]) != vt.V or int(xm.shape[3]) != 3:
+            raise _lib.FpAmdError(f"depth_agreement: views need a ({vt.V},H,W,3) xyz stack, got {tuple(xm.shape)}")
+        V, H, W = int(xm.shape[0]), int(xm.shape[1]), int(xm.shape[2])
+        vw = vt.dev
+    else:
+        if xm.dim() != 3 or int(xm.shape[2]) != 3:
+            raise _lib.FpAmdError(f"depth_agreement: xyz_map must be (H,W,3), got {tuple(xm.shape)}")
+        V, H, W = 1, int(xm.shape[0]), int(xm.shape[1])
+        vw = None
+    if out is None:
+        out = torch.empty((N, 4), dtype=torch.int32, device=dc.device)
+    else:
+        out = _dev(out, torch.int32, "out")
+        if tuple(out.shape) != (N, 4):
+            raise _lib.FpAmdError(f"depth_agreement: out must be ({N}, 4), got {tuple(out.shape)}")
+    _lib.check(_lib.lib().fp_depth_agreement(_ptr(dc), _ptr(xm), _ptr(tf), _ptr(vw), V, H, W, N, oh, ow, t, _ptr(out), _stream(dc)),
+               "fp_depth_agreement")
+    return out
+
+
+class DepthAgreement(NamedTuple):
+    """one row of depth_agreement's table on the host: crop pixels the model covers (`model`), those of them with an observed depth
+    (`valid`), those whose observed depth is within tol of the model's (`agree`) and those where the sensor sees more than tol past the
+    model's surface (`behind`).  `front` = valid - agree - behind: something in front of the model.  A fraction over 0 is NaN."""
+    model: int
+    valid: int
+    agree: int
+    behind: int
+
+    @property
+    def front(self):
+        return self.valid - self.agree - self.behind
+
+    @staticmethod
+    def _frac(a, b):
+        return a / b if b else float("nan")
+
+    @property
+    def valid_frac(self):
+        return self._frac(self.valid, self.model)
+
+    @property
+    def agree_frac(self):
+        return self._frac(self.agree, self.valid)
+
+    @property
+    def behind_frac(self):
+        return self._frac(self.behind, self.valid)
+
+    @classmethod
+    def rows(cls, table):
+        """[DepthAgreement] per row of a (N, 4) table (a device tensor: one device-to-host copy)"""
+        a = table.cpu().numpy() if torch.is_tensor(table) else np.asarray(table)
+        return [cls(*(int(x) for x in r)) for r in np.asarray(a, dtype=np.int64).reshape(-1, 4)]
 
 
 def pose_update(trans, rot, poses, rot_rep="axis_angle", normalize_xyz=True, trans_normalizer=(1.0, 1.0, 1.0),
@@ -1112,6 +1197,7 @@ replicate_channels = _timed("fp_replicate_rows_f16", replicate_channels,
 replicate_segments = _timed("fp_replicate_segments_f16", replicate_segments,
                             lambda buf, seg, c0, c1: (2.0 * (seg.total - len(seg)) * buf.shape[1] * buf.shape[2] * (c1 - c0), 0.0))
 mask_depth_stats = _timed("fp_mask_depth_stats", mask_depth_stats)
+depth_agreement = _timed("fp_depth_agreement", depth_agreement)
 layernorm_res = _timed("fp_layernorm_res_fwd", layernorm_res,
                        lambda br, *a, **k: ((2.0 + (4.0 if k.get("x32") is not None else 2.0) + (4.0 if k.get("want32", True) else 0.0)
                                              + (2.0 if k.get("want16", True) else 0.0)) * br.numel(), 0.0))

@@ -316,6 +316,19 @@ class PoseRefinePredictor:
                                          tf_to_crops=tf_to_crops, input_w=float(self.cfg["input_resize"][0]), obj=o, views=vw)
         return state
 
+    def depth_check(self, poses, xyz_t, K, H, W, mesh_handle, mesh_diameter, tol, out=None, workspace=None, obj=None, views=None):
+        """How well the poses (N,4,4) agree with the observed xyz map the refine loop read: the crop windows of the loop (crop_ratio,
+        input_resize; the two-pose quirk is not applied: every pose is judged through its own window), the render's depth there and
+        ops.depth_agreement against xyz_t through the same windows, on the CURRENT stream -> the (N, 4) int32 table [model, valid,
+        agree, behind] (`out` if given).  The arguments are refine_part's for the same rows: mesh_handle a mesh or an ops.MeshSet with
+        its diameter table, obj the rows' device object index, views the rows' ops.Views; workspace the rasteriser scratch of the part.
+        Writes only its own buffers: the poses and the loop's outputs are read, never written."""
+        oh, ow, _, _ = self._loop_constants()
+        tf_to_crops, bbox2d = ops.crop_windows(poses, K, mesh_diameter, self.cfg["crop_ratio"], (ow, oh), obj=obj, views=views)
+        depth = ops.render_crops(mesh_handle, poses, bbox2d, K, H, W, out_hw=(oh, ow), mesh_diameter=mesh_diameter, xyz_thr=0.001,
+                                 normalize_xyz=False, want=("depth",), workspace=workspace, obj=obj, views=views)["depth"]
+        return ops.depth_agreement(depth, xyz_t, tf_to_crops, tol, views=views, out=out)
+
     def refine_device(self, rgb_t, xyz_t, poses, K, H, W, mesh_handle, mesh_diameter, iteration, workspace=None,
                       shared_translation=False, obj=None, views=None):
         """The refine loop on device tensors only (predict_pose_refine.py:182-235).  No host round trip, no host-side

@@ -72,8 +72,9 @@ const char* fp_last_error(void);
  *   214 -> 215: + fp_attention_segments_f16_fwd (addition only): attention over ragged sequences (several objects' hypotheses).
  *   215 -> 216: several views per call (additions only): + fp_crop_windows_views, fp_render_crops_views, fp_warp_crops_views,
  *               fp_pose_update_views, fp_depth_erode_frames, fp_depth_bilateral_frames, fp_depth_to_xyz_frames.
- *   216 -> 217: registration in several views per call (additions only): + fp_mask_depth_stats, fp_replicate_segments_f16. */
-#define FP_AMD_ABI_VERSION 217
+ *   216 -> 217: registration in several views per call (additions only): + fp_mask_depth_stats, fp_replicate_segments_f16.
+ *   217 -> 218: + fp_depth_agreement (addition only): per-hypothesis depth agreement of a rendered pose with the observed frame. */
+#define FP_AMD_ABI_VERSION 218
 int fp_version(void);
 
 /* Utils.py:104-130 make_mesh_tensors: records caller-owned device tensors.
@@ -153,6 +154,24 @@ int fp_warp_crops_views(const float* rgb /*dev V,H,W,3*/, const float* xyz_map /
                         const float* tf_to_crops /*dev N,9*/, const float* Ks /*dev V,9*/, const int32_t* view /*dev N|NULL*/, int V,
                         const float* poses /*dev N,16*/, const double* diameters /*dev M*/, const int32_t* obj /*dev N|NULL*/, int M,
                         int flags, int mode, int H, int W, int N, int oh, int ow, void* B /*dev N,6,oh,ow*/, void* stream);
+/* How well each pose agrees with the observed depth (the signal that a track is lost), for N hypotheses in one launch.  For hypothesis n
+ * and crop pixel (i, j): z_r = depth_crops[n, j, i], the render's depth at the pose (fp_render_crops* with these tf_to_crops' windows;
+ * 0 where it draws nothing), and z_o = the z of the texel of frame view[n]'s xyz map that the REFINE warp reads for that pixel (the
+ * nearest texel through the inverse of tf_to_crops[n]; 0 outside the frame) -- bit for bit the z channel of fp_warp_crops* in
+ * FP_MODE_REFINE without FP_FLAG_NORMALIZE_XYZ called with the pose's translation zeroed.  counts[n] (int32 x 4), every difference in
+ * f32:  [0] model  = pixels with z_r > 0;
+ *       [1] valid  = model pixels with z_o >= 0.001 (the REFINE threshold);
+ *       [2] agree  = valid pixels with fabsf(z_o - z_r) <= tol;
+ *       [3] behind = valid pixels with z_o - z_r > tol: the sensor sees past the model's surface (free space violated).
+ * valid - agree - behind (not stored) = pixels where something lies in front of the model (an occlusion).  tol is absolute, in the
+ * depth's unit (metres).  The counts are zeroed on the stream first (no host synchronisation: graph-capturable) and summed with integer
+ * atomics: exact, the same on every replay.  xyz_map is a (V,H,W,3) stack, view a per-hypothesis index (dev N int32; NULL allowed only
+ * for V == 1); an index outside 0..V-1 reads nothing (valid = agree = behind = 0).  N == 0 does nothing.  Argument errors
+ * (FP_ERR_INVALID_ARG): NULL tensors, oh / ow / H / W / V below 1, more than 2^20 crop pixels, N outside 0..65535, view NULL with
+ * V > 1, tol negative or not finite. */
+int fp_depth_agreement(const float* depth_crops /*dev N,oh,ow*/, const float* xyz_map /*dev V,H,W,3*/, const float* tf_to_crops /*dev N,9*/,
+                       const int32_t* view /*dev N|NULL*/, int V, int H, int W, int N, int oh, int ow, float tol,
+                       int32_t* counts /*dev N,4*/, void* stream);
 /* fp_pose_update_multi with K = Ks[view[n]] (read by trans_rep deepim only; Ks is required either way) */
 int fp_pose_update_views(const float* trans /*dev N,3*/, const float* rot /*dev N,3|6*/, const float* poses_in /*dev N,16*/,
                          int rot_rep, int normalize_xyz, const float* trans_normalizer /*host 3*/, float rot_normalizer,
