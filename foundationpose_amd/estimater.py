@@ -50,6 +50,7 @@ class FoundationPose:
     # ------------------------------------------------------------------ estimater.py:44-78
     def reset_object(self, model_pts, model_normals, symmetry_tfs=None, mesh=None):
         self._tracker = None   # a captured tracking graph holds the previous object's mesh
+        self.poses = self.scores = None   # ranked hypotheses of the last registration (pose_errors reads them): none for a new object
         max_xyz = np.asarray(mesh.vertices).max(axis=0)
         min_xyz = np.asarray(mesh.vertices).min(axis=0)
         self.model_center = (min_xyz + max_xyz) / 2
@@ -182,8 +183,42 @@ class FoundationPose:
         return best_pose.data.cpu().numpy()
 
     def compute_add_err_to_gt_pose(self, poses):
-        """stub in the reference as well (estimater.py:243-247)"""
+        """stub in the reference as well (estimater.py:243-247); the errors to a known pose are pose_errors' (below)"""
         return -torch.ones(len(poses), device=self.device, dtype=torch.float)
+
+    def pose_errors(self, gt_pose, poses=None, want=("add", "adds", "sym")):
+        """ADD, ADD-S and the symmetry-aware errors (not in the reference) of `poses` against a known pose -> (N, 4) float64 device
+        table [add, adds, add_sym, mssd] in metres over the mesh's vertices (ops.pose_errors; ops.PoseErrors.rows reads it on the host).
+        gt_pose: (4,4), or (G,4,4) with G == N for pose n against ground truth n, in the frame of the mesh handed to reset_object --
+        what register / track_one return and the readers' get_gt_pose gives.  poses: (N,4,4) in the centred-mesh frame like pose_last;
+        None = self.poses, the ranked hypotheses of the last register (row 0 = the returned pose).  The ground truth and
+        self.symmetry_tfs move into the centred frame in float64 on the host."""
+        if poses is None:
+            poses = getattr(self, "poses", None)
+            if poses is None:
+                raise RuntimeError("pose_errors: no registration yet (register first, or pass poses)")
+        poses = torch.as_tensor(poses, device=self.device, dtype=torch.float).reshape(-1, 4, 4).contiguous()
+        to_c, from_c = np.eye(4), np.eye(4)               # T(-model_center), T(+model_center)
+        to_c[:3, 3] = -np.asarray(self.model_center, dtype=np.float64)
+        from_c[:3, 3] = np.asarray(self.model_center, dtype=np.float64)
+        gt = gt_pose.detach().cpu().numpy() if torch.is_tensor(gt_pose) else np.asarray(gt_pose)
+        gt_c = gt.astype(np.float64).reshape(-1, 4, 4) @ from_c
+        sym_c = to_c @ self.symmetry_tfs.detach().cpu().numpy().astype(np.float64).reshape(-1, 4, 4) @ from_c
+        return ops.pose_errors(self.pts, poses, gt_c, symmetry_tfs=sym_c, want=want)
+
+    def hypothesis_report(self, gt_pose, metric="adds"):
+        """Was a good hypothesis among the ranked ones of the last register, and where did the scorer put it?  -> dict: the error
+        (`metric`: "add", "adds", "add_sym" or "mssd", metres) and score of the returned pose (rank 0), the lowest error among the
+        hypotheses, its rank and its score, and the number of hypotheses."""
+        col = ops.PoseErrors._fields.index(metric) if metric in ops.PoseErrors._fields else None
+        if col is None:
+            raise ValueError(f"hypothesis_report: unknown metric {metric!r} (known: {ops.PoseErrors._fields})")
+        table = self.pose_errors(gt_pose, want=("sym",) if col >= 2 else (metric,))
+        err = table[:, col].cpu().numpy()
+        scores = torch.as_tensor(self.scores).detach().cpu().numpy().astype(np.float64)
+        best = int(np.argmin(err))
+        return dict(metric=metric, n=int(len(err)), top_err=float(err[0]), top_score=float(scores[0]), best_err=float(err[best]),
+                    best_rank=best, best_score=float(scores[best]))
 
     # ------------------------------------------------------------------ estimater.py:250-268
     def track_one(self, rgb, depth, K, iteration, extra={}, agreement_tol=None):

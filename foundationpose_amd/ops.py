@@ -591,6 +591,113 @@ class DepthAgreement(NamedTuple):
         return [cls(*(int(x) for x in r)) for r in np.asarray(a, dtype=np.int64).reshape(-1, 4)]
 
 
+_POSE_ERROR_FLAGS = {"add": 1, "adds": 2, "sym": 4}     # FP_ERR_ADD / FP_ERR_ADDS / FP_ERR_SYM (include/fp_amd.h)
+
+
+def _tf_table(t, name):
+    """a (n,4,4) / (4,4) table of transforms, numpy or tensor of any float type -> a (n,4,4) float tensor where it lives (shape and
+    type refused here, before any device work)"""
+    if torch.is_tensor(t):
+        a = t.detach()
+    else:
+        a = np.asarray(t)
+        if a.dtype.kind in "iub":
+            a = a.astype(np.float64)
+        if a.dtype.kind != "f":
+            raise _lib.FpAmdError(f"pose_errors: {name} must be of a float type, got {a.dtype}")
+        a = torch.from_numpy(np.ascontiguousarray(a))
+    if not a.is_floating_point():
+        raise _lib.FpAmdError(f"pose_errors: {name} must be of a float type, got {a.dtype}")
+    if a.dim() == 2:
+        a = a[None]
+    if a.dim() != 3 or tuple(a.shape[1:]) != (4, 4):
+        raise _lib.FpAmdError(f"pose_errors: {name} must be (4,4) or (n,4,4), got {tuple(a.shape)}")
+    return a
+
+
+def pose_errors_workspace(N, P, S, device):
+    """the workspace of pose_errors for N poses, P model points and S symmetries (a captured graph owns its buffers)"""
+    nbytes = int(_lib.lib().fp_pose_errors_workspace_bytes(int(N), int(P), int(S)))
+    return torch.empty(((nbytes + 7) // 8,), dtype=torch.float64, device=device)
+
+
+def pose_errors(model_pts, poses, gt, gt_index=None, symmetry_tfs=None, want=("add", "adds"), out=None, workspace=None):
+    """fp_pose_errors: how far each of the N poses (N,4,4) f32 is from its ground truth, over the model points (P,3) f32 ->
+    (N, 4) float64 device tensor [add, adds, add_sym, mssd] in metres (include/fp_amd.h has the definition; PoseErrors.rows reads it
+    on the host).  gt: (4,4) or (G,4,4), numpy or tensor; gt_index: the (N,) int32 device index of every pose's ground truth (None:
+    all against the one for G == 1, pose n against gt n for G == N).  want: names out of "add", "adds", "sym" ("sym" = add_sym and
+    mssd over symmetry_tfs (S,4,4)); the other columns are NaN.  Poses, ground truths, symmetries and points share one object frame.
+    out / workspace: caller-owned buffers ((N,4) float64; pose_errors_workspace) for a captured graph.  Wrong shapes and tables are
+    refused first, then tensors that are not on the device, of another dtype or not contiguous, then the buffers (FpAmdError)."""
+    names = (want,) if isinstance(want, str) else tuple(want)
+    flags = 0
+    for w in names:
+        if w not in _POSE_ERROR_FLAGS:
+            raise ValueError(f"pose_errors: unknown name {w!r} in want (known: {sorted(_POSE_ERROR_FLAGS)})")
+        flags |= _POSE_ERROR_FLAGS[w]
+    if not flags:
+        raise ValueError("pose_errors: want is empty")
+    # shapes first (they need no device), then device / dtype / layout, then the buffers: all before any device work
+    for name, t in (("model_pts", model_pts), ("poses", poses)):
+        if not torch.is_tensor(t):
+            raise _lib.FpAmdError(f"pose_errors: {name} must be a tensor, got {type(t).__name__}")
+    if model_pts.dim() != 2 or int(model_pts.shape[1]) != 3 or int(model_pts.shape[0]) < 1:
+        raise _lib.FpAmdError(f"pose_errors: model_pts must be (P,3) with P >= 1, got {tuple(model_pts.shape)}")
+    if poses.dim() != 3 or tuple(poses.shape[1:]) != (4, 4):
+        raise _lib.FpAmdError(f"pose_errors: poses must be (N,4,4), got {tuple(poses.shape)}")
+    N, P = int(poses.shape[0]), int(model_pts.shape[0])
+    if gt_index is not None and (not torch.is_tensor(gt_index) or int(gt_index.numel()) != N):
+        raise _lib.FpAmdError(f"pose_errors: {N} poses need a gt_index tensor of {N} entries")
+    g = _tf_table(gt, "gt")
+    G = int(g.shape[0])
+    if G < 1 or (gt_index is None and G not in (1, N)):
+        raise _lib.FpAmdError(f"pose_errors: {G} ground truths for {N} poses need a gt_index")
+    sym = None if symmetry_tfs is None else _tf_table(symmetry_tfs, "symmetry_tfs")
+    S = 0 if sym is None else int(sym.shape[0])
+    if flags & 4 and S == 0:
+        raise _lib.FpAmdError('pose_errors: want "sym" needs symmetry_tfs with at least one transform')
+    pts = _dev(model_pts, torch.float32, "model_pts")
+    ps = _dev(poses, torch.float32, "poses")
+    gi = _dev(gt_index, torch.int32, "gt_index")
+    if out is not None:
+        out = _dev(out, torch.float64, "out")
+        if tuple(out.shape) != (N, 4):
+            raise _lib.FpAmdError(f"pose_errors: out must be ({N}, 4), got {tuple(out.shape)}")
+    need = int(_lib.lib().fp_pose_errors_workspace_bytes(N, P, S))
+    if workspace is not None:
+        if not (torch.is_tensor(workspace) and workspace.is_cuda and workspace.is_contiguous()):
+            raise _lib.FpAmdError("pose_errors: workspace must be a contiguous CUDA(HIP) tensor")
+        if workspace.numel() * workspace.element_size() < need:
+            raise _lib.FpAmdError(f"pose_errors: workspace of {workspace.numel() * workspace.element_size()} bytes, {need} needed "
+                                  f"(pose_errors_workspace)")
+    g = g.to(device=ps.device, dtype=torch.float64).contiguous()          # float64 input never passes through float32
+    sym = None if sym is None else sym.to(device=ps.device, dtype=torch.float64).contiguous()
+    if out is None:
+        out = torch.empty((N, 4), dtype=torch.float64, device=ps.device)
+    if workspace is None:
+        workspace = pose_errors_workspace(N, P, S, ps.device)
+    _lib.check(_lib.lib().fp_pose_errors(_ptr(pts), P, _ptr(sym), S, _ptr(ps), _ptr(g), _ptr(gi), G, N, flags, _ptr(out),
+                                         _ptr(workspace), workspace.numel() * workspace.element_size(), _stream(ps)),
+               "fp_pose_errors")
+    return out
+
+
+class PoseErrors(NamedTuple):
+    """one row of pose_errors' table on the host, in metres: `add` the mean distance of corresponding model points, `adds` the mean
+    distance to the nearest point, `add_sym` / `mssd` the minimum over the symmetry set of the mean / the maximum corresponding
+    distance.  NaN where a column was not computed."""
+    add: float
+    adds: float
+    add_sym: float
+    mssd: float
+
+    @classmethod
+    def rows(cls, table):
+        """[PoseErrors] per row of a (N, 4) table (a device tensor: one device-to-host copy)"""
+        a = table.cpu().numpy() if torch.is_tensor(table) else np.asarray(table)
+        return [cls(*(float(x) for x in r)) for r in np.asarray(a, dtype=np.float64).reshape(-1, 4)]
+
+
 def pose_update(trans, rot, poses, rot_rep="axis_angle", normalize_xyz=True, trans_normalizer=(1.0, 1.0, 1.0),
                 rot_normalizer=1.0, mesh_diameter=1.0, out=None, trans_delta_out=None, rot_delta_out=None, trans_rep="tracknet",
                 K=None, tf_to_crops=None, input_w=0, obj=None, views=None):
@@ -1198,6 +1305,7 @@ replicate_segments = _timed("fp_replicate_segments_f16", replicate_segments,
                             lambda buf, seg, c0, c1: (2.0 * (seg.total - len(seg)) * buf.shape[1] * buf.shape[2] * (c1 - c0), 0.0))
 mask_depth_stats = _timed("fp_mask_depth_stats", mask_depth_stats)
 depth_agreement = _timed("fp_depth_agreement", depth_agreement)
+pose_errors = _timed("fp_pose_errors", pose_errors)
 layernorm_res = _timed("fp_layernorm_res_fwd", layernorm_res,
                        lambda br, *a, **k: ((2.0 + (4.0 if k.get("x32") is not None else 2.0) + (4.0 if k.get("want32", True) else 0.0)
                                              + (2.0 if k.get("want16", True) else 0.0)) * br.numel(), 0.0))

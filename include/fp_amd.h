@@ -73,8 +73,9 @@ const char* fp_last_error(void);
  *   215 -> 216: several views per call (additions only): + fp_crop_windows_views, fp_render_crops_views, fp_warp_crops_views,
  *               fp_pose_update_views, fp_depth_erode_frames, fp_depth_bilateral_frames, fp_depth_to_xyz_frames.
  *   216 -> 217: registration in several views per call (additions only): + fp_mask_depth_stats, fp_replicate_segments_f16.
- *   217 -> 218: + fp_depth_agreement (addition only): per-hypothesis depth agreement of a rendered pose with the observed frame. */
-#define FP_AMD_ABI_VERSION 218
+ *   217 -> 218: + fp_depth_agreement (addition only): per-hypothesis depth agreement of a rendered pose with the observed frame.
+ *   218 -> 219: + fp_pose_errors, fp_pose_errors_workspace_bytes (additions only): ADD, ADD-S and symmetry-aware errors of pose batches. */
+#define FP_AMD_ABI_VERSION 219
 int fp_version(void);
 
 /* Utils.py:104-130 make_mesh_tensors: records caller-owned device tensors.
@@ -172,6 +173,35 @@ int fp_warp_crops_views(const float* rgb /*dev V,H,W,3*/, const float* xyz_map /
 int fp_depth_agreement(const float* depth_crops /*dev N,oh,ow*/, const float* xyz_map /*dev V,H,W,3*/, const float* tf_to_crops /*dev N,9*/,
                        const int32_t* view /*dev N|NULL*/, int V, int H, int W, int N, int oh, int ow, float tol,
                        int32_t* counts /*dev N,4*/, void* stream);
+/* How far each of N poses is from its ground truth, in the units the field reports: out[n] = {add, adds, add_sym, mssd} (float64,
+ * metres).  flags selects the columns (a column that is not selected is NaN): */
+#define FP_ERR_ADD 1  /* add: mean distance of corresponding model points */
+#define FP_ERR_ADDS 2 /* adds: mean distance of each ground-truth point to the nearest predicted point (P x P pairs per pose) */
+#define FP_ERR_SYM 4  /* add_sym and mssd: the minimum over the symmetry set of the mean / of the maximum corresponding distance (BOP) */
+/* Definition (poses are taken as rigid).  Pose n has ground truth g = gt_index[n] (NULL: g = 0 for G == 1, g = n for G == N).
+ *  - T = inv(pose_n) * gt_g in float64, the inverse as [R^T | -R^T t], every 3-term sum as (a0*b0 + a1*b1) + a2*b2:
+ *    T.R[i][j] = (Rp[0][i]*Rg[0][j] + Rp[1][i]*Rg[1][j]) + Rp[2][i]*Rg[2][j],  T.t[i] = (Rp[0][i]*d0 + Rp[1][i]*d1) + Rp[2][i]*d2 with
+ *    d = t_g - t_p.  For symmetry s, T_s = T * S_s: T_s.R[i][j] = (T.R[i][0]*S[0][j] + T.R[i][1]*S[1][j]) + T.R[i][2]*S[2][j],
+ *    T_s.t[i] = ((T.R[i][0]*S.t[0] + T.R[i][1]*S.t[1]) + T.R[i][2]*S.t[2]) + T.t[i].  T and T_s are then rounded to float32.  (Working
+ *    in the predicted pose's object frame keeps the float32 magnitudes at the object's size instead of the camera distance.)
+ *  - Per model point p_j = (x, y, z), in float32 without contraction: q_j = ((R0*x + R1*y) + R2*z) + t per row of T;
+ *    d_j = sqrtf((dx*dx + dy*dy) + dz*dz) of q_j - p_j;  e_j = sqrtf(min_i |q_j - p_i|^2), the squared distance written as for d_j and
+ *    computed directly (not as |q|^2 + |p|^2 - 2 q.p), the minimum over every model point i.
+ *  - add = (sum_j d_j) / P, adds = (sum_j e_j) / P, add_sym = min_s (sum_j d_j(T_s)) / P, mssd = min_s max_j d_j(T_s): the sums in
+ *    float64 in an order that depends on P alone (no floating-point atomics), so row n of a batch has the bits of the call on pose n
+ *    alone and every replay the bits of the first run; the maximum in float32, exact.  With S_0 = I, d_j(T_0) = d_j bit for bit.
+ * A relative transform T that is not finite after the rounding to float32 (a NaN or an infinity in the pose or the ground truth) gives
+ * NaN in every column of that row; a T_s that is not finite gives NaN in add_sym and mssd.  Non-finite model points give unspecified
+ * values.  A gt_index outside 0..G-1 reads nothing and gives NaN in every column of that row.  N == 0 does nothing.  No allocation, no host
+ * synchronisation (graph-capturable); nothing is written outside out and workspace (fp_pose_errors_workspace_bytes(N, P, S) bytes,
+ * 8-byte aligned; 0 for N == 0; monotone in N, P and S; it depends on S and not on flags: S symmetries without FP_ERR_SYM still have
+ * their transforms formed and their room in the workspace, so pass S = 0 when the symmetric columns are not wanted).  Argument errors (FP_ERR_INVALID_ARG): NULL model_pts / poses / gt / out with
+ * N > 0, P outside 1..2^22, N outside 0..65535, G < 1, S outside 0..4096, S > 0 with NULL sym_tfs, FP_ERR_SYM with S == 0, flags 0
+ * or with an unknown bit, gt_index NULL when G is neither 1 nor N, a workspace that is too small or misaligned. */
+size_t fp_pose_errors_workspace_bytes(int N, int P, int S);
+int fp_pose_errors(const float* model_pts /*dev P,3*/, int P, const double* sym_tfs /*dev S,16|NULL*/, int S,
+                   const float* poses /*dev N,16*/, const double* gt /*dev G,16*/, const int32_t* gt_index /*dev N|NULL*/, int G, int N,
+                   int flags, double* out /*dev N,4*/, void* workspace /*dev*/, size_t workspace_bytes, void* stream);
 /* fp_pose_update_multi with K = Ks[view[n]] (read by trans_rep deepim only; Ks is required either way) */
 int fp_pose_update_views(const float* trans /*dev N,3*/, const float* rot /*dev N,3|6*/, const float* poses_in /*dev N,16*/,
                          int rot_rep, int normalize_xyz, const float* trans_normalizer /*host 3*/, float rot_normalizer,

@@ -2,7 +2,9 @@
 """Benchmark driver with the reference's call sequence (run_ycb_video.py:43-130): per object `reset_object`, per
 keyframe `register(iteration=est_refine_iter)` with the instance's visible mask, results as
 `{video_id: {frame id: {ob_id: 4x4}}}` in `<debug_dir>/ycbv_res.yml` -- plus what the reference leaves to an external
-script: ADD / ADD-S per estimate and their AUC (Utils.py:232-266).  `--synthetic N` first mints an N-frame scene in the
+script: ADD / ADD-S per estimate and their AUC (Utils.py:232-266).  `--hypothesis_errors` also evaluates every ranked hypothesis
+of each registration on the device (FoundationPose.hypothesis_report: was a better pose among them, and at which rank?) and adds
+`best_rank_hist` (plus a bucket `none` for registrations that ranked nothing), `ADDS_oracle_mean_m` and `ADDsym_AUC` to the summary.  `--synthetic N` first mints an N-frame scene in the
 BOP layout from the synthetic can (datasets and released weights are not in this container); real data:
 `--ycbv_dir <BOP ycbv root>` with `$YCB_VIDEO_DIR/models` or `--models_dir`."""
 import argparse
@@ -52,6 +54,7 @@ def main(argv=None):
     ap.add_argument("--debug_dir", type=str, default=os.path.join(ROOT, "gpurun_out", "ycbv_debug"))
     ap.add_argument("--synthetic", type=int, default=0)
     ap.add_argument("--standin_weights", action="store_true")
+    ap.add_argument("--hypothesis_errors", action="store_true", help="also report the ADD-S of every ranked hypothesis per registration")
     args = ap.parse_args(argv)
     logging.basicConfig(level=logging.INFO, format="[%(funcName)s()] %(message)s")
 
@@ -84,6 +87,7 @@ def main(argv=None):
     est = FoundationPose(model_pts=box.vertices.copy(), model_normals=box.vertex_normals.copy(), symmetry_tfs=None, mesh=box, scorer=scorer,
                          refiner=refiner, glctx=dr.RasterizeCudaContext(), debug_dir=args.debug_dir, debug=args.debug, device=dev)
     res, errs = {}, {"add": [], "adds": []}
+    reports, add_sym = [], []
     for ob_id in reader_tmp.ob_ids:
         mesh = reader_tmp.get_gt_mesh(ob_id)
         jobs = []
@@ -100,17 +104,31 @@ def main(argv=None):
             mask = reader.get_mask(i, ob_id)
             if mask is None:
                 continue
+            ranked_before = est.poses
             pose = est.register(K=reader.get_K(i), rgb=reader.get_color(i), depth=reader.get_depth(i), ob_mask=mask, ob_id=ob_id, iteration=args.est_refine_iter)
             res.setdefault(reader.get_video_id(), {}).setdefault(reader.id_strs[i], {})[int(ob_id)] = np.asarray(pose).reshape(4, 4).tolist()
             gt = reader.get_gt_pose(i, ob_id, mask=mask)
             errs["add"].append(vis.add_err(pose, gt, pts))
             errs["adds"].append(vis.adds_err(pose, gt, pts))
+            # register's fallback (too little depth under the mask) ranks nothing and leaves the last registration's hypotheses in place
+            if args.hypothesis_errors and est.poses is not None and est.poses is not ranked_before:
+                reports.append(est.hypothesis_report(gt, metric="adds"))
+                add_sym.append(float(est.pose_errors(gt, poses=est.poses[:1], want=("sym",))[0, 2]))
     with open(os.path.join(args.debug_dir, "ycbv_res.yml"), "w") as f:
         yaml.safe_dump(res, f)
     summary = {"n": len(errs["add"]), "ADD_AUC": vis.compute_auc(errs["add"]) if errs["add"] else None,
                "ADDS_AUC": vis.compute_auc(errs["adds"]) if errs["adds"] else None,
                "ADD_mean_m": float(np.mean(errs["add"])) if errs["add"] else None, "ADDS_mean_m": float(np.mean(errs["adds"])) if errs["adds"] else None}
-    logging.info(f"{summary}; poses in {args.debug_dir}/ycbv_res.yml")
+    if args.hypothesis_errors:
+        ranks = [r["best_rank"] for r in reports]
+        summary["hypothesis_reports"] = reports
+        summary["best_rank_hist"] = {"0": sum(r == 0 for r in ranks), "1-4": sum(1 <= r <= 4 for r in ranks), "5+": sum(r >= 5 for r in ranks)}
+        if len(ranks) < summary["n"]:             # registrations that ranked nothing (too little depth in the mask)
+            summary["best_rank_hist"]["none"] = summary["n"] - len(ranks)
+        summary["ADDS_oracle_mean_m"] = float(np.mean([r["best_err"] for r in reports])) if reports else None
+        summary["ADDsym_AUC"] = vis.compute_auc(add_sym) if add_sym else None
+    logged = {k: v for k, v in summary.items() if k != "hypothesis_reports"}     # the per-registration list stays out of the log line
+    logging.info(f"{logged}; poses in {args.debug_dir}/ycbv_res.yml")
     return summary
 
 
