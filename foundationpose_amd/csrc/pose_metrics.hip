@@ -16,6 +16,8 @@
 // on P alone, so row n of a batch has the bits of the call on pose n alone, and every replay has the bits of the first run.  Compiled
 // with -ffp-contract=off (SRCS_EXACT): the float32 per-point values are the ones the numpy restatement (tests/pose_errors_model.py)
 // computes, bit for bit.
+// fp_mspd (BOP's maximum symmetry-aware projection distance, in pixels) is the small sibling of the mssd column: one workgroup per pose,
+// a float32 maximum per symmetry and the minimum over them, exact in any order (k_mspd below; restated in tests/bop_errors_model.py).
 #include "fp_common.h"
 
 namespace {
@@ -233,6 +235,82 @@ __global__ __launch_bounds__(64) void k_pose_finish(const double* __restrict__ p
   }
 }
 
+// fp_mspd: one workgroup per pose.  Per symmetry s the first 12 lanes form M_s = gt_g * S_s in float64 and leave it in LDS as float32;
+// every lane then projects its points (a stride of kThreads apart) under the pose and under M_s and keeps the float32 maximum of the
+// pixel distances; the workgroup's maximum (exact in any order) goes into the minimum over s.  `bad` collects what makes the row NaN.
+struct fp_k4 { float fx, fy, cx, cy; };
+
+__device__ __forceinline__ void project(const float* T, float x, float y, float z, const fp_k4& K, float& u, float& v, bool& bad) {
+  const float X = ((T[0] * x + T[1] * y) + T[2] * z) + T[3];
+  const float Y = ((T[4] * x + T[5] * y) + T[6] * z) + T[7];
+  const float Z = ((T[8] * x + T[9] * y) + T[10] * z) + T[11];
+  bad = bad || !(Z > 0.f);
+  u = (K.fx * X) / Z + K.cx;
+  v = (K.fy * Y) / Z + K.cy;
+}
+
+__global__ __launch_bounds__(kThreads) void k_mspd(const float* __restrict__ pts, int P, const double* __restrict__ sym, int S,
+                                                   const float* __restrict__ poses, const double* __restrict__ gt,
+                                                   const int32_t* __restrict__ gt_index, int G, fp_k4 K, double* __restrict__ out) {
+  __shared__ float M[12];
+  __shared__ float red[kWaves];
+  __shared__ int red_bad[kWaves];
+  const int n = blockIdx.x, tid = threadIdx.x;
+  const int g = gt_of(gt_index, G, n);
+  if (g < 0) {                                              // uniform
+    if (tid == 0) out[n] = __builtin_nan("");
+    return;
+  }
+  float A[12];
+#pragma unroll
+  for (int i = 0; i < 12; ++i) A[i] = poses[(size_t)n * 16 + i];
+  bool bad = !tf_finite(A);
+  const double* B = gt + (size_t)g * 16;
+  float best = __builtin_inff();
+  const int Y = S > 0 ? S : 1;
+  for (int s = 0; s < Y; ++s) {
+    __syncthreads();                                        // the previous M has been read by every wave
+    if (tid < 12) {
+      const int i = tid >> 2, j = tid & 3;
+      double v = B[tid];
+      if (S > 0) {
+        const double* Sm = sym + (size_t)s * 16;
+        v = dot3(B[i * 4], Sm[j], B[i * 4 + 1], Sm[4 + j], B[i * 4 + 2], Sm[8 + j]);
+        if (j == 3) v += B[i * 4 + 3];
+      }
+      M[tid] = (float)v;
+    }
+    __syncthreads();
+    bad = bad || !tf_finite(M);
+    float m = 0.f;
+    for (int p = tid; p < P; p += kThreads) {
+      const float x = pts[(size_t)p * 3], y = pts[(size_t)p * 3 + 1], z = pts[(size_t)p * 3 + 2];
+      float ua, va, ub, vb;
+      project(A, x, y, z, K, ua, va, bad);
+      project(M, x, y, z, K, ub, vb, bad);
+      const float du = ua - ub, dv = va - vb;
+      m = fmaxf(m, sqrtf(du * du + dv * dv));               // (a NaN distance is dropped here; everything that makes one sets `bad`)
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
+    if ((tid & 63) == 0) red[tid >> 6] = m;
+    __syncthreads();
+#pragma unroll
+    for (int w = 0; w < kWaves; ++w) m = w == 0 ? red[0] : fmaxf(m, red[w]);
+    best = fminf(best, m);
+  }
+  const bool wave_bad = __ballot(bad) != 0ull;
+  __syncthreads();
+  if ((tid & 63) == 0) red_bad[tid >> 6] = wave_bad;
+  __syncthreads();
+  if (tid == 0) {
+    bool any_bad = false;
+#pragma unroll
+    for (int w = 0; w < kWaves; ++w) any_bad = any_bad || red_bad[w] != 0;
+    out[n] = any_bad ? __builtin_nan("") : (double)best;
+  }
+}
+
 }  // namespace
 
 extern "C" size_t fp_pose_errors_workspace_bytes(int N, int P, int S) {
@@ -274,5 +352,23 @@ extern "C" int fp_pose_errors(const float* model_pts, int P, const double* sym_t
   FP_CHECK_LAUNCH("fp_pose_errors (points)");
   hipLaunchKernelGGL(k_pose_finish, dim3(N), dim3(64), 0, st, partial, tf, gt_index, G, P, S, L.C, flags, out);
   FP_CHECK_LAUNCH("fp_pose_errors (finish)");
+  return FP_OK;
+}
+
+extern "C" int fp_mspd(const float* model_pts, int P, const double* sym_tfs, int S, const float* poses, const double* gt,
+                       const int32_t* gt_index, int G, int N, const float* K, double* out, void* stream) {
+  FP_REQUIRE(N >= 0 && N <= (1 << 20), "fp_mspd: N=%d outside 0..2^20", N);
+  FP_REQUIRE(P >= 1 && P <= (1 << 22), "fp_mspd: P=%d outside 1..2^22", P);
+  FP_REQUIRE(G >= 1, "fp_mspd: G=%d must be >= 1", G);
+  FP_REQUIRE(S >= 0 && S <= 4096, "fp_mspd: S=%d outside 0..4096", S);
+  FP_REQUIRE(S == 0 || sym_tfs, "fp_mspd: sym_tfs is NULL but S=%d", S);
+  FP_REQUIRE(K, "fp_mspd: NULL K");
+  FP_REQUIRE(K[1] == 0.f, "fp_mspd: K has a skew of %g; the projection is defined without one", (double)K[1]);
+  FP_REQUIRE(gt_index || G == 1 || G == N, "fp_mspd: gt_index is NULL but G=%d is neither 1 nor N=%d", G, N);
+  if (N == 0) return FP_OK;
+  FP_REQUIRE(model_pts && poses && gt && out, "fp_mspd: NULL tensor");
+  const fp_k4 k4{K[0], K[4], K[2], K[5]};
+  hipLaunchKernelGGL(k_mspd, dim3(N), dim3(kThreads), 0, (hipStream_t)stream, model_pts, P, sym_tfs, S, poses, gt, gt_index, G, k4, out);
+  FP_CHECK_LAUNCH("fp_mspd");
   return FP_OK;
 }

@@ -198,23 +198,100 @@ class FoundationPose:
             if poses is None:
                 raise RuntimeError("pose_errors: no registration yet (register first, or pass poses)")
         poses = torch.as_tensor(poses, device=self.device, dtype=torch.float).reshape(-1, 4, 4).contiguous()
+        gt_c, sym_c = self._centred_frames(gt_pose)
+        return ops.pose_errors(self.pts, poses, gt_c, symmetry_tfs=sym_c, want=want)
+
+    # the depth maps bop_errors holds at a time: 48 MiB = 40 full 480 x 640 float32 frames.  Small against the 256 MiB last-level cache,
+    # so a chunk's renders are still on the chip when the counting kernel reads them, and large enough that the raster launches of a
+    # chunk are amortised over tens of poses (all 252 at once would be 310 MB that the rasteriser writes to HBM and the counter reads back)
+    BOP_DEPTH_BUDGET = 48 << 20
+
+    def _centred_frames(self, gt_pose):
+        """ground truth(s) and self.symmetry_tfs in the centred-mesh frame, float64 on the host -> ((G,4,4), (S,4,4))"""
         to_c, from_c = np.eye(4), np.eye(4)               # T(-model_center), T(+model_center)
         to_c[:3, 3] = -np.asarray(self.model_center, dtype=np.float64)
         from_c[:3, 3] = np.asarray(self.model_center, dtype=np.float64)
         gt = gt_pose.detach().cpu().numpy() if torch.is_tensor(gt_pose) else np.asarray(gt_pose)
         gt_c = gt.astype(np.float64).reshape(-1, 4, 4) @ from_c
         sym_c = to_c @ self.symmetry_tfs.detach().cpu().numpy().astype(np.float64).reshape(-1, 4, 4) @ from_c
-        return ops.pose_errors(self.pts, poses, gt_c, symmetry_tfs=sym_c, want=want)
+        return gt_c, sym_c
 
-    def hypothesis_report(self, gt_pose, metric="adds"):
+    def bop_errors(self, gt_pose, depth, K, poses=None, taus=ops.BOP_TAUS, delta=0.015, chunk=None):
+        """The three pose errors BOP ranks by (not in the reference) of `poses` against a known pose -> dict of device tensors:
+        `vsd` (N,T) float64 (visible surface discrepancy per tolerance tau), `mssd` (N,) float64 metres, `mspd` (N,) float64 pixels and
+        `counts`, the (N, 4+T) int32 table VSD is made of (ops.vsd_counts; ops.VsdCounts.rows reads it).  gt_pose and poses as in
+        pose_errors ((4,4) or one per pose; poses None = the ranked hypotheses of the last register), moved into the centred-mesh frame
+        in float64 on the host.  depth: the RAW sensor depth (H,W) in metres, 0 = no measurement -- not the eroded / filtered map register
+        makes of it; K: the camera's intrinsics.  VSD renders the object full-frame at every pose and at the ground truth (rounded to
+        float32 once for the rasteriser; MSSD and MSPD keep the float64 one) with the estimator's own mesh, `chunk` poses at a time
+        (None: as many as BOP_DEPTH_BUDGET holds -- 48 MiB, 40 frames of 480 x 640, instead of 310 MB for 252 poses at once: a chunk's
+        maps are still in the 256 MiB last-level cache when they are counted, and on an MI355X the chunks cost 0.9 ms of raster
+        launches more than one render of all 252); the result does not depend on the chunk.  mssd and mspd run over the mesh's vertices
+        with self.symmetry_tfs.  Out of scope: several cameras (ops.Views) or objects (MeshSet) per call, rendering only a window
+        around the two projections (vsd_counts' origin is there for it), BOP's result files and its matching of estimates to ground
+        truths."""
+        from .Utils import get_mesh_handle
+        if poses is None:
+            poses = getattr(self, "poses", None)
+            if poses is None:
+                raise RuntimeError("bop_errors: no registration yet (register first, or pass poses)")
+        poses = torch.as_tensor(poses, device=self.device, dtype=torch.float).reshape(-1, 4, 4).contiguous()
+        obs = torch.as_tensor(depth, device=self.device, dtype=torch.float).contiguous()
+        if obs.dim() != 2:
+            raise ValueError(f"bop_errors: depth must be (H,W), got {tuple(obs.shape)}")
+        H, W = int(obs.shape[0]), int(obs.shape[1])
+        N = int(poses.shape[0])
+        gt_c, sym_c = self._centred_frames(gt_pose)
+        G = len(gt_c)
+        if G not in (1, N):
+            raise ValueError(f"bop_errors: {G} ground truths for {N} poses (one, or one per pose)")
+        T = int(np.asarray(taus).size)
+        if chunk is None:
+            chunk = self.BOP_DEPTH_BUDGET // (H * W * 4)
+        chunk = max(1, min(int(chunk), 65535))
+        handle = get_mesh_handle(self.mesh_tensors)
+        gt32 = torch.as_tensor(gt_c.astype(np.float32), device=self.device)
+
+        def render(p):
+            return ops.render_crops(handle, p.contiguous(), None, K, H, W, (H, W), mesh_diameter=self.diameter, normalize_xyz=False,
+                                    want=("depth",))["depth"]
+
+        counts = torch.empty((N, 4 + T), dtype=torch.int32, device=self.device)
+        gt_map = render(gt32) if G == 1 else None
+        for a in range(0, N, chunk):
+            b = min(a + chunk, N)
+            ops.vsd_counts(render(poses[a:b]), gt_map if G == 1 else render(gt32[a:b]), obs, K, self.diameter, taus=taus, delta=delta,
+                           out=counts[a:b])
+        c = counts.to(torch.float64)
+        union = c[:, 3:4]
+        vsd = torch.where(union > 0, (c[:, 4:] + union - c[:, 2:3]) / union.clamp(min=1.0), torch.ones_like(c[:, 4:]))
+        mssd = ops.pose_errors(self.pts, poses, gt_c, symmetry_tfs=sym_c, want=("sym",))[:, 3].contiguous()
+        mspd = ops.mspd(self.pts, poses, gt_c, K, symmetry_tfs=sym_c)
+        return dict(vsd=vsd, mssd=mssd, mspd=mspd, counts=counts)
+
+    def hypothesis_report(self, gt_pose, metric="adds", depth=None, K=None):
         """Was a good hypothesis among the ranked ones of the last register, and where did the scorer put it?  -> dict: the error
-        (`metric`: "add", "adds", "add_sym" or "mssd", metres) and score of the returned pose (rank 0), the lowest error among the
-        hypotheses, its rank and its score, and the number of hypotheses."""
+        (`metric`: "add", "adds", "add_sym" or "mssd", metres; with the frame's raw `depth` and `K` also "vsd", the mean over BOP's
+        taus, and "mspd", pixels -- bop_errors) and score of the returned pose (rank 0), the lowest error among the hypotheses, its
+        rank and its score, and the number of hypotheses."""
+        bop = ("vsd", "mspd")
         col = ops.PoseErrors._fields.index(metric) if metric in ops.PoseErrors._fields else None
+        if col is None and metric not in bop:
+            raise ValueError(f"hypothesis_report: unknown metric {metric!r} (known: {ops.PoseErrors._fields + bop})")
         if col is None:
-            raise ValueError(f"hypothesis_report: unknown metric {metric!r} (known: {ops.PoseErrors._fields})")
-        table = self.pose_errors(gt_pose, want=("sym",) if col >= 2 else (metric,))
-        err = table[:, col].cpu().numpy()
+            if K is None or (metric == "vsd" and depth is None):
+                raise ValueError(f"hypothesis_report: metric {metric!r} needs the frame's {'depth and ' if metric == 'vsd' else ''}K")
+            if getattr(self, "poses", None) is None:
+                raise RuntimeError("hypothesis_report: no registration yet (register first)")
+            if metric == "mspd":
+                gt_c, sym_c = self._centred_frames(gt_pose)
+                poses = torch.as_tensor(self.poses, device=self.device, dtype=torch.float).reshape(-1, 4, 4).contiguous()
+                err = ops.mspd(self.pts, poses, gt_c, K, symmetry_tfs=sym_c).cpu().numpy()
+            else:
+                err = self.bop_errors(gt_pose, depth, K)["vsd"].mean(dim=1).cpu().numpy()
+        else:
+            table = self.pose_errors(gt_pose, want=("sym",) if col >= 2 else (metric,))
+            err = table[:, col].cpu().numpy()
         scores = torch.as_tensor(self.scores).detach().cpu().numpy().astype(np.float64)
         best = int(np.argmin(err))
         return dict(metric=metric, n=int(len(err)), top_err=float(err[0]), top_score=float(scores[0]), best_err=float(err[best]),

@@ -594,7 +594,7 @@ class DepthAgreement(NamedTuple):
 _POSE_ERROR_FLAGS = {"add": 1, "adds": 2, "sym": 4}     # FP_ERR_ADD / FP_ERR_ADDS / FP_ERR_SYM (include/fp_amd.h)
 
 
-def _tf_table(t, name):
+def _tf_table(t, name, what="pose_errors"):
     """a (n,4,4) / (4,4) table of transforms, numpy or tensor of any float type -> a (n,4,4) float tensor where it lives (shape and
     type refused here, before any device work)"""
     if torch.is_tensor(t):
@@ -604,14 +604,14 @@ def _tf_table(t, name):
         if a.dtype.kind in "iub":
             a = a.astype(np.float64)
         if a.dtype.kind != "f":
-            raise _lib.FpAmdError(f"pose_errors: {name} must be of a float type, got {a.dtype}")
+            raise _lib.FpAmdError(f"{what}: {name} must be of a float type, got {a.dtype}")
         a = torch.from_numpy(np.ascontiguousarray(a))
     if not a.is_floating_point():
-        raise _lib.FpAmdError(f"pose_errors: {name} must be of a float type, got {a.dtype}")
+        raise _lib.FpAmdError(f"{what}: {name} must be of a float type, got {a.dtype}")
     if a.dim() == 2:
         a = a[None]
     if a.dim() != 3 or tuple(a.shape[1:]) != (4, 4):
-        raise _lib.FpAmdError(f"pose_errors: {name} must be (4,4) or (n,4,4), got {tuple(a.shape)}")
+        raise _lib.FpAmdError(f"{what}: {name} must be (4,4) or (n,4,4), got {tuple(a.shape)}")
     return a
 
 
@@ -696,6 +696,171 @@ class PoseErrors(NamedTuple):
         """[PoseErrors] per row of a (N, 4) table (a device tensor: one device-to-host copy)"""
         a = table.cpu().numpy() if torch.is_tensor(table) else np.asarray(table)
         return [cls(*(float(x) for x in r)) for r in np.asarray(a, dtype=np.float64).reshape(-1, 4)]
+
+
+BOP_TAUS = tuple(0.05 * k for k in range(1, 11))       # BOP's misalignment tolerances of VSD, in units of the object's diameter
+VSD_MAX_T = 16                                         # FP_VSD_MAX_T (include/fp_amd.h)
+_VSD_FAC = {}                                          # (K bytes, H, W, device) -> the depth-to-distance factor on the device
+
+
+def vsd_dist_factor(K, H, W):
+    """the (H,W) float32 depth-to-distance factor of fp_vsd_counts on the host: sqrt(1 + ((u - cx)/fx)^2 + ((v - cy)/fy)^2) in float64
+    with integer u, v (BOP's depth_im_to_dist_im_fast), rounded once"""
+    K = np.asarray(K, dtype=np.float64).reshape(3, 3)
+    a = (np.arange(W, dtype=np.float64)[None, :] - K[0, 2]) / K[0, 0]
+    b = (np.arange(H, dtype=np.float64)[:, None] - K[1, 2]) / K[1, 1]
+    return np.sqrt(1.0 + a * a + b * b).astype(np.float32)
+
+
+def _hostK33(K, what):
+    """K as a finite (3,3) float64 host matrix without skew and with positive focal lengths (ValueError otherwise)"""
+    if torch.is_tensor(K):
+        K = K.detach().cpu().numpy()
+    K = np.asarray(K, dtype=np.float64)
+    if K.size != 9:
+        raise ValueError(f"{what}: K must have 9 entries, got shape {K.shape}")
+    K = K.reshape(3, 3)
+    if not np.isfinite(K).all() or K[0, 0] <= 0 or K[1, 1] <= 0:
+        raise ValueError(f"{what}: K must be finite with positive focal lengths, got {K.tolist()}")
+    if K[0, 1] != 0:
+        raise ValueError(f"{what}: K has a skew of {K[0, 1]}; the BOP errors are defined without one")
+    return K
+
+
+def vsd_counts(est_depth, gt_depth, obs_depth, K, diameter, taus=BOP_TAUS, delta=0.015, gt_index=None, origin=(0, 0), out=None):
+    """fp_vsd_counts: the pixel counts of BOP's visible surface discrepancy of N rendered depth maps est_depth (N,h,w) f32 against the
+    renders gt_depth (G,h,w) of their ground truths and the raw sensor depth obs_depth (H,W), all in metres with 0 = nothing ->
+    (N, 4+T) int32 device table [n_gt_vis, n_est_vis, n_inter, n_union, c_0 .. c_{T-1}] (include/fp_amd.h has the definition;
+    VsdCounts.rows reads it on the host and gives the T errors).  K: the frame's intrinsics (the depth-to-distance factor is built from
+    them on the host in float64 and kept per (K, H, W, device)); diameter: the object's, metres; taus: the T <= 16 tolerances in
+    units of it (the thresholds tau * diameter are formed in float64 and rounded to float32); delta: the visibility tolerance,
+    metres.  gt_index: the (N,) int32 device index of every map's ground truth (None: all against the one for G == 1, map n against
+    gt n for G == N).  origin = (x0, y0): the frame pixel of the maps' top-left pixel, for renders of a window of the frame (the full
+    frame: (0, 0) and h x w = H x W).  out: a caller-owned (N, 4+T) int32 tensor (a captured graph owns its output; the first call for
+    a (K, H, W, device) uploads the factor, so make one call before the capture).  One camera and
+    one object per call (no ops.Views, no MeshSet).  Wrong shapes and values are refused first, then tensors that are not on the
+    device, of another dtype or not contiguous, then the buffer."""
+    what = "vsd_counts"
+    for name, t, nd in (("est_depth", est_depth, 3), ("gt_depth", gt_depth, 3), ("obs_depth", obs_depth, 2)):
+        if not torch.is_tensor(t):
+            raise _lib.FpAmdError(f"{what}: {name} must be a tensor, got {type(t).__name__}")
+        if t.dim() != nd:
+            raise _lib.FpAmdError(f"{what}: {name} must be {'(n,h,w)' if nd == 3 else '(H,W)'}, got {tuple(t.shape)}")
+    N, h, w = (int(x) for x in est_depth.shape)
+    G, H, W = int(gt_depth.shape[0]), int(obs_depth.shape[0]), int(obs_depth.shape[1])
+    if h < 1 or w < 1 or H < 1 or W < 1:
+        raise _lib.FpAmdError(f"{what}: empty images (est_depth {tuple(est_depth.shape)}, obs_depth {tuple(obs_depth.shape)})")
+    if tuple(gt_depth.shape[1:]) != (h, w):
+        raise _lib.FpAmdError(f"{what}: gt_depth must be (G,{h},{w}) like est_depth, got {tuple(gt_depth.shape)}")
+    try:
+        x0, y0 = (int(v) for v in origin)
+    except (TypeError, ValueError):
+        raise _lib.FpAmdError(f"{what}: origin must be (x0, y0), got {origin!r}") from None
+    if x0 < 0 or y0 < 0 or x0 + w > W or y0 + h > H:
+        raise _lib.FpAmdError(f"{what}: the {h} x {w} window at origin ({x0}, {y0}) is not inside the {H} x {W} frame")
+    if gt_index is not None and (not torch.is_tensor(gt_index) or int(gt_index.numel()) != N):
+        raise _lib.FpAmdError(f"{what}: {N} maps need a gt_index tensor of {N} entries")
+    if G < 1 or (gt_index is None and G not in (1, N)):
+        raise _lib.FpAmdError(f"{what}: {G} ground truths for {N} maps need a gt_index")
+    tau = np.asarray(taus, dtype=np.float64).reshape(-1)
+    T = int(tau.size)
+    if not 1 <= T <= VSD_MAX_T:
+        raise ValueError(f"{what}: {T} taus, 1..{VSD_MAX_T} are supported")
+    if not (np.isfinite(tau).all() and (tau >= 0).all()):
+        raise ValueError(f"{what}: taus must be finite and >= 0, got {tau.tolist()}")
+    d, diam = float(delta), float(diameter)
+    if not (np.isfinite(d) and d >= 0):
+        raise ValueError(f"{what}: delta must be finite and >= 0 (metres), got {delta!r}")
+    if not (np.isfinite(diam) and diam > 0):
+        raise ValueError(f"{what}: diameter must be finite and > 0 (metres), got {diameter!r}")
+    K33 = _hostK33(K, what)
+    with np.errstate(over="ignore"):
+        thr = np.ascontiguousarray((tau * diam).astype(np.float32))
+    if not np.isfinite(thr).all():
+        raise ValueError(f"{what}: tau * diameter is beyond float32")
+    est = _dev(est_depth, torch.float32, "est_depth")
+    gtd = _dev(gt_depth, torch.float32, "gt_depth")
+    obs = _dev(obs_depth, torch.float32, "obs_depth")
+    gi = _dev(gt_index, torch.int32, "gt_index")
+    if out is not None:
+        out = _dev(out, torch.int32, "out")
+        if tuple(out.shape) != (N, 4 + T):
+            raise _lib.FpAmdError(f"{what}: out must be ({N}, {4 + T}), got {tuple(out.shape)}")
+    key = (K33.tobytes(), H, W, str(est.device))
+    fac = _VSD_FAC.get(key)
+    if fac is None:
+        if len(_VSD_FAC) >= 8:               # a handful of cameras; a stream of new intrinsics does not grow it without bound
+            _VSD_FAC.clear()
+        fac = _VSD_FAC[key] = torch.from_numpy(vsd_dist_factor(K33, H, W)).to(est.device)
+    if out is None:
+        out = torch.empty((N, 4 + T), dtype=torch.int32, device=est.device)
+    _lib.check(_lib.lib().fp_vsd_counts(_ptr(est), _ptr(gtd), _ptr(gi), G, N, h, w, _ptr(obs), _ptr(fac), H, W, x0, y0, d,
+                                        thr.ctypes.data_as(C.c_void_p), T, _ptr(out), _stream(est)), "fp_vsd_counts")
+    return out
+
+
+class VsdCounts(NamedTuple):
+    """one row of vsd_counts' table on the host: pixels where the ground truth's render is visible (`n_gt_vis`), where the
+    estimate's is (`n_est_vis`), their intersection and union, and per tolerance tau_t the pixels of the intersection whose two
+    distances differ by tau_t * diameter or more (`c`, a tuple of T)."""
+    n_gt_vis: int
+    n_est_vis: int
+    n_inter: int
+    n_union: int
+    c: tuple
+
+    def errors(self):
+        """the T values of VSD, float64: (c_t + n_union - n_inter) / n_union, and 1 when nothing is visible"""
+        if self.n_union == 0:
+            return np.ones(len(self.c))
+        return (np.asarray(self.c, dtype=np.float64) + (self.n_union - self.n_inter)) / float(self.n_union)
+
+    @classmethod
+    def rows(cls, table):
+        """[VsdCounts] per row of a (N, 4+T) table (a device tensor: one device-to-host copy)"""
+        a = table.cpu().numpy() if torch.is_tensor(table) else np.asarray(table)
+        a = np.asarray(a, dtype=np.int64)
+        return [cls(int(r[0]), int(r[1]), int(r[2]), int(r[3]), tuple(int(x) for x in r[4:])) for r in a.reshape(-1, a.shape[-1])]
+
+
+def mspd(model_pts, poses, gt, K, gt_index=None, symmetry_tfs=None, out=None):
+    """fp_mspd: BOP's maximum symmetry-aware projection distance of each of the N poses (N,4,4) f32 to its ground truth, in pixels
+    of the camera K over the model points (P,3) f32 -> (N,) float64 device tensor (include/fp_amd.h has the definition): the
+    minimum over symmetry_tfs (S,4,4; None: the identity alone) of the largest distance between a point's two projections.  gt,
+    gt_index and symmetry_tfs as in pose_errors; a row is NaN for a gt_index out of range, a transform that is not finite or a
+    point at or behind the camera plane.  One camera and one object per call.  Refusals in pose_errors' order."""
+    what = "mspd"
+    for name, t in (("model_pts", model_pts), ("poses", poses)):
+        if not torch.is_tensor(t):
+            raise _lib.FpAmdError(f"{what}: {name} must be a tensor, got {type(t).__name__}")
+    if model_pts.dim() != 2 or int(model_pts.shape[1]) != 3 or int(model_pts.shape[0]) < 1:
+        raise _lib.FpAmdError(f"{what}: model_pts must be (P,3) with P >= 1, got {tuple(model_pts.shape)}")
+    if poses.dim() != 3 or tuple(poses.shape[1:]) != (4, 4):
+        raise _lib.FpAmdError(f"{what}: poses must be (N,4,4), got {tuple(poses.shape)}")
+    N, P = int(poses.shape[0]), int(model_pts.shape[0])
+    if gt_index is not None and (not torch.is_tensor(gt_index) or int(gt_index.numel()) != N):
+        raise _lib.FpAmdError(f"{what}: {N} poses need a gt_index tensor of {N} entries")
+    g = _tf_table(gt, "gt", what)
+    G = int(g.shape[0])
+    if G < 1 or (gt_index is None and G not in (1, N)):
+        raise _lib.FpAmdError(f"{what}: {G} ground truths for {N} poses need a gt_index")
+    sym = None if symmetry_tfs is None else _tf_table(symmetry_tfs, "symmetry_tfs", what)
+    S = 0 if sym is None else int(sym.shape[0])
+    K9 = np.ascontiguousarray(_hostK33(K, what).reshape(9).astype(np.float32))
+    pts = _dev(model_pts, torch.float32, "model_pts")
+    ps = _dev(poses, torch.float32, "poses")
+    gi = _dev(gt_index, torch.int32, "gt_index")
+    if out is not None:
+        out = _dev(out, torch.float64, "out")
+        if tuple(out.shape) != (N,):
+            raise _lib.FpAmdError(f"{what}: out must be ({N},), got {tuple(out.shape)}")
+    g = g.to(device=ps.device, dtype=torch.float64).contiguous()
+    sym = None if S == 0 else sym.to(device=ps.device, dtype=torch.float64).contiguous()
+    if out is None:
+        out = torch.empty((N,), dtype=torch.float64, device=ps.device)
+    _lib.check(_lib.lib().fp_mspd(_ptr(pts), P, _ptr(sym), S, _ptr(ps), _ptr(g), _ptr(gi), G, N, K9.ctypes.data_as(C.c_void_p), _ptr(out),
+                                  _stream(ps)), "fp_mspd")
+    return out
 
 
 def pose_update(trans, rot, poses, rot_rep="axis_angle", normalize_xyz=True, trans_normalizer=(1.0, 1.0, 1.0),
@@ -1306,6 +1471,8 @@ replicate_segments = _timed("fp_replicate_segments_f16", replicate_segments,
 mask_depth_stats = _timed("fp_mask_depth_stats", mask_depth_stats)
 depth_agreement = _timed("fp_depth_agreement", depth_agreement)
 pose_errors = _timed("fp_pose_errors", pose_errors)
+vsd_counts = _timed("fp_vsd_counts", vsd_counts)
+mspd = _timed("fp_mspd", mspd)
 layernorm_res = _timed("fp_layernorm_res_fwd", layernorm_res,
                        lambda br, *a, **k: ((2.0 + (4.0 if k.get("x32") is not None else 2.0) + (4.0 if k.get("want32", True) else 0.0)
                                              + (2.0 if k.get("want16", True) else 0.0)) * br.numel(), 0.0))

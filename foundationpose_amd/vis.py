@@ -33,6 +33,31 @@ def compute_auc(errs, max_val=0.1, step=0.001):
     return float(np.trapezoid(Y, X) / max_val)
 
 
+BOP_THETAS = tuple(0.05 * k for k in range(1, 11))     # BOP's correctness thresholds of VSD and (x diameter) of MSSD
+BOP_THETAS_PX = tuple(5.0 * k for k in range(1, 11))   # ... of MSPD in pixels, for a 640-pixel-wide image (scaled by W / 640)
+
+
+def bop_recall(errs, thetas):
+    """BOP's recall of a list of pose errors: the mean over the thresholds of the fraction of errors with e < theta (a NaN error is
+    an incorrect pose).  errs: any shape (VSD: one error per pose and tau, all pooled); -> float in [0, 1], NaN for no errors."""
+    e = np.asarray(errs, dtype=np.float64).reshape(-1)
+    if e.size == 0:
+        return float("nan")
+    with np.errstate(invalid="ignore"):
+        return float(np.mean([(e < float(t)).mean() for t in thetas]))
+
+
+def bop_average_recall(vsd, mssd_over_diameter, mspd, width):
+    """BOP's average recall (Challenge 2019 onward) -> dict AR_VSD, AR_MSSD, AR_MSPD and AR, their mean.  vsd: (n, T) errors per pose
+    and tau (AR_VSD is the mean over the T taus x 10 thetas 0.05 .. 0.50); mssd_over_diameter: (n,) MSSD divided by the object's
+    diameter (same thetas); mspd: (n,) pixels, thetas 5r .. 50r with r = width / 640."""
+    r = float(width) / 640.0
+    ar = {"AR_VSD": bop_recall(vsd, BOP_THETAS), "AR_MSSD": bop_recall(mssd_over_diameter, BOP_THETAS),
+          "AR_MSPD": bop_recall(mspd, [t * r for t in BOP_THETAS_PX])}
+    ar["AR"] = float(np.mean([ar["AR_VSD"], ar["AR_MSSD"], ar["AR_MSPD"]]))
+    return ar
+
+
 def _jet(v):
     """v in [0,1] -> uint8 RGB, the piecewise-linear JET map"""
     v = np.clip(v, 0, 1)

@@ -74,8 +74,10 @@ const char* fp_last_error(void);
  *               fp_pose_update_views, fp_depth_erode_frames, fp_depth_bilateral_frames, fp_depth_to_xyz_frames.
  *   216 -> 217: registration in several views per call (additions only): + fp_mask_depth_stats, fp_replicate_segments_f16.
  *   217 -> 218: + fp_depth_agreement (addition only): per-hypothesis depth agreement of a rendered pose with the observed frame.
- *   218 -> 219: + fp_pose_errors, fp_pose_errors_workspace_bytes (additions only): ADD, ADD-S and symmetry-aware errors of pose batches. */
-#define FP_AMD_ABI_VERSION 219
+ *   218 -> 219: + fp_pose_errors, fp_pose_errors_workspace_bytes (additions only): ADD, ADD-S and symmetry-aware errors of pose batches.
+ *   219 -> 220: + fp_vsd_counts, fp_mspd (additions only): the pixel counts of BOP's visible surface discrepancy and its maximum
+ *               symmetry-aware projection distance, for pose batches. */
+#define FP_AMD_ABI_VERSION 220
 int fp_version(void);
 
 /* Utils.py:104-130 make_mesh_tensors: records caller-owned device tensors.
@@ -202,6 +204,48 @@ size_t fp_pose_errors_workspace_bytes(int N, int P, int S);
 int fp_pose_errors(const float* model_pts /*dev P,3*/, int P, const double* sym_tfs /*dev S,16|NULL*/, int S,
                    const float* poses /*dev N,16*/, const double* gt /*dev G,16*/, const int32_t* gt_index /*dev N|NULL*/, int G, int N,
                    int flags, double* out /*dev N,4*/, void* workspace /*dev*/, size_t workspace_bytes, void* stream);
+/* The pixel counts of BOP's visible surface discrepancy (VSD) for N estimated poses against their ground truths, from depth renders.
+ * All images share one pixel grid of h x w pixels whose top-left pixel is frame pixel (x0, y0) (full frame: x0 = y0 = 0, h x w = H x W):
+ *   est (N,h,w), gt (G,h,w): rendered depth (camera z, metres, 0 = nothing rendered) at the estimated / the ground-truth poses; pose n
+ *     has ground truth g = gt_index[n] (NULL: g = 0 for G == 1, g = n for G == N);
+ *   obs (H,W): the raw sensor depth in metres;  fac (H,W): the depth-to-distance factor of the frame's pixels, made by the caller as
+ *     fac[v][u] = float32(sqrt(1 + ((u - cx)/fx)^2 + ((v - cy)/fy)^2)) in float64 with integer u, v (BOP's depth_im_to_dist_im_fast);
+ *   delta (BOP: 0.015 m); thr[T] (host), 1 <= T <= FP_VSD_MAX_T: thr[t] = float32(tau_t * diameter).
+ * Per pixel, float32 without contraction, one rounding per operation (obs and fac read at the pixel's frame position):
+ *   Do = obs * fac;  De = est[n] * fac;  Dg = gt[g] * fac
+ *   seen = Do > 0                                            (false for 0, negatives and NaN: no measurement)
+ *   vis(Dm) = Dm > 0 && (!seen || (Dm - Do) <= delta)
+ *   vg = vis(Dg);  ve = vis(De) || (vg && De > 0);  inter = vg && ve;  union = vg || ve;  dist = |Dg - De|
+ * counts[n] = {n_gt_vis = #vg, n_est_vis = #ve, n_inter, n_union, c_0 .. c_{T-1}} with c_t = #(inter && dist >= thr[t]), int32[4 + T].
+ * On the host vsd_t = (c_t + n_union - n_inter) / n_union, and 1 for n_union == 0.  A gt_index outside 0..G-1 reads nothing and gives
+ * a row of -1.  The counts are integers (integer atomics on rows the entry point clears itself on the stream): they do not depend on
+ * what counts held before, a row has the same values alone and in a batch, and every replay repeats them.  Rows of 16-byte-aligned
+ * groups of 4 pixels are read with 16-byte loads (w, W and x0 multiples of 4 and 16-byte-aligned pointers), anything else pixel by
+ * pixel, with the same result.  N == 0 does nothing.  No allocation, no host synchronisation (graph-capturable; thr is read during the
+ * call), nothing is written outside counts.  Argument errors (FP_ERR_INVALID_ARG): NULL est / gt / obs / fac / counts with N > 0, NULL
+ * thr, T outside 1..FP_VSD_MAX_T, N outside 0..65535, G < 1, gt_index NULL when G is neither 1 nor N, h / w / H / W below 1, more than
+ * 2^28 pixels in the window or the frame, a window that is not inside the frame, delta or a thr[t] that is negative or not finite. */
+#define FP_VSD_MAX_T 16
+int fp_vsd_counts(const float* est /*dev N,h,w*/, const float* gt /*dev G,h,w*/, const int32_t* gt_index /*dev N|NULL*/, int G, int N,
+                  int h, int w, const float* obs /*dev H,W*/, const float* fac /*dev H,W*/, int H, int W, int x0, int y0, float delta,
+                  const float* thr /*host T*/, int T, int32_t* counts /*dev N,4+T*/, void* stream);
+/* BOP's maximum symmetry-aware projection distance in pixels: out[n] = min over s of max over model points p of
+ * || proj(P_n p) - proj(M_s p) ||, M_s = gt_g * S_s (S == 0: M_0 = gt_g), g as in fp_pose_errors.
+ *  - P_n is the float32 pose as given.  M_s is formed in float64, every 3-term sum as (a0*b0 + a1*b1) + a2*b2:
+ *    M.R[i][j] = (G.R[i][0]*S.R[0][j] + G.R[i][1]*S.R[1][j]) + G.R[i][2]*S.R[2][j],
+ *    M.t[i] = ((G.R[i][0]*S.t[0] + G.R[i][1]*S.t[1]) + G.R[i][2]*S.t[2]) + G.t[i], and rounded to float32 once.
+ *  - Per model point p = (x, y, z) and transform (R, t), in float32 without contraction: X = ((R00*x + R01*y) + R02*z) + t0, Y and Z
+ *    likewise from rows 1 and 2;  u = (fx * X) / Z + cx,  v = (fy * Y) / Z + cy (K = {fx, 0, cx, 0, fy, cy, 0, 0, 1} on the host, a
+ *    non-zero skew K[1] is refused);  d = sqrtf(du*du + dv*dv) with du, dv the differences of the two projections (P_n's minus M_s's).
+ *  - The maximum and the minimum are exact in float32 whatever their order; out (float64) is the float32 value widened.
+ * A row is NaN if its gt_index is outside 0..G-1, if P_n or any M_s is not finite in float32, or if any transformed point of either
+ * side has Z <= 0 (or NaN) under any s.  One workgroup per pose; no workspace, no atomics, no allocation, no host synchronisation
+ * (graph-capturable), nothing is written outside out.  N == 0 does nothing.  Argument errors (FP_ERR_INVALID_ARG): NULL K, a non-zero
+ * skew, NULL model_pts / poses / gt / out with N > 0, P outside 1..2^22, N outside 0..2^20, G < 1, S outside 0..4096, S > 0 with NULL
+ * sym_tfs, gt_index NULL when G is neither 1 nor N. */
+int fp_mspd(const float* model_pts /*dev P,3*/, int P, const double* sym_tfs /*dev S,16|NULL*/, int S, const float* poses /*dev N,16*/,
+            const double* gt /*dev G,16*/, const int32_t* gt_index /*dev N|NULL*/, int G, int N, const float* K /*host 9*/,
+            double* out /*dev N*/, void* stream);
 /* fp_pose_update_multi with K = Ks[view[n]] (read by trans_rep deepim only; Ks is required either way) */
 int fp_pose_update_views(const float* trans /*dev N,3*/, const float* rot /*dev N,3|6*/, const float* poses_in /*dev N,16*/,
                          int rot_rep, int normalize_xyz, const float* trans_normalizer /*host 3*/, float rot_normalizer,

@@ -4,7 +4,10 @@ keyframe `register(iteration=est_refine_iter)` with the instance's visible mask,
 `{video_id: {frame id: {ob_id: 4x4}}}` in `<debug_dir>/ycbv_res.yml` -- plus what the reference leaves to an external
 script: ADD / ADD-S per estimate and their AUC (Utils.py:232-266).  `--hypothesis_errors` also evaluates every ranked hypothesis
 of each registration on the device (FoundationPose.hypothesis_report: was a better pose among them, and at which rank?) and adds
-`best_rank_hist` (plus a bucket `none` for registrations that ranked nothing), `ADDS_oracle_mean_m` and `ADDsym_AUC` to the summary.  `--synthetic N` first mints an N-frame scene in the
+`best_rank_hist` (plus a bucket `none` for registrations that ranked nothing), `ADDS_oracle_mean_m` and `ADDsym_AUC` to the summary.
+`--bop_scores` adds the three errors BOP ranks by (VSD, MSSD, MSPD: FoundationPose.bop_errors) of every returned pose and their
+average recalls `AR_VSD`, `AR_MSSD`, `AR_MSPD`, `AR` (vis.bop_average_recall; one estimate per ground-truth instance, BOP's own
+matching and result files are not reproduced).  `--synthetic N` first mints an N-frame scene in the
 BOP layout from the synthetic can (datasets and released weights are not in this container); real data:
 `--ycbv_dir <BOP ycbv root>` with `$YCB_VIDEO_DIR/models` or `--models_dir`."""
 import argparse
@@ -55,6 +58,9 @@ def main(argv=None):
     ap.add_argument("--synthetic", type=int, default=0)
     ap.add_argument("--standin_weights", action="store_true")
     ap.add_argument("--hypothesis_errors", action="store_true", help="also report the ADD-S of every ranked hypothesis per registration")
+    ap.add_argument("--bop_scores", action="store_true",
+                    help="also report BOP's VSD / MSSD / MSPD average recalls; VSD compares with the reader's depth, where pixels under "
+                         "1 mm or beyond the reader's zfar are 0 and count as 'no measurement'")
     args = ap.parse_args(argv)
     logging.basicConfig(level=logging.INFO, format="[%(funcName)s()] %(message)s")
 
@@ -88,6 +94,8 @@ def main(argv=None):
                          refiner=refiner, glctx=dr.RasterizeCudaContext(), debug_dir=args.debug_dir, debug=args.debug, device=dev)
     res, errs = {}, {"add": [], "adds": []}
     reports, add_sym = [], []
+    bop = {"vsd": [], "mssd_over_diameter": [], "mspd": [], "vsd_best_rank": []}
+    width = None
     for ob_id in reader_tmp.ob_ids:
         mesh = reader_tmp.get_gt_mesh(ob_id)
         jobs = []
@@ -114,6 +122,15 @@ def main(argv=None):
             if args.hypothesis_errors and est.poses is not None and est.poses is not ranked_before:
                 reports.append(est.hypothesis_report(gt, metric="adds"))
                 add_sym.append(float(est.pose_errors(gt, poses=est.poses[:1], want=("sym",))[0, 2]))
+            if args.bop_scores and est.poses is not None and est.poses is not ranked_before:
+                raw = reader.get_depth(i)               # the sensor's depth, not the eroded / filtered map register makes of it
+                width = int(raw.shape[1])
+                e = est.bop_errors(gt, raw, reader.get_K(i), poses=None if args.hypothesis_errors else est.poses[:1])
+                bop["vsd"].append(e["vsd"][0].cpu().numpy())
+                bop["mssd_over_diameter"].append(float(e["mssd"][0]) / est.diameter)
+                bop["mspd"].append(float(e["mspd"][0]))
+                if args.hypothesis_errors:          # the VSD-oracle rank next to the ADD-S one
+                    bop["vsd_best_rank"].append(int(np.argmin(e["vsd"].mean(dim=1).cpu().numpy())))
     with open(os.path.join(args.debug_dir, "ycbv_res.yml"), "w") as f:
         yaml.safe_dump(res, f)
     summary = {"n": len(errs["add"]), "ADD_AUC": vis.compute_auc(errs["add"]) if errs["add"] else None,
@@ -127,7 +144,15 @@ def main(argv=None):
             summary["best_rank_hist"]["none"] = summary["n"] - len(ranks)
         summary["ADDS_oracle_mean_m"] = float(np.mean([r["best_err"] for r in reports])) if reports else None
         summary["ADDsym_AUC"] = vis.compute_auc(add_sym) if add_sym else None
-    logged = {k: v for k, v in summary.items() if k != "hypothesis_reports"}     # the per-registration list stays out of the log line
+    if args.bop_scores:
+        if bop["mspd"]:
+            summary.update(vis.bop_average_recall(np.stack(bop["vsd"]), bop["mssd_over_diameter"], bop["mspd"], width))
+        else:
+            summary.update({"AR_VSD": None, "AR_MSSD": None, "AR_MSPD": None, "AR": None})
+        summary["bop_errors"] = {k: [np.asarray(v).tolist() for v in bop[k]] for k in ("vsd", "mssd_over_diameter", "mspd")}
+        if args.hypothesis_errors:
+            summary["vsd_best_rank"] = bop["vsd_best_rank"]
+    logged = {k: v for k, v in summary.items() if k not in ("hypothesis_reports", "bop_errors")}     # the per-registration list stays out of the log line
     logging.info(f"{logged}; poses in {args.debug_dir}/ycbv_res.yml")
     return summary
 
