@@ -42,7 +42,10 @@ __device__ __forceinline__ void warp_pixel(const float* __restrict__ rgb, const 
   // ---- rgb, bilinear with zero padding (tap order nw, ne, sw, se as torch grid_sample)
   {
     const float fx0 = floorf(ix), fy0 = floorf(iy);
-    const int x0 = (int)fx0, y0 = (int)fy0, x1 = x0 + 1, y1 = y0 + 1;
+    // A window with an infinite (or, beyond 2^31 px, merely huge) offset saturates the conversion at INT_MAX.  x0 + 1 in int is then
+    // signed overflow, undefined: the compiler tested x1 >= 0 as x0 > -2 and x1 < W on the wrapped sum, found the tap inside the frame
+    // and loaded from 2^31 texels past it (an illegal address).  The unsigned sum wraps by definition, so x1 = INT_MIN fails x1 >= 0.
+    const int x0 = (int)fx0, y0 = (int)fy0, x1 = (int)((unsigned)x0 + 1u), y1 = (int)((unsigned)y0 + 1u);
     const float wnw = ((float)x1 - ix) * ((float)y1 - iy);
     const float wne = (ix - (float)x0) * ((float)y1 - iy);
     const float wsw = ((float)x1 - ix) * (iy - (float)y0);
