@@ -18,7 +18,7 @@ import torch.nn.functional as F
 
 from . import dr, ops
 from .Utils import (bilateral_filter_depth, cluster_poses, compute_mesh_diameter, erode_depth, euler_matrix,
-                    make_mesh_tensors, sample_views_icosphere, set_seed)
+                    make_mesh_tensors, mesh_handle_from_tensors, sample_views_icosphere, set_seed)
 from .predict_pose_refine import PoseRefinePredictor
 from .predict_score import ScorePredictor
 
@@ -26,9 +26,9 @@ from .predict_score import ScorePredictor
 class FoundationPose:
     def __init__(self, model_pts, model_normals, symmetry_tfs=None, mesh=None, scorer: ScorePredictor = None,
                  refiner: PoseRefinePredictor = None, glctx=None, debug=0, debug_dir="/tmp/foundationpose_amd_debug",
-                 device="cuda", track_graph=False):
+                 device="cuda", track_graph=False, mesh_tensors=None):
         """track_graph=True replays track_one as one captured hipGraph per frame (same arithmetic; off by default so
-        that the call sequence of the reference is followed literally)"""
+        that the call sequence of the reference is followed literally); mesh_tensors: as in reset_object"""
         self.gt_pose = None
         self.track_graph = bool(track_graph)
         self._tracker = None
@@ -39,7 +39,7 @@ class FoundationPose:
         if debug >= 1:
             os.makedirs(debug_dir, exist_ok=True)
         self.device = torch.device(device)
-        self.reset_object(model_pts, model_normals, symmetry_tfs=symmetry_tfs, mesh=mesh)
+        self.reset_object(model_pts, model_normals, symmetry_tfs=symmetry_tfs, mesh=mesh, mesh_tensors=mesh_tensors)
         self.make_rotation_grid(min_n_views=40, inplane_step=60)
         self.glctx = glctx
         self.scorer = scorer if scorer is not None else ScorePredictor(device=device)
@@ -47,8 +47,23 @@ class FoundationPose:
         self.pose_last = None  # used for tracking; w.r.t. the centred mesh
         self.depth_agreement = None   # ops.DepthAgreement of the last tracking call made with an agreement_tol (None without)
 
+    @classmethod
+    def from_reference_views(cls, rgbs, depths, masks, ob_in_cams, Ks, voxel=None, reconstruct_args=None, **kwargs):
+        """An estimator for an object without a CAD model: its mesh is fused from V posed RGB-D reference views with masks
+        (reconstruct.reconstruct_object: rgbs (V,H,W,3), depths (V,H,W) metres, masks (V,H,W), ob_in_cams (V,4,4), Ks (V,3,3) or one
+        (3,3); voxel=None: the longest side gets 128 voxels; reconstruct_args: its further keywords), then the constructor as for any
+        other mesh (kwargs: scorer, refiner, symmetry_tfs, device, ...).  Poses come out in the frame of ob_in_cams; reset_object
+        centres the mesh as usual (model_center)."""
+        from .reconstruct import reconstruct_object
+        args = dict(reconstruct_args or {})
+        args.setdefault("device", kwargs.get("device", "cuda"))
+        mesh, tensors = reconstruct_object(rgbs, depths, masks, ob_in_cams, Ks, voxel=voxel, **args)
+        return cls(model_pts=mesh.vertices, model_normals=mesh.vertex_normals, mesh=mesh, mesh_tensors=tensors, **kwargs)
+
     # ------------------------------------------------------------------ estimater.py:44-78
-    def reset_object(self, model_pts, model_normals, symmetry_tfs=None, mesh=None):
+    def reset_object(self, model_pts, model_normals, symmetry_tfs=None, mesh=None, mesh_tensors=None):
+        """mesh_tensors: the device tensors of `mesh` as given (not centred), where the caller has them already (a reconstruction's):
+        they are centred on the device in place of a second upload of the mesh, to the bits make_mesh_tensors gives"""
         self._tracker = None   # a captured tracking graph holds the previous object's mesh
         self.poses = self.scores = None   # ranked hypotheses of the last registration (pose_errors reads them): none for a new object
         max_xyz = np.asarray(mesh.vertices).max(axis=0)
@@ -70,7 +85,14 @@ class FoundationPose:
         self.normals = F.normalize(torch.tensor(nrm, dtype=torch.float32, device=self.device), dim=-1)
         self.mesh_path = None
         self.mesh = mesh
-        self.mesh_tensors = make_mesh_tensors(self.mesh, device=self.device)
+        if mesh_tensors is None:
+            self.mesh_tensors = make_mesh_tensors(self.mesh, device=self.device)
+        else:
+            t = {k: v.to(self.device) for k, v in mesh_tensors.items() if k != "_handle"}
+            center = torch.as_tensor(self.model_center, dtype=torch.float64, device=self.device)
+            t["pos"] = (t["pos"].double() - center).float()        # the host's float64 subtraction, rounded once
+            t["_handle"] = mesh_handle_from_tensors(t)
+            self.mesh_tensors = t
         if symmetry_tfs is None:
             self.symmetry_tfs = torch.eye(4, device=self.device).float()[None]
         else:

@@ -712,7 +712,7 @@ def vsd_dist_factor(K, H, W):
     return np.sqrt(1.0 + a * a + b * b).astype(np.float32)
 
 
-def _hostK33(K, what):
+def _hostK33(K, what, no_skew="the BOP errors are defined without one"):
     """K as a finite (3,3) float64 host matrix without skew and with positive focal lengths (ValueError otherwise)"""
     if torch.is_tensor(K):
         K = K.detach().cpu().numpy()
@@ -723,7 +723,7 @@ def _hostK33(K, what):
     if not np.isfinite(K).all() or K[0, 0] <= 0 or K[1, 1] <= 0:
         raise ValueError(f"{what}: K must be finite with positive focal lengths, got {K.tolist()}")
     if K[0, 1] != 0:
-        raise ValueError(f"{what}: K has a skew of {K[0, 1]}; the BOP errors are defined without one")
+        raise ValueError(f"{what}: K has a skew of {K[0, 1]}; {no_skew}")
     return K
 
 
@@ -861,6 +861,132 @@ def mspd(model_pts, poses, gt, K, gt_index=None, symmetry_tfs=None, out=None):
     _lib.check(_lib.lib().fp_mspd(_ptr(pts), P, _ptr(sym), S, _ptr(ps), _ptr(g), _ptr(gi), G, N, K9.ctypes.data_as(C.c_void_p), _ptr(out),
                                   _stream(ps)), "fp_mspd")
     return out
+
+
+TSDF_MAX_DIM = 4096                                    # FP_TSDF_MAX_DIM (include/fp_amd.h)
+
+
+def _tsdf_grid(what, tsdf, weight, color, color_weight, origin, voxel):
+    """shapes and values of a TSDF volume's arrays -> ((nz, ny, nx), origin as 3 float32 on the host, voxel); nothing about devices"""
+    for name, t in (("tsdf", tsdf), ("weight", weight), ("color", color), ("color_weight", color_weight)):
+        if not torch.is_tensor(t):
+            raise _lib.FpAmdError(f"{what}: {name} must be a tensor, got {type(t).__name__}")
+    if tsdf.dim() != 3:
+        raise _lib.FpAmdError(f"{what}: tsdf must be (nz,ny,nx), got {tuple(tsdf.shape)}")
+    dims = tuple(int(x) for x in tsdf.shape)
+    if min(dims) < 1 or max(dims) > TSDF_MAX_DIM or dims[0] * dims[1] * dims[2] > 1 << 30:
+        raise _lib.FpAmdError(f"{what}: a volume of {dims} voxels; every dimension must be 1..{TSDF_MAX_DIM} and their product <= 2^30")
+    for name, t, shape in (("weight", weight, dims), ("color", color, dims + (3,)), ("color_weight", color_weight, dims)):
+        if tuple(t.shape) != shape:
+            raise _lib.FpAmdError(f"{what}: {name} must be {shape} like tsdf, got {tuple(t.shape)}")
+    try:
+        o = np.asarray(origin, dtype=np.float64).reshape(-1)
+    except (TypeError, ValueError):
+        raise ValueError(f"{what}: origin must be 3 numbers, got {origin!r}") from None
+    if o.size != 3 or not np.isfinite(o).all() or not np.isfinite(o.astype(np.float32)).all():
+        raise ValueError(f"{what}: origin must be 3 finite numbers (metres), got {origin!r}")
+    s = float(voxel)
+    if not (np.isfinite(s) and s > 0 and np.isfinite(np.float32(s)) and np.float32(s) > 0):
+        raise ValueError(f"{what}: voxel must be finite and > 0 (metres), got {voxel!r}")
+    return dims, np.ascontiguousarray(o.astype(np.float32)), s
+
+
+def tsdf_integrate(tsdf, weight, color, color_weight, depth, rgb, masks, ob_in_cams, Ks, origin, voxel, trunc, min_depth=0.001):
+    """fp_tsdf_integrate: fuses V posed RGB-D views into a truncated-signed-distance volume, in place (include/fp_amd.h has the
+    definition).  The volume: tsdf, weight, color_weight (nz,ny,nx) and color (nz,ny,nx,3), float32 on the device, a fresh one being
+    tsdf = 1 and zeros; voxel (ix, iy, iz) is at origin + (ix, iy, iz) * voxel in the object frame (metres); trunc: the truncation
+    distance, metres.  The views: depth (V,H,W) f32 metres, rgb (V,H,W,3) f32, masks (V,H,W) uint8 or None (pixels with mask 0 saw
+    past the object and carve the volume empty: the views are assumed to show the object unoccluded), ob_in_cams (V,4,4) f32
+    object-to-camera, Ks: V intrinsic matrices on the host (a skew is refused; uploaded as float64) or a (V,3,3) float64 device tensor
+    (taken as is: a view whose K has a skew or is not finite is skipped, like one whose pose is not finite).  Depths below min_depth
+    are holes.  One launch, no allocation with device Ks, no synchronisation: capturable in a graph; views can be streamed in over
+    several calls, with the bits of one call.  Wrong shapes and values are refused first, then tensors that are not on the device, of
+    another dtype or not contiguous, then the volume's arrays."""
+    what = "tsdf_integrate"
+    for name, t, nd in (("depth", depth, 3), ("rgb", rgb, 4), ("ob_in_cams", ob_in_cams, 3)):
+        if not torch.is_tensor(t):
+            raise _lib.FpAmdError(f"{what}: {name} must be a tensor, got {type(t).__name__}")
+        if t.dim() != nd:
+            raise _lib.FpAmdError(f"{what}: {name} must have {nd} dimensions, got {tuple(t.shape)}")
+    V, H, W = (int(x) for x in depth.shape)
+    if V > 4096:
+        raise _lib.FpAmdError(f"{what}: {V} views in one call, at most 4096 (fuse them in several calls)")
+    if H < 1 or W < 1 or H * W > 1 << 28:
+        raise _lib.FpAmdError(f"{what}: frames of {H} x {W} pixels (1 .. 2^28 pixels are supported)")
+    if tuple(rgb.shape) != (V, H, W, 3):
+        raise _lib.FpAmdError(f"{what}: rgb must be ({V},{H},{W},3) like depth, got {tuple(rgb.shape)}")
+    if masks is not None and (not torch.is_tensor(masks) or tuple(masks.shape) != (V, H, W)):
+        raise _lib.FpAmdError(f"{what}: masks must be a ({V},{H},{W}) tensor like depth or None")
+    if tuple(ob_in_cams.shape) != (V, 4, 4):
+        raise _lib.FpAmdError(f"{what}: ob_in_cams must be ({V},4,4), got {tuple(ob_in_cams.shape)}")
+    dims, o, s = _tsdf_grid(what, tsdf, weight, color, color_weight, origin, voxel)
+    tr, md = float(trunc), float(min_depth)
+    if not (np.isfinite(tr) and tr > 0 and np.isfinite(np.float32(tr)) and np.float32(tr) > 0):
+        raise ValueError(f"{what}: trunc must be finite and > 0 (metres), got {trunc!r}")
+    if not (np.isfinite(md) and md >= 0):
+        raise ValueError(f"{what}: min_depth must be finite and >= 0 (metres), got {min_depth!r}")
+    K_dev = None
+    if torch.is_tensor(Ks) and Ks.is_cuda:
+        if tuple(Ks.shape) != (V, 3, 3):
+            raise _lib.FpAmdError(f"{what}: device Ks must be ({V},3,3), got {tuple(Ks.shape)}")
+        K_dev = Ks
+    else:
+        Kh = [_hostK33(K, what, "the projection of a voxel is defined without one") for K in Ks]
+        if len(Kh) != V:
+            raise _lib.FpAmdError(f"{what}: {len(Kh)} intrinsic matrices for {V} views")
+    d = _dev(depth, torch.float32, "depth")
+    c = _dev(rgb, torch.float32, "rgb")
+    m = _dev(masks, torch.uint8, "masks")
+    P = _dev(ob_in_cams, torch.float32, "ob_in_cams")
+    K_dev = _dev(K_dev, torch.float64, "Ks")
+    vol = [_dev(t, torch.float32, name) for name, t in (("tsdf", tsdf), ("weight", weight), ("color", color), ("color_weight", color_weight))]
+    if V == 0:
+        return
+    if K_dev is None:
+        K_dev = torch.as_tensor(np.stack(Kh), device=d.device)
+    _lib.check(_lib.lib().fp_tsdf_integrate(_ptr(d), _ptr(c), _ptr(m), _ptr(P), _ptr(K_dev), V, H, W, dims[0], dims[1], dims[2],
+                                            o.ctypes.data_as(C.c_void_p), s, tr, md, _ptr(vol[0]), _ptr(vol[1]), _ptr(vol[2]), _ptr(vol[3]),
+                                            _stream(d)), "fp_tsdf_integrate")
+
+
+def tsdf_extract(tsdf, weight, color, color_weight, origin, voxel, min_weight=1.0):
+    """The surface of a TSDF volume (arrays, origin and voxel as in tsdf_integrate) as a welded triangle mesh on the device, by
+    marching tetrahedra over the cubes whose corners all have weight >= min_weight (fp_tsdf_count_triangles -> torch.cumsum -> one
+    host read of the total -> fp_tsdf_emit_triangles -> torch.unique over the corners' grid-edge keys; include/fp_amd.h has the
+    definition) -> dict(pos (U,3) f32, vnormals (U,3) f32, vertex_color (U,3) f32 in the units of color, faces (T,3) int32), the
+    vertices in the order of their sorted keys and the faces in the order cube, tetrahedron, table: the same bits every time.  No surface
+    gives U = T = 0.  The host read of the total makes this a setup call: it synchronises and cannot be captured in a graph.
+    Refusals in tsdf_integrate's order."""
+    what = "tsdf_extract"
+    dims, o, s = _tsdf_grid(what, tsdf, weight, color, color_weight, origin, voxel)
+    mw = float(min_weight)
+    if not np.isfinite(mw):
+        raise ValueError(f"{what}: min_weight must be finite, got {min_weight!r}")
+    f, w, c, cw = [_dev(t, torch.float32, name) for name, t in (("tsdf", tsdf), ("weight", weight), ("color", color), ("color_weight", color_weight))]
+    dev, L, st = f.device, _lib.lib(), _stream(f)
+    nz, ny, nx = dims
+    ncubes = (nz - 1) * (ny - 1) * (nx - 1)
+    total = 0
+    if ncubes > 0:
+        counts = torch.empty((ncubes,), dtype=torch.int32, device=dev)
+        _lib.check(L.fp_tsdf_count_triangles(_ptr(f), _ptr(w), nz, ny, nx, mw, _ptr(counts), st), "fp_tsdf_count_triangles")
+        ends = torch.cumsum(counts, 0, dtype=torch.int64)
+        total = int(ends[-1].item())
+    if total == 0:
+        e = torch.empty((0, 3), dtype=torch.float32, device=dev)
+        return dict(pos=e, vnormals=e.clone(), vertex_color=e.clone(), faces=torch.empty((0, 3), dtype=torch.int32, device=dev))
+    if total > 1 << 29:
+        raise _lib.FpAmdError(f"{what}: {total} triangles, more than 2^29: use a coarser volume")
+    offsets = (ends - counts).contiguous()
+    keys = torch.empty((3 * total,), dtype=torch.int64, device=dev)
+    pos, col, nrm = (torch.empty((3 * total, 3), dtype=torch.float32, device=dev) for _ in range(3))
+    _lib.check(L.fp_tsdf_emit_triangles(_ptr(f), _ptr(w), _ptr(c), _ptr(cw), nz, ny, nx, o.ctypes.data_as(C.c_void_p), s, mw, _ptr(offsets),
+                                        total, _ptr(keys), _ptr(pos), _ptr(col), _ptr(nrm), st), "fp_tsdf_emit_triangles")
+    uk, inv = torch.unique(keys, return_inverse=True)
+    # every corner on one grid edge carries the same bits; the first of them stands for the vertex
+    first = torch.full((int(uk.numel()),), 3 * total, dtype=torch.int64, device=dev)
+    first.scatter_reduce_(0, inv, torch.arange(3 * total, dtype=torch.int64, device=dev), "amin")
+    return dict(pos=pos[first], vnormals=nrm[first], vertex_color=col[first], faces=inv.reshape(total, 3).to(torch.int32))
 
 
 def pose_update(trans, rot, poses, rot_rep="axis_angle", normalize_xyz=True, trans_normalizer=(1.0, 1.0, 1.0),

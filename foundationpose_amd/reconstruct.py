@@ -1,0 +1,169 @@
+"""Model-free object setup: an object's mesh from a few posed RGB-D reference views with masks, by truncated-signed-distance (TSDF)
+fusion and marching tetrahedra on the device (ops.tsdf_integrate / ops.tsdf_extract; include/fp_amd.h has the definition).  It stands
+where the reference trains a neural object field (bundlesdf/, not built: DESIGN.md section 7): what setup hands to FoundationPose is a
+mesh in the object frame either way.  Colours are per vertex; there is no texture atlas, no simplification and no removal of small
+components: the masks do the carving, and the views are assumed to show the object unoccluded."""
+import numpy as np
+import torch
+
+from . import ops
+from .mesh import SimpleMesh
+
+PAD_VOXELS = 3          # voxels kept free around the observed points, so that the surface closes inside the volume
+
+
+def _host(x):
+    """a list of arrays / an array / a tensor -> an array or a tensor, where it is: shapes are checked before anything is uploaded"""
+    if x is None or torch.is_tensor(x):
+        return x
+    return np.ascontiguousarray(np.asarray(x))
+
+
+def _upload(x, dtype, device):
+    if x is None:
+        return None
+    if not torch.is_tensor(x):
+        x = torch.as_tensor(x)
+    return x.to(device=device, dtype=dtype).contiguous()
+
+
+def _views_in(rgbs, depths, masks, ob_in_cams, Ks, device, what):
+    """the arguments every entry point here takes, their shapes checked where they are and then uploaded once -> device tensors (depth
+    (V,H,W) f32, rgb (V,H,W,3) f32 in 0..255 | None, masks (V,H,W) uint8 | None, poses (V,4,4) f32) and the host Ks (V,3,3) float64"""
+    d, c, m, P = _host(depths), _host(rgbs), _host(masks), _host(ob_in_cams)
+    if d.ndim != 3:
+        raise ValueError(f"{what}: depths must be (V,H,W), got {tuple(d.shape)}")
+    V = int(d.shape[0])
+    if V == 0:
+        raise ValueError(f"{what}: no views")
+    if c is not None and tuple(c.shape) != tuple(d.shape) + (3,):
+        raise ValueError(f"{what}: rgbs must be {tuple(d.shape) + (3,)} like depths, got {tuple(c.shape)}")
+    if m is not None and tuple(m.shape) != tuple(d.shape):
+        raise ValueError(f"{what}: masks must be {tuple(d.shape)} like depths, got {tuple(m.shape)}")
+    if tuple(P.shape) != (V, 4, 4):
+        raise ValueError(f"{what}: ob_in_cams must be ({V},4,4), got {tuple(P.shape)}")
+    K = np.asarray(Ks.detach().cpu().numpy() if torch.is_tensor(Ks) else Ks, dtype=np.float64)
+    if K.shape == (3, 3):
+        K = np.tile(K[None], (V, 1, 1))
+    if K.shape != (V, 3, 3):
+        raise ValueError(f"{what}: Ks must be ({V},3,3) or one (3,3) matrix, got {K.shape}")
+    return (_upload(d, torch.float32, device), _upload(c, torch.float32, device), _upload(m, torch.uint8, device),
+            _upload(P, torch.float32, device), K)
+
+
+class TsdfVolume:
+    """A TSDF volume on the device: dims = (nz, ny, nx) voxels of pitch `voxel` (metres), voxel (ix, iy, iz) at origin + (ix, iy, iz) *
+    voxel in the object frame, truncation `trunc` (default 4 voxels)."""
+
+    def __init__(self, origin, dims, voxel, trunc=None, device="cuda", min_depth=0.001):
+        self.origin = np.asarray(origin, dtype=np.float64).reshape(3)
+        self.dims = tuple(int(n) for n in dims)
+        if len(self.dims) != 3:
+            raise ValueError(f"TsdfVolume: dims must be (nz, ny, nx), got {dims!r}")
+        self.voxel = float(voxel)
+        self.trunc = 4.0 * self.voxel if trunc is None else float(trunc)
+        self.min_depth = float(min_depth)
+        self.device = torch.device(device)
+        self.tsdf = torch.empty(self.dims, dtype=torch.float32, device=self.device)
+        self.weight = torch.empty(self.dims, dtype=torch.float32, device=self.device)
+        self.color = torch.empty(self.dims + (3,), dtype=torch.float32, device=self.device)
+        self.color_weight = torch.empty(self.dims, dtype=torch.float32, device=self.device)
+        self.reset()
+
+    def arrays(self):
+        return self.tsdf, self.weight, self.color, self.color_weight
+
+    def reset(self):
+        """nothing observed: tsdf = 1, everything else 0 (fills on the stream: capturable)"""
+        self.tsdf.fill_(1.0)
+        self.weight.zero_()
+        self.color.zero_()
+        self.color_weight.zero_()
+
+    def integrate(self, rgbs, depths, masks, ob_in_cams, Ks):
+        """fuses V views: rgbs (V,H,W,3) uint8 or float in 0..255, depths (V,H,W) metres, masks (V,H,W) bool / uint8 or None,
+        ob_in_cams (V,4,4), Ks (V,3,3) or one (3,3).  Views can be streamed in over several calls; the volume then holds the bits of
+        one call over all of them."""
+        if rgbs is None:
+            raise ValueError("TsdfVolume.integrate: rgbs are required")
+        self._integrate(*_views_in(rgbs, depths, masks, ob_in_cams, Ks, self.device, "TsdfVolume.integrate"))
+
+    def _integrate(self, d, c, m, P, K):
+        ops.tsdf_integrate(*self.arrays(), d, c, m, P, K, self.origin, self.voxel, self.trunc, self.min_depth)
+
+    def extract(self, min_weight=1):
+        """the surface over the voxels observed at least min_weight times -> (SimpleMesh with uint8 vertex colours, mesh_tensors):
+        the second is the device dict FoundationPose and the rasteriser take (pos, vnormals, faces, vertex_color in [0,1], _handle),
+        made from the extraction's device tensors without a host round trip, with the colours rounded to the mesh's uint8 ones: the
+        bits make_mesh_tensors(mesh) would give.  A setup call (it synchronises).  ValueError when the
+        volume holds no surface."""
+        from .Utils import mesh_handle_from_tensors
+        out = ops.tsdf_extract(*self.arrays(), self.origin, self.voxel, min_weight)
+        if int(out["faces"].shape[0]) == 0:
+            raise ValueError("TsdfVolume.extract: no surface in the volume (no voxel pair on both sides of a surface was observed "
+                             f"{min_weight} times: check the poses, the masks and the volume's bounds)")
+        cols = out["vertex_color"].add(0.5).floor_().clamp_(0, 255)
+        t = dict(pos=out["pos"], vnormals=out["vnormals"], faces=out["faces"], vertex_color=cols / 255.0)
+        t["_handle"] = mesh_handle_from_tensors(t)
+        cols = cols.to(torch.uint8).cpu().numpy()
+        mesh = SimpleMesh(out["pos"].cpu().numpy(), out["faces"].cpu().numpy(), vertex_normals=out["vnormals"].cpu().numpy(),
+                          vertex_colors=cols)
+        return mesh, t
+
+
+def bounds_from_views(depths, masks, ob_in_cams, Ks, margin=0.0, min_depth=0.001, device="cuda"):
+    """the box (lo, hi: float64 (3,), object frame, metres) of the masked depth pixels of all views, grown by margin: the pixels are
+    back-projected on the device (fp_depth_to_xyz_frames) and mapped to the object frame.  Every masked pixel counts, so a mask that
+    covers background stretches the box.  ValueError when no masked pixel has a depth."""
+    what = "bounds_from_views"
+    if masks is None:
+        raise ValueError(f"{what}: masks are required (without them the box is the whole scene's)")
+    d, _, m, P, K = _views_in(None, depths, masks, ob_in_cams, Ks, device, what)
+    return _bounds(d, m, P, K, margin, min_depth, what)
+
+
+def _bounds(d, m, P, K, margin, min_depth, what):
+    """bounds_from_views of views that are on the device already"""
+    V = int(d.shape[0])
+    xyz = ops.depth_to_xyz_frames(d, ops.Views(list(K), np.arange(V), d.device))          # (V,H,W,3), camera frame
+    valid = (m != 0) & (d >= min_depth)
+    cam_in_ob = torch.as_tensor(np.linalg.inv(P.double().cpu().numpy()), device=d.device, dtype=torch.float32)     # (V,4,4)
+    R, t = cam_in_ob[:, :3, :3], cam_in_ob[:, :3, 3]
+    lo, hi = [], []
+    for k in range(3):
+        q = (xyz[..., 0] * R[:, k, 0, None, None] + xyz[..., 1] * R[:, k, 1, None, None]) + xyz[..., 2] * R[:, k, 2, None, None] + t[:, k, None, None]
+        lo.append(torch.where(valid, q, torch.full_like(q, float("inf"))).amin())
+        hi.append(torch.where(valid, q, torch.full_like(q, float("-inf"))).amax())
+    box = torch.stack(lo + hi).double().cpu().numpy()
+    if not np.isfinite(box).all():
+        raise ValueError(f"{what}: the masks are empty (no masked pixel of the {V} views has a depth of at least {min_depth} m)")
+    return box[:3] - margin, box[3:] + margin
+
+
+def reconstruct_object(rgbs, depths, masks, ob_in_cams, Ks, voxel=None, trunc=None, margin=None, min_weight=1, min_depth=0.001,
+                       longest=128, device="cuda"):
+    """V posed RGB-D reference views with masks -> (SimpleMesh, mesh_tensors) of the object, in the frame of the poses: the box of the
+    masked depths (bounds_from_views) -> a TsdfVolume over it -> fuse -> extract.  voxel=None picks the pitch that gives the longest
+    side `longest` voxels; margin defaults to three voxels around the observed points; trunc to four voxels.  ValueError, naming the
+    cause, when there are no views, the masks are empty or no surface was found."""
+    what = "reconstruct_object"
+    n = len(depths) if depths is not None else 0
+    if n == 0:
+        raise ValueError(f"{what}: no views")
+    if rgbs is None or masks is None:
+        raise ValueError(f"{what}: rgbs and masks are required")
+    d, c, m, P, K = _views_in(rgbs, depths, masks, ob_in_cams, Ks, device, what)
+    lo, hi = _bounds(d, m, P, K, 0.0, min_depth, what)
+    side = float((hi - lo).max())
+    if voxel is None:
+        voxel = max(side, 1e-6) / (int(longest) - 1 - 2 * PAD_VOXELS)
+    voxel = float(voxel)
+    margin = PAD_VOXELS * voxel if margin is None else float(margin)
+    lo, hi = lo - margin, hi + margin
+    nx, ny, nz = (int(np.ceil(e / voxel - 1e-9)) + 1 for e in (hi - lo))
+    vol = TsdfVolume(lo, (nz, ny, nx), voxel, trunc, device, min_depth)
+    vol._integrate(d, c, m, P, K)
+    try:
+        return vol.extract(min_weight)
+    except ValueError as e:
+        raise ValueError(f"{what}: no surface found in the {n} views ({e})") from None

@@ -51,3 +51,19 @@ def perturbed_poses(pose, n, seed=0, max_trans=0.02, max_rot_deg=10.0):
         out[i, :3, :3] = dR @ out[i, :3, :3]
         out[i, :3, 3] += rng.uniform(-1, 1, size=3) * max_trans / np.sqrt(3)
     return out
+
+
+def reference_view_poses(n=16, distance=0.5):
+    """n object-in-camera poses (n,4,4) float64 looking at the origin from all around at `distance`: views spread evenly over the
+    42-view icosphere of the estimator's rotation grid (view 0, then each time the view farthest from those taken)"""
+    from .Utils import sample_views_icosphere
+    cams = sample_views_icosphere(42, radius=distance)
+    if not 1 <= n <= len(cams):
+        raise ValueError(f"reference_view_poses: 1..{len(cams)} views, got {n}")
+    eye = cams[:, :3, 3]
+    sel, d = [0], np.linalg.norm(eye - eye[0], axis=1)
+    while len(sel) < n:
+        k = int(np.argmax(d))
+        sel.append(k)
+        d = np.minimum(d, np.linalg.norm(eye - eye[k], axis=1))
+    return np.stack([np.linalg.inv(cams[k]) for k in sel])

@@ -76,8 +76,10 @@ const char* fp_last_error(void);
  *   217 -> 218: + fp_depth_agreement (addition only): per-hypothesis depth agreement of a rendered pose with the observed frame.
  *   218 -> 219: + fp_pose_errors, fp_pose_errors_workspace_bytes (additions only): ADD, ADD-S and symmetry-aware errors of pose batches.
  *   219 -> 220: + fp_vsd_counts, fp_mspd (additions only): the pixel counts of BOP's visible surface discrepancy and its maximum
- *               symmetry-aware projection distance, for pose batches. */
-#define FP_AMD_ABI_VERSION 220
+ *               symmetry-aware projection distance, for pose batches.
+ *   220 -> 221: + fp_tsdf_integrate, fp_tsdf_count_triangles, fp_tsdf_emit_triangles (additions only): an object's mesh from posed
+ *               RGB-D reference views (truncated-signed-distance fusion and marching tetrahedra). */
+#define FP_AMD_ABI_VERSION 221
 int fp_version(void);
 
 /* Utils.py:104-130 make_mesh_tensors: records caller-owned device tensors.
@@ -246,6 +248,68 @@ int fp_vsd_counts(const float* est /*dev N,h,w*/, const float* gt /*dev G,h,w*/,
 int fp_mspd(const float* model_pts /*dev P,3*/, int P, const double* sym_tfs /*dev S,16|NULL*/, int S, const float* poses /*dev N,16*/,
             const double* gt /*dev G,16*/, const int32_t* gt_index /*dev N|NULL*/, int G, int N, const float* K /*host 9*/,
             double* out /*dev N*/, void* stream);
+
+/* An object's mesh from posed RGB-D reference views: truncated-signed-distance (TSDF) fusion into a caller-owned volume, then marching
+ * tetrahedra.  The volume has nz x ny x nx voxels; voxel (ix, iy, iz) has the linear index i = (iz * ny + iy) * nx + ix and, in the
+ * object frame, the position p = (ox + float(ix) * s, oy + float(iy) * s, oz + float(iz) * s) (origin o = {ox, oy, oz} and pitch s in
+ * metres; every operation below is float32 without contraction, one rounding per operation, in the order written).  Its arrays:
+ * tsdf (nz,ny,nx) in units of trunc, 1 where never observed; weight (nz,ny,nx), the number of observations; color (nz,ny,nx,3) in the
+ * units of rgb; color_weight (nz,ny,nx).  A fresh volume is tsdf = 1 and zeros elsewhere (the caller fills it).
+ *
+ * fp_tsdf_integrate fuses V views into the volume: depth (V,H,W) metres, rgb (V,H,W,3), masks (V,H,W) uint8 (NULL: every pixel is the
+ * object's), ob_in_cams (V,16) row-major object-to-camera transforms T, Ks (V,9) float64 on the device (as the *_views entry points
+ * take them), rounded to float32 {fx, skew, cx, 0, fy, cy, ...}.  One voxel per lane; the views are visited inside the kernel in index
+ * order, so a voxel's running means have one summation order: no atomics, every call repeats its bits, and a call over views 0..k
+ * followed by a call over k+1..V-1 leaves the bits of one call over 0..V-1.  A view whose 16 pose values, fx, fy, cx, cy are not all
+ * finite, or whose skew is not 0, is skipped for every voxel.  Otherwise, per voxel:
+ *   X = ((T00*px + T01*py) + T02*pz) + T03, Y and Z likewise from rows 1 and 2;   skip the view unless Z > 0;
+ *   u = floorf(((fx * X) / Z + cx) + 0.5f),  v = floorf(((fy * Y) / Z + cy) + 0.5f);   skip the view unless 0 <= u < W and 0 <= v < H
+ *     (compared as floats: a NaN or an infinity skips);
+ *   mask[v][u] == 0: the pixel saw past the object, the voxel is empty: obs = 1, no colour (this is the space carving that removes
+ *     the background and the table; the views are assumed to show the object unoccluded);
+ *   otherwise d = depth[v][u];  skip the view unless d >= min_depth (holes, negatives, NaN);  sdf = d - Z;  skip the view if
+ *     sdf < -trunc (the voxel is hidden behind the surface);  q = sdf / trunc;  obs = q < 1 ? q : 1;
+ *   tsdf = (tsdf * weight + obs) / (weight + 1);  weight = weight + 1;
+ *   and, when the mask is not 0 and |sdf| <= trunc, per channel color = (color * color_weight + rgb[v][u]) / (color_weight + 1), then
+ *     color_weight = color_weight + 1.
+ * No index outside the frames or the volume is formed.  V == 0 does nothing.  No allocation, no host synchronisation
+ * (graph-capturable; origin is read during the call); nothing is written outside the four arrays.
+ *
+ * fp_tsdf_count_triangles: counts[c] (int32, 0..12) for each of the (nz-1)(ny-1)(nx-1) cubes, c = (cz * (ny-1) + cy) * (nx-1) + cx,
+ * whose corner of smallest index is voxel (cx, cy, cz).  A cube is split along its main diagonal into the six Kuhn tetrahedra, one per
+ * permutation (a, b, c) of the axes (x = 0, y = 1, z = 2) in lexicographic order, with the corners p0 = the cube's corner,
+ * p1 = p0 + e_a, p2 = p1 + e_b, p3 = p2 + e_c (neighbouring cubes split their common face alike, which makes the surface watertight).
+ * A tetrahedron counts only if weight >= min_weight at its four corners.  Corner k is inside when tsdf < 0 (0 is outside); the four
+ * bits select one of 16 cases with 0, 1 or 2 triangles (csrc/tsdf_tables.h, written by csrc/gen_tsdf_tables.py).  A volume with a
+ * dimension of 1 has no cubes: nothing is written.
+ *
+ * fp_tsdf_emit_triangles: the triangles themselves.  offsets (int64, one per cube) is the exclusive prefix sum of counts and total
+ * its sum; triangle offsets[c] + j is the j-th of cube c, in the order tetrahedron, then table order; so the output does not depend on
+ * scheduling.  Per triangle corner (3 per triangle, rows 3 * t + k of the outputs), which lies on the grid edge between the voxels
+ * a < b (linear indices):
+ *   keys = a * 2^32 + b (int64);  t = fa / (fa - fb) with fa = tsdf[a], fb = tsdf[b];
+ *   pos = pa + t * (pb - pa) per component (every tetrahedron sharing the edge computes the same bits);
+ *   col = ca + t * (cb - ca) per channel when color_weight > 0 at both ends, the colour of the one end where it is, 128 otherwise;
+ *   nrm = g / sqrtf((gx*gx + gy*gy) + gz*gz) with g = ga + t * (gb - ga) per component, or (0, 0, 1) unless that length is > 0.  The
+ *     gradient of tsdf at a voxel is, per axis, 0.5f * (tsdf[i+1] - tsdf[i-1]) inside, tsdf[i+1] - tsdf[i] at the low face and
+ *     tsdf[i] - tsdf[i-1] at the high face of the volume.
+ * (v1 - v0) x (v2 - v0) points towards increasing tsdf (outwards).  A triangle whose index is not below total is not written.
+ * No allocation, no host synchronisation; nothing is written outside the four outputs.
+ * Argument errors (FP_ERR_INVALID_ARG): NULL origin; NULL depth / rgb / ob_in_cams / Ks with V > 0; a NULL volume array or output;
+ * V outside 0..4096; H or W below 1 or more than 2^28 pixels; a dimension outside 1..FP_TSDF_MAX_DIM or more than 2^30 voxels; voxel or
+ * trunc not finite or not > 0; min_depth or min_weight not finite; min_depth < 0; an origin that is not finite; total outside
+ * 0..2^29. */
+#define FP_TSDF_MAX_DIM 4096
+int fp_tsdf_integrate(const float* depth /*dev V,H,W*/, const float* rgb /*dev V,H,W,3*/, const uint8_t* masks /*dev V,H,W|NULL*/,
+                      const float* ob_in_cams /*dev V,16*/, const double* Ks /*dev V,9*/, int V, int H, int W, int nz, int ny, int nx,
+                      const float* origin /*host 3*/, float voxel, float trunc, float min_depth, float* tsdf /*dev nz,ny,nx*/,
+                      float* weight /*dev nz,ny,nx*/, float* color /*dev nz,ny,nx,3*/, float* color_weight /*dev nz,ny,nx*/, void* stream);
+int fp_tsdf_count_triangles(const float* tsdf /*dev nz,ny,nx*/, const float* weight /*dev nz,ny,nx*/, int nz, int ny, int nx,
+                            float min_weight, int32_t* counts /*dev (nz-1)(ny-1)(nx-1)*/, void* stream);
+int fp_tsdf_emit_triangles(const float* tsdf /*dev*/, const float* weight /*dev*/, const float* color /*dev*/,
+                           const float* color_weight /*dev*/, int nz, int ny, int nx, const float* origin /*host 3*/, float voxel,
+                           float min_weight, const int64_t* offsets /*dev, one per cube*/, long long total, int64_t* keys /*dev 3*total*/,
+                           float* pos /*dev 3*total,3*/, float* col /*dev 3*total,3*/, float* nrm /*dev 3*total,3*/, void* stream);
 /* fp_pose_update_multi with K = Ks[view[n]] (read by trans_rep deepim only; Ks is required either way) */
 int fp_pose_update_views(const float* trans /*dev N,3*/, const float* rot /*dev N,3|6*/, const float* poses_in /*dev N,16*/,
                          int rot_rep, int normalize_xyz, const float* trans_normalizer /*host 3*/, float rot_normalizer,

@@ -3,7 +3,10 @@
 first frame, track the following frames, write ob_in_cam/<frame>.txt.  `--synthetic N` first writes an N-frame
 synthetic sequence (the textured can moving in front of the camera) in the demo layout, because the reference's
 demo_data and weights are not redistributable; with real data pass --mesh_file / --test_scene_dir and put the
-checkpoints under $FOUNDATIONPOSE_WEIGHTS.  Visualisation (debug >= 1 overlays) is not implemented."""
+checkpoints under $FOUNDATIONPOSE_WEIGHTS.  Visualisation (debug >= 1 overlays) is not implemented.
+Without a CAD model: `--ref_views DIR` (a directory in the same layout whose frames each carry a mask and an annotated pose) fuses the
+object's mesh from those reference views (foundationpose_amd/reconstruct.py) in place of --mesh_file; `--synthetic_ref_views N` writes
+such a directory from the can first; `--save_mesh PATH` writes the mesh that was used as a PLY."""
 import argparse
 import logging
 import os
@@ -46,6 +49,33 @@ def write_synthetic_demo(out_dir, n_frames, dev):
     return mesh_file, out_dir, poses
 
 
+def write_synthetic_ref_views(out_dir, n_views, dev, distance=0.5):
+    """n_views frames of the can seen from all around at `distance`, composed like the demo frames, with masks and poses"""
+    from foundationpose_amd import synthetic as syn
+    from foundationpose_amd.datareader import write_sequence
+    from foundationpose_amd.mesh import make_can_mesh
+    from foundationpose_amd.Utils import make_mesh_tensors, nvdiffrast_render
+    gm = make_mesh_tensors(make_can_mesh(), device=dev)
+    poses = syn.reference_view_poses(n_views, distance)
+    color, depth, _ = nvdiffrast_render(K=syn.YCBV_K, H=syn.H, W=syn.W, ob_in_cams=torch.as_tensor(poses, device=dev, dtype=torch.float),
+                                        mesh_tensors=gm, use_light=True, extra={})
+    frames = [syn.compose_frame(color[i].cpu().numpy(), depth[i].cpu().numpy(), seed=100 + i) for i in range(n_views)]
+    write_sequence(out_dir, syn.YCBV_K, [f[0] for f in frames], [f[1] for f in frames], [f[2] for f in frames], gt_poses=list(poses))
+    return out_dir
+
+
+def read_ref_views(ref_dir):
+    """-> rgbs, depths, masks, ob_in_cams, K of a reference-view directory; every frame needs its mask and its pose"""
+    from foundationpose_amd.datareader import YcbineoatReader
+    reader = YcbineoatReader(video_dir=ref_dir, shorter_side=None, zfar=np.inf)
+    n = len(reader)
+    if len(reader.gt_pose_files) != n:
+        raise SystemExit(f"--ref_views {ref_dir}: {n} frames but {len(reader.gt_pose_files)} poses under annotated_poses/")
+    poses = np.stack([reader.get_gt_pose(i) for i in range(n)])
+    return (np.stack([reader.get_color(i) for i in range(n)]), np.stack([reader.get_depth(i) for i in range(n)]).astype(np.float32),
+            np.stack([reader.get_mask(i) for i in range(n)]), poses.astype(np.float32), reader.K)
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--mesh_file", type=str, default=None)
@@ -57,13 +87,16 @@ def main(argv=None):
     ap.add_argument("--synthetic", type=int, default=0, help="write an N-frame synthetic demo sequence first and run on it")
     ap.add_argument("--track_graph", action="store_true", help="replay track_one as one captured hipGraph per frame")
     ap.add_argument("--standin_weights", action="store_true", help="seeded stand-in checkpoints instead of weights/")
+    ap.add_argument("--ref_views", type=str, default=None, help="posed RGB-D reference views with masks, in place of --mesh_file")
+    ap.add_argument("--synthetic_ref_views", type=int, default=0, help="write N reference views of the can first and use them")
+    ap.add_argument("--save_mesh", type=str, default=None, help="write the mesh that is used to this PLY")
     args = ap.parse_args(argv)
     logging.basicConfig(level=logging.INFO, format="[%(funcName)s()] %(message)s")
 
     from foundationpose_amd import dr
     from foundationpose_amd.datareader import YcbineoatReader
     from foundationpose_amd.estimater import FoundationPose
-    from foundationpose_amd.mesh_io import load_mesh
+    from foundationpose_amd.mesh_io import load_mesh, save_ply
     from foundationpose_amd.predict_pose_refine import PoseRefinePredictor
     from foundationpose_amd.predict_score import ScorePredictor
     from foundationpose_amd.Utils import set_seed
@@ -75,9 +108,19 @@ def main(argv=None):
     if args.synthetic > 0:
         args.mesh_file, args.test_scene_dir, gt = write_synthetic_demo(os.path.join(args.debug_dir, "synthetic_scene"), args.synthetic, dev)
         args.standin_weights = True
-    if not args.mesh_file or not args.test_scene_dir:
-        ap.error("--mesh_file and --test_scene_dir are required (or --synthetic N)")
-    mesh = load_mesh(args.mesh_file)
+    if args.synthetic_ref_views > 0:
+        args.ref_views = write_synthetic_ref_views(os.path.join(args.debug_dir, "synthetic_ref_views"), args.synthetic_ref_views, dev)
+    if not (args.mesh_file or args.ref_views) or not args.test_scene_dir:
+        ap.error("--mesh_file (or --ref_views) and --test_scene_dir are required (or --synthetic N)")
+    if args.ref_views:
+        from foundationpose_amd.reconstruct import reconstruct_object
+        t0 = time.perf_counter()
+        mesh, _ = reconstruct_object(*read_ref_views(args.ref_views), device=dev)
+        logging.info(f"mesh from {args.ref_views}: {len(mesh.vertices)} vertices, {len(mesh.faces)} faces in {time.perf_counter() - t0:.2f} s")
+    else:
+        mesh = load_mesh(args.mesh_file)
+    if args.save_mesh:
+        save_ply(mesh, args.save_mesh)
     os.makedirs(os.path.join(args.debug_dir, "ob_in_cam"), exist_ok=True)
     if args.standin_weights:
         scorer = ScorePredictor(cfg=dict(DEFAULT_SCORE_CFG), state_dict=random_state_dict("score", seed=0), device=dev)
