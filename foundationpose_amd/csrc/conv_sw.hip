@@ -70,7 +70,22 @@ __device__ __forceinline__ int sw_q(const IgemmGeom& g, int m) {
 
 // Tile shapes: 512 x 128 (the product's, every layer since round 4: see SW_FORCE_512 below) and 256 x 256 (N % 256 == 0); each wave owns
 // 128 x 64 outputs = 16 MFMAs per k-step either way.
-template <int BM, int BN, int TM>
+// S16 (round 7): the main loop on v_mfma_f32_16x16x32_f16 instead of v_mfma_f32_32x32x16_f16.  The wave tile, the LDS image of the
+// weights, the staging and the schedule are the same; what changes is the fragment map -- lane l holds row (l & 15) and the 16-byte chunk
+// (l >> 4) of a 64-byte row, so ONE ds_read_b128 fetches a K = 32 fragment of 16 rows: 8 pixel + 4 weight fragments per k-step, 32 MFMAs:
+//  * ds_read_b128 serves the lanes in four non-contiguous groups of 16 ({0-3, 12-15, 20-27}, {4-11, 16-19, 28-31}, + 32), i.e. 8 rows of
+//    one chunk and the 8 other rows of its neighbour.  The patch is therefore swizzled chunk ^ 2 * ((row >> 2) & 1): conflict-free for 16
+//    consecutive patch rows at ANY offset, 2-way across one image-row crossing (tests/test_conv_sw16_model.py; chunk ^ ((row >> 2) & 3)
+//    is 2-way under this lane map: 1027 against 681 clocks per k-step for the fragment reads alone, scripts/conv_loop_probe).
+//  * the weight rows keep their image (and the tile-packed copy its layout); a fragment's A rows take the tile's channel quads in the order
+//    sigma = (0, 2, 3, 1), which makes the aligned 16-row read conflict-free on that image; the epilogue undoes sigma (igemm_epilogue.h).
+//  * a 16x16x32 MFMA holds the SIMD's vector issue for half of its 16 cycles (a 32x32x16 for a quarter of its 32), so the tap addresses in
+//    the MFMA shadow are cut to three instructions per fragment (add, shift, and-xor), 24 per k-step: with the five-instruction form of the
+//    32x32x16 loop (64 per k-step) the partner group's fragment reads no longer found issue slots (scripts/conv_loop_probe,
+//    profiles/r07_a_mfma_shape_probe.log: 1390 -> 1302 clocks per k-step).
+// Sums of 32 products per MFMA instead of 2 x 16: by the ISA equal to S16 = false up to fp32 summation order only; measured on gfx950 the two
+// loops return the same bits on every tested layer (profiles/r07_b_ab_mfma_shape.log), and the tests hold both to the policy's flip gates.
+template <int BM, int BN, int TM, bool S16>
 __global__ __launch_bounds__(512, 1) void k_conv_sw(IgemmParams p) {
   constexpr int BK = SW_BK, NW = 8, THREADS = 512;
   constexpr int NWN = BN / 64;
@@ -84,7 +99,8 @@ __global__ __launch_bounds__(512, 1) void k_conv_sw(IgemmParams p) {
   static_assert(WI >= 1 && PI >= 1 && PI <= 7 && SW_PROWS == PI * 16 * NW, "tile shape");
   constexpr int STAGES_BYTES = 2 * SW_PATCH_BYTES + SW_NSTW * W_BYTES;
   constexpr int LDS_MAIN = ig_lds_main<BM, BN>(STAGES_BYTES);
-  auto swz = [](int row) { return (row >> 2) & 3; };
+  auto swz = [](int row) { return (row >> 2) & 3; };                    // weight rows, and patch rows of the 32x32x16 loop
+  auto swzp = [](int row) { return S16 ? (row >> 1) & 2 : (row >> 2) & 3; };   // patch rows
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   SW_CLK(t_start);
   unsigned char* const patch = smem;                              // 2 x SW_PATCH_BYTES
@@ -116,7 +132,7 @@ __global__ __launch_bounds__(512, 1) void k_conv_sw(IgemmParams p) {
 #pragma unroll
   for (int j = 0; j < PI; ++j) {
     const int row = (wid * PI + j) * 16 + (lane >> 2);
-    const int c = (lane & 3) ^ swz(row);
+    const int c = (lane & 3) ^ swzp(row);
     int q = q0 + row;
     q = q < qmax ? q : qmax;
     poff32[j] = (unsigned)(((long long)q * p.in.cstride + p.in.coff + c * 8) * 2);
@@ -152,28 +168,43 @@ __global__ __launch_bounds__(512, 1) void k_conv_sw(IgemmParams p) {
                                                (int)woff32[j], wsoff, 0, 0);
   };
 
-  float16_ acc[2][TM];
+  // accumulators: 2 x TM tiles of 32 ch x 32 px (16 floats per lane), or 4 x 2 TM tiles of 16 x 16 (4 floats per lane)
+  constexpr int NFA = S16 ? 2 * TM : TM, NFW = S16 ? 4 : 2;       // pixel / weight fragment rows of a wave (x 2 k halves for 32x32x16)
+  constexpr int FR = S16 ? 16 : 32;                               // rows of a fragment
+  typedef float float4_ __attribute__((ext_vector_type(4)));
+  typedef typename std::conditional<S16, float4_, float16_>::type acc_t;
+  acc_t acc[NFW][NFA];
 #pragma unroll
-  for (int i = 0; i < 2; ++i)
+  for (int i = 0; i < NFW; ++i)
 #pragma unroll
-    for (int j = 0; j < TM; ++j)
+    for (int j = 0; j < NFA; ++j)
 #pragma unroll
-      for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
+      for (int e = 0; e < (S16 ? 4 : 16); ++e) acc[i][j][e] = 0.f;
 
   // fragment addressing: the lane's pixel rows (position in the patch at tap (0,0)) and its weight rows
-  const int frow = lane & 31, fhalf = lane >> 5;
-  int arow[TM], w_off[2][2];
+  const int frow = lane & (FR - 1), fhalf = lane >> (S16 ? 4 : 5);     // fhalf: the lane's 16-byte chunk (S16) / chunk within a k half
+  int arow[NFA], w_off[2][2];                                      // S16: w_off[t >> 1][t & 1] is weight fragment t
 #pragma unroll
-  for (int t = 0; t < TM; ++t) {
-    int m = m0 + wm * (32 * TM) + t * 32 + frow;
+  for (int t = 0; t < NFA; ++t) {
+    int m = m0 + wm * (32 * TM) + t * FR + frow;
     m = m < p.M ? m : p.M - 1;
     arow[t] = sw_q(p.in, m) - q0;
+    if constexpr (S16) arow[t] = (arow[t] << 6) + (fhalf << 4);    // as a byte address: a tap adds shift << 6, the swizzle flips bit 5
   }
+  if constexpr (S16) {
+    const int quad = (0x1320 >> (4 * (frow >> 2))) & 3;            // sigma
 #pragma unroll
-  for (int t = 0; t < 2; ++t) {
-    const int rw = wn * 64 + t * 32 + frow;
+    for (int t = 0; t < 4; ++t) {
+      const int rw = wn * 64 + t * 16 + 4 * quad + (frow & 3);
+      w_off[t >> 1][t & 1] = rw * ROWB + ((fhalf ^ swz(rw)) << 4);
+    }
+  } else {
 #pragma unroll
-    for (int kk = 0; kk < 2; ++kk) w_off[t][kk] = rw * ROWB + (((2 * kk + fhalf) ^ swz(rw)) << 4);
+    for (int t = 0; t < 2; ++t) {
+      const int rw = wn * 64 + t * 32 + frow;
+#pragma unroll
+      for (int kk = 0; kk < 2; ++kk) w_off[t][kk] = rw * ROWB + (((2 * kk + fhalf) ^ swz(rw)) << 4);
+    }
   }
 
   // ---- prologue: patch(0) + W of k-steps 0..2 in flight; patch(0) and W(0) landed and visible
@@ -187,11 +218,12 @@ __global__ __launch_bounds__(512, 1) void k_conv_sw(IgemmParams p) {
   SW_CLK(t_cold);
   if (grp) __builtin_amdgcn_s_barrier();           // group 1 sits out interval 0
 
-  half8 fa[2][TM], fw[2][2];
-  static_assert(TM == 4, "the four fragment addresses of the next tap are computed behind the four MFMA groups of a k-step");
-  int anext[TM];                                   // fragment addresses of the next k-step's tap, inside a patch buffer
+  half8 fa[2][TM], fw[2][2];                       // S16: fa[t >> 2][t & 3] is pixel fragment t, fw[t >> 1][t & 1] weight fragment t
+  static_assert(TM == 4, "the fragment addresses of the next tap are computed behind the MFMA groups of a k-step, one per group of four");
+  int anext[NFA];                                  // fragment addresses of the next k-step's tap, inside a patch buffer
 #pragma unroll
-  for (int t = 0; t < TM; ++t) anext[t] = (arow[t] << 6) + ((fhalf ^ swz(arow[t])) << 4);     // tap (0,0) of the first k-step
+  for (int t = 0; t < NFA; ++t)                    // tap (0,0) of the first k-step
+    anext[t] = S16 ? arow[t] ^ ((arow[t] >> 3) & 32) : (arow[t] << 6) + ((fhalf ^ swz(arow[t])) << 4);
   // one k-step = (chunk cc, tap T).  LAST: cc is the last chunk (no next patch; the weight prefetch runs dry).
   // vmcnt bookkeeping (loads retire in order): this wave's pieces of W(s+1) must have landed when it leaves the memory
   // cluster; younger and allowed in flight are W(s+2), W(s+3) and the patch pieces issued in this and the previous step.
@@ -207,17 +239,24 @@ __global__ __launch_bounds__(512, 1) void k_conv_sw(IgemmParams p) {
     // behind the MFMAs of the previous k-step (anext, below): the stand-alone probe of this loop (scripts/conv_loop_probe,
     // profiles/r06_i_conv_loop_probe.log) put the memory cluster at ~610 clk against the partner group's 512 clk of MFMAs, and without
     // the 32 address instructions at ~535 (matrix-pipe occupancy 0.84 -> 0.96); in the MFMA shadow they are free (<= 5 per MFMA hide)
+    if constexpr (S16) {
 #pragma unroll
-    for (int t = 0; t < TM; ++t) {
-      const int a0 = anext[t];
-      fa[0][t] = *reinterpret_cast<const half8*>(pb + a0);
-      fa[1][t] = *reinterpret_cast<const half8*>(pb + (a0 ^ 32));
+      for (int t = 0; t < NFA; ++t) fa[t >> 2][t & 3] = *reinterpret_cast<const half8*>(pb + anext[t]);
+#pragma unroll
+      for (int t = 0; t < 4; ++t) fw[t >> 1][t & 1] = *reinterpret_cast<const half8*>(wb + w_off[t >> 1][t & 1]);
+    } else {
+#pragma unroll
+      for (int t = 0; t < TM; ++t) {
+        const int a0 = anext[t];
+        fa[0][t] = *reinterpret_cast<const half8*>(pb + a0);
+        fa[1][t] = *reinterpret_cast<const half8*>(pb + (a0 ^ 32));
+      }
+#pragma unroll
+      for (int kk = 0; kk < 2; ++kk)
+#pragma unroll
+        for (int t = 0; t < 2; ++t) fw[kk][t] = *reinterpret_cast<const half8*>(wb + w_off[t][kk]);
     }
     (void)shift;
-#pragma unroll
-    for (int kk = 0; kk < 2; ++kk)
-#pragma unroll
-      for (int t = 0; t < 2; ++t) fw[kk][t] = *reinterpret_cast<const half8*>(wb + w_off[t][kk]);
     if constexpr (!LAST) {
       if constexpr (T < PI) stage_patch(cc + 1, T);
       // k-step s+3 = (cc, T+3) or (cc+1, T-6)
@@ -242,6 +281,22 @@ __global__ __launch_bounds__(512, 1) void k_conv_sw(IgemmParams p) {
       // the NEXT k-step's tap: (T + 1) % 9 -- the patch buffer (chunk parity) is added where the address is used
       constexpr int TN = (T + 1) % 9, kyn = TN / 3, kxn = TN - 3 * kyn;
       const int shift_n = kyn * Wp + kxn;
+      if constexpr (S16) {
+        int sh = shift_n << 6;
+        asm volatile("" : "+s"(sh));               // keep the per-tap recomputation: 72 hoisted tap addresses would spill
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+          for (int jh = 0; jh < 2; ++jh) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+              acc[i][jh * 4 + j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(fw[i >> 1][i & 1], fa[jh][j], acc[i][jh * 4 + j], 0, 0, 0);
+            // one pixel fragment's address behind each group of four MFMAs (8 fragments = the eight (i, jh) groups)
+            const int t = i * 2 + jh;
+            const int x = arow[t] + sh;
+            anext[t] = x ^ ((x >> 3) & 32);
+          }
+      } else {
 #pragma unroll
       for (int kk = 0; kk < 2; ++kk)
 #pragma unroll
@@ -258,6 +313,7 @@ __global__ __launch_bounds__(512, 1) void k_conv_sw(IgemmParams p) {
             anext[t] = (pr << 6) + ((fhalf ^ swz(pr)) << 4);
           }
         }
+      }
     }
     __builtin_amdgcn_s_setprio(0);
     __builtin_amdgcn_sched_barrier(0);
@@ -488,14 +544,14 @@ int sw_ls_launch(const IgemmParams& p, hipStream_t stream) {
   return FP_OK;
 }
 
-template <int BM, int BN, int TM>
+template <int BM, int BN, int TM, bool S16>
 int sw_launch(const IgemmParams& p, hipStream_t stream) {
   constexpr int LDS = ig_lds_main<BM, BN>(2 * sw_prows(BM) * SW_BK * 2 + SW_NSTW * BN * SW_BK * 2) + IG_BIAS_LDS;
   static_assert(LDS <= 160 * 1024, "does not fit the 160 KiB LDS");
   const long long tiles = (long long)fp_cdiv(p.M, BM) * (p.N / BN);
   FP_REQUIRE(tiles < (1ll << 31), "fp_igemm_f16_fwd: too many tiles");
-  FP_SET_MAX_LDS((k_conv_sw<BM, BN, TM>), LDS);
-  hipLaunchKernelGGL((k_conv_sw<BM, BN, TM>), dim3((unsigned)tiles), dim3(512), LDS, stream, p);
+  FP_SET_MAX_LDS((k_conv_sw<BM, BN, TM, S16>), LDS);
+  hipLaunchKernelGGL((k_conv_sw<BM, BN, TM, S16>), dim3((unsigned)tiles), dim3(512), LDS, stream, p);
   FP_CHECK_LAUNCH("fp_igemm_f16_fwd(conv_sw)");
   return FP_OK;
 }
@@ -556,8 +612,9 @@ int fp_conv3x3_sw_tile_rows(const IgemmParams& p) { return sw_tile_rows(p); }
 
 int fp_conv3x3_sw_launch(const IgemmParams& p, hipStream_t stream) {
   if (sw_variant(p) == 1) return sw_ls_launch<256, 128, 4>(p, stream);
-  if (sw_use_256(p)) return sw_launch<256, 256, 4>(p, stream);
-  return sw_launch<512, 128, 4>(p, stream);
+  // p.mfma16: the MFMA shape of the ping-pong kernel's main loop (FP_IGEMM_MFMA_* of the epilogue flags; include/fp_amd.h)
+  if (sw_use_256(p)) return p.mfma16 ? sw_launch<256, 256, 4, true>(p, stream) : sw_launch<256, 256, 4, false>(p, stream);
+  return p.mfma16 ? sw_launch<512, 128, 4, true>(p, stream) : sw_launch<512, 128, 4, false>(p, stream);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------

@@ -395,7 +395,10 @@ static int ig_build_params(const void* x, const fp_igemm_geom* x_geom, const voi
   FP_REQUIRE(!e.residual || e.r_geom, "%s: residual without geometry", who);
   FP_REQUIRE((e.bn_scale == nullptr) == (e.bn_shift == nullptr), "%s: bn_scale and bn_shift go together", who);
   FP_REQUIRE(!e.bn_scale || (e.flags & FP_IGEMM_ROUND_ACC), "%s: BatchNorm needs FP_IGEMM_ROUND_ACC (conv semantics)", who);
-  FP_REQUIRE((e.flags & ~(FP_IGEMM_RELU | FP_IGEMM_ROUND_ACC | FP_IGEMM_HAS_W_TILES)) == 0, "%s: unknown flags 0x%x", who, e.flags);
+  FP_REQUIRE((e.flags & ~(FP_IGEMM_RELU | FP_IGEMM_ROUND_ACC | FP_IGEMM_HAS_W_TILES | FP_IGEMM_MFMA_16X16X32 | FP_IGEMM_MFMA_32X32X16)) == 0,
+             "%s: unknown flags 0x%x", who, e.flags);
+  FP_REQUIRE((e.flags & (FP_IGEMM_MFMA_16X16X32 | FP_IGEMM_MFMA_32X32X16)) != (FP_IGEMM_MFMA_16X16X32 | FP_IGEMM_MFMA_32X32X16),
+             "%s: FP_IGEMM_MFMA_16X16X32 and FP_IGEMM_MFMA_32X32X16 exclude each other", who);
   FP_REQUIRE((e.pe == nullptr) == (e.y_pe == nullptr) && (!e.pe || e.pe_period > 0), "%s: pe, pe_period and y_pe go together", who);
   FP_REQUIRE((((size_t)x | (size_t)w | (size_t)y | (size_t)e.residual | (size_t)e.bias | (size_t)e.bn_scale | (size_t)e.bn_shift |
                (size_t)e.pe | (size_t)e.y_pe) & 15) == 0, "%s: tensors must be 16-byte aligned", who);
@@ -411,6 +414,7 @@ static int ig_build_params(const void* x, const fp_igemm_geom* x_geom, const voi
   p.pe = e.pe; p.Ype = (_Float16*)e.y_pe; p.pe_period = e.pe_period;
   p.M = M; p.N = N; p.Cin = Cin; p.taps = taps; p.relu = (e.flags & FP_IGEMM_RELU) ? 1 : 0;
   p.round_acc = (e.flags & FP_IGEMM_ROUND_ACC) ? 1 : 0;
+  p.mfma16 = (e.flags & FP_IGEMM_MFMA_32X32X16) ? 0 : ((e.flags & FP_IGEMM_MFMA_16X16X32) ? 1 : SW_DEFAULT_MFMA16);
   p.in = ig_geom(x_geom); p.out = ig_geom(y_geom); p.res = e.residual ? ig_geom(e.r_geom) : ig_geom(y_geom);
   p.slab = nullptr; p.nsplit = 0;
   return FP_OK;

@@ -8,6 +8,9 @@ typedef _Float16 half4 __attribute__((ext_vector_type(4)));
 typedef float float16_ __attribute__((ext_vector_type(16)));
 
 #define IG_BK 64
+#ifndef SW_DEFAULT_MFMA16
+#define SW_DEFAULT_MFMA16 1   // k_conv_sw without FP_IGEMM_MFMA_*: the 16x16x32 main loop (IgemmParams.mfma16)
+#endif
 
 struct IgemmGeom {      // row m -> element offset of pixel (b, y*stride + pad_off, x*stride + pad_off) in a padded NHWC buffer
   int HoWo, Wo;         // output pixels per image / per row (1,1 for a plain GEMM)
@@ -54,6 +57,7 @@ struct IgemmParams {
   int round_acc;        // FP_IGEMM_ROUND_ACC: the accumulator is rounded to fp16 BEFORE the bias is added (nn.Conv2d under
                         // autocast: ATen adds the bias to the fp16 convolution output); 0: one rounding of acc + bias (nn.Linear)
   IgemmGeom in, out, res;
+  int mfma16;           // k_conv_sw: main loop on v_mfma_f32_16x16x32_f16 (1) or v_mfma_f32_32x32x16_f16 (0); FP_IGEMM_MFMA_*
   float* slab;          // split-K only (fp_igemm_f16_splitk_fwd): fp32 partial accumulators in fragment order,
   int nsplit;           //   [split][tile][wave][(i, g, j)][lane] x float4; 0 = not split
 };

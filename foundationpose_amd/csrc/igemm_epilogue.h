@@ -4,6 +4,7 @@
 // LDS layout of a kernel that uses it: [0, ig_lds_main) shared by the staging buffers of the main loop and, afterwards,
 // the E tile + its two row-offset tables; then IG_BIAS_LDS bytes of per-channel vectors (ig_bias_to_lds).
 #pragma once
+#include <type_traits>
 #include "igemm_common.h"
 
 #ifdef FP_PROFILE_BUILD
@@ -26,9 +27,14 @@ constexpr int ig_lds_main(int stage_bytes) {
   return stage_bytes > BM * BN * 2 + BM * 16 ? stage_bytes : BM * BN * 2 + BM * 16;   // E tile + the two row-offset tables
 }
 
-template <int BM, int BN, int TM, int THREADS, int DBG, bool FULL>
-__device__ __forceinline__ void ig_epilogue_body(const IgemmParams& p, float16_ (&acc)[2][TM], unsigned char* smem, int m0, int n0,
+// Acc: float16_[2][TM], the accumulators of v_mfma_f32_32x32x16_f16 (2 x TM tiles of 32 channels x 32 pixels), or float4_[4][2 * TM],
+// those of v_mfma_f32_16x16x32_f16 (4 x 2 TM tiles of 16 x 16, conv_sw.hip) -- the same 128 x 64 wave tile either way
+typedef float ig_float4 __attribute__((ext_vector_type(4)));
+template <int BM, int BN, int TM, int THREADS, int DBG, bool FULL, typename Acc>
+__device__ __forceinline__ void ig_epilogue_body(const IgemmParams& p, Acc& acc, unsigned char* smem, int m0, int n0,
                                                  int wm, int wn, int tid, int lane, const float* bias_lds) {
+  constexpr bool S16 = std::is_same<Acc, ig_float4[4][2 * TM]>::value;
+  static_assert(S16 || std::is_same<Acc, float16_[2][TM]>::value, "accumulator layout");
   constexpr int CPR = BN / 8;                      // 16-byte chunks per row of the epilogue tile
   constexpr int NIT = (BM * CPR) / THREADS;
   // ---- epilogue: accumulators (+bias) -> half -> swizzled LDS tile E[m][n] -> 16-B coalesced row stores
@@ -63,48 +69,72 @@ __device__ __forceinline__ void ig_epilogue_body(const IgemmParams& p, float16_ 
     }
   }
   IG_CLK(te2);
-  // D[i = channel][j = pixel]: lane holds pixel (lane & 31), channels 8g + 4*(lane>>5) + {0..3}, g = reg >> 2
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      const int nl = wn * 64 + i * 32 + 8 * g + 4 * (lane >> 5);   // first of 4 consecutive channels (tile-local)
-      // per-channel vectors of these 4 channels (LDS broadcast reads; kept out of registers until here)
-      const float4_ bv = *reinterpret_cast<const float4_*>(bias_lds + nl);
-      float4_ sc = {1.f, 1.f, 1.f, 1.f}, sh = {0.f, 0.f, 0.f, 0.f};
+  // 4 consecutive channels nl .. nl + 3 (tile-local) of pixel row ml: accumulators -> the policy's roundings -> E tile
+  auto put4 = [&](int nl, int ml, float a0, float a1, float a2, float a3, const float4_& bv, const float4_& sc, const float4_& sh) {
+    half4 v;
+    if (round_acc) {
+      // the reference's autocast op sequence for conv (+ BatchNorm): every op rounds its result to fp16.  Packed
+      // fp16 math where it is exact: v_cvt_pk_f16_f32 for the conv output, v_pk_add_f16 for the bias (an IEEE half
+      // add of two halves equals their fp32 sum rounded to half: when the fp32 sum is inexact the smaller addend is
+      // below 1/8 ulp of the larger), fp32 FMA for BatchNorm (fp32 statistics)
+      typedef _Float16 half2_ __attribute__((ext_vector_type(2)));
+      const half2_ b01 = {(_Float16)bv[0], (_Float16)bv[1]}, b23 = {(_Float16)bv[2], (_Float16)bv[3]};
+      half2_ t01 = {(_Float16)a0, (_Float16)a1};
+      half2_ t23 = {(_Float16)a2, (_Float16)a3};
+      t01 = t01 + b01;
+      t23 = t23 + b23;
       if (has_bn) {
-        sc = *reinterpret_cast<const float4_*>(bias_lds + IG_VEC_FLOATS + nl);
-        sh = *reinterpret_cast<const float4_*>(bias_lds + 2 * IG_VEC_FLOATS + nl);
+        v[0] = (_Float16)fmaf((float)t01[0], sc[0], sh[0]);
+        v[1] = (_Float16)fmaf((float)t01[1], sc[1], sh[1]);
+        v[2] = (_Float16)fmaf((float)t23[0], sc[2], sh[2]);
+        v[3] = (_Float16)fmaf((float)t23[1], sc[3], sh[3]);
+      } else {
+        v[0] = t01[0]; v[1] = t01[1]; v[2] = t23[0]; v[3] = t23[1];
       }
+    } else {
+      v[0] = (_Float16)(a0 + bv[0]); v[1] = (_Float16)(a1 + bv[1]); v[2] = (_Float16)(a2 + bv[2]); v[3] = (_Float16)(a3 + bv[3]);
+    }
+    const int chunk = (nl >> 3) ^ (ml & 15);
+    *reinterpret_cast<half4*>(E + ml * (2 * BN) + (chunk << 4) + ((nl & 4) << 1)) = v;
+  };
+  // per-channel vectors of 4 channels (LDS broadcast reads; kept out of registers until here)
+  auto vecs = [&](int nl, float4_& bv, float4_& sc, float4_& sh) {
+    bv = *reinterpret_cast<const float4_*>(bias_lds + nl);
+    sc = float4_{1.f, 1.f, 1.f, 1.f}; sh = float4_{0.f, 0.f, 0.f, 0.f};
+    if (has_bn) {
+      sc = *reinterpret_cast<const float4_*>(bias_lds + IG_VEC_FLOATS + nl);
+      sh = *reinterpret_cast<const float4_*>(bias_lds + 2 * IG_VEC_FLOATS + nl);
+    }
+  };
+  if constexpr (S16) {
+    // 16x16x32: D[channel][pixel] of a 16 x 16 tile: lane holds pixel (lane & 15) and the tile's channel quad (lane >> 4), which conv_sw.hip
+    // maps to channels 4 * sigma(lane >> 4) + {0..3}, sigma = (0, 2, 3, 1): the order of the weight rows in its A fragments
+    const int quad = (0x1320 >> (4 * (lane >> 4))) & 3;
 #pragma unroll
-      for (int j = 0; j < TM; ++j) {
-        const int ml = wm * (32 * TM) + j * 32 + (lane & 31);
-        half4 v;
-        if (round_acc) {
-          // the reference's autocast op sequence for conv (+ BatchNorm): every op rounds its result to fp16.  Packed
-          // fp16 math where it is exact: v_cvt_pk_f16_f32 for the conv output, v_pk_add_f16 for the bias (an IEEE half
-          // add of two halves equals their fp32 sum rounded to half: when the fp32 sum is inexact the smaller addend is
-          // below 1/8 ulp of the larger), fp32 FMA for BatchNorm (fp32 statistics)
-          typedef _Float16 half2_ __attribute__((ext_vector_type(2)));
-          const half2_ b01 = {(_Float16)bv[0], (_Float16)bv[1]}, b23 = {(_Float16)bv[2], (_Float16)bv[3]};
-          half2_ t01 = {(_Float16)acc[i][j][g * 4 + 0], (_Float16)acc[i][j][g * 4 + 1]};
-          half2_ t23 = {(_Float16)acc[i][j][g * 4 + 2], (_Float16)acc[i][j][g * 4 + 3]};
-          t01 = t01 + b01;
-          t23 = t23 + b23;
-          if (has_bn) {
-            v[0] = (_Float16)fmaf((float)t01[0], sc[0], sh[0]);
-            v[1] = (_Float16)fmaf((float)t01[1], sc[1], sh[1]);
-            v[2] = (_Float16)fmaf((float)t23[0], sc[2], sh[2]);
-            v[3] = (_Float16)fmaf((float)t23[1], sc[3], sh[3]);
-          } else {
-            v[0] = t01[0]; v[1] = t01[1]; v[2] = t23[0]; v[3] = t23[1];
-          }
-        } else {
+    for (int i = 0; i < 4; ++i) {
+      const int nl = wn * 64 + i * 16 + 4 * quad;
+      float4_ bv, sc, sh;
+      vecs(nl, bv, sc, sh);
 #pragma unroll
-          for (int e = 0; e < 4; ++e) v[e] = (_Float16)(acc[i][j][g * 4 + e] + bv[e]);
+      for (int j = 0; j < 2 * TM; ++j) {
+        const int ml = wm * (32 * TM) + j * 16 + (lane & 15);
+        put4(nl, ml, acc[i][j][0], acc[i][j][1], acc[i][j][2], acc[i][j][3], bv, sc, sh);
+      }
+    }
+  } else {
+    // 32x32x16: D[i = channel][j = pixel]: lane holds pixel (lane & 31), channels 8g + 4*(lane>>5) + {0..3}, g = reg >> 2
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        const int nl = wn * 64 + i * 32 + 8 * g + 4 * (lane >> 5);   // first of 4 consecutive channels (tile-local)
+        float4_ bv, sc, sh;
+        vecs(nl, bv, sc, sh);
+#pragma unroll
+        for (int j = 0; j < TM; ++j) {
+          const int ml = wm * (32 * TM) + j * 32 + (lane & 31);
+          put4(nl, ml, acc[i][j][g * 4 + 0], acc[i][j][g * 4 + 1], acc[i][j][g * 4 + 2], acc[i][j][g * 4 + 3], bv, sc, sh);
         }
-        const int chunk = (nl >> 3) ^ (ml & 15);
-        *reinterpret_cast<half4*>(E + ml * (2 * BN) + (chunk << 4) + ((nl & 4) << 1)) = v;
       }
     }
   }
@@ -140,8 +170,8 @@ __device__ __forceinline__ void ig_epilogue_body(const IgemmParams& p, float16_ 
 #endif
 }
 
-template <int BM, int BN, int TM, int THREADS, int DBG = 0>
-__device__ __forceinline__ void ig_epilogue(const IgemmParams& p, float16_ (&acc)[2][TM], unsigned char* smem, int m0, int n0,
+template <int BM, int BN, int TM, int THREADS, int DBG = 0, typename Acc>
+__device__ __forceinline__ void ig_epilogue(const IgemmParams& p, Acc& acc, unsigned char* smem, int m0, int n0,
                                             int wm, int wn, int tid, int lane, const float* bias_lds) {
   if (m0 + BM <= p.M) ig_epilogue_body<BM, BN, TM, THREADS, DBG, true>(p, acc, smem, m0, n0, wm, wn, tid, lane, bias_lds);
   else ig_epilogue_body<BM, BN, TM, THREADS, DBG, false>(p, acc, smem, m0, n0, wm, wn, tid, lane, bias_lds);

@@ -76,6 +76,10 @@ MERGED_HEAD_QKV = True
 # round 6: the whole encoder layer behind the attention context as ONE launch (csrc/linear_ln.hip k_rows512<.., TAIL>): out_proj + norm1
 # and the fused FFN + norm2 + token mean above, with norm1's fp16 output staying in LDS between them.  Same bits as the two launches.
 FUSED_TAIL = True
+# round 7: the main loop of the shifted-window 3x3 convolution (csrc/conv_sw.hip) on v_mfma_f32_16x16x32_f16; overrides(CONV_MFMA_16X16X32=False)
+# goes back to v_mfma_f32_32x32x16_f16.  The same products and rounding points; gated as equal up to summation-order flips
+# (tests/test_gpu_conv_sw16.py), measured bit-identical on the MI355X.  Read by ops.igemm_f16 at every call.  Why: DESIGN.md 3.2 / 8.1 (the clock the chip holds).
+CONV_MFMA_16X16X32 = True
 
 
 def _conv_backend():
@@ -219,7 +223,7 @@ SPLITK_TARGET_WGS = 384        # (tile, piece) workgroups a launch should have: 
 # the hard ceiling of both thresholds: overlap.SubBatches' default min_rows (a call of >= 2 x 32 hypotheses is split into sub-batches)
 SMALL_CALL_CEILING = 31
 
-_SWITCHES = ("FUSED_OUT_PROJ_LN", "FUSED_FFN", "ROWS_QKV", "PACKED_CONV_TILES", "MERGED_HEAD_QKV", "FUSED_TAIL", "SPLITK_MAX_HYPS", "HEADS_TWO_STREAMS_MAX_HYPS")
+_SWITCHES = ("FUSED_OUT_PROJ_LN", "FUSED_FFN", "ROWS_QKV", "PACKED_CONV_TILES", "MERGED_HEAD_QKV", "FUSED_TAIL", "CONV_MFMA_16X16X32", "SPLITK_MAX_HYPS", "HEADS_TWO_STREAMS_MAX_HYPS")
 
 
 @contextlib.contextmanager

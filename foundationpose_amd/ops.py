@@ -1081,6 +1081,8 @@ class IgemmGeom(C.Structure):
 IGEMM_RELU = 1
 IGEMM_ROUND_ACC = 2
 IGEMM_HAS_W_TILES = 4
+IGEMM_MFMA_16X16X32 = 16
+IGEMM_MFMA_32X32X16 = 32
 
 
 class IgemmEpilogue(C.Structure):
@@ -1100,8 +1102,9 @@ def pack_conv3x3_tiles(w, N, Cin):
 
 
 def igemm_f16(x, x_geom, w, bias, y, y_geom, M, N, Cin, taps, relu=False, residual=None, r_geom=None, bn_scale=None,
-              bn_shift=None, conv_rounding=False, pe=None, y_pe=None, w_tiles=None):
-    """y = act(f16(epilogue(implicit_gemm(x, w))) (+ residual)) -- see fp_igemm_f16_fwd.  conv_rounding: nn.Conv2d under
+              bn_shift=None, conv_rounding=False, pe=None, y_pe=None, w_tiles=None, mfma16=None):
+    """y = act(f16(epilogue(implicit_gemm(x, w))) (+ residual)) -- see fp_igemm_f16_fwd.  mfma16: the MFMA shape of the shifted-window
+    conv's main loop (True 16x16x32, False 32x32x16); None = the engine switch CONV_MFMA_16X16X32.  conv_rounding: nn.Conv2d under
     autocast (accumulator rounded to fp16 before the bias add, optional BatchNorm as scale/shift with its own rounding);
     otherwise nn.Linear (one rounding of accumulator + bias).  pe (S, N) f32 + y_pe (M, N) fp16: second output
     f16(f32(y) + pe[m % S]).  All tensors are device buffers owned by the caller (y is written in place and returned)."""
@@ -1113,7 +1116,11 @@ def igemm_f16(x, x_geom, w, bias, y, y_geom, M, N, Cin, taps, relu=False, residu
     ep.bias, ep.bn_scale, ep.bn_shift = _ptr(b), _ptr(sc), _ptr(sh)
     ep.residual = _ptr(r)
     ep.r_geom = C.pointer(r_geom) if r_geom is not None else None
-    ep.flags = (IGEMM_RELU if relu else 0) | (IGEMM_ROUND_ACC if conv_rounding else 0) | IGEMM_HAS_W_TILES
+    if mfma16 is None:
+        from . import engine               # engine imports this module
+        mfma16 = engine.CONV_MFMA_16X16X32
+    ep.flags = (IGEMM_RELU if relu else 0) | (IGEMM_ROUND_ACC if conv_rounding else 0) | IGEMM_HAS_W_TILES | \
+        (IGEMM_MFMA_16X16X32 if mfma16 else IGEMM_MFMA_32X32X16)
     ep.pe, ep.pe_period, ep.y_pe = _ptr(pe), (int(pe.shape[-2]) if pe is not None else 0), _ptr(y_pe)
     ep.w_tiles = _ptr(_dev(w_tiles, torch.float16, "w_tiles"))
     st = _lib.lib().fp_igemm_f16_fwd(_ptr(x), C.byref(x_geom), _ptr(w), _ptr(y), C.byref(y_geom), int(M), int(N), int(Cin),

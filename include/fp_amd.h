@@ -78,8 +78,9 @@ const char* fp_last_error(void);
  *   219 -> 220: + fp_vsd_counts, fp_mspd (additions only): the pixel counts of BOP's visible surface discrepancy and its maximum
  *               symmetry-aware projection distance, for pose batches.
  *   220 -> 221: + fp_tsdf_integrate, fp_tsdf_count_triangles, fp_tsdf_emit_triangles (additions only): an object's mesh from posed
- *               RGB-D reference views (truncated-signed-distance fusion and marching tetrahedra). */
-#define FP_AMD_ABI_VERSION 221
+ *               RGB-D reference views (truncated-signed-distance fusion and marching tetrahedra).
+ *   221 -> 222: + FP_IGEMM_MFMA_16X16X32 / FP_IGEMM_MFMA_32X32X16 (additions only; an older library refuses the bits as unknown flags). */
+#define FP_AMD_ABI_VERSION 222
 int fp_version(void);
 
 /* Utils.py:104-130 make_mesh_tensors: records caller-owned device tensors.
@@ -416,6 +417,13 @@ typedef struct {
                                 bias to the fp16 convolution output) and BatchNorm, if given, rounds once more; without the
                                 flag: nn.Linear semantics, one rounding of accumulator + bias */
 
+/* Which MFMA instruction the main loop of the shifted-window 3x3 kernel (csrc/conv_sw.hip, ping-pong schedule) runs on: 32 v_mfma_f32_16x16x32_f16
+ * or 16 v_mfma_f32_32x32x16_f16 per wave and k-step.  The same products with the same rounding points; the order of the fp32 sums inside an
+ * MFMA is the hardware's, so the two are specified to agree up to summation order (on gfx950 they were measured to agree bit for bit).  Neither bit: the library's default (16x16x32); both: refused.
+ * Ignored by the launches that do not reach that kernel. */
+#define FP_IGEMM_MFMA_16X16X32 16
+#define FP_IGEMM_MFMA_32X32X16 32
+
 /* What fp_igemm_f16_fwd does with the fp32 accumulators (all members optional; NULL struct = plain fp16 store) */
 typedef struct {
   const float* bias;           /* dev (N) f32 | NULL; for conv semantics fp16-representable values */
@@ -423,7 +431,7 @@ typedef struct {
   const float* bn_shift;
   const void* residual;        /* dev fp16 | NULL: `out += identity` (network_modules.py:107), rounded to fp16 */
   const fp_igemm_geom* r_geom; /* host: addressing of the residual */
-  int flags;                   /* FP_IGEMM_RELU | FP_IGEMM_ROUND_ACC | FP_IGEMM_HAS_W_TILES */
+  int flags;                   /* FP_IGEMM_RELU | FP_IGEMM_ROUND_ACC | FP_IGEMM_HAS_W_TILES | FP_IGEMM_MFMA_* */
   const float* pe;             /* dev (pe_period, N) f32 | NULL: second output y_pe[m, n] = f16(f32(y[m, n]) + pe[m % pe_period, n]), */
   int pe_period;               /*   the PositionalEmbedding add of network_modules.py:133-137 fused into the last conv of the */
   void* y_pe;                  /*   encoder; y_pe is a plain (M, N) fp16 matrix */

@@ -9,6 +9,8 @@
 //   LS4   : 4 waves (one per SIMD, the whole register file), a wave owns 128 px x 128 ch = 32 MFMAs per k-step; the 16 fragment reads
 //           of k-step s + 1 and the step's 3 LDS-DMA pieces are interleaved with the MFMAs of k-step s; ONE barrier per k-step
 //   *_M   : the same loops with the MFMAs only (what the matrix pipe does alone under each wave shape)
+//   *16   : PP8_AC / PP8_M on v_mfma_f32_16x16x32_f16 (round 7; `cvprobe 2000 random shape [rounds]` interleaves the two shapes);
+//           AC16_* / MEM16_*: that loop taken apart as the PP8_* / MEM_* arms do (k_pp8_s16's FLAGS)
 //   *_ND  : no LDS-DMA in the loop;  *_NR: no fragment reads in the loop;  PP8_LW / _DF / _MEM: see main()
 #include <hip/hip_runtime.h>
 #include <cstdio>
@@ -210,6 +212,105 @@ __global__ __launch_bounds__(512, 1) void k_pp8(const _Float16* __restrict__ W, 
   if (tid == 0) atomicAdd(clk, t1 - t0);
 }
 
+// ---- round 7: the same loop on v_mfma_f32_16x16x32_f16 (DESIGN.md 8.1 "MFMA shape").  The wave tile stays 128 px x 64 ch: 8 pixel fragments x 4
+// weight fragments of 16 rows x K = 32, ONE ds_read_b128 each (lane l: row l & 15, 16-byte chunk l >> 4), 32 MFMAs per k-step, the tap
+// addresses of the next k-step one behind each group of four MFMAs (PP8_AC's schedule).  ds_read_b128 serves the lanes in four
+// non-contiguous groups of 16 ({0-3, 12-15, 20-27}, ...) that each hold 8 rows of one chunk and 8 of its neighbour, so the patch swizzle
+// is chunk ^ 2 * ((row >> 2) & 1) and the weight rows keep the image of the 32x32x16 loop with the tile's channel quads in the order 0, 2, 3, 1.
+// FLAGS: 1 = MFMAs only
+typedef float float4_ __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ int swz16(int row) { return (row >> 1) & 2; }
+template <int FLAGS>
+__global__ __launch_bounds__(512, 1) void k_pp8_s16(const _Float16* __restrict__ W, const _Float16* __restrict__ P, float* out, unsigned long long* clk, int ksteps, int tiles_per_wg) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  constexpr bool MONLY = FLAGS & 1, NODMA = FLAGS & 2, NOREAD = FLAGS & 4, NOMFMA = FLAGS & 16, OLDSWZ = FLAGS & 2048, SPREAD = FLAGS & 4096;
+  auto sz = [](int row) { return OLDSWZ ? swz(row) : swz16(row); };
+  unsigned char* patch = smem; unsigned char* wring = smem + 2 * PATCH_BYTES;
+  const int tid = threadIdx.x, lane = tid & 63, wid = __builtin_amdgcn_readfirstlane(tid >> 6), grp = wid >> 2;
+  const int wm = wid >> 1, wn = wid & 1, frow = lane & 15, fch = lane >> 4;
+  const __amdgpu_buffer_rsrc_t rsW = __builtin_amdgcn_make_buffer_rsrc(const_cast<_Float16*>(W), 0, 0x7FFFFFFF, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rsP = __builtin_amdgcn_make_buffer_rsrc(const_cast<_Float16*>(P), 0, 0x7FFFFFFF, 0x00020000);
+  float4_ acc[4][8];
+  for (int i = 0; i < 4; ++i) for (int j = 0; j < 8; ++j) for (int e = 0; e < 4; ++e) acc[i][j][e] = 0.f;
+  half8 fa[8], fw[4];
+  for (int j = 0; j < 8; ++j) for (int e = 0; e < 8; ++e) fa[j][e] = (_Float16)(0.001f * (lane + e + j));
+  for (int j = 0; j < 4; ++j) for (int e = 0; e < 8; ++e) fw[j][e] = (_Float16)(0.002f * (lane - e + j));
+  int arow[8], anext[8], abase[8], w_off[4];
+  for (int t = 0; t < 8; ++t) { arow[t] = wm * 128 + t * 16 + frow + 43; const int pr = arow[t] - 43; anext[t] = (pr << 6) + ((fch ^ sz(pr)) << 4); abase[t] = (pr << 6) + (fch << 4); }
+  for (int t = 0; t < 4; ++t) { const int q = frow >> 2, rw = wn * 64 + t * 16 + (OLDSWZ ? frow : 4 * ((0x1320 >> (4 * q)) & 3) + (frow & 3)); w_off[t] = rw * ROWB + ((fch ^ swz(rw)) << 4); }
+  const unsigned long long t0 = clock64();
+  for (int tile = 0; tile < tiles_per_wg; ++tile) {
+    const int pbase = ((blockIdx.x * tiles_per_wg + tile) % 4096) * (PATCH_BYTES * 2);
+    if (grp) __builtin_amdgcn_s_barrier();
+    for (int s = 0; s < ksteps; ++s) {
+      const int T = s % 9, cc = s / 9;
+      const unsigned char* pb = patch + (cc & 1) * PATCH_BYTES;
+      const unsigned char* wb = wring + (s & (NSTW - 1)) * W_BYTES;
+      if (!MONLY) {
+        if (!NOREAD) {
+#pragma unroll
+          for (int t = 0; t < 8; ++t) fa[t] = *reinterpret_cast<const half8*>(pb + anext[t]);
+#pragma unroll
+          for (int t = 0; t < 4; ++t) fw[t] = *reinterpret_cast<const half8*>(wb + w_off[t]);
+        }
+        if (!NODMA) {
+        if (T < 5) dma16(rsP, patch + ((cc + 1) & 1) * PATCH_BYTES + (wid * 5 + T) * 1024, lane * 16, pbase + (wid * 5 + T) * 1024);
+        dma16(rsW, wring + ((s + 3) & (NSTW - 1)) * W_BYTES + wid * 1024, lane * 16, ((s + 3) % 144) * W_BYTES + wid * 1024);
+        asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
+        }
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      }
+      __builtin_amdgcn_sched_barrier(0);
+      __builtin_amdgcn_s_barrier();
+      __builtin_amdgcn_sched_barrier(0);
+      __builtin_amdgcn_s_setprio(1);
+      if (NOMFMA) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) asm volatile("" :: "v"(fa[j]));
+        asm volatile("" :: "v"(fw[0]), "v"(fw[1]), "v"(fw[2]), "v"(fw[3]));
+      } else {
+        const int s1 = s + 1, T1 = s1 % 9;
+        const int shift1 = (T1 / 3) * 42 + (T1 % 3) - 43;
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+          for (int jh = 0; jh < 2; ++jh) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) acc[i][jh * 4 + j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(fw[i], fa[jh * 4 + j], acc[i][jh * 4 + j], 0, 0, 0);
+            if (!MONLY) {
+              const int t = i * 2 + jh;
+              if (OLDSWZ) {
+                int ar = arow[t]; asm volatile("" : "+v"(ar));
+                const int pr = ar + shift1;
+                anext[t] = (pr << 6) + ((fch ^ sz(pr)) << 4);
+              } else {                          // three vector instructions: add, shift, and-xor (bit 2 of the row = bit 8 of x -> bit 5)
+                int sh = (shift1 + 43) << 6; asm volatile("" : "+s"(sh));
+                const int x = abase[t] + sh;
+                anext[t] = x ^ ((x >> 3) & 32);
+              }
+            }
+          }
+        if (SPREAD && !MONLY) {      // address instructions spread behind single MFMAs instead of where the compiler clumps them
+#pragma unroll
+          for (int q = 0; q < 32; ++q) { __builtin_amdgcn_sched_group_barrier(0x008, 1, 0); __builtin_amdgcn_sched_group_barrier(0x002, OLDSWZ ? 2 : 1, 0); }
+        }
+      }
+      __builtin_amdgcn_s_setprio(0);
+      __builtin_amdgcn_sched_barrier(0);
+      __builtin_amdgcn_s_barrier();
+      __builtin_amdgcn_sched_barrier(0);
+    }
+    if (!grp) __builtin_amdgcn_s_barrier();
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+  }
+  const unsigned long long t1 = clock64();
+  float sum = 0.f;
+  for (int i = 0; i < 4; ++i) for (int j = 0; j < 8; ++j) for (int e = 0; e < 4; ++e) sum += acc[i][j][e];
+  out[blockIdx.x * 512 + tid] = sum;
+  if (tid == 0) atomicAdd(clk, t1 - t0);
+}
+
 template <int FLAGS>
 __global__ __launch_bounds__(256, 1) void k_ls4(const _Float16* __restrict__ W, const _Float16* __restrict__ P, float* out, unsigned long long* clk, int ksteps, int tiles_per_wg) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -301,7 +402,7 @@ static void run(const char* name, K kern, int threads, const _Float16* W, const 
     unsigned long long c; CK(hipMemcpy(&c, clk, 8, hipMemcpyDeviceToHost));
     const double per = (double)c / wgs / (ksteps * tiles);
     const double tf = 2.0 * 512 * 128 * 32 * ksteps * tiles * wgs / (ms * 1e-3) / 1e12;
-    if (rep == 2) printf("%-8s %8.1f clk per k-step (1024 = matrix pipe full)  occupancy %.3f   %7.1f TFLOP/s  %.3f ms  %.0f MHz\n", name, per, 1024.0 / per, tf, ms,
+    if (rep == 2) printf("%-9s %8.1f clk per k-step (1024 = matrix pipe full)  occupancy %.3f   %7.1f TFLOP/s  %.3f ms  %.0f MHz\n", name, per, 1024.0 / per, tf, ms,
                          (double)c / wgs / (ms * 1e3));
   }
 }
@@ -326,10 +427,25 @@ int main(int argc, char** argv) {
     free(h);
     printf("operands: random (weights N(0, 0.02), activations relu(N(0, 0.5)))\n");
   }
+  if (argc > 3) {           // argv[3] = "shape" (round 7): the product's loop and the MFMA-only loop on both MFMA shapes, interleaved in this one process
+    const int rounds = argc > 4 ? atoi(argv[4]) : 8;
+    for (int r = 0; r < rounds; ++r) {
+      printf("round %d\n", r);
+      run("PP8_AC", k_pp8<1024>, 512, W, P, out, clk); run("PP8_AC16", k_pp8_s16<0>, 512, W, P, out, clk);
+      run("PP8_M", k_pp8<1>, 512, W, P, out, clk); run("PP8_M16", k_pp8_s16<1>, 512, W, P, out, clk);
+    }
+    return 0;
+  }
   if (g_tiles > 100) {      // long launches: the three that matter, twice
     for (int r = 0; r < 2; ++r) { run("PP8", k_pp8<0>, 512, W, P, out, clk); run("PP8_AC", k_pp8<1024>, 512, W, P, out, clk); run("PP8_M", k_pp8<1>, 512, W, P, out, clk);
                                   run("LS4", k_ls4<0>, 256, W, P, out, clk); run("LS4_M", k_ls4<1>, 256, W, P, out, clk); run("PP8_NR", k_pp8<4>, 512, W, P, out, clk); run("PP8_ND", k_pp8<2>, 512, W, P, out, clk); }
     return 0;
+  }
+  if (argc == 1) {          // the 16x16x32 loop taken apart (round 7), next to the 32x32x16 loop's arms below
+    run("PP8_AC16", k_pp8_s16<0>, 512, W, P, out, clk); run("AC16_SP", k_pp8_s16<4096>, 512, W, P, out, clk); run("AC16_OSW", k_pp8_s16<2048>, 512, W, P, out, clk);
+    run("AC16_ND", k_pp8_s16<2>, 512, W, P, out, clk); run("AC16_NR", k_pp8_s16<4>, 512, W, P, out, clk); run("AC16_NDNR", k_pp8_s16<6>, 512, W, P, out, clk);
+    run("AC16_MEM", k_pp8_s16<16>, 512, W, P, out, clk); run("MEM16_ND", k_pp8_s16<16 | 2>, 512, W, P, out, clk); run("MEM16_NR", k_pp8_s16<16 | 4>, 512, W, P, out, clk);
+    run("MEM16_OSW", k_pp8_s16<16 | 2 | 2048>, 512, W, P, out, clk); run("PP8_M16", k_pp8_s16<1>, 512, W, P, out, clk);
   }
   run("PP8", k_pp8<0>, 512, W, P, out, clk);
   run("PP8_M", k_pp8<1>, 512, W, P, out, clk);

@@ -142,7 +142,7 @@ t_render() {     # fp_render_crops alone (LIBS="product ..."): us per launch + o
   done
 }
 t_convprobe() {  # stand-alone replica of the conv main loop (scripts/conv_loop_probe): short (clocks per k-step), long with random operands (power cap)
-  hipcc --offload-arch=gfx950 -O3 -o /tmp/cvprobe scripts/conv_loop_probe/probe.hip && { timeout 200 /tmp/cvprobe; timeout 300 /tmp/cvprobe 2000; timeout 300 /tmp/cvprobe 2000 random; } | tee $O/${TAG}_conv_loop_probe.log
+  hipcc --offload-arch=gfx950 -O3 -o /tmp/cvprobe scripts/conv_loop_probe/probe.hip && { timeout 200 /tmp/cvprobe; timeout 300 /tmp/cvprobe 2000; timeout 300 /tmp/cvprobe 2000 random; timeout 300 /tmp/cvprobe 2000 random shape 8; } | tee $O/${TAG}_conv_loop_probe.log
 }
 for task in "$@"; do
   el "$task"
