@@ -125,6 +125,18 @@ def _to_dev_f32(x, device="cuda"):
     return torch.as_tensor(x, dtype=torch.float, device=device).contiguous()
 
 
+def stack_frames(frames, device, dtype, convert_after_upload=False):
+    """V frames (a list, or one stacked tensor / array) -> one contiguous (V, ...) tensor of `dtype` on `device`.  Each frame is converted
+    on the host before its upload (a float64 depth map crosses PCIe as float32); convert_after_upload=True uploads the frames as they
+    are and converts the stack on the device (a uint8 colour image crosses as a quarter of its float32 bytes)."""
+    first = None if convert_after_upload else dtype
+    if isinstance(frames, (list, tuple)):
+        t = torch.stack([torch.as_tensor(f, device=device, dtype=first) for f in frames])
+    else:
+        t = torch.as_tensor(frames, device=device, dtype=first)
+    return t.to(dtype).contiguous()
+
+
 def erode_depth(depth, radius=2, depth_diff_thres=0.001, ratio_thres=0.8, zfar=100, device="cuda"):
     """Utils.py:387-395: numpy in => numpy out, tensor in => tensor out."""
     out = ops.erode_depth(_to_dev_f32(depth, device), radius, depth_diff_thres, ratio_thres, float(zfar))

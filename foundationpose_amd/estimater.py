@@ -18,7 +18,7 @@ import torch.nn.functional as F
 
 from . import dr, ops
 from .Utils import (bilateral_filter_depth, cluster_poses, compute_mesh_diameter, erode_depth, euler_matrix,
-                    make_mesh_tensors, mesh_handle_from_tensors, sample_views_icosphere, set_seed)
+                    make_mesh_tensors, mesh_handle_from_tensors, sample_views_icosphere, set_seed, stack_frames)
 from .predict_pose_refine import PoseRefinePredictor
 from .predict_score import ScorePredictor
 
@@ -136,8 +136,11 @@ class FoundationPose:
         self.rot_grid = torch.as_tensor(rot_grid, device=self.device, dtype=torch.float)
 
     def generate_random_pose_hypo(self, K, rgb, depth, mask, scene_pts=None):
+        return self.grid_at(self.guess_translation(depth=depth, mask=mask, K=K))
+
+    def grid_at(self, center):
+        """the rotation grid with every hypothesis at the one translation `center` (generate_random_pose_hypo, estimater.py:127-134)"""
         ob_in_cams = self.rot_grid.clone()
-        center = self.guess_translation(depth=depth, mask=mask, K=K)
         ob_in_cams[:, :3, 3] = torch.as_tensor(center, device=self.device, dtype=torch.float).reshape(1, 3)
         return ob_in_cams
 
@@ -145,7 +148,8 @@ class FoundationPose:
     def guess_translation(self, depth, mask, K):
         """Initial translation of every hypothesis (semantics of estimater.py:137-156): the ray through the centre of the
         mask's bounding box, at the median of the valid depths inside the mask; zeros when the mask or the valid set is
-        empty.  Computed on the device: the depth map never leaves HBM (the reference does this in numpy)."""
+        empty.  Computed on the device: the depth map never leaves HBM (the reference does this in numpy).  The centre itself is
+        translation_from_stats', from the six numbers found here."""
         d = torch.as_tensor(depth, device=self.device, dtype=torch.float)
         m = torch.as_tensor(np.asarray(mask) if not torch.is_tensor(mask) else mask, device=self.device) > 0
         rows, cols = torch.nonzero(m.any(dim=1)).reshape(-1), torch.nonzero(m.any(dim=0)).reshape(-1)
@@ -160,11 +164,9 @@ class FoundationPose:
         n = zs.numel()
         stats = torch.stack([rows[0], rows[-1], cols[0], cols[-1]]).to(torch.float64)
         mid = torch.stack([zs[(n - 1) // 2], zs[n // 2]])          # numpy's median: mean of the two middle values
-        v0, v1, u0, u1 = stats.tolist()                            # six scalars cross PCIe, not a 640x480 image
+        box = stats.tolist()                                       # six scalars cross PCIe, not a 640x480 image
         lo, hi = mid.tolist()
-        zc = float(np.float32(np.float32(lo) + np.float32(hi)) / np.float32(2.0)) if lo != hi else lo
-        center = (np.linalg.inv(K) @ np.asarray([(u0 + u1) / 2.0, (v0 + v1) / 2.0, 1]).reshape(3, 1)) * zc   # estimater.py:149
-        return center.reshape(3)
+        return translation_from_stats(K, box, n, lo, hi)
 
     # ------------------------------------------------------------------ estimater.py:159-240
     def register(self, K, rgb, depth, ob_mask, ob_id=None, glctx=None, iteration=5):
@@ -177,14 +179,7 @@ class FoundationPose:
         ob_mask = np.asarray(ob_mask.data.cpu().numpy() if torch.is_tensor(ob_mask) else ob_mask)
         mask_t = torch.as_tensor(ob_mask, device=self.device) > 0
         if int(((depth_t >= 0.001) & mask_t).sum()) < 4:
-            logging.info("valid too small, return")
-            pose = np.eye(4)
-            pose[:3, 3] = self.guess_translation(depth=depth_t, mask=mask_t, K=K)
-            return pose
-        self.H, self.W = int(depth_t.shape[0]), int(depth_t.shape[1])
-        self.K = K
-        self.ob_id = ob_id
-        self.ob_mask = ob_mask
+            return _guess_pose(self.guess_translation(depth=depth_t, mask=mask_t, K=K))
         poses = self.generate_random_pose_hypo(K=K, rgb=rgb, depth=depth_t, mask=mask_t, scene_pts=None)
         xyz_map = ops.depth_to_xyz(depth_t, K, zfar=float("inf"), f64_internal=True)  # depth2xyzmap (numpy variant)
         poses, vis = self.refiner.predict(mesh=self.mesh, mesh_tensors=self.mesh_tensors, rgb=rgb, depth=depth_t, K=K,
@@ -194,15 +189,7 @@ class FoundationPose:
         scores, vis = self.scorer.predict(mesh=self.mesh, rgb=rgb, depth=depth_t, K=K, ob_in_cams=poses,
                                           normal_map=None, mesh_tensors=self.mesh_tensors, glctx=self.glctx,
                                           mesh_diameter=self.diameter, get_vis=self.debug >= 2)
-        ids = torch.as_tensor(scores).argsort(descending=True)
-        scores = scores[ids]
-        poses = poses[ids]
-        best_pose = poses[0] @ self.get_tf_to_centered_mesh()
-        self.pose_last = poses[0]
-        self.best_id = ids[0]
-        self.poses = poses
-        self.scores = scores
-        return best_pose.data.cpu().numpy()
+        return _set_registration(self, poses, scores, depth_t.shape, K, ob_id, ob_mask)
 
     def compute_add_err_to_gt_pose(self, poses):
         """stub in the reference as well (estimater.py:243-247); the errors to a known pose are pose_errors' (below)"""
@@ -345,10 +332,10 @@ class FoundationPose:
                 self.depth_agreement = extra["depth_agreement"] = ops.DepthAgreement.rows(self._tracker.agreement)[0]
             return (pose @ self.get_tf_to_centered_mesh()).data.cpu().numpy().reshape(4, 4)
         depth_t = torch.as_tensor(depth, device=self.device, dtype=torch.float).contiguous()
-        depth_t = ops.erode_depth(depth_t, radius=2)
-        depth_t = ops.bilateral_filter_depth(depth_t, radius=2)
-        xyz_map = ops.depth_to_xyz(depth_t, K, zfar=float("inf"), f64_internal=False)  # depth2xyzmap_batch variant
-        pose, vis = self.refiner.predict(mesh=self.mesh, mesh_tensors=self.mesh_tensors, rgb=rgb, depth=depth_t, K=K,
+        xyz_map = ops.ingest_frame(depth_t, K)
+        # depth=None: the refiner reads the xyz map alone (`depth` is the reference's signature), and the filtered depth stays inside
+        # the ingest -- a predict() that began to read it would fail here, not see an unfiltered map
+        pose, vis = self.refiner.predict(mesh=self.mesh, mesh_tensors=self.mesh_tensors, rgb=rgb, depth=None, K=K,
                                          ob_in_cams=self.pose_last.reshape(1, 4, 4), normal_map=None, xyz_map=xyz_map,
                                          mesh_diameter=self.diameter, glctx=self.glctx, iteration=iteration,
                                          get_vis=self.debug >= 2)
@@ -367,38 +354,120 @@ class FoundationPose:
     track = track_one  # the north-star calls it track(); the reference method is track_one
 
 
-def track_objects(estimators, rgb, depth, K, iteration=2, agreement_tol=None):
-    """track_one for several objects in one frame: ONE batched refine loop over the objects' hypotheses (one each, from every
-    estimator's pose_last), replayed as captured hipGraphs (graphs.GraphedTracker over the objects' meshes) on one shared depth
-    ingest, instead of len(estimators) separate calls.  Per object the result is what its own track_one computes (the hypotheses of
-    a call never mix; each one draws its own mesh and uses its own diameter).  Every estimator must be registered and all must share
-    ONE refiner object (its network and configuration are the loop's).  The captured tracker is cached on that refiner under
-    (estimators, frame size, K, iteration), like track_one's.  -> [4x4 np.ndarray] per estimator, in its original mesh frame;
-    updates each pose_last.  register_objects is the batched register().  agreement_tol (metres): also check every tracked pose against
-    the observed depth (GraphedTracker agreement_tol) and set each estimator's depth_agreement (an ops.DepthAgreement; None without)."""
-    tol = None if agreement_tol is None else ops._check_tol(agreement_tol, "track_objects")
+# ---------------------------------------------------------------------- the batched calls: several estimators per call
+# track_objects / track_views / depth_agreement / register_objects / register_views share the argument rules, the cache on the shared
+# refiner and the per-estimator epilogues below; what differs between them is which kernels they launch.
+
+def _check_estimators(name, estimators, scorer=False, registered=False):
+    """The rules every batched call puts on its estimator list, in one order: not empty, ONE refiner object, (scorer=True:) ONE scorer
+    object, every estimator once, (registered=True:) everybody has a pose_last.  Reads `scorer` / `pose_last` only where the flag asks
+    for the rule, and nothing else.  Every caller runs this first and its view, frame and mask rules (_check_views, _check_masks)
+    after it: who is asked before what about, so a call that breaks a rule of each kind is told about its estimators (register_views
+    used to name the view or mask first; within each kind the order is the one it had).
+    -> (list of estimators, the refiner, the scorer or None)"""
     ests = list(estimators)
     if not ests:
-        raise ValueError("track_objects: no estimators")
-    for i, e in enumerate(ests):
-        if e.pose_last is None:
-            raise RuntimeError(f"track_objects: estimator {i} is not registered (call register first)")
-    refiner = ests[0].refiner
+        raise ValueError(f"{name}: no estimators")
+    refiner, shared = ests[0].refiner, None
     if any(e.refiner is not refiner for e in ests):
-        raise ValueError("track_objects: the estimators must share one refiner object (FoundationPose(..., refiner=shared))")
+        raise ValueError(f"{name}: the estimators must share one refiner object (FoundationPose(..., refiner=shared))")
+    if scorer:
+        shared = ests[0].scorer
+        if any(e.scorer is not shared for e in ests):
+            raise ValueError(f"{name}: the estimators must share one scorer object (FoundationPose(..., scorer=shared))")
     if len({id(e) for e in ests}) != len(ests):
-        raise ValueError("track_objects: an estimator is listed twice")
-    dev = ests[0].device
-    hw = tuple(np.asarray(depth).shape[:2]) if not torch.is_tensor(depth) else tuple(depth.shape[:2])
-    key = (tuple((id(e), id(e.mesh_tensors)) for e in ests), hw, np.asarray(K, dtype=np.float64).tobytes(), int(iteration), tol)
-    cached = getattr(refiner, "_objects_tracker", None)
+        raise ValueError(f"{name}: an estimator is listed twice")
+    if registered:
+        for i, e in enumerate(ests):
+            if e.pose_last is None:
+                raise RuntimeError(f"{name}: estimator {i} is not registered (call register first)")
+    return ests, refiner, shared
+
+
+def _frame_hw(f):
+    return tuple(f.shape[:2]) if torch.is_tensor(f) else tuple(np.asarray(f).shape[:2])
+
+
+def _check_views(name, n, views, depths, Ks, rgbs=None):
+    """The rules of a call over several camera frames: one view index per estimator (n of them), one depth frame and one K (and with
+    rgbs one rgb frame) per view, every index inside 0..V-1, all frames of one size.  -> (views, rgbs, depths, Ks) as lists, (H, W)"""
+    views = [int(v) for v in views]
+    if len(views) != n:
+        raise ValueError(f"{name}: {n} estimators but {len(views)} view indices")
+    rgbs, depths, Ks = None if rgbs is None else list(rgbs), list(depths), list(Ks)
+    V = len(depths)
+    if V < 1 or len(Ks) != V or (rgbs is not None and len(rgbs) != V):
+        have = ("" if rgbs is None else f"{len(rgbs)} rgb frames, ") + f"{V} depth frames and {len(Ks)} intrinsics"
+        raise ValueError(f"{name}: {have}: need one of each per view")
+    for i, v in enumerate(views):
+        if not 0 <= v < V:
+            raise ValueError(f"{name}: estimator {i} views frame {v}, outside 0..{V - 1}")
+    hws = {_frame_hw(f) for f in (rgbs or []) + depths}
+    if len(hws) != 1:
+        raise ValueError(f"{name}: the frames differ in size {sorted(hws)}; all views must have one H x W")
+    return views, rgbs, depths, Ks, hws.pop()
+
+
+def _check_masks(name, n, ob_masks, ob_ids):
+    """one mask and (unless ob_ids is None) one object id per estimator -> (masks, ob_ids) as lists"""
+    masks = list(ob_masks)
+    if len(masks) != n:
+        raise ValueError(f"{name}: {n} estimators but {len(masks)} masks")
+    ob_ids = [None] * n if ob_ids is None else list(ob_ids)
+    if len(ob_ids) != n:
+        raise ValueError(f"{name}: {n} estimators but {len(ob_ids)} object ids")
+    return masks, ob_ids
+
+
+def _objects_key(ests):
+    return tuple((id(e), id(e.mesh_tensors)) for e in ests)
+
+
+def _cached(refiner, attr, key, ests, build):
+    """`build()`'s object, cached on the shared refiner as `attr` = (key, object, estimators, mesh dicts) until the key changes.  The
+    keys hold _objects_key's ids; the entry keeps the estimators and their mesh dicts alive, so those ids cannot be reused while it
+    is cached."""
+    cached = getattr(refiner, attr, None)
     if cached is None or cached[0] != key:
+        cached = (key, build(), ests, [e.mesh_tensors for e in ests])
+        setattr(refiner, attr, cached)
+    return cached[1]
+
+
+def _object_tables(refiner, ests):
+    """the MeshSet and diameter table of `ests`' objects, cached on the shared refiner under the estimators and their mesh tensors"""
+    def build():
+        from .Utils import get_mesh_handle
+        return ops.MeshSet([get_mesh_handle(e.mesh_tensors) for e in ests]), ops.object_diameters([e.diameter for e in ests], ests[0].device)
+    return _cached(refiner, "_objects_tables", _objects_key(ests), ests, build)
+
+
+def _set_agreement(ests, trk):
+    """each estimator's depth_agreement from a tracker's table (one copy; one hypothesis per estimator), or None without a check"""
+    rows = [None] * len(ests) if trk.agreement is None else ops.DepthAgreement.rows(trk.agreement)
+    for e, r in zip(ests, rows):
+        e.depth_agreement = r
+
+
+def _track(name, estimators, views, rgb, depth, K, iteration, agreement_tol):
+    """track_objects (views=None: one frame rgb / depth with one K) and track_views (the frames and Ks as lists): the captured
+    tracker over the estimators' meshes, cached on their refiner, stepped from every pose_last"""
+    tol = None if agreement_tol is None else ops._check_tol(agreement_tol, name)
+    ests, refiner, _ = _check_estimators(name, estimators, registered=True)
+    if views is None:
+        hw = _frame_hw(depth)
+        key = (_objects_key(ests), hw, np.asarray(K, dtype=np.float64).tobytes(), int(iteration), tol)
+    else:
+        views, rgb, depth, K, hw = _check_views(name, len(ests), views, depth, K, rgbs=rgb)
+        Kb = b"".join(np.asarray(k, dtype=np.float64).reshape(9).tobytes() for k in K)
+        key = (_objects_key(ests), tuple(views), hw, Kb, int(iteration), tol)
+    dev = ests[0].device
+
+    def capture():
         from .graphs import GraphedTracker
-        trk = GraphedTracker(refiner, [e.mesh_tensors for e in ests], [e.diameter for e in ests], K, hw[0], hw[1], n_hyp=1,
-                             iteration=iteration, device=dev, agreement_tol=tol).capture()
-        # the entry keeps the estimators and their mesh dicts alive, so the ids of its key cannot be reused while it is cached
-        cached = refiner._objects_tracker = (key, trk, ests, [e.mesh_tensors for e in ests])
-    trk = cached[1]
+        return GraphedTracker(refiner, [e.mesh_tensors for e in ests], [e.diameter for e in ests], K, hw[0], hw[1], n_hyp=1,
+                              iteration=iteration, device=dev, views=views, agreement_tol=tol).capture()
+    trk = _cached(refiner, "_objects_tracker" if views is None else "_views_tracker", key, ests, capture)
     start = torch.stack([e.pose_last.reshape(4, 4).to(dev, torch.float32) for e in ests])
     out = trk.step(rgb, depth, start).clone()
     _set_agreement(ests, trk)
@@ -409,15 +478,17 @@ def track_objects(estimators, rgb, depth, K, iteration=2, agreement_tol=None):
     return poses
 
 
-def _set_agreement(ests, trk):
-    """each estimator's depth_agreement from a tracker's table (one copy; one hypothesis per estimator), or None without a check"""
-    rows = [None] * len(ests) if trk.agreement is None else ops.DepthAgreement.rows(trk.agreement)
-    for e, r in zip(ests, rows):
-        e.depth_agreement = r
-
-
-def _frame_hw(f):
-    return tuple(f.shape[:2]) if torch.is_tensor(f) else tuple(np.asarray(f).shape[:2])
+def track_objects(estimators, rgb, depth, K, iteration=2, agreement_tol=None):
+    """track_one for several objects in one frame: ONE batched refine loop over the objects' hypotheses (one each, from every
+    estimator's pose_last), replayed as captured hipGraphs (graphs.GraphedTracker over the objects' meshes) on one shared depth
+    ingest, instead of len(estimators) separate calls.  Per object the result is what its own track_one computes (the hypotheses of
+    a call never mix; each one draws its own mesh and uses its own diameter).  Every estimator must be registered, listed once, and
+    all must share ONE refiner object (its network and configuration are the loop's).  The captured tracker is cached on that refiner
+    under (estimators, frame size, K, iteration, agreement_tol), like track_one's.  -> [4x4 np.ndarray] per estimator, in its original
+    mesh frame; updates each pose_last.  register_objects is the batched register().  agreement_tol (metres): also check every tracked
+    pose against the observed depth (GraphedTracker agreement_tol) and set each estimator's depth_agreement (an ops.DepthAgreement;
+    None without)."""
+    return _track("track_objects", estimators, None, rgb, depth, K, iteration, agreement_tol)
 
 
 def track_views(estimators, views, rgbs, depths, Ks, iteration=2, agreement_tol=None):
@@ -426,101 +497,34 @@ def track_views(estimators, views, rgbs, depths, Ks, iteration=2, agreement_tol=
     (graphs.GraphedTracker with views) on one batched depth ingest of all frames.  Per estimator the result is what its own track_one
     on its frame computes; two estimators may share a mesh (one object seen by two cameras, each pose in its own camera's frame).
     Every estimator must be registered, listed once, and all must share ONE refiner object; the frames must have one size.  The
-    captured tracker is cached on that refiner, like track_objects'.  -> [4x4 np.ndarray] per estimator, in its original mesh
-    frame; updates each pose_last.  agreement_tol (metres): also check every tracked pose against its frame's observed depth and set
-    each estimator's depth_agreement, as track_objects does."""
-    tol = None if agreement_tol is None else ops._check_tol(agreement_tol, "track_views")
-    ests = list(estimators)
-    if not ests:
-        raise ValueError("track_views: no estimators")
-    views = [int(v) for v in views]
-    if len(views) != len(ests):
-        raise ValueError(f"track_views: {len(ests)} estimators but {len(views)} view indices")
-    rgbs, depths, Ks = list(rgbs), list(depths), list(Ks)
-    V = len(depths)
-    if V < 1 or len(rgbs) != V or len(Ks) != V:
-        raise ValueError(f"track_views: {len(rgbs)} rgb frames, {V} depth frames and {len(Ks)} intrinsics: need one of each per view")
-    for i, v in enumerate(views):
-        if not 0 <= v < V:
-            raise ValueError(f"track_views: estimator {i} views frame {v}, outside 0..{V - 1}")
-    hws = {_frame_hw(f) for f in rgbs + depths}
-    if len(hws) != 1:
-        raise ValueError(f"track_views: the frames differ in size {sorted(hws)}; all views must have one H x W")
-    for i, e in enumerate(ests):
-        if e.pose_last is None:
-            raise RuntimeError(f"track_views: estimator {i} is not registered (call register first)")
-    refiner = ests[0].refiner
-    if any(e.refiner is not refiner for e in ests):
-        raise ValueError("track_views: the estimators must share one refiner object (FoundationPose(..., refiner=shared))")
-    if len({id(e) for e in ests}) != len(ests):
-        raise ValueError("track_views: an estimator is listed twice")
-    dev = ests[0].device
-    hw = hws.pop()
-    Kb = b"".join(np.asarray(K, dtype=np.float64).reshape(9).tobytes() for K in Ks)
-    key = (tuple((id(e), id(e.mesh_tensors)) for e in ests), tuple(views), hw, Kb, int(iteration), tol)
-    cached = getattr(refiner, "_views_tracker", None)
-    if cached is None or cached[0] != key:
-        from .graphs import GraphedTracker
-        trk = GraphedTracker(refiner, [e.mesh_tensors for e in ests], [e.diameter for e in ests], Ks, hw[0], hw[1], n_hyp=1,
-                             iteration=iteration, device=dev, views=views, agreement_tol=tol).capture()
-        # the entry keeps the estimators and their mesh dicts alive, so the ids of its key cannot be reused while it is cached
-        cached = refiner._views_tracker = (key, trk, ests, [e.mesh_tensors for e in ests])
-    trk = cached[1]
-    start = torch.stack([e.pose_last.reshape(4, 4).to(dev, torch.float32) for e in ests])
-    out = trk.step(rgbs, depths, start).clone()
-    _set_agreement(ests, trk)
-    poses = []
-    for k, e in enumerate(ests):
-        e.pose_last = out[k:k + 1]
-        poses.append((out[k] @ e.get_tf_to_centered_mesh()).data.cpu().numpy().reshape(4, 4))
-    return poses
+    captured tracker is cached on that refiner, like track_objects' (the two calls share their body, _track).  -> [4x4 np.ndarray] per
+    estimator, in its original mesh frame; updates each pose_last.  agreement_tol (metres): also check every tracked pose against its
+    frame's observed depth and set each estimator's depth_agreement, as track_objects does."""
+    return _track("track_views", estimators, views, rgbs, depths, Ks, iteration, agreement_tol)
 
 
 def depth_agreement(estimators, depths, Ks, views=None, tol=0.01):
     """How well each estimator's current pose_last agrees with the observed depth: estimator k's pose on frame views[k] of depths
     (intrinsics Ks[views[k]]), or with views=None on the one frame `depths` with the one K `Ks` -- the check the trackers run with
     agreement_tol, on a registration or re-registration (register / register_objects / register_views) without changing them.  The
-    depth goes through the tracking ingest (erode, bilateral, back-projection in f32: ops.ingest_frames for several views); the crop
-    windows and crop size are those of the estimators' ONE shared refiner.  tol: absolute, in metres.
-    -> [ops.DepthAgreement] per estimator (one device-to-host copy)."""
+    depth goes through the tracking ingest (erode, bilateral, back-projection in f32: ops.ingest_frame, or ops.ingest_frames for
+    several views); the crop windows and crop size are those of the estimators' ONE shared refiner.  The argument rules are the
+    trackers'.  tol: absolute, in metres.  -> [ops.DepthAgreement] per estimator (one device-to-host copy)."""
     t = ops._check_tol(tol, "depth_agreement")
-    ests = list(estimators)
-    if not ests:
-        raise ValueError("depth_agreement: no estimators")
-    refiner = ests[0].refiner
-    if any(e.refiner is not refiner for e in ests):
-        raise ValueError("depth_agreement: the estimators must share one refiner object (FoundationPose(..., refiner=shared))")
-    if len({id(e) for e in ests}) != len(ests):
-        raise ValueError("depth_agreement: an estimator is listed twice")
-    for i, e in enumerate(ests):
-        if e.pose_last is None:
-            raise RuntimeError(f"depth_agreement: estimator {i} is not registered (call register first)")
+    ests, refiner, _ = _check_estimators("depth_agreement", estimators, registered=True)
+    if views is not None:
+        views, _, depths, Ks, (H, W) = _check_views("depth_agreement", len(ests), views, depths, Ks)
     dev = ests[0].device
-    vt = None
     with torch.inference_mode():
         if views is None:
             d = torch.as_tensor(depths, device=dev, dtype=torch.float).contiguous()
-            d = ops.bilateral_filter_depth(ops.erode_depth(d, radius=2), radius=2)
-            xyz = ops.depth_to_xyz(d, Ks, zfar=float("inf"), f64_internal=False)
+            xyz = ops.ingest_frame(d, Ks)
             H, W = int(d.shape[0]), int(d.shape[1])
-            K = Ks
+            K, vt = Ks, None
         else:
-            views = [int(v) for v in views]
-            depths, Ks = list(depths), list(Ks)
-            V = len(depths)
-            if len(views) != len(ests):
-                raise ValueError(f"depth_agreement: {len(ests)} estimators but {len(views)} view indices")
-            if V < 1 or len(Ks) != V:
-                raise ValueError(f"depth_agreement: {V} depth frames and {len(Ks)} intrinsics: need one of each per view")
-            if any(not 0 <= v < V for v in views):
-                raise ValueError(f"depth_agreement: a view index outside 0..{V - 1}")
-            if len({_frame_hw(f) for f in depths}) != 1:
-                raise ValueError("depth_agreement: the frames differ in size; all views must have one H x W")
-            stack = torch.stack([torch.as_tensor(f, device=dev, dtype=torch.float) for f in depths]).contiguous()
-            vt = ops.Views(Ks, views, dev)
+            stack = stack_frames(depths, dev, torch.float)
+            K, vt = None, ops.Views(Ks, views, dev)
             xyz = ops.ingest_frames(stack, vt, f64_internal=False)
-            H, W = int(stack.shape[1]), int(stack.shape[2])
-            K = None
         mset, diam = _object_tables(refiner, ests)
         obj = torch.arange(len(ests), dtype=torch.int32, device=dev)
         P = torch.stack([e.pose_last.reshape(4, 4).to(dev, torch.float32) for e in ests]).contiguous()
@@ -528,19 +532,44 @@ def depth_agreement(estimators, depths, Ks, views=None, tol=0.01):
     return ops.DepthAgreement.rows(table)
 
 
-def _object_tables(refiner, ests):
-    """the MeshSet and diameter table of `ests`' objects, cached on the shared refiner like track_objects' tracker, under the
-    estimators and their mesh tensors"""
-    key = tuple((id(e), id(e.mesh_tensors)) for e in ests)
-    cached = getattr(refiner, "_objects_tables", None)
-    if cached is None or cached[0] != key:
-        from .Utils import get_mesh_handle
-        dev = ests[0].device
-        mset = ops.MeshSet([get_mesh_handle(e.mesh_tensors) for e in ests])
-        # the entry keeps the estimators and their mesh dicts alive, so the ids of its key cannot be reused while it is cached
-        cached = refiner._objects_tables = (key, mset, ops.object_diameters([e.diameter for e in ests], dev), ests,
-                                            [e.mesh_tensors for e in ests])
-    return cached[1], cached[2]
+def translation_from_stats(K, box, n, lo, hi):
+    """guess_translation's centre (estimater.py:137-156) from the numbers fp_mask_depth_stats returns for one mask (the box
+    [v0, v1, u0, u1], the valid count n, the two middle valid depths lo / hi as float32) -- and from the same numbers as
+    guess_translation finds them with torch: this is the one place the centre is computed.  Zeros for an empty mask or an empty valid
+    set, as there."""
+    if int(box[1]) < 0 or int(n) == 0:
+        return np.zeros((3))
+    v0, v1, u0, u1 = (float(x) for x in box)
+    lo, hi = float(lo), float(hi)
+    zc = float(np.float32(np.float32(lo) + np.float32(hi)) / np.float32(2.0)) if lo != hi else lo
+    center = (np.linalg.inv(K) @ np.asarray([(u0 + u1) / 2.0, (v0 + v1) / 2.0, 1]).reshape(3, 1)) * zc   # estimater.py:149
+    return center.reshape(3)
+
+
+def _guess_pose(center, who=""):
+    """register()'s answer for a mask with fewer than 4 valid depths (estimater.py:174-178): no rotation, the guessed translation;
+    the estimator keeps its state"""
+    logging.info(f"{who}valid too small, return")
+    pose = np.eye(4)
+    pose[:3, 3] = center
+    return pose
+
+
+def _set_registration(e, poses, scores, hw, K, ob_id, ob_mask):
+    """The end of a registration of estimator `e` (estimater.py:224-240): its refined hypotheses ranked by score, and the state
+    register() leaves (H, W, K, ob_id, ob_mask, scores, poses, pose_last, best_id), all set here: a registration whose refine or
+    scoring raises leaves the estimator as it was, the frame's K and mask included.  -> the best pose, 4x4 np.ndarray in the original
+    mesh frame"""
+    ids = torch.as_tensor(scores).argsort(descending=True)
+    e.H, e.W = int(hw[0]), int(hw[1])
+    e.K = K
+    e.ob_id = ob_id
+    e.ob_mask = ob_mask
+    e.scores = scores[ids]
+    e.poses = poses[ids]
+    e.pose_last = e.poses[0]
+    e.best_id = ids[0]
+    return (e.poses[0] @ e.get_tf_to_centered_mesh()).data.cpu().numpy()
 
 
 def register_objects(estimators, K, rgb, depth, ob_masks, ob_ids=None, iteration=5):
@@ -549,24 +578,10 @@ def register_objects(estimators, K, rgb, depth, ob_masks, ob_ids=None, iteration
     attention stays inside each object) instead of len(estimators) register() calls.  ob_masks[k] is estimator k's object mask,
     ob_ids[k] its id.  Per object the result, and the state set on the estimator (H, W, K, ob_id, ob_mask, pose_last, best_id,
     poses, scores), is what its own register() computes; an object whose mask holds fewer than 4 valid depths gets register()'s
-    guess-translation pose and keeps its state, as there.  All estimators must share ONE refiner and ONE scorer object.
-    -> [4x4 np.ndarray] per estimator, in its original mesh frame."""
-    ests = list(estimators)
-    if not ests:
-        raise ValueError("register_objects: no estimators")
-    masks = list(ob_masks)
-    if len(masks) != len(ests):
-        raise ValueError(f"register_objects: {len(ests)} estimators but {len(masks)} masks")
-    ob_ids = [None] * len(ests) if ob_ids is None else list(ob_ids)
-    if len(ob_ids) != len(ests):
-        raise ValueError(f"register_objects: {len(ests)} estimators but {len(ob_ids)} object ids")
-    refiner, scorer = ests[0].refiner, ests[0].scorer
-    if any(e.refiner is not refiner for e in ests):
-        raise ValueError("register_objects: the estimators must share one refiner object (FoundationPose(..., refiner=shared))")
-    if any(e.scorer is not scorer for e in ests):
-        raise ValueError("register_objects: the estimators must share one scorer object (FoundationPose(..., scorer=shared))")
-    if len({id(e) for e in ests}) != len(ests):
-        raise ValueError("register_objects: an estimator is listed twice")
+    guess-translation pose and keeps its state, as there.  Every estimator is listed once and all must share ONE refiner and ONE
+    scorer object.  -> [4x4 np.ndarray] per estimator, in its original mesh frame."""
+    ests, refiner, scorer = _check_estimators("register_objects", estimators, scorer=True)
+    masks, ob_ids = _check_masks("register_objects", len(ests), ob_masks, ob_ids)
     set_seed(0)
     dev = ests[0].device
     for e in ests:
@@ -582,10 +597,7 @@ def register_objects(estimators, K, rgb, depth, ob_masks, ob_ids=None, iteration
         masks_np.append(m)
         mask_t = torch.as_tensor(m, device=dev) > 0
         if int(((depth_t >= 0.001) & mask_t).sum()) < 4:
-            logging.info(f"object {k}: valid too small, return")
-            pose = np.eye(4)
-            pose[:3, 3] = e.guess_translation(depth=depth_t, mask=mask_t, K=K)
-            out[k] = pose
+            out[k] = _guess_pose(e.guess_translation(depth=depth_t, mask=mask_t, K=K), f"object {k}: ")
             lengths.append(0)
             continue
         P = e.generate_random_pose_hypo(K=K, rgb=rgb, depth=depth_t, mask=mask_t, scene_pts=None)
@@ -606,32 +618,9 @@ def register_objects(estimators, K, rgb, depth, ob_masks, ob_ids=None, iteration
         scores = scorer.predict_objects(rgb, depth_t, K, poses, mset, diam, seg)
     for k, e in enumerate(ests):
         a, b = seg.rows(k)
-        if b == a:
-            continue
-        ids = scores[a:b].argsort(descending=True)
-        e.H, e.W = int(depth_t.shape[0]), int(depth_t.shape[1])
-        e.K = K
-        e.ob_id = ob_ids[k]
-        e.ob_mask = masks_np[k]
-        e.scores = scores[a:b][ids]
-        e.poses = poses[a:b][ids]
-        e.pose_last = e.poses[0]
-        e.best_id = ids[0]
-        out[k] = (e.poses[0] @ e.get_tf_to_centered_mesh()).data.cpu().numpy()
+        if b > a:
+            out[k] = _set_registration(e, poses[a:b], scores[a:b], depth_t.shape, K, ob_ids[k], masks_np[k])
     return out
-
-
-def translation_from_stats(K, box, n, lo, hi):
-    """guess_translation's centre (estimater.py:137-156) from the numbers fp_mask_depth_stats returns for one mask (the box
-    [v0, v1, u0, u1], the valid count n, the two middle valid depths lo / hi as float32), with guess_translation's own expression:
-    the same bits.  Zeros for an empty mask or an empty valid set, as there."""
-    if int(box[1]) < 0 or int(n) == 0:
-        return np.zeros((3))
-    v0, v1, u0, u1 = (float(x) for x in box)
-    lo, hi = float(lo), float(hi)
-    zc = float(np.float32(np.float32(lo) + np.float32(hi)) / np.float32(2.0)) if lo != hi else lo
-    center = (np.linalg.inv(K) @ np.asarray([(u0 + u1) / 2.0, (v0 + v1) / 2.0, 1]).reshape(3, 1)) * zc   # estimater.py:149
-    return center.reshape(3)
 
 
 def register_views(estimators, views, rgbs, depths, Ks, ob_masks, ob_ids=None, iteration=5):
@@ -642,50 +631,23 @@ def register_views(estimators, views, rgbs, depths, Ks, ob_masks, ob_ids=None, i
     (predict_objects with views).  Per estimator the result, and the state set on it (H, W, K = Ks[views[k]], ob_id, ob_mask,
     pose_last, best_id, poses, scores), is what its own register() on its frame computes; an estimator whose mask holds fewer than 4
     valid depths gets register()'s guess-translation pose and keeps its state.  The argument rules are track_views': every estimator
-    listed once, all sharing ONE refiner and ONE scorer, the frames of one size; two estimators may share a mesh (one object seen by
-    two cameras).  -> [4x4 np.ndarray] per estimator, each in its own camera's frame and the original mesh frame.  track_views is the
-    batched track_one that follows."""
-    ests = list(estimators)
-    if not ests:
-        raise ValueError("register_views: no estimators")
-    views = [int(v) for v in views]
-    if len(views) != len(ests):
-        raise ValueError(f"register_views: {len(ests)} estimators but {len(views)} view indices")
-    masks = list(ob_masks)
-    if len(masks) != len(ests):
-        raise ValueError(f"register_views: {len(ests)} estimators but {len(masks)} masks")
-    ob_ids = [None] * len(ests) if ob_ids is None else list(ob_ids)
-    if len(ob_ids) != len(ests):
-        raise ValueError(f"register_views: {len(ests)} estimators but {len(ob_ids)} object ids")
-    rgbs, depths, Ks = list(rgbs), list(depths), list(Ks)
-    V = len(depths)
-    if V < 1 or len(rgbs) != V or len(Ks) != V:
-        raise ValueError(f"register_views: {len(rgbs)} rgb frames, {V} depth frames and {len(Ks)} intrinsics: need one of each per view")
-    for i, v in enumerate(views):
-        if not 0 <= v < V:
-            raise ValueError(f"register_views: estimator {i} views frame {v}, outside 0..{V - 1}")
-    hws = {_frame_hw(f) for f in rgbs + depths}
-    if len(hws) != 1:
-        raise ValueError(f"register_views: the frames differ in size {sorted(hws)}; all views must have one H x W")
-    hw = hws.pop()
+    listed once, all sharing ONE refiner and ONE scorer, the frames of one size (and every mask of that size); two estimators may
+    share a mesh (one object seen by two cameras).  -> [4x4 np.ndarray] per estimator, each in its own camera's frame and the original
+    mesh frame.  track_views is the batched track_one that follows."""
+    ests, refiner, scorer = _check_estimators("register_views", estimators, scorer=True)
+    views, rgbs, depths, Ks, hw = _check_views("register_views", len(ests), views, depths, Ks, rgbs=rgbs)
+    masks, ob_ids = _check_masks("register_views", len(ests), ob_masks, ob_ids)
     masks_np = [np.asarray(m.data.cpu().numpy() if torch.is_tensor(m) else m) for m in masks]
     for i, m in enumerate(masks_np):
         if m.shape != hw:
             raise ValueError(f"register_views: mask {i} has shape {m.shape}, the frames are {hw}")
-    refiner, scorer = ests[0].refiner, ests[0].scorer
-    if any(e.refiner is not refiner for e in ests):
-        raise ValueError("register_views: the estimators must share one refiner object (FoundationPose(..., refiner=shared))")
-    if any(e.scorer is not scorer for e in ests):
-        raise ValueError("register_views: the estimators must share one scorer object (FoundationPose(..., scorer=shared))")
-    if len({id(e) for e in ests}) != len(ests):
-        raise ValueError("register_views: an estimator is listed twice")
     set_seed(0)
     dev = ests[0].device
     for e in ests:
         if e.glctx is None:
             e.glctx = dr.RasterizeCudaContext(e.device)
     # register()'s depth ingest, once for all frames
-    depth_t = torch.stack([torch.as_tensor(d, device=dev, dtype=torch.float) for d in depths]).contiguous()
+    depth_t = stack_frames(depths, dev, torch.float)
     depth_t = ops.bilateral_filter_depth_frames(ops.erode_depth_frames(depth_t, radius=2), radius=2)
     # every mask's translation guess and valid-depth count: one launch, one copy back
     mk = torch.as_tensor(np.stack([m > 0 for m in masks_np]).astype(np.uint8), device=dev)
@@ -694,14 +656,10 @@ def register_views(estimators, views, rgbs, depths, Ks, ob_masks, ob_ids=None, i
     for k, e in enumerate(ests):
         center = translation_from_stats(Ks[views[k]], box[k], cnt[k], lo[k], hi[k])
         if cnt[k] < 4:
-            logging.info(f"estimator {k}: valid too small, return")
-            pose = np.eye(4)
-            pose[:3, 3] = center
-            out[k] = pose
+            out[k] = _guess_pose(center, f"estimator {k}: ")
             lengths.append(0)
             continue
-        P = e.rot_grid.clone()                           # generate_random_pose_hypo
-        P[:, :3, 3] = torch.as_tensor(center, device=dev, dtype=torch.float).reshape(1, 3)
+        P = e.grid_at(center)
         hyps.append(P)
         lengths.append(int(P.shape[0]))
     if not hyps:
@@ -713,25 +671,14 @@ def register_views(estimators, views, rgbs, depths, Ks, ob_masks, ob_ids=None, i
     vt = ops.Views(Ks, hyp_view, dev)
     with torch.inference_mode():
         xyz_t = ops.depth_to_xyz_frames(depth_t, vt, zfar=float("inf"), f64_internal=True).contiguous()   # depth2xyzmap (numpy variant)
-        rgb_t = torch.stack([torch.as_tensor(r, device=dev) for r in rgbs]).to(torch.float).contiguous()
-        H, W = hw
-        poses, trans, rot = refiner.refine_device(rgb_t, xyz_t, torch.cat(hyps).contiguous(), None, H, W, mset, diam, iteration,
+        rgb_t = stack_frames(rgbs, dev, torch.float, convert_after_upload=True)
+        poses, trans, rot = refiner.refine_device(rgb_t, xyz_t, torch.cat(hyps).contiguous(), None, hw[0], hw[1], mset, diam, iteration,
                                                   shared_translation=seg, views=vt,
                                                   obj=ObjectIndex(np.repeat(np.arange(len(ests)), lengths), dev, view=hyp_view))
         refiner.last_trans_update, refiner.last_rot_update = trans, rot
         scores = scorer.predict_objects(rgb_t, depth_t, None, poses, mset, diam, seg, views=vt)
     for k, e in enumerate(ests):
         a, b = seg.rows(k)
-        if b == a:
-            continue
-        ids = scores[a:b].argsort(descending=True)
-        e.H, e.W = int(H), int(W)
-        e.K = Ks[views[k]]
-        e.ob_id = ob_ids[k]
-        e.ob_mask = masks_np[k]
-        e.scores = scores[a:b][ids]
-        e.poses = poses[a:b][ids]
-        e.pose_last = e.poses[0]
-        e.best_id = ids[0]
-        out[k] = (e.poses[0] @ e.get_tf_to_centered_mesh()).data.cpu().numpy()
+        if b > a:
+            out[k] = _set_registration(e, poses[a:b], scores[a:b], hw, Ks[views[k]], ob_ids[k], masks_np[k])
     return out

@@ -200,8 +200,7 @@ class GraphedTracker:
     def _pre(self):
         if self.views is not None:
             return ops.ingest_frames(self.depth, self.views, f64_internal=False)
-        d = ops.bilateral_filter_depth(ops.erode_depth(self.depth, radius=2), radius=2)
-        return ops.depth_to_xyz(d, self.K, zfar=float("inf"), f64_internal=False)     # depth2xyzmap_batch variant
+        return ops.ingest_frame(self.depth, self.K)
 
     def _part(self, h, xyz):
         self.refiner.refine_part(h, self.parts[h], self.rgb, xyz, self.poses_in, self.K, self.H, self.W, self.handle,
@@ -346,8 +345,7 @@ class FramePipeline:
             if poses_host is not None:
                 self.poses[slot].copy_(poses_host, non_blocking=True)
             self.rgb[slot].copy_(self.rgb_u8[slot])
-            d = ops.bilateral_filter_depth(ops.erode_depth(self.depth[slot], radius=2), radius=2)
-            self.xyz[slot].copy_(ops.depth_to_xyz(d, t.K, zfar=float("inf"), f64_internal=False))
+            self.xyz[slot].copy_(ops.ingest_frame(self.depth[slot], t.K))
             self.ready[slot].record(self.ingest)
         self.used[slot] = True
 

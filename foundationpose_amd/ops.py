@@ -266,6 +266,13 @@ def depth_to_xyz(depth, K, zfar=float("inf"), f64_internal=False):
     return out
 
 
+def ingest_frame(depth, K, f64_internal=False):
+    """the tracking ingest (erode -> bilateral -> back-projection, estimater.py:255-257) of one (H,W) depth frame in the three
+    one-frame launches -> xyz (H,W,3); ingest_frames is the same for a stack"""
+    d = bilateral_filter_depth(erode_depth(depth, radius=2), radius=2)
+    return depth_to_xyz(d, K, zfar=float("inf"), f64_internal=f64_internal)     # f64_internal=False: the depth2xyzmap_batch variant
+
+
 def _frames(t, what, ndim):
     d = _dev(t, torch.float32, what)
     if d.dim() != ndim:

@@ -4,7 +4,7 @@ import numpy as np
 import torch
 
 from . import ops
-from .Utils import get_mesh_handle, make_mesh_tensors
+from .Utils import get_mesh_handle, make_mesh_tensors, stack_frames
 from .engine import ScorePlan
 from .h5_dataset import ScoreMultiPairH5Dataset
 from .pose_dataset import BatchPoseData
@@ -212,10 +212,8 @@ class ScorePredictor:
                 raise ValueError("predict_objects: views must be an ops.Views")
             if views.dev is not None and len(views) != N:
                 raise ValueError(f"predict_objects: {N} poses but a view index of {len(views)}")
-            rgb_t = torch.stack([torch.as_tensor(r, device=dev) for r in rgb]).to(torch.float).contiguous() \
-                if isinstance(rgb, (list, tuple)) else torch.as_tensor(rgb, device=dev).to(torch.float).contiguous()
-            depth_t = torch.stack([torch.as_tensor(d, device=dev, dtype=torch.float) for d in depth]).contiguous() \
-                if isinstance(depth, (list, tuple)) else torch.as_tensor(depth, device=dev, dtype=torch.float).contiguous()
+            rgb_t = stack_frames(rgb, dev, torch.float, convert_after_upload=True)
+            depth_t = stack_frames(depth, dev, torch.float)
             if rgb_t.dim() != 4 or depth_t.dim() != 3 or rgb_t.shape[0] != views.V or depth_t.shape[0] != views.V:
                 raise ValueError(f"predict_objects: {views.V} views need (V,H,W,3) / (V,H,W) stacks, got {tuple(rgb_t.shape)} / "
                                  f"{tuple(depth_t.shape)}")

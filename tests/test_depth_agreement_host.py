@@ -133,3 +133,45 @@ def test_keywords_refuse_bad_tolerances_before_device_work():
         ops.depth_agreement(torch.zeros(1, 2, 2), torch.zeros(2, 2, 3), torch.zeros(1, 3, 3), 0.01)
     # defaults: no keyword, no check (the estimator starts without a record)
     assert FoundationPose.track_one.__defaults__[-1] is None
+
+
+class _Est:
+    """what depth_agreement reads before it touches a device"""
+
+    def __init__(self, refiner):
+        self.refiner, self.pose_last, self.device = refiner, object(), "cpu"
+
+
+def test_depth_agreement_refusals_without_device():
+    """one broken rule per call; a stub has no mesh, so anything past the checks would raise AttributeError instead"""
+    from foundationpose_amd.estimater import depth_agreement
+    r = object()
+    a, b = _Est(r), _Est(r)
+    depth, K = np.zeros((4, 6), np.float32), np.eye(3)
+    two = dict(depths=[depth, depth], Ks=[K, K])
+    with pytest.raises(ValueError, match="depth_agreement: no estimators"):
+        depth_agreement([], depth, K)
+    with pytest.raises(ValueError, match="depth_agreement: no estimators"):
+        depth_agreement([], views=[], **two)
+    for kw in (dict(depths=depth, Ks=K), dict(views=[0, 1], **two)):
+        with pytest.raises(ValueError, match="depth_agreement: the estimators must share one refiner"):
+            depth_agreement([a, _Est(object())], **kw)
+        with pytest.raises(ValueError, match="depth_agreement: an estimator is listed twice"):
+            depth_agreement([a, a], **kw)
+        unreg = _Est(r)
+        unreg.pose_last = None
+        with pytest.raises(RuntimeError, match="depth_agreement: estimator 1 is not registered"):
+            depth_agreement([a, unreg], **kw)
+        for bad in (-0.001, float("nan"), float("inf"), "x"):
+            with pytest.raises(ValueError, match="tolerance"):
+                depth_agreement([a, b], tol=bad, **kw)
+    with pytest.raises(ValueError, match="depth_agreement: 2 estimators but 1 view indices"):
+        depth_agreement([a, b], views=[0], **two)
+    with pytest.raises(ValueError, match="one of each per view"):
+        depth_agreement([a, b], [depth, depth], [K], views=[0, 1])
+    with pytest.raises(ValueError, match="views frame 2, outside 0..1"):
+        depth_agreement([a, b], views=[0, 2], **two)
+    with pytest.raises(ValueError, match="views frame -1, outside 0..1"):
+        depth_agreement([a, b], views=[-1, 0], **two)
+    with pytest.raises(ValueError, match="one H x W"):
+        depth_agreement([a, b], [depth, np.zeros((5, 6), np.float32)], [K, K], views=[0, 1])

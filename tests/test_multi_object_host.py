@@ -1,7 +1,8 @@
 """CPU: the multi-object entry points (several objects per refine call) -- argument errors of the C ABI, reported without a GPU,
-and the per-object grouping of the two-pose quirk on hand-made object indices."""
+the per-object grouping of the two-pose quirk on hand-made object indices, and track_objects' refusals that need no device."""
 import ctypes as C
 
+import numpy as np
 import pytest
 
 
@@ -109,3 +110,27 @@ def test_parts_keep_quirk_pairs_together():
     assert parts_for_pairs(parts, two_pose_pairs(obj)) == parts
     obj = list(range(32)) * 2                                       # the same interleaved: every pair straddles
     assert parts_for_pairs(parts, two_pose_pairs(obj)) == [(0, 64)]
+
+
+class _Est:
+    """what track_objects reads before it touches a device"""
+
+    def __init__(self, refiner):
+        self.refiner, self.pose_last, self.device = refiner, object(), "cpu"
+
+
+def test_track_objects_refusals_without_device():
+    """one broken rule per call; a stub has no mesh, so anything past the checks would raise AttributeError instead"""
+    from foundationpose_amd.estimater import track_objects
+    r = object()
+    a, b = _Est(r), _Est(r)
+    rgb, depth, K = np.zeros((4, 6, 3), np.uint8), np.zeros((4, 6), np.float32), np.eye(3)
+    with pytest.raises(ValueError, match="track_objects: no estimators"):
+        track_objects([], rgb, depth, K)
+    with pytest.raises(ValueError, match="track_objects: the estimators must share one refiner"):
+        track_objects([a, _Est(object())], rgb, depth, K)
+    with pytest.raises(ValueError, match="track_objects: an estimator is listed twice"):
+        track_objects([a, b, a], rgb, depth, K)
+    b.pose_last = None
+    with pytest.raises(RuntimeError, match="track_objects: estimator 1 is not registered"):
+        track_objects([a, b], rgb, depth, K)
