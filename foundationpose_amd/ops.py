@@ -44,6 +44,14 @@ def _ptr(t):
     return C.c_void_p(0 if t is None else t.data_ptr())
 
 
+def _overlap(a, b):
+    """do the bytes of two contiguous tensors intersect (None: no)"""
+    if not (torch.is_tensor(a) and torch.is_tensor(b)) or a.device != b.device or a.numel() == 0 or b.numel() == 0:
+        return False
+    a0, b0 = a.data_ptr(), b.data_ptr()
+    return a0 < b0 + b.numel() * b.element_size() and b0 < a0 + a.numel() * a.element_size()
+
+
 def _hostK64(K):
     return np.ascontiguousarray(np.asarray(K, dtype=np.float64).reshape(9))
 
@@ -1002,7 +1010,10 @@ def pose_update(trans, rot, poses, rot_rep="axis_angle", normalize_xyz=True, tra
     """fp_pose_update.  trans_rep='deepim' needs K, tf_to_crops (N,3,3) and the crop width (predict_pose_refine.py:201-215);
     any trans_rep other than 'tracknet' / 'deepim' is the reference's plain `else` branch (:217-218): the raw output.  Several
     objects: mesh_diameter = the (M,) table of object_diameters, obj = the per-hypothesis object index (fp_pose_update_multi).  Several
-    views: views = an ops.Views (K unused; fp_pose_update_views)"""
+    views: views = an ops.Views (K unused; fp_pose_update_views).  `out` must not overlap `poses` (the kernel reads poses_in and writes
+    poses_out as __restrict__ rows): an in-place update is refused."""
+    if _overlap(out, poses):
+        raise _lib.FpAmdError("pose_update: out must not overlap poses (poses_in / poses_out are __restrict__; there is no in-place update)")
     tr = _dev(trans, torch.float32, "trans")
     ro = _dev(rot, torch.float32, "rot")
     P = _dev(poses, torch.float32, "poses")

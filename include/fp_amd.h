@@ -311,7 +311,8 @@ int fp_tsdf_emit_triangles(const float* tsdf /*dev*/, const float* weight /*dev*
                            const float* color_weight /*dev*/, int nz, int ny, int nx, const float* origin /*host 3*/, float voxel,
                            float min_weight, const int64_t* offsets /*dev, one per cube*/, long long total, int64_t* keys /*dev 3*total*/,
                            float* pos /*dev 3*total,3*/, float* col /*dev 3*total,3*/, float* nrm /*dev 3*total,3*/, void* stream);
-/* fp_pose_update_multi with K = Ks[view[n]] (read by trans_rep deepim only; Ks is required either way) */
+/* fp_pose_update_multi with K = Ks[view[n]] (read by trans_rep deepim only; Ks is required either way).  A view[n] outside 0..V-1:
+ * all of poses_out row n (16 values) and of the given trans_delta_out / rot_delta_out rows n are NaN, whatever trans_rep. */
 int fp_pose_update_views(const float* trans /*dev N,3*/, const float* rot /*dev N,3|6*/, const float* poses_in /*dev N,16*/,
                          int rot_rep, int normalize_xyz, const float* trans_normalizer /*host 3*/, float rot_normalizer,
                          const double* diameters /*dev M*/, const int32_t* obj /*dev N|NULL*/, int M, int N,
@@ -372,14 +373,18 @@ int fp_warp_crops_multi(const float* rgb /*dev*/, const float* xyz_map /*dev|NUL
 
 /* predict_pose_refine.py:195-234 + Utils.py:848-855 + pytorch3d so3_exp_map / rotation_6d_to_matrix.
  * trans_delta_out / rot_delta_out (optional): the metric translation delta and the applied rotation matrix
- * (so3_exp_map(.)^T), i.e. what the reference keeps in last_trans_update / last_rot_update (:238-239). */
+ * (so3_exp_map(.)^T), i.e. what the reference keeps in last_trans_update / last_rot_update (:238-239).
+ * poses_in and poses_out MUST NOT OVERLAP (this and the _multi / _views forms): the kernel holds both as __restrict__, there is no
+ * in-place update.  Exactly rows 0..N-1 of each given output are written; N == 0 writes nothing. */
 int fp_pose_update(const float* trans /*dev N,3*/, const float* rot /*dev N,3|6*/,
                    const float* poses_in /*dev N,16*/, int rot_rep, int normalize_xyz,
                    const float* trans_normalizer /*host 3*/, float rot_normalizer, float mesh_diameter, int N,
                    float* poses_out /*dev N,16*/, float* trans_delta_out /*dev N,3|NULL*/,
                    float* rot_delta_out /*dev N,9|NULL*/, int trans_rep, const float* K9 /*host 9 f32|NULL (deepim)*/,
                    const float* tf_to_crops /*dev N,9|NULL (deepim)*/, float input_w /*crop width (deepim)*/, void* stream);
-/* fp_pose_update with the diameter of hypothesis n = diameters[obj[n]] */
+/* fp_pose_update with the diameter of hypothesis n = diameters[obj[n]].  An obj[n] outside 0..M-1 reads no diameter: it counts as
+ * NaN, so with normalize_xyz the translation column of poses_out row n and trans_delta_out row n are NaN (the rotation block is what
+ * it is for any diameter); without normalize_xyz the diameter is not used and the row is the scalar form's. */
 int fp_pose_update_multi(const float* trans /*dev N,3*/, const float* rot /*dev N,3|6*/, const float* poses_in /*dev N,16*/,
                          int rot_rep, int normalize_xyz, const float* trans_normalizer /*host 3*/, float rot_normalizer,
                          const double* diameters /*dev M*/, const int32_t* obj /*dev N|NULL*/, int M, int N,
