@@ -17,7 +17,8 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import dr, ops
-from .Utils import (bilateral_filter_depth, cluster_poses, compute_mesh_diameter, erode_depth, euler_matrix,
+from .crops import Scene
+from .Utils import (bilateral_filter_depth, cluster_poses, compute_mesh_diameter, erode_depth, euler_matrix, get_mesh_handle,
                     make_mesh_tensors, mesh_handle_from_tensors, sample_views_icosphere, set_seed, stack_frames)
 from .predict_pose_refine import PoseRefinePredictor
 from .predict_score import ScorePredictor
@@ -239,7 +240,6 @@ class FoundationPose:
         with self.symmetry_tfs.  Out of scope: several cameras (ops.Views) or objects (MeshSet) per call, rendering only a window
         around the two projections (vsd_counts' origin is there for it), BOP's result files and its matching of estimates to ground
         truths."""
-        from .Utils import get_mesh_handle
         if poses is None:
             poses = getattr(self, "poses", None)
             if poses is None:
@@ -343,11 +343,10 @@ class FoundationPose:
             extra["vis"] = vis
         self.pose_last = pose
         if tol is not None:
-            from .Utils import get_mesh_handle
             with torch.inference_mode():
                 H, W = int(depth_t.shape[0]), int(depth_t.shape[1])
-                table = self.refiner.depth_check(pose.reshape(-1, 4, 4).contiguous(), xyz_map, K, H, W, get_mesh_handle(self.mesh_tensors),
-                                                 self.diameter, tol)
+                P = pose.reshape(-1, 4, 4).contiguous()
+                table = self.refiner.depth_check(P, xyz_map, Scene(get_mesh_handle(self.mesh_tensors), self.diameter, K, H, W, P.shape[0]), tol)
             self.depth_agreement = extra["depth_agreement"] = ops.DepthAgreement.rows(table)[0]
         return (pose @ self.get_tf_to_centered_mesh()).data.cpu().numpy().reshape(4, 4)
 
@@ -437,7 +436,6 @@ def _cached(refiner, attr, key, ests, build):
 def _object_tables(refiner, ests):
     """the MeshSet and diameter table of `ests`' objects, cached on the shared refiner under the estimators and their mesh tensors"""
     def build():
-        from .Utils import get_mesh_handle
         return ops.MeshSet([get_mesh_handle(e.mesh_tensors) for e in ests]), ops.object_diameters([e.diameter for e in ests], ests[0].device)
     return _cached(refiner, "_objects_tables", _objects_key(ests), ests, build)
 
@@ -528,7 +526,7 @@ def depth_agreement(estimators, depths, Ks, views=None, tol=0.01):
         mset, diam = _object_tables(refiner, ests)
         obj = torch.arange(len(ests), dtype=torch.int32, device=dev)
         P = torch.stack([e.pose_last.reshape(4, 4).to(dev, torch.float32) for e in ests]).contiguous()
-        table = refiner.depth_check(P, xyz, K, H, W, mset, diam, t, obj=obj, views=vt)
+        table = refiner.depth_check(P, xyz, Scene(mset, diam, K, H, W, len(ests), obj=obj, views=vt, who="depth_agreement"), t)
     return ops.DepthAgreement.rows(table)
 
 

@@ -13,6 +13,7 @@ import numpy as np
 import torch
 
 from . import ops
+from .crops import Scene
 from .Utils import get_mesh_handle
 
 
@@ -146,8 +147,8 @@ class GraphedTracker:
         self.multi = isinstance(mesh_tensors, (list, tuple))
         if views is not None and not self.multi:
             raise ValueError("GraphedTracker: views need a list of meshes (one per object)")
+        from .predict_pose_refine import ObjectIndex, parts_for_pairs
         if self.multi:
-            from .predict_pose_refine import ObjectIndex
             if len(mesh_tensors) < 1 or len(mesh_diameter) != len(mesh_tensors):
                 raise ValueError(f"GraphedTracker: {len(mesh_tensors)} meshes and {len(mesh_diameter)} diameters")
             if views is not None and len(views) != len(mesh_tensors):
@@ -169,13 +170,10 @@ class GraphedTracker:
         else:
             self.K = np.asarray(K, dtype=np.float64).copy()
             self.V = 1
-        if self.multi:
-            self.diameter = ops.object_diameters(mesh_diameter, self.dev)
-            self.obj = ObjectIndex(np.repeat(np.arange(self.M), self.n_hyp), self.dev,
-                                   view=None if self.views is None else self.views.host)
-        else:
-            self.diameter = float(mesh_diameter)
-            self.obj = None
+        self.diameter = ops.object_diameters(mesh_diameter, self.dev) if self.multi else float(mesh_diameter)
+        self.obj = None if not self.multi else ObjectIndex(np.repeat(np.arange(self.M), self.n_hyp), self.dev,
+                                                           view=None if self.views is None else self.views.host)
+        self.scene = Scene(self.handle, self.diameter, self.K, self.H, self.W, self.N, obj=self.obj, views=self.views, who="GraphedTracker")
         fr = () if self.views is None else (self.V,)
         self.rgb = torch.zeros(fr + (H, W, 3), dtype=torch.float32, device=self.dev)
         self.depth = torch.zeros(fr + (H, W), dtype=torch.float32, device=self.dev)
@@ -184,12 +182,8 @@ class GraphedTracker:
         # the tracker: the outputs and one rasteriser scratch per part here, the encoder's activation sets by
         # (batch, H, W, slot) in the plan (never dropped)
         oh, ow = int(refiner.cfg["input_resize"][0]), int(refiner.cfg["input_resize"][1])
-        self.parts = refiner.sub.parts(self.N, self.dev)
-        if self.obj is not None:
-            from .predict_pose_refine import parts_for_pairs
-            self.parts = parts_for_pairs(self.parts, self.obj.pairs)
-        self.workspace = [torch.empty(max(16, ops.workspace_bytes(b - a, self.handle.V, self.handle.T, oh, ow)),
-                                      dtype=torch.uint8, device=self.dev) for a, b in self.parts]
+        self.parts = parts_for_pairs(refiner.sub.parts(self.N, self.dev), self.scene.pair_list)
+        self.workspace = [self.scene.workspace(b - a, oh, ow, self.dev) for a, b in self.parts]
         self.outs = refiner.alloc_outputs(self.N, self.dev) + (self.R,)
         self.poses_out = self.outs[0]
         self.agreement = None if self.agreement_tol is None else torch.zeros((self.N, 4), dtype=torch.int32, device=self.dev)
@@ -203,15 +197,12 @@ class GraphedTracker:
         return ops.ingest_frame(self.depth, self.K)
 
     def _part(self, h, xyz):
-        self.refiner.refine_part(h, self.parts[h], self.rgb, xyz, self.poses_in, self.K, self.H, self.W, self.handle,
-                                 self.diameter, range(self.R), self.outs, self.workspace[h], obj=self.obj, views=self.views)
+        self.refiner.refine_part(h, self.parts[h], self.rgb, xyz, self.poses_in, self.scene, range(self.R), self.outs, self.workspace[h])
         if self.agreement_tol is not None:
             a, b = self.parts[h]
             P = self.poses_out if self.R > 0 else self.poses_in       # no iteration: the output is the input (copied after the join)
-            self.refiner.depth_check(P[a:b], xyz, self.K, self.H, self.W, self.handle, self.diameter, self.agreement_tol,
-                                     out=self.agreement[a:b], workspace=self.workspace[h],
-                                     obj=None if self.obj is None else self.obj.dev[a:b],
-                                     views=None if self.views is None else self.views.rows(a, b))
+            self.refiner.depth_check(P[a:b], xyz, self.scene.rows(a, b), self.agreement_tol, out=self.agreement[a:b],
+                                     workspace=self.workspace[h])
 
     def _body(self, xyz=None):
         """the frame without graphs: same launches, same streams (xyz given: the refine loop alone, on that map)"""

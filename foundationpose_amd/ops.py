@@ -211,24 +211,19 @@ class Views:
     def pair_rows(self, a, b):
         return None if self._rows is None else self._rows.pair_rows(a, b)
 
+    def _cut(self, host, dev):
+        v = object.__new__(Views)
+        v.__dict__.update(self.__dict__, host=host, dev=dev, _rows=None)
+        return v
+
     def rows(self, a, b):
         """the table for hypotheses a..b of the call (shares the K tables; the index is a slice: nothing is copied)"""
-        v = object.__new__(Views)
-        v.__dict__.update(self.__dict__)
-        v.host = None if self.host is None else self.host[a:b]
-        v.dev = None if self.dev is None else self.dev[a:b]
-        v._rows = None
-        return v
+        return self._cut(None, None) if self.host is None else self._cut(self.host[a:b], self.dev[a:b])
 
     def take(self, idx):
         """the table for the hypotheses idx (host indices into this table's rows; shares the K tables, uploads the gathered index)"""
-        v = object.__new__(Views)
-        v.__dict__.update(self.__dict__)
-        if self.host is not None:
-            v.host = self.host[np.asarray(idx, dtype=np.int64)]
-            v.dev = torch.as_tensor(v.host.astype(np.int32), device=self.device)
-        v._rows = None
-        return v
+        host = None if self.host is None else self.host[np.asarray(idx, dtype=np.int64)]
+        return self._cut(host, None if host is None else torch.as_tensor(host.astype(np.int32), device=self.device))
 
 
 def _views(views, what, N=None):
@@ -630,6 +625,39 @@ def _tf_table(t, name, what="pose_errors"):
     return a
 
 
+def _pose_tables(what, model_pts, poses, gt, gt_index, symmetry_tfs):
+    """the shape refusals pose_errors and mspd share, in their one order (they need no device): model_pts (P,3), poses (N,4,4), the
+    gt_index length, the gt table against N, the symmetry table -> (N, P, gt (G,4,4), G, symmetries (S,4,4) or None, S)"""
+    for name, t in (("model_pts", model_pts), ("poses", poses)):
+        if not torch.is_tensor(t):
+            raise _lib.FpAmdError(f"{what}: {name} must be a tensor, got {type(t).__name__}")
+    if model_pts.dim() != 2 or int(model_pts.shape[1]) != 3 or int(model_pts.shape[0]) < 1:
+        raise _lib.FpAmdError(f"{what}: model_pts must be (P,3) with P >= 1, got {tuple(model_pts.shape)}")
+    if poses.dim() != 3 or tuple(poses.shape[1:]) != (4, 4):
+        raise _lib.FpAmdError(f"{what}: poses must be (N,4,4), got {tuple(poses.shape)}")
+    N, P = int(poses.shape[0]), int(model_pts.shape[0])
+    if gt_index is not None and (not torch.is_tensor(gt_index) or int(gt_index.numel()) != N):
+        raise _lib.FpAmdError(f"{what}: {N} poses need a gt_index tensor of {N} entries")
+    g = _tf_table(gt, "gt", what)
+    G = int(g.shape[0])
+    if G < 1 or (gt_index is None and G not in (1, N)):
+        raise _lib.FpAmdError(f"{what}: {G} ground truths for {N} poses need a gt_index")
+    sym = None if symmetry_tfs is None else _tf_table(symmetry_tfs, "symmetry_tfs", what)
+    return N, P, g, G, sym, 0 if sym is None else int(sym.shape[0])
+
+
+def _pose_operands(what, model_pts, poses, gt_index, out, out_shape):
+    """the device / dtype / layout refusals that follow them -> (model_pts, poses, gt_index, out) as the kernels take them"""
+    pts = _dev(model_pts, torch.float32, "model_pts")
+    ps = _dev(poses, torch.float32, "poses")
+    gi = _dev(gt_index, torch.int32, "gt_index")
+    if out is not None:
+        out = _dev(out, torch.float64, "out")
+        if tuple(out.shape) != out_shape:
+            raise _lib.FpAmdError(f"{what}: out must be {out_shape}, got {tuple(out.shape)}")
+    return pts, ps, gi, out
+
+
 def pose_errors_workspace(N, P, S, device):
     """the workspace of pose_errors for N poses, P model points and S symmetries (a captured graph owns its buffers)"""
     nbytes = int(_lib.lib().fp_pose_errors_workspace_bytes(int(N), int(P), int(S)))
@@ -653,31 +681,10 @@ def pose_errors(model_pts, poses, gt, gt_index=None, symmetry_tfs=None, want=("a
     if not flags:
         raise ValueError("pose_errors: want is empty")
     # shapes first (they need no device), then device / dtype / layout, then the buffers: all before any device work
-    for name, t in (("model_pts", model_pts), ("poses", poses)):
-        if not torch.is_tensor(t):
-            raise _lib.FpAmdError(f"pose_errors: {name} must be a tensor, got {type(t).__name__}")
-    if model_pts.dim() != 2 or int(model_pts.shape[1]) != 3 or int(model_pts.shape[0]) < 1:
-        raise _lib.FpAmdError(f"pose_errors: model_pts must be (P,3) with P >= 1, got {tuple(model_pts.shape)}")
-    if poses.dim() != 3 or tuple(poses.shape[1:]) != (4, 4):
-        raise _lib.FpAmdError(f"pose_errors: poses must be (N,4,4), got {tuple(poses.shape)}")
-    N, P = int(poses.shape[0]), int(model_pts.shape[0])
-    if gt_index is not None and (not torch.is_tensor(gt_index) or int(gt_index.numel()) != N):
-        raise _lib.FpAmdError(f"pose_errors: {N} poses need a gt_index tensor of {N} entries")
-    g = _tf_table(gt, "gt")
-    G = int(g.shape[0])
-    if G < 1 or (gt_index is None and G not in (1, N)):
-        raise _lib.FpAmdError(f"pose_errors: {G} ground truths for {N} poses need a gt_index")
-    sym = None if symmetry_tfs is None else _tf_table(symmetry_tfs, "symmetry_tfs")
-    S = 0 if sym is None else int(sym.shape[0])
+    N, P, g, G, sym, S = _pose_tables("pose_errors", model_pts, poses, gt, gt_index, symmetry_tfs)
     if flags & 4 and S == 0:
         raise _lib.FpAmdError('pose_errors: want "sym" needs symmetry_tfs with at least one transform')
-    pts = _dev(model_pts, torch.float32, "model_pts")
-    ps = _dev(poses, torch.float32, "poses")
-    gi = _dev(gt_index, torch.int32, "gt_index")
-    if out is not None:
-        out = _dev(out, torch.float64, "out")
-        if tuple(out.shape) != (N, 4):
-            raise _lib.FpAmdError(f"pose_errors: out must be ({N}, 4), got {tuple(out.shape)}")
+    pts, ps, gi, out = _pose_operands("pose_errors", model_pts, poses, gt_index, out, (N, 4))
     need = int(_lib.lib().fp_pose_errors_workspace_bytes(N, P, S))
     if workspace is not None:
         if not (torch.is_tensor(workspace) and workspace.is_cuda and workspace.is_contiguous()):
@@ -844,31 +851,9 @@ def mspd(model_pts, poses, gt, K, gt_index=None, symmetry_tfs=None, out=None):
     minimum over symmetry_tfs (S,4,4; None: the identity alone) of the largest distance between a point's two projections.  gt,
     gt_index and symmetry_tfs as in pose_errors; a row is NaN for a gt_index out of range, a transform that is not finite or a
     point at or behind the camera plane.  One camera and one object per call.  Refusals in pose_errors' order."""
-    what = "mspd"
-    for name, t in (("model_pts", model_pts), ("poses", poses)):
-        if not torch.is_tensor(t):
-            raise _lib.FpAmdError(f"{what}: {name} must be a tensor, got {type(t).__name__}")
-    if model_pts.dim() != 2 or int(model_pts.shape[1]) != 3 or int(model_pts.shape[0]) < 1:
-        raise _lib.FpAmdError(f"{what}: model_pts must be (P,3) with P >= 1, got {tuple(model_pts.shape)}")
-    if poses.dim() != 3 or tuple(poses.shape[1:]) != (4, 4):
-        raise _lib.FpAmdError(f"{what}: poses must be (N,4,4), got {tuple(poses.shape)}")
-    N, P = int(poses.shape[0]), int(model_pts.shape[0])
-    if gt_index is not None and (not torch.is_tensor(gt_index) or int(gt_index.numel()) != N):
-        raise _lib.FpAmdError(f"{what}: {N} poses need a gt_index tensor of {N} entries")
-    g = _tf_table(gt, "gt", what)
-    G = int(g.shape[0])
-    if G < 1 or (gt_index is None and G not in (1, N)):
-        raise _lib.FpAmdError(f"{what}: {G} ground truths for {N} poses need a gt_index")
-    sym = None if symmetry_tfs is None else _tf_table(symmetry_tfs, "symmetry_tfs", what)
-    S = 0 if sym is None else int(sym.shape[0])
-    K9 = np.ascontiguousarray(_hostK33(K, what).reshape(9).astype(np.float32))
-    pts = _dev(model_pts, torch.float32, "model_pts")
-    ps = _dev(poses, torch.float32, "poses")
-    gi = _dev(gt_index, torch.int32, "gt_index")
-    if out is not None:
-        out = _dev(out, torch.float64, "out")
-        if tuple(out.shape) != (N,):
-            raise _lib.FpAmdError(f"{what}: out must be ({N},), got {tuple(out.shape)}")
+    N, P, g, G, sym, S = _pose_tables("mspd", model_pts, poses, gt, gt_index, symmetry_tfs)
+    K9 = np.ascontiguousarray(_hostK33(K, "mspd").reshape(9).astype(np.float32))
+    pts, ps, gi, out = _pose_operands("mspd", model_pts, poses, gt_index, out, (N,))
     g = g.to(device=ps.device, dtype=torch.float64).contiguous()
     sym = None if S == 0 else sym.to(device=ps.device, dtype=torch.float64).contiguous()
     if out is None:
@@ -1119,6 +1104,19 @@ def pack_conv3x3_tiles(w, N, Cin):
     return out
 
 
+def _igemm_epilogue(bias, residual, r_geom, bn_scale, bn_shift, pe, y_pe, flags, w_tiles=None):
+    """the fp_igemm_epilogue of igemm_f16 / igemm_f16_splitk: dtype and layout checks of its tensors, `flags` as the caller built them"""
+    pe = _dev(pe, torch.float32, "pe")
+    ep = IgemmEpilogue()
+    ep.bias, ep.bn_scale = _ptr(_dev(bias, torch.float32, "bias")), _ptr(_dev(bn_scale, torch.float32, "bn_scale"))
+    ep.bn_shift, ep.residual = _ptr(_dev(bn_shift, torch.float32, "bn_shift")), _ptr(_dev(residual, torch.float16, "residual"))
+    ep.r_geom = C.pointer(r_geom) if r_geom is not None else None
+    ep.flags = flags
+    ep.pe, ep.pe_period, ep.y_pe = _ptr(pe), (int(pe.shape[-2]) if pe is not None else 0), _ptr(_dev(y_pe, torch.float16, "y_pe"))
+    ep.w_tiles = _ptr(_dev(w_tiles, torch.float16, "w_tiles"))
+    return ep
+
+
 def igemm_f16(x, x_geom, w, bias, y, y_geom, M, N, Cin, taps, relu=False, residual=None, r_geom=None, bn_scale=None,
               bn_shift=None, conv_rounding=False, pe=None, y_pe=None, w_tiles=None, mfma16=None):
     """y = act(f16(epilogue(implicit_gemm(x, w))) (+ residual)) -- see fp_igemm_f16_fwd.  mfma16: the MFMA shape of the shifted-window
@@ -1127,20 +1125,12 @@ def igemm_f16(x, x_geom, w, bias, y, y_geom, M, N, Cin, taps, relu=False, residu
     otherwise nn.Linear (one rounding of accumulator + bias).  pe (S, N) f32 + y_pe (M, N) fp16: second output
     f16(f32(y) + pe[m % S]).  All tensors are device buffers owned by the caller (y is written in place and returned)."""
     x = _dev(x, torch.float16, "x"); w = _dev(w, torch.float16, "w"); y = _dev(y, torch.float16, "y")
-    b = _dev(bias, torch.float32, "bias"); r = _dev(residual, torch.float16, "residual")
-    sc = _dev(bn_scale, torch.float32, "bn_scale"); sh = _dev(bn_shift, torch.float32, "bn_shift")
-    pe = _dev(pe, torch.float32, "pe"); y_pe = _dev(y_pe, torch.float16, "y_pe")
-    ep = IgemmEpilogue()
-    ep.bias, ep.bn_scale, ep.bn_shift = _ptr(b), _ptr(sc), _ptr(sh)
-    ep.residual = _ptr(r)
-    ep.r_geom = C.pointer(r_geom) if r_geom is not None else None
     if mfma16 is None:
         from . import engine               # engine imports this module
         mfma16 = engine.CONV_MFMA_16X16X32
-    ep.flags = (IGEMM_RELU if relu else 0) | (IGEMM_ROUND_ACC if conv_rounding else 0) | IGEMM_HAS_W_TILES | \
-        (IGEMM_MFMA_16X16X32 if mfma16 else IGEMM_MFMA_32X32X16)
-    ep.pe, ep.pe_period, ep.y_pe = _ptr(pe), (int(pe.shape[-2]) if pe is not None else 0), _ptr(y_pe)
-    ep.w_tiles = _ptr(_dev(w_tiles, torch.float16, "w_tiles"))
+    ep = _igemm_epilogue(bias, residual, r_geom, bn_scale, bn_shift, pe, y_pe,
+                         (IGEMM_RELU if relu else 0) | (IGEMM_ROUND_ACC if conv_rounding else 0) | IGEMM_HAS_W_TILES |
+                         (IGEMM_MFMA_16X16X32 if mfma16 else IGEMM_MFMA_32X32X16), w_tiles)
     st = _lib.lib().fp_igemm_f16_fwd(_ptr(x), C.byref(x_geom), _ptr(w), _ptr(y), C.byref(y_geom), int(M), int(N), int(Cin),
                                      int(taps), C.byref(ep), _stream(x))
     _lib.check(st, "fp_igemm_f16_fwd")
@@ -1157,16 +1147,8 @@ def igemm_f16_splitk(x, x_geom, w, bias, y, y_geom, M, N, Cin, taps, splits, wor
     pieces, partial sums through the caller-owned `workspace` (uint8, >= igemm_splitk_workspace_bytes), see
     fp_igemm_f16_splitk_fwd.  Equal to igemm_f16 up to fp32 summation order."""
     x = _dev(x, torch.float16, "x"); w = _dev(w, torch.float16, "w"); y = _dev(y, torch.float16, "y")
-    b = _dev(bias, torch.float32, "bias"); r = _dev(residual, torch.float16, "residual")
-    sc = _dev(bn_scale, torch.float32, "bn_scale"); sh = _dev(bn_shift, torch.float32, "bn_shift")
-    pe = _dev(pe, torch.float32, "pe"); y_pe = _dev(y_pe, torch.float16, "y_pe")
     ws = _dev(workspace, torch.uint8, "workspace")
-    ep = IgemmEpilogue()
-    ep.bias, ep.bn_scale, ep.bn_shift = _ptr(b), _ptr(sc), _ptr(sh)
-    ep.residual = _ptr(r)
-    ep.r_geom = C.pointer(r_geom) if r_geom is not None else None
-    ep.flags = (IGEMM_RELU if relu else 0) | (IGEMM_ROUND_ACC if conv_rounding else 0)
-    ep.pe, ep.pe_period, ep.y_pe = _ptr(pe), (int(pe.shape[-2]) if pe is not None else 0), _ptr(y_pe)
+    ep = _igemm_epilogue(bias, residual, r_geom, bn_scale, bn_shift, pe, y_pe, (IGEMM_RELU if relu else 0) | (IGEMM_ROUND_ACC if conv_rounding else 0))
     st = _lib.lib().fp_igemm_f16_splitk_fwd(_ptr(x), C.byref(x_geom), _ptr(w), _ptr(y), C.byref(y_geom), int(M), int(N), int(Cin),
                                             int(taps), C.byref(ep), int(splits), _ptr(ws), ws.numel(), _stream(x))
     _lib.check(st, "fp_igemm_f16_splitk_fwd")
@@ -1296,17 +1278,7 @@ def linear_layernorm_res(x16, w_packed, bias, gamma, beta, eps=1e-5, x32=None, t
     if K != 512:
         raise _lib.FpAmdError(f"linear_layernorm_res: x16 (..., {K}), must be (..., 512)")
     M = x16.numel() // K
-    if x16.is_contiguous():
-        x, ldx = x16, K
-    else:
-        # a column block of a contiguous (..., ldx) tensor: unit stride in the last dimension, every leading stride that of the wide tensor
-        ldx = int(x16.stride(-2)) if x16.dim() >= 2 else K
-        ok = x16.stride(-1) == 1 and ldx % 8 == 0 and ldx >= K and x16.storage_offset() % 8 == 0
-        for d in range(x16.dim() - 2, 0, -1):
-            ok = ok and x16.stride(d - 1) == x16.stride(d) * x16.shape[d]
-        if not ok:
-            raise _lib.FpAmdError("linear_layernorm_res: x16 must be contiguous or a column block of a contiguous tensor")
-        x = x16
+    x, ldx = x16, _column_block(x16, "linear_layernorm_res: x16", sep="")
     x32 = _dev(x32, torch.float32, "x32"); tok16 = _dev(tok16, torch.float16, "tok16"); pe = _dev(pe, torch.float32, "pe")
     S = int(pe.shape[-2]) if pe is not None else 0
     shape = tuple(x.shape[:-1]) + (D,)
@@ -1341,10 +1313,11 @@ def ffn_layernorm_mean(y16, w1_packed, b1, w2_packed, b2, x32, gamma, beta, eps=
     return out
 
 
-def _column_block(x16, name):
-    """-> row stride (fp16 values) of an (..., 512) fp16 tensor that is contiguous or a column block of a contiguous wider tensor"""
+def _column_block(x16, name, sep=":"):
+    """-> row stride (fp16 values) of an (..., 512) fp16 tensor that is contiguous or a column block of a contiguous wider tensor (unit
+    stride in the last dimension, every leading stride that of the wide tensor)"""
     if not (torch.is_tensor(x16) and x16.is_cuda and x16.dtype == torch.float16 and int(x16.shape[-1]) == 512):
-        raise _lib.FpAmdError(f"{name}: must be a CUDA float16 tensor (..., 512)")
+        raise _lib.FpAmdError(f"{name}{sep} must be a CUDA float16 tensor (..., 512)")
     if x16.is_contiguous():
         return 512
     ldx = int(x16.stride(-2)) if x16.dim() >= 2 else 512
@@ -1352,7 +1325,7 @@ def _column_block(x16, name):
     for d in range(x16.dim() - 2, 0, -1):
         ok = ok and x16.stride(d - 1) == x16.stride(d) * x16.shape[d]
     if not ok:
-        raise _lib.FpAmdError(f"{name}: must be contiguous or a column block of a contiguous tensor")
+        raise _lib.FpAmdError(f"{name}{sep} must be contiguous or a column block of a contiguous tensor")
     return ldx
 
 

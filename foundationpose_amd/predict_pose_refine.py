@@ -11,6 +11,7 @@ import numpy as np
 import torch
 
 from . import ops
+from .crops import Scene, crop_stage
 from .Utils import get_mesh_handle, make_mesh_tensors
 from .engine import RefinePlan
 from .h5_dataset import PoseRefinePairH5Dataset
@@ -57,20 +58,12 @@ def make_crop_data_batch(render_size, ob_in_cams, mesh, rgb, depth, K, crop_rati
     poseA = torch.as_tensor(ob_in_cams, dtype=torch.float, device=handle.device).reshape(-1, 4, 4).contiguous()
     N = poseA.shape[0]
     oh, ow = int(cfg["input_resize"][0]), int(cfg["input_resize"][1])
-    tf_to_crops, bbox2d = ops.crop_windows(poseA, K, mesh_diameter, crop_ratio, (render_size[1], render_size[0]))
-    if N == 2:
-        # reference broadcasting quirk: with exactly two poses transform_pts pairs pose i with
-        # corner i, so both hypotheses are rendered with [umin_0, vmin_0, umax_1, vmax_1]
-        bbox2d = torch.stack([bbox2d[0, 0], bbox2d[0, 1], bbox2d[1, 2], bbox2d[1, 3]])[None].expand(2, 4).contiguous()
     if AB is None:
         AB = torch.empty((2 * N, 6, oh, ow), dtype=torch.float32, device=handle.device)
     normalize = bool(cfg["normalize_xyz"])
-    for b in range(0, N, 4096):
-        e = min(N, b + 4096)
-        ops.render_crops(handle, poseA[b:e], bbox2d[b:e], K, H, W, out_hw=(oh, ow), mesh_diameter=mesh_diameter,
-                         xyz_thr=0.001, normalize_xyz=normalize, A_out=AB[b:e])
-        ops.warp_crops(rgb, xyz_map, None, tf_to_crops[b:e], K, poseA[b:e], mesh_diameter, ops.MODE_REFINE,
-                       normalize_xyz=normalize, out_hw=(oh, ow), B_out=AB[N + b:N + e])
+    tf_to_crops, bbox2d = crop_stage(Scene(handle, mesh_diameter, K, H, W, N), poseA, rgb, xyz_map, None, ops.MODE_REFINE, crop_ratio,
+                                     (oh, ow), 0.001, normalize, AB, adjust_bbox=two_pose_call_quirk if N == 2 else None, chunk=4096,
+                                     window_hw=render_size)
     normalAs = normalBs = None
     if cfg.get("use_normal", False):
         # predict_pose_refine.py:50,58,75-76: the rendered normals and the frame's normal map go through the SAME nearest
@@ -181,6 +174,12 @@ def apply_two_pose_quirk(bbox2d, pairs):
     return bbox2d
 
 
+def two_pose_call_quirk(bbox2d):
+    """the quirk of a call of exactly two poses: transform_pts pairs pose i with corner i, so both are rendered with
+    [umin_0, vmin_0, umax_1, vmax_1].  bbox2d (2, 4) -> a new one: apply_two_pose_quirk's values through the torch kernels a captured graph holds"""
+    return torch.stack([bbox2d[0, 0], bbox2d[0, 1], bbox2d[1, 2], bbox2d[1, 3]])[None].expand(2, 4).contiguous()
+
+
 class PoseRefinePredictor:
     run_name = "2023-10-28-18-33-37"
 
@@ -249,85 +248,63 @@ class PoseRefinePredictor:
         tn = [float(tn)] * 3 if isinstance(tn, (int, float)) else [float(v) for v in tn]
         return oh, ow, tn, bool(self.cfg["normalize_xyz"])
 
-    def refine_part(self, slot, rows, rgb_t, xyz_t, poses, K, H, W, mesh_handle, mesh_diameter, iterations, outs, workspace=None,
-                    state=None, shared_translation=False, obj=None, views=None):
+    def refine_part(self, slot, rows, rgb_t, xyz_t, poses, scene, iterations, outs, workspace=None, state=None, shared_translation=False):
         """Iterations `iterations` (a range) of the refine loop for the hypotheses rows=(a, b) of `poses`, on the CURRENT
-        stream, with the activation-buffer set `slot`: per iteration fp_crop_windows -> fp_render_crops (A) +
-        fp_warp_crops (B) -> RefineNet plan -> fp_pose_update.  outs = (poses_out (N,4,4), trans_delta (N,3), rot_delta
-        (N,3,3), n_iterations_total): the last iteration writes rows a..b of them.  state: what the previous call for this
-        part returned (None for the first iteration).  shared_translation: the hypotheses a..b of `poses` all have the same
-        translation (register(): estimater.py:132-133 puts every rotation of the grid at the guessed centre), so in
-        iteration 0 they share one crop window and one observed crop: it is warped once and the stem of the fp16 plan
-        encodes it once (engine._HipEncoder, bit-identical to 252 copies).  Several objects: mesh_handle = an ops.MeshSet,
-        mesh_diameter = its ops.object_diameters table, obj = the call's ObjectIndex (rows a..b of it are this part's).  Several views:
-        views = the call's ops.Views, rgb_t / xyz_t = (V,H,W,3) frame stacks, mesh_handle an ops.MeshSet with its diameter table (K
-        unused).  shared_translation may also be an ops.Segments of the call's rows (a batched registration): the rows of each segment
-        share one translation (the caller guarantees it, as with True), so iteration 0 warps one observed crop per piece of a segment
-        in this part (segment_pieces) and the plan replicates each into its rows (engine._HipEncoder, segmented shared_b).  -> state"""
+        stream, with the activation-buffer set `slot`: per iteration crops.crop_stage (fp_crop_windows -> fp_render_crops (A) +
+        fp_warp_crops (B)) -> RefineNet plan -> fp_pose_update.  scene: the crops.Scene of ALL of `poses` (rows a..b of it are this
+        part's; with views rgb_t / xyz_t are (V,H,W,3) stacks).  outs = (poses_out (N,4,4), trans_delta (N,3), rot_delta (N,3,3),
+        n_iterations_total): the last iteration writes rows a..b of them.  state: what the previous call for this part returned (None
+        for the first iteration).  shared_translation: the hypotheses a..b all have the same translation (register(): estimater.py:132-133
+        puts every rotation of the grid at the guessed centre), so in iteration 0 they share one crop window and one observed crop: it
+        is warped once and the stem of the fp16 plan encodes it once (engine._HipEncoder, bit-identical to 252 copies).  Or an
+        ops.Segments of the call's rows (a batched registration; the caller guarantees one translation per segment): iteration 0 warps
+        one observed crop per piece of a segment in this part (segment_pieces), from the piece's first row, and the plan replicates each
+        into its rows (engine._HipEncoder, segmented shared_b).  -> state"""
         plan = self.plan()
         a, b = rows
         n = b - a
         oh, ow, tn, normalize = self._loop_constants()
         poses_out, trans_delta, rot_delta, total = outs
-        o = obj.dev[a:b] if obj is not None else None
-        vw = views.rows(a, b) if views is not None else None
-        grouped = obj if obj is not None else views        # the quirk per object, per view, or per (view, object)
-        pairs = grouped.pair_rows(a, b) if grouped is not None else None
-        tables = obj is not None or views is not None
+        part = scene.rows(a, b)
+        pairs = part.pairs if part.grouped else None        # the quirk per object / view (two_pose_pairs), or of the whole call
+        quirk = (lambda bbox2d: apply_two_pose_quirk(bbox2d, pairs)) if pairs is not None else \
+            two_pose_call_quirk if not part.grouped and poses.shape[0] == 2 else None
+        segmented = isinstance(shared_translation, ops.Segments)
         if state is None:
             state = dict(P=poses[a:b], AB=torch.empty((2 * n, 6, oh, ow), dtype=plan.dtype, device=poses.device), raw=None)
         for it in iterations:
             last = it + 1 == total
             P, AB = state["P"], state["AB"]
-            tf_to_crops, bbox2d = ops.crop_windows(P, K, mesh_diameter, self.cfg["crop_ratio"], (ow, oh), obj=o, views=vw)
-            if grouped is not None:
-                if pairs is not None:       # the quirk below, per object / view (two_pose_pairs)
-                    apply_two_pose_quirk(bbox2d, pairs)
-            elif poses.shape[0] == 2:
-                # reference broadcasting quirk (SURVEY App. D.5): with exactly two poses transform_pts pairs pose i with
-                # corner i, so both hypotheses are rendered with [umin_0, vmin_0, umax_1, vmax_1]
-                bbox2d = torch.stack([bbox2d[0, 0], bbox2d[0, 1], bbox2d[1, 2], bbox2d[1, 3]])[None].expand(2, 4).contiguous()
-            ops.render_crops(mesh_handle, P, bbox2d, K, H, W, out_hw=(oh, ow), mesh_diameter=mesh_diameter, xyz_thr=0.001,
-                             normalize_xyz=normalize, A_out=AB[:n], workspace=workspace, obj=o, views=vw)
-            pieces = segment_pieces(shared_translation.offsets, a, b) \
-                if isinstance(shared_translation, ops.Segments) and it == 0 and plan.hip else None
+            # iteration 0 of a shared translation: B rows n..n+S hold one observed crop per piece (S pieces), the plan replicates them
+            pieces = segment_pieces(shared_translation.offsets, a, b) if segmented and it == 0 and plan.hip else None
             if pieces is not None and len(pieces) < n:
-                # one observed crop per piece, from the piece's first row (its view, object and translation are the piece's)
-                S = len(pieces)
-                first_h = np.asarray([p0 for p0, _ in pieces], dtype=np.int64)
-                first = torch.as_tensor(first_h, device=poses.device)
-                ops.warp_crops(rgb_t, xyz_t, None, tf_to_crops.index_select(0, first), K, P.index_select(0, first), mesh_diameter,
-                               ops.MODE_REFINE, normalize_xyz=normalize, out_hw=(oh, ow), B_out=AB[n:n + S],
-                               obj=None if o is None else o.index_select(0, first), views=None if vw is None else vw.take(first_h))
-                raw = plan(AB[:n + S], slot=slot, shared_b=ops.Segments([e - p0 for p0, e in pieces], poses.device))
+                warp_rows = (np.asarray([p0 for p0, _ in pieces], dtype=np.int64), AB[n:n + len(pieces)])
+                shared_b = ops.Segments([e - p0 for p0, e in pieces], poses.device)
+            elif bool(shared_translation) and not segmented and it == 0 and n > 1 and plan.hip:
+                warp_rows, shared_b = ((0, 1), AB[n:n + 1]), True
             else:
-                shared = bool(shared_translation) and not isinstance(shared_translation, ops.Segments) and it == 0 and n > 1 and plan.hip
-                ops.warp_crops(rgb_t, xyz_t, None, tf_to_crops[:1] if shared else tf_to_crops, K, P[:1] if shared else P, mesh_diameter,
-                               ops.MODE_REFINE, normalize_xyz=normalize, out_hw=(oh, ow), B_out=AB[n:n + 1] if shared else AB[n:],
-                               obj=None if o is None else (o[:1] if shared else o), views=vw)
-                raw = plan(AB[:n + 1], slot=slot, shared_b=True) if shared else plan(AB, slot=slot)
+                warp_rows = shared_b = None
+            tf_to_crops, _ = crop_stage(part, P, rgb_t, xyz_t, None, ops.MODE_REFINE, self.cfg["crop_ratio"], (oh, ow), 0.001, normalize,
+                                        AB, workspace=workspace, adjust_bbox=quirk, warp_rows=warp_rows)
+            raw = plan(AB, slot=slot) if warp_rows is None else plan(AB[:n + warp_rows[1].shape[0]], slot=slot, shared_b=shared_b)
             state["raw"] = raw
-            state["P"] = ops.pose_update(raw["trans"], raw["rot"], P, rot_rep=self.cfg["rot_rep"], normalize_xyz=normalize,
-                                         trans_normalizer=tn, rot_normalizer=float(self.cfg["rot_normalizer"]),
-                                         mesh_diameter=mesh_diameter if tables else float(mesh_diameter),
-                                         out=poses_out[a:b] if last else None,
-                                         trans_delta_out=trans_delta[a:b] if last else None,
-                                         rot_delta_out=rot_delta[a:b] if last else None, trans_rep=str(self.cfg["trans_rep"]), K=K,
-                                         tf_to_crops=tf_to_crops, input_w=float(self.cfg["input_resize"][0]), obj=o, views=vw)
+            state["P"] = part.pose_update(raw["trans"], raw["rot"], P, rot_rep=self.cfg["rot_rep"], normalize_xyz=normalize,
+                                          trans_normalizer=tn, rot_normalizer=float(self.cfg["rot_normalizer"]),
+                                          out=poses_out[a:b] if last else None, trans_delta_out=trans_delta[a:b] if last else None,
+                                          rot_delta_out=rot_delta[a:b] if last else None, trans_rep=str(self.cfg["trans_rep"]),
+                                          tf_to_crops=tf_to_crops, input_w=float(self.cfg["input_resize"][0]))
         return state
 
-    def depth_check(self, poses, xyz_t, K, H, W, mesh_handle, mesh_diameter, tol, out=None, workspace=None, obj=None, views=None):
+    def depth_check(self, poses, xyz_t, scene, tol, out=None, workspace=None):
         """How well the poses (N,4,4) agree with the observed xyz map the refine loop read: the crop windows of the loop (crop_ratio,
         input_resize; the two-pose quirk is not applied: every pose is judged through its own window), the render's depth there and
         ops.depth_agreement against xyz_t through the same windows, on the CURRENT stream -> the (N, 4) int32 table [model, valid,
-        agree, behind] (`out` if given).  The arguments are refine_part's for the same rows: mesh_handle a mesh or an ops.MeshSet with
-        its diameter table, obj the rows' device object index, views the rows' ops.Views; workspace the rasteriser scratch of the part.
-        Writes only its own buffers: the poses and the loop's outputs are read, never written."""
+        agree, behind] (`out` if given).  scene: the crops.Scene of these poses (a part's: scene.rows(a, b)); workspace: the part's
+        rasteriser scratch.  Writes only its own buffers."""
         oh, ow, _, _ = self._loop_constants()
-        tf_to_crops, bbox2d = ops.crop_windows(poses, K, mesh_diameter, self.cfg["crop_ratio"], (ow, oh), obj=obj, views=views)
-        depth = ops.render_crops(mesh_handle, poses, bbox2d, K, H, W, out_hw=(oh, ow), mesh_diameter=mesh_diameter, xyz_thr=0.001,
-                                 normalize_xyz=False, want=("depth",), workspace=workspace, obj=obj, views=views)["depth"]
-        return ops.depth_agreement(depth, xyz_t, tf_to_crops, tol, views=views, out=out)
+        tf_to_crops, bbox2d = scene.crop_windows(poses, self.cfg["crop_ratio"], (ow, oh))
+        depth = scene.render_crops(poses, bbox2d, (oh, ow), xyz_thr=0.001, normalize_xyz=False, want=("depth",), workspace=workspace)["depth"]
+        return scene.depth_agreement(depth, xyz_t, tf_to_crops, tol, out=out)
 
     def refine_device(self, rgb_t, xyz_t, poses, K, H, W, mesh_handle, mesh_diameter, iteration, workspace=None,
                       shared_translation=False, obj=None, views=None):
@@ -337,36 +314,20 @@ class PoseRefinePredictor:
         joined once at the end.  workspace: optional rasteriser scratch, one uint8 tensor per part.
         -> (poses (N,4,4), trans_delta (N,3) in metres, rot_mat_delta (N,3,3)) of the last iteration, as the reference
         keeps them in last_trans_update / last_rot_update (predict_pose_refine.py:238-239).
-        Several objects in one call: mesh_handle = an ops.MeshSet, mesh_diameter = its ops.object_diameters table, obj = an
-        ObjectIndex of the N hypotheses (any order of objects; the two-pose quirk per object, two_pose_pairs).
-        Several views in one call: views = an ops.Views of the N hypotheses, rgb_t / xyz_t = (V,H,W,3) frame stacks, mesh_handle an
-        ops.MeshSet with its diameter table; with obj too, the ObjectIndex must be built with view=views.host (the quirk per (view,
-        object)).  shared_translation=True (one translation for the whole call) is refused with views; an ops.Segments of the N rows
-        (one translation per segment, e.g. per (camera, object) of a batched registration) works with obj, views or both."""
+        K .. mesh_diameter, obj and views make the call's crops.Scene (which checks their rules).  Several objects: mesh_handle = an
+        ops.MeshSet, mesh_diameter = its ops.object_diameters table, obj = an ObjectIndex of the N hypotheses (any order).  Several views:
+        views = an ops.Views of the N hypotheses, rgb_t / xyz_t = (V,H,W,3) stacks, the ObjectIndex built with view=views.host.
+        shared_translation=True is refused with views; an ops.Segments of the N rows (one translation each) works with obj, views or both."""
         self.plan()
         N = poses.shape[0]
         dev = poses.device
-        if obj is not None and len(obj) != N:
-            raise ValueError(f"refine_device: {N} poses but an object index of {len(obj)}")
         segmented = isinstance(shared_translation, ops.Segments)
         if segmented and shared_translation.total != N:
             raise ValueError(f"refine_device: {N} poses but shared_translation segments cover {shared_translation.total}")
-        if views is not None:
-            if shared_translation and not segmented:
-                raise ValueError("refine_device: shared_translation (registration) is not supported with views")
-            if not isinstance(views, ops.Views):
-                raise ValueError("refine_device: views must be an ops.Views")
-            if views.dev is not None and len(views) != N:
-                raise ValueError(f"refine_device: {N} poses but a view index of {len(views)}")
-            if obj is not None:
-                vh = np.zeros(N, dtype=np.int64) if views.host is None else views.host
-                if obj.view is None or not np.array_equal(obj.view, vh):
-                    raise ValueError("refine_device: with views, the ObjectIndex must be built with view=views.host "
-                                     "(the two-pose quirk is grouped per (view, object))")
-        parts = self.sub.parts(N, dev)
-        grouped = obj if obj is not None else views
-        if grouped is not None:
-            parts = parts_for_pairs(parts, grouped.pairs)
+        if views is not None and shared_translation and not segmented:
+            raise ValueError("refine_device: shared_translation (registration) is not supported with views")
+        scene = Scene(mesh_handle, mesh_diameter, K, H, W, N, obj=obj, views=views, who="refine_device")
+        parts = parts_for_pairs(self.sub.parts(N, dev), scene.pair_list)
         if workspace is not None and torch.is_tensor(workspace):
             workspace = [workspace]
         if workspace is not None and len(workspace) != len(parts):
@@ -382,9 +343,8 @@ class PoseRefinePredictor:
         for it in range(iteration):
             for h, rows in enumerate(parts):
                 with torch.cuda.stream(streams[h]):
-                    state[h] = self.refine_part(h, rows, rgb_t, xyz_t, poses, K, H, W, mesh_handle, mesh_diameter, range(it, it + 1),
-                                                outs, None if workspace is None else workspace[h], state[h],
-                                                shared_translation=shared_translation, obj=obj, views=views)
+                    state[h] = self.refine_part(h, rows, rgb_t, xyz_t, poses, scene, range(it, it + 1), outs,
+                                                None if workspace is None else workspace[h], state[h], shared_translation=shared_translation)
         self.sub.join(streams)
         self._raw_parts = [None if st is None else st["raw"] for st in state]   # last_raw_output
         return outs[:3]
@@ -409,15 +369,15 @@ class PoseRefinePredictor:
 
         def build():
             oh, ow, _, _ = self._loop_constants()
+            scene = Scene(handle, mesh_diameter, K, H, W, N)
             g = dict(rgb=torch.empty_like(rgb_t), xyz=torch.empty_like(xyz_t), poses=torch.empty_like(poses), mesh=mesh_tensors,
                      outs=self.alloc_outputs(N, dev) + (int(iteration),), state=[None] * len(parts),
-                     ws=[torch.empty(max(16, ops.workspace_bytes(b - a, handle.V, handle.T, oh, ow)), dtype=torch.uint8, device=dev)
-                         for a, b in parts])
+                     ws=[scene.workspace(b - a, oh, ow, dev) for a, b in parts])
             g["rgb"].copy_(rgb_t); g["xyz"].copy_(xyz_t); g["poses"].copy_(poses)
 
             def body(h):
-                g["state"][h] = self.refine_part(h, parts[h], g["rgb"], g["xyz"], g["poses"], K, H, W, handle, mesh_diameter,
-                                                 range(int(iteration)), g["outs"], g["ws"][h], None, shared_translation=shared_translation)
+                g["state"][h] = self.refine_part(h, parts[h], g["rgb"], g["xyz"], g["poses"], scene, range(int(iteration)), g["outs"],
+                                                 g["ws"][h], None, shared_translation=shared_translation)
             g["graphs"] = PartGraphs(self.sub, dev, len(parts), body)
             return g
         g = self._graphs.get(key, mode, build)
@@ -471,10 +431,8 @@ class PoseRefinePredictor:
             P_in = torch.as_tensor(ob_in_cams, device=dev, dtype=torch.float).reshape(-1, 4, 4).contiguous()
             canv = []
             for P in (P_in, B_in_cams):
-                AB = torch.empty((2 * P.shape[0], 6, int(self.cfg["input_resize"][0]), int(self.cfg["input_resize"][1])),
-                                 dtype=torch.float32, device=dev)
                 b = make_crop_data_batch(self.cfg["input_resize"], P, mesh, rgb_t, None, K, self.cfg["crop_ratio"], xyz_t, cfg=self.cfg,
-                                         mesh_tensors=mesh_tensors, mesh_diameter=mesh_diameter, AB=AB, depth_hw=(H, W))
+                                         mesh_tensors=mesh_tensors, mesh_diameter=mesh_diameter, depth_hw=(H, W))
                 n = P.shape[0]
                 canv.append(crop_rows_canvas(b.AB[:n].cpu().numpy(), b.AB[n:].cpu().numpy()))
             return B_in_cams, make_grid_image(canv, nrow=2, padding=2, pad_value=255)

@@ -4,6 +4,7 @@ import numpy as np
 import torch
 
 from . import ops
+from .crops import Scene, crop_stage
 from .Utils import get_mesh_handle, make_mesh_tensors, stack_frames
 from .engine import ScorePlan
 from .h5_dataset import ScoreMultiPairH5Dataset
@@ -27,16 +28,10 @@ def make_crop_data_batch(render_size, ob_in_cams, mesh, rgb, depth, K, crop_rati
     poseA = torch.as_tensor(ob_in_cams, dtype=torch.float, device=handle.device).reshape(-1, 4, 4).contiguous()
     N = poseA.shape[0]
     oh, ow = int(cfg["input_resize"][0]), int(cfg["input_resize"][1])
-    tf_to_crops, bbox2d = ops.crop_windows(poseA, K, mesh_diameter, crop_ratio, (render_size[1], render_size[0]))
     if AB is None:
         AB = torch.empty((2 * N, 6, oh, ow), dtype=torch.float32, device=handle.device)
-    normalize = bool(cfg["normalize_xyz"])
-    for b in range(0, N, 4096):
-        e = min(N, b + 4096)
-        ops.render_crops(handle, poseA[b:e], bbox2d[b:e], K, H, W, out_hw=(oh, ow), mesh_diameter=mesh_diameter,
-                         xyz_thr=0.1, normalize_xyz=normalize, A_out=AB[b:e], workspace=workspace)
-        ops.warp_crops(rgb, None, depth, tf_to_crops[b:e], K, poseA[b:e], mesh_diameter, ops.MODE_SCORE,
-                       normalize_xyz=normalize, out_hw=(oh, ow), B_out=AB[N + b:N + e])
+    tf_to_crops, _ = crop_stage(Scene(handle, mesh_diameter, K, H, W, N), poseA, rgb, None, depth, ops.MODE_SCORE, crop_ratio, (oh, ow),
+                                0.1, bool(cfg["normalize_xyz"]), AB, workspace=workspace, chunk=4096, window_hw=render_size)
     Ks = torch.as_tensor(np.asarray(K, dtype=np.float64), dtype=torch.float, device=handle.device).reshape(1, 3, 3).expand(N, 3, 3)
     mesh_diameters = torch.ones((N,), dtype=torch.float, device=handle.device) * float(mesh_diameter)
     batch = BatchPoseData(rgbAs=AB[:N, :3], rgbBs=AB[N:, :3], xyz_mapAs=AB[:N, 3:], xyz_mapBs=AB[N:, 3:], poseA=poseA,
@@ -107,26 +102,18 @@ class ScorePredictor:
 
         def build():
             oh, ow = int(self.cfg["input_resize"][0]), int(self.cfg["input_resize"][1])
+            scene = Scene(handle, mesh_diameter, K, H, W, N)
             g = dict(rgb=torch.empty_like(rgb_t), depth=torch.empty_like(depth_t), poses=torch.empty_like(poses), mesh=mesh_tensors,
-                     feats=torch.empty((N, 512), dtype=plan.dtype, device=dev),
-                     ws=[torch.empty(max(16, ops.workspace_bytes(b - a, handle.V, handle.T, oh, ow)), dtype=torch.uint8, device=dev)
-                         for a, b in parts])
+                     feats=torch.empty((N, 512), dtype=plan.dtype, device=dev), ws=[scene.workspace(b - a, oh, ow, dev) for a, b in parts])
             g["rgb"].copy_(rgb_t); g["depth"].copy_(depth_t); g["poses"].copy_(poses)
-
-            normalize = bool(self.cfg["normalize_xyz"])
 
             def body(h):
                 # the launches of make_crop_data_batch without its BatchPoseData bookkeeping (whose intrinsics / diameter tensors
-                # are host -> device copies, which a stream capture does not allow): crop windows, rendered crop, observed crop
+                # are host -> device copies, which a stream capture does not allow)
                 a, b = parts[h]
-                n = b - a
-                P = g["poses"][a:b]
-                AB = torch.empty((2 * n, 6, oh, ow), dtype=plan.dtype, device=dev)
-                tf_to_crops, bbox2d = ops.crop_windows(P, K, mesh_diameter, self.cfg["crop_ratio"], (ow, oh))
-                ops.render_crops(handle, P, bbox2d, K, H, W, out_hw=(oh, ow), mesh_diameter=mesh_diameter, xyz_thr=0.1,
-                                 normalize_xyz=normalize, A_out=AB[:n], workspace=g["ws"][h])
-                ops.warp_crops(g["rgb"], None, g["depth"], tf_to_crops, K, P, mesh_diameter, ops.MODE_SCORE, normalize_xyz=normalize,
-                               out_hw=(oh, ow), B_out=AB[n:])
+                AB = torch.empty((2 * (b - a), 6, oh, ow), dtype=plan.dtype, device=dev)
+                crop_stage(scene.rows(a, b), g["poses"][a:b], g["rgb"], None, g["depth"], ops.MODE_SCORE, self.cfg["crop_ratio"], (oh, ow),
+                           0.1, bool(self.cfg["normalize_xyz"]), AB, workspace=g["ws"][h])
                 plan.features(AB, slot=h, out=g["feats"][a:b])
             g["graphs"] = PartGraphs(self.sub, dev, len(parts), body)
             return g
@@ -208,23 +195,17 @@ class ScorePredictor:
             raise ValueError(f"predict_objects: {len(segments)} segments and {int(object_diameters.numel())} diameters for a set of "
                              f"{mesh_set.M} meshes")
         if views is not None:
-            if not isinstance(views, ops.Views):
-                raise ValueError("predict_objects: views must be an ops.Views")
-            if views.dev is not None and len(views) != N:
-                raise ValueError(f"predict_objects: {N} poses but a view index of {len(views)}")
             rgb_t = stack_frames(rgb, dev, torch.float, convert_after_upload=True)
             depth_t = stack_frames(depth, dev, torch.float)
-            if rgb_t.dim() != 4 or depth_t.dim() != 3 or rgb_t.shape[0] != views.V or depth_t.shape[0] != views.V:
-                raise ValueError(f"predict_objects: {views.V} views need (V,H,W,3) / (V,H,W) stacks, got {tuple(rgb_t.shape)} / "
-                                 f"{tuple(depth_t.shape)}")
-            H, W = int(depth_t.shape[1]), int(depth_t.shape[2])
         else:
             rgb_t = torch.as_tensor(rgb, device=dev).to(torch.float).contiguous()
             depth_t = torch.as_tensor(depth, device=dev, dtype=torch.float).contiguous()
-            H, W = int(depth_t.shape[0]), int(depth_t.shape[1])
+        scene = Scene(mesh_set, object_diameters, K, depth_t.shape[-2], depth_t.shape[-1], N, obj=segments.row_ids(), views=views,
+                      who="predict_objects")
+        if views is not None and (rgb_t.dim() != 4 or depth_t.dim() != 3 or rgb_t.shape[0] != views.V or depth_t.shape[0] != views.V):
+            raise ValueError(f"predict_objects: {views.V} views need (V,H,W,3) / (V,H,W) stacks, got {tuple(rgb_t.shape)} / "
+                             f"{tuple(depth_t.shape)}")
         oh, ow = int(self.cfg["input_resize"][0]), int(self.cfg["input_resize"][1])
-        normalize = bool(self.cfg["normalize_xyz"])
-        obj = segments.row_ids()
         feats = torch.empty((N, 512), dtype=plan.dtype, device=dev)
         if N:
             parts = self.sub.parts(N, dev)
@@ -232,19 +213,9 @@ class ScorePredictor:
             self.sub.fork(streams)
             for h, (a, b) in enumerate(parts):
                 with torch.cuda.stream(streams[h]):
-                    # make_crop_data_batch's launches with the per-hypothesis object index
-                    n = b - a
-                    P, o = poses[a:b], obj[a:b]
-                    vw = None if views is None else views.rows(a, b)
-                    AB = torch.empty((2 * n, 6, oh, ow), dtype=plan.dtype, device=dev)
-                    tf_to_crops, bbox2d = ops.crop_windows(P, K, object_diameters, self.cfg["crop_ratio"], (ow, oh), obj=o, views=vw)
-                    for c in range(0, n, 4096):
-                        e = min(n, c + 4096)
-                        vc = None if vw is None else vw.rows(c, e)
-                        ops.render_crops(mesh_set, P[c:e], bbox2d[c:e], K, H, W, out_hw=(oh, ow), mesh_diameter=object_diameters,
-                                         xyz_thr=0.1, normalize_xyz=normalize, A_out=AB[c:e], obj=o[c:e], views=vc)
-                        ops.warp_crops(rgb_t, None, depth_t, tf_to_crops[c:e], K, P[c:e], object_diameters, ops.MODE_SCORE,
-                                       normalize_xyz=normalize, out_hw=(oh, ow), B_out=AB[n + c:n + e], obj=o[c:e], views=vc)
+                    AB = torch.empty((2 * (b - a), 6, oh, ow), dtype=plan.dtype, device=dev)
+                    crop_stage(scene.rows(a, b), poses[a:b], rgb_t, None, depth_t, ops.MODE_SCORE, self.cfg["crop_ratio"], (oh, ow), 0.1,
+                               bool(self.cfg["normalize_xyz"]), AB, chunk=4096)
                     plan.features(AB, slot=h, out=feats[a:b])
             self.sub.join(streams)
         return plan.head_segments(feats, segments) + 100  # predict_score.py:209

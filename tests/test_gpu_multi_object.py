@@ -283,18 +283,20 @@ def _first_inputs(pred, scene, frame, dev, meshes, gmeshes, names, obj, P):
     """the network input (A rendered | B observed, fp16) of the first refine iteration: multi-object call against per-object calls
     -> (multi (2N, 6, h, w), per-object rows arranged like the multi-object call)"""
     from foundationpose_amd import ops
+    from foundationpose_amd.crops import Scene
     from foundationpose_amd.predict_pose_refine import ObjectIndex
     mset, handles, diam = _set(names, meshes, gmeshes, dev)
     Pt, N = _t(P, dev), len(P)
-    st = pred.refine_part(0, (0, N), frame["rgb_t"], frame["xyz_t"], Pt, scene["K"], 480, 640, mset, ops.object_diameters(diam, dev),
-                          range(1), pred.alloc_outputs(N, dev) + (1,), obj=ObjectIndex(obj, dev))
+    st = pred.refine_part(0, (0, N), frame["rgb_t"], frame["xyz_t"], Pt,
+                          Scene(mset, ops.object_diameters(diam, dev), scene["K"], 480, 640, N, obj=ObjectIndex(obj, dev)),
+                          range(1), pred.alloc_outputs(N, dev) + (1,))
     multi = st["AB"].clone()
     single = torch.empty_like(multi)
     for k in range(len(names)):
         rows = np.nonzero(np.asarray(obj) == k)[0]
         r = torch.as_tensor(rows, device=dev)
         n = len(rows)
-        sk = pred.refine_part(0, (0, n), frame["rgb_t"], frame["xyz_t"], Pt[r].contiguous(), scene["K"], 480, 640, handles[k], diam[k],
+        sk = pred.refine_part(0, (0, n), frame["rgb_t"], frame["xyz_t"], Pt[r].contiguous(), Scene(handles[k], diam[k], scene["K"], 480, 640, n),
                               range(1), pred.alloc_outputs(n, dev) + (1,))
         single[r], single[r + N] = sk["AB"][:n], sk["AB"][n:]
     return multi, single

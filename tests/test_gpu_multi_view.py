@@ -124,6 +124,7 @@ def _views_vs_single(pred, scene, stack, dev, meshes, gmeshes, names, obj, view,
     """-> (one multi-view refine call, per-view calls) as poses, or with first=True the first network input (2N, 6, h, w).
     same_size: every per-view call refines ALL of P (rows kept in place) with that view's frame and K and contributes its rows"""
     from foundationpose_amd import ops
+    from foundationpose_amd.crops import Scene
     from foundationpose_amd.predict_pose_refine import ObjectIndex
     mset, _, diam = _set(names, meshes, gmeshes, dev)
     dt = ops.object_diameters(diam, dev)
@@ -131,8 +132,8 @@ def _views_vs_single(pred, scene, stack, dev, meshes, gmeshes, names, obj, view,
     vt = ops.Views(stack["Ks"], view, dev)
     oi = ObjectIndex(obj, dev, view=view) if obj is not None else None
     if first:
-        st = pred.refine_part(0, (0, N), stack["rgb_t"], stack["xyz_t"], Pt, None, 480, 640, mset, dt, range(1),
-                              pred.alloc_outputs(N, dev) + (1,), obj=oi, views=vt)
+        st = pred.refine_part(0, (0, N), stack["rgb_t"], stack["xyz_t"], Pt, Scene(mset, dt, None, 480, 640, N, obj=oi, views=vt), range(1),
+                              pred.alloc_outputs(N, dev) + (1,))
         multi = st["AB"].clone()
     else:
         multi = pred.refine_device(stack["rgb_t"], stack["xyz_t"], Pt, None, 480, 640, mset, dt, iteration, obj=oi, views=vt)[0]
@@ -148,7 +149,8 @@ def _views_vs_single(pred, scene, stack, dev, meshes, gmeshes, names, obj, view,
         args = (stack["rgb_t"][v], stack["xyz_t"][v], Pv, stack["Ks"][v], 480, 640, mset, dt)
         if first:
             n = len(sel)
-            sk = pred.refine_part(0, (0, n), *args, range(1), pred.alloc_outputs(n, dev) + (1,), obj=ov)
+            sk = pred.refine_part(0, (0, n), *args[:3], Scene(mset, dt, stack["Ks"][v], 480, 640, n, obj=ov), range(1),
+                                  pred.alloc_outputs(n, dev) + (1,))
             single[r], single[r + N] = sk["AB"][:n], sk["AB"][n:]
         else:
             out = pred.refine_device(*args, iteration, obj=ov)[0]
@@ -201,9 +203,10 @@ def test_one_object_in_two_views_is_not_the_two_pose_quirk(scene, dev, meshes, g
         from foundationpose_amd import ops
         from foundationpose_amd.predict_pose_refine import ObjectIndex
         mset, _, diam = _set(("can",), meshes, gmeshes, dev)
-        naive = pred.refine_part(0, (0, 2), stack["rgb_t"][0], stack["xyz_t"][0], _t(P, dev), stack["Ks"][0], 480, 640, mset,
-                                 ops.object_diameters(diam, dev), range(1), pred.alloc_outputs(2, dev) + (1,),
-                                 obj=ObjectIndex([0, 0], dev))["AB"]
+        from foundationpose_amd.crops import Scene
+        naive = pred.refine_part(0, (0, 2), stack["rgb_t"][0], stack["xyz_t"][0], _t(P, dev),
+                                 Scene(mset, ops.object_diameters(diam, dev), stack["Ks"][0], 480, 640, 2, obj=ObjectIndex([0, 0], dev)),
+                                 range(1), pred.alloc_outputs(2, dev) + (1,))["AB"]
         assert not torch.equal(a[:1], naive[:1])
         # one view, two hypotheses: the quirk applies as in the single-view call
         a, b = _views_vs_single(pred, scene, stack, dev, meshes, gmeshes, ("can",), None, [1, 1], P, first=True)
