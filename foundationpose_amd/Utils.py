@@ -40,7 +40,8 @@ def make_mesh_tensors(mesh, device="cuda", max_tex_size=None):
             step = int(np.ceil(max(img.shape[:2]) / max_tex_size))
             img = img[::step, ::step]  # decimation; the reference uses cv2.resize (Utils.py:110-114, setup-time only)
         t["tex"] = torch.as_tensor(np.ascontiguousarray(img), device=device, dtype=torch.float)[None] / 255.0
-        t["uv_idx"] = torch.as_tensor(np.asarray(mesh.faces), device=device, dtype=torch.int)
+        uv_faces = getattr(visual, "uv_faces", None)      # a per-triangle atlas (reconstruct.bake_texture) indexes uv by its own table
+        t["uv_idx"] = torch.as_tensor(np.asarray(mesh.faces if uv_faces is None else uv_faces), device=device, dtype=torch.int)
         uv = torch.as_tensor(np.asarray(visual.uv), device=device, dtype=torch.float)
         uv[:, 1] = 1 - uv[:, 1]
         t["uv"] = uv

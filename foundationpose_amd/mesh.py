@@ -15,10 +15,13 @@ class _Material:
 class TextureVisual:
     kind = "texture"
 
-    def __init__(self, uv, image):
+    def __init__(self, uv, image, uv_faces=None, vertex_colors=None):
         self.uv = np.asarray(uv, dtype=np.float64)
         self.material = _Material(image)
-        self.vertex_colors = None
+        # uv_faces (F,3): rows of uv per face corner, where they are not the faces' vertex indices (a per-triangle atlas: every
+        # face has its own three uv rows); vertex_colors are kept beside the texture for the formats without one (PLY)
+        self.uv_faces = None if uv_faces is None else np.asarray(uv_faces, dtype=np.int64)
+        self.vertex_colors = None if vertex_colors is None else np.asarray(vertex_colors)
 
 
 class ColorVisual:
@@ -41,12 +44,14 @@ def vertex_normals_from_faces(vertices, faces):
 
 
 class SimpleMesh:
-    def __init__(self, vertices, faces, vertex_normals=None, uv=None, texture=None, vertex_colors=None):
+    def __init__(self, vertices, faces, vertex_normals=None, uv=None, texture=None, vertex_colors=None, uv_faces=None):
         self.vertices = np.asarray(vertices, dtype=np.float64)
         self.faces = np.asarray(faces, dtype=np.int64)
         self._vn = None if vertex_normals is None else np.asarray(vertex_normals, dtype=np.float64)
+        if uv_faces is not None and (texture is None or uv is None or np.shape(uv_faces) != self.faces.shape):
+            raise ValueError(f"SimpleMesh: uv_faces needs uv and a texture and the shape of faces {self.faces.shape}, got {np.shape(uv_faces)}")
         if texture is not None and uv is not None:
-            self.visual = TextureVisual(uv, np.asarray(texture))
+            self.visual = TextureVisual(uv, np.asarray(texture), uv_faces, vertex_colors)
         else:
             self.visual = ColorVisual(vertex_colors)
 

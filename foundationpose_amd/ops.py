@@ -989,6 +989,116 @@ def tsdf_extract(tsdf, weight, color, color_weight, origin, voxel, min_weight=1.
     return dict(pos=pos[first], vnormals=nrm[first], vertex_color=col[first], faces=inv.reshape(total, 3).to(torch.int32))
 
 
+TEXTURE_BAKE_MAX_TEXELS, TEXTURE_BAKE_MAX_SIDE = 16, 16384       # FP_TEXTURE_BAKE_MAX_TEXELS / _SIDE (include/fp_amd.h)
+
+
+def texture_atlas_layout(F, texels, Bx=None):
+    """the per-triangle atlas of F faces with texels x texels blocks, Bx block columns (None: ceil(sqrt(F))) -> (Bx, Ht, Wt); ValueError
+    for a block side outside 2..16, Bx < 1 or an atlas of more than 16384 texels a side"""
+    what = "texture_bake"
+    F, T = int(F), int(texels)
+    if not 2 <= T <= TEXTURE_BAKE_MAX_TEXELS:
+        raise ValueError(f"{what}: texels must be 2..{TEXTURE_BAKE_MAX_TEXELS} (the side of a face's block), got {texels!r}")
+    if F > 1 << 24:
+        raise ValueError(f"{what}: {F} faces, at most 2^24")
+    if Bx is None:
+        Bx = max(int(np.ceil(np.sqrt(F))), 1)
+        while Bx * Bx < F:
+            Bx += 1
+        while Bx > 1 and (Bx - 1) * (Bx - 1) >= F:
+            Bx -= 1
+    Bx = int(Bx)
+    if Bx < 1:
+        raise ValueError(f"{what}: Bx must be >= 1 block columns, got {Bx}")
+    Ht, Wt = -(-F // Bx) * T, Bx * T
+    if max(Ht, Wt) > TEXTURE_BAKE_MAX_SIDE:
+        raise ValueError(f"{what}: an atlas of {Ht} x {Wt} texels for {F} faces; at most {TEXTURE_BAKE_MAX_SIDE} a side (fewer texels a "
+                         "face, or another Bx)")
+    return Bx, Ht, Wt
+
+
+def texture_atlas_uv(F, texels, Bx, device=None):
+    """the texture coordinates that go with texture_bake's atlas -> uv (3F,2) float32 (float64, rounded once), uv_idx (F,3) int32:
+    corner k of face f half a texel inside its block, at ((bx*T + 0.5 + dx_k) / Wt, (by*T + 0.5 + dy_k) / Ht) with (dx, dy) = (0,0),
+    (T-1,0), (0,T-1): the rasteriser's convention (the row index grows with v), so a bilinear tap inside the triangle reads the
+    block's own texels"""
+    Bx, Ht, Wt = texture_atlas_layout(F, texels, Bx)
+    T = int(texels)
+    f = torch.arange(int(F), dtype=torch.float64, device=device)
+    bx, by = torch.remainder(f, Bx), torch.div(f, Bx, rounding_mode="floor")
+    dx = torch.tensor([0.0, T - 1.0, 0.0], dtype=torch.float64, device=device)
+    dy = torch.tensor([0.0, 0.0, T - 1.0], dtype=torch.float64, device=device)
+    uv = torch.stack([(bx[:, None] * T + 0.5 + dx[None]) / Wt, (by[:, None] * T + 0.5 + dy[None]) / Ht], -1)
+    return uv.reshape(3 * int(F), 2).float().contiguous(), torch.arange(3 * int(F), dtype=torch.int32, device=device).view(int(F), 3)
+
+
+def texture_bake(pos, faces, vertex_color, depth, rgb, masks, ob_in_cams, Ks, tol, min_cos, texels=4, Bx=None, min_depth=0.001):
+    """fp_texture_bake: a per-triangle texture atlas for a mesh from the posed RGB-D views it was fused from (include/fp_amd.h has the
+    definition) -> (tex (Ht,Wt,3) f32 in the units of rgb, coverage (Ht,Wt) uint8: the views blended into each texel, uv (3F,2) f32,
+    uv_idx (F,3) int32).  pos (Nv,3) f32 and faces (F,3) int32 in the frame of the poses; vertex_color (Nv,3) f32 in the units of rgb
+    or None: what a texel no view sees falls back to (None: 128).  The views as tsdf_integrate takes them.  tol (metres): a view
+    colours a texel when its depth there is within tol of the texel's; min_cos: the smallest cosine between the face's normal and the
+    ray.  Face f owns the texels x texels block (f % Bx, f / Bx); Bx=None: ceil(sqrt(F)).  One launch, no synchronisation: with device
+    Ks capturable in a graph (the outputs are allocated before it).  Refusals in tsdf_integrate's order."""
+    what = "texture_bake"
+    for name, t, nd in (("pos", pos, 2), ("faces", faces, 2), ("depth", depth, 3), ("rgb", rgb, 4), ("ob_in_cams", ob_in_cams, 3)):
+        if not torch.is_tensor(t):
+            raise _lib.FpAmdError(f"{what}: {name} must be a tensor, got {type(t).__name__}")
+        if t.dim() != nd:
+            raise _lib.FpAmdError(f"{what}: {name} must have {nd} dimensions, got {tuple(t.shape)}")
+    if pos.shape[1] != 3 or faces.shape[1] != 3:
+        raise _lib.FpAmdError(f"{what}: pos must be (Nv,3) and faces (F,3), got {tuple(pos.shape)} and {tuple(faces.shape)}")
+    Nv, F = int(pos.shape[0]), int(faces.shape[0])
+    if vertex_color is not None and (not torch.is_tensor(vertex_color) or tuple(vertex_color.shape) != (Nv, 3)):
+        raise _lib.FpAmdError(f"{what}: vertex_color must be a ({Nv},3) tensor like pos or None")
+    V, H, W = (int(x) for x in depth.shape)
+    if V > 4096:
+        raise _lib.FpAmdError(f"{what}: {V} views in one call, at most 4096")
+    if H < 1 or W < 1 or H * W > 1 << 28:
+        raise _lib.FpAmdError(f"{what}: frames of {H} x {W} pixels (1 .. 2^28 pixels are supported)")
+    if tuple(rgb.shape) != (V, H, W, 3):
+        raise _lib.FpAmdError(f"{what}: rgb must be ({V},{H},{W},3) like depth, got {tuple(rgb.shape)}")
+    if masks is not None and (not torch.is_tensor(masks) or tuple(masks.shape) != (V, H, W)):
+        raise _lib.FpAmdError(f"{what}: masks must be a ({V},{H},{W}) tensor like depth or None")
+    if tuple(ob_in_cams.shape) != (V, 4, 4):
+        raise _lib.FpAmdError(f"{what}: ob_in_cams must be ({V},4,4), got {tuple(ob_in_cams.shape)}")
+    Bx, Ht, Wt = texture_atlas_layout(F, texels, Bx)
+    tl, mc, md = float(tol), float(min_cos), float(min_depth)
+    if not (np.isfinite(tl) and tl >= 0 and np.isfinite(np.float32(tl))):
+        raise ValueError(f"{what}: tol must be finite and >= 0 (metres), got {tol!r}")
+    if not (0 < np.float32(mc) <= 1):
+        raise ValueError(f"{what}: min_cos must be in (0, 1], got {min_cos!r}")
+    if not (np.isfinite(md) and md >= 0):
+        raise ValueError(f"{what}: min_depth must be finite and >= 0 (metres), got {min_depth!r}")
+    K_dev = None
+    if torch.is_tensor(Ks) and Ks.is_cuda:
+        if tuple(Ks.shape) != (V, 3, 3):
+            raise _lib.FpAmdError(f"{what}: device Ks must be ({V},3,3), got {tuple(Ks.shape)}")
+        K_dev = Ks
+    else:
+        Kh = [_hostK33(K, what, "the projection of a texel is defined without one") for K in Ks]
+        if len(Kh) != V:
+            raise _lib.FpAmdError(f"{what}: {len(Kh)} intrinsic matrices for {V} views")
+    p = _dev(pos, torch.float32, "pos")
+    fc = _dev(faces, torch.int32, "faces")
+    vc = _dev(vertex_color, torch.float32, "vertex_color")
+    d = _dev(depth, torch.float32, "depth")
+    c = _dev(rgb, torch.float32, "rgb")
+    m = _dev(masks, torch.uint8, "masks")
+    P = _dev(ob_in_cams, torch.float32, "ob_in_cams")
+    K_dev = _dev(K_dev, torch.float64, "Ks")
+    tex = torch.empty((Ht, Wt, 3), dtype=torch.float32, device=p.device)
+    coverage = torch.empty((Ht, Wt), dtype=torch.uint8, device=p.device)
+    uv, uv_idx = texture_atlas_uv(F, texels, Bx, p.device)
+    if F == 0:
+        return tex, coverage, uv, uv_idx
+    if K_dev is None and V > 0:
+        K_dev = torch.as_tensor(np.stack(Kh), device=p.device)
+    _lib.check(_lib.lib().fp_texture_bake(_ptr(p), Nv, _ptr(fc), F, _ptr(vc), _ptr(d), _ptr(c), _ptr(m), _ptr(P), _ptr(K_dev), V, H, W,
+                                          int(texels), Bx, tl, mc, md, _ptr(tex), _ptr(coverage), _stream(p)), "fp_texture_bake")
+    return tex, coverage, uv, uv_idx
+
+
 def pose_update(trans, rot, poses, rot_rep="axis_angle", normalize_xyz=True, trans_normalizer=(1.0, 1.0, 1.0),
                 rot_normalizer=1.0, mesh_diameter=1.0, out=None, trans_delta_out=None, rot_delta_out=None, trans_rep="tracknet",
                 K=None, tf_to_crops=None, input_w=0, obj=None, views=None):

@@ -1,8 +1,10 @@
 """Model-free object setup: an object's mesh from a few posed RGB-D reference views with masks, by truncated-signed-distance (TSDF)
 fusion and marching tetrahedra on the device (ops.tsdf_integrate / ops.tsdf_extract; include/fp_amd.h has the definition).  It stands
 where the reference trains a neural object field (bundlesdf/, not built: DESIGN.md section 7): what setup hands to FoundationPose is a
-mesh in the object frame either way.  Colours are per vertex; there is no texture atlas, no simplification and no removal of small
-components: the masks do the carving, and the views are assumed to show the object unoccluded."""
+mesh in the object frame either way.  Colours are per vertex, as coarse as the voxel pitch; bake_texture (reconstruct_object's
+texture=T) adds a per-triangle texture atlas blended from the same views at their own resolution (ops.texture_bake).  There is no
+simplification and no removal of small components: the masks do the carving, and the views are assumed to show the object
+unoccluded."""
 import numpy as np
 import torch
 
@@ -111,6 +113,46 @@ class TsdfVolume:
         return mesh, t
 
 
+def bake_texture(mesh_tensors, rgbs, depths, masks, ob_in_cams, Ks, texels=4, tol=None, min_cos=0.2, min_depth=0.001):
+    """A texture atlas for a reconstructed mesh from the views it was fused from -> (SimpleMesh, mesh_tensors).  mesh_tensors: the
+    device dict TsdfVolume.extract returns (pos, faces, vnormals, vertex_color in [0,1]); the views as TsdfVolume.integrate takes
+    them.  Face f gets a texels x texels block of a square-ish atlas (ops.texture_bake: every texel is a point of its face, coloured
+    from the views that face it within min_cos and whose depth there is within tol metres of it, blended by cos^2; a texel no view sees
+    keeps the interpolated vertex colour).  tol is required: twice the voxel pitch of the fusion is what reconstruct_object passes.
+    The atlas is rounded as the vertex colours are: floor(x + 0.5) clamped to 0..255.  The returned dict carries tex (1,Ht,Wt,3) in
+    [0,1], uv (3F,2), uv_idx (F,3) and the unchanged pos, faces and vnormals; the SimpleMesh the same atlas as a uint8 image, uv in the
+    file convention (u, 1 - v) with visual.uv_faces, and the vertex colours beside it (save_ply).  A setup call (it synchronises)."""
+    what = "bake_texture"
+    if tol is None:
+        raise ValueError(f"{what}: tol is required (metres; about twice the voxel pitch the mesh was fused at)")
+    if rgbs is None:
+        raise ValueError(f"{what}: rgbs are required")
+    for k in ("pos", "faces", "vnormals"):
+        if k not in mesh_tensors:
+            raise ValueError(f"{what}: mesh_tensors has no '{k}'")
+    dev = mesh_tensors["pos"].device
+    return _bake(mesh_tensors, *_views_in(rgbs, depths, masks, ob_in_cams, Ks, dev, what), texels, tol, min_cos, min_depth)
+
+
+def _bake(t, d, c, m, P, K, texels, tol, min_cos, min_depth):
+    """bake_texture of views that are on the device already"""
+    from .Utils import mesh_handle_from_tensors
+    vc = t.get("vertex_color")
+    if vc is not None:
+        vc = vc.mul(255.0).add_(0.5).floor_().clamp_(0, 255)               # the mesh's uint8 colours, in the units of rgb
+    tex, coverage, uv, uv_idx = ops.texture_bake(t["pos"], t["faces"], vc, d, c, m, P, K, tol, min_cos, texels, None, min_depth)
+    tex = tex.add_(0.5).floor_().clamp_(0, 255)
+    out = dict(pos=t["pos"], vnormals=t["vnormals"], faces=t["faces"], tex=(tex / 255.0)[None], uv=uv, uv_idx=uv_idx)
+    out["_handle"] = mesh_handle_from_tensors(out)
+    uv_file = uv.double().cpu().numpy()
+    uv_file[:, 1] = 1.0 - uv_file[:, 1]
+    mesh = SimpleMesh(t["pos"].cpu().numpy(), t["faces"].cpu().numpy(), vertex_normals=t["vnormals"].cpu().numpy(), uv=uv_file,
+                      texture=tex.to(torch.uint8).cpu().numpy(), uv_faces=uv_idx.cpu().numpy(),
+                      vertex_colors=None if vc is None else vc.to(torch.uint8).cpu().numpy())
+    mesh.visual.coverage = coverage.cpu().numpy()          # (Ht,Wt) uint8: how many views were blended into each texel
+    return mesh, out
+
+
 def bounds_from_views(depths, masks, ob_in_cams, Ks, margin=0.0, min_depth=0.001, device="cuda"):
     """the box (lo, hi: float64 (3,), object frame, metres) of the masked depth pixels of all views, grown by margin: the pixels are
     back-projected on the device (fp_depth_to_xyz_frames) and mapped to the object frame.  Every masked pixel counts, so a mask that
@@ -141,17 +183,21 @@ def _bounds(d, m, P, K, margin, min_depth, what):
 
 
 def reconstruct_object(rgbs, depths, masks, ob_in_cams, Ks, voxel=None, trunc=None, margin=None, min_weight=1, min_depth=0.001,
-                       longest=128, device="cuda"):
+                       longest=128, device="cuda", texture=None, texture_min_cos=0.2):
     """V posed RGB-D reference views with masks -> (SimpleMesh, mesh_tensors) of the object, in the frame of the poses: the box of the
     masked depths (bounds_from_views) -> a TsdfVolume over it -> fuse -> extract.  voxel=None picks the pitch that gives the longest
-    side `longest` voxels; margin defaults to three voxels around the observed points; trunc to four voxels.  ValueError, naming the
-    cause, when there are no views, the masks are empty or no surface was found."""
+    side `longest` voxels; margin defaults to three voxels around the observed points; trunc to four voxels.  texture=T (2..16) bakes a
+    texture atlas of T x T texels a face from the same views onto the mesh (bake_texture with tol = two voxels): the mesh and the
+    tensors then carry the atlas in place of the vertex colours alone.  ValueError, naming the cause, when there are no views, the
+    masks are empty or no surface was found."""
     what = "reconstruct_object"
     n = len(depths) if depths is not None else 0
     if n == 0:
         raise ValueError(f"{what}: no views")
     if rgbs is None or masks is None:
         raise ValueError(f"{what}: rgbs and masks are required")
+    if texture is not None:
+        ops.texture_atlas_layout(1, texture)          # a block side outside 2..16 is refused before the fusion
     d, c, m, P, K = _views_in(rgbs, depths, masks, ob_in_cams, Ks, device, what)
     lo, hi = _bounds(d, m, P, K, 0.0, min_depth, what)
     side = float((hi - lo).max())
@@ -164,6 +210,9 @@ def reconstruct_object(rgbs, depths, masks, ob_in_cams, Ks, voxel=None, trunc=No
     vol = TsdfVolume(lo, (nz, ny, nx), voxel, trunc, device, min_depth)
     vol._integrate(d, c, m, P, K)
     try:
-        return vol.extract(min_weight)
+        mesh, tensors = vol.extract(min_weight)
     except ValueError as e:
         raise ValueError(f"{what}: no surface found in the {n} views ({e})") from None
+    if texture is None:
+        return mesh, tensors
+    return _bake(tensors, d, c, m, P, K, int(texture), 2.0 * voxel, texture_min_cos, min_depth)

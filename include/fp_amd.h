@@ -79,8 +79,9 @@ const char* fp_last_error(void);
  *               symmetry-aware projection distance, for pose batches.
  *   220 -> 221: + fp_tsdf_integrate, fp_tsdf_count_triangles, fp_tsdf_emit_triangles (additions only): an object's mesh from posed
  *               RGB-D reference views (truncated-signed-distance fusion and marching tetrahedra).
- *   221 -> 222: + FP_IGEMM_MFMA_16X16X32 / FP_IGEMM_MFMA_32X32X16 (additions only; an older library refuses the bits as unknown flags). */
-#define FP_AMD_ABI_VERSION 222
+ *   221 -> 222: + FP_IGEMM_MFMA_16X16X32 / FP_IGEMM_MFMA_32X32X16 (additions only; an older library refuses the bits as unknown flags).
+ *   222 -> 223: + fp_texture_bake (addition only): a texture atlas for a fused mesh from its posed RGB-D reference views. */
+#define FP_AMD_ABI_VERSION 223
 int fp_version(void);
 
 /* Utils.py:104-130 make_mesh_tensors: records caller-owned device tensors.
@@ -311,6 +312,46 @@ int fp_tsdf_emit_triangles(const float* tsdf /*dev*/, const float* weight /*dev*
                            const float* color_weight /*dev*/, int nz, int ny, int nx, const float* origin /*host 3*/, float voxel,
                            float min_weight, const int64_t* offsets /*dev, one per cube*/, long long total, int64_t* keys /*dev 3*total*/,
                            float* pos /*dev 3*total,3*/, float* col /*dev 3*total,3*/, float* nrm /*dev 3*total,3*/, void* stream);
+/* A texture atlas for a mesh from posed RGB-D reference views (those its TSDF volume was fused from): every texel is a point of one
+ * face, coloured from the views that see it.  The atlas is per triangle: face f owns the T x T texel block at block column f % Bx and
+ * block row f / Bx, so Wt = Bx * T, Ht = ceil(F / Bx) * T, and texel (i, j) of the block (i along x) is tex[(f / Bx) * T + j][(f % Bx) *
+ * T + i].  The blocks with an index >= F (the rest of the last block row) get tex = 0 and coverage = 0; every texel of the atlas is
+ * written and nothing else is.  A mesh samples the block through uv corners half a texel inside it: corner k of face f at
+ * (((f % Bx) * T + 0.5 + dx_k) / Wt, ((f / Bx) * T + 0.5 + dy_k) / Ht) with (dx, dy) = (0, 0), (T-1, 0), (0, T-1), the row index growing
+ * with v (the convention of fp_mesh_create), so that a bilinear tap inside the triangle reads the block's own texels only.
+ * pos (Nv,3) and faces (F,3) are the mesh in the frame of the poses; vertex_color (Nv,3) in the units of rgb (NULL: 128) is what a
+ * texel no view sees falls back to; the views are fp_tsdf_integrate's (depth, rgb, masks, ob_in_cams, Ks: prepared alike, K rounded to
+ * float32; a view with a pose or intrinsic that is not finite, or with a skew, is skipped).  Every operation is float32 without
+ * contraction, one rounding per operation, as parenthesised.  Per texel (f, i, j):
+ *   a = (float)i / (float)(T-1), b = (float)j / (float)(T-1);  s = a + b;  if s > 1: a = a / s, b = b / s (a texel beyond the hypotenuse
+ *     is a point on it: it holds the edge's colour for the taps that straddle the edge);  c = (1 - a) - b;
+ *   p = (c*p0 + a*p1) + b*p2 per component, with p0, p1, p2 the face's vertices;
+ *   n = (p1 - p0) x (p2 - p0): n.x = e1.y*e2.z - e1.z*e2.y, and cyclic;  nn = (n.x*n.x + n.y*n.y) + n.z*n.z;
+ *   fallback = (c*col0 + a*col1) + b*col2 per channel, with 128 for the colour of a vertex whose index is outside 0..Nv-1; 128 without
+ *     vertex_color.
+ * A face with an index outside 0..Nv-1 or without nn > 0 && nn < infinity (no area, a vertex that is not finite) is unusable: its
+ * texels get the fallback and coverage 0.  Otherwise the views are visited in index order; per view, with T its pose:
+ *   X = ((T00*p.x + T01*p.y) + T02*p.z) + T03, Y and Z likewise from rows 1 and 2;  skip the view unless Z > 0;
+ *   N = R n: N.x = (T00*n.x + T01*n.y) + T02*n.z, ...;  d = (N.x*X + N.y*Y) + N.z*Z;  NN = (N.x*N.x + N.y*N.y) + N.z*N.z;
+ *   rr = (X*X + Y*Y) + Z*Z;  w = (d*d) / (NN*rr) (cos^2 of the angle between the normal and the ray);
+ *   skip the view unless d < 0 (the face looks at the camera) and w >= min_cos*min_cos (not grazing);
+ *   u = floorf(((fx * X) / Z + cx) + 0.5f), v likewise;  skip the view unless 0 <= u < W and 0 <= v < H (compared as floats);
+ *   skip the view if mask[v][u] == 0;  dz = depth[v][u];  skip the view unless dz >= min_depth;
+ *   skip the view unless fabsf(dz - Z) <= tol (another surface hides the texel in this view);
+ *   per channel acc = acc + w * rgb[v][u];  accw = accw + w;  cnt = cnt + 1.
+ * Then tex = cnt > 0 ? acc / accw : fallback and coverage = min(cnt, 255).  One texel per lane, the views inside the kernel in one
+ * order: no atomics, no allocation, no host synchronisation (graph-capturable), every call repeats its bits.  No index outside pos,
+ * faces, vertex_color or the frames is formed.  F == 0 does nothing.
+ * Argument errors (FP_ERR_INVALID_ARG): NULL pos / faces / tex / coverage with F > 0; NULL depth / rgb / ob_in_cams / Ks with V > 0 (and
+ * F > 0); T outside 2..FP_TEXTURE_BAKE_MAX_TEXELS; Bx < 1; Wt or Ht above FP_TEXTURE_BAKE_MAX_SIDE; F outside 0..2^24; Nv < 0; V outside
+ * 0..4096; H or W below 1 or more than 2^28 pixels; tol or min_depth not finite or below 0; min_cos not in (0, 1]. */
+#define FP_TEXTURE_BAKE_MAX_TEXELS 16
+#define FP_TEXTURE_BAKE_MAX_SIDE 16384
+int fp_texture_bake(const float* pos /*dev Nv,3*/, int Nv, const int32_t* faces /*dev F,3*/, int F,
+                    const float* vertex_color /*dev Nv,3 in 0..255 | NULL*/, const float* depth /*dev V,H,W*/,
+                    const float* rgb /*dev V,H,W,3 in 0..255*/, const uint8_t* masks /*dev V,H,W|NULL*/,
+                    const float* ob_in_cams /*dev V,16*/, const double* Ks /*dev V,9*/, int V, int H, int W, int T, int Bx, float tol,
+                    float min_cos, float min_depth, float* tex /*dev Ht,Wt,3*/, uint8_t* coverage /*dev Ht,Wt*/, void* stream);
 /* fp_pose_update_multi with K = Ks[view[n]] (read by trans_rep deepim only; Ks is required either way).  A view[n] outside 0..V-1:
  * all of poses_out row n (16 values) and of the given trans_delta_out / rot_delta_out rows n are NaN, whatever trans_rep. */
 int fp_pose_update_views(const float* trans /*dev N,3*/, const float* rot /*dev N,3|6*/, const float* poses_in /*dev N,16*/,

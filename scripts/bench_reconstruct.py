@@ -7,8 +7,13 @@ voxels over the can's box:
             voxel; the views' pixels are gathers that mostly hit the caches) over the achievable HBM bandwidth as the floor;
   extract   ops.tsdf_extract (count -> cumsum -> the host read of the total -> emit -> torch.unique), HIP events around the whole
             call, and the two kernels alone through the C entry points;
-  host      tests/tsdf_model.py (float32 numpy, the same bits) on the same views: integrate and extract, once each (--host_dims).
-Prints one JSON line; times in milliseconds."""
+  bake      ops.texture_bake of an atlas of --texels x --texels texels a face onto the extracted mesh from the same 16 views (tol = two
+            voxels, min_cos 0.2; the outputs' allocation is inside the timed call), HIP events, warm, the median of --reps; the bytes
+            it must write at the least (13 bytes a texel) over the achievable HBM bandwidth as the floor;
+  host      tests/tsdf_model.py (float32 numpy, the same bits) on the same views: integrate and extract, once each (--host_dims), and
+            tests/texture_bake_model.py for the bake.
+Prints one JSON line; times in milliseconds.  --bake_out FILE puts the bake's figures under "bench" in that JSON file
+(profiles/texture_bake.json), beside what the GPU test wrote there."""
 import argparse, ctypes as C, json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -27,7 +32,9 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--reps", type=int, default=20)
 ap.add_argument("--dims", type=int, nargs="+", default=[128, 256])
 ap.add_argument("--host_dims", type=int, nargs="*", default=[128], help="volume sizes the host restatement is timed at")
+ap.add_argument("--texels", type=int, default=4, help="side of a face's block in the baked atlas")
 ap.add_argument("--out", type=str, default=None)
+ap.add_argument("--bake_out", type=str, default=None)
 args = ap.parse_args()
 dev = torch.device("cuda:0")
 V, H, W = 16, syn.H, syn.W
@@ -84,6 +91,14 @@ for n in args.dims:
     floor = n ** 3 * 48 / HBM_ACHIEVABLE * 1e3
     r = dict(voxel_mm=s * 1e3, fuse_ms=t_fuse[0], fuse_min_ms=t_fuse[1], fuse_floor_ms=floor, extract_ms=t_extract[0], extract_min_ms=t_extract[1],
              count_kernel_ms=t_count[0], emit_kernel_ms=t_emit[0], vertices=int(mesh["pos"].shape[0]), faces=T)
+    vcol = mesh["vertex_color"].add(0.5).floor_().clamp_(0, 255)
+    bake = lambda: ops.texture_bake(mesh["pos"], mesh["faces"], vcol, depth, rgb, masks, P, Ks, 2 * s, 0.2, args.texels)   # noqa: E731
+    t_bake = timed(bake)
+    tex, cov, _, _ = bake()
+    real = T * args.texels ** 2                        # texels of the faces' blocks; the rest of the last block row is padding
+    r.update(bake_ms=t_bake[0], bake_min_ms=t_bake[1], bake_floor_ms=tex.shape[0] * tex.shape[1] * 13 / HBM_ACHIEVABLE * 1e3,
+             atlas=[int(tex.shape[0]), int(tex.shape[1])], texels=args.texels,
+             fallback_share=(int((cov == 0).sum()) - (tex.shape[0] * tex.shape[1] - real)) / max(real, 1))
     if n in args.host_dims:
         ref = tm.Volume((n, n, n), vol.origin, vol.voxel, vol.trunc)
         d_h, c_h, m_h = depth.cpu().numpy(), rgb.cpu().numpy(), masks.cpu().numpy()
@@ -94,11 +109,24 @@ for n in args.dims:
         t2 = time.perf_counter()
         same = bool(np.array_equal(hp.view(np.uint32), mesh["pos"].cpu().numpy().view(np.uint32)) and np.array_equal(hf, mesh["faces"].cpu().numpy()))
         r.update(host_fuse_ms=(t1 - t0) * 1e3, host_extract_ms=(t2 - t1) * 1e3, host_mesh_bit_equal=same)
+        import texture_bake_model as tb
+        t3 = time.perf_counter()
+        h_tex, h_cov = tb.bake(mesh["pos"].cpu().numpy(), mesh["faces"].cpu().numpy(), vcol.cpu().numpy(), d_h, c_h, m_h, poses, Ks.cpu().numpy(),
+                               args.texels, tb.default_bx(T), 2 * s, 0.2)
+        r.update(host_bake_ms=(time.perf_counter() - t3) * 1e3,
+                 host_atlas_bit_equal=bool(np.array_equal(h_tex.view(np.uint32), tex.cpu().numpy().view(np.uint32)) and np.array_equal(h_cov, cov.cpu().numpy())))
     res["volumes"][str(n)] = r
-    del vol, arrays, mesh, counts, offsets, keys, rows
+    del vol, arrays, mesh, counts, offsets, keys, rows, tex, cov, vcol
     torch.cuda.empty_cache()
 line = json.dumps(res)
 print(line)
 if args.out:
     with open(args.out, "w") as f:
         f.write(line + "\n")
+if args.bake_out:
+    doc = json.load(open(args.bake_out)) if os.path.exists(args.bake_out) else {}
+    keys = ("voxel_mm", "faces", "atlas", "texels", "bake_ms", "bake_min_ms", "bake_floor_ms", "fuse_ms", "extract_ms", "fallback_share",
+            "host_bake_ms", "host_atlas_bit_equal")
+    doc["bench"] = {"views": V, "frame": [H, W], "volumes": {n: {k: r[k] for k in keys if k in r} for n, r in res["volumes"].items()}}
+    with open(args.bake_out, "w") as f:
+        json.dump(doc, f, indent=1)

@@ -6,7 +6,9 @@ demo_data and weights are not redistributable; with real data pass --mesh_file /
 checkpoints under $FOUNDATIONPOSE_WEIGHTS.  Visualisation (debug >= 1 overlays) is not implemented.
 Without a CAD model: `--ref_views DIR` (a directory in the same layout whose frames each carry a mask and an annotated pose) fuses the
 object's mesh from those reference views (foundationpose_amd/reconstruct.py) in place of --mesh_file; `--synthetic_ref_views N` writes
-such a directory from the can first; `--save_mesh PATH` writes the mesh that was used as a PLY."""
+such a directory from the can first; `--ref_texture T` bakes a texture atlas of T x T texels a face onto that mesh from the same views;
+`--save_mesh PATH` writes the mesh that was used: a PLY (positions, normals, vertex colours), or with a path ending in .obj an OBJ with
+its MTL and the texture as a PNG."""
 import argparse
 import logging
 import os
@@ -89,14 +91,15 @@ def main(argv=None):
     ap.add_argument("--standin_weights", action="store_true", help="seeded stand-in checkpoints instead of weights/")
     ap.add_argument("--ref_views", type=str, default=None, help="posed RGB-D reference views with masks, in place of --mesh_file")
     ap.add_argument("--synthetic_ref_views", type=int, default=0, help="write N reference views of the can first and use them")
-    ap.add_argument("--save_mesh", type=str, default=None, help="write the mesh that is used to this PLY")
+    ap.add_argument("--ref_texture", type=int, default=0, help="with --ref_views: bake a texture atlas of T x T texels a face (2..16)")
+    ap.add_argument("--save_mesh", type=str, default=None, help="write the mesh that is used to this PLY (or .obj: OBJ + MTL + PNG)")
     args = ap.parse_args(argv)
     logging.basicConfig(level=logging.INFO, format="[%(funcName)s()] %(message)s")
 
     from foundationpose_amd import dr
     from foundationpose_amd.datareader import YcbineoatReader
     from foundationpose_amd.estimater import FoundationPose
-    from foundationpose_amd.mesh_io import load_mesh, save_ply
+    from foundationpose_amd.mesh_io import load_mesh, save_obj, save_ply
     from foundationpose_amd.predict_pose_refine import PoseRefinePredictor
     from foundationpose_amd.predict_score import ScorePredictor
     from foundationpose_amd.Utils import set_seed
@@ -115,12 +118,16 @@ def main(argv=None):
     if args.ref_views:
         from foundationpose_amd.reconstruct import reconstruct_object
         t0 = time.perf_counter()
-        mesh, _ = reconstruct_object(*read_ref_views(args.ref_views), device=dev)
-        logging.info(f"mesh from {args.ref_views}: {len(mesh.vertices)} vertices, {len(mesh.faces)} faces in {time.perf_counter() - t0:.2f} s")
+        mesh, _ = reconstruct_object(*read_ref_views(args.ref_views), device=dev, texture=args.ref_texture or None)
+        atlas = getattr(getattr(mesh.visual, "material", None), "image", None)
+        logging.info(f"mesh from {args.ref_views}: {len(mesh.vertices)} vertices, {len(mesh.faces)} faces"
+                     + ("" if atlas is None else f", atlas {atlas.shape[0]} x {atlas.shape[1]}") + f" in {time.perf_counter() - t0:.2f} s")
     else:
         mesh = load_mesh(args.mesh_file)
+    if args.ref_texture and not args.ref_views:
+        ap.error("--ref_texture needs --ref_views (or --synthetic_ref_views N)")
     if args.save_mesh:
-        save_ply(mesh, args.save_mesh)
+        (save_obj if args.save_mesh.lower().endswith(".obj") else save_ply)(mesh, args.save_mesh)
     os.makedirs(os.path.join(args.debug_dir, "ob_in_cam"), exist_ok=True)
     if args.standin_weights:
         scorer = ScorePredictor(cfg=dict(DEFAULT_SCORE_CFG), state_dict=random_state_dict("score", seed=0), device=dev)
