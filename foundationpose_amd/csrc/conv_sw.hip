@@ -59,6 +59,17 @@ __device__ __forceinline__ void sw_wait_vm() {
   asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
 }
 
+// acc += a * b on v_mfma_f32_16x16x32_f16 with the accumulator tied to its registers.  The builtin leaves destination and addend
+// independent, and over the nine unrolled taps the register allocator then moves the 32 accumulator quads of a wave from k-step to
+// k-step; the holes that leaves cost k_conv_sw<512,128,4,true> 256 VGPRs for 203 live values, the whole register file of a CU at two
+// waves per SIMD.  Tied, it is 219, which leaves a third wave of up to 64 registers per SIMD to a light kernel of another stream
+// (tests/test_conv_sw_resources_host.py holds it to 224).  The operands' waits are still the compiler's; each accumulator is used once
+// per k-step, 31 MFMAs apart, and is read by other instructions only behind the barriers in front of the epilogue.
+typedef float sw_float4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ void sw_mfma16(sw_float4& acc, const half8& a, const half8& b) {
+  asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, %0" : "+v"(acc) : "v"(a), "v"(b));
+}
+
 // padded-grid index of tap (0,0) of output pixel m: (b * Hp + oy) * Wp + ox
 __device__ __forceinline__ int sw_q(const IgemmGeom& g, int m) {
   const int b = ig_fastdiv(m, g.mulP, g.shrP);
@@ -98,7 +109,7 @@ __global__ __launch_bounds__(512, 1) void k_conv_sw(IgemmParams p) {
   constexpr int PI = SW_PROWS / 16 / NW;            // patch instructions per wave and chunk: one at each of taps 0..PI-1
   static_assert(WI >= 1 && PI >= 1 && PI <= 7 && SW_PROWS == PI * 16 * NW, "tile shape");
   constexpr int STAGES_BYTES = 2 * SW_PATCH_BYTES + SW_NSTW * W_BYTES;
-  constexpr int LDS_MAIN = ig_lds_main<BM, BN>(STAGES_BYTES);
+  constexpr int LDS_MAIN = ig_lds_main_slim<BM, BN>(STAGES_BYTES);
   auto swz = [](int row) { return (row >> 2) & 3; };                    // weight rows, and patch rows of the 32x32x16 loop
   auto swzp = [](int row) { return S16 ? (row >> 1) & 2 : (row >> 2) & 3; };   // patch rows
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -220,10 +231,12 @@ __global__ __launch_bounds__(512, 1) void k_conv_sw(IgemmParams p) {
 
   half8 fa[2][TM], fw[2][2];                       // S16: fa[t >> 2][t & 3] is pixel fragment t, fw[t >> 1][t & 1] weight fragment t
   static_assert(TM == 4, "the fragment addresses of the next tap are computed behind the MFMA groups of a k-step, one per group of four");
-  int anext[NFA];                                  // fragment addresses of the next k-step's tap, inside a patch buffer
+  int anext[NFA], aflip[NFA];                      // fragment addresses of the next k-step's tap, inside a patch buffer (S16: ^ aflip, the swizzle bit)
 #pragma unroll
-  for (int t = 0; t < NFA; ++t)                    // tap (0,0) of the first k-step
-    anext[t] = S16 ? arow[t] ^ ((arow[t] >> 3) & 32) : (arow[t] << 6) + ((fhalf ^ swz(arow[t])) << 4);
+  for (int t = 0; t < NFA; ++t) {                  // tap (0,0) of the first k-step
+    anext[t] = S16 ? arow[t] : (arow[t] << 6) + ((fhalf ^ swz(arow[t])) << 4);
+    aflip[t] = S16 ? (arow[t] >> 3) & 32 : 0;
+  }
   // one k-step = (chunk cc, tap T).  LAST: cc is the last chunk (no next patch; the weight prefetch runs dry).
   // vmcnt bookkeeping (loads retire in order): this wave's pieces of W(s+1) must have landed when it leaves the memory
   // cluster; younger and allowed in flight are W(s+2), W(s+3) and the patch pieces issued in this and the previous step.
@@ -241,7 +254,7 @@ __global__ __launch_bounds__(512, 1) void k_conv_sw(IgemmParams p) {
     // the 32 address instructions at ~535 (matrix-pipe occupancy 0.84 -> 0.96); in the MFMA shadow they are free (<= 5 per MFMA hide)
     if constexpr (S16) {
 #pragma unroll
-      for (int t = 0; t < NFA; ++t) fa[t >> 2][t & 3] = *reinterpret_cast<const half8*>(pb + anext[t]);
+      for (int t = 0; t < NFA; ++t) fa[t >> 2][t & 3] = *reinterpret_cast<const half8*>(pb + (anext[t] ^ aflip[t]));
 #pragma unroll
       for (int t = 0; t < 4; ++t) fw[t >> 1][t & 1] = *reinterpret_cast<const half8*>(wb + w_off[t >> 1][t & 1]);
     } else {
@@ -288,13 +301,19 @@ __global__ __launch_bounds__(512, 1) void k_conv_sw(IgemmParams p) {
         for (int i = 0; i < 4; ++i)
 #pragma unroll
           for (int jh = 0; jh < 2; ++jh) {
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-              acc[i][jh * 4 + j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(fw[i >> 1][i & 1], fa[jh][j], acc[i][jh * 4 + j], 0, 0, 0);
-            // one pixel fragment's address behind each group of four MFMAs (8 fragments = the eight (i, jh) groups)
+            // one pixel fragment's address with each group of four MFMAs (8 fragments = the eight (i, jh) groups), one of its three
+            // instructions behind each of the first three: a 16x16x32 MFMA leaves the vector issue port free for half of its cycles, which
+            // takes one instruction and not three
             const int t = i * 2 + jh;
-            const int x = arow[t] + sh;
-            anext[t] = x ^ ((x >> 3) & 32);
+            int x, y;
+            sw_mfma16(acc[i][jh * 4 + 0], fw[i >> 1][i & 1], fa[jh][0]);
+            asm volatile("v_add_u32 %0, %1, %2" : "=v"(x) : "s"(sh), "v"(arow[t]));
+            sw_mfma16(acc[i][jh * 4 + 1], fw[i >> 1][i & 1], fa[jh][1]);
+            asm volatile("v_lshrrev_b32 %0, 3, %1" : "=v"(y) : "v"(x));
+            sw_mfma16(acc[i][jh * 4 + 2], fw[i >> 1][i & 1], fa[jh][2]);
+            asm volatile("v_and_b32 %0, 32, %0" : "+v"(y));
+            sw_mfma16(acc[i][jh * 4 + 3], fw[i >> 1][i & 1], fa[jh][3]);
+            anext[t] = x; aflip[t] = y;            // x ^ y where the address is used
           }
       } else {
 #pragma unroll
@@ -336,7 +355,7 @@ __global__ __launch_bounds__(512, 1) void k_conv_sw(IgemmParams p) {
   if (!grp) __builtin_amdgcn_s_barrier();          // group 0 waits out group 1's last compute cluster
   __syncthreads();
   SW_CLK(t_loop);
-  ig_epilogue<BM, BN, TM, THREADS, 0>(p, acc, smem, m0, n0, wm, wn, tid, lane, bias_lds);
+  ig_epilogue<BM, BN, TM, THREADS, 0, true>(p, acc, smem, m0, n0, wm, wn, tid, lane, bias_lds);
 #ifdef FP_PROFILE_BUILD
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // stores drained: the workgroup's resources are free from here
   SW_CLK(t_end);
@@ -544,9 +563,17 @@ int sw_ls_launch(const IgemmParams& p, hipStream_t stream) {
   return FP_OK;
 }
 
+// LDS of a k_conv_sw workgroup.  512 x 128: 128 KiB of staging buffers = the E tile, 2 KiB of row table, 3 KiB of vectors = 136192 B,
+// 107 allocation granules of 1280 B: with the 25872 B (21 granules) of a k_raster workgroup on 160-pixel crops that is the CU's 160 KiB
+constexpr int sw_lds_bytes(int BM, int BN) {
+  return (BM == 256 ? ig_lds_main_slim<256, 256>(2 * sw_prows(256) * SW_BK * 2 + SW_NSTW * 256 * SW_BK * 2)
+                    : ig_lds_main_slim<512, 128>(2 * sw_prows(512) * SW_BK * 2 + SW_NSTW * 128 * SW_BK * 2)) + IG_BIAS_LDS;
+}
+
 template <int BM, int BN, int TM, bool S16>
 int sw_launch(const IgemmParams& p, hipStream_t stream) {
-  constexpr int LDS = ig_lds_main<BM, BN>(2 * sw_prows(BM) * SW_BK * 2 + SW_NSTW * BN * SW_BK * 2) + IG_BIAS_LDS;
+  static_assert((BM == 256 && BN == 256) || (BM == 512 && BN == 128), "tile shapes of sw_lds_bytes");
+  constexpr int LDS = sw_lds_bytes(BM, BN);
   static_assert(LDS <= 160 * 1024, "does not fit the 160 KiB LDS");
   const long long tiles = (long long)fp_cdiv(p.M, BM) * (p.N / BN);
   FP_REQUIRE(tiles < (1ll << 31), "fp_igemm_f16_fwd: too many tiles");
@@ -605,10 +632,16 @@ bool fp_conv3x3_sw_applicable(const IgemmParams& p) {
   if (p.Cin % 64 != 0 || p.N % 128 != 0) return false;
   const long long bytes = (long long)(p.M / g.HoWo) * g.Hp * g.Wp * g.cstride * 2;
   if (bytes >= (1ll << 31)) return false;           // 32-bit byte offsets in the LDS-DMA source addresses
+  // 32-bit tile-relative row offsets in the epilogue's output table (igemm_epilogue.h, SLIM): elements of the output buffer
+  const IgemmGeom& o = p.out;
+  const long long imgs = o.bsplit > 0 ? o.bsplit : p.M / g.HoWo, groups = o.bsplit > 0 ? (p.M / g.HoWo) / o.bsplit + 1 : 0;
+  if (imgs * o.Hp * o.Wp * o.cstride + o.coff + groups * (long long)o.cgroup >= (1ll << 31)) return false;
   return sw_span(g, BM) <= (sw_variant(p) == 1 ? LS_PROWS : sw_prows(BM));
 }
 
 int fp_conv3x3_sw_tile_rows(const IgemmParams& p) { return sw_tile_rows(p); }
+
+extern "C" int fp_conv3x3_sw_lds_bytes(void) { return sw_lds_bytes(512, 128); }
 
 int fp_conv3x3_sw_launch(const IgemmParams& p, hipStream_t stream) {
   if (sw_variant(p) == 1) return sw_ls_launch<256, 128, 4>(p, stream);

@@ -27,10 +27,21 @@ constexpr int ig_lds_main(int stage_bytes) {
   return stage_bytes > BM * BN * 2 + BM * 16 ? stage_bytes : BM * BN * 2 + BM * 16;   // E tile + the two row-offset tables
 }
 
+// SLIM (k_conv_sw): the row tables take BM * 4 bytes behind the E tile instead of BM * 16, so that a workgroup leaves LDS for a light
+// workgroup of another stream (ig_lds_main_slim; conv_sw.hip).  The output table holds 32-bit offsets relative to the tile's first
+// row (the launcher checks that the buffers stay below 2^31 elements); the residual table is needed only until the residual rows are
+// requested, so it borrows the first BM * 8 bytes of the E tile, and a barrier separates its last read from the first write of E.
+// The addresses are the same 64-bit element offsets either way.
+template <int BM, int BN>
+constexpr int ig_lds_main_slim(int stage_bytes) {
+  return stage_bytes > BM * BN * 2 + BM * 4 ? stage_bytes : BM * BN * 2 + BM * 4;
+}
+#define IG_ROW_NONE ((int)0x80000000)            // SLIM: a row past M
+
 // Acc: float16_[2][TM], the accumulators of v_mfma_f32_32x32x16_f16 (2 x TM tiles of 32 channels x 32 pixels), or float4_[4][2 * TM],
 // those of v_mfma_f32_16x16x32_f16 (4 x 2 TM tiles of 16 x 16, conv_sw.hip) -- the same 128 x 64 wave tile either way
 typedef float ig_float4 __attribute__((ext_vector_type(4)));
-template <int BM, int BN, int TM, int THREADS, int DBG, bool FULL, typename Acc>
+template <int BM, int BN, int TM, int THREADS, int DBG, bool FULL, bool SLIM, typename Acc>
 __device__ __forceinline__ void ig_epilogue_body(const IgemmParams& p, Acc& acc, unsigned char* smem, int m0, int n0,
                                                  int wm, int wn, int tid, int lane, const float* bias_lds) {
   constexpr bool S16 = std::is_same<Acc, ig_float4[4][2 * TM]>::value;
@@ -48,12 +59,16 @@ __device__ __forceinline__ void ig_epilogue_body(const IgemmParams& p, Acc& acc,
   typedef float float4_ __attribute__((ext_vector_type(4)));
   const bool round_acc = p.round_acc != 0, has_bn = p.bn_scale != nullptr;
   long long* rowY = reinterpret_cast<long long*>(smem + BM * 2 * BN);
-  long long* rowR = rowY + BM;
+  long long* rowR = SLIM ? reinterpret_cast<long long*>(smem) : rowY + BM;
+  int* rowY32 = reinterpret_cast<int*>(smem + BM * 2 * BN);        // SLIM: in place of rowY
+  const long long baseY = SLIM ? ig_row_off(p.out, m0) + n0 : 0;   // m0 < M
+  auto row_exists = [&](int ml) { return SLIM ? rowY32[ml] != IG_ROW_NONE : rowY[ml] >= 0; };
   IG_CLK(te0);
   for (int r = tid; r < BM; r += THREADS) {
     const int m = m0 + r;
     const bool in = m < p.M;
-    rowY[r] = in ? ig_row_off(p.out, m) + n0 : -1;
+    if constexpr (SLIM) rowY32[r] = in ? (int)(ig_row_off(p.out, m) + n0 - baseY) : IG_ROW_NONE;
+    else rowY[r] = in ? ig_row_off(p.out, m) + n0 : -1;
     if (p.R) rowR[r] = in ? ig_row_off(p.res, m) + n0 : 0;
   }
   __syncthreads();
@@ -65,7 +80,15 @@ __device__ __forceinline__ void ig_epilogue_body(const IgemmParams& p, Acc& acc,
     for (int it = 0; it < NIT; ++it) {
       const int qd = tid + it * THREADS;
       const int ml = qd / CPR, ch = qd % CPR;
-      if (FULL || rowY[ml] >= 0) rv[it] = *reinterpret_cast<const half8*>(p.R + rowR[ml] + ch * 8);
+      if (FULL || row_exists(ml)) rv[it] = *reinterpret_cast<const half8*>(p.R + rowR[ml] + ch * 8);
+    }
+    if constexpr (SLIM) {
+      // rowR sits in the E tile: every wave has read it (its loads are issued) before any wave writes E.  A bare barrier: __syncthreads()
+      // would also wait for the residual rows themselves, whose latency the transposition is there to cover
+      __builtin_amdgcn_sched_barrier(0);
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      __builtin_amdgcn_s_barrier();
+      __builtin_amdgcn_sched_barrier(0);
     }
   }
   IG_CLK(te2);
@@ -145,8 +168,8 @@ __device__ __forceinline__ void ig_epilogue_body(const IgemmParams& p, Acc& acc,
   for (int it = 0; it < NIT; ++it) {
     const int qd = tid + it * THREADS;
     const int ml = qd / CPR, ch = qd % CPR;
-    const long long yo = rowY[ml];
-    if (!FULL && yo < 0) continue;
+    if (!FULL && !row_exists(ml)) continue;
+    const long long yo = SLIM ? baseY + rowY32[ml] : rowY[ml];
     half8 v = *reinterpret_cast<const half8*>(E + ml * (2 * BN) + ((ch ^ (ml & 15)) << 4));
     if (p.R) v = v + rv[it];                       // IEEE half add == the fp32 add of two halves rounded once
     if (p.relu) v = __builtin_elementwise_max(v, zero);
@@ -170,11 +193,11 @@ __device__ __forceinline__ void ig_epilogue_body(const IgemmParams& p, Acc& acc,
 #endif
 }
 
-template <int BM, int BN, int TM, int THREADS, int DBG = 0, typename Acc>
+template <int BM, int BN, int TM, int THREADS, int DBG = 0, bool SLIM = false, typename Acc>
 __device__ __forceinline__ void ig_epilogue(const IgemmParams& p, Acc& acc, unsigned char* smem, int m0, int n0,
                                             int wm, int wn, int tid, int lane, const float* bias_lds) {
-  if (m0 + BM <= p.M) ig_epilogue_body<BM, BN, TM, THREADS, DBG, true>(p, acc, smem, m0, n0, wm, wn, tid, lane, bias_lds);
-  else ig_epilogue_body<BM, BN, TM, THREADS, DBG, false>(p, acc, smem, m0, n0, wm, wn, tid, lane, bias_lds);
+  if (m0 + BM <= p.M) ig_epilogue_body<BM, BN, TM, THREADS, DBG, true, SLIM>(p, acc, smem, m0, n0, wm, wn, tid, lane, bias_lds);
+  else ig_epilogue_body<BM, BN, TM, THREADS, DBG, false, SLIM>(p, acc, smem, m0, n0, wm, wn, tid, lane, bias_lds);
 }
 // Kernel entry, BEFORE the first operand stage is requested: wave 0 sends the tile's bias straight to LDS with one
 // LDS-DMA (1 KiB = 256 floats; reads past the end of the bias vector return 0 through the buffer descriptor's bound).

@@ -601,6 +601,12 @@ extern "C" size_t fp_workspace_bytes(int N, int V, int T, int oh, int ow) {
   return ws_layout(N, V, T, oh).total;
 }
 
+// LDS of a k_raster workgroup: the strip's z-buffer, the queue counter and the queue of big triangles
+extern "C" size_t fp_raster_lds_bytes(int ow) {
+  if (ow <= 0) return 0;
+  return (size_t)FP_STRIP_ROWS * ow * sizeof(unsigned long long) + 16 + FP_BIG_MAX * sizeof(BigTri);
+}
+
 extern "C" size_t fp_mesh_set_workspace_bytes(const fp_mesh_set* set, int N, int oh, int ow) {
   if (!set) return 0;
   return fp_workspace_bytes(N, set->maxV, set->maxT, oh, ow);
@@ -632,7 +638,7 @@ static int render_launch(const char* name, const fp_mesh& one, const MeshTable& 
   ws.lists32 = L.ids16 ? nullptr : (int*)(w8 + L.lists);
   ws.vstride = maxV; ws.tstride = maxT;
   const dim3 gv(fp_cdiv(maxV, 256), N), gb(fp_cdiv(maxT, 256), N), gr(L.nstrips, N);
-  const size_t lds = (size_t)FP_STRIP_ROWS * ow * sizeof(unsigned long long) + 16 + FP_BIG_MAX * sizeof(BigTri);
+  const size_t lds = fp_raster_lds_bytes(ow);
   if constexpr (VIEWS) {
     hipLaunchKernelGGL((k_vertex<MULTI, fp_views>), gv, dim3(256), 0, st, one, tab, poses, bbox2d, K, H, W, oh, ow, L.nstrips, ws, vt);
     FP_CHECK_LAUNCH("fp_render_crops_views(vertex)");

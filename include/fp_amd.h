@@ -80,8 +80,10 @@ const char* fp_last_error(void);
  *   220 -> 221: + fp_tsdf_integrate, fp_tsdf_count_triangles, fp_tsdf_emit_triangles (additions only): an object's mesh from posed
  *               RGB-D reference views (truncated-signed-distance fusion and marching tetrahedra).
  *   221 -> 222: + FP_IGEMM_MFMA_16X16X32 / FP_IGEMM_MFMA_32X32X16 (additions only; an older library refuses the bits as unknown flags).
- *   222 -> 223: + fp_texture_bake (addition only): a texture atlas for a fused mesh from its posed RGB-D reference views. */
-#define FP_AMD_ABI_VERSION 223
+ *   222 -> 223: + fp_texture_bake (addition only): a texture atlas for a fused mesh from its posed RGB-D reference views.
+ *   223 -> 224: + fp_raster_lds_bytes, fp_conv3x3_sw_lds_bytes (additions only): the LDS a workgroup of the rasteriser and of the
+ *               3x3 convolution asks for at launch. */
+#define FP_AMD_ABI_VERSION 224
 int fp_version(void);
 
 /* Utils.py:104-130 make_mesh_tensors: records caller-owned device tensors.
@@ -374,6 +376,10 @@ int fp_crop_windows_multi(const float* poses /*dev N,16*/, const double* K /*hos
 /* bytes of scratch fp_render_crops needs for (N hypotheses, V vertices, T triangles, oh x ow crops): per-hypothesis
  * vertex records (32 B/vertex) and per-strip triangle lists; caller-owned device memory, no alignment beyond 256 B */
 size_t fp_workspace_bytes(int N, int V, int T, int oh, int ow);
+/* bytes of LDS one workgroup of the rasteriser's third kernel (k_raster) asks for at launch, for crops `ow` pixels wide; host only.
+ * Together with fp_conv3x3_sw_lds_bytes it must stay within the 160 KiB of a CU, so that a strip of the rasteriser of one
+ * sub-batch stream fits beside a tile of the 3x3 convolution of another (tests/test_conv_sw_resources_host.py). */
+size_t fp_raster_lds_bytes(int ow);
 
 /* Utils.py:133-219 nvdiffrast_render (dr.rasterize + interpolate x5 + texture + Lambert shading + flips)
  * fused with predict_pose_refine.py:54-56 (*255), h5_dataset.py:79-114 (/255, xyz - t, 1/radius, masks)
@@ -503,6 +509,8 @@ int fp_igemm_f16_fwd(const void* x /*dev*/, const fp_igemm_geom* x_geom /*host*/
  *   w_tiles[((bn * 9 * Cin / 32 + s) * 128 + r) * 32 + 8 * pc + e] = w[128 bn + r][tap * Cin + 32 cc + 8 * (pc ^ ((r >> 2) & 3)) + e].
  * N % 128 == 0, Cin % 32 == 0; w_tiles has the size of w and must not alias it.  No reference counterpart (a layout, not an operation). */
 int fp_pack_conv3x3_tiles_f16(const void* w /*dev*/, void* w_tiles /*dev*/, int N, int Cin, void* stream);
+/* bytes of LDS one workgroup of the shifted-window 3x3 convolution (512 x 128 tiles, every product layer) asks for at launch; host only */
+int fp_conv3x3_sw_lds_bytes(void);
 
 /* fp_igemm_f16_fwd for launches of a few dozen tiles -- the reference's tracking call (estimater.py:250-268: ONE hypothesis, so the
  * 512 -> 512 convolutions are 400 x 512 x 4608 products = 16 tiles on 256 CUs, each running its whole k loop): the k range is cut into
