@@ -636,6 +636,12 @@ bool fp_conv3x3_sw_applicable(const IgemmParams& p) {
   const IgemmGeom& o = p.out;
   const long long imgs = o.bsplit > 0 ? o.bsplit : p.M / g.HoWo, groups = o.bsplit > 0 ? (p.M / g.HoWo) / o.bsplit + 1 : 0;
   if (imgs * o.Hp * o.Wp * o.cstride + o.coff + groups * (long long)o.cgroup >= (1ll << 31)) return false;
+  // ... and 32-bit byte offsets from the buffer's start for the output rows and for the residual rows (ig_epilogue_spec, SLIM)
+  if (p.R) {
+    const IgemmGeom& r = p.res;
+    const long long rimgs = r.bsplit > 0 ? r.bsplit : p.M / g.HoWo, rgroups = r.bsplit > 0 ? (p.M / g.HoWo) / r.bsplit + 1 : 0;
+    if (rimgs * r.Hp * r.Wp * r.cstride + r.coff + rgroups * (long long)r.cgroup >= (1ll << 31)) return false;
+  }
   return sw_span(g, BM) <= (sw_variant(p) == 1 ? LS_PROWS : sw_prows(BM));
 }
 

@@ -384,6 +384,15 @@ static int ig_dispatch(IgemmParams& p, hipStream_t stream) {
 }
 
 
+// The epilogue's layer kind (IgemmParams.epi): the kinds the library compiles a body for, otherwise 0 = the generic body.  Those are the
+// layers of the two networks' plans: conv rounding + bias + ReLU, with or without BatchNorm, with or without a residual, and the token
+// layer's second output on top of a residual.  Everything else -- nn.Linear rounding, no bias, no ReLU -- is rare enough to stay generic.
+static int ig_epilogue_mode(const IgemmParams& p, int flags) {
+  if (flags & FP_IGEMM_EPILOGUE_GENERIC) return 0;
+  if (!p.round_acc || !p.bias || !p.relu || (p.Ype && !p.R)) return 0;
+  return IG_EPI_CONV | (p.bn_scale ? IG_EPI_BN : 0) | (p.R ? IG_EPI_RES : 0) | (p.Ype ? IG_EPI_PE : 0);
+}
+
 static int ig_build_params(const void* x, const fp_igemm_geom* x_geom, const void* w, void* y, const fp_igemm_geom* y_geom,
                            int M, int N, int Cin, int taps, const fp_igemm_epilogue* ep, IgemmParams& p, const char* who) {
   FP_REQUIRE(x && w && y && x_geom && y_geom, "%s: NULL tensor / geometry", who);
@@ -395,7 +404,7 @@ static int ig_build_params(const void* x, const fp_igemm_geom* x_geom, const voi
   FP_REQUIRE(!e.residual || e.r_geom, "%s: residual without geometry", who);
   FP_REQUIRE((e.bn_scale == nullptr) == (e.bn_shift == nullptr), "%s: bn_scale and bn_shift go together", who);
   FP_REQUIRE(!e.bn_scale || (e.flags & FP_IGEMM_ROUND_ACC), "%s: BatchNorm needs FP_IGEMM_ROUND_ACC (conv semantics)", who);
-  FP_REQUIRE((e.flags & ~(FP_IGEMM_RELU | FP_IGEMM_ROUND_ACC | FP_IGEMM_HAS_W_TILES | FP_IGEMM_MFMA_16X16X32 | FP_IGEMM_MFMA_32X32X16)) == 0,
+  FP_REQUIRE((e.flags & ~(FP_IGEMM_RELU | FP_IGEMM_ROUND_ACC | FP_IGEMM_HAS_W_TILES | FP_IGEMM_MFMA_16X16X32 | FP_IGEMM_MFMA_32X32X16 | FP_IGEMM_EPILOGUE_GENERIC)) == 0,
              "%s: unknown flags 0x%x", who, e.flags);
   FP_REQUIRE((e.flags & (FP_IGEMM_MFMA_16X16X32 | FP_IGEMM_MFMA_32X32X16)) != (FP_IGEMM_MFMA_16X16X32 | FP_IGEMM_MFMA_32X32X16),
              "%s: FP_IGEMM_MFMA_16X16X32 and FP_IGEMM_MFMA_32X32X16 exclude each other", who);
@@ -417,6 +426,8 @@ static int ig_build_params(const void* x, const fp_igemm_geom* x_geom, const voi
   p.mfma16 = (e.flags & FP_IGEMM_MFMA_32X32X16) ? 0 : ((e.flags & FP_IGEMM_MFMA_16X16X32) ? 1 : SW_DEFAULT_MFMA16);
   p.in = ig_geom(x_geom); p.out = ig_geom(y_geom); p.res = e.residual ? ig_geom(e.r_geom) : ig_geom(y_geom);
   p.slab = nullptr; p.nsplit = 0;
+  p.epi = ig_epilogue_mode(p, e.flags);
+  ig_fastdiv_init(p.pe_period, &p.pe_mul, &p.pe_shr);
   return FP_OK;
 }
 

@@ -58,9 +58,23 @@ struct IgemmParams {
                         // autocast: ATen adds the bias to the fp16 convolution output); 0: one rounding of acc + bias (nn.Linear)
   IgemmGeom in, out, res;
   int mfma16;           // k_conv_sw: main loop on v_mfma_f32_16x16x32_f16 (1) or v_mfma_f32_32x32x16_f16 (0); FP_IGEMM_MFMA_*
+  int epi;              // layer kind of the epilogue (IG_EPI_* below; igemm.hip ig_epilogue_mode): 0 = the generic body of igemm_epilogue.h
+  unsigned pe_mul, pe_shr;   // m / pe_period as ig_fastdiv (the layer-kind bodies; the generic body divides)
   float* slab;          // split-K only (fp_igemm_f16_splitk_fwd): fp32 partial accumulators in fragment order,
   int nsplit;           //   [split][tile][wave][(i, g, j)][lane] x float4; 0 = not split
 };
+
+// IgemmParams.epi: what the epilogue of a launch consists of, as a bit set.  Bit 0 marks a body compiled for exactly that set
+// (ig_epilogue_spec); the library compiles the six kinds of layer the two networks' plans launch -- IG_EPI_CONV, + BatchNorm, each
+// plain / with a residual / with a residual and the positional second output -- and every other combination runs mode 0.
+#define IG_EPI_SPEC 1
+#define IG_EPI_ROUND_ACC 2
+#define IG_EPI_BIAS 4
+#define IG_EPI_BN 8
+#define IG_EPI_RES 16
+#define IG_EPI_RELU 32
+#define IG_EPI_PE 64
+#define IG_EPI_CONV (IG_EPI_SPEC | IG_EPI_ROUND_ACC | IG_EPI_BIAS | IG_EPI_RELU)   // nn.Conv2d rounding, bias, ReLU
 
 __device__ __forceinline__ long long ig_row_off(const IgemmGeom& g, int m) {
   const int b = ig_fastdiv(m, g.mulP, g.shrP);

@@ -41,9 +41,221 @@ constexpr int ig_lds_main_slim(int stage_bytes) {
 // Acc: float16_[2][TM], the accumulators of v_mfma_f32_32x32x16_f16 (2 x TM tiles of 32 channels x 32 pixels), or float4_[4][2 * TM],
 // those of v_mfma_f32_16x16x32_f16 (4 x 2 TM tiles of 16 x 16, conv_sw.hip) -- the same 128 x 64 wave tile either way
 typedef float ig_float4 __attribute__((ext_vector_type(4)));
-template <int BM, int BN, int TM, int THREADS, int DBG, bool FULL, bool SLIM, typename Acc>
-__device__ __forceinline__ void ig_epilogue_body(const IgemmParams& p, Acc& acc, unsigned char* smem, int m0, int n0,
+// What a layer-kind body reads of IgemmParams, copied once in front of the dispatch.  Not for speed: the compiler forwards the reads of a by-value
+// kernel argument to the constant kernel-argument segment only up to a bounded number of reads; past it the whole block is copied to private
+// memory and every scalar of the main loop is read back from there (seen with the sixth body reading IgemmParams directly: an alloca and a memcpy
+// of the block in the IR, and "illegal VGPR to SGPR copy" at the main loop's scalar operands).  tests/test_igemm_epilogue_resources_host.py
+// holds every kernel of the family to a private segment of zero bytes.
+struct IgEpiArgs {
+  IgemmGeom out, res;
+  const _Float16* R;
+  _Float16* Y;
+  const float* pe;
+  _Float16* Ype;
+  int pe_period;
+  unsigned pe_mul, pe_shr;
+  int N;
+};
+
+// a kernel-argument pointer as the compiler can prove it wave-uniform (a buffer descriptor has to live in scalar registers)
+template <typename T>
+__device__ __forceinline__ T* ig_uniform_ptr(const T* ptr) {
+  const unsigned long long a = reinterpret_cast<unsigned long long>(ptr);
+  const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)a), hi = __builtin_amdgcn_readfirstlane((unsigned)(a >> 32));
+  return reinterpret_cast<T*>(((unsigned long long)hi << 32) | lo);
+}
+
+// max(v, 0) of eight halves as four v_pk_max_f16.  __builtin_elementwise_max is maxnum, which has to quiet a signalling NaN first: for a value
+// read back from LDS the compiler cannot know there is none and puts a v_pk_max_f16(v, v) in front of every max.  The E tile holds results of
+// conversions, adds and FMAs only, which are never signalling, and for every other input the instruction alone returns maxnum's bits
+// (a quiet NaN gives 0, -0 against +0 gives +0, whichever side it is on).
+__device__ __forceinline__ half8 ig_relu8(const half8& v) {
+  typedef _Float16 half2_ __attribute__((ext_vector_type(2)));
+  half8 r;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    const half2_ x = {v[2 * e], v[2 * e + 1]};
+    half2_ y;
+    asm("v_pk_max_f16 %0, %1, 0" : "=v"(y) : "v"(x));
+    r[2 * e] = y[0]; r[2 * e + 1] = y[1];
+  }
+  return r;
+}
+
+// ---- Layer-kind bodies (round 9): the epilogue of a WHOLE tile with the layer kind EPI (IG_EPI_* bits, igemm_common.h) fixed at compile
+// time.  The arithmetic per element and its order are the generic body's below, statement for statement -- the same roundings, the same
+// fmaf, IEEE half adds -- so a mode returns the generic body's bits; what goes is what the generic body executes per 4 values around
+// that arithmetic: the tests of round_acc / has_bn, the bias converted to fp16 again for every accumulator group, residual add and ReLU
+// computed and then selected, and addresses rebuilt that move by a compile-time constant:
+//  * E-tile write: row (lane & 15 or & 31) and the swizzled chunk depend on (lane, wn, i) only, so there is one base per channel quad i and
+//    the pixel tile j is a constant in the ds_write offset field (chunk = c0 ^ (m & 15), m & 15 == lane & 15 in every pixel tile);
+//  * store loop: iteration `it` handles row tid / CPR + it * RPI and chunk tid % CPR: RPI is a multiple of 16, so the swizzle term is
+//    the same in every iteration, and the E read and the row tables are one base + it * constant;
+//  * SLIM (k_conv_sw, whose launcher holds the output and the residual buffer below 2^31 elements): rows are stored, and residual rows
+//    loaded, through ONE buffer descriptor on the tensor's base with a 32-bit byte offset per lane, not through 64-bit lane addresses.
+//    (The descriptor sits on the buffer's start, not on the tile: offsets relative to the tile's first row can be negative under bsplit.)
+// A missing bias is not a mode (the generic body adds the +0 that ig_bias_to_lds leaves in LDS, which turns -0 into +0; dropping the add would not).
+template <int BM, int BN, int TM, int THREADS, bool SLIM, int EPI, typename Acc>
+__device__ __forceinline__ void ig_epilogue_spec(const IgEpiArgs& p, Acc& acc, unsigned char* smem, int m0, int n0,
                                                  int wm, int wn, int tid, int lane, const float* bias_lds) {
+  constexpr bool S16 = std::is_same<Acc, ig_float4[4][2 * TM]>::value;
+  static_assert(S16 || std::is_same<Acc, float16_[2][TM]>::value, "accumulator layout");
+  static_assert((EPI & IG_EPI_SPEC) && (EPI & IG_EPI_BIAS), "a layer kind with a bias");
+  constexpr bool ROUND_ACC = (EPI & IG_EPI_ROUND_ACC) != 0, HAS_BN = (EPI & IG_EPI_BN) != 0, RES = (EPI & IG_EPI_RES) != 0;
+  constexpr bool RELU = (EPI & IG_EPI_RELU) != 0, PE = (EPI & IG_EPI_PE) != 0;
+  static_assert(ROUND_ACC || !HAS_BN, "BatchNorm follows the conv rounding");
+  constexpr int CPR = BN / 8;                      // 16-byte chunks per row of the epilogue tile
+  constexpr int NIT = (BM * CPR) / THREADS;
+  constexpr int RPI = THREADS / CPR;               // rows per iteration of the store loop
+  static_assert(THREADS % CPR == 0 && RPI % 16 == 0 && NIT * RPI == BM, "the store loop's swizzle term must not depend on the iteration");
+  constexpr int ROWB = 2 * BN;                     // bytes per row of E
+  typedef float float4_ __attribute__((ext_vector_type(4)));
+  typedef _Float16 half2_ __attribute__((ext_vector_type(2)));
+  typedef unsigned uint4_ __attribute__((ext_vector_type(4)));
+  unsigned char* E = smem;
+  long long* rowY = reinterpret_cast<long long*>(smem + BM * ROWB);
+  long long* rowR = SLIM ? reinterpret_cast<long long*>(smem) : rowY + BM;
+  int* rowY32 = reinterpret_cast<int*>(smem + BM * ROWB);           // SLIM: in place of rowY
+  const long long baseY = SLIM ? ig_row_off(p.out, m0) + n0 : 0;
+  IG_CLK(te0);
+  for (int r = tid; r < BM; r += THREADS) {
+    const int m = m0 + r;                          // < M: a whole tile
+    if constexpr (SLIM) rowY32[r] = (int)(ig_row_off(p.out, m) + n0 - baseY);
+    else rowY[r] = ig_row_off(p.out, m) + n0;
+    if constexpr (RES) rowR[r] = ig_row_off(p.res, m) + n0;
+  }
+  __syncthreads();
+  IG_CLK(te1);
+  const int ml0 = tid / CPR, ch = tid % CPR;       // iteration `it` of this thread: row ml0 + it * RPI, chunk ch
+  // The residual rows are requested before the transposition: their HBM latency overlaps it
+  half8 rv[RES ? NIT : 1];
+  if constexpr (RES) {
+    if constexpr (SLIM) {
+      const __amdgpu_buffer_rsrc_t rsR = __builtin_amdgcn_make_buffer_rsrc(ig_uniform_ptr(p.R), 0, -1, 0x00020000);
+      const int* rR = reinterpret_cast<const int*>(rowR + ml0);    // the low words: offsets below 2^31 elements
+#pragma unroll
+      for (int it = 0; it < NIT; ++it)
+        rv[it] = __builtin_bit_cast(half8, __builtin_amdgcn_raw_buffer_load_b128(rsR, (int)(((unsigned)rR[it * RPI * 2] + ch * 8) << 1), 0, 0));
+      // rowR sits in the E tile: every wave has read it (its loads are issued) before any wave writes E.  A bare barrier: __syncthreads()
+      // would also wait for the residual rows themselves, whose latency the transposition is there to cover
+      __builtin_amdgcn_sched_barrier(0);
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      __builtin_amdgcn_s_barrier();
+      __builtin_amdgcn_sched_barrier(0);
+    } else {
+      const long long* rR = rowR + ml0;
+#pragma unroll
+      for (int it = 0; it < NIT; ++it) rv[it] = *reinterpret_cast<const half8*>(p.R + rR[it * RPI] + ch * 8);
+    }
+  }
+  IG_CLK(te2);
+  // per-channel values of 4 consecutive channels nl .. nl + 3 (LDS broadcast reads), formed once per channel quad
+  struct Vecs { float4_ bv, sc, sh; half2_ b01, b23; };
+  auto vecs = [&](int nl) {
+    Vecs c;
+    c.bv = *reinterpret_cast<const float4_*>(bias_lds + nl);
+    c.b01 = half2_{(_Float16)c.bv[0], (_Float16)c.bv[1]};
+    c.b23 = half2_{(_Float16)c.bv[2], (_Float16)c.bv[3]};
+    if constexpr (HAS_BN) {
+      c.sc = *reinterpret_cast<const float4_*>(bias_lds + IG_VEC_FLOATS + nl);
+      c.sh = *reinterpret_cast<const float4_*>(bias_lds + 2 * IG_VEC_FLOATS + nl);
+    }
+    return c;
+  };
+  // accumulators of those 4 channels of one pixel -> the policy's roundings -> E tile (the generic body's put4 has the why)
+  auto put4 = [&](unsigned char* dst, float a0, float a1, float a2, float a3, const Vecs& c) {
+    half4 v;
+    if constexpr (ROUND_ACC) {
+      half2_ t01 = {(_Float16)a0, (_Float16)a1};
+      half2_ t23 = {(_Float16)a2, (_Float16)a3};
+      t01 = t01 + c.b01;
+      t23 = t23 + c.b23;
+      if constexpr (HAS_BN) {
+        v[0] = (_Float16)fmaf((float)t01[0], c.sc[0], c.sh[0]);
+        v[1] = (_Float16)fmaf((float)t01[1], c.sc[1], c.sh[1]);
+        v[2] = (_Float16)fmaf((float)t23[0], c.sc[2], c.sh[2]);
+        v[3] = (_Float16)fmaf((float)t23[1], c.sc[3], c.sh[3]);
+      } else {
+        v[0] = t01[0]; v[1] = t01[1]; v[2] = t23[0]; v[3] = t23[1];
+      }
+    } else {
+      v[0] = (_Float16)(a0 + c.bv[0]); v[1] = (_Float16)(a1 + c.bv[1]); v[2] = (_Float16)(a2 + c.bv[2]); v[3] = (_Float16)(a3 + c.bv[3]);
+    }
+    *reinterpret_cast<half4*>(dst) = v;
+  };
+  const int r15 = lane & 15;                       // == m & 15 of the lane's row in every pixel tile
+  if constexpr (S16) {
+    // 16x16x32: lane holds pixel (lane & 15) and channels 4 * sigma(lane >> 4) + {0..3} of a 16 x 16 tile, sigma = (0, 2, 3, 1)
+    const int quad = (0x1320 >> (4 * (lane >> 4))) & 3;
+    unsigned char* Erow = E + (wm * (32 * TM) + r15) * ROWB + ((quad & 1) << 3);
+    const int cx = (wn * 8 + (quad >> 1)) ^ r15;   // chunk of channel quad i: (wn * 8 + 2 i + (quad >> 1)) ^ r15 = cx ^ 2 i
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const Vecs c = vecs(wn * 64 + i * 16 + 4 * quad);
+      unsigned char* Ei = Erow + ((cx ^ (2 * i)) << 4);
+#pragma unroll
+      for (int j = 0; j < 2 * TM; ++j) put4(Ei + j * (16 * ROWB), acc[i][j][0], acc[i][j][1], acc[i][j][2], acc[i][j][3], c);
+    }
+  } else {
+    // 32x32x16: lane holds pixel (lane & 31), channels 8g + 4 * (lane >> 5) + {0..3} of a 32 x 32 tile, g = reg >> 2
+    unsigned char* Erow = E + (wm * (32 * TM) + (lane & 31)) * ROWB + ((lane >> 5) << 3);
+    const int cx = (wn * 8) ^ r15;                 // chunk of (i, g): (wn * 8 + 4 i + g) ^ r15 = cx ^ (4 i + g)
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        const Vecs c = vecs(wn * 64 + i * 32 + 8 * g + 4 * (lane >> 5));
+        unsigned char* Ei = Erow + ((cx ^ (4 * i + g)) << 4);
+#pragma unroll
+        for (int j = 0; j < TM; ++j)
+          put4(Ei + j * (32 * ROWB), acc[i][j][g * 4 + 0], acc[i][j][g * 4 + 1], acc[i][j][g * 4 + 2], acc[i][j][g * 4 + 3], c);
+      }
+    }
+  }
+  __syncthreads();
+  IG_CLK(te3);
+  const unsigned char* Erd = E + ml0 * ROWB + ((ch ^ (ml0 & 15)) << 4);
+  const __amdgpu_buffer_rsrc_t rsY = __builtin_amdgcn_make_buffer_rsrc(ig_uniform_ptr(p.Y), 0, -1, 0x00020000);   // SLIM only
+  const unsigned cbY = ((unsigned)baseY + ch * 8) << 1;      // SLIM: byte offset of the lane's chunk in the tile's first row (below 2^32)
+#pragma unroll
+  for (int it = 0; it < NIT; ++it) {
+    half8 v = *reinterpret_cast<const half8*>(Erd + it * (RPI * ROWB));
+    if constexpr (RES) v = v + rv[it];             // IEEE half add == the fp32 add of two halves rounded once
+    if constexpr (RELU) v = ig_relu8(v);
+    if constexpr (SLIM) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(uint4_, v), rsY, (int)(cbY + ((unsigned)rowY32[ml0 + it * RPI] << 1)), 0, 0);
+    else *reinterpret_cast<half8*>(p.Y + rowY[ml0 + it * RPI] + ch * 8) = v;
+    if constexpr (PE) {                            // tokens + positional table, rounded for the in_proj GEMM
+      const int m = m0 + ml0 + it * RPI;
+      const int mp = m - ig_fastdiv(m, p.pe_mul, p.pe_shr) * p.pe_period;   // m % pe_period
+      const float* per = p.pe + (size_t)mp * p.N + n0 + ch * 8;
+      const float4_ e0 = *reinterpret_cast<const float4_*>(per), e1 = *reinterpret_cast<const float4_*>(per + 4);
+      half8 w;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) { w[e] = (_Float16)((float)v[e] + e0[e]); w[4 + e] = (_Float16)((float)v[4 + e] + e1[e]); }
+      *reinterpret_cast<half8*>(p.Ype + (size_t)m * p.N + n0 + ch * 8) = w;
+      // one row at a time: batched over the 16 iterations, the table rows (8 registers each) on top of the residual rows take k_conv_sw past
+      // the 224 registers it is held to (tests/test_conv_sw_resources_host.py); one launch per network and step has this body
+      __builtin_amdgcn_sched_barrier(0);
+    }
+  }
+#ifdef FP_PROFILE_BUILD
+  IG_CLK(te4);
+  if (tid == 0) {
+    atomicAdd(&ig_epi_dbg[0], te1 - te0); atomicAdd(&ig_epi_dbg[1], te2 - te1); atomicAdd(&ig_epi_dbg[2], te3 - te2);
+    atomicAdd(&ig_epi_dbg[3], te4 - te3); atomicAdd(&ig_epi_dbg[4], 1ull);
+  }
+#endif
+}
+// EPI: 0 = the generic body below, which reads the layer kind from IgemmParams at run time (any combination; the A/B arm of
+// FP_IGEMM_EPILOGUE_GENERIC); otherwise one of the IG_EPI_* layer kinds of ig_epilogue_spec, FULL tiles only.
+template <int BM, int BN, int TM, int THREADS, int DBG, bool FULL, bool SLIM, int EPI = 0, typename Acc, typename P>
+__device__ __forceinline__ void ig_epilogue_body(const P& p, Acc& acc, unsigned char* smem, int m0, int n0,
+                                                 int wm, int wn, int tid, int lane, const float* bias_lds) {
+  if constexpr (EPI != 0) {
+    static_assert(FULL && std::is_same<P, IgEpiArgs>::value, "the layer-kind bodies take whole tiles and their own argument block");
+    ig_epilogue_spec<BM, BN, TM, THREADS, SLIM, EPI>(p, acc, smem, m0, n0, wm, wn, tid, lane, bias_lds);
+  } else {   // the generic body, line for line as before the layer kinds (and left at its indentation)
+  static_assert(std::is_same<P, IgemmParams>::value, "the generic body reads IgemmParams");
   constexpr bool S16 = std::is_same<Acc, ig_float4[4][2 * TM]>::value;
   static_assert(S16 || std::is_same<Acc, float16_[2][TM]>::value, "accumulator layout");
   constexpr int CPR = BN / 8;                      // 16-byte chunks per row of the epilogue tile
@@ -191,12 +403,30 @@ __device__ __forceinline__ void ig_epilogue_body(const IgemmParams& p, Acc& acc,
     atomicAdd(&ig_epi_dbg[3], te4 - te3); atomicAdd(&ig_epi_dbg[4], 1ull);
   }
 #endif
+  }
 }
 
 template <int BM, int BN, int TM, int THREADS, int DBG = 0, bool SLIM = false, typename Acc>
 __device__ __forceinline__ void ig_epilogue(const IgemmParams& p, Acc& acc, unsigned char* smem, int m0, int n0,
                                             int wm, int wn, int tid, int lane, const float* bias_lds) {
-  if (m0 + BM <= p.M) ig_epilogue_body<BM, BN, TM, THREADS, DBG, true, SLIM>(p, acc, smem, m0, n0, wm, wn, tid, lane, bias_lds);
+  if (m0 + BM <= p.M) {
+    if constexpr (DBG == 0) {
+      // p.epi is a kernel argument: a scalar branch, the same for every wave of the launch (igemm.hip picks it: ig_epilogue_mode)
+#define IG_EPI_CASE(E) case E: ig_epilogue_body<BM, BN, TM, THREADS, DBG, true, SLIM, E>(q, acc, smem, m0, n0, wm, wn, tid, lane, bias_lds); return
+      const IgEpiArgs q = {p.out, p.res, p.R, p.Y, p.pe, p.Ype, p.pe_period, p.pe_mul, p.pe_shr, p.N};
+      switch (p.epi) {
+        IG_EPI_CASE(IG_EPI_CONV);
+        IG_EPI_CASE(IG_EPI_CONV | IG_EPI_RES);
+        IG_EPI_CASE(IG_EPI_CONV | IG_EPI_RES | IG_EPI_PE);
+        IG_EPI_CASE(IG_EPI_CONV | IG_EPI_BN);
+        IG_EPI_CASE(IG_EPI_CONV | IG_EPI_BN | IG_EPI_RES);
+        IG_EPI_CASE(IG_EPI_CONV | IG_EPI_BN | IG_EPI_RES | IG_EPI_PE);
+        default: break;
+      }
+#undef IG_EPI_CASE
+    }
+    ig_epilogue_body<BM, BN, TM, THREADS, DBG, true, SLIM>(p, acc, smem, m0, n0, wm, wn, tid, lane, bias_lds);
+  }
   else ig_epilogue_body<BM, BN, TM, THREADS, DBG, false, SLIM>(p, acc, smem, m0, n0, wm, wn, tid, lane, bias_lds);
 }
 // Kernel entry, BEFORE the first operand stage is requested: wave 0 sends the tile's bias straight to LDS with one

@@ -80,6 +80,10 @@ FUSED_TAIL = True
 # goes back to v_mfma_f32_32x32x16_f16.  The same products and rounding points; gated as equal up to summation-order flips
 # (tests/test_gpu_conv_sw16.py), measured bit-identical on the MI355X.  Read by ops.igemm_f16 at every call.  Why: DESIGN.md 3.2 / 8.1 (the clock the chip holds).
 CONV_MFMA_16X16X32 = True
+# round 9: fp_igemm_f16_fwd runs the epilogue body compiled for the launch's layer kind (csrc/igemm_epilogue.h ig_epilogue_spec);
+# overrides(SPECIALIZED_EPILOGUE=False) sets FP_IGEMM_EPILOGUE_GENERIC, the one body that reads the kind at run time.  The same arithmetic in
+# the same order: the same bits (tests/test_gpu_igemm_epilogue_modes.py).  Read by ops.igemm_f16 at every call.
+SPECIALIZED_EPILOGUE = True
 
 
 def _conv_backend():
@@ -223,7 +227,7 @@ SPLITK_TARGET_WGS = 384        # (tile, piece) workgroups a launch should have: 
 # the hard ceiling of both thresholds: overlap.SubBatches' default min_rows (a call of >= 2 x 32 hypotheses is split into sub-batches)
 SMALL_CALL_CEILING = 31
 
-_SWITCHES = ("FUSED_OUT_PROJ_LN", "FUSED_FFN", "ROWS_QKV", "PACKED_CONV_TILES", "MERGED_HEAD_QKV", "FUSED_TAIL", "CONV_MFMA_16X16X32", "SPLITK_MAX_HYPS", "HEADS_TWO_STREAMS_MAX_HYPS")
+_SWITCHES = ("FUSED_OUT_PROJ_LN", "FUSED_FFN", "ROWS_QKV", "PACKED_CONV_TILES", "MERGED_HEAD_QKV", "FUSED_TAIL", "CONV_MFMA_16X16X32", "SPECIALIZED_EPILOGUE", "SPLITK_MAX_HYPS", "HEADS_TWO_STREAMS_MAX_HYPS")
 
 
 @contextlib.contextmanager

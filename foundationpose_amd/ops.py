@@ -1196,6 +1196,7 @@ IGEMM_ROUND_ACC = 2
 IGEMM_HAS_W_TILES = 4
 IGEMM_MFMA_16X16X32 = 16
 IGEMM_MFMA_32X32X16 = 32
+IGEMM_EPILOGUE_GENERIC = 64
 
 
 class IgemmEpilogue(C.Structure):
@@ -1235,12 +1236,13 @@ def igemm_f16(x, x_geom, w, bias, y, y_geom, M, N, Cin, taps, relu=False, residu
     otherwise nn.Linear (one rounding of accumulator + bias).  pe (S, N) f32 + y_pe (M, N) fp16: second output
     f16(f32(y) + pe[m % S]).  All tensors are device buffers owned by the caller (y is written in place and returned)."""
     x = _dev(x, torch.float16, "x"); w = _dev(w, torch.float16, "w"); y = _dev(y, torch.float16, "y")
+    from . import engine                   # engine imports this module
     if mfma16 is None:
-        from . import engine               # engine imports this module
         mfma16 = engine.CONV_MFMA_16X16X32
     ep = _igemm_epilogue(bias, residual, r_geom, bn_scale, bn_shift, pe, y_pe,
                          (IGEMM_RELU if relu else 0) | (IGEMM_ROUND_ACC if conv_rounding else 0) | IGEMM_HAS_W_TILES |
-                         (IGEMM_MFMA_16X16X32 if mfma16 else IGEMM_MFMA_32X32X16), w_tiles)
+                         (IGEMM_MFMA_16X16X32 if mfma16 else IGEMM_MFMA_32X32X16) |
+                         (0 if engine.SPECIALIZED_EPILOGUE else IGEMM_EPILOGUE_GENERIC), w_tiles)
     st = _lib.lib().fp_igemm_f16_fwd(_ptr(x), C.byref(x_geom), _ptr(w), _ptr(y), C.byref(y_geom), int(M), int(N), int(Cin),
                                      int(taps), C.byref(ep), _stream(x))
     _lib.check(st, "fp_igemm_f16_fwd")

@@ -82,8 +82,9 @@ const char* fp_last_error(void);
  *   221 -> 222: + FP_IGEMM_MFMA_16X16X32 / FP_IGEMM_MFMA_32X32X16 (additions only; an older library refuses the bits as unknown flags).
  *   222 -> 223: + fp_texture_bake (addition only): a texture atlas for a fused mesh from its posed RGB-D reference views.
  *   223 -> 224: + fp_raster_lds_bytes, fp_conv3x3_sw_lds_bytes (additions only): the LDS a workgroup of the rasteriser and of the
- *               3x3 convolution asks for at launch. */
-#define FP_AMD_ABI_VERSION 224
+ *               3x3 convolution asks for at launch.
+ *   224 -> 225: + FP_IGEMM_EPILOGUE_GENERIC (addition only; an older library refuses the bit as an unknown flag). */
+#define FP_AMD_ABI_VERSION 225
 int fp_version(void);
 
 /* Utils.py:104-130 make_mesh_tensors: records caller-owned device tensors.
@@ -476,6 +477,13 @@ typedef struct {
 #define FP_IGEMM_MFMA_16X16X32 16
 #define FP_IGEMM_MFMA_32X32X16 32
 
+/* fp_igemm_f16_fwd compiles the epilogue of the layer kinds the networks launch (conv rounding + bias + ReLU, with or without BatchNorm,
+ * residual, positional second output) as bodies of their own, chosen per launch from the members below; every other combination runs one
+ * generic body that reads them at run time.  With this bit a launch runs the generic body whatever its kind: the same arithmetic in the
+ * same order, hence the same bits -- the A/B arm of that specialisation (tests/test_gpu_igemm_epilogue_modes.py) and nothing a product
+ * call needs.  Ignored by fp_igemm_f16_splitk_fwd, whose epilogue is a kernel of its own. */
+#define FP_IGEMM_EPILOGUE_GENERIC 64
+
 /* What fp_igemm_f16_fwd does with the fp32 accumulators (all members optional; NULL struct = plain fp16 store) */
 typedef struct {
   const float* bias;           /* dev (N) f32 | NULL; for conv semantics fp16-representable values */
@@ -483,7 +491,7 @@ typedef struct {
   const float* bn_shift;
   const void* residual;        /* dev fp16 | NULL: `out += identity` (network_modules.py:107), rounded to fp16 */
   const fp_igemm_geom* r_geom; /* host: addressing of the residual */
-  int flags;                   /* FP_IGEMM_RELU | FP_IGEMM_ROUND_ACC | FP_IGEMM_HAS_W_TILES | FP_IGEMM_MFMA_* */
+  int flags;                   /* FP_IGEMM_RELU | FP_IGEMM_ROUND_ACC | FP_IGEMM_HAS_W_TILES | FP_IGEMM_MFMA_* | FP_IGEMM_EPILOGUE_GENERIC */
   const float* pe;             /* dev (pe_period, N) f32 | NULL: second output y_pe[m, n] = f16(f32(y[m, n]) + pe[m % pe_period, n]), */
   int pe_period;               /*   the PositionalEmbedding add of network_modules.py:133-137 fused into the last conv of the */
   void* y_pe;                  /*   encoder; y_pe is a plain (M, N) fp16 matrix */
