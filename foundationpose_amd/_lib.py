@@ -10,7 +10,7 @@ import torch  # noqa: F401  (must precede CDLL: shares the HIP runtime with PyTo
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("FP_AMD_LIB") or os.path.join(_HERE, "csrc", "libfp_amd.so")   # FP_AMD_LIB: A/B builds
-ABI_VERSION = 225    # = FP_AMD_ABI_VERSION of include/fp_amd.h (tests/test_abi.py keeps the two in step)
+ABI_VERSION = 226    # = FP_AMD_ABI_VERSION of include/fp_amd.h (tests/test_abi.py keeps the two in step)
 _lib = None
 
 vp, ci, cf, cd, sz = C.c_void_p, C.c_int, C.c_float, C.c_double, C.c_size_t
@@ -38,6 +38,8 @@ SIGNATURES = {
     "fp_warp_crops_views": (ci, [vp, vp, vp, vp, vp, vp, ci, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, ci, vp, vp]),
     "fp_pose_update_views": (ci, [vp, vp, vp, ci, ci, vp, cf, vp, vp, ci, ci, vp, vp, vp, ci, vp, vp, ci, vp, cf, vp]),
     "fp_depth_agreement": (ci, [vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, cf, vp, vp]),
+    "fp_icp_workspace_bytes": (sz, [ci, ci, ci]),
+    "fp_icp_point_plane": (ci, [vp, vp, vp, vp, vp, ci, ci, ci, vp, ci, ci, ci, cf, cd, ci, vp, vp, vp, sz, vp]),
     "fp_pose_errors_workspace_bytes": (sz, [ci, ci, ci]),
     "fp_pose_errors": (ci, [vp, ci, vp, ci, vp, vp, vp, ci, ci, ci, vp, vp, sz, vp]),
     "fp_vsd_counts": (ci, [vp, vp, vp, ci, ci, ci, ci, vp, vp, ci, ci, ci, ci, cf, vp, ci, vp, vp]),

@@ -79,6 +79,9 @@ class Scene:
     def depth_agreement(self, depth_crops, xyz_map, tf_to_crops, tol, out=None):
         return ops.depth_agreement(depth_crops, xyz_map, tf_to_crops, tol, views=self.views, out=out)
 
+    def icp_point_plane(self, xyz_crops, normal_crops, xyz_map, tf_to_crops, poses, max_dist, **kw):
+        return ops.icp_point_plane(xyz_crops, normal_crops, xyz_map, tf_to_crops, poses, max_dist, views=self.views, **kw)
+
 
 def crop_stage(scene, poses, rgb, xyz_map, depth, mode, crop_ratio, out_hw, xyz_thr, normalize_xyz, AB, workspace=None, adjust_bbox=None,
                warp_rows=None, chunk=None, window_hw=None):

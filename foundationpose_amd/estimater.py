@@ -54,12 +54,15 @@ class FoundationPose:
         (reconstruct.reconstruct_object: rgbs (V,H,W,3), depths (V,H,W) metres, masks (V,H,W), ob_in_cams (V,4,4), Ks (V,3,3) or one
         (3,3); voxel=None: the longest side gets 128 voxels; reconstruct_args: its further keywords), then the constructor as for any
         other mesh (kwargs: scorer, refiner, symmetry_tfs, device, ...).  Poses come out in the frame of ob_in_cams; reset_object
-        centres the mesh as usual (model_center)."""
+        centres the mesh as usual (model_center).  With reconstruct_args={"refine_poses": R} the view poses are polished against the
+        fused mesh first; the estimator keeps them as ref_ob_in_cams ((V,4,4) float32; None without)."""
         from .reconstruct import reconstruct_object
         args = dict(reconstruct_args or {})
         args.setdefault("device", kwargs.get("device", "cuda"))
         mesh, tensors = reconstruct_object(rgbs, depths, masks, ob_in_cams, Ks, voxel=voxel, **args)
-        return cls(model_pts=mesh.vertices, model_normals=mesh.vertex_normals, mesh=mesh, mesh_tensors=tensors, **kwargs)
+        est = cls(model_pts=mesh.vertices, model_normals=mesh.vertex_normals, mesh=mesh, mesh_tensors=tensors, **kwargs)
+        est.ref_ob_in_cams = getattr(mesh, "ob_in_cams", None)
+        return est
 
     # ------------------------------------------------------------------ estimater.py:44-78
     def reset_object(self, model_pts, model_normals, symmetry_tfs=None, mesh=None, mesh_tensors=None):
@@ -350,6 +353,14 @@ class FoundationPose:
             self.depth_agreement = extra["depth_agreement"] = ops.DepthAgreement.rows(table)[0]
         return (pose @ self.get_tf_to_centered_mesh()).data.cpu().numpy().reshape(4, 4)
 
+    def polish(self, depth, K, iterations=3, max_dist=0.02, extra=None):
+        """Polish pose_last against the observed depth by point-to-plane ICP (depth_polish of this one estimator; not in the
+        reference): -> the pose as track_one returns it; with a dict `extra`, extra["icp"] = the last iteration's ops.IcpStep."""
+        step = depth_polish([self], depth, K, iterations=iterations, max_dist=max_dist)[0]
+        if extra is not None:
+            extra["icp"] = step
+        return (self.pose_last.reshape(4, 4) @ self.get_tf_to_centered_mesh()).data.cpu().numpy().reshape(4, 4)
+
     track = track_one  # the north-star calls it track(); the reference method is track_one (SURVEY.md 0)
 
 
@@ -528,6 +539,40 @@ def depth_agreement(estimators, depths, Ks, views=None, tol=0.01):
         P = torch.stack([e.pose_last.reshape(4, 4).to(dev, torch.float32) for e in ests]).contiguous()
         table = refiner.depth_check(P, xyz, Scene(mset, diam, K, H, W, len(ests), obj=obj, views=vt, who="depth_agreement"), t)
     return ops.DepthAgreement.rows(table)
+
+
+def depth_polish(estimators, depths, Ks, views=None, iterations=3, max_dist=0.02):
+    """Polish each estimator's current pose_last against the observed depth by `iterations` steps of point-to-plane ICP
+    (PoseRefinePredictor.depth_polish; include/fp_amd.h fp_icp_point_plane): estimator k's pose on frame views[k] of depths (intrinsics
+    Ks[views[k]]), or with views=None on the one frame `depths` with the one K `Ks`.  The argument rules, the depth ingest and the crop
+    windows are those of depth_agreement.  Sets each estimator's pose_last (a pose whose step could not be solved stays as it was) and
+    -> [ops.IcpStep] of the last iteration per estimator (one device-to-host copy).  The trackers and their graphs are not touched."""
+    ops._check_icp(max_dist, 1e-3, 64, "depth_polish")
+    if isinstance(iterations, bool) or not isinstance(iterations, (int, np.integer)) or int(iterations) < 1:
+        raise ValueError(f"depth_polish: iterations must be an int >= 1, got {iterations!r}")
+    ests, refiner, _ = _check_estimators("depth_polish", estimators, registered=True)
+    if views is not None:
+        views, _, depths, Ks, (H, W) = _check_views("depth_polish", len(ests), views, depths, Ks)
+    dev = ests[0].device
+    with torch.inference_mode():
+        if views is None:
+            d = torch.as_tensor(depths, device=dev, dtype=torch.float).contiguous()
+            xyz = ops.ingest_frame(d, Ks)
+            H, W = int(d.shape[0]), int(d.shape[1])
+            K, vt = Ks, None
+        else:
+            stack = stack_frames(depths, dev, torch.float)
+            K, vt = None, ops.Views(Ks, views, dev)
+            xyz = ops.ingest_frames(stack, vt, f64_internal=False)
+        mset, diam = _object_tables(refiner, ests)
+        obj = torch.arange(len(ests), dtype=torch.int32, device=dev)
+        P = torch.stack([e.pose_last.reshape(4, 4).to(dev, torch.float32) for e in ests]).contiguous()
+        out, system = refiner.depth_polish(P, xyz, Scene(mset, diam, K, H, W, len(ests), obj=obj, views=vt, who="depth_polish"),
+                                           iterations=int(iterations), max_dist=max_dist)
+        out = out.clone()
+    for k, e in enumerate(ests):
+        e.pose_last = out[k:k + 1]
+    return ops.IcpStep.rows(system)
 
 
 def translation_from_stats(K, box, n, lo, hi):

@@ -601,6 +601,112 @@ class DepthAgreement(NamedTuple):
         return [cls(*(int(x) for x in r)) for r in np.asarray(a, dtype=np.int64).reshape(-1, 4)]
 
 
+def _check_icp(max_dist, damping, min_pairs, what):
+    """the numbers of an ICP step: max_dist (metres) and damping finite and >= 0, min_pairs an int >= 6; refused with ValueError
+    before any device work"""
+    vals = []
+    for name, v in (("max_dist", max_dist), ("damping", damping)):
+        try:
+            f = float(v)
+        except (TypeError, ValueError):
+            raise ValueError(f"{what}: {name} must be a number, got {v!r}") from None
+        if not (np.isfinite(f) and f >= 0.0):
+            raise ValueError(f"{what}: {name} must be finite and >= 0, got {v!r}")
+        vals.append(f)
+    if isinstance(min_pairs, bool) or not isinstance(min_pairs, (int, np.integer)) or int(min_pairs) < 6:
+        raise ValueError(f"{what}: min_pairs must be an int >= 6 (the unknowns of a step), got {min_pairs!r}")
+    return vals[0], vals[1], int(min_pairs)
+
+
+def icp_workspace(N, oh, ow, device):
+    """the workspace of icp_point_plane for N hypotheses at (oh, ow) crops (a captured graph owns its buffers)"""
+    nbytes = int(_lib.lib().fp_icp_workspace_bytes(int(N), int(oh), int(ow)))
+    return torch.empty(((nbytes + 7) // 8,), dtype=torch.float64, device=device)
+
+
+def icp_point_plane(xyz_crops, normal_crops, xyz_map, tf_to_crops, poses, max_dist, damping=1e-3, min_pairs=64, views=None,
+                    system=None, poses_out=None, workspace=None):
+    """fp_icp_point_plane: one Gauss-Newton step of point-to-plane ICP per hypothesis.  xyz_crops / normal_crops (N,oh,ow,3): the
+    render of the model at `poses` (N,4,4) through the crop windows tf_to_crops (N,3,3) -- render_crops(want=("xyz", "normal"),
+    normalize_xyz=False); xyz_map (H,W,3): the observed points, read through the same windows as depth_agreement reads them.  Pairs
+    farther apart than max_dist (metres) are dropped; damping scales diag(A); fewer than min_pairs pairs leave the pose as it is.
+    -> (poses_out (N,4,4) f32, system (N,40) f64) device tensors; IcpStep.rows reads `system` on the host (include/fp_amd.h has the
+    definition and the layout).  system / poses_out / workspace: caller-owned buffers ((N,40) float64; (N,4,4) float32, not
+    overlapping `poses`; icp_workspace) for a captured graph.  Several views: views = an ops.Views and xyz_map the (V,H,W,3) stack."""
+    md, dmp, mp = _check_icp(max_dist, damping, min_pairs, "icp_point_plane")
+    xc = _dev(xyz_crops, torch.float32, "xyz_crops")
+    nc = _dev(normal_crops, torch.float32, "normal_crops")
+    xm = _dev(xyz_map, torch.float32, "xyz_map")
+    tf = _dev(tf_to_crops, torch.float32, "tf_to_crops")
+    P = _dev(poses, torch.float32, "poses")
+    if xc.dim() != 4 or int(xc.shape[3]) != 3:
+        raise _lib.FpAmdError(f"icp_point_plane: xyz_crops must be (N,oh,ow,3), got {tuple(xc.shape)}")
+    N, oh, ow = (int(x) for x in xc.shape[:3])
+    if tuple(nc.shape) != tuple(xc.shape):
+        raise _lib.FpAmdError(f"icp_point_plane: normal_crops must be {tuple(xc.shape)} like xyz_crops, got {tuple(nc.shape)}")
+    if tuple(tf.shape[-2:]) != (3, 3) or tf.numel() != 9 * N:
+        raise _lib.FpAmdError(f"icp_point_plane: {N} crops but tf_to_crops of shape {tuple(tf.shape)}")
+    if tuple(P.shape) != (N, 4, 4):
+        raise _lib.FpAmdError(f"icp_point_plane: {N} crops but poses of shape {tuple(P.shape)}")
+    if views is not None:
+        vt = _views(views, "icp_point_plane", N)
+        if xm.dim() != 4 or int(xm.shape[0]) != vt.V or int(xm.shape[3]) != 3:
+            raise _lib.FpAmdError(f"icp_point_plane: views need a ({vt.V},H,W,3) xyz stack, got {tuple(xm.shape)}")
+        V, H, W = int(xm.shape[0]), int(xm.shape[1]), int(xm.shape[2])
+        vw = vt.dev
+    else:
+        if xm.dim() != 3 or int(xm.shape[2]) != 3:
+            raise _lib.FpAmdError(f"icp_point_plane: xyz_map must be (H,W,3), got {tuple(xm.shape)}")
+        V, H, W = 1, int(xm.shape[0]), int(xm.shape[1])
+        vw = None
+    if system is None:
+        system = torch.empty((N, 40), dtype=torch.float64, device=xc.device)
+    else:
+        system = _dev(system, torch.float64, "system")
+        if tuple(system.shape) != (N, 40):
+            raise _lib.FpAmdError(f"icp_point_plane: system must be ({N}, 40), got {tuple(system.shape)}")
+    if poses_out is None:
+        poses_out = torch.empty((N, 4, 4), dtype=torch.float32, device=xc.device)
+    else:
+        poses_out = _dev(poses_out, torch.float32, "poses_out")
+        if tuple(poses_out.shape) != (N, 4, 4):
+            raise _lib.FpAmdError(f"icp_point_plane: poses_out must be ({N}, 4, 4), got {tuple(poses_out.shape)}")
+        if _overlap(poses_out, P):
+            raise _lib.FpAmdError("icp_point_plane: poses_out must not overlap poses (there is no in-place update)")
+    need = int(_lib.lib().fp_icp_workspace_bytes(N, oh, ow))
+    if workspace is None:
+        workspace = icp_workspace(N, oh, ow, xc.device)
+    else:
+        if not (torch.is_tensor(workspace) and workspace.is_cuda and workspace.is_contiguous()):
+            raise _lib.FpAmdError("icp_point_plane: workspace must be a contiguous CUDA(HIP) tensor")
+        if workspace.numel() * workspace.element_size() < need:
+            raise _lib.FpAmdError(f"icp_point_plane: workspace of {workspace.numel() * workspace.element_size()} bytes, {need} needed "
+                                  f"(icp_workspace)")
+    _lib.check(_lib.lib().fp_icp_point_plane(_ptr(xc), _ptr(nc), _ptr(xm), _ptr(tf), _ptr(vw), V, H, W, _ptr(P), N, oh, ow, md, dmp, mp,
+                                             _ptr(system), _ptr(poses_out), _ptr(workspace),
+                                             workspace.numel() * workspace.element_size(), _stream(xc)), "fp_icp_point_plane")
+    return poses_out, system
+
+
+class IcpStep(NamedTuple):
+    """one row of icp_point_plane's `system` on the host: `pairs` the model / sensor point pairs the step was solved over, `rms` their
+    point-to-plane RMS BEFORE the step in metres (NaN without pairs), `status` 0 solved / 1 fewer than min_pairs pairs / 2 degenerate
+    (a pivot of the factorisation <= 0 or a non-finite pose), `twist` the step (w0, w1, w2, v0, v1, v2): rotation vector in radians
+    about the pose's origin and translation in metres, zeros unless status is 0."""
+    pairs: int
+    rms: float
+    status: int
+    twist: tuple
+
+    @classmethod
+    def rows(cls, table):
+        """[IcpStep] per row of a (N, 40) system (a device tensor: one device-to-host copy)"""
+        a = table.cpu().numpy() if torch.is_tensor(table) else np.asarray(table)
+        a = np.asarray(a, dtype=np.float64).reshape(-1, 40)
+        return [cls(int(r[28]), float(np.sqrt(r[27] / r[28])) if r[28] > 0 else float("nan"), int(r[29]),
+                    tuple(float(x) for x in r[30:36])) for r in a]
+
+
 _POSE_ERROR_FLAGS = {"add": 1, "adds": 2, "sym": 4}     # FP_ERR_ADD / FP_ERR_ADDS / FP_ERR_SYM (include/fp_amd.h)
 
 
@@ -1707,6 +1813,7 @@ replicate_segments = _timed("fp_replicate_segments_f16", replicate_segments,
 mask_depth_stats = _timed("fp_mask_depth_stats", mask_depth_stats)
 depth_agreement = _timed("fp_depth_agreement", depth_agreement)
 pose_errors = _timed("fp_pose_errors", pose_errors)
+icp_point_plane = _timed("fp_icp_point_plane", icp_point_plane)
 vsd_counts = _timed("fp_vsd_counts", vsd_counts)
 mspd = _timed("fp_mspd", mspd)
 layernorm_res = _timed("fp_layernorm_res_fwd", layernorm_res,

@@ -306,6 +306,29 @@ class PoseRefinePredictor:
         depth = scene.render_crops(poses, bbox2d, (oh, ow), xyz_thr=0.001, normalize_xyz=False, want=("depth",), workspace=workspace)["depth"]
         return scene.depth_agreement(depth, xyz_t, tf_to_crops, tol, out=out)
 
+    def depth_polish(self, poses, xyz_t, scene, iterations=3, max_dist=0.02, damping=1e-3, workspace=None):
+        """Polish the poses (N,4,4) against the observed xyz map by `iterations` Gauss-Newton steps of point-to-plane ICP
+        (ops.icp_point_plane; include/fp_amd.h has the definition), on the CURRENT stream.  Per iteration: the crop windows of the loop
+        at the current poses (crop_ratio, input_resize; every pose through its own window: the two-pose quirk is not applied), the
+        render's camera-frame xyz and normals there, and one step against xyz_t through the same windows.  The poses ping-pong between
+        two buffers of the call's own; `poses` is only read.  scene: the crops.Scene of these poses; workspace: the rasteriser scratch.
+        -> (poses (N,4,4), system (N,40) float64 of the LAST iteration: ops.IcpStep.rows reads it)."""
+        if isinstance(iterations, bool) or not isinstance(iterations, (int, np.integer)) or int(iterations) < 1:
+            raise ValueError(f"depth_polish: iterations must be an int >= 1, got {iterations!r}")
+        ops._check_icp(max_dist, damping, 64, "depth_polish")
+        oh, ow, _, _ = self._loop_constants()
+        N = int(poses.shape[0])
+        P = poses
+        buf = [torch.empty((N, 4, 4), dtype=torch.float32, device=poses.device) for _ in range(min(2, int(iterations)))]
+        system = torch.empty((N, 40), dtype=torch.float64, device=poses.device)
+        icp_ws = ops.icp_workspace(N, oh, ow, poses.device)
+        for it in range(int(iterations)):
+            tf_to_crops, bbox2d = scene.crop_windows(P, self.cfg["crop_ratio"], (ow, oh))
+            r = scene.render_crops(P, bbox2d, (oh, ow), xyz_thr=0.001, normalize_xyz=False, want=("xyz", "normal"), workspace=workspace)
+            P, _ = scene.icp_point_plane(r["xyz"], r["normal"], xyz_t, tf_to_crops, P, max_dist, damping=damping, system=system,
+                                         poses_out=buf[it % 2], workspace=icp_ws)
+        return P, system
+
     def refine_device(self, rgb_t, xyz_t, poses, K, H, W, mesh_handle, mesh_diameter, iteration, workspace=None,
                       shared_translation=False, obj=None, views=None):
         """The refine loop on device tensors only (predict_pose_refine.py:182-235).  No host round trip, no host-side

@@ -182,13 +182,61 @@ def _bounds(d, m, P, K, margin, min_depth, what):
     return box[:3] - margin, box[3:] + margin
 
 
+ICP_CROP = (160, 160)    # the crops refine_view_poses renders the mesh into, and their window's ratio to the mesh's sphere
+ICP_CROP_RATIO = 1.2
+
+
+def refine_view_poses(mesh_tensors, depths, masks, ob_in_cams, Ks, iterations=3, max_dist=0.01):
+    """Polish the poses of V reference views against a mesh of the object (a fused one: TsdfVolume.extract's mesh_tensors) by
+    `iterations` Gauss-Newton steps of point-to-plane ICP per view (ops.icp_point_plane, view v for row v of an ops.Views): per
+    iteration the crop windows around the object at the current poses, the mesh's camera-frame points and normals there, and one
+    step against the view's own depth -- masked, and back-projected unfiltered.  The windows hold the sphere about the frame's origin
+    that holds the mesh (the poses' frame need not be centred on it).  -> (poses (V,4,4) float32 device tensor, [ops.IcpStep] of the
+    last iteration).  A view whose step cannot be solved (too few pairs) keeps its pose.  A setup call (it synchronises)."""
+    what = "refine_view_poses"
+    if masks is None:
+        raise ValueError(f"{what}: masks are required")
+    if isinstance(iterations, bool) or not isinstance(iterations, (int, np.integer)) or int(iterations) < 1:
+        raise ValueError(f"{what}: iterations must be an int >= 1, got {iterations!r}")
+    ops._check_icp(max_dist, 1e-3, 64, what)
+    for k in ("pos", "faces", "vnormals"):
+        if k not in mesh_tensors:
+            raise ValueError(f"{what}: mesh_tensors has no '{k}'")
+    d, _, m, P, K = _views_in(None, depths, masks, ob_in_cams, Ks, mesh_tensors["pos"].device, what)
+    return _refine_views(mesh_tensors, d, m, P, K, int(iterations), max_dist)
+
+
+def _refine_views(t, d, m, P, K, iterations, max_dist):
+    """refine_view_poses of views that are on the device already"""
+    from .Utils import get_mesh_handle
+    dev = d.device
+    V, H, W = (int(x) for x in d.shape)
+    vt = ops.Views(list(K), np.arange(V), dev)
+    xyz = ops.depth_to_xyz_frames(torch.where(m != 0, d, torch.zeros_like(d)).contiguous(), vt)
+    mset = ops.MeshSet([get_mesh_handle(t)])
+    diam = ops.object_diameters([2.0 * float(t["pos"].norm(dim=1).max())], dev)
+    oh, ow = ICP_CROP
+    system = torch.empty((V, 40), dtype=torch.float64, device=dev)
+    ws = ops.icp_workspace(V, oh, ow, dev)
+    P = P.contiguous()
+    for _ in range(iterations):
+        tf, bb = ops.crop_windows(P, None, diam, ICP_CROP_RATIO, (ow, oh), views=vt)
+        r = ops.render_crops(mset, P, bb, None, H, W, (oh, ow), diam, normalize_xyz=False, want=("xyz", "normal"), views=vt)
+        P, _ = ops.icp_point_plane(r["xyz"], r["normal"], xyz, tf, P, max_dist, views=vt, system=system, workspace=ws)
+    return P, ops.IcpStep.rows(system)
+
+
 def reconstruct_object(rgbs, depths, masks, ob_in_cams, Ks, voxel=None, trunc=None, margin=None, min_weight=1, min_depth=0.001,
-                       longest=128, device="cuda", texture=None, texture_min_cos=0.2):
+                       longest=128, device="cuda", texture=None, texture_min_cos=0.2, refine_poses=0, refine_iterations=3,
+                       refine_max_dist=0.01):
     """V posed RGB-D reference views with masks -> (SimpleMesh, mesh_tensors) of the object, in the frame of the poses: the box of the
     masked depths (bounds_from_views) -> a TsdfVolume over it -> fuse -> extract.  voxel=None picks the pitch that gives the longest
     side `longest` voxels; margin defaults to three voxels around the observed points; trunc to four voxels.  texture=T (2..16) bakes a
     texture atlas of T x T texels a face from the same views onto the mesh (bake_texture with tol = two voxels): the mesh and the
-    tensors then carry the atlas in place of the vertex colours alone.  ValueError, naming the cause, when there are no views, the
+    tensors then carry the atlas in place of the vertex colours alone.  refine_poses=R (default 0: the poses are trusted as given): R
+    rounds of refine_view_poses of every view against the fused mesh (refine_iterations steps, pairs within refine_max_dist), each
+    followed by a fresh fusion of the same volume from the refined poses and a new extraction; the texture is baked with the refined
+    poses, and the mesh carries them as mesh.ob_in_cams ((V,4,4) float32).  ValueError, naming the cause, when there are no views, the
     masks are empty or no surface was found."""
     what = "reconstruct_object"
     n = len(depths) if depths is not None else 0
@@ -196,6 +244,8 @@ def reconstruct_object(rgbs, depths, masks, ob_in_cams, Ks, voxel=None, trunc=No
         raise ValueError(f"{what}: no views")
     if rgbs is None or masks is None:
         raise ValueError(f"{what}: rgbs and masks are required")
+    if isinstance(refine_poses, bool) or not isinstance(refine_poses, (int, np.integer)) or int(refine_poses) < 0:
+        raise ValueError(f"{what}: refine_poses must be an int >= 0, got {refine_poses!r}")
     if texture is not None:
         ops.texture_atlas_layout(1, texture)          # a block side outside 2..16 is refused before the fusion
     d, c, m, P, K = _views_in(rgbs, depths, masks, ob_in_cams, Ks, device, what)
@@ -213,6 +263,16 @@ def reconstruct_object(rgbs, depths, masks, ob_in_cams, Ks, voxel=None, trunc=No
         mesh, tensors = vol.extract(min_weight)
     except ValueError as e:
         raise ValueError(f"{what}: no surface found in the {n} views ({e})") from None
-    if texture is None:
-        return mesh, tensors
-    return _bake(tensors, d, c, m, P, K, int(texture), 2.0 * voxel, texture_min_cos, min_depth)
+    for _ in range(int(refine_poses)):
+        P, _ = _refine_views(tensors, d, m, P, K, int(refine_iterations), refine_max_dist)
+        vol.reset()
+        vol._integrate(d, c, m, P, K)
+        try:
+            mesh, tensors = vol.extract(min_weight)
+        except ValueError as e:
+            raise ValueError(f"{what}: no surface found in the {n} views after refining their poses ({e})") from None
+    if texture is not None:
+        mesh, tensors = _bake(tensors, d, c, m, P, K, int(texture), 2.0 * voxel, texture_min_cos, min_depth)
+    if int(refine_poses) > 0:
+        mesh.ob_in_cams = P.cpu().numpy()
+    return mesh, tensors

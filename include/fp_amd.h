@@ -83,8 +83,10 @@ const char* fp_last_error(void);
  *   222 -> 223: + fp_texture_bake (addition only): a texture atlas for a fused mesh from its posed RGB-D reference views.
  *   223 -> 224: + fp_raster_lds_bytes, fp_conv3x3_sw_lds_bytes (additions only): the LDS a workgroup of the rasteriser and of the
  *               3x3 convolution asks for at launch.
- *   224 -> 225: + FP_IGEMM_EPILOGUE_GENERIC (addition only; an older library refuses the bit as an unknown flag). */
-#define FP_AMD_ABI_VERSION 225
+ *   224 -> 225: + FP_IGEMM_EPILOGUE_GENERIC (addition only; an older library refuses the bit as an unknown flag).
+ *   225 -> 226: + fp_icp_point_plane, fp_icp_workspace_bytes (additions only): one Gauss-Newton step of point-to-plane ICP per
+ *               hypothesis, the render of a pose against the observed depth. */
+#define FP_AMD_ABI_VERSION 226
 int fp_version(void);
 
 /* Utils.py:104-130 make_mesh_tensors: records caller-owned device tensors.
@@ -182,6 +184,47 @@ int fp_warp_crops_views(const float* rgb /*dev V,H,W,3*/, const float* xyz_map /
 int fp_depth_agreement(const float* depth_crops /*dev N,oh,ow*/, const float* xyz_map /*dev V,H,W,3*/, const float* tf_to_crops /*dev N,9*/,
                        const int32_t* view /*dev N|NULL*/, int V, int H, int W, int N, int oh, int ow, float tol,
                        int32_t* counts /*dev N,4*/, void* stream);
+/* Polish poses against the observed depth: ONE Gauss-Newton step of point-to-plane ICP for each of N hypotheses, in two launches.
+ * Defined to the float32 operation.  Per crop pixel (i, j) of hypothesis n, all in float32, one rounding per operation, every 3-term
+ * sum as (a0*b0 + a1*b1) + a2*b2:
+ *   p = xyz_crops[n, j, i], m = normal_crops[n, j, i]: the camera-frame point and unit normal fp_render_crops* writes at poses_in[n]
+ *       through these tf_to_crops' windows (without FP_FLAG_NORMALIZE_XYZ; 0 where it draws nothing);
+ *   model = p.z > 0 && m.m > 0;
+ *   q = the texel of frame view[n]'s xyz map that fp_depth_agreement reads for that pixel (the nearest texel through the inverse of
+ *       tf_to_crops[n]), all three channels; (0, 0, 0) outside the frame or for a view index outside 0..V-1: nothing is read there;
+ *   valid = model && q.z >= 0.001f;   e = q - p;   pair = valid && e.e <= max_dist * max_dist (the product in float32; a NaN anywhere
+ *       makes a comparison false, so the pixel is no pair);
+ *   r = m.e;   a = p - c with c = (poses_in[n][3], [7], [11]);   J = (a1*m2 - a2*m1, a2*m0 - a0*m2, a0*m1 - a1*m0, m0, m1, m2).
+ * The step moves the model as p' = c + dR(w) (p - c) + v: it rotates about the pose's own origin (the convention of
+ * egocentric_delta_pose_to_pose), so J.x ~ r with x = (w, v).
+ * Per hypothesis, float64: A = sum J^T J (its 21 upper entries), b = sum J^T r, sum r*r and the pair count, over the pairs.  Each term is
+ * the product of the two float32 values widened to double (exact).  The sums run over chunks of 256 consecutive crop pixels (pixel
+ * j * ow + i), inside a chunk over 4 waves of 64: within a wave by the xor tree (s += s of lane ^ 32, ^ 16, ^ 8, ^ 4, ^ 2, ^ 1; a pixel
+ * that is no pair adds +0), the waves in index order, then the chunks in index order starting from +0.  The order depends on (oh, ow)
+ * alone and there are no floating-point atomics: row n has the same bits alone, in any batch and on every replay.
+ * Solve, float64, without contraction: A_l = A + damping * diag(A) (A_l[j][j] = A[j][j] + damping * A[j][j]); LDL^T without pivoting,
+ * for j = 0..5:  v_k = L[j][k] * d[k] and s = A_l[j][j], s = s - L[j][k] * v_k for k = 0..j-1 in order, d[j] = s;  for i = j+1..5:
+ * u = A[j][i], u = u - L[i][k] * v_k for k = 0..j-1 in order, L[i][j] = u / d[j].  Forward: y[i] = b[i], y[i] = y[i] - L[i][k] * y[k]
+ * for k = 0..i-1.  Diagonal: z[i] = y[i] / d[i].  Back, i = 5..0: x[i] = z[i], x[i] = x[i] - L[k][i] * x[k] for k = i+1..5 in order.
+ * status: 2 when a value of the poses_in row (all 16) is not finite; else 1 when pairs < min_pairs; else 2 when a pivot d[j] is <= 0 or
+ * not finite or a component of x is not finite; else 0.  For status != 0, x = 0 and the poses_out row is the poses_in row bit for bit.
+ * Pose update, float64: th = sqrt((w0*w0 + w1*w1) + w2*w2); dR = I + [w]x below th = 1e-12, else with k = w / th, c = cos th, s = sin th:
+ * dR = c I + s [k]x + (1 - c) k k^T (Rodrigues);  R' = dR * R_in (each entry (dR[i][0]*R[0][j] + dR[i][1]*R[1][j]) + dR[i][2]*R[2][j]),
+ * t' = t_in + v, each rounded once to float32; row 3 is copied.
+ * system[n] (float64 x 40): [0..20] A's upper triangle row-major, [21..26] b, [27] sum r*r, [28] pairs, [29] status, [30..35] x,
+ * [36..39] 0.  The sums are reported whatever the status.  poses_out may be NULL (the system alone); poses_in and poses_out must not
+ * overlap.  No allocation, no host synchronisation, no memset (graph-capturable); nothing is written outside system, poses_out and
+ * workspace (fp_icp_workspace_bytes(N, oh, ow) bytes, 8-byte aligned; 0 for N <= 0).  N == 0 does nothing.  Argument errors
+ * (FP_ERR_INVALID_ARG): NULL tensors with N > 0, oh / ow / H / W / V below 1, more than 2^20 crop pixels, N outside 0..65535, view NULL
+ * with V > 1, max_dist or damping negative or not finite, min_pairs < 6, overlapping pose tables, a workspace that is too small or
+ * misaligned. */
+size_t fp_icp_workspace_bytes(int N, int oh, int ow);
+int fp_icp_point_plane(const float* xyz_crops /*dev N,oh,ow,3*/, const float* normal_crops /*dev N,oh,ow,3*/,
+                       const float* xyz_map /*dev V,H,W,3*/, const float* tf_to_crops /*dev N,9*/,
+                       const int32_t* view /*dev N|NULL*/, int V, int H, int W, const float* poses_in /*dev N,16*/,
+                       int N, int oh, int ow, float max_dist, double damping, int min_pairs,
+                       double* system /*dev N,40*/, float* poses_out /*dev N,16|NULL*/,
+                       void* workspace, size_t workspace_bytes, void* stream);
 /* How far each of N poses is from its ground truth, in the units the field reports: out[n] = {add, adds, add_sym, mssd} (float64,
  * metres).  flags selects the columns (a column that is not selected is NaN): */
 #define FP_ERR_ADD 1  /* add: mean distance of corresponding model points */

@@ -92,6 +92,8 @@ def main(argv=None):
     ap.add_argument("--ref_views", type=str, default=None, help="posed RGB-D reference views with masks, in place of --mesh_file")
     ap.add_argument("--synthetic_ref_views", type=int, default=0, help="write N reference views of the can first and use them")
     ap.add_argument("--ref_texture", type=int, default=0, help="with --ref_views: bake a texture atlas of T x T texels a face (2..16)")
+    ap.add_argument("--ref_refine_poses", type=int, default=0,
+                    help="with --ref_views: rounds of polishing the view poses against the fused mesh (point-to-plane ICP) and fusing again")
     ap.add_argument("--save_mesh", type=str, default=None, help="write the mesh that is used to this PLY (or .obj: OBJ + MTL + PNG)")
     args = ap.parse_args(argv)
     logging.basicConfig(level=logging.INFO, format="[%(funcName)s()] %(message)s")
@@ -115,13 +117,17 @@ def main(argv=None):
         args.ref_views = write_synthetic_ref_views(os.path.join(args.debug_dir, "synthetic_ref_views"), args.synthetic_ref_views, dev)
     if not (args.mesh_file or args.ref_views) or not args.test_scene_dir:
         ap.error("--mesh_file (or --ref_views) and --test_scene_dir are required (or --synthetic N)")
+    if args.ref_refine_poses and not args.ref_views:
+        ap.error("--ref_refine_poses needs --ref_views (or --synthetic_ref_views N)")
     if args.ref_views:
         from foundationpose_amd.reconstruct import reconstruct_object
         t0 = time.perf_counter()
-        mesh, _ = reconstruct_object(*read_ref_views(args.ref_views), device=dev, texture=args.ref_texture or None)
+        mesh, _ = reconstruct_object(*read_ref_views(args.ref_views), device=dev, texture=args.ref_texture or None,
+                                     refine_poses=args.ref_refine_poses)
         atlas = getattr(getattr(mesh.visual, "material", None), "image", None)
         logging.info(f"mesh from {args.ref_views}: {len(mesh.vertices)} vertices, {len(mesh.faces)} faces"
-                     + ("" if atlas is None else f", atlas {atlas.shape[0]} x {atlas.shape[1]}") + f" in {time.perf_counter() - t0:.2f} s")
+                     + ("" if atlas is None else f", atlas {atlas.shape[0]} x {atlas.shape[1]}")
+                     + (f", view poses refined {args.ref_refine_poses} x" if args.ref_refine_poses else "") + f" in {time.perf_counter() - t0:.2f} s")
     else:
         mesh = load_mesh(args.mesh_file)
     if args.ref_texture and not args.ref_views:
