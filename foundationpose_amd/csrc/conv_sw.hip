@@ -26,7 +26,9 @@
 #include "igemm_epilogue.h"
 
 #ifdef FP_PROFILE_BUILD
-// profiling build only: 100 MHz wall-clock time per phase, summed over the workgroups of a launch (scripts/dbg_conv_sw.py)
+// profiling build only: 100 MHz wall-clock time per phase, summed over the workgroups of a launch (scripts/dbg_conv_sw.py):
+// [0] cold start = kernel entry -> first operands landed, [1] main loop, [2] epilogue + drain, [3] workgroups, [4] the part of [0] up to
+// "first operand DMAs issued", [6] / [7] first entry / last exit
 __device__ unsigned long long sw_dbg[8];
 extern "C" int fp_dbg_conv_sw(unsigned long long* out, int reset) {
   if (reset) { unsigned long long z[8] = {0, 0, 0, 0, 0, 0, ~0ull, 0}; return (int)hipMemcpyToSymbol(HIP_SYMBOL(sw_dbg), z, sizeof(z)); }
@@ -70,11 +72,23 @@ __device__ __forceinline__ void sw_mfma16(sw_float4& acc, const half8& a, const 
   asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, %0" : "+v"(acc) : "v"(a), "v"(b));
 }
 
-// padded-grid index of tap (0,0) of output pixel m: (b * Hp + oy) * Wp + ox
-__device__ __forceinline__ int sw_q(const IgemmGeom& g, int m) {
-  const int b = ig_fastdiv(m, g.mulP, g.shrP);
+// n / d as umulhi(n, mul) >> shr, WITHOUT the select of ig_fastdiv for a divisor of 1 (mul == 0).  fp_conv3x3_sw_applicable refuses a
+// geometry with Wo < 2 (and HoWo is a multiple of Wo), so the two divisors of this file are never 1; with the select, every one of the
+// ~16 divisions in front of the first operand DMA was a branch whose taken side waited for its own scalar load of shr.
+__device__ __forceinline__ int sw_div(int n, unsigned mul, unsigned shr) { return (int)(__umulhi((unsigned)n, mul) >> shr); }
+
+// The input geometry as k_conv_sw holds it: values read once at the top of the kernel
+struct SwGeom {
+  int HoWo, Wo, Hp, Wp;
+  unsigned mulP, shrP, mulW, shrW;
+};
+
+// padded-grid index of tap (0,0) of output pixel m: (b * Hp + oy) * Wp + ox.  G: SwGeom or IgemmGeom
+template <typename G>
+__device__ __forceinline__ int sw_q(const G& g, int m) {
+  const int b = sw_div(m, g.mulP, g.shrP);
   const int r = m - b * g.HoWo;
-  const int oy = ig_fastdiv(r, g.mulW, g.shrW);
+  const int oy = sw_div(r, g.mulW, g.shrW);
   const int ox = r - oy * g.Wo;
   return (b * g.Hp + oy) * g.Wp + ox;
 }
@@ -122,31 +136,56 @@ __global__ __launch_bounds__(512, 1) void k_conv_sw(IgemmParams p) {
   const int wm = wid / NWN, wn = wid - wm * NWN;
   float* bias_lds = reinterpret_cast<float*>(smem + LDS_MAIN);
 
+  // ---- Tile boundaries (round 10): the first operands leave as early as the wave can send them.  Everything in front of the first patch
+  // and weight DMA reads the HEAD of IgemmParams (igemm_common.h), fetched here in one go -- adjacent kernel-argument dwords become wide
+  // scalar loads behind ONE wait -- and pinned to scalar registers, so that no field is loaded (and waited for) where it is first used.
+  const _Float16* A_ = p.A;
+  const _Float16* W_ = p.Wt;
+  const _Float16* Wpk_ = p.Wpk;
+  const float* bias_ = p.bias;
+  const float* bnsc_ = p.bn_scale;
+  const float* bnsh_ = p.bn_shift;
+  const int M = p.M, N = p.N, Cin = p.Cin, cstride = p.in.cstride, coff = p.in.coff;
+  const SwGeom gi = {p.in.HoWo, p.in.Wo, p.in.Hp, p.in.Wp, p.in.mulP, p.in.shrP, p.in.mulW, p.in.shrW};
+  // (inputs of an empty asm: the values exist here, in whatever registers they were loaded to -- tied outputs cost a move each)
+  asm volatile("" ::"s"(A_), "s"(W_), "s"(Wpk_), "s"(bias_), "s"(bnsc_), "s"(bnsh_), "s"(M), "s"(N), "s"(Cin), "s"(cstride), "s"(coff),
+               "s"(gi.HoWo), "s"(gi.Wo), "s"(gi.Hp), "s"(gi.Wp), "s"(gi.mulP), "s"(gi.shrP), "s"(gi.mulW), "s"(gi.shrW));
+  __builtin_amdgcn_sched_barrier(0);               // nothing that needs a part of the head is scheduled in front of the loads of the rest
+
   // XCD-aware tile order (as igemm.hip): neighbouring pixel tiles (overlapping halos) and the channel tiles of one pixel
   // tile run on the same XCD
-  const int tiles_n = p.N / BN;
-  const int nwg = gridDim.x;
+  const int tiles_n = N / BN;
+  const int nwg = (int)(((unsigned)M + BM - 1) / BM) * tiles_n;   // == gridDim.x (sw_launch), without the round trip for a hidden argument
   const int xcd = blockIdx.x & 7, loc = blockIdx.x >> 3;
   const int qd8 = nwg >> 3, r8 = nwg & 7;
   const int tile = (xcd < r8 ? xcd * (qd8 + 1) : r8 * (qd8 + 1) + (xcd - r8) * qd8) + loc;
-  const int bm = tile / tiles_n, bn = tile - bm * tiles_n;
+  // (the emulated scalar division is ~35 instructions in front of the first DMA; every layer of the two networks has 1, 2 or 4 channel tiles)
+  const int bm = __builtin_popcount(tiles_n) == 1 ? tile >> __builtin_ctz(tiles_n) : tile / tiles_n, bn = tile - bm * tiles_n;
   const int m0 = bm * BM, n0 = bn * BN;
-  const int Cin = p.Cin, Ktot = 9 * Cin, Wp = p.in.Wp;
+  const int Ktot = 9 * Cin, Wp = gi.Wp;
   const int ncc = Cin / BK;
-  ig_bias_to_lds(p, n0, bias_lds, wid, lane);
+  ig_bias_to_lds(bias_, bnsc_, bnsh_, N, n0, bias_lds, wid, lane);
 
   // ---- DMA sources.  Patch row R <-> padded pixel q0 + R (clamped into the tensor: clamped rows are never read by a
   // row that is stored).  Wave w owns patch instructions 4w..4w+3 (16 rows each).
-  const int q0 = sw_q(p.in, m0);
-  const int qmax = (p.M / p.in.HoWo) * p.in.Hp * Wp - 1;
+  const int q0 = sw_q(gi, m0);
+  const int qmax = sw_div(M, gi.mulP, gi.shrP) * gi.Hp * Wp - 1;   // M / HoWo images
   unsigned poff32[PI], woff32[WI];
+  {
+    // byte offset of pixel min(q0 + row, qmax), channel chunk c: (q * cstride + coff + c * 8) * 2.  The product with the positive pixel
+    // stride is monotonic, so the clamp is applied to the product: ONE vector multiplication for the wave's first piece, and an add and a
+    // min per piece (pieces are 16 pixels apart, and the swizzle term of a row depends on row % 16 only).  Unsigned: the tensor ends below
+    // 2^31 bytes and the unclamped rows of a patch lie less than 2^31 bytes behind it (fp_conv3x3_sw_applicable)
+    const int row0 = wid * PI * 16 + (lane >> 2);
+    const int c = (lane & 3) ^ swzp(row0);
+    static_assert(((16 >> 1) & 2) == 0 && ((16 >> 2) & 3) == 0, "swzp(row0 + 16 j) == swzp(row0)");
+    const unsigned ps2 = (unsigned)cstride * 2, omax = (unsigned)qmax * ps2, lane_off = (unsigned)(coff + c * 8) * 2;
+    const unsigned o0 = (unsigned)(q0 + row0) * ps2;
 #pragma unroll
-  for (int j = 0; j < PI; ++j) {
-    const int row = (wid * PI + j) * 16 + (lane >> 2);
-    const int c = (lane & 3) ^ swzp(row);
-    int q = q0 + row;
-    q = q < qmax ? q : qmax;
-    poff32[j] = (unsigned)(((long long)q * p.in.cstride + p.in.coff + c * 8) * 2);
+    for (int j = 0; j < PI; ++j) {
+      const unsigned o = o0 + j * 16 * ps2;
+      poff32[j] = (o < omax ? o : omax) + lane_off;
+    }
   }
 #pragma unroll
   for (int j = 0; j < WI; ++j) {
@@ -156,14 +195,14 @@ __global__ __launch_bounds__(512, 1) void k_conv_sw(IgemmParams p) {
   }
   // Tile-packed weights (round 5, fp_pack_conv3x3_tiles_f16; BN = 128 only): the 8 KiB a k-step stages are one contiguous run that
   // already is the LDS image, so a piece is 1 KiB of consecutive addresses (8 whole 128-byte lines) instead of 16 half lines of 16 weight rows
-  const bool wpk = (BN == 128) && p.Wpk != nullptr;
+  const bool wpk = (BN == 128) && Wpk_ != nullptr;
   if (wpk) {
 #pragma unroll
     for (int j = 0; j < WI; ++j) woff32[j] = (unsigned)(((wid * WI + j) * 64 + lane) * 16);
   }
   const int wpk_base = wpk ? bn * (ncc * 9) * W_BYTES : 0;
-  const __amdgpu_buffer_rsrc_t rsA = __builtin_amdgcn_make_buffer_rsrc(const_cast<_Float16*>(p.A), 0, 0x7FFFFFFF, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rsW = __builtin_amdgcn_make_buffer_rsrc(const_cast<_Float16*>(wpk ? p.Wpk : p.Wt), 0, 0x7FFFFFFF, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rsA = __builtin_amdgcn_make_buffer_rsrc(const_cast<_Float16*>(A_), 0, 0x7FFFFFFF, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rsW = __builtin_amdgcn_make_buffer_rsrc(const_cast<_Float16*>(wpk ? Wpk_ : W_), 0, 0x7FFFFFFF, 0x00020000);
 
   auto stage_patch = [&](int cc, int j) {          // piece j (0..3) of this wave of the patch of chunk cc
     unsigned char* dst = patch + (cc & 1) * SW_PATCH_BYTES + (wid * PI + j) * 1024;
@@ -178,6 +217,17 @@ __global__ __launch_bounds__(512, 1) void k_conv_sw(IgemmParams p) {
       __builtin_amdgcn_raw_ptr_buffer_load_lds(rsW, (__attribute__((address_space(3))) void*)(dst + j * 1024), 16,
                                                (int)woff32[j], wsoff, 0, 0);
   };
+
+  // ---- prologue, first half: patch(0) + W of k-steps 0..2 requested.  Per wave the vector-memory operations keep their order and number
+  // (bias oldest, the patch pieces, the three weight stages): the counted vmcnt waits of the k-steps rely on it.  What the first fragment
+  // read needs and the DMAs do not -- accumulators, fragment rows, weight offsets -- is computed behind them, under their latency.
+#pragma unroll
+  for (int j = 0; j < PI; ++j) stage_patch(0, j);
+  stage_w(0, 0, 0);
+  stage_w(0, 1, 1);
+  stage_w(0, 2, 2);
+  __builtin_amdgcn_sched_barrier(0);
+  SW_CLK(t_issue);
 
   // accumulators: 2 x TM tiles of 32 ch x 32 px (16 floats per lane), or 4 x 2 TM tiles of 16 x 16 (4 floats per lane)
   constexpr int NFA = S16 ? 2 * TM : TM, NFW = S16 ? 4 : 2;       // pixel / weight fragment rows of a wave (x 2 k halves for 32x32x16)
@@ -198,8 +248,8 @@ __global__ __launch_bounds__(512, 1) void k_conv_sw(IgemmParams p) {
 #pragma unroll
   for (int t = 0; t < NFA; ++t) {
     int m = m0 + wm * (32 * TM) + t * FR + frow;
-    m = m < p.M ? m : p.M - 1;
-    arow[t] = sw_q(p.in, m) - q0;
+    m = m < M ? m : M - 1;
+    arow[t] = sw_q(gi, m) - q0;
     if constexpr (S16) arow[t] = (arow[t] << 6) + (fhalf << 4);    // as a byte address: a tap adds shift << 6, the swizzle flips bit 5
   }
   if constexpr (S16) {
@@ -217,19 +267,6 @@ __global__ __launch_bounds__(512, 1) void k_conv_sw(IgemmParams p) {
       for (int kk = 0; kk < 2; ++kk) w_off[t][kk] = rw * ROWB + (((2 * kk + fhalf) ^ swz(rw)) << 4);
     }
   }
-
-  // ---- prologue: patch(0) + W of k-steps 0..2 in flight; patch(0) and W(0) landed and visible
-#pragma unroll
-  for (int j = 0; j < PI; ++j) stage_patch(0, j);
-  stage_w(0, 0, 0);
-  stage_w(0, 1, 1);
-  stage_w(0, 2, 2);
-  sw_wait_vm<2 * WI>();
-  __builtin_amdgcn_s_barrier();
-  SW_CLK(t_cold);
-  if (grp) __builtin_amdgcn_s_barrier();           // group 1 sits out interval 0
-
-  half8 fa[2][TM], fw[2][2];                       // S16: fa[t >> 2][t & 3] is pixel fragment t, fw[t >> 1][t & 1] weight fragment t
   static_assert(TM == 4, "the fragment addresses of the next tap are computed behind the MFMA groups of a k-step, one per group of four");
   int anext[NFA], aflip[NFA];                      // fragment addresses of the next k-step's tap, inside a patch buffer (S16: ^ aflip, the swizzle bit)
 #pragma unroll
@@ -237,6 +274,27 @@ __global__ __launch_bounds__(512, 1) void k_conv_sw(IgemmParams p) {
     anext[t] = S16 ? arow[t] : (arow[t] << 6) + ((fhalf ^ swz(arow[t])) << 4);
     aflip[t] = S16 ? (arow[t] >> 3) & 32 : 0;
   }
+
+  // ... and computed HERE: an empty asm per value keeps the compiler from sinking the computation behind the wait, where nothing covers it
+#pragma unroll
+  for (int t = 0; t < NFA; ++t) {
+    asm volatile("" : "+v"(arow[t]), "+v"(anext[t]));
+    if constexpr (S16) asm volatile("" : "+v"(aflip[t]));
+  }
+  asm volatile("" : "+v"(w_off[0][0]), "+v"(w_off[0][1]), "+v"(w_off[1][0]), "+v"(w_off[1][1]));
+#pragma unroll
+  for (int i = 0; i < NFW; ++i)
+#pragma unroll
+    for (int j = 0; j < NFA; ++j) asm volatile("" : "+v"(acc[i][j]));
+  __builtin_amdgcn_sched_barrier(0);
+
+  // ---- prologue, second half: patch(0) and W(0) landed and visible (W of k-steps 1 and 2 in flight)
+  sw_wait_vm<2 * WI>();
+  __builtin_amdgcn_s_barrier();
+  SW_CLK(t_cold);
+  if (grp) __builtin_amdgcn_s_barrier();           // group 1 sits out interval 0
+
+  half8 fa[2][TM], fw[2][2];                       // S16: fa[t >> 2][t & 3] is pixel fragment t, fw[t >> 1][t & 1] weight fragment t
   // one k-step = (chunk cc, tap T).  LAST: cc is the last chunk (no next patch; the weight prefetch runs dry).
   // vmcnt bookkeeping (loads retire in order): this wave's pieces of W(s+1) must have landed when it leaves the memory
   // cluster; younger and allowed in flight are W(s+2), W(s+3) and the patch pieces issued in this and the previous step.
@@ -361,7 +419,7 @@ __global__ __launch_bounds__(512, 1) void k_conv_sw(IgemmParams p) {
   SW_CLK(t_end);
   if (tid == 0) {
     atomicAdd(&sw_dbg[0], t_cold - t_start); atomicAdd(&sw_dbg[1], t_loop - t_cold); atomicAdd(&sw_dbg[2], t_end - t_loop);
-    atomicAdd(&sw_dbg[3], 1ull); atomicMin(&sw_dbg[6], t_start); atomicMax(&sw_dbg[7], t_end);
+    atomicAdd(&sw_dbg[3], 1ull); atomicAdd(&sw_dbg[4], t_issue - t_start); atomicMin(&sw_dbg[6], t_start); atomicMax(&sw_dbg[7], t_end);
   }
 #endif
 }
@@ -627,11 +685,15 @@ bool fp_conv3x3_sw_applicable(const IgemmParams& p) {
   const IgemmGeom& g = p.in;
   if (p.taps != 9 || g.stride != 1 || g.off != 0 || g.bsplit != 0) return false;
   if (g.HoWo % g.Wo != 0 || g.Wp != g.Wo + 2 || g.Hp != g.HoWo / g.Wo + 2) return false;
+  // images one pixel wide: the kernels divide by Wo and HoWo without the divisor-1 case of ig_fastdiv (sw_div).  Nothing is lost: a patch
+  // of such a tile (two border pixels per output pixel) fits no patch buffer, sw_span below
+  if (g.Wo < 2) return false;
   const int BM = sw_tile_rows(p);
   if (p.M % g.HoWo != 0 || p.M < 2 * BM) return false;
   if (p.Cin % 64 != 0 || p.N % 128 != 0) return false;
   const long long bytes = (long long)(p.M / g.HoWo) * g.Hp * g.Wp * g.cstride * 2;
   if (bytes >= (1ll << 31)) return false;           // 32-bit byte offsets in the LDS-DMA source addresses
+  if (g.cstride >= (1 << 19)) return false;         // ... formed BEFORE the clamp to the tensor's end: 1024 rows of a patch stay below 2^31 bytes
   // 32-bit tile-relative row offsets in the epilogue's output table (igemm_epilogue.h, SLIM): elements of the output buffer
   const IgemmGeom& o = p.out;
   const long long imgs = o.bsplit > 0 ? o.bsplit : p.M / g.HoWo, groups = o.bsplit > 0 ? (p.M / g.HoWo) / o.bsplit + 1 : 0;

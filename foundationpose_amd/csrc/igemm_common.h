@@ -1,6 +1,7 @@
 // Shared by igemm.hip and conv3x3.hip: operand addressing and the kernel parameter block of fp_igemm_f16_fwd.
 #pragma once
 #include <hip/hip_fp16.h>
+#include <stddef.h>
 #include "fp_common.h"
 
 typedef _Float16 half8 __attribute__((ext_vector_type(8)));
@@ -41,28 +42,34 @@ __device__ __forceinline__ int ig_fastdiv(int n, unsigned mul, unsigned shr) {
 }
 
 struct IgemmParams {
+  // ---- the head: everything k_conv_sw reads in front of its first operand DMA (conv_sw.hip), as the first 128 bytes of the block, so
+  // that the kernel fetches it with two wide scalar loads at its top instead of one load (and one wait) per field where the field is
+  // first used.  Keep these members together and in front; the static_asserts below hold the layout.
   const _Float16* A;
   const _Float16* Wt;   // [N][taps*Cin]
   const _Float16* Wpk;  // the same weights tile-packed (fp_pack_conv3x3_tiles_f16) or null: read by k_conv_sw<512,128> only
   const float* bias;    // [N] or null
   const float* bn_scale;   // [N] or null: eval-mode BatchNorm as y = x * scale + shift, applied to the fp16-rounded conv + bias
   const float* bn_shift;
+  int M, N, Cin, taps;
+  IgemmGeom in;
+  // ---- the rest: the epilogue's
+  IgemmGeom out, res;
   const _Float16* R;    // residual or null
   _Float16* Y;
   const float* pe;      // optional second output (the positional-embedding add of network_modules.py:133-137 fused into the
   _Float16* Ype;        // last conv): Ype[m][n] = f16(f32(y[m][n]) + pe[m % pe_period][n]), a plain (M, N) matrix
   int pe_period;
-  int M, N, Cin, taps;
   int relu;
   int round_acc;        // FP_IGEMM_ROUND_ACC: the accumulator is rounded to fp16 BEFORE the bias is added (nn.Conv2d under
                         // autocast: ATen adds the bias to the fp16 convolution output); 0: one rounding of acc + bias (nn.Linear)
-  IgemmGeom in, out, res;
   int mfma16;           // k_conv_sw: main loop on v_mfma_f32_16x16x32_f16 (1) or v_mfma_f32_32x32x16_f16 (0); FP_IGEMM_MFMA_*
   int epi;              // layer kind of the epilogue (IG_EPI_* below; igemm.hip ig_epilogue_mode): 0 = the generic body of igemm_epilogue.h
   unsigned pe_mul, pe_shr;   // m / pe_period as ig_fastdiv (the layer-kind bodies; the generic body divides)
   float* slab;          // split-K only (fp_igemm_f16_splitk_fwd): fp32 partial accumulators in fragment order,
   int nsplit;           //   [split][tile][wave][(i, g, j)][lane] x float4; 0 = not split
 };
+static_assert(sizeof(IgemmGeom) == 64 && offsetof(IgemmParams, in) == 64 && offsetof(IgemmParams, out) == 128, "the head of IgemmParams is its first 128 bytes");
 
 // IgemmParams.epi: what the epilogue of a launch consists of, as a bit set.  Bit 0 marks a body compiled for exactly that set
 // (ig_epilogue_spec); the library compiles the six kinds of layer the two networks' plans launch -- IG_EPI_CONV, + BatchNorm, each

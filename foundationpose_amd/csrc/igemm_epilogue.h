@@ -9,8 +9,9 @@
 
 #ifdef FP_PROFILE_BUILD
 // profiling build only: 100 MHz wall-clock time per epilogue phase, summed over the workgroups of a launch (one copy per translation
-// unit; conv_sw.hip reports its own through fp_dbg_conv_sw): [0] row tables + barrier, [1] residual requests, [2] accumulators ->
-// E tile + barrier, [3] E tile -> stores issued (waits for the residual rows), [4] calls
+// unit; conv_sw.hip reports its own through fp_dbg_conv_sw): [0] row tables + barrier, [1] residual requests (layer-kind bodies of
+// k_conv_sw: the residual row offsets read + barrier), [2] accumulators -> E tile + barrier (there: with the residual requests, issued
+// in groups under the transposition), [3] E tile -> stores issued (waits for the residual rows), [4] calls
 static __device__ unsigned long long ig_epi_dbg[8];
 #define IG_CLK(t) const unsigned long long t = wall_clock64()
 #else
@@ -129,15 +130,28 @@ __device__ __forceinline__ void ig_epilogue_spec(const IgEpiArgs& p, Acc& acc, u
   const int ml0 = tid / CPR, ch = tid % CPR;       // iteration `it` of this thread: row ml0 + it * RPI, chunk ch
   // The residual rows are requested before the transposition: their HBM latency overlaps it
   half8 rv[RES ? NIT : 1];
+  // SLIM: ... and UNDER it (round 10).  Sixteen 16-byte loads per lane issued back to back are 128 KB of requests per workgroup; the waves
+  // then sit at the issue of their loads until the memory pipe has taken them, and the transposition starts when the rows have all but
+  // arrived.  So the loads go out in NRG groups, one in front of each channel group of the transposition, and VALU and LDS transpose while
+  // the memory pipe streams.  The lane's row offsets leave the E tile first (rowR borrows it), as 32-bit byte offsets in registers.
+  constexpr int NRG = S16 ? 4 : 8;                 // channel groups of the transposition below: i, or (i, g)
+  static_assert(NIT % NRG == 0, "residual loads per channel group");
+  unsigned roff[RES && SLIM ? NIT : 1];
+  const __amdgpu_buffer_rsrc_t rsR = __builtin_amdgcn_make_buffer_rsrc(ig_uniform_ptr(p.R), 0, -1, 0x00020000);   // RES && SLIM only
+  auto res_group = [&](int g) {                    // SLIM: the residual rows of store iterations [g, g + 1) * NIT / NRG
+    if constexpr (RES && SLIM) {
+#pragma unroll
+      for (int it = g * (NIT / NRG); it < (g + 1) * (NIT / NRG); ++it)
+        rv[it] = __builtin_bit_cast(half8, __builtin_amdgcn_raw_buffer_load_b128(rsR, (int)roff[it], 0, 0));
+      __builtin_amdgcn_sched_barrier(0);           // where it stands: not hoisted in front of, nor sunk behind, the groups around it
+    }
+  };
   if constexpr (RES) {
     if constexpr (SLIM) {
-      const __amdgpu_buffer_rsrc_t rsR = __builtin_amdgcn_make_buffer_rsrc(ig_uniform_ptr(p.R), 0, -1, 0x00020000);
       const int* rR = reinterpret_cast<const int*>(rowR + ml0);    // the low words: offsets below 2^31 elements
 #pragma unroll
-      for (int it = 0; it < NIT; ++it)
-        rv[it] = __builtin_bit_cast(half8, __builtin_amdgcn_raw_buffer_load_b128(rsR, (int)(((unsigned)rR[it * RPI * 2] + ch * 8) << 1), 0, 0));
-      // rowR sits in the E tile: every wave has read it (its loads are issued) before any wave writes E.  A bare barrier: __syncthreads()
-      // would also wait for the residual rows themselves, whose latency the transposition is there to cover
+      for (int it = 0; it < NIT; ++it) roff[it] = ((unsigned)rR[it * RPI * 2] + ch * 8) << 1;
+      // rowR sits in the E tile: every wave has read it (the offsets are in its registers) before any wave writes E
       __builtin_amdgcn_sched_barrier(0);
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       __builtin_amdgcn_s_barrier();
@@ -191,6 +205,7 @@ __device__ __forceinline__ void ig_epilogue_spec(const IgEpiArgs& p, Acc& acc, u
     const int cx = (wn * 8 + (quad >> 1)) ^ r15;   // chunk of channel quad i: (wn * 8 + 2 i + (quad >> 1)) ^ r15 = cx ^ 2 i
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
+      res_group(i);
       const Vecs c = vecs(wn * 64 + i * 16 + 4 * quad);
       unsigned char* Ei = Erow + ((cx ^ (2 * i)) << 4);
 #pragma unroll
@@ -204,6 +219,7 @@ __device__ __forceinline__ void ig_epilogue_spec(const IgEpiArgs& p, Acc& acc, u
     for (int i = 0; i < 2; ++i) {
 #pragma unroll
       for (int g = 0; g < 4; ++g) {
+        res_group(i * 4 + g);
         const Vecs c = vecs(wn * 64 + i * 32 + 8 * g + 4 * (lane >> 5));
         unsigned char* Ei = Erow + ((cx ^ (4 * i + g)) << 4);
 #pragma unroll
@@ -434,15 +450,20 @@ __device__ __forceinline__ void ig_epilogue(const IgemmParams& p, Acc& acc, unsi
 // Being the oldest vector-memory operation of the wave it is covered by every later counted vmcnt wait, and it is
 // visible to the workgroup after the first barrier of the main loop.  The LDS area is always IG_BIAS_LDS bytes.
 // Three vectors of IG_VEC_FLOATS floats: bias, BatchNorm scale, BatchNorm shift (waves 0, 1, 2 fetch one each).
-__device__ __forceinline__ void ig_bias_to_lds(const IgemmParams& p, int n0, float* bias_lds, int wid, int lane) {
+// (The vectors and N as values: k_conv_sw passes the copies it reads at its top, conv_sw.hip.)
+__device__ __forceinline__ void ig_bias_to_lds(const float* bias, const float* bn_scale, const float* bn_shift, int N, int n0, float* bias_lds,
+                                               int wid, int lane) {
   if (wid > 2) return;
-  const float* src = wid == 0 ? p.bias : (wid == 1 ? p.bn_scale : p.bn_shift);
+  const float* src = wid == 0 ? bias : (wid == 1 ? bn_scale : bn_shift);
   float* dst = bias_lds + wid * IG_VEC_FLOATS;
   if (src) {
-    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(src), 0, p.N * 4, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(src), 0, N * 4, 0x00020000);
     __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (__attribute__((address_space(3))) void*)dst, 16, lane * 16, n0 * 4, 0, 0);
   } else if (wid == 0) {
     typedef float f4 __attribute__((ext_vector_type(4)));
     *reinterpret_cast<f4*>(dst + lane * 4) = f4{0.f, 0.f, 0.f, 0.f};
   }
+}
+__device__ __forceinline__ void ig_bias_to_lds(const IgemmParams& p, int n0, float* bias_lds, int wid, int lane) {
+  ig_bias_to_lds(p.bias, p.bn_scale, p.bn_shift, p.N, n0, bias_lds, wid, lane);
 }

@@ -1,4 +1,7 @@
-"""phase timers of k_conv_sw (profiling build): cold start / main loop / epilogue per workgroup, and the epilogue's own phases, 100 MHz wall clock
+"""phase timers of k_conv_sw (profiling build): cold start / main loop / epilogue per workgroup, and the epilogue's own phases, 100 MHz wall clock.
+Cold start = kernel entry -> first operands landed; its first part, up to the issue of the first operand DMAs, is the prologue's own share.
+Residual layers: the residual rows are requested in groups under the accumulators -> E tile transposition, so the phase in front of it is
+only the read of the row offsets (a library from before that change reports "residual requests" and "acc->E" under the same two names).
     FP_AMD_LIB=foundationpose_amd/csrc/libfp_amd_profile.so python scripts/dbg_conv_sw.py"""
 import sys, os, ctypes as C
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -30,10 +33,10 @@ for (B, H, Ci, Co) in ((504, 40, 128, 128), (252, 40, 256, 256), (252, 20, 512, 
         L.fp_dbg_conv_sw(out, 0)
         if HAVE_EPI: L.fp_dbg_conv_sw_epilogue(epi, 0)
         n = out[3]
-        line = (f"B={B} {Ci}->{Co} {'+res' if res else 'nores'}: {e0.elapsed_time(e1) * 1e3:.1f} us; {n} tiles = {n / 256:.2f} rounds; per tile: cold {out[0] / n * 10:.0f} ns, loop {out[1] / n * 10:.0f} ns, "
+        line = (f"B={B} {Ci}->{Co} {'+res' if res else 'nores'}: {e0.elapsed_time(e1) * 1e3:.1f} us; {n} tiles = {n / 256:.2f} rounds; per tile: cold {out[0] / n * 10:.0f} ns (first operand DMAs issued after {out[4] / n * 10:.0f}), loop {out[1] / n * 10:.0f} ns, "
                 f"epilogue+drain {out[2] / n * 10:.0f} ns; span {(out[7] - out[6]) * 10 / 1e3:.1f} us")
         if HAVE_EPI and epi[4]:
             m = epi[4]
-            line += (f"; epilogue: row tables {epi[0] / m * 10:.0f}, residual requests {epi[1] / m * 10:.0f}, acc->E {epi[2] / m * 10:.0f}, "
+            line += (f"; epilogue: row tables {epi[0] / m * 10:.0f}, residual offsets read {epi[1] / m * 10:.0f}, acc->E + residual requests {epi[2] / m * 10:.0f}, "
                      f"E->stores issued {epi[3] / m * 10:.0f}, drain {(out[2] - epi[0] - epi[1] - epi[2] - epi[3]) / m * 10:.0f} ns")
         print(line, flush=True)

@@ -37,8 +37,9 @@ for mode in ("serialized", "concurrent", "serialized", "concurrent"):
     for _ in range(2):
         step()
     torch.cuda.synchronize()
-    out = (C.c_ulonglong * 8)()
+    out, epi = (C.c_ulonglong * 8)(), (C.c_ulonglong * 8)()
     L.fp_dbg_conv_sw(out, 1)
+    L.fp_dbg_conv_sw_epilogue(epi, 1)
     t0 = time.perf_counter()
     K = 5
     for _ in range(K):
@@ -46,7 +47,13 @@ for mode in ("serialized", "concurrent", "serialized", "concurrent"):
     torch.cuda.synchronize()
     dt = (time.perf_counter() - t0) / K * 1e3
     L.fp_dbg_conv_sw(out, 0)
+    L.fp_dbg_conv_sw_epilogue(epi, 0)
     n = out[3]
-    r = dict(ms_per_step=dt, tiles_per_step=n / K, cold_us=out[0] / n / 100, loop_us=out[1] / n / 100, epilogue_us=out[2] / n / 100,
+    r = dict(ms_per_step=dt, tiles_per_step=n / K, cold_us=out[0] / n / 100, issue_us=out[4] / n / 100, loop_us=out[1] / n / 100, epilogue_us=out[2] / n / 100,
              cu_ms_per_step=(out[0] + out[1] + out[2]) / 100 / 1e3 / K / 256)
+    # issue_us: the part of cold_us up to the issue of the first operand DMAs.  The epilogue's phases per whole tile (layer kinds with and
+    # without a residual together): row tables, residual offsets read (before round 10: residual requests), accumulators -> E tile (+ the
+    # residual requests under it), E tile -> stores issued
+    if epi[4]:
+        r["epilogue_phases_us"] = [round(epi[k] / epi[4] / 100, 3) for k in range(4)]
     print(mode, json.dumps(r), flush=True)
