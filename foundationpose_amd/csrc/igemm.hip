@@ -404,7 +404,8 @@ static int ig_build_params(const void* x, const fp_igemm_geom* x_geom, const voi
   FP_REQUIRE(!e.residual || e.r_geom, "%s: residual without geometry", who);
   FP_REQUIRE((e.bn_scale == nullptr) == (e.bn_shift == nullptr), "%s: bn_scale and bn_shift go together", who);
   FP_REQUIRE(!e.bn_scale || (e.flags & FP_IGEMM_ROUND_ACC), "%s: BatchNorm needs FP_IGEMM_ROUND_ACC (conv semantics)", who);
-  FP_REQUIRE((e.flags & ~(FP_IGEMM_RELU | FP_IGEMM_ROUND_ACC | FP_IGEMM_HAS_W_TILES | FP_IGEMM_MFMA_16X16X32 | FP_IGEMM_MFMA_32X32X16 | FP_IGEMM_EPILOGUE_GENERIC)) == 0,
+  FP_REQUIRE((e.flags & ~(FP_IGEMM_RELU | FP_IGEMM_ROUND_ACC | FP_IGEMM_HAS_W_TILES | FP_IGEMM_MFMA_16X16X32 | FP_IGEMM_MFMA_32X32X16 | FP_IGEMM_EPILOGUE_GENERIC |
+                           FP_IGEMM_DIRECT_STORE | FP_IGEMM_W_TILES_DIRECT)) == 0,
              "%s: unknown flags 0x%x", who, e.flags);
   FP_REQUIRE((e.flags & (FP_IGEMM_MFMA_16X16X32 | FP_IGEMM_MFMA_32X32X16)) != (FP_IGEMM_MFMA_16X16X32 | FP_IGEMM_MFMA_32X32X16),
              "%s: FP_IGEMM_MFMA_16X16X32 and FP_IGEMM_MFMA_32X32X16 exclude each other", who);
@@ -417,6 +418,7 @@ static int ig_build_params(const void* x, const fp_igemm_geom* x_geom, const voi
   // w_tiles is a trailing member added in ABI 212: it is READ only when the caller says the struct has it (a native caller compiled
   // against an older header passes a shorter struct and can never set the bit)
   const void* w_tiles = (e.flags & FP_IGEMM_HAS_W_TILES) ? e.w_tiles : nullptr;
+  FP_REQUIRE(!(e.flags & FP_IGEMM_W_TILES_DIRECT) || w_tiles, "%s: FP_IGEMM_W_TILES_DIRECT without w_tiles (and FP_IGEMM_HAS_W_TILES)", who);
   FP_REQUIRE(!w_tiles || (taps == 9 && (((size_t)w_tiles) & 15) == 0 && w_tiles != w), "%s: w_tiles is for 3x3 convolutions, 16-byte aligned, not w itself", who);
   p.A = (const _Float16*)x; p.Wt = (const _Float16*)w; p.Wpk = (const _Float16*)w_tiles; p.bias = e.bias; p.bn_scale = e.bn_scale; p.bn_shift = e.bn_shift;
   p.R = (const _Float16*)e.residual; p.Y = (_Float16*)y;
@@ -427,6 +429,7 @@ static int ig_build_params(const void* x, const fp_igemm_geom* x_geom, const voi
   p.in = ig_geom(x_geom); p.out = ig_geom(y_geom); p.res = e.residual ? ig_geom(e.r_geom) : ig_geom(y_geom);
   p.slab = nullptr; p.nsplit = 0;
   p.epi = ig_epilogue_mode(p, e.flags);
+  p.direct = (e.flags & FP_IGEMM_DIRECT_STORE) ? 1 : 0; p.wpk_direct = (e.flags & FP_IGEMM_W_TILES_DIRECT) ? 1 : 0;
   ig_fastdiv_init(p.pe_period, &p.pe_mul, &p.pe_shr);
   return FP_OK;
 }

@@ -66,9 +66,13 @@ struct IgemmParams {
   int mfma16;           // k_conv_sw: main loop on v_mfma_f32_16x16x32_f16 (1) or v_mfma_f32_32x32x16_f16 (0); FP_IGEMM_MFMA_*
   int epi;              // layer kind of the epilogue (IG_EPI_* below; igemm.hip ig_epilogue_mode): 0 = the generic body of igemm_epilogue.h
   unsigned pe_mul, pe_shr;   // m / pe_period as ig_fastdiv (the layer-kind bodies; the generic body divides)
+  int direct;           // FP_IGEMM_DIRECT_STORE: the 512 x 128 tile of k_conv_sw leaves from its accumulators where k_conv_sw_direct applies (conv_sw.hip)
   float* slab;          // split-K only (fp_igemm_f16_splitk_fwd): fp32 partial accumulators in fragment order,
   int nsplit;           //   [split][tile][wave][(i, g, j)][lane] x float4; 0 = not split
+  int wpk_direct;       // FP_IGEMM_W_TILES_DIRECT: Wpk has the row order of fp_pack_conv3x3_tiles_direct_f16
 };
+// (direct and wpk_direct, round 11, sit where the block had padding: its size, and with it every kernel's argument layout, is what it was)
+static_assert(sizeof(IgemmParams) == 336, "IgemmParams grew: the hidden kernel arguments move");
 static_assert(sizeof(IgemmGeom) == 64 && offsetof(IgemmParams, in) == 64 && offsetof(IgemmParams, out) == 128, "the head of IgemmParams is its first 128 bytes");
 
 // IgemmParams.epi: what the epilogue of a launch consists of, as a bit set.  Bit 0 marks a body compiled for exactly that set

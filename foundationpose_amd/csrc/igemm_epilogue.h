@@ -11,7 +11,7 @@
 // profiling build only: 100 MHz wall-clock time per epilogue phase, summed over the workgroups of a launch (one copy per translation
 // unit; conv_sw.hip reports its own through fp_dbg_conv_sw): [0] row tables + barrier, [1] residual requests (layer-kind bodies of
 // k_conv_sw: the residual row offsets read + barrier), [2] accumulators -> E tile + barrier (there: with the residual requests, issued
-// in groups under the transposition), [3] E tile -> stores issued (waits for the residual rows), [4] calls
+// in groups under the transposition), [3] E tile -> stores issued (waits for the residual rows), [4] calls; [5..7]: ig_epilogue_direct
 static __device__ unsigned long long ig_epi_dbg[8];
 #define IG_CLK(t) const unsigned long long t = wall_clock64()
 #else
@@ -75,6 +75,20 @@ __device__ __forceinline__ half8 ig_relu8(const half8& v) {
   half8 r;
 #pragma unroll
   for (int e = 0; e < 4; ++e) {
+    const half2_ x = {v[2 * e], v[2 * e + 1]};
+    half2_ y;
+    asm("v_pk_max_f16 %0, %1, 0" : "=v"(y) : "v"(x));
+    r[2 * e] = y[0]; r[2 * e + 1] = y[1];
+  }
+  return r;
+}
+
+// ... of four halves (the direct epilogue below): the same instruction, twice
+__device__ __forceinline__ half4 ig_relu4(const half4& v) {
+  typedef _Float16 half2_ __attribute__((ext_vector_type(2)));
+  half4 r;
+#pragma unroll
+  for (int e = 0; e < 2; ++e) {
     const half2_ x = {v[2 * e], v[2 * e + 1]};
     half2_ y;
     asm("v_pk_max_f16 %0, %1, 0" : "=v"(y) : "v"(x));
@@ -262,6 +276,102 @@ __device__ __forceinline__ void ig_epilogue_spec(const IgEpiArgs& p, Acc& acc, u
   }
 #endif
 }
+// ---- The direct epilogue (round 11, k_conv_sw_direct of conv_sw.hip): the 512 x 128 tile leaves straight from the accumulators.  That
+// kernel issues its 16x16x32 MFMAs with pixels as A and weights as B and orders the weight rows so that lane l of wave (wm, wn) holds, in
+// acc[t][j][e], pixel row wm * 128 + 16 j + 4 (l >> 4) + e and channel wn * 64 + 4 (l & 15) + t of the tile: four consecutive channels of a
+// pixel per lane (8 bytes), the 64 channels of a pixel in 16 consecutive lanes (one 128-byte line), and the SAME four channels for the whole
+// tile, so the per-channel vectors are read once.  No E tile and no barrier between conversion and store: a wave stores a pixel tile as
+// soon as it is converted, and the eight waves are free to drift apart.
+// The statements per element and their order are those of ig_epilogue_spec (put4, then + residual, then ReLU): the same bits given the same
+// accumulators.  rowY32: the output row table the kernel built in its prologue (element offsets from the buffer's start, channel n0
+// included; IG_ROW_NONE for a row past M).  The residual table goes over the operand stages (the caller's barrier retired their last read);
+// residual rows are requested one group of two pixel tiles ahead of their use.  FULL: every row of the tile exists.
+template <int EPI, bool FULL, typename Acc>
+__device__ __forceinline__ void ig_epilogue_direct(const IgEpiArgs& p, Acc& acc, unsigned char* smem, const int* rowY32, int m0, int n0, int M,
+                                                   int wm, int wn, int tid, int lane, const float* bias_lds) {
+  constexpr int TM = 4;                            // the 512 x 128 tile: thread `tid` owns row `tid` of the tables
+  static_assert(std::is_same<Acc, ig_float4[4][2 * TM]>::value, "accumulators of the 16x16x32 loop");
+  static_assert((EPI & IG_EPI_CONV) == IG_EPI_CONV && !(EPI & IG_EPI_PE), "conv rounding + bias + ReLU, without the positional output");
+  constexpr bool HAS_BN = (EPI & IG_EPI_BN) != 0, RES = (EPI & IG_EPI_RES) != 0;
+  typedef float float4_ __attribute__((ext_vector_type(4)));
+  typedef int int4_ __attribute__((ext_vector_type(4)));
+  typedef unsigned uint2_ __attribute__((ext_vector_type(2)));
+  typedef _Float16 half2_ __attribute__((ext_vector_type(2)));
+  constexpr int JG = 2, NG = 2 * TM / JG;          // pixel tiles per residual group, groups
+  const int nl = wn * 64 + 4 * (lane & 15);        // the lane's four channels, tile-local
+  const int prow = wm * (32 * TM) + 4 * (lane >> 4);   // its four rows of pixel tile j: prow + 16 j + e
+  int* rowR32 = reinterpret_cast<int*>(smem);
+  IG_CLK(te0);
+  if constexpr (RES) {
+    // (a row past M: the offset of the last row, which is loaded and never stored)
+    const int m = FULL || m0 + tid < M ? m0 + tid : M - 1;
+    rowR32[tid] = (int)(ig_row_off(p.res, m) + n0);
+    __syncthreads();
+  }
+  IG_CLK(te1);
+  const float4_ bv = *reinterpret_cast<const float4_*>(bias_lds + nl);
+  const half2_ b01 = {(_Float16)bv[0], (_Float16)bv[1]}, b23 = {(_Float16)bv[2], (_Float16)bv[3]};
+  float4_ sc, sh;
+  if constexpr (HAS_BN) {
+    sc = *reinterpret_cast<const float4_*>(bias_lds + IG_VEC_FLOATS + nl);
+    sh = *reinterpret_cast<const float4_*>(bias_lds + 2 * IG_VEC_FLOATS + nl);
+  }
+  const __amdgpu_buffer_rsrc_t rsY = __builtin_amdgcn_make_buffer_rsrc(ig_uniform_ptr(p.Y), 0, -1, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rsR = __builtin_amdgcn_make_buffer_rsrc(ig_uniform_ptr(p.R), 0, -1, 0x00020000);   // RES only
+  half4 rv[RES ? 2 : 1][JG * 4];
+  auto res_group = [&](int g) {                    // the residual rows of pixel tiles [g, g + 1) * JG: 8-byte loads
+    if constexpr (RES) {
+#pragma unroll
+      for (int jj = 0; jj < JG; ++jj) {
+        const int4_ ro = *reinterpret_cast<const int4_*>(rowR32 + prow + 16 * (g * JG + jj));
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+          rv[g & 1][jj * 4 + e] = __builtin_bit_cast(half4, __builtin_amdgcn_raw_buffer_load_b64(rsR, (int)((unsigned)(ro[e] + nl) << 1), 0, 0));
+      }
+      __builtin_amdgcn_sched_barrier(0);           // where it stands: not hoisted in front of, nor sunk behind, the groups around it
+    }
+  };
+  res_group(0);
+#pragma unroll
+  for (int g = 0; g < NG; ++g) {
+    if (g + 1 < NG) res_group(g + 1);
+#pragma unroll
+    for (int jj = 0; jj < JG; ++jj) {
+      const int j = g * JG + jj;
+      const int4_ yo = *reinterpret_cast<const int4_*>(rowY32 + prow + 16 * j);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        // put4 of ig_epilogue_spec (ROUND_ACC), statement for statement
+        half4 v;
+        half2_ t01 = {(_Float16)acc[0][j][e], (_Float16)acc[1][j][e]};
+        half2_ t23 = {(_Float16)acc[2][j][e], (_Float16)acc[3][j][e]};
+        t01 = t01 + b01;
+        t23 = t23 + b23;
+        if constexpr (HAS_BN) {
+          v[0] = (_Float16)fmaf((float)t01[0], sc[0], sh[0]);
+          v[1] = (_Float16)fmaf((float)t01[1], sc[1], sh[1]);
+          v[2] = (_Float16)fmaf((float)t23[0], sc[2], sh[2]);
+          v[3] = (_Float16)fmaf((float)t23[1], sc[3], sh[3]);
+        } else {
+          v[0] = t01[0]; v[1] = t01[1]; v[2] = t23[0]; v[3] = t23[1];
+        }
+        // ... and of its store loop
+        if constexpr (RES) v = v + rv[g & 1][jj * 4 + e];   // IEEE half add == the fp32 add of two halves rounded once
+        v = ig_relu4(v);
+        if (FULL || yo[e] != IG_ROW_NONE)
+          __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(uint2_, v), rsY, (int)((unsigned)(yo[e] + nl) << 1), 0, 0);
+      }
+    }
+    __builtin_amdgcn_sched_barrier(0);
+  }
+#ifdef FP_PROFILE_BUILD
+  // slots of its own, so that a step that runs both kernels keeps them apart: [5] the residual table + its barrier (the output table is
+  // built in the kernel's prologue and counts as cold start), [6] conversions + stores issued, [7] calls
+  IG_CLK(te2);
+  if (tid == 0) { atomicAdd(&ig_epi_dbg[5], te1 - te0); atomicAdd(&ig_epi_dbg[6], te2 - te1); atomicAdd(&ig_epi_dbg[7], 1ull); }
+#endif
+}
+
 // EPI: 0 = the generic body below, which reads the layer kind from IgemmParams at run time (any combination; the A/B arm of
 // FP_IGEMM_EPILOGUE_GENERIC); otherwise one of the IG_EPI_* layer kinds of ig_epilogue_spec, FULL tiles only.
 template <int BM, int BN, int TM, int THREADS, int DBG, bool FULL, bool SLIM, int EPI = 0, typename Acc, typename P>

@@ -84,6 +84,12 @@ CONV_MFMA_16X16X32 = True
 # overrides(SPECIALIZED_EPILOGUE=False) sets FP_IGEMM_EPILOGUE_GENERIC, the one body that reads the kind at run time.  The same arithmetic in
 # the same order: the same bits (tests/test_gpu_igemm_epilogue_modes.py).  Read by ops.igemm_f16 at every call.
 SPECIALIZED_EPILOGUE = True
+# round 11: the 512 x 128 tiles of the shifted-window 3x3 convolution leave straight from their accumulators (csrc/conv_sw.hip
+# k_conv_sw_direct: the MFMA operands exchanged, no transposition through LDS) in the layers that kernel exists for: conv rounding + bias +
+# ReLU with or without BatchNorm and residual, on 16x16x32 MFMAs.  The token layer (positional second output) stays on k_conv_sw.  A plan
+# packs each layer's weight tiles for the kernel the layer runs (_conv_params); overrides(CONV_DIRECT_STORE=False) is the A/B arm.  The same
+# products in the same order and the same epilogue statements: the same bits (tests/test_gpu_conv_sw_direct.py).
+CONV_DIRECT_STORE = True
 
 
 def _conv_backend():
@@ -199,17 +205,20 @@ class _TorchEncoderLayer:
 
 
 # ------------------------------------------------------------------------------------------------ HIP plan (fp16 autocast policy)
-def _conv_params(sd, conv_p, bn_p):
-    """-> dict(w (Cout, kh*kw*Cin) fp16 with k ordered (ky, kx, ci), bias f32 (fp16-rounded) | None, scale, shift | None)"""
+def _conv_params(sd, conv_p, bn_p, second_output=False):
+    """-> dict(w (Cout, kh*kw*Cin) fp16 with k ordered (ky, kx, ci), bias f32 (fp16-rounded) | None, scale, shift | None).
+    second_output: the layer also writes the positional output (its launches stay on k_conv_sw whatever CONV_DIRECT_STORE says)"""
     w = sd[conv_p + ".weight"].float()
     b = sd.get(conv_p + ".bias")
     scale, shift = _bn_affine(sd, bn_p)
     wk = w.permute(0, 2, 3, 1).reshape(w.shape[0], -1).to(torch.float16).contiguous()
     # round 5: the tile-packed copy the shifted-window kernel fetches as contiguous 8 KiB runs (fp_pack_conv3x3_tiles_f16); 3x3 only
-    tiles = None
+    # round 11: ... in the row order of the kernel the layer's launches run: k_conv_sw_direct takes the layers k_conv_sw took, under these
+    # conditions (csrc/conv_sw.hip sw_direct; a launch whose kernel cannot read its pack is refused, never run permuted)
+    tiles, direct = None, bool(CONV_DIRECT_STORE and CONV_MFMA_16X16X32 and SPECIALIZED_EPILOGUE and b is not None and not second_output)
     if wk.is_cuda and w.shape[2] == 3 and w.shape[3] == 3 and w.shape[0] % 128 == 0 and w.shape[1] % 32 == 0 and PACKED_CONV_TILES:
-        tiles = ops.pack_conv3x3_tiles(wk, w.shape[0], w.shape[1])
-    return dict(w=wk, w_tiles=tiles, bias=None if b is None else _r16(b.float()), scale=scale, shift=shift)
+        tiles = (ops.pack_conv3x3_tiles_direct if direct else ops.pack_conv3x3_tiles)(wk, w.shape[0], w.shape[1])
+    return dict(w=wk, w_tiles=tiles, tiles_direct=direct and tiles is not None, bias=None if b is None else _r16(b.float()), scale=scale, shift=shift)
 
 
 # Round 5: split-K for the reference's tracking call.  With ONE hypothesis (estimater.py:250-268) the encoder's convolutions are
@@ -227,7 +236,7 @@ SPLITK_TARGET_WGS = 384        # (tile, piece) workgroups a launch should have: 
 # the hard ceiling of both thresholds: overlap.SubBatches' default min_rows (a call of >= 2 x 32 hypotheses is split into sub-batches)
 SMALL_CALL_CEILING = 31
 
-_SWITCHES = ("FUSED_OUT_PROJ_LN", "FUSED_FFN", "ROWS_QKV", "PACKED_CONV_TILES", "MERGED_HEAD_QKV", "FUSED_TAIL", "CONV_MFMA_16X16X32", "SPECIALIZED_EPILOGUE", "SPLITK_MAX_HYPS", "HEADS_TWO_STREAMS_MAX_HYPS")
+_SWITCHES = ("FUSED_OUT_PROJ_LN", "FUSED_FFN", "ROWS_QKV", "PACKED_CONV_TILES", "MERGED_HEAD_QKV", "FUSED_TAIL", "CONV_MFMA_16X16X32", "SPECIALIZED_EPILOGUE", "CONV_DIRECT_STORE", "SPLITK_MAX_HYPS", "HEADS_TWO_STREAMS_MAX_HYPS")
 
 
 @contextlib.contextmanager
@@ -285,7 +294,7 @@ class _HipEncoder:
                          ("j3", joint + ".3"), ("j4", joint + ".4")):
             names += [(blk + "a", pre + ".conv1", pre + ".bn1"), (blk + "b", pre + ".conv2", pre + ".bn2")]
         names.append(("j2", joint + ".2.net.0", joint + ".2.net.1"))
-        self.w = {k: _conv_params(sd, c, b) for k, c, b in names}
+        self.w = {k: _conv_params(sd, c, b, second_output=(k == "j4b")) for k, c, b in names}
         self.pe = sd["pos_embed.pe"].float().reshape(-1, sd["pos_embed.pe"].shape[-1]).contiguous()   # (400, 512) f32
         self.device = device
         self._bufs = {}
@@ -325,7 +334,7 @@ class _HipEncoder:
                                         conv_rounding=True, pe=pe, y_pe=y_pe)
         return ops.igemm_f16(x, gin, c["w"], c["bias"], y, gout, Bn * Ho * Wo, Cout, Cin, 9, relu=relu, residual=res, r_geom=gres,
                              bn_scale=c["scale"], bn_shift=c["shift"], conv_rounding=True, pe=pe, y_pe=y_pe,
-                             w_tiles=c["w_tiles"] if stride == 1 else None)
+                             w_tiles=c["w_tiles"] if stride == 1 else None, w_tiles_direct=c["tiles_direct"] and stride == 1)
 
     def __call__(self, AB, slot=0, shared_b=False, small_calls=True):
         """AB (2n,6,H,W) fp16 -> (tokens (n, H/8 * W/8, 512) fp16 before the positional table,

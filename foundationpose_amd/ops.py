@@ -1303,6 +1303,8 @@ IGEMM_HAS_W_TILES = 4
 IGEMM_MFMA_16X16X32 = 16
 IGEMM_MFMA_32X32X16 = 32
 IGEMM_EPILOGUE_GENERIC = 64
+IGEMM_DIRECT_STORE = 256
+IGEMM_W_TILES_DIRECT = 512
 
 
 class IgemmEpilogue(C.Structure):
@@ -1321,6 +1323,15 @@ def pack_conv3x3_tiles(w, N, Cin):
     return out
 
 
+def pack_conv3x3_tiles_direct(w, N, Cin):
+    """pack_conv3x3_tiles with the rows of each 128-channel tile in the order of the direct-store kernel (fp_pack_conv3x3_tiles_direct_f16):
+    the w_tiles of an igemm_f16 call with w_tiles_direct=True"""
+    w = _dev(w, torch.float16, "w")
+    out = torch.empty_like(w)
+    _lib.check(_lib.lib().fp_pack_conv3x3_tiles_direct_f16(_ptr(w), _ptr(out), int(N), int(Cin), _stream(w)), "fp_pack_conv3x3_tiles_direct_f16")
+    return out
+
+
 def _igemm_epilogue(bias, residual, r_geom, bn_scale, bn_shift, pe, y_pe, flags, w_tiles=None):
     """the fp_igemm_epilogue of igemm_f16 / igemm_f16_splitk: dtype and layout checks of its tensors, `flags` as the caller built them"""
     pe = _dev(pe, torch.float32, "pe")
@@ -1335,9 +1346,12 @@ def _igemm_epilogue(bias, residual, r_geom, bn_scale, bn_shift, pe, y_pe, flags,
 
 
 def igemm_f16(x, x_geom, w, bias, y, y_geom, M, N, Cin, taps, relu=False, residual=None, r_geom=None, bn_scale=None,
-              bn_shift=None, conv_rounding=False, pe=None, y_pe=None, w_tiles=None, mfma16=None):
+              bn_shift=None, conv_rounding=False, pe=None, y_pe=None, w_tiles=None, mfma16=None, direct_store=None, w_tiles_direct=False):
     """y = act(f16(epilogue(implicit_gemm(x, w))) (+ residual)) -- see fp_igemm_f16_fwd.  mfma16: the MFMA shape of the shifted-window
-    conv's main loop (True 16x16x32, False 32x32x16); None = the engine switch CONV_MFMA_16X16X32.  conv_rounding: nn.Conv2d under
+    conv's main loop (True 16x16x32, False 32x32x16); None = the engine switch CONV_MFMA_16X16X32.  direct_store: FP_IGEMM_DIRECT_STORE,
+    the shifted-window conv's 512 x 128 tile stored from its accumulators where that kernel exists; None = the engine switch
+    CONV_DIRECT_STORE, except that a w_tiles in the other kernel's layout keeps the launch on that kernel.  w_tiles_direct: w_tiles comes
+    from pack_conv3x3_tiles_direct (the library refuses a pack that the launch's kernel cannot read).  conv_rounding: nn.Conv2d under
     autocast (accumulator rounded to fp16 before the bias add, optional BatchNorm as scale/shift with its own rounding);
     otherwise nn.Linear (one rounding of accumulator + bias).  pe (S, N) f32 + y_pe (M, N) fp16: second output
     f16(f32(y) + pe[m % S]).  All tensors are device buffers owned by the caller (y is written in place and returned)."""
@@ -1345,10 +1359,13 @@ def igemm_f16(x, x_geom, w, bias, y, y_geom, M, N, Cin, taps, relu=False, residu
     from . import engine                   # engine imports this module
     if mfma16 is None:
         mfma16 = engine.CONV_MFMA_16X16X32
+    if direct_store is None:
+        direct_store = engine.CONV_DIRECT_STORE and (w_tiles is None or bool(w_tiles_direct))
     ep = _igemm_epilogue(bias, residual, r_geom, bn_scale, bn_shift, pe, y_pe,
                          (IGEMM_RELU if relu else 0) | (IGEMM_ROUND_ACC if conv_rounding else 0) | IGEMM_HAS_W_TILES |
                          (IGEMM_MFMA_16X16X32 if mfma16 else IGEMM_MFMA_32X32X16) |
-                         (0 if engine.SPECIALIZED_EPILOGUE else IGEMM_EPILOGUE_GENERIC), w_tiles)
+                         (0 if engine.SPECIALIZED_EPILOGUE else IGEMM_EPILOGUE_GENERIC) |
+                         (IGEMM_DIRECT_STORE if direct_store else 0) | (IGEMM_W_TILES_DIRECT if w_tiles_direct else 0), w_tiles)
     st = _lib.lib().fp_igemm_f16_fwd(_ptr(x), C.byref(x_geom), _ptr(w), _ptr(y), C.byref(y_geom), int(M), int(N), int(Cin),
                                      int(taps), C.byref(ep), _stream(x))
     _lib.check(st, "fp_igemm_f16_fwd")

@@ -85,8 +85,10 @@ const char* fp_last_error(void);
  *               3x3 convolution asks for at launch.
  *   224 -> 225: + FP_IGEMM_EPILOGUE_GENERIC (addition only; an older library refuses the bit as an unknown flag).
  *   225 -> 226: + fp_icp_point_plane, fp_icp_workspace_bytes (additions only): one Gauss-Newton step of point-to-plane ICP per
- *               hypothesis, the render of a pose against the observed depth. */
-#define FP_AMD_ABI_VERSION 226
+ *               hypothesis, the render of a pose against the observed depth.
+ *   226 -> 227: + FP_IGEMM_DIRECT_STORE / FP_IGEMM_W_TILES_DIRECT, fp_pack_conv3x3_tiles_direct_f16 (additions only; an older library
+ *               refuses the bits as unknown flags). */
+#define FP_AMD_ABI_VERSION 227
 int fp_version(void);
 
 /* Utils.py:104-130 make_mesh_tensors: records caller-owned device tensors.
@@ -527,6 +529,18 @@ typedef struct {
  * call needs.  Ignored by fp_igemm_f16_splitk_fwd, whose epilogue is a kernel of its own. */
 #define FP_IGEMM_EPILOGUE_GENERIC 64
 
+/* The shifted-window 3x3 kernel's 512 x 128 tile stored straight from the accumulators (csrc/conv_sw.hip k_conv_sw_direct): the 16x16x32
+ * MFMAs are issued with pixels as A and weights as B, a lane then owns four consecutive channels of a pixel and stores them as they are
+ * converted, without the transposition through LDS.  The same products in the same k order and the same epilogue statements per element
+ * (measured on gfx950: the same bits).  Taken by the launches that kernel exists for -- that tile, 16x16x32 MFMAs, conv rounding + bias +
+ * ReLU with or without BatchNorm and residual, no positional output, not FP_IGEMM_EPILOGUE_GENERIC -- and ignored by every other one.
+ * FP_IGEMM_W_TILES_DIRECT: w_tiles comes from fp_pack_conv3x3_tiles_direct_f16, the row order of that kernel.  A launch that reads w_tiles
+ * refuses the layout of the other kernel (FP_ERR_INVALID_ARG). */
+/* (flag values 8 and 128 are not assigned: the library refuses them as unknown, which tests/test_abi.py and
+ * tests/test_gpu_igemm_epilogue_modes.py rely on) */
+#define FP_IGEMM_DIRECT_STORE 256
+#define FP_IGEMM_W_TILES_DIRECT 512
+
 /* What fp_igemm_f16_fwd does with the fp32 accumulators (all members optional; NULL struct = plain fp16 store) */
 typedef struct {
   const float* bias;           /* dev (N) f32 | NULL; for conv semantics fp16-representable values */
@@ -534,7 +548,7 @@ typedef struct {
   const float* bn_shift;
   const void* residual;        /* dev fp16 | NULL: `out += identity` (network_modules.py:107), rounded to fp16 */
   const fp_igemm_geom* r_geom; /* host: addressing of the residual */
-  int flags;                   /* FP_IGEMM_RELU | FP_IGEMM_ROUND_ACC | FP_IGEMM_HAS_W_TILES | FP_IGEMM_MFMA_* | FP_IGEMM_EPILOGUE_GENERIC */
+  int flags;                   /* FP_IGEMM_RELU | FP_IGEMM_ROUND_ACC | FP_IGEMM_HAS_W_TILES | FP_IGEMM_MFMA_* | FP_IGEMM_EPILOGUE_GENERIC | FP_IGEMM_DIRECT_STORE | FP_IGEMM_W_TILES_DIRECT */
   const float* pe;             /* dev (pe_period, N) f32 | NULL: second output y_pe[m, n] = f16(f32(y[m, n]) + pe[m % pe_period, n]), */
   int pe_period;               /*   the PositionalEmbedding add of network_modules.py:133-137 fused into the last conv of the */
   void* y_pe;                  /*   encoder; y_pe is a plain (M, N) fp16 matrix */
@@ -560,6 +574,11 @@ int fp_igemm_f16_fwd(const void* x /*dev*/, const fp_igemm_geom* x_geom /*host*/
  *   w_tiles[((bn * 9 * Cin / 32 + s) * 128 + r) * 32 + 8 * pc + e] = w[128 bn + r][tap * Cin + 32 cc + 8 * (pc ^ ((r >> 2) & 3)) + e].
  * N % 128 == 0, Cin % 32 == 0; w_tiles has the size of w and must not alias it.  No reference counterpart (a layout, not an operation). */
 int fp_pack_conv3x3_tiles_f16(const void* w /*dev*/, void* w_tiles /*dev*/, int N, int Cin, void* stream);
+/* The same repack for FP_IGEMM_DIRECT_STORE launches (flag FP_IGEMM_W_TILES_DIRECT): row r of a 128-channel tile holds weight row
+ *   rho(r) = (r & 64) + 4 * (4 * tau((r >> 2) & 3) + (r & 3)) + ((r >> 4) & 3),  tau = (0, 3, 1, 2),
+ * of that tile, its chunks where the layout above puts them (by r, not by rho(r)):
+ *   w_tiles[((bn * 9 * Cin / 32 + s) * 128 + r) * 32 + 8 * pc + e] = w[128 bn + rho(r)][tap * Cin + 32 cc + 8 * (pc ^ ((r >> 2) & 3)) + e]. */
+int fp_pack_conv3x3_tiles_direct_f16(const void* w /*dev*/, void* w_tiles /*dev*/, int N, int Cin, void* stream);
 /* bytes of LDS one workgroup of the shifted-window 3x3 convolution (512 x 128 tiles, every product layer) asks for at launch; host only */
 int fp_conv3x3_sw_lds_bytes(void);
 
