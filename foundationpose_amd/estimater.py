@@ -55,7 +55,8 @@ class FoundationPose:
         (3,3); voxel=None: the longest side gets 128 voxels; reconstruct_args: its further keywords), then the constructor as for any
         other mesh (kwargs: scorer, refiner, symmetry_tfs, device, ...).  Poses come out in the frame of ob_in_cams; reset_object
         centres the mesh as usual (model_center).  With reconstruct_args={"refine_poses": R} the view poses are polished against the
-        fused mesh first; the estimator keeps them as ref_ob_in_cams ((V,4,4) float32; None without)."""
+        fused mesh first (with "refine_against": "volume" beside it, against the volume itself); the estimator keeps them as ref_ob_in_cams
+        ((V,4,4) float32; None without)."""
         from .reconstruct import reconstruct_object
         args = dict(reconstruct_args or {})
         args.setdefault("device", kwargs.get("device", "cuda"))

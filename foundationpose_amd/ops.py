@@ -1095,6 +1095,96 @@ def tsdf_extract(tsdf, weight, color, color_weight, origin, voxel, min_weight=1.
     return dict(pos=pos[first], vnormals=nrm[first], vertex_color=col[first], faces=inv.reshape(total, 3).to(torch.int32))
 
 
+RAYCAST_OUTPUTS = ("depth", "xyz", "normal", "color")
+TSDF_RAYCAST_MAX_SAMPLES = 65536       # FP_TSDF_RAYCAST_MAX_SAMPLES (include/fp_amd.h)
+RAYCAST_NO_Z_FAR = float(np.finfo(np.float32).max)      # a z_far that cuts nothing: the box alone ends the rays
+
+
+def tsdf_raycast(tsdf, weight, color, color_weight, origin, voxel, poses, K, H, W, out_hw=None, bbox2d=None, step=None, min_weight=1.0,
+                 z_near=0.001, z_far=None, want=RAYCAST_OUTPUTS, out=None, views=None):
+    """fp_tsdf_raycast: the zero surface of a TSDF volume (arrays, origin and voxel as in tsdf_integrate) seen from the N poses
+    (N,4,4) f32 object-to-camera, through the crop windows bbox2d (N,4) f32 (crop_windows') into out_hw = (oh, ow) crops, or full
+    frame (bbox2d None: out_hw None or (H, W)) -> dict of the outputs in `want`: depth (N,oh,ow) metres, xyz (N,oh,ow,3) camera-frame
+    points, normal (N,oh,ow,3) camera-frame unit normals, color (N,oh,ow,3) in the units of the volume's; zeros where a ray meets no
+    surface.  The pixel convention is render_crops': depth / xyz / normal stand where a render of the extracted mesh stands in
+    depth_agreement and icp_point_plane (include/fp_amd.h has the definition).  K: one camera (3x3, no skew); several views: views = an
+    ops.Views (K unused), row n sees through Ks[view[n]].  step: the distance between samples in metres of camera depth (None: one
+    voxel); rays start at z_near and end at z_far (None: where they leave the volume).  Only voxels observed min_weight times count.
+    out: a dict of caller-owned buffers for (some of) the wanted outputs, so that a loop allocates nothing.  One launch, no
+    synchronisation: capturable in a graph.  Wrong shapes and values are refused first, then tensors that are not on the device, of
+    another dtype or not contiguous."""
+    what = "tsdf_raycast"
+    dims, o, s = _tsdf_grid(what, tsdf, weight, color, color_weight, origin, voxel)
+    if not torch.is_tensor(poses):
+        raise _lib.FpAmdError(f"{what}: poses must be a tensor, got {type(poses).__name__}")
+    if poses.dim() != 3 or tuple(poses.shape[1:]) != (4, 4):
+        raise _lib.FpAmdError(f"{what}: poses must be (N,4,4), got {tuple(poses.shape)}")
+    N, H, W = int(poses.shape[0]), int(H), int(W)
+    if N > 65535:
+        raise _lib.FpAmdError(f"{what}: {N} poses in one call, at most 65535 (chunk the batch)")
+    if H < 1 or W < 1:
+        raise _lib.FpAmdError(f"{what}: a frame of {H} x {W} pixels")
+    if bbox2d is None:
+        oh, ow = (H, W) if out_hw is None else (int(out_hw[0]), int(out_hw[1]))
+        if (oh, ow) != (H, W):
+            raise _lib.FpAmdError(f"{what}: without bbox2d the crop is the frame: out_hw must be ({H}, {W}), got ({oh}, {ow})")
+    else:
+        if out_hw is None:
+            raise _lib.FpAmdError(f"{what}: out_hw is required with bbox2d")
+        oh, ow = int(out_hw[0]), int(out_hw[1])
+        if not torch.is_tensor(bbox2d) or tuple(bbox2d.shape) != (N, 4):
+            raise _lib.FpAmdError(f"{what}: bbox2d must be a ({N},4) tensor, got "
+                                  f"{tuple(bbox2d.shape) if torch.is_tensor(bbox2d) else type(bbox2d).__name__}")
+    if oh < 1 or ow < 1 or oh * ow > 1 << 20:
+        raise _lib.FpAmdError(f"{what}: crops of {oh} x {ow} pixels (1 .. 2^20 pixels are supported)")
+    want = tuple(want)
+    if not want or any(w not in RAYCAST_OUTPUTS for w in want):
+        raise ValueError(f"{what}: want must name at least one of {RAYCAST_OUTPUTS}, got {want!r}")
+    st = s if step is None else float(step)
+    if not (np.isfinite(st) and st > 0 and np.isfinite(np.float32(st)) and np.float32(st) > 0):
+        raise ValueError(f"{what}: step must be finite and > 0 (metres), got {step!r}")
+    diag = float(np.sqrt(sum((n - 1.0) ** 2 for n in dims))) * s
+    if diag / st > TSDF_RAYCAST_MAX_SAMPLES - 2:
+        raise ValueError(f"{what}: step={st!r} gives {diag / st:.0f} samples along the volume's diagonal, more than "
+                         f"{TSDF_RAYCAST_MAX_SAMPLES - 2}: use a longer step")
+    zn, zf, mw = float(z_near), RAYCAST_NO_Z_FAR if z_far is None else float(z_far), float(min_weight)
+    if not (np.isfinite(zn) and zn >= 0):
+        raise ValueError(f"{what}: z_near must be finite and >= 0 (metres), got {z_near!r}")
+    if not (np.isfinite(zf) and zf >= zn):
+        raise ValueError(f"{what}: z_far must be finite and >= z_near (metres; None for no limit), got {z_far!r}")
+    if not np.isfinite(mw):
+        raise ValueError(f"{what}: min_weight must be finite, got {min_weight!r}")
+    K9 = vt = None
+    if views is not None:
+        vt = _views(views, what, N)
+    else:
+        K9 = np.ascontiguousarray(_hostK33(K, what, "the rays are defined without one").reshape(9).astype(np.float32))
+    shapes = dict(depth=(N, oh, ow), xyz=(N, oh, ow, 3), normal=(N, oh, ow, 3), color=(N, oh, ow, 3))
+    out = dict(out or {})
+    for name in out:
+        if name not in want:
+            raise ValueError(f"{what}: out has a buffer for '{name}', which is not in want={want!r}")
+        if not torch.is_tensor(out[name]) or tuple(out[name].shape) != shapes[name]:
+            raise _lib.FpAmdError(f"{what}: out['{name}'] must be a {shapes[name]} tensor")
+    P = _dev(poses, torch.float32, "poses")
+    bb = _dev(bbox2d, torch.float32, "bbox2d")
+    f, w, c, cw = [_dev(t, torch.float32, name) for name, t in (("tsdf", tsdf), ("weight", weight), ("color", color), ("color_weight", color_weight))]
+    res = {}
+    for name in RAYCAST_OUTPUTS:
+        if name in want:
+            res[name] = _dev(out[name], torch.float32, f"out['{name}']") if name in out else torch.empty(shapes[name], dtype=torch.float32,
+                                                                                                         device=P.device)
+    if N == 0:
+        return res
+    nul = C.c_void_p(0)
+    _lib.check(_lib.lib().fp_tsdf_raycast(_ptr(f), _ptr(w), _ptr(c), _ptr(cw), dims[0], dims[1], dims[2], o.ctypes.data_as(C.c_void_p), s, mw,
+                                          _ptr(P), nul if K9 is None else K9.ctypes.data_as(C.c_void_p), nul if vt is None else _ptr(vt.K32),
+                                          nul if vt is None else _ptr(vt.dev), 0 if vt is None else vt.V, _ptr(bb), H, W, N, oh, ow, st, zn,
+                                          zf, _ptr(res.get("depth")), _ptr(res.get("xyz")), _ptr(res.get("normal")), _ptr(res.get("color")),
+                                          _stream(P)), "fp_tsdf_raycast")
+    return res
+
+
 TEXTURE_BAKE_MAX_TEXELS, TEXTURE_BAKE_MAX_SIDE = 16, 16384       # FP_TEXTURE_BAKE_MAX_TEXELS / _SIDE (include/fp_amd.h)
 
 

@@ -70,6 +70,7 @@ class TsdfVolume:
         self.weight = torch.empty(self.dims, dtype=torch.float32, device=self.device)
         self.color = torch.empty(self.dims + (3,), dtype=torch.float32, device=self.device)
         self.color_weight = torch.empty(self.dims, dtype=torch.float32, device=self.device)
+        self.left_out = None          # integrate_aligned: the views of its last call that it did not fuse
         self.reset()
 
     def arrays(self):
@@ -111,6 +112,78 @@ class TsdfVolume:
         mesh = SimpleMesh(out["pos"].cpu().numpy(), out["faces"].cpu().numpy(), vertex_normals=out["vnormals"].cpu().numpy(),
                           vertex_colors=cols)
         return mesh, t
+
+    def raycast(self, ob_in_cams, K, size, bbox2d=None, step=None, min_weight=1, z_near=0.001, z_far=None,
+                want=ops.RAYCAST_OUTPUTS):
+        """what the volume looks like from the poses ob_in_cams (N,4,4), without extracting a mesh (ops.tsdf_raycast) -> a dict of
+        device tensors: depth (N,h,w) metres, xyz and normal (N,h,w,3) in the camera frame, color (N,h,w,3) in the units of the
+        fused rgb; zeros where a ray meets no surface.  K: one camera (3,3), or an ops.Views whose row n names the camera of pose n.
+        size = (h, w): the frame, or with bbox2d ((N,4) device tensor, ops.crop_windows') the crops the windows are resampled into.
+        step=None samples every voxel pitch of camera depth; z_far=None lets the rays run to the far side of the volume; only voxels
+        observed min_weight times count.  One launch, no synchronisation."""
+        P = _upload(_host(ob_in_cams), torch.float32, self.device)
+        if P.dim() == 2:
+            P = P[None]
+        views = K if isinstance(K, ops.Views) else None
+        h, w = int(size[0]), int(size[1])
+        return ops.tsdf_raycast(*self.arrays(), self.origin, self.voxel, P.contiguous(), None if views is not None else K, h, w, (h, w),
+                                bbox2d, step, min_weight, z_near, z_far, want, views=views)
+
+    def depth_agreement(self, depths, masks, ob_in_cams, Ks, tol=None):
+        """how well the volume, as fused so far, explains V posed views -> (V,4) int32 device tensor, the counts of
+        ops.depth_agreement (ops.DepthAgreement.rows reads them) per view: the pixels where the volume shows a surface from the view's
+        pose (`model`), those of them where the view has a masked depth (`valid`), those where the two depths are within tol
+        (`agree`) and those where the view sees more than tol past the volume's surface (`behind`).  The volume's raycast depth, full
+        frame, against each view's masked, back-projected depth; tol=None: two voxels."""
+        what = "TsdfVolume.depth_agreement"
+        if masks is None:
+            raise ValueError(f"{what}: masks are required")
+        tol = ops._check_tol(2.0 * self.voxel if tol is None else tol, what)
+        d, _, m, P, K = _views_in(None, depths, masks, ob_in_cams, Ks, self.device, what)
+        V, H, W = (int(x) for x in d.shape)
+        if H < 2 or W < 2:
+            raise ValueError(f"{what}: frames of {H} x {W} pixels (at least 2 x 2)")
+        vt = ops.Views(list(K), np.arange(V), self.device)
+        xyz = ops.depth_to_xyz_frames(torch.where(m != 0, d, torch.zeros_like(d)).contiguous(), vt)
+        r = ops.tsdf_raycast(*self.arrays(), self.origin, self.voxel, P.contiguous(), None, H, W, want=("depth",), views=vt)
+        # the window that is the frame: crop pixel (i, j) reads texel (i, j)
+        tf = torch.tensor([[W / (W - 1.0), 0.0, -0.5], [0.0, H / (H - 1.0), -0.5], [0.0, 0.0, 1.0]], dtype=torch.float32, device=self.device)
+        return ops.depth_agreement(r["depth"], xyz, tf.repeat(V, 1, 1).contiguous(), tol, views=vt)
+
+    def integrate_aligned(self, rgbs, depths, masks, ob_in_cams, Ks, iterations=3, max_dist=0.01, trusted=1):
+        """fuses V views whose poses are only approximately known (a turntable, a robot arm, a previous tracker: a few millimetres and
+        a degree or so off), one after the other: the first `trusted` views as given, every later view first aligned to the volume as
+        fused so far (align_views_to_volume: `iterations` steps of point-to-plane ICP, pairs within max_dist) and then fused with the
+        aligned pose -> the views' poses, (V,4,4) float32 on the device: the aligned pose of every view that was fused, the given one
+        of the others.  A view one of whose steps could not be solved (too few pairs: it does not overlap what was fused before it)
+        keeps the pose it was given and is left out of the volume, since nothing vouches for that pose; this is decided on the
+        device, there is no host read per view.  Which views that were is `self.left_out` afterwards, a (V,) bool device tensor.
+        This polishes pose guesses; it is not pose estimation from nothing: a view without a pose within reach of the ICP (about a
+        centimetre) cannot be placed."""
+        what = "TsdfVolume.integrate_aligned"
+        if rgbs is None or masks is None:
+            raise ValueError(f"{what}: rgbs and masks are required")
+        iterations = _check_iterations(iterations, what)
+        ops._check_icp(max_dist, 1e-3, 64, what)
+        if isinstance(trusted, bool) or not isinstance(trusted, (int, np.integer)) or int(trusted) < 0:
+            raise ValueError(f"{what}: trusted must be an int >= 0, got {trusted!r}")
+        d, c, m, P, K = _views_in(rgbs, depths, masks, ob_in_cams, Ks, self.device, what)
+        V = int(d.shape[0])
+        t = min(int(trusted), V)
+        self.left_out = torch.zeros((V,), dtype=torch.bool, device=self.device)
+        if t > 0:
+            self._integrate(d[:t], c[:t], m[:t], P[:t], K[:t])
+        if t == V:
+            return P
+        side = _AlignSide(self, d, m, K)
+        used = [P[:t]]
+        nan = torch.full((1, 4, 4), float("nan"), dtype=torch.float32, device=self.device)
+        for v in range(t, V):
+            Q, bad = side.align(P[v:v + 1].contiguous(), side.vt.rows(v, v + 1), iterations, max_dist)
+            self._integrate(d[v:v + 1], c[v:v + 1], m[v:v + 1], torch.where(bad[:, None, None], nan, Q), K[v:v + 1])   # a NaN pose: skipped
+            used.append(torch.where(bad[:, None, None], P[v:v + 1], Q))
+            self.left_out[v:v + 1] = bad
+        return torch.cat(used)
 
 
 def bake_texture(mesh_tensors, rgbs, depths, masks, ob_in_cams, Ks, texels=4, tol=None, min_cos=0.2, min_depth=0.001):
@@ -186,6 +259,12 @@ ICP_CROP = (160, 160)    # the crops refine_view_poses renders the mesh into, an
 ICP_CROP_RATIO = 1.2
 
 
+def _check_iterations(iterations, what):
+    if isinstance(iterations, bool) or not isinstance(iterations, (int, np.integer)) or int(iterations) < 1:
+        raise ValueError(f"{what}: iterations must be an int >= 1, got {iterations!r}")
+    return int(iterations)
+
+
 def refine_view_poses(mesh_tensors, depths, masks, ob_in_cams, Ks, iterations=3, max_dist=0.01):
     """Polish the poses of V reference views against a mesh of the object (a fused one: TsdfVolume.extract's mesh_tensors) by
     `iterations` Gauss-Newton steps of point-to-plane ICP per view (ops.icp_point_plane, view v for row v of an ops.Views): per
@@ -196,14 +275,13 @@ def refine_view_poses(mesh_tensors, depths, masks, ob_in_cams, Ks, iterations=3,
     what = "refine_view_poses"
     if masks is None:
         raise ValueError(f"{what}: masks are required")
-    if isinstance(iterations, bool) or not isinstance(iterations, (int, np.integer)) or int(iterations) < 1:
-        raise ValueError(f"{what}: iterations must be an int >= 1, got {iterations!r}")
+    iterations = _check_iterations(iterations, what)
     ops._check_icp(max_dist, 1e-3, 64, what)
     for k in ("pos", "faces", "vnormals"):
         if k not in mesh_tensors:
             raise ValueError(f"{what}: mesh_tensors has no '{k}'")
     d, _, m, P, K = _views_in(None, depths, masks, ob_in_cams, Ks, mesh_tensors["pos"].device, what)
-    return _refine_views(mesh_tensors, d, m, P, K, int(iterations), max_dist)
+    return _refine_views(mesh_tensors, d, m, P, K, iterations, max_dist)
 
 
 def _refine_views(t, d, m, P, K, iterations, max_dist):
@@ -226,9 +304,65 @@ def _refine_views(t, d, m, P, K, iterations, max_dist):
     return P, ops.IcpStep.rows(system)
 
 
+class _AlignSide:
+    """what aligning views to a volume reuses from one step to the next: the views' table, their masked back-projected depth, the
+    sphere about the frame's origin that holds the volume's box, and the buffers of the raycast and of the ICP step"""
+
+    def __init__(self, vol, d, m, K):
+        dev = d.device
+        V = int(d.shape[0])
+        self.vol, self.H, self.W = vol, int(d.shape[1]), int(d.shape[2])
+        self.vt = ops.Views(list(K), np.arange(V), dev)
+        self.xyz = ops.depth_to_xyz_frames(torch.where(m != 0, d, torch.zeros_like(d)).contiguous(), self.vt)
+        nz, ny, nx = vol.dims
+        hi = vol.origin + (np.asarray([nx, ny, nz], dtype=np.float64) - 1.0) * vol.voxel
+        self.diam = ops.object_diameters([2.0 * float(np.linalg.norm(np.maximum(np.abs(vol.origin), np.abs(hi))))], dev)
+        self.bufs = {}
+
+    def align(self, P, vt, iterations, max_dist, min_weight=1):
+        """-> (poses (n,4,4), bad (n,) bool: a step of the row had a non-zero status), both on the device"""
+        n, (oh, ow) = int(P.shape[0]), ICP_CROP
+        if n not in self.bufs:
+            dev = P.device
+            self.bufs[n] = (dict(xyz=torch.empty((n, oh, ow, 3), dtype=torch.float32, device=dev),
+                                 normal=torch.empty((n, oh, ow, 3), dtype=torch.float32, device=dev)),
+                            torch.empty((n, 40), dtype=torch.float64, device=dev), ops.icp_workspace(n, oh, ow, dev))
+        out, system, ws = self.bufs[n]
+        vol = self.vol
+        bad = torch.zeros((n,), dtype=torch.bool, device=P.device)
+        for _ in range(iterations):
+            tf, bb = ops.crop_windows(P, None, self.diam, ICP_CROP_RATIO, (ow, oh), views=vt)
+            r = ops.tsdf_raycast(*vol.arrays(), vol.origin, vol.voxel, P, None, self.H, self.W, (oh, ow), bb, min_weight=min_weight,
+                                 want=("xyz", "normal"), out=out, views=vt)
+            P, _ = ops.icp_point_plane(r["xyz"], r["normal"], self.xyz, tf, P, max_dist, views=vt, system=system, workspace=ws)
+            bad = bad | (system[:, 29] != 0)
+        return P, bad
+
+
+def align_views_to_volume(vol, depths, masks, ob_in_cams, Ks, iterations=3, max_dist=0.01):
+    """refine_view_poses against the volume itself: the poses of V views polished by `iterations` Gauss-Newton steps of point-to-plane
+    ICP per view against the zero surface of the TsdfVolume `vol`, raycast at the current poses (ops.tsdf_raycast) where
+    refine_view_poses renders a mesh -- no extraction, no mesh handle, and no host synchronisation inside the loop.  The windows
+    (ICP_CROP crops, ICP_CROP_RATIO) hold the sphere about the frame's origin that holds the volume's box; the sensor side is each
+    view's own masked depth, back-projected unfiltered.  -> (poses (V,4,4) float32 device tensor, [ops.IcpStep] of the last iteration:
+    read on the host after the loop).  A view whose step cannot be solved keeps its pose.  The poses must be within reach of the ICP
+    (max_dist): this polishes pose guesses, it does not find a pose from nothing."""
+    what = "align_views_to_volume"
+    if not isinstance(vol, TsdfVolume):
+        raise ValueError(f"{what}: vol must be a TsdfVolume, got {type(vol).__name__}")
+    if masks is None:
+        raise ValueError(f"{what}: masks are required")
+    iterations = _check_iterations(iterations, what)
+    ops._check_icp(max_dist, 1e-3, 64, what)
+    d, _, m, P, K = _views_in(None, depths, masks, ob_in_cams, Ks, vol.device, what)
+    side = _AlignSide(vol, d, m, K)
+    P, _ = side.align(P.contiguous(), side.vt, iterations, max_dist)
+    return P, ops.IcpStep.rows(side.bufs[int(d.shape[0])][1])
+
+
 def reconstruct_object(rgbs, depths, masks, ob_in_cams, Ks, voxel=None, trunc=None, margin=None, min_weight=1, min_depth=0.001,
                        longest=128, device="cuda", texture=None, texture_min_cos=0.2, refine_poses=0, refine_iterations=3,
-                       refine_max_dist=0.01):
+                       refine_max_dist=0.01, refine_against="mesh"):
     """V posed RGB-D reference views with masks -> (SimpleMesh, mesh_tensors) of the object, in the frame of the poses: the box of the
     masked depths (bounds_from_views) -> a TsdfVolume over it -> fuse -> extract.  voxel=None picks the pitch that gives the longest
     side `longest` voxels; margin defaults to three voxels around the observed points; trunc to four voxels.  texture=T (2..16) bakes a
@@ -236,7 +370,9 @@ def reconstruct_object(rgbs, depths, masks, ob_in_cams, Ks, voxel=None, trunc=No
     tensors then carry the atlas in place of the vertex colours alone.  refine_poses=R (default 0: the poses are trusted as given): R
     rounds of refine_view_poses of every view against the fused mesh (refine_iterations steps, pairs within refine_max_dist), each
     followed by a fresh fusion of the same volume from the refined poses and a new extraction; the texture is baked with the refined
-    poses, and the mesh carries them as mesh.ob_in_cams ((V,4,4) float32).  ValueError, naming the cause, when there are no views, the
+    poses, and the mesh carries them as mesh.ob_in_cams ((V,4,4) float32).  refine_against="volume" polishes the views
+    against the volume itself in those rounds (align_views_to_volume: no mesh is extracted between the rounds, only once at the end);
+    "mesh" (the default) is the path described above.  ValueError, naming the cause, when there are no views, the
     masks are empty or no surface was found."""
     what = "reconstruct_object"
     n = len(depths) if depths is not None else 0
@@ -246,6 +382,8 @@ def reconstruct_object(rgbs, depths, masks, ob_in_cams, Ks, voxel=None, trunc=No
         raise ValueError(f"{what}: rgbs and masks are required")
     if isinstance(refine_poses, bool) or not isinstance(refine_poses, (int, np.integer)) or int(refine_poses) < 0:
         raise ValueError(f"{what}: refine_poses must be an int >= 0, got {refine_poses!r}")
+    if refine_against not in ("mesh", "volume"):
+        raise ValueError(f"{what}: refine_against must be 'mesh' or 'volume', got {refine_against!r}")
     if texture is not None:
         ops.texture_atlas_layout(1, texture)          # a block side outside 2..16 is refused before the fusion
     d, c, m, P, K = _views_in(rgbs, depths, masks, ob_in_cams, Ks, device, what)
@@ -259,11 +397,17 @@ def reconstruct_object(rgbs, depths, masks, ob_in_cams, Ks, voxel=None, trunc=No
     nx, ny, nz = (int(np.ceil(e / voxel - 1e-9)) + 1 for e in (hi - lo))
     vol = TsdfVolume(lo, (nz, ny, nx), voxel, trunc, device, min_depth)
     vol._integrate(d, c, m, P, K)
+    by_volume = refine_against == "volume" and int(refine_poses) > 0
+    side = _AlignSide(vol, d, m, K) if by_volume else None          # the views' side once for all rounds
+    for _ in range(int(refine_poses) if by_volume else 0):          # no mesh and no host read between the rounds: one extraction, below
+        P, _ = side.align(P.contiguous(), side.vt, int(refine_iterations), refine_max_dist, min_weight)
+        vol.reset()
+        vol._integrate(d, c, m, P, K)
     try:
         mesh, tensors = vol.extract(min_weight)
     except ValueError as e:
-        raise ValueError(f"{what}: no surface found in the {n} views ({e})") from None
-    for _ in range(int(refine_poses)):
+        raise ValueError(f"{what}: no surface found in the {n} views" + (" after refining their poses" if by_volume else "") + f" ({e})") from None
+    for _ in range(0 if by_volume else int(refine_poses)):
         P, _ = _refine_views(tensors, d, m, P, K, int(refine_iterations), refine_max_dist)
         vol.reset()
         vol._integrate(d, c, m, P, K)

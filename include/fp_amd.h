@@ -87,8 +87,10 @@ const char* fp_last_error(void);
  *   225 -> 226: + fp_icp_point_plane, fp_icp_workspace_bytes (additions only): one Gauss-Newton step of point-to-plane ICP per
  *               hypothesis, the render of a pose against the observed depth.
  *   226 -> 227: + FP_IGEMM_DIRECT_STORE / FP_IGEMM_W_TILES_DIRECT, fp_pack_conv3x3_tiles_direct_f16 (additions only; an older library
- *               refuses the bits as unknown flags). */
-#define FP_AMD_ABI_VERSION 227
+ *               refuses the bits as unknown flags).
+ *   227 -> 228: + fp_tsdf_raycast (addition only): depth, points, normals and colours of a TSDF volume's zero surface at any pose, in
+ *               the layout fp_icp_point_plane and fp_depth_agreement read. */
+#define FP_AMD_ABI_VERSION 228
 int fp_version(void);
 
 /* Utils.py:104-130 make_mesh_tensors: records caller-owned device tensors.
@@ -360,6 +362,58 @@ int fp_tsdf_emit_triangles(const float* tsdf /*dev*/, const float* weight /*dev*
                            const float* color_weight /*dev*/, int nz, int ny, int nx, const float* origin /*host 3*/, float voxel,
                            float min_weight, const int64_t* offsets /*dev, one per cube*/, long long total, int64_t* keys /*dev 3*total*/,
                            float* pos /*dev 3*total,3*/, float* col /*dev 3*total,3*/, float* nrm /*dev 3*total,3*/, void* stream);
+/* The zero surface of a TSDF volume (the arrays, nz / ny / nx, origin and voxel of fp_tsdf_integrate) seen from N poses: per crop pixel
+ * the depth, the camera-frame point, the camera-frame unit normal and the colour of the first crossing of tsdf from >= 0 to < 0 along the
+ * pixel's ray.  The pixel convention is the rasteriser's (fp_render_crops), so depth / xyz / normal drop into fp_depth_agreement and
+ * fp_icp_point_plane beside the same tf_to_crops as a render of the extracted mesh does.  Every operation is float32 without
+ * contraction, one rounding per operation, in the order written; every 3-term sum is (a0*b0 + a1*b1) + a2*b2.
+ * Per row n: T = poses[n] (object to camera, taken as rigid: R its 3x3 block, t its last column); {fx, skew, cx, fy, cy} from K (one
+ * camera on the host, Ks NULL) or from Ks[view[n]] (the float32 table of fp_render_crops_views, K NULL; view NULL means view 0, allowed
+ * for V == 1); (umin, vmin, umax, vmax) = bbox2d[n], or (0, 0, W, H) with bbox2d NULL (which requires oh == H and ow == W).  The row is all
+ * misses when one of T's 16 values, fx, fy, cx or cy is not finite, when the table's skew is not 0, when view[n] is outside 0..V-1, or
+ * when the volume has a dimension of 1 (no cells).  Otherwise
+ *   ax = (float)ow / (umax - umin),  ay = (float)oh / (vmax - vmin);   o_k = -((R0k*t0 + R1k*t1) + R2k*t2)   (o = -R^T t),
+ * and per crop pixel (i, j), i along x:
+ *   u = umin + ((float)i + 0.5f) / ax,  v = vmin + ((float)j + 0.5f) / ay   (full frame: exactly i + 0.5, j + 0.5);
+ *   dc = ((u - cx) / fx, (v - cy) / fy, 1);   d_k = (R0k*dc.x + R1k*dc.y) + R2k   (d = R^T dc).
+ * A point of the ray is o + z * d per component, z its camera depth.
+ * Clipping: z0 = z_near, z1 = z_far; per axis a (x, y, z) with lo = origin_a and hi = origin_a + (float)(n_a - 1) * voxel:
+ *   d_a == 0: the pixel is a miss unless lo <= o_a && o_a <= hi (inside that slab for every z);
+ *   otherwise t1 = (lo - o_a) / d_a, t2 = (hi - o_a) / d_a, tmin = t1 < t2 ? t1 : t2, tmax = t1 < t2 ? t2 : t1,
+ *     z0 = tmin > z0 ? tmin : z0,  z1 = tmax < z1 ? tmax : z1;
+ * the pixel is a miss unless z0 <= z1.
+ * March: samples k = 0, 1, ... at z_k = z0 + (float)k * step while z_k <= z1 (and k < FP_TSDF_RAYCAST_MAX_SAMPLES, which a rigid pose
+ * never reaches: see the argument errors).  A sample: per axis q = ((o_a + z_k * d_a) - lo) / voxel, c_a = floorf(q), f_a = q - c_a.  It is
+ * unknown unless 0 <= c_a <= n_a - 2 on every axis and weight >= min_weight at all eight corners of cell (c_x, c_y, c_z); otherwise its
+ * value is the trilinear interpolation of tsdf: with lerp(a, b, t) = a + t * (b - a) and V[dx][dy][dz] the corner values,
+ *   lerp(lerp(lerp(V000, V100, f_x), lerp(V010, V110, f_x), f_y), lerp(lerp(V001, V101, f_x), lerp(V011, V111, f_x), f_y), f_z).
+ * An unknown sample forgets the previous one.  A known sample f < 0 ends the ray: as a hit when the sample before it was known (it
+ * was >= 0: "0 is outside", as in the extraction), as a miss otherwise (the first known sample after the start or after an unknown
+ * stretch: the surface is met from behind).  On a hit z* = z_prev + step * (f_prev / (f_prev - f)); there is no refinement sample.
+ * Outputs on a hit: depth = z*; xyz = (z* * dc.x, z* * dc.y, z*); with q, c_a, f_a of the point o + z* * d as above, c_a clamped to
+ * 0..n_a-2 (cf = floorf(q); cf = cf >= 0 ? cf : 0; cf = cf <= n_a-2 ? cf : n_a-2; f_a = q - cf) and the weights not consulted:
+ *   normal: the gradient fp_tsdf_emit_triangles defines at each corner voxel, interpolated trilinearly per component as above, g;
+ *     len = sqrtf((g.x*g.x + g.y*g.y) + g.z*g.z);  m = g / len per component;  normal_k = (Rk0*m.x + Rk1*m.y) + Rk2*m.z;  (0, 0, 0) unless
+ *     len > 0 (the m.m > 0 test of fp_icp_point_plane then drops the pixel);
+ *   color: over the corners in the order dx + 2 dy + 4 dz = 0..7 with color_weight > 0: w = (wx * wy) * wz with wx = dx ? f_x : 1 - f_x
+ *     and likewise; acc = acc + w * color per channel, accw = accw + w (both from 0); color = acc / accw, or 128 unless accw > 0.
+ * A miss writes 0 to every output.  Each of depth (N,oh,ow), xyz, normal, color (N,oh,ow,3) may be NULL; every element of the others is
+ * written exactly once and nothing else is.  One lane per crop pixel, no atomics, no workspace, no allocation, no host synchronisation
+ * (graph-capturable; origin and K are read during the call); every call repeats its bits, and a row has the bits of a call on it alone.
+ * No index outside the volume is formed.  N == 0 does nothing.
+ * Argument errors (FP_ERR_INVALID_ARG): a NULL volume array or origin; every output NULL; NULL poses with N > 0; a dimension outside
+ * 1..FP_TSDF_MAX_DIM or more than 2^30 voxels; an origin that is not finite; voxel or step not finite or not > 0; z_near < 0,
+ * z_far < z_near, or either not finite; min_weight not finite; N outside 0..65535; oh / ow / H / W below 1; more than 2^20 crop pixels;
+ * bbox2d NULL with oh != H or ow != W; both or neither of K and Ks; a non-zero skew in K; view with K; V < 1 or view NULL with V > 1
+ * (with Ks); a step so short that the volume's diagonal sqrt((nx-1)^2 + (ny-1)^2 + (nz-1)^2) * voxel holds more than
+ * FP_TSDF_RAYCAST_MAX_SAMPLES - 2 of it (a ray's stretch inside the box is at most the diagonal, as |d| >= 1 for a rigid pose). */
+#define FP_TSDF_RAYCAST_MAX_SAMPLES 65536
+int fp_tsdf_raycast(const float* tsdf /*dev nz,ny,nx*/, const float* weight /*dev nz,ny,nx*/, const float* color /*dev nz,ny,nx,3*/,
+                    const float* color_weight /*dev nz,ny,nx*/, int nz, int ny, int nx, const float* origin /*host 3*/, float voxel,
+                    float min_weight, const float* poses /*dev N,16*/, const float* K /*host 9|NULL*/, const float* Ks /*dev V,9|NULL*/,
+                    const int32_t* view /*dev N|NULL*/, int V, const float* bbox2d /*dev N,4|NULL*/, int H, int W, int N, int oh, int ow,
+                    float step, float z_near, float z_far, float* depth /*dev N,oh,ow|NULL*/, float* xyz /*dev N,oh,ow,3|NULL*/,
+                    float* normal /*dev N,oh,ow,3|NULL*/, float* color_out /*dev N,oh,ow,3|NULL*/, void* stream);
 /* A texture atlas for a mesh from posed RGB-D reference views (those its TSDF volume was fused from): every texel is a point of one
  * face, coloured from the views that see it.  The atlas is per triangle: face f owns the T x T texel block at block column f % Bx and
  * block row f / Bx, so Wt = Bx * T, Ht = ceil(F / Bx) * T, and texel (i, j) of the block (i along x) is tex[(f / Bx) * T + j][(f % Bx) *

@@ -94,6 +94,8 @@ def main(argv=None):
     ap.add_argument("--ref_texture", type=int, default=0, help="with --ref_views: bake a texture atlas of T x T texels a face (2..16)")
     ap.add_argument("--ref_refine_poses", type=int, default=0,
                     help="with --ref_views: rounds of polishing the view poses against the fused mesh (point-to-plane ICP) and fusing again")
+    ap.add_argument("--ref_refine_against", choices=("mesh", "volume"), default="mesh",
+                    help="with --ref_refine_poses: polish the view poses against the extracted mesh, or against the volume itself (raycast)")
     ap.add_argument("--save_mesh", type=str, default=None, help="write the mesh that is used to this PLY (or .obj: OBJ + MTL + PNG)")
     args = ap.parse_args(argv)
     logging.basicConfig(level=logging.INFO, format="[%(funcName)s()] %(message)s")
@@ -123,7 +125,7 @@ def main(argv=None):
         from foundationpose_amd.reconstruct import reconstruct_object
         t0 = time.perf_counter()
         mesh, _ = reconstruct_object(*read_ref_views(args.ref_views), device=dev, texture=args.ref_texture or None,
-                                     refine_poses=args.ref_refine_poses)
+                                     refine_poses=args.ref_refine_poses, refine_against=args.ref_refine_against)
         atlas = getattr(getattr(mesh.visual, "material", None), "image", None)
         logging.info(f"mesh from {args.ref_views}: {len(mesh.vertices)} vertices, {len(mesh.faces)} faces"
                      + ("" if atlas is None else f", atlas {atlas.shape[0]} x {atlas.shape[1]}")
