@@ -56,7 +56,8 @@ class FoundationPose:
         other mesh (kwargs: scorer, refiner, symmetry_tfs, device, ...).  Poses come out in the frame of ob_in_cams; reset_object
         centres the mesh as usual (model_center).  With reconstruct_args={"refine_poses": R} the view poses are polished against the
         fused mesh first (with "refine_against": "volume" beside it, against the volume itself); the estimator keeps them as ref_ob_in_cams
-        ((V,4,4) float32; None without)."""
+        ((V,4,4) float32; None without).  reconstruct_args={"keep_components": "largest"} (or an int: the fewest triangles of a
+        surface component that stays) drops floaters from the mesh at every extraction of the call."""
         from .reconstruct import reconstruct_object
         args = dict(reconstruct_args or {})
         args.setdefault("device", kwargs.get("device", "cuda"))

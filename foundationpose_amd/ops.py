@@ -1055,19 +1055,76 @@ def tsdf_integrate(tsdf, weight, color, color_weight, depth, rgb, masks, ob_in_c
                                             _stream(d)), "fp_tsdf_integrate")
 
 
-def tsdf_extract(tsdf, weight, color, color_weight, origin, voxel, min_weight=1.0):
+def tsdf_components(counts, dims):
+    """fp_tsdf_label_components: the face-connected components of the cubes with triangles (include/fp_amd.h has the definition).
+    counts: fp_tsdf_count_triangles' int32 device tensor, one element per cube of a volume of dims = (nz, ny, nx) voxels, in any shape
+    -> (labels, sizes), int32 device tensors shaped (nz-1, ny-1, nx-1): labels = the smallest cube index of a cube's component, -1
+    where counts <= 0; sizes = the component's triangles at that smallest cube, 0 elsewhere.  Integer atomics only: the same bits every
+    time.  Three launches, no synchronisation: capturable in a graph (the two outputs are allocated before them)."""
+    what = "tsdf_components"
+    try:
+        nz, ny, nx = (int(n) for n in dims)
+    except (TypeError, ValueError):
+        raise ValueError(f"{what}: dims must be (nz, ny, nx), got {dims!r}") from None
+    if min(nz, ny, nx) < 1 or max(nz, ny, nx) > TSDF_MAX_DIM or nz * ny * nx > 1 << 30:
+        raise _lib.FpAmdError(f"{what}: a volume of {(nz, ny, nx)} voxels; every dimension must be 1..{TSDF_MAX_DIM} and their product <= 2^30")
+    if not torch.is_tensor(counts):
+        raise _lib.FpAmdError(f"{what}: counts must be a tensor, got {type(counts).__name__}")
+    shape = (nz - 1, ny - 1, nx - 1)
+    if counts.numel() != shape[0] * shape[1] * shape[2]:
+        raise _lib.FpAmdError(f"{what}: counts has {counts.numel()} elements, a volume of {(nz, ny, nx)} voxels has {shape[0] * shape[1] * shape[2]} cubes")
+    n = _dev(counts, torch.int32, "counts")
+    labels = torch.empty(shape, dtype=torch.int32, device=n.device)
+    sizes = torch.empty(shape, dtype=torch.int32, device=n.device)
+    _lib.check(_lib.lib().fp_tsdf_label_components(_ptr(n), nz, ny, nx, _ptr(labels), _ptr(sizes), _stream(n)), "fp_tsdf_label_components")
+    return labels, sizes
+
+
+def _check_keep(what, keep, name="keep"):
+    """keep of tsdf_extract: None | 'largest' | an int >= 1"""
+    if keep is None or (isinstance(keep, str) and keep == "largest"):
+        return keep
+    if isinstance(keep, bool) or not isinstance(keep, (int, np.integer)) or int(keep) < 1:
+        raise ValueError(f"{what}: {name} must be None, 'largest' or an int >= 1 (the fewest triangles of a component that stays), got {keep!r}")
+    return int(keep)
+
+
+def _component_report(what, labels, sizes, keep):
+    """-> (sizes of all components as a descending host list, labels of the kept ones as a device tensor); one host read"""
+    roots = torch.nonzero(sizes.reshape(-1) > 0).reshape(-1)              # ascending labels
+    tri = sizes.reshape(-1)[roots]
+    host = tri.cpu().numpy().astype(np.int64)
+    if host.size == 0:
+        return [], roots
+    if keep == "largest":
+        kept = roots[int(np.argmax(host)):][:1]                            # argmax: the first of equals, the smaller label
+    else:
+        if int(host.max()) < keep:
+            raise ValueError(f"{what}: keep={keep} triangles, the largest of the {host.size} components has {int(host.max())}")
+        kept = roots[tri >= keep]
+    return sorted((int(x) for x in host), reverse=True), kept
+
+
+def tsdf_extract(tsdf, weight, color, color_weight, origin, voxel, min_weight=1.0, keep=None):
     """The surface of a TSDF volume (arrays, origin and voxel as in tsdf_integrate) as a welded triangle mesh on the device, by
     marching tetrahedra over the cubes whose corners all have weight >= min_weight (fp_tsdf_count_triangles -> torch.cumsum -> one
     host read of the total -> fp_tsdf_emit_triangles -> torch.unique over the corners' grid-edge keys; include/fp_amd.h has the
     definition) -> dict(pos (U,3) f32, vnormals (U,3) f32, vertex_color (U,3) f32 in the units of color, faces (T,3) int32), the
     vertices in the order of their sorted keys and the faces in the order cube, tetrahedron, table: the same bits every time.  No surface
     gives U = T = 0.  The host read of the total makes this a setup call: it synchronises and cannot be captured in a graph.
+    keep drops floaters: None (the default) keeps every triangle and launches nothing more; 'largest' keeps the face-connected
+    component of cubes (tsdf_components) with the most triangles, the one with the smaller label among equals; an int n >= 1 keeps
+    every component of at least n triangles (ValueError, naming the largest, when none has that many).  The kept mesh is the
+    unfiltered one without the dropped cubes' triangles: the triangles in their order, the vertices in the order of the sorted keys
+    of the corners that remain; the dict then also holds components (the triangles of every component, a descending host list) and
+    dropped_triangles.  Only the mesh is filtered: the volume stays as fused.
     Refusals in tsdf_integrate's order."""
     what = "tsdf_extract"
     dims, o, s = _tsdf_grid(what, tsdf, weight, color, color_weight, origin, voxel)
     mw = float(min_weight)
     if not np.isfinite(mw):
         raise ValueError(f"{what}: min_weight must be finite, got {min_weight!r}")
+    keep = _check_keep(what, keep)
     f, w, c, cw = [_dev(t, torch.float32, name) for name, t in (("tsdf", tsdf), ("weight", weight), ("color", color), ("color_weight", color_weight))]
     dev, L, st = f.device, _lib.lib(), _stream(f)
     nz, ny, nx = dims
@@ -1078,21 +1135,36 @@ def tsdf_extract(tsdf, weight, color, color_weight, origin, voxel, min_weight=1.
         _lib.check(L.fp_tsdf_count_triangles(_ptr(f), _ptr(w), nz, ny, nx, mw, _ptr(counts), st), "fp_tsdf_count_triangles")
         ends = torch.cumsum(counts, 0, dtype=torch.int64)
         total = int(ends[-1].item())
+    report = {} if keep is None else dict(components=[], dropped_triangles=0)
     if total == 0:
         e = torch.empty((0, 3), dtype=torch.float32, device=dev)
-        return dict(pos=e, vnormals=e.clone(), vertex_color=e.clone(), faces=torch.empty((0, 3), dtype=torch.int32, device=dev))
+        return dict(report, pos=e, vnormals=e.clone(), vertex_color=e.clone(), faces=torch.empty((0, 3), dtype=torch.int32, device=dev))
     if total > 1 << 29:
         raise _lib.FpAmdError(f"{what}: {total} triangles, more than 2^29: use a coarser volume")
+    keep_cube = None
+    if keep is not None:
+        labels, sizes = tsdf_components(counts, dims)
+        report["components"], kept = _component_report(what, labels, sizes, keep)
+        is_kept = torch.zeros((ncubes,), dtype=torch.bool, device=dev)
+        is_kept[kept] = True
+        labels = labels.reshape(-1)
+        keep_cube = (labels >= 0) & is_kept[labels.clamp(min=0).long()]
     offsets = (ends - counts).contiguous()
     keys = torch.empty((3 * total,), dtype=torch.int64, device=dev)
     pos, col, nrm = (torch.empty((3 * total, 3), dtype=torch.float32, device=dev) for _ in range(3))
     _lib.check(L.fp_tsdf_emit_triangles(_ptr(f), _ptr(w), _ptr(c), _ptr(cw), nz, ny, nx, o.ctypes.data_as(C.c_void_p), s, mw, _ptr(offsets),
                                         total, _ptr(keys), _ptr(pos), _ptr(col), _ptr(nrm), st), "fp_tsdf_emit_triangles")
+    if keep_cube is not None:
+        # the rows of the kept cubes' triangles, in their order; what is welded below is what remains
+        rows = torch.repeat_interleave(keep_cube, counts.long(), output_size=total).repeat_interleave(3)
+        keys, pos, col, nrm = keys[rows], pos[rows], col[rows], nrm[rows]
+        report["dropped_triangles"] = total - int(keys.numel()) // 3
+        total = int(keys.numel()) // 3
     uk, inv = torch.unique(keys, return_inverse=True)
     # every corner on one grid edge carries the same bits; the first of them stands for the vertex
     first = torch.full((int(uk.numel()),), 3 * total, dtype=torch.int64, device=dev)
     first.scatter_reduce_(0, inv, torch.arange(3 * total, dtype=torch.int64, device=dev), "amin")
-    return dict(pos=pos[first], vnormals=nrm[first], vertex_color=col[first], faces=inv.reshape(total, 3).to(torch.int32))
+    return dict(report, pos=pos[first], vnormals=nrm[first], vertex_color=col[first], faces=inv.reshape(total, 3).to(torch.int32))
 
 
 RAYCAST_OUTPUTS = ("depth", "xyz", "normal", "color")
@@ -1921,6 +1993,7 @@ mask_depth_stats = _timed("fp_mask_depth_stats", mask_depth_stats)
 depth_agreement = _timed("fp_depth_agreement", depth_agreement)
 pose_errors = _timed("fp_pose_errors", pose_errors)
 icp_point_plane = _timed("fp_icp_point_plane", icp_point_plane)
+tsdf_components = _timed("fp_tsdf_label_components", tsdf_components)
 vsd_counts = _timed("fp_vsd_counts", vsd_counts)
 mspd = _timed("fp_mspd", mspd)
 layernorm_res = _timed("fp_layernorm_res_fwd", layernorm_res,

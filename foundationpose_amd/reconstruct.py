@@ -3,12 +3,12 @@ fusion and marching tetrahedra on the device (ops.tsdf_integrate / ops.tsdf_extr
 where the reference trains a neural object field (bundlesdf/, not built: DESIGN.md section 7): what setup hands to FoundationPose is a
 mesh in the object frame either way.  Colours are per vertex, as coarse as the voxel pitch; bake_texture (reconstruct_object's
 texture=T) adds a per-triangle texture atlas blended from the same views at their own resolution (ops.texture_bake).  There is no
-simplification and no removal of small components: the masks do the carving, and the views are assumed to show the object
-unoccluded."""
+simplification: the masks do the carving, and the views are assumed to show the object unoccluded.  What the carving leaves behind
+as a floater can be dropped from the mesh at extraction (keep= / keep_components=: ops.tsdf_components); the volume stays as fused."""
 import numpy as np
 import torch
 
-from . import ops
+from . import _lib, ops
 from .mesh import SimpleMesh
 
 PAD_VOXELS = 3          # voxels kept free around the observed points, so that the surface closes inside the volume
@@ -94,14 +94,34 @@ class TsdfVolume:
     def _integrate(self, d, c, m, P, K):
         ops.tsdf_integrate(*self.arrays(), d, c, m, P, K, self.origin, self.voxel, self.trunc, self.min_depth)
 
-    def extract(self, min_weight=1):
+    def components(self, min_weight=1):
+        """the surface components extract(keep=...) chooses among, without extracting (ops.tsdf_components over the cubes'
+        triangle counts) -> dict(labels (nz-1,ny-1,nx-1) int32 on the device: the smallest cube index of each cube's face-connected
+        component, -1 where the cube has no triangle; components: the triangles of every component, a descending host list).  A
+        setup call (it synchronises)."""
+        nz, ny, nx = self.dims
+        shape = (max(nz - 1, 0), max(ny - 1, 0), max(nx - 1, 0))
+        mw = float(min_weight)
+        if not np.isfinite(mw):
+            raise ValueError(f"TsdfVolume.components: min_weight must be finite, got {min_weight!r}")
+        if 0 in shape:
+            return dict(labels=torch.empty(shape, dtype=torch.int32, device=self.device), components=[])
+        counts = torch.empty(shape, dtype=torch.int32, device=self.device)
+        _lib.check(_lib.lib().fp_tsdf_count_triangles(ops._ptr(self.tsdf), ops._ptr(self.weight), nz, ny, nx, mw, ops._ptr(counts),
+                                                      ops._stream(self.tsdf)), "fp_tsdf_count_triangles")
+        labels, sizes = ops.tsdf_components(counts, self.dims)
+        sizes = sizes[sizes > 0].cpu().numpy()
+        return dict(labels=labels, components=sorted((int(x) for x in sizes), reverse=True))
+
+    def extract(self, min_weight=1, keep=None):
         """the surface over the voxels observed at least min_weight times -> (SimpleMesh with uint8 vertex colours, mesh_tensors):
         the second is the device dict FoundationPose and the rasteriser take (pos, vnormals, faces, vertex_color in [0,1], _handle),
         made from the extraction's device tensors without a host round trip, with the colours rounded to the mesh's uint8 ones: the
-        bits make_mesh_tensors(mesh) would give.  A setup call (it synchronises).  ValueError when the
-        volume holds no surface."""
+        bits make_mesh_tensors(mesh) would give.  keep ('largest' or the fewest triangles of a component that stays; ops.tsdf_extract)
+        drops floaters from the mesh, not from the volume; the mesh then carries components (the triangles of every component found,
+        descending) and dropped_triangles.  A setup call (it synchronises).  ValueError when the volume holds no surface."""
         from .Utils import mesh_handle_from_tensors
-        out = ops.tsdf_extract(*self.arrays(), self.origin, self.voxel, min_weight)
+        out = ops.tsdf_extract(*self.arrays(), self.origin, self.voxel, min_weight, keep)
         if int(out["faces"].shape[0]) == 0:
             raise ValueError("TsdfVolume.extract: no surface in the volume (no voxel pair on both sides of a surface was observed "
                              f"{min_weight} times: check the poses, the masks and the volume's bounds)")
@@ -111,6 +131,8 @@ class TsdfVolume:
         cols = cols.to(torch.uint8).cpu().numpy()
         mesh = SimpleMesh(out["pos"].cpu().numpy(), out["faces"].cpu().numpy(), vertex_normals=out["vnormals"].cpu().numpy(),
                           vertex_colors=cols)
+        if keep is not None:
+            mesh.components, mesh.dropped_triangles = out["components"], out["dropped_triangles"]
         return mesh, t
 
     def raycast(self, ob_in_cams, K, size, bbox2d=None, step=None, min_weight=1, z_near=0.001, z_far=None,
@@ -362,7 +384,7 @@ def align_views_to_volume(vol, depths, masks, ob_in_cams, Ks, iterations=3, max_
 
 def reconstruct_object(rgbs, depths, masks, ob_in_cams, Ks, voxel=None, trunc=None, margin=None, min_weight=1, min_depth=0.001,
                        longest=128, device="cuda", texture=None, texture_min_cos=0.2, refine_poses=0, refine_iterations=3,
-                       refine_max_dist=0.01, refine_against="mesh"):
+                       refine_max_dist=0.01, refine_against="mesh", keep_components=None):
     """V posed RGB-D reference views with masks -> (SimpleMesh, mesh_tensors) of the object, in the frame of the poses: the box of the
     masked depths (bounds_from_views) -> a TsdfVolume over it -> fuse -> extract.  voxel=None picks the pitch that gives the longest
     side `longest` voxels; margin defaults to three voxels around the observed points; trunc to four voxels.  texture=T (2..16) bakes a
@@ -372,7 +394,10 @@ def reconstruct_object(rgbs, depths, masks, ob_in_cams, Ks, voxel=None, trunc=No
     followed by a fresh fusion of the same volume from the refined poses and a new extraction; the texture is baked with the refined
     poses, and the mesh carries them as mesh.ob_in_cams ((V,4,4) float32).  refine_against="volume" polishes the views
     against the volume itself in those rounds (align_views_to_volume: no mesh is extracted between the rounds, only once at the end);
-    "mesh" (the default) is the path described above.  ValueError, naming the cause, when there are no views, the
+    "mesh" (the default) is the path described above.  keep_components ('largest', or the fewest triangles of a surface component
+    that stays; None keeps all) drops floaters at every extraction of the call, those of the refine_poses rounds included
+    (TsdfVolume.extract's keep): the mesh then carries components and dropped_triangles.  The volume is left as fused, so the
+    rounds of refine_against="volume" still see a floater.  ValueError, naming the cause, when there are no views, the
     masks are empty or no surface was found."""
     what = "reconstruct_object"
     n = len(depths) if depths is not None else 0
@@ -384,6 +409,7 @@ def reconstruct_object(rgbs, depths, masks, ob_in_cams, Ks, voxel=None, trunc=No
         raise ValueError(f"{what}: refine_poses must be an int >= 0, got {refine_poses!r}")
     if refine_against not in ("mesh", "volume"):
         raise ValueError(f"{what}: refine_against must be 'mesh' or 'volume', got {refine_against!r}")
+    keep_components = ops._check_keep(what, keep_components, "keep_components")
     if texture is not None:
         ops.texture_atlas_layout(1, texture)          # a block side outside 2..16 is refused before the fusion
     d, c, m, P, K = _views_in(rgbs, depths, masks, ob_in_cams, Ks, device, what)
@@ -404,19 +430,26 @@ def reconstruct_object(rgbs, depths, masks, ob_in_cams, Ks, voxel=None, trunc=No
         vol.reset()
         vol._integrate(d, c, m, P, K)
     try:
-        mesh, tensors = vol.extract(min_weight)
+        mesh, tensors = vol.extract(min_weight, keep_components)
     except ValueError as e:
+        if "no surface" not in str(e):             # keep_components asks for more triangles than any component has
+            raise
         raise ValueError(f"{what}: no surface found in the {n} views" + (" after refining their poses" if by_volume else "") + f" ({e})") from None
     for _ in range(0 if by_volume else int(refine_poses)):
         P, _ = _refine_views(tensors, d, m, P, K, int(refine_iterations), refine_max_dist)
         vol.reset()
         vol._integrate(d, c, m, P, K)
         try:
-            mesh, tensors = vol.extract(min_weight)
+            mesh, tensors = vol.extract(min_weight, keep_components)
         except ValueError as e:
+            if "no surface" not in str(e):
+                raise
             raise ValueError(f"{what}: no surface found in the {n} views after refining their poses ({e})") from None
+    report = (mesh.components, mesh.dropped_triangles) if keep_components is not None else None
     if texture is not None:
         mesh, tensors = _bake(tensors, d, c, m, P, K, int(texture), 2.0 * voxel, texture_min_cos, min_depth)
+    if report is not None:
+        mesh.components, mesh.dropped_triangles = report
     if int(refine_poses) > 0:
         mesh.ob_in_cams = P.cpu().numpy()
     return mesh, tensors

@@ -89,8 +89,10 @@ const char* fp_last_error(void);
  *   226 -> 227: + FP_IGEMM_DIRECT_STORE / FP_IGEMM_W_TILES_DIRECT, fp_pack_conv3x3_tiles_direct_f16 (additions only; an older library
  *               refuses the bits as unknown flags).
  *   227 -> 228: + fp_tsdf_raycast (addition only): depth, points, normals and colours of a TSDF volume's zero surface at any pose, in
- *               the layout fp_icp_point_plane and fp_depth_agreement read. */
-#define FP_AMD_ABI_VERSION 228
+ *               the layout fp_icp_point_plane and fp_depth_agreement read.
+ *   228 -> 229: + fp_tsdf_label_components (addition only): the face-connected components of a volume's surface cubes and their
+ *               triangle counts, for dropping floaters at extraction. */
+#define FP_AMD_ABI_VERSION 229
 int fp_version(void);
 
 /* Utils.py:104-130 make_mesh_tensors: records caller-owned device tensors.
@@ -362,6 +364,25 @@ int fp_tsdf_emit_triangles(const float* tsdf /*dev*/, const float* weight /*dev*
                            const float* color_weight /*dev*/, int nz, int ny, int nx, const float* origin /*host 3*/, float voxel,
                            float min_weight, const int64_t* offsets /*dev, one per cube*/, long long total, int64_t* keys /*dev 3*total*/,
                            float* pos /*dev 3*total,3*/, float* col /*dev 3*total,3*/, float* nrm /*dev 3*total,3*/, void* stream);
+/* The surface components of a volume's cubes, for dropping floaters at extraction.  counts is fp_tsdf_count_triangles' output for a
+ * volume of nz x ny x nx voxels: one int32 per cube, c = (cz * (ny-1) + cy) * (nx-1) + cx.
+ *   A cube is active when counts[c] > 0.
+ *   Two active cubes are adjacent when exactly one of cx, cy, cz differs, by 1: they share a face.
+ *   A component is a maximal set of active cubes connected through adjacent pairs.
+ *   labels[c] (int32) = the smallest cube index of c's component, or -1 for a cube that is not active.
+ *   sizes[c] (int32) = the sum of counts over the component when labels[c] == c, and 0 everywhere else (an extraction has at most
+ *     2^29 triangles, so it fits).
+ * Faces are enough: two triangles that share a mesh edge lie in the same tetrahedron face, and that face belongs either to one cube or
+ * to two face-adjacent cubes that both emitted triangles.  So every edge-connected piece of the mesh lies inside one component, and
+ * dropping a component removes whole closed surfaces and opens nothing in what is kept.
+ * Union-find over the cube array with integer atomics only (min and +), so both outputs have one value whatever the scheduling: the
+ * definition's, bit for bit.  A volume with a dimension of 1 has no cubes: nothing is written.  No allocation, no host synchronisation
+ * and no memset (every element of both outputs is written by the kernels; graph-capturable); nothing is written outside labels and
+ * sizes.  The volume itself is not touched: fp_tsdf_raycast still sees what a dropped component was extracted from.
+ * Argument errors (FP_ERR_INVALID_ARG), before any launch: a dimension outside 1..FP_TSDF_MAX_DIM or more than 2^30 voxels; NULL counts /
+ * labels / sizes when there are cubes. */
+int fp_tsdf_label_components(const int32_t* counts /*dev (nz-1)(ny-1)(nx-1)*/, int nz, int ny, int nx,
+                             int32_t* labels /*dev, one per cube*/, int32_t* sizes /*dev, one per cube*/, void* stream);
 /* The zero surface of a TSDF volume (the arrays, nz / ny / nx, origin and voxel of fp_tsdf_integrate) seen from N poses: per crop pixel
  * the depth, the camera-frame point, the camera-frame unit normal and the colour of the first crossing of tsdf from >= 0 to < 0 along the
  * pixel's ray.  The pixel convention is the rasteriser's (fp_render_crops), so depth / xyz / normal drop into fp_depth_agreement and

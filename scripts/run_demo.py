@@ -7,6 +7,7 @@ checkpoints under $FOUNDATIONPOSE_WEIGHTS.  Visualisation (debug >= 1 overlays) 
 Without a CAD model: `--ref_views DIR` (a directory in the same layout whose frames each carry a mask and an annotated pose) fuses the
 object's mesh from those reference views (foundationpose_amd/reconstruct.py) in place of --mesh_file; `--synthetic_ref_views N` writes
 such a directory from the can first; `--ref_texture T` bakes a texture atlas of T x T texels a face onto that mesh from the same views;
+`--ref_keep_components largest|N` drops floaters from it (all but the largest surface component, or those under N triangles);
 `--save_mesh PATH` writes the mesh that was used: a PLY (positions, normals, vertex colours), or with a path ending in .obj an OBJ with
 its MTL and the texture as a PNG."""
 import argparse
@@ -96,6 +97,9 @@ def main(argv=None):
                     help="with --ref_views: rounds of polishing the view poses against the fused mesh (point-to-plane ICP) and fusing again")
     ap.add_argument("--ref_refine_against", choices=("mesh", "volume"), default="mesh",
                     help="with --ref_refine_poses: polish the view poses against the extracted mesh, or against the volume itself (raycast)")
+    ap.add_argument("--ref_keep_components", type=lambda v: v if v == "largest" else int(v), default=None, metavar="{largest,N}",
+                    help="with --ref_views: drop floaters from the fused mesh: keep the surface component with the most triangles, or every "
+                         "component of at least N triangles")
     ap.add_argument("--save_mesh", type=str, default=None, help="write the mesh that is used to this PLY (or .obj: OBJ + MTL + PNG)")
     args = ap.parse_args(argv)
     logging.basicConfig(level=logging.INFO, format="[%(funcName)s()] %(message)s")
@@ -121,15 +125,20 @@ def main(argv=None):
         ap.error("--mesh_file (or --ref_views) and --test_scene_dir are required (or --synthetic N)")
     if args.ref_refine_poses and not args.ref_views:
         ap.error("--ref_refine_poses needs --ref_views (or --synthetic_ref_views N)")
+    if args.ref_keep_components is not None and not args.ref_views:
+        ap.error("--ref_keep_components needs --ref_views (or --synthetic_ref_views N)")
     if args.ref_views:
         from foundationpose_amd.reconstruct import reconstruct_object
         t0 = time.perf_counter()
         mesh, _ = reconstruct_object(*read_ref_views(args.ref_views), device=dev, texture=args.ref_texture or None,
-                                     refine_poses=args.ref_refine_poses, refine_against=args.ref_refine_against)
+                                     refine_poses=args.ref_refine_poses, refine_against=args.ref_refine_against,
+                                     keep_components=args.ref_keep_components)
         atlas = getattr(getattr(mesh.visual, "material", None), "image", None)
         logging.info(f"mesh from {args.ref_views}: {len(mesh.vertices)} vertices, {len(mesh.faces)} faces"
                      + ("" if atlas is None else f", atlas {atlas.shape[0]} x {atlas.shape[1]}")
-                     + (f", view poses refined {args.ref_refine_poses} x" if args.ref_refine_poses else "") + f" in {time.perf_counter() - t0:.2f} s")
+                     + (f", view poses refined {args.ref_refine_poses} x" if args.ref_refine_poses else "")
+                     + ("" if args.ref_keep_components is None else f", {len(mesh.components)} surface components, {mesh.dropped_triangles} triangles dropped")
+                     + f" in {time.perf_counter() - t0:.2f} s")
     else:
         mesh = load_mesh(args.mesh_file)
     if args.ref_texture and not args.ref_views:
