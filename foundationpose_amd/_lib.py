@@ -10,7 +10,7 @@ import torch  # noqa: F401  (must precede CDLL: shares the HIP runtime with PyTo
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("FP_AMD_LIB") or os.path.join(_HERE, "csrc", "libfp_amd.so")   # FP_AMD_LIB: A/B builds
-ABI_VERSION = 229    # = FP_AMD_ABI_VERSION of include/fp_amd.h (tests/test_abi.py keeps the two in step)
+ABI_VERSION = 230    # = FP_AMD_ABI_VERSION of include/fp_amd.h (tests/test_abi.py keeps the two in step)
 _lib = None
 
 vp, ci, cf, cd, sz = C.c_void_p, C.c_int, C.c_float, C.c_double, C.c_size_t
@@ -27,16 +27,11 @@ SIGNATURES = {
     "fp_depth_erode": (ci, [vp, vp, ci, ci, ci, cf, cf, cf, vp]),
     "fp_depth_bilateral": (ci, [vp, vp, ci, ci, ci, cf, cf, cf, vp]),
     "fp_depth_to_xyz": (ci, [vp, vp, cf, ci, vp, ci, ci, vp]),
-    "fp_crop_windows": (ci, [vp, vp, cd, cd, ci, ci, ci, vp, vp, vp]),
-    "fp_crop_windows_multi": (ci, [vp, vp, vp, vp, ci, cd, ci, ci, ci, vp, vp, vp]),
+    "fp_crop_windows": (ci, [vp, vp, vp, vp, ci, cd, vp, vp, ci, cd, ci, ci, ci, vp, vp, vp]),
     "fp_depth_erode_frames": (ci, [vp, vp, ci, ci, ci, ci, cf, cf, cf, vp]),
     "fp_depth_bilateral_frames": (ci, [vp, vp, ci, ci, ci, ci, cf, cf, cf, vp]),
     "fp_depth_to_xyz_frames": (ci, [vp, vp, cf, ci, vp, ci, ci, ci, vp]),
     "fp_mask_depth_stats": (ci, [vp, vp, vp, ci, ci, ci, ci, cf, vp, vp]),
-    "fp_crop_windows_views": (ci, [vp, vp, vp, ci, vp, vp, ci, cd, ci, ci, ci, vp, vp, vp]),
-    "fp_render_crops_views": (ci, [vp, vp, vp, vp, vp, ci, vp, vp, ci, ci, ci, ci, ci, cf, cf, cf, ci, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]),
-    "fp_warp_crops_views": (ci, [vp, vp, vp, vp, vp, vp, ci, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, ci, vp, vp]),
-    "fp_pose_update_views": (ci, [vp, vp, vp, ci, ci, vp, cf, vp, vp, ci, ci, vp, vp, vp, ci, vp, vp, ci, vp, cf, vp]),
     "fp_depth_agreement": (ci, [vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, cf, vp, vp]),
     "fp_icp_workspace_bytes": (sz, [ci, ci, ci]),
     "fp_icp_point_plane": (ci, [vp, vp, vp, vp, vp, ci, ci, ci, vp, ci, ci, ci, cf, cd, ci, vp, vp, vp, sz, vp]),
@@ -52,12 +47,9 @@ SIGNATURES = {
     "fp_texture_bake": (ci, [vp, ci, vp, ci, vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, cf, cf, cf, vp, vp, vp]),
     "fp_workspace_bytes": (sz, [ci, ci, ci, ci, ci]),
     "fp_raster_lds_bytes": (sz, [ci]),
-    "fp_render_crops": (ci, [vp, vp, vp, vp, ci, ci, ci, ci, ci, cf, cf, cf, cf, ci, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]),
-    "fp_render_crops_multi": (ci, [vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, cf, cf, cf, ci, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]),
-    "fp_warp_crops": (ci, [vp, vp, vp, vp, vp, vp, cf, ci, ci, ci, ci, ci, ci, ci, vp, vp]),
-    "fp_warp_crops_multi": (ci, [vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, ci, vp, vp]),
-    "fp_pose_update": (ci, [vp, vp, vp, ci, ci, vp, cf, cf, ci, vp, vp, vp, ci, vp, vp, cf, vp]),
-    "fp_pose_update_multi": (ci, [vp, vp, vp, ci, ci, vp, cf, vp, vp, ci, ci, vp, vp, vp, ci, vp, vp, cf, vp]),
+    "fp_render_crops": (ci, [vp, vp, vp, vp, cf, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, cf, cf, cf, ci, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]),
+    "fp_warp_crops": (ci, [vp, vp, vp, vp, vp, vp, vp, ci, vp, cf, vp, vp, ci, ci, ci, ci, ci, ci, ci, ci, vp, vp]),
+    "fp_pose_update": (ci, [vp, vp, vp, ci, ci, vp, cf, cf, vp, vp, ci, ci, vp, vp, vp, ci, vp, vp, vp, ci, vp, cf, vp]),
     "fp_conv7x7s2_bn_relu_fwd": (ci, [vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, vp]),
     "fp_igemm_f16_fwd": (ci, [vp, vp, vp, vp, vp, ci, ci, ci, ci, vp, vp]),
     "fp_pack_conv3x3_tiles_f16": (ci, [vp, vp, ci, ci, vp]),

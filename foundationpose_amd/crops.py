@@ -26,7 +26,7 @@ class Scene:
                     raise ValueError(f"{who}: with views, the ObjectIndex must be built with view=views.host "
                                      "(the two-pose quirk is grouped per (view, object))")
         self.mesh, self.K, self.H, self.W, self.n, self.views = mesh, K, int(H), int(W), n, views
-        # the one float-versus-table decision: a table goes to the *_multi / *_views entry points, anything else is one object's float
+        # the one float-versus-table decision: a table is the entry points' diameter table, anything else is one object's float
         self.diameter = diameter if torch.is_tensor(diameter) else float(diameter)
         self.obj = obj.dev if isinstance(obj, ops.PairRows) else obj
         # the index that knows the quirk's groups, and where this scene's rows start in it

@@ -116,15 +116,15 @@ __global__ void k_depth_to_xyz(const float* __restrict__ depth, fp_k9d K1, float
 }
 
 // ---------------------------------------------------------------- a5+a6 (Utils.py:577-621, float64 internals)
-// per-object diameters (the *_multi entry points): diam[obj[n]] (obj NULL: diam[0]); an index outside 0..M-1 reads as NaN
+// per-object diameters (a call with a diameter table): diam[obj[n]] (obj NULL: diam[0]); an index outside 0..M-1 reads as NaN
 __device__ __forceinline__ double diameter_of(const double* __restrict__ diam, const int32_t* __restrict__ obj, int M, int n) {
   const int o = obj ? obj[n] : 0;
   return (unsigned)o < (unsigned)M ? diam[o] : __builtin_nan("");
 }
 
-// MULTI: the radius of hypothesis n is diam[obj[n]] * crop_ratio / 2, the expression fp_crop_windows evaluates on the host (f64,
-// no contraction: the same bits); otherwise `radius`.  VIEWS: K of hypothesis n = the f64 table entry of view[n] (one lane per
-// hypothesis: a per-lane read); an index outside 0..V-1 gives NaN K, so NaN windows
+// MULTI: the radius of hypothesis n is diam[obj[n]] * crop_ratio / 2, the expression fp_crop_windows evaluates on the host for
+// its scalar form (f64, no contraction: the same bits); otherwise `radius`.  VIEWS: K of hypothesis n = the f64 table entry of
+// view[n] (one lane per hypothesis: a per-lane read); an index outside 0..V-1 gives NaN K, so NaN windows
 template <bool MULTI, typename... VT>
 __global__ void k_crop_windows(const float* __restrict__ poses, fp_k9d K1, double radius1, const double* __restrict__ diam,
                                const int32_t* __restrict__ obj, int M, double crop_ratio, int out_w, int out_h,
@@ -476,51 +476,38 @@ extern "C" int fp_depth_to_xyz_frames(const float* depth, const double* Ks, floa
   return FP_OK;
 }
 
-extern "C" int fp_crop_windows(const float* poses, const double* K, double mesh_diameter, double crop_ratio,
+// The crop stage's scene arguments (K | Ks / view / V; mesh_diameter | diameters / obj / M) are checked by fp_check_objects and
+// fp_check_views (fp_common.h); FP_LAUNCH_FORM names the instantiation each form runs.
+extern "C" int fp_crop_windows(const float* poses, const double* K, const double* Ks, const int32_t* view, int V,
+                               double mesh_diameter, const double* diameters, const int32_t* obj, int M, double crop_ratio,
                                int out_w, int out_h, int N, float* tf_to_crops, float* bbox2d, void* stream) {
-  FP_REQUIRE(N >= 0, "fp_crop_windows: N < 0");
+  const char* name = "fp_crop_windows";
+  const bool objects = fp_has_objects(diameters, obj, M), views = fp_has_views(Ks, view, V);
+  FP_REQUIRE(N >= 0, "%s: N < 0", name);
+  if (objects) if (const int st = fp_check_objects(name, diameters, obj, M)) return st;
+  if (views) if (const int st = fp_check_views(name, K, Ks, view, V, objects)) return st;
   if (N == 0) return FP_OK;
-  FP_REQUIRE(poses && K && tf_to_crops && bbox2d && out_w > 1 && out_h > 1, "fp_crop_windows: bad arguments");
-  fp_k9d Kd;
-  for (int i = 0; i < 9; ++i) Kd.v[i] = K[i];
-  const double radius = mesh_diameter * crop_ratio / 2.0;
-  hipLaunchKernelGGL(k_crop_windows<false>, dim3(fp_cdiv(N, 64)), dim3(64), 0, (hipStream_t)stream, poses, Kd, radius,
-                     nullptr, nullptr, 0, 0.0, out_w, out_h, N, tf_to_crops, bbox2d);
-  FP_CHECK_LAUNCH("fp_crop_windows");
-  return FP_OK;
-}
-
-extern "C" int fp_crop_windows_multi(const float* poses, const double* K, const double* diameters, const int32_t* obj, int M,
-                                     double crop_ratio, int out_w, int out_h, int N, float* tf_to_crops, float* bbox2d,
-                                     void* stream) {
-  FP_REQUIRE(N >= 0, "fp_crop_windows_multi: N < 0");
-  FP_REQUIRE(M >= 1 && diameters, "fp_crop_windows_multi: need the diameters of M >= 1 objects (M=%d)", M);
-  FP_REQUIRE(obj || M == 1, "fp_crop_windows_multi: obj is NULL but there are %d objects", M);
-  if (N == 0) return FP_OK;
-  FP_REQUIRE(poses && K && tf_to_crops && bbox2d && out_w > 1 && out_h > 1, "fp_crop_windows_multi: bad arguments");
-  fp_k9d Kd;
-  for (int i = 0; i < 9; ++i) Kd.v[i] = K[i];
-  hipLaunchKernelGGL(k_crop_windows<true>, dim3(fp_cdiv(N, 64)), dim3(64), 0, (hipStream_t)stream, poses, Kd, 0.0, diameters,
-                     obj, M, crop_ratio, out_w, out_h, N, tf_to_crops, bbox2d);
-  FP_CHECK_LAUNCH("fp_crop_windows_multi");
-  return FP_OK;
-}
-
-extern "C" int fp_crop_windows_views(const float* poses, const double* Ks, const int32_t* view, int V, const double* diameters,
-                                     const int32_t* obj, int M, double crop_ratio, int out_w, int out_h, int N, float* tf_to_crops,
-                                     float* bbox2d, void* stream) {
-  FP_REQUIRE(N >= 0, "fp_crop_windows_views: N < 0");
-  FP_REQUIRE(V >= 1 && Ks, "fp_crop_windows_views: need the K table of V >= 1 views (V=%d)", V);
-  FP_REQUIRE(view || V == 1, "fp_crop_windows_views: view is NULL but there are %d views", V);
-  FP_REQUIRE(M >= 1 && diameters, "fp_crop_windows_views: need the diameters of M >= 1 objects (M=%d)", M);
-  FP_REQUIRE(obj || M == 1, "fp_crop_windows_views: obj is NULL but there are %d objects", M);
-  if (N == 0) return FP_OK;
-  FP_REQUIRE(poses && tf_to_crops && bbox2d && out_w > 1 && out_h > 1, "fp_crop_windows_views: bad arguments");
-  const fp_k9d unused = {};
-  const fp_views vt = {Ks, view, V};
-  hipLaunchKernelGGL((k_crop_windows<true, fp_views>), dim3(fp_cdiv(N, 64)), dim3(64), 0, (hipStream_t)stream, poses, unused, 0.0,
-                     diameters, obj, M, crop_ratio, out_w, out_h, N, tf_to_crops, bbox2d, vt);
-  FP_CHECK_LAUNCH("fp_crop_windows_views");
+  FP_REQUIRE(K || views, "%s: neither K nor a view table (Ks) is given", name);
+  FP_REQUIRE(poses && tf_to_crops && bbox2d && out_w > 1 && out_h > 1, "%s: bad arguments", name);
+  fp_k9d Kd = {};
+  if (K) for (int i = 0; i < 9; ++i) Kd.v[i] = K[i];
+  // the scalar form passes its radius and no ratio, the table forms the ratio and no radius: the arguments of the three
+  // instantiations are what they always were
+  const double radius = objects ? 0.0 : mesh_diameter * crop_ratio / 2.0, ratio = objects ? crop_ratio : 0.0;
+  const dim3 grid(fp_cdiv(N, 64)), block(64);
+  const hipStream_t st = (hipStream_t)stream;
+  if (!objects) {
+    hipLaunchKernelGGL(k_crop_windows<false>, grid, block, 0, st, poses, Kd, radius, diameters, obj, M, ratio, out_w, out_h, N,
+                       tf_to_crops, bbox2d);
+  } else if (!views) {
+    hipLaunchKernelGGL(k_crop_windows<true>, grid, block, 0, st, poses, Kd, radius, diameters, obj, M, ratio, out_w, out_h, N,
+                       tf_to_crops, bbox2d);
+  } else {
+    const fp_views vt = {Ks, view, V};
+    hipLaunchKernelGGL((k_crop_windows<true, fp_views>), grid, block, 0, st, poses, Kd, radius, diameters, obj, M, ratio, out_w,
+                       out_h, N, tf_to_crops, bbox2d, vt);
+  }
+  FP_CHECK_LAUNCH(name);
   return FP_OK;
 }
 
@@ -529,7 +516,7 @@ static int pose_update_launch(const char* name, const float* trans, const float*
                               int normalize_xyz, const float* trans_normalizer, float rot_normalizer, float mesh_diameter,
                               const double* diam, const int32_t* obj, int M, int N, float* poses_out, float* trans_delta_out,
                               float* rot_delta_out, int trans_rep, const float* K9, const float* tf_to_crops, float input_w,
-                              void* stream, const fp_views& vt = fp_views{nullptr, nullptr, 0}) {
+                              void* stream, const fp_views& vt) {
   FP_REQUIRE(trans && rot && poses_in && poses_out, "%s: NULL tensor", name);
   FP_REQUIRE(rot_rep == FP_ROT_AXIS_ANGLE || rot_rep == FP_ROT_6D, "%s: unknown rot_rep %d", name, rot_rep);
   FP_REQUIRE(trans_rep == FP_TRANS_TRACKNET || trans_rep == FP_TRANS_DEEPIM || trans_rep == FP_TRANS_RAW, "%s: unknown trans_rep %d", name, trans_rep);
@@ -551,46 +538,21 @@ static int pose_update_launch(const char* name, const float* trans, const float*
   return FP_OK;
 }
 
-extern "C" int fp_pose_update(const float* trans, const float* rot, const float* poses_in, int rot_rep,
-                              int normalize_xyz, const float* trans_normalizer, float rot_normalizer,
-                              float mesh_diameter, int N, float* poses_out, float* trans_delta_out, float* rot_delta_out,
-                              int trans_rep, const float* K9, const float* tf_to_crops, float input_w, void* stream) {
-  FP_REQUIRE(N >= 0, "fp_pose_update: N < 0");
-  if (N == 0) return FP_OK;
-  return pose_update_launch<false>("fp_pose_update", trans, rot, poses_in, rot_rep, normalize_xyz, trans_normalizer,
-                                   rot_normalizer, mesh_diameter, nullptr, nullptr, 0, N, poses_out, trans_delta_out,
-                                   rot_delta_out, trans_rep, K9, tf_to_crops, input_w, stream);
-}
-
-extern "C" int fp_pose_update_multi(const float* trans, const float* rot, const float* poses_in, int rot_rep,
-                                    int normalize_xyz, const float* trans_normalizer, float rot_normalizer,
-                                    const double* diameters, const int32_t* obj, int M, int N, float* poses_out,
-                                    float* trans_delta_out, float* rot_delta_out, int trans_rep, const float* K9,
-                                    const float* tf_to_crops, float input_w, void* stream) {
-  FP_REQUIRE(N >= 0, "fp_pose_update_multi: N < 0");
-  FP_REQUIRE(M >= 1 && diameters, "fp_pose_update_multi: need the diameters of M >= 1 objects (M=%d)", M);
-  FP_REQUIRE(obj || M == 1, "fp_pose_update_multi: obj is NULL but there are %d objects", M);
-  if (N == 0) return FP_OK;
-  return pose_update_launch<true>("fp_pose_update_multi", trans, rot, poses_in, rot_rep, normalize_xyz, trans_normalizer,
-                                  rot_normalizer, 0.f, diameters, obj, M, N, poses_out, trans_delta_out, rot_delta_out,
-                                  trans_rep, K9, tf_to_crops, input_w, stream);
-}
-
-extern "C" int fp_pose_update_views(const float* trans, const float* rot, const float* poses_in, int rot_rep,
-                                    int normalize_xyz, const float* trans_normalizer, float rot_normalizer,
-                                    const double* diameters, const int32_t* obj, int M, int N, float* poses_out,
-                                    float* trans_delta_out, float* rot_delta_out, int trans_rep, const float* Ks,
-                                    const int32_t* view, int V, const float* tf_to_crops, float input_w, void* stream) {
-  FP_REQUIRE(N >= 0, "fp_pose_update_views: N < 0");
-  FP_REQUIRE(V >= 1 && Ks, "fp_pose_update_views: need the K table of V >= 1 views (V=%d)", V);
-  FP_REQUIRE(view || V == 1, "fp_pose_update_views: view is NULL but there are %d views", V);
-  FP_REQUIRE(M >= 1 && diameters, "fp_pose_update_views: need the diameters of M >= 1 objects (M=%d)", M);
-  FP_REQUIRE(obj || M == 1, "fp_pose_update_views: obj is NULL but there are %d objects", M);
+extern "C" int fp_pose_update(const float* trans, const float* rot, const float* poses_in, int rot_rep, int normalize_xyz,
+                              const float* trans_normalizer, float rot_normalizer, float mesh_diameter, const double* diameters,
+                              const int32_t* obj, int M, int N, float* poses_out, float* trans_delta_out, float* rot_delta_out,
+                              int trans_rep, const float* K, const float* Ks, const int32_t* view, int V,
+                              const float* tf_to_crops, float input_w, void* stream) {
+  const char* name = "fp_pose_update";
+  const bool objects = fp_has_objects(diameters, obj, M), views = fp_has_views(Ks, view, V);
+  FP_REQUIRE(N >= 0, "%s: N < 0", name);
+  if (objects) if (const int st = fp_check_objects(name, diameters, obj, M)) return st;
+  if (views) if (const int st = fp_check_views(name, K, Ks, view, V, objects)) return st;
   if (N == 0) return FP_OK;
   const fp_views vt = {Ks, view, V};
-  return pose_update_launch<true, true>("fp_pose_update_views", trans, rot, poses_in, rot_rep, normalize_xyz, trans_normalizer,
-                                        rot_normalizer, 0.f, diameters, obj, M, N, poses_out, trans_delta_out, rot_delta_out,
-                                        trans_rep, nullptr, tf_to_crops, input_w, stream, vt);
+  return FP_LAUNCH_FORM(objects, views, pose_update_launch, name, trans, rot, poses_in, rot_rep, normalize_xyz, trans_normalizer,
+                        rot_normalizer, objects ? 0.f : mesh_diameter, diameters, obj, M, N, poses_out, trans_delta_out,
+                        rot_delta_out, trans_rep, K, tf_to_crops, input_w, stream, vt);
 }
 
 extern "C" int fp_mask_depth_stats(const float* depth, const uint8_t* masks, const int32_t* view, int V, int M, int H, int W,

@@ -226,8 +226,8 @@ struct RenderWs {
   int vstride, tstride;    // mesh set: the V / T of a hypothesis' rows above = the set's largest (one mesh: its own V / T)
 };
 
-// Where a kernel finds the mesh of hypothesis n.  MULTI = false (fp_render_crops): the one mesh, passed by value; the table is
-// unused and the instantiation is the single-mesh kernel.  MULTI = true (fp_render_crops_multi): entry obj[n] of the set's device
+// Where a kernel finds the mesh of hypothesis n.  MULTI = false (fp_render_crops with `mesh`): the one mesh, passed by value; the
+// table is unused and the instantiation is the single-mesh kernel.  MULTI = true (with `set`): entry obj[n] of the set's device
 // table (obj NULL: entry 0).  n = blockIdx.y, so the address is wave-uniform and the 72-byte descriptor comes in with scalar loads,
 // once per workgroup.  An index outside 0..M-1 reads as an empty mesh (nothing drawn) with a NaN diameter.
 struct MeshTable {
@@ -242,8 +242,8 @@ __device__ __forceinline__ int obj_of(const MeshTable& tab, int n) {
   return (unsigned)o < (unsigned)tab.M ? o : -1;
 }
 
-// VIEWS (fp_render_crops_views, always with MULTI): hypothesis n also reads its K from entry view[n] of the (V, 9) table, with the
-// same uniform scalar loads as the descriptor; a view index outside 0..V-1 reads as an empty mesh too (nothing drawn)
+// VIEWS (a call with a view table, always with MULTI): hypothesis n also reads its K from entry view[n] of the (V, 9) table, with
+// the same uniform scalar loads as the descriptor; a view index outside 0..V-1 reads as an empty mesh too (nothing drawn)
 template <bool MULTI, bool VIEWS = false>
 __device__ __forceinline__ fp_mesh mesh_of(const fp_mesh& one, const MeshTable& tab, int n, const fp_views& vt = fp_views{}) {
   if (!MULTI) return one;
@@ -612,14 +612,13 @@ extern "C" size_t fp_mesh_set_workspace_bytes(const fp_mesh_set* set, int N, int
   return fp_workspace_bytes(N, set->maxV, set->maxT, oh, ow);
 }
 
-// the three launches of one render, shared by fp_render_crops (MULTI = false: `one`, maxV = V, maxT = T),
-// fp_render_crops_multi (MULTI = true: the set's table, grids sized by its largest mesh) and fp_render_crops_views (VIEWS = true:
-// K from the view table `vt`, K9 unused)
+// the three launches of one render.  MULTI = false: the one mesh `one`, maxV = V, maxT = T; MULTI = true: the set's table `tab`,
+// grids sized by its largest mesh; VIEWS = true: K from the view table `vt`, K9 unused
 template <bool MULTI, bool VIEWS = false>
 static int render_launch(const char* name, const fp_mesh& one, const MeshTable& tab, int maxV, int maxT, const float* poses,
                          const float* bbox2d, const float* K9, int H, int W, int N, int oh, int ow, float w_ambient,
                          float w_diffuse, float inv_r, float xyz_thr, int flags, const RenderOut& out, void* workspace,
-                         size_t workspace_bytes, hipStream_t st, const fp_views& vt = fp_views{nullptr, nullptr, 0}) {
+                         size_t workspace_bytes, hipStream_t st, const fp_views& vt) {
   FP_REQUIRE(oh > 0 && ow > 0 && oh <= 1024 && ow <= 1024, "%s: output size %dx%d unsupported (max 1024)", name, oh, ow);
   FP_REQUIRE(bbox2d || (oh == H && ow == W), "%s: full-frame render needs oh==H and ow==W", name);
   FP_REQUIRE(N <= 65535, "%s: N=%d exceeds the grid limit; chunk the batch", name, N);
@@ -641,17 +640,17 @@ static int render_launch(const char* name, const fp_mesh& one, const MeshTable& 
   const size_t lds = fp_raster_lds_bytes(ow);
   if constexpr (VIEWS) {
     hipLaunchKernelGGL((k_vertex<MULTI, fp_views>), gv, dim3(256), 0, st, one, tab, poses, bbox2d, K, H, W, oh, ow, L.nstrips, ws, vt);
-    FP_CHECK_LAUNCH("fp_render_crops_views(vertex)");
+    FP_CHECK_LAUNCH("fp_render_crops(vertex)");
     hipLaunchKernelGGL((k_bin<MULTI, fp_views>), gb, dim3(256), 0, st, one, tab, oh, ow, L.nstrips, ws, vt);
-    FP_CHECK_LAUNCH("fp_render_crops_views(bin)");
+    FP_CHECK_LAUNCH("fp_render_crops(bin)");
     FP_SET_MAX_LDS((k_raster<MULTI, fp_views>), 160 * 1024);
     hipLaunchKernelGGL((k_raster<MULTI, fp_views>), gr, dim3(FP_RASTER_THREADS), lds, st, one, tab, poses, bbox2d, K, H, W, oh, ow,
                        L.nstrips, w_ambient, w_diffuse, inv_r, xyz_thr, flags, out, ws, vt);
   } else {
     hipLaunchKernelGGL(k_vertex<MULTI>, gv, dim3(256), 0, st, one, tab, poses, bbox2d, K, H, W, oh, ow, L.nstrips, ws);
-    FP_CHECK_LAUNCH(MULTI ? "fp_render_crops_multi(vertex)" : "fp_render_crops(vertex)");
+    FP_CHECK_LAUNCH("fp_render_crops(vertex)");
     hipLaunchKernelGGL(k_bin<MULTI>, gb, dim3(256), 0, st, one, tab, oh, ow, L.nstrips, ws);
-    FP_CHECK_LAUNCH(MULTI ? "fp_render_crops_multi(bin)" : "fp_render_crops(bin)");
+    FP_CHECK_LAUNCH("fp_render_crops(bin)");
     FP_SET_MAX_LDS(k_raster<MULTI>, 160 * 1024);
     hipLaunchKernelGGL(k_raster<MULTI>, gr, dim3(FP_RASTER_THREADS), lds, st, one, tab, poses, bbox2d, K, H, W, oh, ow, L.nstrips,
                        w_ambient, w_diffuse, inv_r, xyz_thr, flags, out, ws);
@@ -660,60 +659,35 @@ static int render_launch(const char* name, const fp_mesh& one, const MeshTable& 
   return FP_OK;
 }
 
-extern "C" int fp_render_crops(const fp_mesh* mesh, const float* poses, const float* bbox2d, const float* K9, int H,
-                               int W, int N, int oh, int ow, float w_ambient, float w_diffuse, float mesh_diameter,
-                               float xyz_thr, int flags, void* A, float* color, float* depth, float* xyz,
-                               float* normal, uint32_t* zbuf, int32_t* tri_id, void* workspace,
-                               size_t workspace_bytes, void* stream) {
-  FP_REQUIRE(N >= 0, "fp_render_crops: N < 0");
-  FP_REQUIRE((flags & ~FP_RENDER_FLAG_MASK) == 0, "fp_render_crops: unknown flag bits 0x%x", flags & ~FP_RENDER_FLAG_MASK);
+// The object side of a render is one mesh with its scalar diameter, or a mesh set with obj and the diameter table (M is the
+// set's); a view table goes with the set.  The camera side is checked like the other crop-stage entry points' (fp_common.h).
+extern "C" int fp_render_crops(const fp_mesh* mesh, const fp_mesh_set* set, const int32_t* obj, const double* diameters,
+                               float mesh_diameter, const float* poses, const float* bbox2d, const float* K, const float* Ks,
+                               const int32_t* view, int V, int H, int W, int N, int oh, int ow, float w_ambient,
+                               float w_diffuse, float xyz_thr, int flags, void* A, float* color, float* depth, float* xyz,
+                               float* normal, uint32_t* zbuf, int32_t* tri_id, void* workspace, size_t workspace_bytes,
+                               void* stream) {
+  const char* name = "fp_render_crops";
+  const bool views = fp_has_views(Ks, view, V), objects = set || obj || diameters || (views && !mesh);
+  FP_REQUIRE(N >= 0, "%s: N < 0", name);
+  FP_REQUIRE((flags & ~FP_RENDER_FLAG_MASK) == 0, "%s: unknown flag bits 0x%x", name, flags & ~FP_RENDER_FLAG_MASK);
+  if (objects) {
+    FP_REQUIRE(set, "%s: NULL mesh set", name);
+    FP_REQUIRE(!mesh, "%s: both a mesh and a mesh set are given; pass exactly one", name);
+    FP_REQUIRE(obj || set->M == 1, "%s: obj is NULL but the set has %d meshes", name, set->M);
+    FP_REQUIRE(diameters || !(flags & FP_FLAG_NORMALIZE_XYZ), "%s: FP_FLAG_NORMALIZE_XYZ needs the diameters", name);
+  }
+  if (views) if (const int st = fp_check_views(name, K, Ks, view, V, objects)) return st;
   if (N == 0) return FP_OK;
-  FP_REQUIRE(mesh && poses && K9, "fp_render_crops: NULL mesh/poses/K");
-  const float inv_r = 1.0f / (mesh_diameter * 0.5f);
-  const MeshTable none = {nullptr, nullptr, nullptr, 0};
-  const RenderOut out = {A, color, depth, xyz, normal, zbuf, tri_id};
-  return render_launch<false>("fp_render_crops", *mesh, none, mesh->V, mesh->T, poses, bbox2d, K9, H, W, N, oh, ow, w_ambient,
-                              w_diffuse, inv_r, xyz_thr, flags, out, workspace, workspace_bytes, (hipStream_t)stream);
-}
-
-extern "C" int fp_render_crops_multi(const fp_mesh_set* set, const int32_t* obj, const double* diameters, const float* poses,
-                                     const float* bbox2d, const float* K9, int H, int W, int N, int oh, int ow, float w_ambient,
-                                     float w_diffuse, float xyz_thr, int flags, void* A, float* color, float* depth, float* xyz,
-                                     float* normal, uint32_t* zbuf, int32_t* tri_id, void* workspace, size_t workspace_bytes,
-                                     void* stream) {
-  FP_REQUIRE(N >= 0, "fp_render_crops_multi: N < 0");
-  FP_REQUIRE((flags & ~FP_RENDER_FLAG_MASK) == 0, "fp_render_crops_multi: unknown flag bits 0x%x", flags & ~FP_RENDER_FLAG_MASK);
-  FP_REQUIRE(set, "fp_render_crops_multi: NULL mesh set");
-  FP_REQUIRE(obj || set->M == 1, "fp_render_crops_multi: obj is NULL but the set has %d meshes", set->M);
-  FP_REQUIRE(diameters || !(flags & FP_FLAG_NORMALIZE_XYZ), "fp_render_crops_multi: FP_FLAG_NORMALIZE_XYZ needs the diameters");
-  if (N == 0) return FP_OK;
-  FP_REQUIRE(poses && K9, "fp_render_crops_multi: NULL poses/K");
+  FP_REQUIRE(mesh || set, "%s: NULL mesh set and NULL mesh; pass exactly one", name);
+  FP_REQUIRE(K || views, "%s: neither K nor a view table (Ks) is given", name);
+  FP_REQUIRE(poses, "%s: NULL poses", name);
   const fp_mesh none = {};
-  const MeshTable tab = {set->meshes, obj, diameters, set->M};
-  const RenderOut out = {A, color, depth, xyz, normal, zbuf, tri_id};
-  return render_launch<true>("fp_render_crops_multi", none, tab, set->maxV, set->maxT, poses, bbox2d, K9, H, W, N, oh, ow,
-                             w_ambient, w_diffuse, 0.f, xyz_thr, flags, out, workspace, workspace_bytes, (hipStream_t)stream);
-}
-
-extern "C" int fp_render_crops_views(const fp_mesh_set* set, const int32_t* obj, const double* diameters, const float* Ks,
-                                     const int32_t* view, int V, const float* poses, const float* bbox2d, int H, int W, int N, int oh,
-                                     int ow, float w_ambient, float w_diffuse, float xyz_thr, int flags, void* A, float* color,
-                                     float* depth, float* xyz, float* normal, uint32_t* zbuf, int32_t* tri_id, void* workspace,
-                                     size_t workspace_bytes, void* stream) {
-  FP_REQUIRE(N >= 0, "fp_render_crops_views: N < 0");
-  FP_REQUIRE((flags & ~FP_RENDER_FLAG_MASK) == 0, "fp_render_crops_views: unknown flag bits 0x%x", flags & ~FP_RENDER_FLAG_MASK);
-  FP_REQUIRE(set, "fp_render_crops_views: NULL mesh set");
-  FP_REQUIRE(obj || set->M == 1, "fp_render_crops_views: obj is NULL but the set has %d meshes", set->M);
-  FP_REQUIRE(diameters || !(flags & FP_FLAG_NORMALIZE_XYZ), "fp_render_crops_views: FP_FLAG_NORMALIZE_XYZ needs the diameters");
-  FP_REQUIRE(V >= 1 && Ks, "fp_render_crops_views: need the K table of V >= 1 views (V=%d)", V);
-  FP_REQUIRE(view || V == 1, "fp_render_crops_views: view is NULL but there are %d views", V);
-  if (N == 0) return FP_OK;
-  FP_REQUIRE(poses, "fp_render_crops_views: NULL poses");
-  const fp_mesh none = {};
-  const MeshTable tab = {set->meshes, obj, diameters, set->M};
+  const MeshTable tab = objects ? MeshTable{set->meshes, obj, diameters, set->M} : MeshTable{nullptr, nullptr, nullptr, 0};
+  const float inv_r = objects ? 0.f : 1.0f / (mesh_diameter * 0.5f);
   const RenderOut out = {A, color, depth, xyz, normal, zbuf, tri_id};
   const fp_views vt = {Ks, view, V};
-  return render_launch<true, true>("fp_render_crops_views", none, tab, set->maxV, set->maxT, poses, bbox2d, nullptr, H, W, N, oh,
-                                   ow, w_ambient, w_diffuse, 0.f, xyz_thr, flags, out, workspace, workspace_bytes,
-                                   (hipStream_t)stream, vt);
+  return FP_LAUNCH_FORM(objects, views, render_launch, name, objects ? none : *mesh, tab, objects ? set->maxV : mesh->V,
+                        objects ? set->maxT : mesh->T, poses, bbox2d, K, H, W, N, oh, ow, w_ambient, w_diffuse, inv_r, xyz_thr,
+                        flags, out, workspace, workspace_bytes, (hipStream_t)stream, vt);
 }

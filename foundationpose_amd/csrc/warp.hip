@@ -105,12 +105,13 @@ __device__ __forceinline__ void warp_pixel(const float* __restrict__ rgb, const 
 // operation, the integer division a multiply-shift.
 // (WarpConst and warp_const: crop_map.h)
 
-// Per-object diameters (fp_warp_crops_multi, MULTI = true): the same lane also computes 1 / (d / 2) of the hypothesis' object,
-// d = diam[obj[n]] rounded to float -- the host expression of fp_warp_crops (IEEE division, no contraction: the same bits).
+// Per-object diameters (fp_warp_crops with a diameter table, MULTI = true): the same lane also computes 1 / (d / 2) of the
+// hypothesis' object, d = diam[obj[n]] rounded to float -- the host expression of the scalar form (IEEE division, no contraction:
+// the same bits).
 struct WarpObjects { const double* diam; const int32_t* obj; int M; };
 
-// Several views (fp_warp_crops_views, VIEWS = true, always with MULTI): hypothesis n reads frame view[n] of the (V, H, W, C) stacks
-// and K = Ks[view[n]].  n = blockIdx.y, so the index and the 9 floats come in with uniform scalar loads, once per wave.  An index
+// Several views (fp_warp_crops with a view table, VIEWS = true, always with MULTI): hypothesis n reads frame view[n] of the
+// (V, H, W, C) stacks and K = Ks[view[n]].  n = blockIdx.y, so the index and the 9 floats come in with uniform scalar loads, once per wave.  An index
 // outside 0..V-1 reads nothing: the bounds of the frame become 0 x 0, so every pixel gets what a pixel outside the frame gets.
 template <int MODE, bool MULTI, typename... VT>
 __global__ __launch_bounds__(256) void k_warp(const float* __restrict__ rgb, const float* __restrict__ xyz_map,
@@ -175,7 +176,7 @@ __global__ __launch_bounds__(256) void k_warp(const float* __restrict__ rgb, con
 template <bool MULTI, bool VIEWS = false>
 static int warp_launch(const char* name, const float* rgb, const float* xyz_map, const float* depth, const float* tf_to_crops,
                        const float* K9, const float* poses, float inv_r, const WarpObjects& objs, int flags, int mode, int H,
-                       int W, int N, int oh, int ow, void* B, void* stream, const fp_views& vt = fp_views{nullptr, nullptr, 0}) {
+                       int W, int N, int oh, int ow, void* B, void* stream, const fp_views& vt) {
   FP_REQUIRE(rgb && tf_to_crops && (K9 || VIEWS) && poses && B, "%s: NULL tensor", name);
   FP_REQUIRE(H > 1 && W > 1 && oh > 1 && ow > 1, "%s: degenerate sizes", name);
   FP_REQUIRE(N <= 65535, "%s: N=%d exceeds the grid limit; chunk the batch", name, N);
@@ -206,44 +207,23 @@ static int warp_launch(const char* name, const float* rgb, const float* xyz_map,
 }
 
 extern "C" int fp_warp_crops(const float* rgb, const float* xyz_map, const float* depth, const float* tf_to_crops,
-                             const float* K9, const float* poses, float mesh_diameter, int flags, int mode, int H,
+                             const float* K, const float* Ks, const int32_t* view, int V, const float* poses,
+                             float mesh_diameter, const double* diameters, const int32_t* obj, int M, int flags, int mode, int H,
                              int W, int N, int oh, int ow, void* B, void* stream) {
-  FP_REQUIRE(N >= 0, "fp_warp_crops: N < 0");
-  if (N == 0) return FP_OK;
-  const float inv_r = 1.0f / (mesh_diameter * 0.5f);
-  const WarpObjects none = {nullptr, nullptr, 0};
-  return warp_launch<false>("fp_warp_crops", rgb, xyz_map, depth, tf_to_crops, K9, poses, inv_r, none, flags, mode, H, W, N,
-                            oh, ow, B, stream);
-}
-
-extern "C" int fp_warp_crops_multi(const float* rgb, const float* xyz_map, const float* depth, const float* tf_to_crops,
-                                   const float* K9, const float* poses, const double* diameters, const int32_t* obj, int M,
-                                   int flags, int mode, int H, int W, int N, int oh, int ow, void* B, void* stream) {
-  FP_REQUIRE(N >= 0, "fp_warp_crops_multi: N < 0");
-  FP_REQUIRE(M >= 1 && diameters, "fp_warp_crops_multi: need the diameters of M >= 1 objects (M=%d)", M);
-  FP_REQUIRE(obj || M == 1, "fp_warp_crops_multi: obj is NULL but there are %d objects", M);
-  if (N == 0) return FP_OK;
-  const WarpObjects objs = {diameters, obj, M};
-  return warp_launch<true>("fp_warp_crops_multi", rgb, xyz_map, depth, tf_to_crops, K9, poses, 0.f, objs, flags, mode, H, W,
-                           N, oh, ow, B, stream);
-}
-
-extern "C" int fp_warp_crops_views(const float* rgb, const float* xyz_map, const float* depth, const float* tf_to_crops,
-                                   const float* Ks, const int32_t* view, int V, const float* poses, const double* diameters,
-                                   const int32_t* obj, int M, int flags, int mode, int H, int W, int N, int oh, int ow, void* B,
-                                   void* stream) {
-  FP_REQUIRE(N >= 0, "fp_warp_crops_views: N < 0");
-  FP_REQUIRE((flags & ~(FP_FLAG_NORMALIZE_XYZ | FP_FLAG_OUT_F16)) == 0, "fp_warp_crops_views: unknown flag bits 0x%x",
+  const char* name = "fp_warp_crops";
+  const bool objects = fp_has_objects(diameters, obj, M), views = fp_has_views(Ks, view, V);
+  FP_REQUIRE(N >= 0, "%s: N < 0", name);
+  FP_REQUIRE((flags & ~(FP_FLAG_NORMALIZE_XYZ | FP_FLAG_OUT_F16)) == 0, "%s: unknown flag bits 0x%x", name,
              flags & ~(FP_FLAG_NORMALIZE_XYZ | FP_FLAG_OUT_F16));
-  FP_REQUIRE(V >= 1 && Ks, "fp_warp_crops_views: need the K table of V >= 1 views (V=%d)", V);
-  FP_REQUIRE(view || V == 1, "fp_warp_crops_views: view is NULL but there are %d views", V);
-  FP_REQUIRE(M >= 1 && diameters, "fp_warp_crops_views: need the diameters of M >= 1 objects (M=%d)", M);
-  FP_REQUIRE(obj || M == 1, "fp_warp_crops_views: obj is NULL but there are %d objects", M);
+  if (objects) if (const int st = fp_check_objects(name, diameters, obj, M)) return st;
+  if (views) if (const int st = fp_check_views(name, K, Ks, view, V, objects)) return st;
   if (N == 0) return FP_OK;
+  FP_REQUIRE(K || views, "%s: neither K nor a view table (Ks) is given", name);
+  const float inv_r = objects ? 0.f : 1.0f / (mesh_diameter * 0.5f);
   const WarpObjects objs = {diameters, obj, M};
   const fp_views vt = {Ks, view, V};
-  return warp_launch<true, true>("fp_warp_crops_views", rgb, xyz_map, depth, tf_to_crops, nullptr, poses, 0.f, objs, flags, mode,
-                                 H, W, N, oh, ow, B, stream, vt);
+  return FP_LAUNCH_FORM(objects, views, warp_launch, name, rgb, xyz_map, depth, tf_to_crops, K, poses, inv_r, objs, flags, mode,
+                        H, W, N, oh, ow, B, stream, vt);
 }
 
 // fp_depth_agreement: the render's depth of hypothesis n against the observed z the REFINE warp reads for the same crop pixel (the

@@ -170,8 +170,8 @@ class PairRows:
 
 
 class Views:
-    """The view table of a call over several camera frames of one size (the *_views entry points): hypothesis n reads frame view[n]
-    of the frame stacks and the intrinsics Ks[view[n]].  Built once from host data, like predict_pose_refine.ObjectIndex and Segments:
+    """The view table of a call over several camera frames of one size (the Ks / view / V of the C ABI): hypothesis n reads frame
+    view[n] of the frame stacks and the intrinsics Ks[view[n]].  Built once from host data, like predict_pose_refine.ObjectIndex and Segments:
     the (V, 9) K tables in float64 (crop windows, back-projection) and float32 (render, warp, pose update) -- exactly the values the
     single-view paths pass from the host -- and the int32 device index (None for one view without an index: all hypotheses view 0).
     `pairs` / pair_rows: the two-pose quirk grouped per view (every hypothesis one object; with several objects the ObjectIndex built
@@ -234,11 +234,24 @@ def _views(views, what, N=None):
     return views
 
 
-def _objects_views(mesh_diameter, obj, what):
+def _scene(what, N, K, mesh_diameter, obj, views, k64=False, need_K=True):
+    """The scene of a crop-stage call as the flat arguments its entry point takes (include/fp_amd.h, "The crop stage"):
+    camera = (K, Ks, view, V), one host K (float64 for crop windows, else float32; NULL when not needed) or the tables of an
+    ops.Views, and objects = (mesh_diameter, diameters, obj, M), one scalar or the table of object_diameters with the per-hypothesis
+    index.  Views go with the table."""
     objs = _objects(mesh_diameter, obj, what)
+    if views is not None:
+        vt = _views(views, what, N)
+        if objs is None:
+            raise _lib.FpAmdError(f"{what}: views need the per-object diameter table (object_diameters), not a scalar")
+        camera = (None, _ptr(vt.K64 if k64 else vt.K32), _ptr(vt.dev), vt.V)
+    else:
+        Kh = (_hostK64 if k64 else _hostK32)(K) if need_K else None
+        camera = (None if Kh is None else Kh.ctypes.data_as(C.c_void_p), None, None, 0)    # the pointer object keeps Kh alive
     if objs is None:
-        raise _lib.FpAmdError(f"{what}: views need the per-object diameter table (object_diameters), not a scalar")
-    return objs
+        return camera, (float(mesh_diameter) if k64 else float(np.float32(mesh_diameter)), None, None, 0)
+    d, o, M = objs
+    return camera, (0.0, _ptr(d), _ptr(o), M)
 
 
 def erode_depth(depth, radius=2, depth_diff_thres=0.001, ratio_thres=0.8, zfar=100.0):
@@ -351,31 +364,15 @@ def mask_depth_stats_host(stats):
 
 
 def crop_windows(poses, K, mesh_diameter, crop_ratio, out_size=(160, 160), obj=None, views=None):
-    """-> tf_to_crops (N,3,3) f32, bbox2d (N,4) f32.  out_size = (width, height).  Several objects: mesh_diameter = the (M,)
-    table of object_diameters, obj = the per-hypothesis object index (fp_crop_windows_multi).  Several views: views = an ops.Views
-    (K unused; fp_crop_windows_views)."""
+    """-> tf_to_crops (N,3,3) f32, bbox2d (N,4) f32 (fp_crop_windows).  out_size = (width, height).  Several objects: mesh_diameter =
+    the (M,) table of object_diameters, obj = the per-hypothesis object index.  Several views: views = an ops.Views (K unused)."""
     P = _dev(poses, torch.float32, "poses")
     N = int(P.shape[0])
     tf = torch.empty((N, 3, 3), dtype=torch.float32, device=P.device)
     bb = torch.empty((N, 4), dtype=torch.float32, device=P.device)
-    if views is not None:
-        vt = _views(views, "crop_windows", N)
-        d, o, M = _objects_views(mesh_diameter, obj, "crop_windows")
-        _lib.check(_lib.lib().fp_crop_windows_views(_ptr(P), _ptr(vt.K64), _ptr(vt.dev), vt.V, _ptr(d), _ptr(o), M, float(crop_ratio),
-                                                    int(out_size[0]), int(out_size[1]), N, _ptr(tf), _ptr(bb), _stream(P)),
-                   "fp_crop_windows_views")
-        return tf, bb
-    Kd = _hostK64(K)
-    objs = _objects(mesh_diameter, obj, "crop_windows")
-    if objs is None:
-        _lib.check(_lib.lib().fp_crop_windows(_ptr(P), Kd.ctypes.data_as(C.c_void_p), float(mesh_diameter),
-                                              float(crop_ratio), int(out_size[0]), int(out_size[1]), N, _ptr(tf), _ptr(bb),
-                                              _stream(P)), "fp_crop_windows")
-    else:
-        d, o, M = objs
-        _lib.check(_lib.lib().fp_crop_windows_multi(_ptr(P), Kd.ctypes.data_as(C.c_void_p), _ptr(d), _ptr(o), M, float(crop_ratio),
-                                                    int(out_size[0]), int(out_size[1]), N, _ptr(tf), _ptr(bb), _stream(P)),
-                   "fp_crop_windows_multi")
+    (Kp, Ks, view, V), (dia, d, o, M) = _scene("crop_windows", N, K, mesh_diameter, obj, views, k64=True)
+    _lib.check(_lib.lib().fp_crop_windows(_ptr(P), Kp, Ks, view, V, dia, d, o, M, float(crop_ratio), int(out_size[0]),
+                                          int(out_size[1]), N, _ptr(tf), _ptr(bb), _stream(P)), "fp_crop_windows")
     return tf, bb
 
 
@@ -412,19 +409,18 @@ def render_crops(mesh, poses, bbox2d, K, H, W, out_hw=(160, 160), mesh_diameter=
     """Fused render of N hypotheses (see fp_render_crops).  Returns dict of requested outputs.  workspace: caller-owned
     uint8 scratch of at least workspace_bytes(...) bytes (a captured hipGraph must own its scratch); default: a
     per-device scratch that grows on demand.  Several objects: mesh = a MeshSet, obj = the per-hypothesis object index, mesh_diameter =
-    the (M,) table of object_diameters (fp_render_crops_multi: hypothesis n draws mesh obj[n]).  Several views: views = an ops.Views
-    with a MeshSet (K unused; fp_render_crops_views: hypothesis n projects with K view[n])."""
+    the (M,) table of object_diameters (hypothesis n draws mesh obj[n]).  Several views: views = an ops.Views with a MeshSet (K
+    unused: hypothesis n projects with K view[n])."""
     multi = isinstance(mesh, MeshSet)
     if views is not None and not multi:
         raise _lib.FpAmdError("render_crops: views need a MeshSet")
-    if multi:
-        d, o, M = _objects(mesh_diameter, obj, "render_crops") or (None, None, 0)
-        if d is None or M != mesh.M:
-            raise _lib.FpAmdError(f"render_crops: a MeshSet of {mesh.M} meshes needs a ({mesh.M},) diameter table")
-    elif obj is not None:
+    if multi and not (torch.is_tensor(mesh_diameter) and mesh_diameter.dim() == 1 and mesh_diameter.numel() == mesh.M):
+        raise _lib.FpAmdError(f"render_crops: a MeshSet of {mesh.M} meshes needs a ({mesh.M},) diameter table")
+    if not multi and obj is not None:
         raise _lib.FpAmdError("render_crops: an object index needs a MeshSet")
     P = _dev(poses, torch.float32, "poses")
     N = int(P.shape[0])
+    (Kp, Ks, view, V), (dia, d, o, _) = _scene("render_crops", N, K, mesh_diameter if multi else float(mesh_diameter), obj, views)
     bb = _dev(bbox2d, torch.float32, "bbox2d")
     oh, ow = int(out_hw[0]), int(out_hw[1])
     dev = P.device
@@ -455,24 +451,10 @@ def render_crops(mesh, poses, bbox2d, K, H, W, out_hw=(160, 160), mesh_diameter=
             raise _lib.FpAmdError(f"render_crops: workspace has {ws.numel()} bytes, {need} needed")
     else:
         ws = _workspace(need, dev)
-    K9 = _hostK32(K) if views is None else None
     flags = (FLAG_NORMALIZE_XYZ if normalize_xyz else 0) | (FLAG_OUT_F16 if (A is not None and A.dtype == torch.float16) else 0)
-    if views is not None:
-        vt = _views(views, "render_crops", N)
-        st = L.fp_render_crops_views(mesh.handle, _ptr(o), _ptr(d), _ptr(vt.K32), _ptr(vt.dev), vt.V, _ptr(P), _ptr(bb), int(H), int(W),
-                                     N, oh, ow, w_ambient, w_diffuse, xyz_thr, flags, _ptr(A), _ptr(color), _ptr(depth), _ptr(xyz),
-                                     _ptr(normal), _ptr(zbuf), _ptr(tri), _ptr(ws), 0 if ws is None else ws.numel(), _stream(P))
-        _lib.check(st, "fp_render_crops_views")
-        return outs
-    if multi:
-        st = L.fp_render_crops_multi(mesh.handle, _ptr(o), _ptr(d), _ptr(P), _ptr(bb), K9.ctypes.data_as(C.c_void_p), int(H), int(W),
-                                     N, oh, ow, w_ambient, w_diffuse, xyz_thr, flags, _ptr(A), _ptr(color), _ptr(depth), _ptr(xyz),
-                                     _ptr(normal), _ptr(zbuf), _ptr(tri), _ptr(ws), 0 if ws is None else ws.numel(), _stream(P))
-        _lib.check(st, "fp_render_crops_multi")
-        return outs
-    st = L.fp_render_crops(mesh.handle, _ptr(P), _ptr(bb), K9.ctypes.data_as(C.c_void_p), int(H), int(W), N, oh, ow,
-                           w_ambient, w_diffuse, float(np.float32(mesh_diameter)), xyz_thr, flags, _ptr(A), _ptr(color),
-                           _ptr(depth), _ptr(xyz), _ptr(normal), _ptr(zbuf), _ptr(tri), _ptr(ws),
+    one, mset = (None, mesh.handle) if multi else (mesh.handle, None)
+    st = L.fp_render_crops(one, mset, o, d, dia, _ptr(P), _ptr(bb), Kp, Ks, view, V, int(H), int(W), N, oh, ow, w_ambient, w_diffuse,
+                           xyz_thr, flags, _ptr(A), _ptr(color), _ptr(depth), _ptr(xyz), _ptr(normal), _ptr(zbuf), _ptr(tri), _ptr(ws),
                            0 if ws is None else ws.numel(), _stream(P))
     _lib.check(st, "fp_render_crops")
     return outs
@@ -481,8 +463,7 @@ def render_crops(mesh, poses, bbox2d, K, H, W, out_hw=(160, 160), mesh_diameter=
 def warp_crops(rgb, xyz_map, depth, tf_to_crops, K, poses, mesh_diameter, mode, normalize_xyz=True, out_f16=False,
                out_hw=(160, 160), B_out=None, obj=None, views=None):
     """fp_warp_crops.  Several objects: mesh_diameter = the (M,) table of object_diameters, obj = the per-hypothesis object
-    index (fp_warp_crops_multi).  Several views: views = an ops.Views, rgb / xyz_map / depth = (V,H,W,3) / (V,H,W,3) / (V,H,W) frame
-    stacks (K unused; fp_warp_crops_views)."""
+    index.  Several views: views = an ops.Views, rgb / xyz_map / depth = (V,H,W,3) / (V,H,W,3) / (V,H,W) frame stacks (K unused)."""
     rgbf = _dev(rgb, torch.float32, "rgb")
     H, W = (int(rgbf.shape[0]), int(rgbf.shape[1])) if views is None else (int(rgbf.shape[1]), int(rgbf.shape[2]))
     xm = _dev(xyz_map, torch.float32, "xyz_map")
@@ -494,25 +475,11 @@ def warp_crops(rgb, xyz_map, depth, tf_to_crops, K, poses, mesh_diameter, mode, 
     B = B_out if B_out is not None else torch.empty((N, 6, oh, ow), dtype=torch.float16 if out_f16 else torch.float32,
                                                     device=P.device)
     flags = (FLAG_NORMALIZE_XYZ if normalize_xyz else 0) | (FLAG_OUT_F16 if B.dtype == torch.float16 else 0)
-    if views is not None:
-        vt = _views(views, "warp_crops", N)
-        if rgbf.dim() != 4 or int(rgbf.shape[0]) != vt.V:
-            raise _lib.FpAmdError(f"warp_crops: views need a ({vt.V},H,W,3) rgb stack, got {tuple(rgbf.shape)}")
-        d, o, M = _objects_views(mesh_diameter, obj, "warp_crops")
-        st = _lib.lib().fp_warp_crops_views(_ptr(rgbf), _ptr(xm), _ptr(dp), _ptr(tf), _ptr(vt.K32), _ptr(vt.dev), vt.V, _ptr(P), _ptr(d),
-                                            _ptr(o), M, flags, int(mode), H, W, N, oh, ow, _ptr(B), _stream(P))
-        _lib.check(st, "fp_warp_crops_views")
-        return B
-    K9 = _hostK32(K)
-    objs = _objects(mesh_diameter, obj, "warp_crops")
-    if objs is not None:
-        d, o, M = objs
-        st = _lib.lib().fp_warp_crops_multi(_ptr(rgbf), _ptr(xm), _ptr(dp), _ptr(tf), K9.ctypes.data_as(C.c_void_p), _ptr(P), _ptr(d),
-                                            _ptr(o), M, flags, int(mode), H, W, N, oh, ow, _ptr(B), _stream(P))
-        _lib.check(st, "fp_warp_crops_multi")
-        return B
-    st = _lib.lib().fp_warp_crops(_ptr(rgbf), _ptr(xm), _ptr(dp), _ptr(tf), K9.ctypes.data_as(C.c_void_p), _ptr(P),
-                                  float(np.float32(mesh_diameter)), flags, int(mode), H, W, N, oh, ow, _ptr(B), _stream(P))
+    if views is not None and (rgbf.dim() != 4 or int(rgbf.shape[0]) != _views(views, "warp_crops", N).V):
+        raise _lib.FpAmdError(f"warp_crops: views need a ({views.V},H,W,3) rgb stack, got {tuple(rgbf.shape)}")
+    (Kp, Ks, view, V), (dia, d, o, M) = _scene("warp_crops", N, K, mesh_diameter, obj, views)
+    st = _lib.lib().fp_warp_crops(_ptr(rgbf), _ptr(xm), _ptr(dp), _ptr(tf), Kp, Ks, view, V, _ptr(P), dia, d, o, M, flags, int(mode),
+                                  H, W, N, oh, ow, _ptr(B), _stream(P))
     _lib.check(st, "fp_warp_crops")
     return B
 
@@ -1372,9 +1339,9 @@ def pose_update(trans, rot, poses, rot_rep="axis_angle", normalize_xyz=True, tra
                 K=None, tf_to_crops=None, input_w=0, obj=None, views=None):
     """fp_pose_update.  trans_rep='deepim' needs K, tf_to_crops (N,3,3) and the crop width (predict_pose_refine.py:201-215);
     any trans_rep other than 'tracknet' / 'deepim' is the reference's plain `else` branch (:217-218): the raw output.  Several
-    objects: mesh_diameter = the (M,) table of object_diameters, obj = the per-hypothesis object index (fp_pose_update_multi).  Several
-    views: views = an ops.Views (K unused; fp_pose_update_views).  `out` must not overlap `poses` (the kernel reads poses_in and writes
-    poses_out as __restrict__ rows): an in-place update is refused."""
+    objects: mesh_diameter = the (M,) table of object_diameters, obj = the per-hypothesis object index.  Several views: views = an
+    ops.Views (K unused).  `out` must not overlap `poses` (the kernel reads poses_in and writes poses_out as __restrict__ rows): an
+    in-place update is refused."""
     if _overlap(out, poses):
         raise _lib.FpAmdError("pose_update: out must not overlap poses (poses_in / poses_out are __restrict__; there is no in-place update)")
     tr = _dev(trans, torch.float32, "trans")
@@ -1390,34 +1357,14 @@ def pose_update(trans, rot, poses, rot_rep="axis_angle", normalize_xyz=True, tra
     tn = np.ascontiguousarray(np.broadcast_to(np.asarray(trans_normalizer, dtype=np.float32).reshape(-1), (3,)))
     O = out if out is not None else torch.empty_like(P)
     deepim = trans_rep == "deepim"
-    K9 = _hostK32(K) if deepim and views is None else None
     tf = _dev(tf_to_crops, torch.float32, "tf_to_crops") if deepim else None
     tro = TRANS_DEEPIM if deepim else (TRANS_TRACKNET if trans_rep == "tracknet" else TRANS_RAW)
-    if views is not None:
-        vt = _views(views, "pose_update", N)
-        d, o, M = _objects_views(mesh_diameter, obj, "pose_update")
-        st = _lib.lib().fp_pose_update_views(_ptr(tr), _ptr(ro), _ptr(P), rr, int(bool(normalize_xyz)), tn.ctypes.data_as(C.c_void_p),
-                                             float(rot_normalizer), _ptr(d), _ptr(o), M, N, _ptr(O),
-                                             _ptr(_dev(trans_delta_out, torch.float32, "trans_delta_out")),
-                                             _ptr(_dev(rot_delta_out, torch.float32, "rot_delta_out")), tro, _ptr(vt.K32), _ptr(vt.dev),
-                                             vt.V, _ptr(tf), float(input_w), _stream(P))
-        _lib.check(st, "fp_pose_update_views")
-        return O
-    objs = _objects(mesh_diameter, obj, "pose_update")
-    if objs is not None:
-        d, o, M = objs
-        st = _lib.lib().fp_pose_update_multi(_ptr(tr), _ptr(ro), _ptr(P), rr, int(bool(normalize_xyz)), tn.ctypes.data_as(C.c_void_p),
-                                             float(rot_normalizer), _ptr(d), _ptr(o), M, N, _ptr(O),
-                                             _ptr(_dev(trans_delta_out, torch.float32, "trans_delta_out")),
-                                             _ptr(_dev(rot_delta_out, torch.float32, "rot_delta_out")), tro,
-                                             K9.ctypes.data_as(C.c_void_p) if deepim else None, _ptr(tf), float(input_w), _stream(P))
-        _lib.check(st, "fp_pose_update_multi")
-        return O
-    st = _lib.lib().fp_pose_update(_ptr(tr), _ptr(ro), _ptr(P), rr, int(bool(normalize_xyz)),
-                                   tn.ctypes.data_as(C.c_void_p), float(rot_normalizer), float(np.float32(mesh_diameter)),
-                                   N, _ptr(O), _ptr(_dev(trans_delta_out, torch.float32, "trans_delta_out")),
-                                   _ptr(_dev(rot_delta_out, torch.float32, "rot_delta_out")), tro,
-                                   K9.ctypes.data_as(C.c_void_p) if deepim else None, _ptr(tf), float(input_w), _stream(P))
+    (Kp, Ks, view, V), (dia, d, o, M) = _scene("pose_update", N, K, mesh_diameter, obj, views, need_K=deepim)
+    st = _lib.lib().fp_pose_update(_ptr(tr), _ptr(ro), _ptr(P), rr, int(bool(normalize_xyz)), tn.ctypes.data_as(C.c_void_p),
+                                   float(rot_normalizer), dia, d, o, M, N, _ptr(O),
+                                   _ptr(_dev(trans_delta_out, torch.float32, "trans_delta_out")),
+                                   _ptr(_dev(rot_delta_out, torch.float32, "rot_delta_out")), tro, Kp, Ks, view, V, _ptr(tf),
+                                   float(input_w), _stream(P))
     _lib.check(st, "fp_pose_update")
     return O
 

@@ -177,12 +177,12 @@ class ScorePredictor:
                         views=None):
         """predict() for the hypotheses of several objects in ONE call.  ob_in_cams (N,4,4) grouped by object: segments
         (ops.Segments, total N) segment k = the hypotheses of object k = entry k of mesh_set (ops.MeshSet) and of object_diameters
-        (ops.object_diameters).  The per-hypothesis half runs the multi-object kernels (fp_crop_windows_multi, fp_render_crops_multi,
-        fp_warp_crops_multi) in predict()'s sub-batches on its streams; the cross-hypothesis attention runs per object
+        (ops.object_diameters).  The per-hypothesis half runs the crop stage with the object table (fp_crop_windows, fp_render_crops,
+        fp_warp_crops) in predict()'s sub-batches on its streams; the cross-hypothesis attention runs per object
         (ScorePlan.head_segments), so no object's scores see another object's hypotheses.  Per object the scores are what
         predict() of that object's hypotheses alone returns.  -> scores (N,) f32 device tensor = logit + 100.  get_vis and
         feature_exchange are not supported here.  Several camera frames: views = an ops.Views of the N hypotheses, rgb / depth =
-        (V,H,W,3) / (V,H,W) stacks (K unused): the crops come from the *_views kernels, each hypothesis from its own frame."""
+        (V,H,W,3) / (V,H,W) stacks (K unused): the crops come from the view-table kernels, each hypothesis from its own frame."""
         if get_vis or feature_exchange is not None:
             raise NotImplementedError("predict_objects: get_vis and feature_exchange are supported by predict() only")
         plan = self.plan()

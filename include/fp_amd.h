@@ -91,8 +91,13 @@ const char* fp_last_error(void);
  *   227 -> 228: + fp_tsdf_raycast (addition only): depth, points, normals and colours of a TSDF volume's zero surface at any pose, in
  *               the layout fp_icp_point_plane and fp_depth_agreement read.
  *   228 -> 229: + fp_tsdf_label_components (addition only): the face-connected components of a volume's surface cubes and their
- *               triangle counts, for dropping floaters at extraction. */
-#define FP_AMD_ABI_VERSION 229
+ *               triangle counts, for dropping floaters at extraction.
+ *   229 -> 230: fp_crop_windows, fp_render_crops, fp_warp_crops and fp_pose_update CHANGED SIGNATURE IN PLACE: each now takes the camera
+ *               as K or as Ks / view / V and the object as mesh_diameter or as diameters / obj / M (render: mesh or set) in one argument
+ *               list.  REMOVED: fp_crop_windows_multi, fp_crop_windows_views, fp_render_crops_multi, fp_render_crops_views,
+ *               fp_warp_crops_multi, fp_warp_crops_views, fp_pose_update_multi, fp_pose_update_views.  A caller of the four base names
+ *               built against an older header passes the wrong arguments: gate on fp_version(). */
+#define FP_AMD_ABI_VERSION 230
 int fp_version(void);
 
 /* Utils.py:104-130 make_mesh_tensors: records caller-owned device tensors.
@@ -104,13 +109,9 @@ int fp_mesh_create(const float* pos /*dev*/, const float* nrm /*dev*/, const int
                    int Wt, fp_mesh** out);
 void fp_mesh_destroy(fp_mesh* mesh);
 
-/* Several objects per call.  A mesh set holds M mesh descriptors (fp_mesh_create) in one device table; every *_multi entry point
- * takes a per-hypothesis object index obj (dev N int32, values 0..M-1, any order; NULL allowed only for M == 1: all 0) and the
- * per-object diameters (dev M f64).  Hypothesis n then sees exactly what the scalar entry point sees for the mesh meshes[obj[n]]
- * and the diameter diameters[obj[n]] (passed as that double to fp_crop_windows and rounded to float for the others): the outputs
- * are bit-identical.  An index outside 0..M-1 renders nothing and yields NaN-scaled values, never a memory access out of the set.
- * fp_mesh_set_create is a SETUP call: it allocates the device table and copies the descriptors synchronously (the per-frame
- * entry points below copy nothing, so they can be captured in a hipGraph).  The set refers to the meshes' tensors, it does not own
+/* Several objects per call: a mesh set holds M mesh descriptors (fp_mesh_create) in one device table, for fp_render_crops (see "The
+ * crop stage" below).  fp_mesh_set_create is a SETUP call: it allocates the device table and copies the descriptors synchronously (the
+ * per-frame entry points copy nothing, so they can be captured in a hipGraph).  The set refers to the meshes' tensors, it does not own
  * them; the fp_mesh handles themselves may be destroyed after the call.  V and T of every mesh: 1..FP_MESH_SET_MAX_ELEMS. */
 #define FP_MESH_SET_MAX_ELEMS (1 << 26)
 int fp_mesh_set_create(const fp_mesh* const* meshes /*host M*/, int M, fp_mesh_set** out);
@@ -147,31 +148,6 @@ int fp_depth_to_xyz_frames(const float* depth /*dev V,H,W*/, const double* Ks /*
 int fp_mask_depth_stats(const float* depth /*dev V,H,W*/, const uint8_t* masks /*dev M,H,W*/, const int32_t* view /*dev M|NULL*/,
                         int V, int M, int H, int W, float min_depth, int32_t* out /*dev M,8*/, void* stream);
 
-/* Several views per call (the *_views entry points; estimater.py:250-268 track_one on several camera frames at once).  Each takes the
- * arguments of its *_multi form with the one host K replaced by a VIEW TABLE: Ks (dev V,9: f64 for fp_crop_windows_views, f32 for the
- * others -- the values the single-view entry points take on the host) and a per-hypothesis view index view (dev N int32, values
- * 0..V-1, any order; NULL allowed only for V == 1: all 0).  Image inputs are FRAME STACKS of V frames of one H x W, frame v at
- * element offset (size_t)v * H * W * C.  obj may be NULL for a one-mesh set / M == 1 as in the *_multi forms.  Hypothesis n then sees
- * exactly what the *_multi entry point sees when it is called with frame view[n] and K Ks[view[n]]: the outputs are bit-identical.
- * A view index outside 0..V-1 never reads outside the stack or the table: the render draws nothing, the warp writes what a pixel
- * outside the frame gets, crop windows and pose update write NaN.  Argument errors (FP_ERR_INVALID_ARG, fp_last_error): a NULL K
- * table, V < 1, view NULL with V > 1, unknown flag bits, and those of the *_multi form. */
-/* fp_crop_windows_multi with K = Ks[view[n]] (f64) */
-int fp_crop_windows_views(const float* poses /*dev N,16*/, const double* Ks /*dev V,9*/, const int32_t* view /*dev N|NULL*/, int V,
-                          const double* diameters /*dev M*/, const int32_t* obj /*dev N|NULL*/, int M, double crop_ratio, int out_w,
-                          int out_h, int N, float* tf_to_crops /*dev N,9*/, float* bbox2d /*dev N,4*/, void* stream);
-/* fp_render_crops_multi with K = Ks[view[n]] (f32); workspace: fp_mesh_set_workspace_bytes(set, N, oh, ow) */
-int fp_render_crops_views(const fp_mesh_set* set, const int32_t* obj /*dev N|NULL*/, const double* diameters /*dev M|NULL*/,
-                          const float* Ks /*dev V,9*/, const int32_t* view /*dev N|NULL*/, int V, const float* poses /*dev N,16*/,
-                          const float* bbox2d /*dev N,4|NULL*/, int H, int W, int N, int oh, int ow, float w_ambient, float w_diffuse,
-                          float xyz_thr, int flags, void* A /*dev*/, float* color /*dev*/, float* depth /*dev*/, float* xyz /*dev*/,
-                          float* normal /*dev*/, uint32_t* zbuf /*dev*/, int32_t* tri_id /*dev*/, void* workspace /*dev*/,
-                          size_t workspace_bytes, void* stream);
-/* fp_warp_crops_multi on frame view[n] of the stacks rgb (V,H,W,3), xyz_map (V,H,W,3; REFINE) / depth (V,H,W; SCORE), K = Ks[view[n]] */
-int fp_warp_crops_views(const float* rgb /*dev V,H,W,3*/, const float* xyz_map /*dev V,H,W,3|NULL*/, const float* depth /*dev V,H,W|NULL*/,
-                        const float* tf_to_crops /*dev N,9*/, const float* Ks /*dev V,9*/, const int32_t* view /*dev N|NULL*/, int V,
-                        const float* poses /*dev N,16*/, const double* diameters /*dev M*/, const int32_t* obj /*dev N|NULL*/, int M,
-                        int flags, int mode, int H, int W, int N, int oh, int ow, void* B /*dev N,6,oh,ow*/, void* stream);
 /* How well each pose agrees with the observed depth (the signal that a track is lost), for N hypotheses in one launch.  For hypothesis n
  * and crop pixel (i, j): z_r = depth_crops[n, j, i], the render's depth at the pose (fp_render_crops* with these tf_to_crops' windows;
  * 0 where it draws nothing), and z_o = the z of the texel of frame view[n]'s xyz map that the REFINE warp reads for that pixel (the
@@ -311,8 +287,8 @@ int fp_mspd(const float* model_pts /*dev P,3*/, int P, const double* sym_tfs /*d
  * units of rgb; color_weight (nz,ny,nx).  A fresh volume is tsdf = 1 and zeros elsewhere (the caller fills it).
  *
  * fp_tsdf_integrate fuses V views into the volume: depth (V,H,W) metres, rgb (V,H,W,3), masks (V,H,W) uint8 (NULL: every pixel is the
- * object's), ob_in_cams (V,16) row-major object-to-camera transforms T, Ks (V,9) float64 on the device (as the *_views entry points
- * take them), rounded to float32 {fx, skew, cx, 0, fy, cy, ...}.  One voxel per lane; the views are visited inside the kernel in index
+ * object's), ob_in_cams (V,16) row-major object-to-camera transforms T, Ks (V,9) float64 on the device (as the crop stage's view
+ * tables), rounded to float32 {fx, skew, cx, 0, fy, cy, ...}.  One voxel per lane; the views are visited inside the kernel in index
  * order, so a voxel's running means have one summation order: no atomics, every call repeats its bits, and a call over views 0..k
  * followed by a call over k+1..V-1 leaves the bits of one call over 0..V-1.  A view whose 16 pose values, fx, fy, cx, cy are not all
  * finite, or whose skew is not 0, is skipped for every voxel.  Otherwise, per voxel:
@@ -389,7 +365,7 @@ int fp_tsdf_label_components(const int32_t* counts /*dev (nz-1)(ny-1)(nx-1)*/, i
  * fp_icp_point_plane beside the same tf_to_crops as a render of the extracted mesh does.  Every operation is float32 without
  * contraction, one rounding per operation, in the order written; every 3-term sum is (a0*b0 + a1*b1) + a2*b2.
  * Per row n: T = poses[n] (object to camera, taken as rigid: R its 3x3 block, t its last column); {fx, skew, cx, fy, cy} from K (one
- * camera on the host, Ks NULL) or from Ks[view[n]] (the float32 table of fp_render_crops_views, K NULL; view NULL means view 0, allowed
+ * camera on the host, Ks NULL) or from Ks[view[n]] (the float32 table fp_render_crops takes, K NULL; view NULL means view 0, allowed
  * for V == 1); (umin, vmin, umax, vmax) = bbox2d[n], or (0, 0, W, H) with bbox2d NULL (which requires oh == H and ow == W).  The row is all
  * misses when one of T's 16 values, fx, fy, cx or cy is not finite, when the table's skew is not 0, when view[n] is outside 0..V-1, or
  * when the volume has a dimension of 1 (no cells).  Otherwise
@@ -475,24 +451,34 @@ int fp_texture_bake(const float* pos /*dev Nv,3*/, int Nv, const int32_t* faces 
                     const float* rgb /*dev V,H,W,3 in 0..255*/, const uint8_t* masks /*dev V,H,W|NULL*/,
                     const float* ob_in_cams /*dev V,16*/, const double* Ks /*dev V,9*/, int V, int H, int W, int T, int Bx, float tol,
                     float min_cos, float min_depth, float* tex /*dev Ht,Wt,3*/, uint8_t* coverage /*dev Ht,Wt*/, void* stream);
-/* fp_pose_update_multi with K = Ks[view[n]] (read by trans_rep deepim only; Ks is required either way).  A view[n] outside 0..V-1:
- * all of poses_out row n (16 values) and of the given trans_delta_out / rot_delta_out rows n are NaN, whatever trans_rep. */
-int fp_pose_update_views(const float* trans /*dev N,3*/, const float* rot /*dev N,3|6*/, const float* poses_in /*dev N,16*/,
-                         int rot_rep, int normalize_xyz, const float* trans_normalizer /*host 3*/, float rot_normalizer,
-                         const double* diameters /*dev M*/, const int32_t* obj /*dev N|NULL*/, int M, int N,
-                         float* poses_out /*dev N,16*/, float* trans_delta_out /*dev N,3|NULL*/, float* rot_delta_out /*dev N,9|NULL*/,
-                         int trans_rep, const float* Ks /*dev V,9*/, const int32_t* view /*dev N|NULL*/, int V,
-                         const float* tf_to_crops /*dev N,9|NULL*/, float input_w, void* stream);
+/* ---- The crop stage: crop windows, render, warp and pose update of N hypotheses (estimater.py:250-268 track_one; several objects
+ * and several camera frames per call).  The four entry points describe the scene with the same arguments:
+ *   Camera, exactly one of
+ *     K  (host 9): one camera for every hypothesis (f64 for fp_crop_windows, f32 for the others), with Ks = view = NULL and V = 0;
+ *     Ks (dev V,9; same type as K), view (dev N int32, values 0..V-1, any order; NULL allowed only for V == 1: all 0) and V >= 1: a
+ *        VIEW TABLE, hypothesis n has K = Ks[view[n]], with K = NULL.  Image inputs are then FRAME STACKS of V frames of one H x W,
+ *        frame v at element offset (size_t)v * H * W * C, and hypothesis n reads frame view[n].
+ *   Object, exactly one of
+ *     mesh_diameter: one object, with diameters = obj = NULL and M = 0 (fp_render_crops: with `mesh`);
+ *     diameters (dev M f64), obj (dev N int32, values 0..M-1, any order; NULL allowed only for M == 1: all 0) and M >= 1: hypothesis n
+ *        has the diameter diameters[obj[n]] (fp_render_crops: and draws mesh obj[n] of `set`, whose size is M; mesh_diameter is
+ *        not read).
+ *   A view table goes with the diameter table (M == 1 and obj NULL for one object); Ks with a scalar mesh_diameter is refused.
+ * Hypothesis n of a table call sees exactly what the one-camera, one-object call sees for frame view[n], K = Ks[view[n]], mesh
+ * meshes[obj[n]] and the diameter diameters[obj[n]] (passed as that double to fp_crop_windows and rounded to float for the others):
+ * the outputs are bit-identical.  An obj[n] outside 0..M-1 renders nothing and yields NaN-scaled values, never a memory access out of
+ * the set.  A view[n] outside 0..V-1 never reads outside the stack or the table: the render draws nothing, the warp writes what a
+ * pixel outside the frame gets, crop windows and pose update write NaN.
+ * Argument errors (FP_ERR_INVALID_ARG, fp_last_error), checked in this order: N < 0; unknown flag bits (render, warp); a diameter
+ * table that is NULL or has M < 1, obj NULL with M > 1; both K and a view table, a NULL K table or V < 1, view NULL with V > 1, a view
+ * table without the diameter table; then N == 0 returns FP_OK; then neither K nor Ks (fp_pose_update: see there) and NULL tensors. */
 
 /* Utils.py:577-621 compute_crop_window_tf_batch(method='box_3d') and the bbox of
  * predict_pose_refine.py:44-45 / predict_score.py:74-75 (closed-form inverse). */
-int fp_crop_windows(const float* poses /*dev N,16*/, const double* K /*host 9*/, double mesh_diameter,
-                    double crop_ratio, int out_w, int out_h, int N, float* tf_to_crops /*dev N,9*/,
-                    float* bbox2d /*dev N,4*/, void* stream);
-/* fp_crop_windows with the diameter of hypothesis n = diameters[obj[n]] */
-int fp_crop_windows_multi(const float* poses /*dev N,16*/, const double* K /*host 9*/, const double* diameters /*dev M*/,
-                          const int32_t* obj /*dev N|NULL*/, int M, double crop_ratio, int out_w, int out_h, int N,
-                          float* tf_to_crops /*dev N,9*/, float* bbox2d /*dev N,4*/, void* stream);
+int fp_crop_windows(const float* poses /*dev N,16*/, const double* K /*host 9|NULL*/, const double* Ks /*dev V,9|NULL*/,
+                    const int32_t* view /*dev N|NULL*/, int V, double mesh_diameter, const double* diameters /*dev M|NULL*/,
+                    const int32_t* obj /*dev N|NULL*/, int M, double crop_ratio, int out_w, int out_h, int N,
+                    float* tf_to_crops /*dev N,9*/, float* bbox2d /*dev N,4*/, void* stream);
 
 /* bytes of scratch fp_render_crops needs for (N hypotheses, V vertices, T triangles, oh x ow crops): per-hypothesis
  * vertex records (32 B/vertex) and per-strip triangle lists; caller-owned device memory, no alignment beyond 256 B */
@@ -505,60 +491,48 @@ size_t fp_raster_lds_bytes(int ow);
 /* Utils.py:133-219 nvdiffrast_render (dr.rasterize + interpolate x5 + texture + Lambert shading + flips)
  * fused with predict_pose_refine.py:54-56 (*255), h5_dataset.py:79-114 (/255, xyz - t, 1/radius, masks)
  * and the channel concat of predict_pose_refine.py:187 (A = [rgb, xyz]).
+ * Exactly one of `mesh` (with mesh_diameter; workspace: fp_workspace_bytes) and `set` (with obj and diameters, the meshes may
+ * differ in V, T and texture / vertex colour; diameters may be NULL without FP_FLAG_NORMALIZE_XYZ; workspace:
+ * fp_mesh_set_workspace_bytes(set, N, oh, ow)); a NULL set where obj, diameters or a view table ask for one is refused.
  * bbox2d NULL => full frame (needs oh=H, ow=W).  Any output may be NULL.
  *   A      (N,6,oh,ow) f32|f16 ; color (N,oh,ow,3) ; depth (N,oh,ow) ; xyz (N,oh,ow,3) ; normal (N,oh,ow,3)
  *   zbuf   (N,oh,ow) u32 fixed-point camera depth of the winner, FP_ZBUF_EMPTY if none ; tri_id i32, -1 if none */
-int fp_render_crops(const fp_mesh* mesh, const float* poses /*dev N,16*/, const float* bbox2d /*dev N,4|NULL*/,
-                    const float* K9 /*host 9 f32*/, int H, int W, int N, int oh, int ow, float w_ambient,
-                    float w_diffuse, float mesh_diameter, float xyz_thr, int flags, void* A /*dev*/,
-                    float* color /*dev*/, float* depth /*dev*/, float* xyz /*dev*/, float* normal /*dev*/,
-                    uint32_t* zbuf /*dev*/, int32_t* tri_id /*dev*/, void* workspace /*dev*/,
-                    size_t workspace_bytes, void* stream);
-
-/* fp_render_crops with hypothesis n drawing mesh obj[n] of the set (meshes may differ in V, T and texture / vertex colour);
- * diameters may be NULL without FP_FLAG_NORMALIZE_XYZ.  workspace: fp_mesh_set_workspace_bytes(set, N, oh, ow). */
-int fp_render_crops_multi(const fp_mesh_set* set, const int32_t* obj /*dev N|NULL*/, const double* diameters /*dev M|NULL*/,
-                          const float* poses /*dev N,16*/, const float* bbox2d /*dev N,4|NULL*/, const float* K9 /*host 9 f32*/,
-                          int H, int W, int N, int oh, int ow, float w_ambient, float w_diffuse, float xyz_thr, int flags,
-                          void* A /*dev*/, float* color /*dev*/, float* depth /*dev*/, float* xyz /*dev*/, float* normal /*dev*/,
-                          uint32_t* zbuf /*dev*/, int32_t* tri_id /*dev*/, void* workspace /*dev*/, size_t workspace_bytes,
-                          void* stream);
+int fp_render_crops(const fp_mesh* mesh /*|NULL*/, const fp_mesh_set* set /*|NULL*/, const int32_t* obj /*dev N|NULL*/,
+                    const double* diameters /*dev M|NULL*/, float mesh_diameter, const float* poses /*dev N,16*/,
+                    const float* bbox2d /*dev N,4|NULL*/, const float* K /*host 9|NULL*/, const float* Ks /*dev V,9|NULL*/,
+                    const int32_t* view /*dev N|NULL*/, int V, int H, int W, int N, int oh, int ow, float w_ambient,
+                    float w_diffuse, float xyz_thr, int flags, void* A /*dev*/, float* color /*dev*/, float* depth /*dev*/,
+                    float* xyz /*dev*/, float* normal /*dev*/, uint32_t* zbuf /*dev*/, int32_t* tri_id /*dev*/,
+                    void* workspace /*dev*/, size_t workspace_bytes, void* stream);
 
 /* kornia warp_perspective call sites predict_pose_refine.py:63,72 / predict_score.py:89,90 fused with
  * h5_dataset.py:79-114 (refine) or :137-170 (score: depth crop -> frame -> back-projection -> crop) and
  * the concat of predict_pose_refine.py:188 (B = [rgb, xyz]).
- * rgb (H,W,3) f32 in 0..255; xyz_map (H,W,3) f32 (REFINE); depth (H,W) f32 (SCORE). */
+ * rgb (H,W,3) f32 in 0..255; xyz_map (H,W,3) f32 (REFINE); depth (H,W) f32 (SCORE); with a view table each is a (V,...) stack. */
 int fp_warp_crops(const float* rgb /*dev*/, const float* xyz_map /*dev|NULL*/, const float* depth /*dev|NULL*/,
-                  const float* tf_to_crops /*dev N,9*/, const float* K9 /*host 9 f32*/,
-                  const float* poses /*dev N,16*/, float mesh_diameter, int flags, int mode, int H, int W,
-                  int N, int oh, int ow, void* B /*dev N,6,oh,ow*/, void* stream);
-
-/* fp_warp_crops with the diameter of hypothesis n = diameters[obj[n]] */
-int fp_warp_crops_multi(const float* rgb /*dev*/, const float* xyz_map /*dev|NULL*/, const float* depth /*dev|NULL*/,
-                        const float* tf_to_crops /*dev N,9*/, const float* K9 /*host 9 f32*/, const float* poses /*dev N,16*/,
-                        const double* diameters /*dev M*/, const int32_t* obj /*dev N|NULL*/, int M, int flags, int mode, int H,
-                        int W, int N, int oh, int ow, void* B /*dev N,6,oh,ow*/, void* stream);
+                  const float* tf_to_crops /*dev N,9*/, const float* K /*host 9|NULL*/, const float* Ks /*dev V,9|NULL*/,
+                  const int32_t* view /*dev N|NULL*/, int V, const float* poses /*dev N,16*/, float mesh_diameter,
+                  const double* diameters /*dev M|NULL*/, const int32_t* obj /*dev N|NULL*/, int M, int flags, int mode, int H,
+                  int W, int N, int oh, int ow, void* B /*dev N,6,oh,ow*/, void* stream);
 
 /* predict_pose_refine.py:195-234 + Utils.py:848-855 + pytorch3d so3_exp_map / rotation_6d_to_matrix.
  * trans_delta_out / rot_delta_out (optional): the metric translation delta and the applied rotation matrix
  * (so3_exp_map(.)^T), i.e. what the reference keeps in last_trans_update / last_rot_update (:238-239).
- * poses_in and poses_out MUST NOT OVERLAP (this and the _multi / _views forms): the kernel holds both as __restrict__, there is no
- * in-place update.  Exactly rows 0..N-1 of each given output are written; N == 0 writes nothing. */
-int fp_pose_update(const float* trans /*dev N,3*/, const float* rot /*dev N,3|6*/,
-                   const float* poses_in /*dev N,16*/, int rot_rep, int normalize_xyz,
-                   const float* trans_normalizer /*host 3*/, float rot_normalizer, float mesh_diameter, int N,
-                   float* poses_out /*dev N,16*/, float* trans_delta_out /*dev N,3|NULL*/,
-                   float* rot_delta_out /*dev N,9|NULL*/, int trans_rep, const float* K9 /*host 9 f32|NULL (deepim)*/,
-                   const float* tf_to_crops /*dev N,9|NULL (deepim)*/, float input_w /*crop width (deepim)*/, void* stream);
-/* fp_pose_update with the diameter of hypothesis n = diameters[obj[n]].  An obj[n] outside 0..M-1 reads no diameter: it counts as
- * NaN, so with normalize_xyz the translation column of poses_out row n and trans_delta_out row n are NaN (the rotation block is what
- * it is for any diameter); without normalize_xyz the diameter is not used and the row is the scalar form's. */
-int fp_pose_update_multi(const float* trans /*dev N,3*/, const float* rot /*dev N,3|6*/, const float* poses_in /*dev N,16*/,
-                         int rot_rep, int normalize_xyz, const float* trans_normalizer /*host 3*/, float rot_normalizer,
-                         const double* diameters /*dev M*/, const int32_t* obj /*dev N|NULL*/, int M, int N,
-                         float* poses_out /*dev N,16*/, float* trans_delta_out /*dev N,3|NULL*/, float* rot_delta_out /*dev N,9|NULL*/,
-                         int trans_rep, const float* K9 /*host 9 f32|NULL (deepim)*/, const float* tf_to_crops /*dev N,9|NULL*/,
-                         float input_w, void* stream);
+ * poses_in and poses_out MUST NOT OVERLAP: the kernel holds both as __restrict__, there is no in-place update.  Exactly rows
+ * 0..N-1 of each given output are written; N == 0 writes nothing.
+ * The camera is read by trans_rep deepim only (with tf_to_crops and input_w, the crop width): without a view table K may be NULL
+ * for the other trans_reps; a view table, once any of Ks / view / V is given, is required whole whatever trans_rep.
+ * An obj[n] outside 0..M-1 reads no diameter: it counts as NaN, so with normalize_xyz the translation column of poses_out row n and
+ * trans_delta_out row n are NaN (the rotation block is what it is for any diameter); without normalize_xyz the diameter is not
+ * used and the row is the scalar form's.  A view[n] outside 0..V-1: all of poses_out row n (16 values) and of the given
+ * trans_delta_out / rot_delta_out rows n are NaN, whatever trans_rep. */
+int fp_pose_update(const float* trans /*dev N,3*/, const float* rot /*dev N,3|6*/, const float* poses_in /*dev N,16*/,
+                   int rot_rep, int normalize_xyz, const float* trans_normalizer /*host 3*/, float rot_normalizer,
+                   float mesh_diameter, const double* diameters /*dev M|NULL*/, const int32_t* obj /*dev N|NULL*/, int M, int N,
+                   float* poses_out /*dev N,16*/, float* trans_delta_out /*dev N,3|NULL*/, float* rot_delta_out /*dev N,9|NULL*/,
+                   int trans_rep, const float* K /*host 9|NULL*/, const float* Ks /*dev V,9|NULL*/,
+                   const int32_t* view /*dev N|NULL*/, int V, const float* tf_to_crops /*dev N,9|NULL (deepim)*/,
+                   float input_w /*crop width (deepim)*/, void* stream);
 
 /* ---- network stage.  Arithmetic policy of every entry point below = the op sequence torch.cuda.amp.autocast(fp16)
  * produces for the reference's modules (predict_pose_refine.py:190-191, predict_score.py:193-194): fp16 operands,

@@ -14,8 +14,8 @@ A = torch.empty((N, 6, 160, 160), dtype=torch.float16, device=dev)
 L = _lib.lib(); ws = torch.empty(L.fp_workspace_bytes(N, h.V, h.T, 160, 160), dtype=torch.uint8, device=dev)
 K9 = np.ascontiguousarray(np.asarray(sc["K"], np.float64).reshape(9).astype(np.float32))
 def run(flags):
-    st = L.fp_render_crops(h.handle, poses.data_ptr(), bb.data_ptr(), K9.ctypes.data_as(C.c_void_p), 480, 640, N, 160, 160, 0.8, 0.5,
-                           float(sc["diameter"]), 0.001, flags, A.data_ptr(), None, None, None, None, None, None, ws.data_ptr(), ws.numel(),
+    st = L.fp_render_crops(h.handle, None, None, None, float(sc["diameter"]), poses.data_ptr(), bb.data_ptr(),
+                           K9.ctypes.data_as(C.c_void_p), None, None, 0, 480, 640, N, 160, 160, 0.8, 0.5, 0.001, flags, A.data_ptr(), None, None, None, None, None, None, ws.data_ptr(), ws.numel(),
                            C.c_void_p(torch.cuda.current_stream().cuda_stream))
     assert st == 0
 for name, fl in (("full", 3), ("no shading", 3 | 0x10000), ("no phase1", 3 | 0x20000), ("neither", 3 | 0x30000),

@@ -40,8 +40,8 @@ def one():
         K9 = np.ascontiguousarray(np.asarray(sc["K"], np.float64).reshape(9).astype(np.float32))
 
         def run(full):
-            st = L.fp_render_crops(h.handle, poses.data_ptr(), bb.data_ptr(), K9.ctypes.data_as(C.c_void_p), 480, 640, N, 160, 160,
-                                   0.8, 0.5, float(sc["diameter"]), 0.001, 3, A.data_ptr(), col.data_ptr() if full else None, None,
+            st = L.fp_render_crops(h.handle, None, None, None, float(sc["diameter"]), poses.data_ptr(), bb.data_ptr(),
+                                   K9.ctypes.data_as(C.c_void_p), None, None, 0, 480, 640, N, 160, 160, 0.8, 0.5, 0.001, 3, A.data_ptr(), col.data_ptr() if full else None, None,
                                    xyz.data_ptr() if full else None, None, zb.data_ptr() if full else None,
                                    ti.data_ptr() if full else None, ws.data_ptr(), ws.numel(),
                                    C.c_void_p(torch.cuda.current_stream().cuda_stream))

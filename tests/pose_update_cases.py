@@ -1,4 +1,4 @@
-"""Generated inputs for fp_pose_update / _multi / _views (k_pose_update of csrc/frame_ops.hip), in the style of
+"""Generated inputs for fp_pose_update in its three forms (k_pose_update of csrc/frame_ops.hip), in the style of
 tests/geometry_cases.py: sizes around the 64-thread block, rotations at the clamp of so3_exp_map, at saturated tanh and next to pi,
 degenerate 6d pairs, 'deepim' windows and intrinsics the scene never has, object and view indices outside their tables.  Seeded, numpy
 only.  cases(scene) returns a list of named records (plain dicts); every record carries its inputs, `targets` (what it is there

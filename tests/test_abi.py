@@ -111,11 +111,11 @@ def test_argument_errors_are_reported_without_gpu():
     assert lib.fp_replicate_rows_f16(C.c_void_p(16), C.c_void_p(32), 0, 10, 128, 256, 256, 2560, None) == 0       # nothing to do
     # fp_render_crops defines two flag bits; anything else (e.g. the phase-skip bits of the profiling build) is refused
     for bad in (0x10000, 0x80000, 4):
-        assert lib.fp_render_crops(None, None, None, None, 480, 640, 0, 160, 160, 0.8, 0.5, 0.17, 0.001, 3 | bad, None, None, None, None,
-                                   None, None, None, None, 0, None) == -1
+        assert lib.fp_render_crops(None, None, None, None, 0.17, None, None, None, None, None, 0, 480, 640, 0, 160, 160, 0.8, 0.5, 0.001,
+                                   3 | bad, None, None, None, None, None, None, None, None, 0, None) == -1
         assert b"unknown flag bits" in lib.fp_last_error()
-    assert lib.fp_render_crops(None, None, None, None, 480, 640, 0, 160, 160, 0.8, 0.5, 0.17, 0.001, 3, None, None, None, None,
-                               None, None, None, None, 0, None) == 0       # N == 0: nothing to do
+    assert lib.fp_render_crops(None, None, None, None, 0.17, None, None, None, None, None, 0, 480, 640, 0, 160, 160, 0.8, 0.5, 0.001, 3,
+                               None, None, None, None, None, None, None, None, 0, None) == 0       # N == 0: nothing to do
 
 
 def test_product_does_not_import_oracle():

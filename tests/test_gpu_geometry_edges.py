@@ -117,7 +117,7 @@ def handles(scene, dev):
 
 
 def _render_in_arenas(handle, P, bb, K, H, W, out_hw, diameter, dev, normalize=True, f16=False):
-    """fp_render_crops (the single-mesh entry point) with every output inside a poisoned arena -> (dict of tensors, arenas)"""
+    """fp_render_crops (one mesh, one host K) with every output inside a poisoned arena -> (dict of tensors, arenas)"""
     import ctypes as C
     from foundationpose_amd import _lib, ops
     N, (oh, ow) = int(P.shape[0]), out_hw
@@ -130,9 +130,10 @@ def _render_in_arenas(handle, P, bb, K, H, W, out_hw, diameter, dev, normalize=T
     K9 = ops._hostK32(K)
     p = lambda k: C.c_void_p(ar[k].view.data_ptr())
     flags = (ops.FLAG_NORMALIZE_XYZ if normalize else 0) | (ops.FLAG_OUT_F16 if f16 else 0)
-    st = L.fp_render_crops(handle.handle, C.c_void_p(P.data_ptr()), C.c_void_p(bb.data_ptr()), K9.ctypes.data_as(C.c_void_p), int(H),
-                           int(W), N, oh, ow, 0.8, 0.5, float(np.float32(diameter)), 0.001, flags, p("A"), p("color"), p("depth"),
-                           p("xyz"), p("normal"), p("zbuf"), p("tri_id"), C.c_void_p(ws.data_ptr()), ws.numel(), ops._stream(P))
+    st = L.fp_render_crops(handle.handle, None, None, None, float(np.float32(diameter)), C.c_void_p(P.data_ptr()),
+                           C.c_void_p(bb.data_ptr()), K9.ctypes.data_as(C.c_void_p), None, None, 0, int(H), int(W), N, oh, ow, 0.8, 0.5,
+                           0.001, flags, p("A"), p("color"), p("depth"), p("xyz"), p("normal"), p("zbuf"), p("tri_id"),
+                           C.c_void_p(ws.data_ptr()), ws.numel(), ops._stream(P))
     _lib.check(st, "fp_render_crops")
     torch.cuda.synchronize()
     return {k: a.view for k, a in ar.items()}, ar

@@ -1,6 +1,6 @@
-"""GPU: several objects per refine call -- a per-hypothesis object index from the multi-mesh rasteriser (fp_render_crops_multi) up to
+"""GPU: several objects per refine call -- a per-hypothesis object index from the multi-mesh rasteriser (fp_render_crops with a set) up to
 estimater.track_objects.  Every hypothesis of a multi-object call must see what a call for its own object alone computes: the
-kernels bit for bit against their scalar entry points, the refine loop against per-object calls, the graphed tracker against its
+kernels bit for bit against their scalar form, the refine loop against per-object calls, the graphed tracker against its
 eager loop, and the estimator against per-object track_one."""
 import os
 
@@ -197,8 +197,8 @@ def test_render_multi_one_mesh_and_argument_checks(scene, dev, meshes, gmeshes):
     with pytest.raises(_lib.FpAmdError, match="object index"):
         ops.render_crops(two, P, bb, scene["K"], 480, 640, mesh_diameter=ops.object_diameters(diam, dev))
     lib = _lib.lib()
-    assert lib.fp_render_crops_multi(two.handle, None, None, _devptr(P), _devptr(bb), None, 480, 640, 6, 160, 160, 0.8, 0.5, 0.001, 0,
-                                     None, None, None, None, None, None, None, None, 0, None) == -1
+    assert lib.fp_render_crops(None, two.handle, None, None, 0.0, _devptr(P), _devptr(bb), None, None, None, 0, 480, 640, 6, 160, 160,
+                               0.8, 0.5, 0.001, 0, None, None, None, None, None, None, None, None, 0, None) == -1
     assert b"obj is NULL but the set has 2 meshes" in lib.fp_last_error()
 
 

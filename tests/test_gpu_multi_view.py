@@ -1,6 +1,6 @@
-"""GPU: several camera frames per refine call -- a per-hypothesis view index from the kernels (the *_views entry points and the
+"""GPU: several camera frames per refine call -- a per-hypothesis view index from the kernels (the crop stage with a view table and the
 batched ingest) up to estimater.track_views.  Every hypothesis of a multi-view call must see what a call on its own frame alone
-computes: the kernels bit for bit against their *_multi entry points called per view, the refine loop against per-view calls, the
+computes: the kernels bit for bit against their host-K form called per view, the refine loop against per-view calls, the
 graphed tracker against its eager loop, and the estimator against per-estimator track_one on its own frame."""
 import numpy as np
 import pytest
@@ -46,7 +46,7 @@ def _rows(idx, v):
     return np.nonzero(np.asarray(idx) == v)[0]
 
 
-# ------------------------------------------------------------------ 1. per kernel against the *_multi entry points per view
+# ------------------------------------------------------------------ 1. per kernel against the host-K form per view
 ALL_OUT = ("A", "color", "depth", "xyz", "zbuf", "tri_id")
 
 

@@ -1,4 +1,4 @@
-"""CPU: the multi-object entry points (several objects per refine call) -- argument errors of the C ABI, reported without a GPU,
+"""CPU: the crop stage with an object table (several objects per refine call) -- argument errors of the C ABI, reported without a GPU,
 the per-object grouping of the two-pose quirk on hand-made object indices, and track_objects' refusals that need no device."""
 import ctypes as C
 
@@ -34,34 +34,40 @@ def test_mesh_set_argument_errors_are_reported_without_gpu():
         finally:
             lib.fp_mesh_destroy(huge)
         # a NULL set is refused by the render and sized as nothing
-        assert lib.fp_render_crops_multi(None, None, None, C.c_void_p(16), None, C.c_void_p(16), 480, 640, 4, 160, 160, 0.8, 0.5,
-                                         0.001, 1, None, None, None, None, None, None, None, None, 0, None) == -1
-        assert b"NULL mesh set" in lib.fp_last_error()
+        P = C.c_void_p(16)
+        render = lambda mesh, set_, obj, diam, flags, K=P, Ks=None, view=None, V=0: lib.fp_render_crops(
+            mesh, set_, obj, diam, 0.0, P, None, K, Ks, view, V, 480, 640, 4, 160, 160, 0.8, 0.5, 0.001, flags, None, None, None, None,
+            None, None, None, None, 0, None)
+        assert render(None, None, None, None, 1) == -1
+        assert b"NULL mesh set" in lib.fp_last_error() and b"and NULL mesh" in lib.fp_last_error()     # neither a mesh nor a set
         assert lib.fp_mesh_set_workspace_bytes(None, 4, 160, 160) == 0
-        # the per-object diameter entry points: no diameters, no objects, obj NULL with several objects, unknown flags
-        assert lib.fp_crop_windows_multi(C.c_void_p(16), None, None, C.c_void_p(16), 2, 1.2, 160, 160, 4, C.c_void_p(16),
-                                         C.c_void_p(16), None) == -1
-        assert b"fp_crop_windows_multi: need the diameters" in lib.fp_last_error()
-        assert lib.fp_crop_windows_multi(C.c_void_p(16), None, C.c_void_p(16), None, 3, 1.2, 160, 160, 4, C.c_void_p(16),
-                                         C.c_void_p(16), None) == -1
+        # both a mesh and a set (made-up set handle: refused before it is read)
+        assert render(m1, P, None, None, 1) == -1 and b"both a mesh and a mesh set" in lib.fp_last_error()
+        # the per-object diameter table: no diameters, no objects, obj NULL with several objects, unknown flags
+        crop = lambda K, Ks, view, V, diam, obj, M: lib.fp_crop_windows(P, K, Ks, view, V, 0.0, diam, obj, M, 1.2, 160, 160, 4, P, P, None)
+        assert crop(None, None, None, 0, None, P, 2) == -1
+        assert b"fp_crop_windows: need the diameters" in lib.fp_last_error()
+        assert crop(None, None, None, 0, P, None, 3) == -1
         assert b"obj is NULL but there are 3 objects" in lib.fp_last_error()
-        assert lib.fp_warp_crops_multi(None, None, None, None, None, None, C.c_void_p(16), None, 2, 1, 0, 480, 640, 4, 160, 160,
-                                       None, None) == -1
-        assert b"fp_warp_crops_multi: obj is NULL" in lib.fp_last_error()
-        assert lib.fp_warp_crops_multi(None, None, None, None, None, None, C.c_void_p(16), None, 0, 1, 0, 480, 640, 4, 160, 160,
-                                       None, None) == -1
-        assert lib.fp_warp_crops_multi(C.c_void_p(16), C.c_void_p(16), None, C.c_void_p(16), C.c_void_p(16), C.c_void_p(16),
-                                       C.c_void_p(16), C.c_void_p(16), 2, 1, 7, 480, 640, 4, 160, 160, C.c_void_p(16), None) == -1
-        assert b"fp_warp_crops_multi: unknown mode 7" in lib.fp_last_error()
-        assert lib.fp_pose_update_multi(C.c_void_p(16), C.c_void_p(16), C.c_void_p(16), 0, 1, None, 0.35, C.c_void_p(16), None, 4,
-                                        8, C.c_void_p(16), None, None, 0, None, None, 0.0, None) == -1
-        assert b"fp_pose_update_multi: obj is NULL but there are 4 objects" in lib.fp_last_error()
-        assert lib.fp_pose_update_multi(C.c_void_p(16), C.c_void_p(16), C.c_void_p(16), 5, 1, None, 0.35, C.c_void_p(16),
-                                        C.c_void_p(16), 4, 8, C.c_void_p(16), None, None, 0, None, None, 0.0, None) == -1
-        assert b"fp_pose_update_multi: unknown rot_rep 5" in lib.fp_last_error()
+        # the camera: K and a view table, or neither
+        assert crop(P, P, P, 2, P, P, 2) == -1 and b"fp_crop_windows: both K and a view table" in lib.fp_last_error()
+        assert crop(None, None, None, 0, P, P, 2) == -1 and b"fp_crop_windows: neither K nor a view table" in lib.fp_last_error()
+        assert lib.fp_warp_crops(None, None, None, None, None, None, None, 0, None, 0.0, P, None, 2, 1, 0, 480, 640, 4, 160, 160,
+                                 None, None) == -1
+        assert b"fp_warp_crops: obj is NULL" in lib.fp_last_error()
+        assert lib.fp_warp_crops(None, None, None, None, None, None, None, 0, None, 0.0, P, None, 0, 1, 0, 480, 640, 4, 160, 160,
+                                 None, None) == -1
+        assert lib.fp_warp_crops(P, P, None, P, P, None, None, 0, P, 0.0, P, P, 2, 1, 7, 480, 640, 4, 160, 160, P, None) == -1
+        assert b"fp_warp_crops: unknown mode 7" in lib.fp_last_error()
+        assert lib.fp_pose_update(P, P, P, 0, 1, None, 0.35, 0.0, P, None, 4, 8, P, None, None, 0, None, None, None, 0, None, 0.0,
+                                  None) == -1
+        assert b"fp_pose_update: obj is NULL but there are 4 objects" in lib.fp_last_error()
+        assert lib.fp_pose_update(P, P, P, 5, 1, None, 0.35, 0.0, P, P, 4, 8, P, None, None, 0, None, None, None, 0, None, 0.0,
+                                  None) == -1
+        assert b"fp_pose_update: unknown rot_rep 5" in lib.fp_last_error()
         # nothing to do
-        assert lib.fp_pose_update_multi(None, None, None, 0, 1, None, 0.35, C.c_void_p(16), None, 1, 0, None, None, None, 0, None,
-                                        None, 0.0, None) == 0
+        assert lib.fp_pose_update(None, None, None, 0, 1, None, 0.35, 0.0, P, None, 1, 0, None, None, None, 0, None, None, None, 0,
+                                  None, 0.0, None) == 0
         # a real set needs the device table; without a GPU its creation fails loudly, with one the render checks obj
         st = lib.fp_mesh_set_create(arr, 2, C.byref(s))
         if st != 0:
@@ -70,15 +76,11 @@ def test_mesh_set_argument_errors_are_reported_without_gpu():
             try:
                 # sized by the largest V and T of the set; T > 65535: 32-bit triangle lists
                 assert lib.fp_mesh_set_workspace_bytes(s, 4, 160, 160) == lib.fp_workspace_bytes(4, 40000, 70000, 160, 160)
-                assert lib.fp_render_crops_multi(s, None, C.c_void_p(16), C.c_void_p(16), None, C.c_void_p(16), 480, 640, 4, 160,
-                                                 160, 0.8, 0.5, 0.001, 1, None, None, None, None, None, None, None, None, 0, None) == -1
+                assert render(None, s, None, P, 1) == -1
                 assert b"obj is NULL but the set has 2 meshes" in lib.fp_last_error()
-                assert lib.fp_render_crops_multi(s, C.c_void_p(16), None, C.c_void_p(16), None, C.c_void_p(16), 480, 640, 4, 160,
-                                                 160, 0.8, 0.5, 0.001, 1, None, None, None, None, None, None, None, None, 0, None) == -1
+                assert render(None, s, P, None, 1) == -1
                 assert b"FP_FLAG_NORMALIZE_XYZ needs the diameters" in lib.fp_last_error()
-                assert lib.fp_render_crops_multi(s, C.c_void_p(16), None, C.c_void_p(16), None, C.c_void_p(16), 480, 640, 4, 160,
-                                                 160, 0.8, 0.5, 0.001, 0x10000, None, None, None, None, None, None, None, None, 0,
-                                                 None) == -1
+                assert render(None, s, P, None, 0x10000) == -1
                 assert b"unknown flag bits" in lib.fp_last_error()
             finally:
                 lib.fp_mesh_set_destroy(s)

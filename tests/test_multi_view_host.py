@@ -1,4 +1,4 @@
-"""CPU: the multi-view entry points (several camera frames per refine call) -- argument errors of the C ABI, reported without a GPU,
+"""CPU: the crop stage with a view table (several camera frames per refine call) -- argument errors of the C ABI, reported without a GPU,
 the (view, object) grouping of the two-pose quirk on hand-made indices, and the refusals of ops.Views and track_views that need no
 device."""
 import ctypes as C
@@ -13,36 +13,41 @@ def test_views_entry_points_report_argument_errors_without_gpu():
     from foundationpose_amd import _lib
     lib = _lib.lib()
     # crop windows: NULL K table, V < 1, view NULL with V > 1, obj NULL with several objects
-    assert lib.fp_crop_windows_views(P16, None, P16, 2, P16, P16, 2, 1.2, 160, 160, 4, P16, P16, None) == -1
-    assert b"fp_crop_windows_views: need the K table" in lib.fp_last_error()
-    assert lib.fp_crop_windows_views(P16, P16, P16, 0, P16, P16, 2, 1.2, 160, 160, 4, P16, P16, None) == -1
+    crop = lambda Ks, view, V, obj, N=4, diam=P16, M=2: lib.fp_crop_windows(P16 if N else None, None, Ks, view, V, 0.0, diam, obj, M, 1.2,
+                                                                            160, 160, N, P16 if N else None, P16 if N else None, None)
+    assert crop(None, P16, 2, P16) == -1
+    assert b"fp_crop_windows: need the K table" in lib.fp_last_error()
+    assert crop(P16, P16, 0, P16) == -1
     assert b"V >= 1 views (V=0)" in lib.fp_last_error()
-    assert lib.fp_crop_windows_views(P16, P16, None, 3, P16, P16, 2, 1.2, 160, 160, 4, P16, P16, None) == -1
+    assert crop(P16, None, 3, P16) == -1
     assert b"view is NULL but there are 3 views" in lib.fp_last_error()
-    assert lib.fp_crop_windows_views(P16, P16, P16, 3, P16, None, 2, 1.2, 160, 160, 4, P16, P16, None) == -1
+    assert crop(P16, P16, 3, None) == -1
     assert b"obj is NULL but there are 2 objects" in lib.fp_last_error()
+    # a view table goes with the diameter table: Ks with a scalar diameter is refused and says so
+    assert crop(P16, P16, 2, None, diam=None, M=0) == -1
+    assert b"fp_crop_windows: a view table (Ks) with a scalar diameter" in lib.fp_last_error()
     # render: NULL set, unknown flags, NULL K table, missing view index
-    args = lambda Ks, view, V, flags: (None, None, None, Ks, view, V, P16, P16, 480, 640, 4, 160, 160, 0.8, 0.5, 0.001, flags,
-                                       None, None, None, None, None, None, None, None, 0, None)
-    assert lib.fp_render_crops_views(*args(P16, P16, 2, 1)) == -1 and b"fp_render_crops_views: NULL mesh set" in lib.fp_last_error()
-    assert lib.fp_render_crops_views(*args(P16, P16, 2, 0x40)) == -1
-    assert b"fp_render_crops_views: unknown flag bits 0x40" in lib.fp_last_error()
+    args = lambda Ks, view, V, flags: (None, None, None, None, 0.0, P16, P16, None, Ks, view, V, 480, 640, 4, 160, 160, 0.8, 0.5, 0.001,
+                                       flags, None, None, None, None, None, None, None, None, 0, None)
+    assert lib.fp_render_crops(*args(P16, P16, 2, 1)) == -1 and b"fp_render_crops: NULL mesh set" in lib.fp_last_error()
+    assert lib.fp_render_crops(*args(P16, P16, 2, 0x40)) == -1
+    assert b"fp_render_crops: unknown flag bits 0x40" in lib.fp_last_error()
     # warp: unknown flags, NULL K table, V < 1, missing view index, unknown mode
-    wargs = lambda Ks, view, V, flags, mode: (P16, P16, P16, P16, Ks, view, V, P16, P16, P16, 2, flags, mode, 480, 640, 4, 160,
-                                              160, P16, None)
-    assert lib.fp_warp_crops_views(*wargs(P16, P16, 2, 0x10, 0)) == -1
-    assert b"fp_warp_crops_views: unknown flag bits 0x10" in lib.fp_last_error()
-    assert lib.fp_warp_crops_views(*wargs(None, P16, 2, 1, 0)) == -1 and b"need the K table" in lib.fp_last_error()
-    assert lib.fp_warp_crops_views(*wargs(P16, P16, 0, 1, 0)) == -1 and b"(V=0)" in lib.fp_last_error()
-    assert lib.fp_warp_crops_views(*wargs(P16, None, 2, 1, 0)) == -1 and b"view is NULL but there are 2 views" in lib.fp_last_error()
-    assert lib.fp_warp_crops_views(*wargs(P16, P16, 2, 1, 7)) == -1 and b"fp_warp_crops_views: unknown mode 7" in lib.fp_last_error()
+    wargs = lambda Ks, view, V, flags, mode: (P16, P16, P16, P16, None, Ks, view, V, P16, 0.0, P16, P16, 2, flags, mode, 480, 640, 4,
+                                              160, 160, P16, None)
+    assert lib.fp_warp_crops(*wargs(P16, P16, 2, 0x10, 0)) == -1
+    assert b"fp_warp_crops: unknown flag bits 0x10" in lib.fp_last_error()
+    assert lib.fp_warp_crops(*wargs(None, P16, 2, 1, 0)) == -1 and b"need the K table" in lib.fp_last_error()
+    assert lib.fp_warp_crops(*wargs(P16, P16, 0, 1, 0)) == -1 and b"(V=0)" in lib.fp_last_error()
+    assert lib.fp_warp_crops(*wargs(P16, None, 2, 1, 0)) == -1 and b"view is NULL but there are 2 views" in lib.fp_last_error()
+    assert lib.fp_warp_crops(*wargs(P16, P16, 2, 1, 7)) == -1 and b"fp_warp_crops: unknown mode 7" in lib.fp_last_error()
     # pose update: NULL K table, missing view index, unknown rot_rep / trans_rep
-    pargs = lambda Ks, view, V, rr, tr: (P16, P16, P16, rr, 1, None, 0.35, P16, P16, 2, 8, P16, None, None, tr, Ks, view, V, P16,
-                                         160.0, None)
-    assert lib.fp_pose_update_views(*pargs(None, P16, 2, 0, 0)) == -1 and b"fp_pose_update_views: need the K table" in lib.fp_last_error()
-    assert lib.fp_pose_update_views(*pargs(P16, None, 2, 0, 0)) == -1 and b"view is NULL but there are 2 views" in lib.fp_last_error()
-    assert lib.fp_pose_update_views(*pargs(P16, P16, 2, 5, 0)) == -1 and b"unknown rot_rep 5" in lib.fp_last_error()
-    assert lib.fp_pose_update_views(*pargs(P16, P16, 2, 0, 9)) == -1 and b"unknown trans_rep 9" in lib.fp_last_error()
+    pargs = lambda Ks, view, V, rr, tr: (P16, P16, P16, rr, 1, None, 0.35, 0.0, P16, P16, 2, 8, P16, None, None, tr, None, Ks, view, V,
+                                         P16, 160.0, None)
+    assert lib.fp_pose_update(*pargs(None, P16, 2, 0, 0)) == -1 and b"fp_pose_update: need the K table" in lib.fp_last_error()
+    assert lib.fp_pose_update(*pargs(P16, None, 2, 0, 0)) == -1 and b"view is NULL but there are 2 views" in lib.fp_last_error()
+    assert lib.fp_pose_update(*pargs(P16, P16, 2, 5, 0)) == -1 and b"unknown rot_rep 5" in lib.fp_last_error()
+    assert lib.fp_pose_update(*pargs(P16, P16, 2, 0, 9)) == -1 and b"unknown trans_rep 9" in lib.fp_last_error()
     # the batched ingest: V < 1, NULL K table
     assert lib.fp_depth_erode_frames(P16, P16, 480, 640, 0, 2, 0.001, 0.8, 100.0, None) == -1
     assert b"fp_depth_erode_frames: V=0" in lib.fp_last_error()
@@ -51,7 +56,7 @@ def test_views_entry_points_report_argument_errors_without_gpu():
     assert lib.fp_depth_to_xyz_frames(P16, None, 1e9, 0, P16, 480, 640, 2, None) == -1
     assert b"fp_depth_to_xyz_frames: NULL K table" in lib.fp_last_error()
     # N == 0 after valid tables is a no-op
-    assert lib.fp_crop_windows_views(None, P16, P16, 2, P16, P16, 2, 1.2, 160, 160, 0, None, None, None) == 0
+    assert crop(P16, P16, 2, P16, N=0) == 0
 
 
 def test_quirk_is_grouped_per_view_and_object():
