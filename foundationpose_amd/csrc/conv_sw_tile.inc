@@ -42,13 +42,11 @@
                "s"(gi.HoWo), "s"(gi.Wo), "s"(gi.Hp), "s"(gi.Wp), "s"(gi.mulP), "s"(gi.shrP), "s"(gi.mulW), "s"(gi.shrW));
   __builtin_amdgcn_sched_barrier(0);               // nothing that needs a part of the head is scheduled in front of the loads of the rest
 
-  // XCD-aware tile order (as igemm.hip): neighbouring pixel tiles (overlapping halos) and the channel tiles of one pixel
+  // XCD-aware tile order (ig_xcd_tile): neighbouring pixel tiles (overlapping halos) and the channel tiles of one pixel
   // tile run on the same XCD
   const int tiles_n = N / BN;
-  const int nwg = (int)(((unsigned)M + BM - 1) / BM) * tiles_n;   // == gridDim.x (sw_launch), without the round trip for a hidden argument
-  const int xcd = blockIdx.x & 7, loc = blockIdx.x >> 3;
-  const int qd8 = nwg >> 3, r8 = nwg & 7;
-  const int tile = (xcd < r8 ? xcd * (qd8 + 1) : r8 * (qd8 + 1) + (xcd - r8) * qd8) + loc;
+  const int nwg = (int)(((unsigned)M + BM - 1) / BM) * tiles_n;   // == gridDim.x (ig_launch_tiles), without the round trip for a hidden argument
+  const int tile = ig_xcd_tile(blockIdx.x, nwg);
   // (the emulated scalar division is ~35 instructions in front of the first DMA; every layer of the two networks has 1, 2 or 4 channel tiles)
   const int bm = __builtin_popcount(tiles_n) == 1 ? tile >> __builtin_ctz(tiles_n) : tile / tiles_n, bn = tile - bm * tiles_n;
   const int m0 = bm * BM, n0 = bn * BN;
@@ -314,7 +312,7 @@
   SW_CLK(t_loop);
   if constexpr (DIRECT) {
     // p.epi is one of the four layer kinds without the positional output (sw_direct below): a scalar branch
-    const IgEpiArgs q = {p.out, p.res, p.R, p.Y, p.pe, p.Ype, p.pe_period, p.pe_mul, p.pe_shr, p.N};
+    const IgEpiArgs q = ig_epi_args(p);
     const int* rowY32 = reinterpret_cast<const int*>(smem + STAGES_BYTES);
 #define SW_DIRECT_CASE(E)                                                                                     \
     case E:                                                                                                   \

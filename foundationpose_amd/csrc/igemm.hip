@@ -32,7 +32,6 @@
 int fp_igemm_pp_launch(const IgemmParams& p, int variant, hipStream_t stream);   // igemm_pp.hip
 int fp_conv3x3_sw_launch(const IgemmParams& p, hipStream_t stream);               // conv_sw.hip (shifted-window 3x3)
 bool fp_conv3x3_sw_applicable(const IgemmParams& p);
-int fp_conv3x3_sw_tile_rows(const IgemmParams& p);
 
 // Workgroup tile BM (pixels) x BN (channels) x 64 (k); every wave owns (32*TM) x 64 outputs as TM x 2
 // v_mfma_f32_32x32x16_f16 tiles; NST LDS stages (prefetch distance NST-1 k-steps, counted vmcnt + raw s_barrier).
@@ -67,12 +66,9 @@ __global__ __launch_bounds__((BM / (32 * TM)) * (BN / 64) * 64, ((BM / (32 * TM)
   const int wm = wid / NWN, wn = wid - wm * NWN;   // wave position: pixels (m) x channels (n)
   float* bias_lds = reinterpret_cast<float*>(smem + LDS_MAIN);
 
-  // ---- XCD-aware tile order (bijective for any grid size)
   const int tiles_n = p.N / BN;
   const int nwg = gridDim.x;
-  const int xcd = blockIdx.x & 7, loc = blockIdx.x >> 3;
-  const int q = nwg >> 3, r8 = nwg & 7;
-  const int tile = (xcd < r8 ? xcd * (q + 1) : r8 * (q + 1) + (xcd - r8) * q) + loc;
+  const int tile = ig_xcd_tile(blockIdx.x, nwg);
   const int bm = tile / tiles_n, bn = tile - bm * tiles_n;
   const int m0 = bm * BM, n0 = bn * BN;
   const int Ktot = p.taps * p.Cin;
@@ -220,24 +216,17 @@ template <int BM, int BN, int TM, int NST, int BK>
 static int ig_launch(const IgemmParams& p, hipStream_t stream) {
   constexpr int LDS = ig_lds_main<BM, BN>(NST * (BM + BN) * BK * 2) + IG_BIAS_LDS;
   constexpr int THREADS = (BM / (32 * TM)) * (BN / 64) * 64;
-  static_assert(LDS <= 160 * 1024, "tile does not fit the 160 KiB LDS");
-  const long long tiles = (long long)fp_cdiv(p.M, BM) * (p.N / BN);
-  FP_REQUIRE(tiles < (1ll << 31), "fp_igemm_f16_fwd: too many tiles");
-  FP_SET_MAX_LDS((k_igemm_f16<BM, BN, TM, NST, BK>), LDS);
-  hipLaunchKernelGGL((k_igemm_f16<BM, BN, TM, NST, BK>), dim3((unsigned)tiles), dim3(THREADS), LDS, stream, p);
-  FP_CHECK_LAUNCH("fp_igemm_f16_fwd");
-  return FP_OK;
+  return ig_launch_tiles<k_igemm_f16<BM, BN, TM, NST, BK>, BM, BN, THREADS, LDS>(p, stream, "fp_igemm_f16_fwd");
 }
 
 // The second half of a split-K product: one thread per accumulator quad (4 consecutive channels of one pixel) adds the k ranges IN
 // RANGE ORDER (deterministic; another fp32 summation order than the unsplit kernel's) and applies the epilogue of
-// igemm_epilogue.h to its four values -- the same operations in the same order per element: bias / conv rounding / BatchNorm,
-// residual add as an IEEE half add, ReLU, the optional positional second output.
+// igemm_epilogue.h to its four values through that file's per-element helpers: ig_round4 (bias / conv rounding / BatchNorm),
+// residual add as an IEEE half add, ig_relu, ig_add_pe for the optional positional second output.
 template <int BM, int BN, int TM>
 __global__ __launch_bounds__(256) void k_splitk_epilogue(IgemmParams p, int ntiles) {
   constexpr int NWN = BN / 64, NW = (BM / (32 * TM)) * NWN;
   typedef float float4_ __attribute__((ext_vector_type(4)));
-  typedef _Float16 half2_ __attribute__((ext_vector_type(2)));
   const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x;
   const int lane = (int)(t & 63);
   size_t q = t >> 6;
@@ -260,41 +249,23 @@ __global__ __launch_bounds__(256) void k_splitk_epilogue(IgemmParams p, int ntil
     const float4_ b = src[(size_t)s * per_split];
     a[0] += b[0]; a[1] += b[1]; a[2] += b[2]; a[3] += b[3];
   }
-  float4_ bv = {0.f, 0.f, 0.f, 0.f};
+  const float4_ zero = {0.f, 0.f, 0.f, 0.f};
+  float4_ bv = zero;                               // no bias: + 0
   if (p.bias) bv = *reinterpret_cast<const float4_*>(p.bias + n);
+  const ig_half2 b01 = {(_Float16)bv[0], (_Float16)bv[1]}, b23 = {(_Float16)bv[2], (_Float16)bv[3]};
   half4 v;
-  if (p.round_acc) {
-    const half2_ b01 = {(_Float16)bv[0], (_Float16)bv[1]}, b23 = {(_Float16)bv[2], (_Float16)bv[3]};
-    half2_ t01 = {(_Float16)a[0], (_Float16)a[1]};
-    half2_ t23 = {(_Float16)a[2], (_Float16)a[3]};
-    t01 = t01 + b01;
-    t23 = t23 + b23;
-    if (p.bn_scale) {
-      const float4_ sc = *reinterpret_cast<const float4_*>(p.bn_scale + n), sh = *reinterpret_cast<const float4_*>(p.bn_shift + n);
-      v[0] = (_Float16)fmaf((float)t01[0], sc[0], sh[0]);
-      v[1] = (_Float16)fmaf((float)t01[1], sc[1], sh[1]);
-      v[2] = (_Float16)fmaf((float)t23[0], sc[2], sh[2]);
-      v[3] = (_Float16)fmaf((float)t23[1], sc[3], sh[3]);
-    } else {
-      v[0] = t01[0]; v[1] = t01[1]; v[2] = t23[0]; v[3] = t23[1];
-    }
+  if (!p.round_acc) {
+    v = ig_round4<false, false>(a[0], a[1], a[2], a[3], bv, b01, b23, zero, zero);
+  } else if (p.bn_scale) {
+    const float4_ sc = *reinterpret_cast<const float4_*>(p.bn_scale + n), sh = *reinterpret_cast<const float4_*>(p.bn_shift + n);
+    v = ig_round4<true, true>(a[0], a[1], a[2], a[3], bv, b01, b23, sc, sh);
   } else {
-#pragma unroll
-    for (int e = 0; e < 4; ++e) v[e] = (_Float16)(a[e] + bv[e]);
+    v = ig_round4<true, false>(a[0], a[1], a[2], a[3], bv, b01, b23, zero, zero);
   }
   if (p.R) v = v + *reinterpret_cast<const half4*>(p.R + ig_row_off(p.res, m) + n);
-  if (p.relu) {
-    const half4 zero = {0, 0, 0, 0};
-    v = __builtin_elementwise_max(v, zero);
-  }
+  if (p.relu) v = ig_relu(v);
   *reinterpret_cast<half4*>(p.Y + ig_row_off(p.out, m) + n) = v;
-  if (p.Ype) {
-    const float4_ e0 = *reinterpret_cast<const float4_*>(p.pe + (size_t)(m % p.pe_period) * p.N + n);
-    half4 w;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) w[e] = (_Float16)((float)v[e] + e0[e]);
-    *reinterpret_cast<half4*>(p.Ype + (size_t)m * p.N + n) = w;
-  }
+  if (p.Ype) *reinterpret_cast<half4*>(p.Ype + (size_t)m * p.N + n) = ig_add_pe(v, p.pe + (size_t)(m % p.pe_period) * p.N + n);
 }
 
 // split-K always runs the 128 x 128 x 64 tile (4 waves, two stages): it exists for launches of a few dozen tiles
@@ -304,11 +275,9 @@ static size_t ig_splitk_bytes(int M, int N, int splits) {
 }
 static int ig_launch_splitk(const IgemmParams& p, hipStream_t stream) {
   constexpr int LDS = ig_lds_main<SK_BM, SK_BN>(SK_NST * (SK_BM + SK_BN) * SK_BK * 2) + IG_BIAS_LDS;
+  if (int err = ig_launch_tiles<k_igemm_f16<SK_BM, SK_BN, SK_TM, SK_NST, SK_BK, true>, SK_BM, SK_BN, 256, LDS>(p, stream, "fp_igemm_f16_splitk_fwd(partial products)"))
+    return err;
   const long long tiles = (long long)fp_cdiv(p.M, SK_BM) * (p.N / SK_BN);
-  FP_REQUIRE(tiles * p.nsplit < (1ll << 31) && p.nsplit <= 65535, "fp_igemm_f16_splitk_fwd: too many tiles");
-  FP_SET_MAX_LDS((k_igemm_f16<SK_BM, SK_BN, SK_TM, SK_NST, SK_BK, true>), LDS);
-  hipLaunchKernelGGL((k_igemm_f16<SK_BM, SK_BN, SK_TM, SK_NST, SK_BK, true>), dim3((unsigned)tiles, (unsigned)p.nsplit), dim3(256), LDS, stream, p);
-  FP_CHECK_LAUNCH("fp_igemm_f16_splitk_fwd(partial products)");
   const long long threads = tiles * 4 * (8 * SK_TM) * 64;
   hipLaunchKernelGGL((k_splitk_epilogue<SK_BM, SK_BN, SK_TM>), dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, stream, p, (int)tiles);
   FP_CHECK_LAUNCH("fp_igemm_f16_splitk_fwd(reduce + epilogue)");

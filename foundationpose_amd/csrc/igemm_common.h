@@ -1,4 +1,5 @@
-// Shared by igemm.hip and conv3x3.hip: operand addressing and the kernel parameter block of fp_igemm_f16_fwd.
+// Shared by igemm.hip, igemm_pp.hip and conv_sw.hip: operand addressing, the kernel parameter block of fp_igemm_f16_fwd, the tile order
+// and the launcher of the tile kernels.
 #pragma once
 #include <hip/hip_fp16.h>
 #include <stddef.h>
@@ -96,5 +97,28 @@ __device__ __forceinline__ long long ig_row_off(const IgemmGeom& g, int m) {
   if (g.bsplit > 0) { cg = ig_fastdiv(b, g.mulB, g.shrB); bb = b - cg * g.bsplit; }
   return (((long long)bb * g.Hp + (oy * g.stride + g.off)) * g.Wp + (ox * g.stride + g.off)) * g.cstride + g.coff +
          (long long)cg * g.cgroup;
+}
+
+// XCD-aware tile order (bijective for any grid size): workgroup `block` of a grid of nwg runs on XCD block % 8, and the tiles of one XCD are
+// consecutive -- the channel tiles of one pixel tile, and neighbouring pixel tiles, share that XCD's L2.
+// (block as unsigned: the shift of blockIdx.x stays a logical one)
+__device__ __forceinline__ int ig_xcd_tile(unsigned block, int nwg) {
+  const int xcd = block & 7, loc = block >> 3;
+  const int q = nwg >> 3, r8 = nwg & 7;
+  return (xcd < r8 ? xcd * (q + 1) : r8 * (q + 1) + (xcd - r8) * q) + loc;
+}
+
+// The launch of a tile kernel of the family: one workgroup of THREADS threads and LDS bytes per BM x BN tile, times the k ranges of a
+// split-K product (IgemmParams.nsplit; 0 = not split).  `name` is the launch's in the error text.
+template <void (&KERNEL)(IgemmParams), int BM, int BN, int THREADS, int LDS>
+static int ig_launch_tiles(const IgemmParams& p, hipStream_t stream, const char* name) {
+  static_assert(LDS <= 160 * 1024, "tile does not fit the 160 KiB LDS");
+  const long long tiles = (long long)fp_cdiv(p.M, BM) * (p.N / BN);
+  const int ny = p.nsplit ? p.nsplit : 1;
+  FP_REQUIRE(tiles * ny < (1ll << 31) && ny <= 65535, "%s: too many tiles", p.nsplit ? "fp_igemm_f16_splitk_fwd" : "fp_igemm_f16_fwd");
+  FP_SET_MAX_LDS(KERNEL, LDS);
+  hipLaunchKernelGGL(KERNEL, dim3((unsigned)tiles, (unsigned)ny), dim3(THREADS), LDS, stream, p);
+  FP_CHECK_LAUNCH(name);
+  return FP_OK;
 }
 

@@ -1,4 +1,4 @@
-// Shared epilogue of the implicit-GEMM kernels (igemm.hip, igemm_pp.hip): accumulators (+bias) -> half -> swizzled LDS
+// Shared epilogue of the implicit-GEMM kernels (igemm.hip, igemm_pp.hip, conv_sw.hip): accumulators (+bias) -> half -> swizzled LDS
 // tile E[m][n] -> 16-byte coalesced row stores with the residual add and ReLU applied on the way out.
 // Call after a workgroup barrier that retires every read of the staging buffers (the tile reuses them).
 // LDS layout of a kernel that uses it: [0, ig_lds_main) shared by the staging buffers of the main loop and, afterwards,
@@ -39,9 +39,10 @@ constexpr int ig_lds_main_slim(int stage_bytes) {
 }
 #define IG_ROW_NONE ((int)0x80000000)            // SLIM: a row past M
 
-// Acc: float16_[2][TM], the accumulators of v_mfma_f32_32x32x16_f16 (2 x TM tiles of 32 channels x 32 pixels), or float4_[4][2 * TM],
+// Acc: float16_[2][TM], the accumulators of v_mfma_f32_32x32x16_f16 (2 x TM tiles of 32 channels x 32 pixels), or ig_float4[4][2 * TM],
 // those of v_mfma_f32_16x16x32_f16 (4 x 2 TM tiles of 16 x 16, conv_sw.hip) -- the same 128 x 64 wave tile either way
 typedef float ig_float4 __attribute__((ext_vector_type(4)));
+typedef _Float16 ig_half2 __attribute__((ext_vector_type(2)));
 // What a layer-kind body reads of IgemmParams, copied once in front of the dispatch.  Not for speed: the compiler forwards the reads of a by-value
 // kernel argument to the constant kernel-argument segment only up to a bounded number of reads; past it the whole block is copied to private
 // memory and every scalar of the main loop is read back from there (seen with the sixth body reading IgemmParams directly: an alloca and a memcpy
@@ -57,6 +58,9 @@ struct IgEpiArgs {
   unsigned pe_mul, pe_shr;
   int N;
 };
+__device__ __forceinline__ IgEpiArgs ig_epi_args(const IgemmParams& p) {
+  return {p.out, p.res, p.R, p.Y, p.pe, p.Ype, p.pe_period, p.pe_mul, p.pe_shr, p.N};
+}
 
 // a kernel-argument pointer as the compiler can prove it wave-uniform (a buffer descriptor has to live in scalar registers)
 template <typename T>
@@ -66,42 +70,76 @@ __device__ __forceinline__ T* ig_uniform_ptr(const T* ptr) {
   return reinterpret_cast<T*>(((unsigned long long)hi << 32) | lo);
 }
 
-// max(v, 0) of eight halves as four v_pk_max_f16.  __builtin_elementwise_max is maxnum, which has to quiet a signalling NaN first: for a value
-// read back from LDS the compiler cannot know there is none and puts a v_pk_max_f16(v, v) in front of every max.  The E tile holds results of
-// conversions, adds and FMAs only, which are never signalling, and for every other input the instruction alone returns maxnum's bits
-// (a quiet NaN gives 0, -0 against +0 gives +0, whichever side it is on).
-__device__ __forceinline__ half8 ig_relu8(const half8& v) {
-  typedef _Float16 half2_ __attribute__((ext_vector_type(2)));
-  half8 r;
+// max(v, 0) of four or eight halves (V: half4, half8), one packed fp16 max per pair.  __builtin_elementwise_max is maxnum, which has to
+// quiet a signalling NaN first: for a value read back from LDS or from memory the compiler cannot know there is none and puts a packed
+// max of v with itself in front of every max.  These epilogues hand it results of conversions, adds and FMAs only, which are never
+// signalling, and for every other input the instruction alone returns maxnum's bits (a quiet NaN gives 0, -0 against +0 gives +0,
+// whichever side it is on).
+template <typename V>
+__device__ __forceinline__ V ig_relu(const V& v) {
+  V r;
 #pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    const half2_ x = {v[2 * e], v[2 * e + 1]};
-    half2_ y;
+  for (int e = 0; e < (int)(sizeof(V) / 4); ++e) {
+    const ig_half2 x = {v[2 * e], v[2 * e + 1]};
+    ig_half2 y;
     asm("v_pk_max_f16 %0, %1, 0" : "=v"(y) : "v"(x));
     r[2 * e] = y[0]; r[2 * e + 1] = y[1];
   }
   return r;
 }
 
-// ... of four halves (the direct epilogue below): the same instruction, twice
-__device__ __forceinline__ half4 ig_relu4(const half4& v) {
-  typedef _Float16 half2_ __attribute__((ext_vector_type(2)));
-  half4 r;
+// The rounding policy of one accumulator quad -- four consecutive channels of one pixel -- and the ONLY text of it: every epilogue of the
+// family (ig_epilogue_spec, ig_epilogue_direct, ig_epilogue_generic below; k_splitk_epilogue of igemm.hip) calls it, so they return the
+// same bits given the same accumulators.  bv: the bias, b01 / b23: the same as fp16 pairs (ROUND_ACC only; the caller forms them once per
+// channel quad), sc / sh: BatchNorm scale and shift (HAS_BN only).
+//  * ROUND_ACC: the reference's autocast op sequence for conv (+ BatchNorm): every op rounds its result to fp16.  Packed fp16 math where it
+//    is exact: v_cvt_pk_f16_f32 for the conv output, v_pk_add_f16 for the bias (an IEEE half add of two halves equals their fp32 sum rounded
+//    to half: when the fp32 sum is inexact the smaller addend is below 1/8 ulp of the larger), fp32 FMA for BatchNorm (fp32 statistics).
+//  * otherwise (nn.Linear): one rounding of acc + bias.
+// A missing bias is a bias of +0 (which turns -0 into +0; dropping the add would not).
+template <bool ROUND_ACC, bool HAS_BN>
+__device__ __forceinline__ half4 ig_round4(float a0, float a1, float a2, float a3, const ig_float4& bv, const ig_half2& b01, const ig_half2& b23,
+                                           const ig_float4& sc, const ig_float4& sh) {
+  static_assert(ROUND_ACC || !HAS_BN, "BatchNorm follows the conv rounding");
+  half4 v;
+  if constexpr (ROUND_ACC) {
+    ig_half2 t01 = {(_Float16)a0, (_Float16)a1};
+    ig_half2 t23 = {(_Float16)a2, (_Float16)a3};
+    t01 = t01 + b01;
+    t23 = t23 + b23;
+    if constexpr (HAS_BN) {
+      const ig_half2 t[2] = {t01, t23};
 #pragma unroll
-  for (int e = 0; e < 2; ++e) {
-    const half2_ x = {v[2 * e], v[2 * e + 1]};
-    half2_ y;
-    asm("v_pk_max_f16 %0, %1, 0" : "=v"(y) : "v"(x));
-    r[2 * e] = y[0]; r[2 * e + 1] = y[1];
+      for (int e = 0; e < 4; ++e) v[e] = (_Float16)fmaf((float)t[e >> 1][e & 1], sc[e], sh[e]);
+    } else {
+      v[0] = t01[0]; v[1] = t01[1]; v[2] = t23[0]; v[3] = t23[1];
+    }
+  } else {
+    v[0] = (_Float16)(a0 + bv[0]); v[1] = (_Float16)(a1 + bv[1]); v[2] = (_Float16)(a2 + bv[2]); v[3] = (_Float16)(a3 + bv[3]);
   }
-  return r;
+  return v;
+}
+
+// The positional second output of four or eight channels (V: half4, half8): f16(f32(v) + pe), rounded for the in_proj GEMM
+template <typename V>
+__device__ __forceinline__ V ig_add_pe(const V& v, const float* pe) {
+  constexpr int NQ = sizeof(V) / 8;
+  ig_float4 t[NQ];
+#pragma unroll
+  for (int q = 0; q < NQ; ++q) t[q] = *reinterpret_cast<const ig_float4*>(pe + 4 * q);
+  V w;
+#pragma unroll
+  for (int e = 0; e < 4; ++e)
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) w[4 * q + e] = (_Float16)((float)v[4 * q + e] + t[q][e]);
+  return w;
 }
 
 // ---- Layer-kind bodies (round 9): the epilogue of a WHOLE tile with the layer kind EPI (IG_EPI_* bits, igemm_common.h) fixed at compile
-// time.  The arithmetic per element and its order are the generic body's below, statement for statement -- the same roundings, the same
-// fmaf, IEEE half adds -- so a mode returns the generic body's bits; what goes is what the generic body executes per 4 values around
-// that arithmetic: the tests of round_acc / has_bn, the bias converted to fp16 again for every accumulator group, residual add and ReLU
-// computed and then selected, and addresses rebuilt that move by a compile-time constant:
+// time.  The arithmetic per element is the one copy above (ig_round4, then + residual as an IEEE half add, then ig_relu, then ig_add_pe),
+// so a mode returns the generic body's bits; what goes is what the generic body executes per 4 values around that arithmetic: the tests
+// of round_acc / has_bn, the bias converted to fp16 again for every accumulator group, residual add and ReLU computed and then selected,
+// and addresses rebuilt that move by a compile-time constant:
 //  * E-tile write: row (lane & 15 or & 31) and the swizzled chunk depend on (lane, wn, i) only, so there is one base per channel quad i and
 //    the pixel tile j is a constant in the ds_write offset field (chunk = c0 ^ (m & 15), m & 15 == lane & 15 in every pixel tile);
 //  * store loop: iteration `it` handles row tid / CPR + it * RPI and chunk tid % CPR: RPI is a multiple of 16, so the swizzle term is
@@ -118,14 +156,11 @@ __device__ __forceinline__ void ig_epilogue_spec(const IgEpiArgs& p, Acc& acc, u
   static_assert((EPI & IG_EPI_SPEC) && (EPI & IG_EPI_BIAS), "a layer kind with a bias");
   constexpr bool ROUND_ACC = (EPI & IG_EPI_ROUND_ACC) != 0, HAS_BN = (EPI & IG_EPI_BN) != 0, RES = (EPI & IG_EPI_RES) != 0;
   constexpr bool RELU = (EPI & IG_EPI_RELU) != 0, PE = (EPI & IG_EPI_PE) != 0;
-  static_assert(ROUND_ACC || !HAS_BN, "BatchNorm follows the conv rounding");
   constexpr int CPR = BN / 8;                      // 16-byte chunks per row of the epilogue tile
   constexpr int NIT = (BM * CPR) / THREADS;
   constexpr int RPI = THREADS / CPR;               // rows per iteration of the store loop
   static_assert(THREADS % CPR == 0 && RPI % 16 == 0 && NIT * RPI == BM, "the store loop's swizzle term must not depend on the iteration");
   constexpr int ROWB = 2 * BN;                     // bytes per row of E
-  typedef float float4_ __attribute__((ext_vector_type(4)));
-  typedef _Float16 half2_ __attribute__((ext_vector_type(2)));
   typedef unsigned uint4_ __attribute__((ext_vector_type(4)));
   unsigned char* E = smem;
   long long* rowY = reinterpret_cast<long long*>(smem + BM * ROWB);
@@ -178,38 +213,21 @@ __device__ __forceinline__ void ig_epilogue_spec(const IgEpiArgs& p, Acc& acc, u
   }
   IG_CLK(te2);
   // per-channel values of 4 consecutive channels nl .. nl + 3 (LDS broadcast reads), formed once per channel quad
-  struct Vecs { float4_ bv, sc, sh; half2_ b01, b23; };
+  struct Vecs { ig_float4 bv, sc, sh; ig_half2 b01, b23; };
   auto vecs = [&](int nl) {
     Vecs c;
-    c.bv = *reinterpret_cast<const float4_*>(bias_lds + nl);
-    c.b01 = half2_{(_Float16)c.bv[0], (_Float16)c.bv[1]};
-    c.b23 = half2_{(_Float16)c.bv[2], (_Float16)c.bv[3]};
+    c.bv = *reinterpret_cast<const ig_float4*>(bias_lds + nl);
+    c.b01 = ig_half2{(_Float16)c.bv[0], (_Float16)c.bv[1]};
+    c.b23 = ig_half2{(_Float16)c.bv[2], (_Float16)c.bv[3]};
     if constexpr (HAS_BN) {
-      c.sc = *reinterpret_cast<const float4_*>(bias_lds + IG_VEC_FLOATS + nl);
-      c.sh = *reinterpret_cast<const float4_*>(bias_lds + 2 * IG_VEC_FLOATS + nl);
+      c.sc = *reinterpret_cast<const ig_float4*>(bias_lds + IG_VEC_FLOATS + nl);
+      c.sh = *reinterpret_cast<const ig_float4*>(bias_lds + 2 * IG_VEC_FLOATS + nl);
     }
     return c;
   };
-  // accumulators of those 4 channels of one pixel -> the policy's roundings -> E tile (the generic body's put4 has the why)
+  // accumulators of those 4 channels of one pixel -> the policy's roundings (ig_round4) -> E tile
   auto put4 = [&](unsigned char* dst, float a0, float a1, float a2, float a3, const Vecs& c) {
-    half4 v;
-    if constexpr (ROUND_ACC) {
-      half2_ t01 = {(_Float16)a0, (_Float16)a1};
-      half2_ t23 = {(_Float16)a2, (_Float16)a3};
-      t01 = t01 + c.b01;
-      t23 = t23 + c.b23;
-      if constexpr (HAS_BN) {
-        v[0] = (_Float16)fmaf((float)t01[0], c.sc[0], c.sh[0]);
-        v[1] = (_Float16)fmaf((float)t01[1], c.sc[1], c.sh[1]);
-        v[2] = (_Float16)fmaf((float)t23[0], c.sc[2], c.sh[2]);
-        v[3] = (_Float16)fmaf((float)t23[1], c.sc[3], c.sh[3]);
-      } else {
-        v[0] = t01[0]; v[1] = t01[1]; v[2] = t23[0]; v[3] = t23[1];
-      }
-    } else {
-      v[0] = (_Float16)(a0 + c.bv[0]); v[1] = (_Float16)(a1 + c.bv[1]); v[2] = (_Float16)(a2 + c.bv[2]); v[3] = (_Float16)(a3 + c.bv[3]);
-    }
-    *reinterpret_cast<half4*>(dst) = v;
+    *reinterpret_cast<half4*>(dst) = ig_round4<ROUND_ACC, HAS_BN>(a0, a1, a2, a3, c.bv, c.b01, c.b23, c.sc, c.sh);
   };
   const int r15 = lane & 15;                       // == m & 15 of the lane's row in every pixel tile
   if constexpr (S16) {
@@ -251,18 +269,13 @@ __device__ __forceinline__ void ig_epilogue_spec(const IgEpiArgs& p, Acc& acc, u
   for (int it = 0; it < NIT; ++it) {
     half8 v = *reinterpret_cast<const half8*>(Erd + it * (RPI * ROWB));
     if constexpr (RES) v = v + rv[it];             // IEEE half add == the fp32 add of two halves rounded once
-    if constexpr (RELU) v = ig_relu8(v);
+    if constexpr (RELU) v = ig_relu(v);
     if constexpr (SLIM) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(uint4_, v), rsY, (int)(cbY + ((unsigned)rowY32[ml0 + it * RPI] << 1)), 0, 0);
     else *reinterpret_cast<half8*>(p.Y + rowY[ml0 + it * RPI] + ch * 8) = v;
-    if constexpr (PE) {                            // tokens + positional table, rounded for the in_proj GEMM
+    if constexpr (PE) {                            // tokens + positional table
       const int m = m0 + ml0 + it * RPI;
       const int mp = m - ig_fastdiv(m, p.pe_mul, p.pe_shr) * p.pe_period;   // m % pe_period
-      const float* per = p.pe + (size_t)mp * p.N + n0 + ch * 8;
-      const float4_ e0 = *reinterpret_cast<const float4_*>(per), e1 = *reinterpret_cast<const float4_*>(per + 4);
-      half8 w;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) { w[e] = (_Float16)((float)v[e] + e0[e]); w[4 + e] = (_Float16)((float)v[4 + e] + e1[e]); }
-      *reinterpret_cast<half8*>(p.Ype + (size_t)m * p.N + n0 + ch * 8) = w;
+      *reinterpret_cast<half8*>(p.Ype + (size_t)m * p.N + n0 + ch * 8) = ig_add_pe(v, p.pe + (size_t)mp * p.N + n0 + ch * 8);
       // one row at a time: batched over the 16 iterations, the table rows (8 registers each) on top of the residual rows take k_conv_sw past
       // the 224 registers it is held to (tests/test_conv_sw_resources_host.py); one launch per network and step has this body
       __builtin_amdgcn_sched_barrier(0);
@@ -282,7 +295,7 @@ __device__ __forceinline__ void ig_epilogue_spec(const IgEpiArgs& p, Acc& acc, u
 // pixel per lane (8 bytes), the 64 channels of a pixel in 16 consecutive lanes (one 128-byte line), and the SAME four channels for the whole
 // tile, so the per-channel vectors are read once.  No E tile and no barrier between conversion and store: a wave stores a pixel tile as
 // soon as it is converted, and the eight waves are free to drift apart.
-// The statements per element and their order are those of ig_epilogue_spec (put4, then + residual, then ReLU): the same bits given the same
+// Per element it calls what ig_epilogue_spec calls, in its order (ig_round4, then + residual, then ig_relu): the same bits given the same
 // accumulators.  rowY32: the output row table the kernel built in its prologue (element offsets from the buffer's start, channel n0
 // included; IG_ROW_NONE for a row past M).  The residual table goes over the operand stages (the caller's barrier retired their last read);
 // residual rows are requested one group of two pixel tiles ahead of their use.  FULL: every row of the tile exists.
@@ -293,10 +306,8 @@ __device__ __forceinline__ void ig_epilogue_direct(const IgEpiArgs& p, Acc& acc,
   static_assert(std::is_same<Acc, ig_float4[4][2 * TM]>::value, "accumulators of the 16x16x32 loop");
   static_assert((EPI & IG_EPI_CONV) == IG_EPI_CONV && !(EPI & IG_EPI_PE), "conv rounding + bias + ReLU, without the positional output");
   constexpr bool HAS_BN = (EPI & IG_EPI_BN) != 0, RES = (EPI & IG_EPI_RES) != 0;
-  typedef float float4_ __attribute__((ext_vector_type(4)));
   typedef int int4_ __attribute__((ext_vector_type(4)));
   typedef unsigned uint2_ __attribute__((ext_vector_type(2)));
-  typedef _Float16 half2_ __attribute__((ext_vector_type(2)));
   constexpr int JG = 2, NG = 2 * TM / JG;          // pixel tiles per residual group, groups
   const int nl = wn * 64 + 4 * (lane & 15);        // the lane's four channels, tile-local
   const int prow = wm * (32 * TM) + 4 * (lane >> 4);   // its four rows of pixel tile j: prow + 16 j + e
@@ -309,12 +320,12 @@ __device__ __forceinline__ void ig_epilogue_direct(const IgEpiArgs& p, Acc& acc,
     __syncthreads();
   }
   IG_CLK(te1);
-  const float4_ bv = *reinterpret_cast<const float4_*>(bias_lds + nl);
-  const half2_ b01 = {(_Float16)bv[0], (_Float16)bv[1]}, b23 = {(_Float16)bv[2], (_Float16)bv[3]};
-  float4_ sc, sh;
+  const ig_float4 bv = *reinterpret_cast<const ig_float4*>(bias_lds + nl);
+  const ig_half2 b01 = {(_Float16)bv[0], (_Float16)bv[1]}, b23 = {(_Float16)bv[2], (_Float16)bv[3]};
+  ig_float4 sc = {}, sh = {};                      // read by ig_round4 with BatchNorm only
   if constexpr (HAS_BN) {
-    sc = *reinterpret_cast<const float4_*>(bias_lds + IG_VEC_FLOATS + nl);
-    sh = *reinterpret_cast<const float4_*>(bias_lds + 2 * IG_VEC_FLOATS + nl);
+    sc = *reinterpret_cast<const ig_float4*>(bias_lds + IG_VEC_FLOATS + nl);
+    sh = *reinterpret_cast<const ig_float4*>(bias_lds + 2 * IG_VEC_FLOATS + nl);
   }
   const __amdgpu_buffer_rsrc_t rsY = __builtin_amdgcn_make_buffer_rsrc(ig_uniform_ptr(p.Y), 0, -1, 0x00020000);
   const __amdgpu_buffer_rsrc_t rsR = __builtin_amdgcn_make_buffer_rsrc(ig_uniform_ptr(p.R), 0, -1, 0x00020000);   // RES only
@@ -341,23 +352,9 @@ __device__ __forceinline__ void ig_epilogue_direct(const IgEpiArgs& p, Acc& acc,
       const int4_ yo = *reinterpret_cast<const int4_*>(rowY32 + prow + 16 * j);
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
-        // put4 of ig_epilogue_spec (ROUND_ACC), statement for statement
-        half4 v;
-        half2_ t01 = {(_Float16)acc[0][j][e], (_Float16)acc[1][j][e]};
-        half2_ t23 = {(_Float16)acc[2][j][e], (_Float16)acc[3][j][e]};
-        t01 = t01 + b01;
-        t23 = t23 + b23;
-        if constexpr (HAS_BN) {
-          v[0] = (_Float16)fmaf((float)t01[0], sc[0], sh[0]);
-          v[1] = (_Float16)fmaf((float)t01[1], sc[1], sh[1]);
-          v[2] = (_Float16)fmaf((float)t23[0], sc[2], sh[2]);
-          v[3] = (_Float16)fmaf((float)t23[1], sc[3], sh[3]);
-        } else {
-          v[0] = t01[0]; v[1] = t01[1]; v[2] = t23[0]; v[3] = t23[1];
-        }
-        // ... and of its store loop
+        half4 v = ig_round4<true, HAS_BN>(acc[0][j][e], acc[1][j][e], acc[2][j][e], acc[3][j][e], bv, b01, b23, sc, sh);
         if constexpr (RES) v = v + rv[g & 1][jj * 4 + e];   // IEEE half add == the fp32 add of two halves rounded once
-        v = ig_relu4(v);
+        v = ig_relu(v);
         if (FULL || yo[e] != IG_ROW_NONE)
           __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(uint2_, v), rsY, (int)((unsigned)(yo[e] + nl) << 1), 0, 0);
       }
@@ -372,16 +369,11 @@ __device__ __forceinline__ void ig_epilogue_direct(const IgEpiArgs& p, Acc& acc,
 #endif
 }
 
-// EPI: 0 = the generic body below, which reads the layer kind from IgemmParams at run time (any combination; the A/B arm of
-// FP_IGEMM_EPILOGUE_GENERIC); otherwise one of the IG_EPI_* layer kinds of ig_epilogue_spec, FULL tiles only.
-template <int BM, int BN, int TM, int THREADS, int DBG, bool FULL, bool SLIM, int EPI = 0, typename Acc, typename P>
-__device__ __forceinline__ void ig_epilogue_body(const P& p, Acc& acc, unsigned char* smem, int m0, int n0,
-                                                 int wm, int wn, int tid, int lane, const float* bias_lds) {
-  if constexpr (EPI != 0) {
-    static_assert(FULL && std::is_same<P, IgEpiArgs>::value, "the layer-kind bodies take whole tiles and their own argument block");
-    ig_epilogue_spec<BM, BN, TM, THREADS, SLIM, EPI>(p, acc, smem, m0, n0, wm, wn, tid, lane, bias_lds);
-  } else {   // the generic body, line for line as before the layer kinds (and left at its indentation)
-  static_assert(std::is_same<P, IgemmParams>::value, "the generic body reads IgemmParams");
+// ---- The generic body: reads the layer kind from IgemmParams at run time (any combination, partial tiles included; IgemmParams.epi == 0 and
+// the A/B arm of FP_IGEMM_EPILOGUE_GENERIC).  The same per-element helpers as the layer-kind bodies, selected by the run-time flags.
+template <int BM, int BN, int TM, int THREADS, bool FULL, bool SLIM, typename Acc>
+__device__ __forceinline__ void ig_epilogue_generic(const IgemmParams& p, Acc& acc, unsigned char* smem, int m0, int n0,
+                                                    int wm, int wn, int tid, int lane, const float* bias_lds) {
   constexpr bool S16 = std::is_same<Acc, ig_float4[4][2 * TM]>::value;
   static_assert(S16 || std::is_same<Acc, float16_[2][TM]>::value, "accumulator layout");
   constexpr int CPR = BN / 8;                      // 16-byte chunks per row of the epilogue tile
@@ -394,7 +386,6 @@ __device__ __forceinline__ void ig_epilogue_body(const P& p, Acc& acc, unsigned 
   unsigned char* E = smem;   // BM rows x (2*BN) B, low 4 bits of the chunk index XORed with (m & 15)
   // bias: staged into LDS at kernel entry (ig_bias_to_lds) -- a global load issued here would be exposed in full, and
   // under the operand stream's load that is several thousand cycles
-  typedef float float4_ __attribute__((ext_vector_type(4)));
   const bool round_acc = p.round_acc != 0, has_bn = p.bn_scale != nullptr;
   long long* rowY = reinterpret_cast<long long*>(smem + BM * 2 * BN);
   long long* rowR = SLIM ? reinterpret_cast<long long*>(smem) : rowY + BM;
@@ -431,40 +422,25 @@ __device__ __forceinline__ void ig_epilogue_body(const P& p, Acc& acc, unsigned 
   }
   IG_CLK(te2);
   // 4 consecutive channels nl .. nl + 3 (tile-local) of pixel row ml: accumulators -> the policy's roundings -> E tile
-  auto put4 = [&](int nl, int ml, float a0, float a1, float a2, float a3, const float4_& bv, const float4_& sc, const float4_& sh) {
+  auto put4 = [&](int nl, int ml, float a0, float a1, float a2, float a3, const ig_float4& bv, const ig_float4& sc, const ig_float4& sh) {
     half4 v;
     if (round_acc) {
-      // the reference's autocast op sequence for conv (+ BatchNorm): every op rounds its result to fp16.  Packed
-      // fp16 math where it is exact: v_cvt_pk_f16_f32 for the conv output, v_pk_add_f16 for the bias (an IEEE half
-      // add of two halves equals their fp32 sum rounded to half: when the fp32 sum is inexact the smaller addend is
-      // below 1/8 ulp of the larger), fp32 FMA for BatchNorm (fp32 statistics)
-      typedef _Float16 half2_ __attribute__((ext_vector_type(2)));
-      const half2_ b01 = {(_Float16)bv[0], (_Float16)bv[1]}, b23 = {(_Float16)bv[2], (_Float16)bv[3]};
-      half2_ t01 = {(_Float16)a0, (_Float16)a1};
-      half2_ t23 = {(_Float16)a2, (_Float16)a3};
-      t01 = t01 + b01;
-      t23 = t23 + b23;
-      if (has_bn) {
-        v[0] = (_Float16)fmaf((float)t01[0], sc[0], sh[0]);
-        v[1] = (_Float16)fmaf((float)t01[1], sc[1], sh[1]);
-        v[2] = (_Float16)fmaf((float)t23[0], sc[2], sh[2]);
-        v[3] = (_Float16)fmaf((float)t23[1], sc[3], sh[3]);
-      } else {
-        v[0] = t01[0]; v[1] = t01[1]; v[2] = t23[0]; v[3] = t23[1];
-      }
+      const ig_half2 b01 = {(_Float16)bv[0], (_Float16)bv[1]}, b23 = {(_Float16)bv[2], (_Float16)bv[3]};
+      if (has_bn) v = ig_round4<true, true>(a0, a1, a2, a3, bv, b01, b23, sc, sh);
+      else v = ig_round4<true, false>(a0, a1, a2, a3, bv, b01, b23, sc, sh);
     } else {
-      v[0] = (_Float16)(a0 + bv[0]); v[1] = (_Float16)(a1 + bv[1]); v[2] = (_Float16)(a2 + bv[2]); v[3] = (_Float16)(a3 + bv[3]);
+      v = ig_round4<false, false>(a0, a1, a2, a3, bv, ig_half2{}, ig_half2{}, sc, sh);
     }
     const int chunk = (nl >> 3) ^ (ml & 15);
     *reinterpret_cast<half4*>(E + ml * (2 * BN) + (chunk << 4) + ((nl & 4) << 1)) = v;
   };
   // per-channel vectors of 4 channels (LDS broadcast reads; kept out of registers until here)
-  auto vecs = [&](int nl, float4_& bv, float4_& sc, float4_& sh) {
-    bv = *reinterpret_cast<const float4_*>(bias_lds + nl);
-    sc = float4_{1.f, 1.f, 1.f, 1.f}; sh = float4_{0.f, 0.f, 0.f, 0.f};
+  auto vecs = [&](int nl, ig_float4& bv, ig_float4& sc, ig_float4& sh) {
+    bv = *reinterpret_cast<const ig_float4*>(bias_lds + nl);
+    sc = ig_float4{1.f, 1.f, 1.f, 1.f}; sh = ig_float4{0.f, 0.f, 0.f, 0.f};
     if (has_bn) {
-      sc = *reinterpret_cast<const float4_*>(bias_lds + IG_VEC_FLOATS + nl);
-      sh = *reinterpret_cast<const float4_*>(bias_lds + 2 * IG_VEC_FLOATS + nl);
+      sc = *reinterpret_cast<const ig_float4*>(bias_lds + IG_VEC_FLOATS + nl);
+      sh = *reinterpret_cast<const ig_float4*>(bias_lds + 2 * IG_VEC_FLOATS + nl);
     }
   };
   if constexpr (S16) {
@@ -474,7 +450,7 @@ __device__ __forceinline__ void ig_epilogue_body(const P& p, Acc& acc, unsigned 
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       const int nl = wn * 64 + i * 16 + 4 * quad;
-      float4_ bv, sc, sh;
+      ig_float4 bv, sc, sh;
       vecs(nl, bv, sc, sh);
 #pragma unroll
       for (int j = 0; j < 2 * TM; ++j) {
@@ -489,7 +465,7 @@ __device__ __forceinline__ void ig_epilogue_body(const P& p, Acc& acc, unsigned 
 #pragma unroll
       for (int g = 0; g < 4; ++g) {
         const int nl = wn * 64 + i * 32 + 8 * g + 4 * (lane >> 5);   // first of 4 consecutive channels (tile-local)
-        float4_ bv, sc, sh;
+        ig_float4 bv, sc, sh;
         vecs(nl, bv, sc, sh);
 #pragma unroll
         for (int j = 0; j < TM; ++j) {
@@ -512,14 +488,9 @@ __device__ __forceinline__ void ig_epilogue_body(const P& p, Acc& acc, unsigned 
     if (p.R) v = v + rv[it];                       // IEEE half add == the fp32 add of two halves rounded once
     if (p.relu) v = __builtin_elementwise_max(v, zero);
     *reinterpret_cast<half8*>(p.Y + yo + ch * 8) = v;
-    if (p.Ype) {                                   // tokens + positional table, rounded for the in_proj GEMM
+    if (p.Ype) {                                   // tokens + positional table
       const int m = m0 + ml;
-      const float* per = p.pe + (size_t)(m % p.pe_period) * p.N + n0 + ch * 8;
-      const float4_ e0 = *reinterpret_cast<const float4_*>(per), e1 = *reinterpret_cast<const float4_*>(per + 4);
-      half8 w;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) { w[e] = (_Float16)((float)v[e] + e0[e]); w[4 + e] = (_Float16)((float)v[4 + e] + e1[e]); }
-      *reinterpret_cast<half8*>(p.Ype + (size_t)m * p.N + n0 + ch * 8) = w;
+      *reinterpret_cast<half8*>(p.Ype + (size_t)m * p.N + n0 + ch * 8) = ig_add_pe(v, p.pe + (size_t)(m % p.pe_period) * p.N + n0 + ch * 8);
     }
   }
 #ifdef FP_PROFILE_BUILD
@@ -529,17 +500,18 @@ __device__ __forceinline__ void ig_epilogue_body(const P& p, Acc& acc, unsigned 
     atomicAdd(&ig_epi_dbg[3], te4 - te3); atomicAdd(&ig_epi_dbg[4], 1ull);
   }
 #endif
-  }
 }
 
+// A whole tile of one of the six layer kinds the library compiles a body for runs ig_epilogue_spec (DBG == 0: the timing-only builds of
+// k_igemm_pp keep to the generic body); everything else the generic body.
 template <int BM, int BN, int TM, int THREADS, int DBG = 0, bool SLIM = false, typename Acc>
 __device__ __forceinline__ void ig_epilogue(const IgemmParams& p, Acc& acc, unsigned char* smem, int m0, int n0,
                                             int wm, int wn, int tid, int lane, const float* bias_lds) {
   if (m0 + BM <= p.M) {
     if constexpr (DBG == 0) {
       // p.epi is a kernel argument: a scalar branch, the same for every wave of the launch (igemm.hip picks it: ig_epilogue_mode)
-#define IG_EPI_CASE(E) case E: ig_epilogue_body<BM, BN, TM, THREADS, DBG, true, SLIM, E>(q, acc, smem, m0, n0, wm, wn, tid, lane, bias_lds); return
-      const IgEpiArgs q = {p.out, p.res, p.R, p.Y, p.pe, p.Ype, p.pe_period, p.pe_mul, p.pe_shr, p.N};
+#define IG_EPI_CASE(E) case E: ig_epilogue_spec<BM, BN, TM, THREADS, SLIM, E>(q, acc, smem, m0, n0, wm, wn, tid, lane, bias_lds); return
+      const IgEpiArgs q = ig_epi_args(p);
       switch (p.epi) {
         IG_EPI_CASE(IG_EPI_CONV);
         IG_EPI_CASE(IG_EPI_CONV | IG_EPI_RES);
@@ -551,9 +523,9 @@ __device__ __forceinline__ void ig_epilogue(const IgemmParams& p, Acc& acc, unsi
       }
 #undef IG_EPI_CASE
     }
-    ig_epilogue_body<BM, BN, TM, THREADS, DBG, true, SLIM>(p, acc, smem, m0, n0, wm, wn, tid, lane, bias_lds);
+    ig_epilogue_generic<BM, BN, TM, THREADS, true, SLIM>(p, acc, smem, m0, n0, wm, wn, tid, lane, bias_lds);
   }
-  else ig_epilogue_body<BM, BN, TM, THREADS, DBG, false, SLIM>(p, acc, smem, m0, n0, wm, wn, tid, lane, bias_lds);
+  else ig_epilogue_generic<BM, BN, TM, THREADS, false, SLIM>(p, acc, smem, m0, n0, wm, wn, tid, lane, bias_lds);
 }
 // Kernel entry, BEFORE the first operand stage is requested: wave 0 sends the tile's bias straight to LDS with one
 // LDS-DMA (1 KiB = 256 floats; reads past the end of the bias vector return 0 through the buffer descriptor's bound).

@@ -51,12 +51,8 @@ __global__ __launch_bounds__(512, 1) void k_igemm_pp(IgemmParams p) {
   const int wm = wid / NWN, wn = wid - wm * NWN;
   float* bias_lds = reinterpret_cast<float*>(smem + LDS_MAIN);
 
-  // XCD-aware tile order (as igemm.hip)
   const int tiles_n = p.N / BN;
-  const int nwg = gridDim.x;
-  const int xcd = blockIdx.x & 7, loc = blockIdx.x >> 3;
-  const int q = nwg >> 3, r8 = nwg & 7;
-  const int tile = (xcd < r8 ? xcd * (q + 1) : r8 * (q + 1) + (xcd - r8) * q) + loc;
+  const int tile = ig_xcd_tile(blockIdx.x, gridDim.x);
   const int bm = tile / tiles_n, bn = tile - bm * tiles_n;
   const int m0 = bm * BM, n0 = bn * BN;
   const int Ktot = p.taps * p.Cin;
@@ -202,13 +198,7 @@ __global__ __launch_bounds__(512, 1) void k_igemm_pp(IgemmParams p) {
 template <int BM, int BN, int TM, int DBG>
 static int ig_pp_launch(const IgemmParams& p, hipStream_t stream) {
   constexpr int LDS = ig_lds_main<BM, BN>(4 * (BM + BN) * 32 * 2) + IG_BIAS_LDS;
-  static_assert(LDS <= 160 * 1024, "tile does not fit the 160 KiB LDS");
-  const long long tiles = (long long)fp_cdiv(p.M, BM) * (p.N / BN);
-  FP_REQUIRE(tiles < (1ll << 31), "fp_igemm_f16_fwd: too many tiles");
-  FP_SET_MAX_LDS((k_igemm_pp<BM, BN, TM, DBG>), LDS);
-  hipLaunchKernelGGL((k_igemm_pp<BM, BN, TM, DBG>), dim3((unsigned)tiles), dim3(512), LDS, stream, p);
-  FP_CHECK_LAUNCH("fp_igemm_f16_fwd");
-  return FP_OK;
+  return ig_launch_tiles<k_igemm_pp<BM, BN, TM, DBG>, BM, BN, 512, LDS>(p, stream, "fp_igemm_f16_fwd");
 }
 
 

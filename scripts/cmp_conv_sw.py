@@ -1,6 +1,6 @@
 """sha1 of the outputs of the stride-1 3x3 convs at several shapes (full / partial last tile, residual, BatchNorm, token
 layout + positional output): run once per build / mode and compare the lines (profiling aid:
-FP_AMD_LIB=.../libfp_amd_profile.so FP_CONV_SW=classic python scripts/cmp_conv_sw.py)"""
+FP_AMD_LIB=.../libfp_amd_<name>.so python scripts/cmp_conv_sw.py, FP_W_TILES=1 for the tile-packed weights)"""
 import hashlib, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch

@@ -37,9 +37,8 @@ except Exception as e:
     print("   ", sys.argv[2], "FAILED", e)
 PY
 }
-t_ab() {      # same box, back to back: product, lock-step two-per-CU conv (make ab), 3 sub-batch streams; product again
+t_ab() {      # same box, back to back: product, 3 sub-batch streams; product again
   bench_line product $PWD/$CS/libfp_amd.so
-  [ -f $CS/libfp_amd_alt.so ] && bench_line conv_sw_ls $PWD/$CS/libfp_amd_alt.so
   bench_line streams3 $PWD/$CS/libfp_amd.so --streams 3
   bench_line product_again $PWD/$CS/libfp_amd.so
 }

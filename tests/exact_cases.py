@@ -414,6 +414,10 @@ SPLITK_CASES = {
     "splitk s2 20x20 256->512": (Conv("splitk s2 20x20 256->512", 1, 20, 20, 256, 512, stride=2, seed=55), False, True, (35, 1, 36)),
     "splitk 8x8 128->128": (Conv("splitk 8x8 128->128", 1, 8, 8, 128, 128, seed=56), True, True, (5, 17, 1, 18)),
 }
+# ... and the smallest of them (its seed: the same operands) as the token layer -- output without border + the positional second output --
+# which the engine runs split for small calls: launched with every one of LAYER_KINDS, so k_splitk_epilogue's arithmetic is pinned for
+# conv rounding with and without BatchNorm, residual, bias and ReLU, each with the positional add behind it.  (case, piece counts)
+SPLITK_KINDS_CASE = (Conv("splitk 8x8 128->128 tokens", 1, 8, 8, 128, 128, seed=56, pe_period=64), (5, 17, 1, 18))
 SPLITK_LINEAR_CASES = {"splitk linear 400x512x512": (Linear(400, 512, 512, seed=57), (3, 7, 1, 8)),
                        "splitk linear 37x64x128": (Linear(37, 64, 128, seed=58), (1,))}
 

@@ -21,7 +21,7 @@ from amp_util import conv_amp_ref, r16
 MIN_CHANGED = 0.01
 # (bias, BatchNorm, residual, ReLU) as the GPU file launches them: the four layer kinds, then a bias-less and a ReLU-less one
 KINDS = ec.LAYER_KINDS
-ALL_CONV = {**ec.CONV_CASES, **{n: v[0] for n, v in ec.SPLITK_CASES.items()}}
+ALL_CONV = {**ec.CONV_CASES, **{n: v[0] for n, v in ec.SPLITK_CASES.items()}, ec.SPLITK_KINDS_CASE[0].name: ec.SPLITK_KINDS_CASE[0]}
 ALL_LINEAR = {c.name + f" seed {c.seed}": c for c in ec.LINEAR_CASES + ec.LINEAR512_CASES + [v[0] for v in ec.SPLITK_LINEAR_CASES.values()]}
 
 
@@ -153,6 +153,16 @@ def test_a_splitk_piece_one_step_short_changes_at_least_one_per_cent(name):
         assert f >= MIN_CHANGED, (name, splits, f)
         whole = ec.conv_acc(c, op["ix"], op["iw"], keep=ec.conv_keep_steps(c, range(nk)))
         assert np.array_equal(whole, case["A"])
+
+
+def test_the_splitk_token_case_has_an_exact_positional_output_for_every_layer_kind():
+    """pe_output asserts that the float32 add equals the float64 one; the second output differs from the first, so it is checked at all"""
+    c, counts = ec.SPLITK_KINDS_CASE
+    case = ec.conv_case(c)
+    assert c.M == 64 and c.pe_period == c.M and all(1 <= s <= 9 * c.Cin // 64 for s in counts)
+    for flags in KINDS:
+        ref = ec.conv_epilogue(case["A"], case["op"], *flags).reshape(c.M, c.Cout)
+        assert _changed(ec.pe_output(ref, case["op"]["pe"]), ref) >= 0.5, flags
 
 
 @pytest.mark.parametrize("name", list(ALL_LINEAR))

@@ -328,6 +328,25 @@ def test_splitk_conv_with_uneven_pieces(dev, name):
             assert torch.equal(yf.view(torch.int16), unsplit.view(torch.int16)), f"{name} x{splits}: not the bits of the unsplit call"
 
 
+@pytest.mark.parametrize("flags", ec.LAYER_KINDS, ids=lambda f: "bias%d-bn%d-res%d-relu%d" % f)
+def test_splitk_token_layer_of_every_layer_kind(dev, flags):
+    """k_splitk_epilogue with conv rounding: the 64-pixel token layer (output without border + the positional second output), split as
+    the engine splits it for small calls, with each layer kind -- BatchNorm and residual on and off, a bias-less and a ReLU-less layer.
+    Both outputs are the reference; the first is the bits of the unsplit call"""
+    c, counts = ec.SPLITK_KINDS_CASE
+    case = ec.conv_case(c)
+    run = _ConvRun(dev, c, case, layout="tokens")
+    kind = f"(bias, BatchNorm, residual, ReLU) = {flags}"
+    rec = _conv_record(c, case, entry=f"fp_igemm_f16_splitk_fwd taps=9, {kind}")
+    unsplit = run.launch(_conv_record(c, case, entry=f"fp_igemm_f16_fwd taps=9, {kind}, the unsplit call of"), flags, _conv_path(c))
+    nk = 9 * c.Cin // 64
+    for splits in counts:
+        assert 1 <= splits <= nk
+        for fill in (0x7f, 0xff):
+            yf = run.launch(rec, flags, f"split-K 128x128, {splits} of {nk} k-steps", splits=splits, fill=fill)
+            assert torch.equal(yf.view(torch.int16), unsplit.view(torch.int16)), f"{c.name} {flags} x{splits}: not the bits of the unsplit call"
+
+
 # ------------------------------------------------------------------ (b), (c), (e): Linear
 def _matrix(ld, coff=0):
     from foundationpose_amd import ops
