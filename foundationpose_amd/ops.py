@@ -793,6 +793,130 @@ class PoseErrors(NamedTuple):
         return [cls(*(float(x) for x in r)) for r in np.asarray(a, dtype=np.float64).reshape(-1, 4)]
 
 
+MESH_DISTANCE_OUTPUTS = ("dist2", "face", "closest")
+_MESH_DISTANCE_DTYPES = {"dist2": torch.float32, "face": torch.int32, "closest": torch.float32}
+
+
+def mesh_point_distance(points, mesh_tensors=None, pos=None, faces=None, want=MESH_DISTANCE_OUTPUTS, out=None):
+    """fp_mesh_point_distance: the exact distance from the points (Q,3) f32 to the surface of a triangle mesh -> dict of device tensors:
+    `dist2` (Q,) f32 the squared distance to the nearest point of any triangle, `face` (Q,) int32 that triangle, `closest` (Q,3) f32
+    that point (include/fp_amd.h has the definition: Ericson's region walk in float32, the smallest (dist2, face) wins; +inf / -1 /
+    zeros for a query that no triangle answers).  The mesh is mesh_tensors (a dict with pos (Nv,3) f32 and faces (F,3) int32, as
+    make_mesh_tensors and TsdfVolume.extract give) or pos= and faces= themselves.  want: names out of "dist2", "face", "closest";
+    dist2 is always computed and returned.  out: a dict of caller-owned buffers for some of the wanted names.  Brute force: Q x F pair
+    tests.  The workspace (8 bytes a query) is the library's per-stream scratch, or a fresh allocation inside a stream capture.
+    Wrong shapes are refused first, then tensors that are not on the device, of another dtype or not contiguous, then buffers that
+    overlap an input or each other (FpAmdError)."""
+    what = "mesh_point_distance"
+    names = (want,) if isinstance(want, str) else tuple(want)
+    for w in names:
+        if w not in MESH_DISTANCE_OUTPUTS:
+            raise ValueError(f"{what}: unknown name {w!r} in want (known: {list(MESH_DISTANCE_OUTPUTS)})")
+    if not names:
+        raise ValueError(f"{what}: want is empty")
+    names = tuple(n for n in MESH_DISTANCE_OUTPUTS if n in names or n == "dist2")
+    if mesh_tensors is not None:
+        if pos is not None or faces is not None:
+            raise _lib.FpAmdError(f"{what}: pass mesh_tensors or pos / faces, not both")
+        for k in ("pos", "faces"):
+            if k not in mesh_tensors:
+                raise _lib.FpAmdError(f"{what}: mesh_tensors has no '{k}'")
+        pos, faces = mesh_tensors["pos"], mesh_tensors["faces"]
+    if pos is None or faces is None:
+        raise _lib.FpAmdError(f"{what}: no mesh (pass mesh_tensors, or pos and faces)")
+    for name, t in (("points", points), ("pos", pos), ("faces", faces)):
+        if not torch.is_tensor(t):
+            raise _lib.FpAmdError(f"{what}: {name} must be a tensor, got {type(t).__name__}")
+        if t.dim() != 2 or int(t.shape[1]) != 3:
+            raise _lib.FpAmdError(f"{what}: {name} must be (n,3), got {tuple(t.shape)}")
+    Q, Nv, F = int(points.shape[0]), int(pos.shape[0]), int(faces.shape[0])
+    if max(Q, F) > (1 << 30):
+        raise _lib.FpAmdError(f"{what}: {Q} points against {F} faces (at most 2^30 of either)")
+    out = dict(out or {})
+    shapes = {"dist2": (Q,), "face": (Q,), "closest": (Q, 3)}
+    for k, t in out.items():
+        if k not in names:
+            raise _lib.FpAmdError(f"{what}: out has '{k}', which is not among the wanted outputs {list(names)}")
+        if not torch.is_tensor(t) or tuple(t.shape) != shapes[k]:
+            raise _lib.FpAmdError(f"{what}: out['{k}'] must be a tensor of shape {shapes[k]}, got "
+                                  f"{tuple(t.shape) if torch.is_tensor(t) else type(t).__name__}")
+    pts = _dev(points, torch.float32, "points")
+    vp_ = _dev(pos, torch.float32, "pos")
+    fc = _dev(faces, torch.int32, "faces")
+    for k in list(out):
+        out[k] = _dev(out[k], _MESH_DISTANCE_DTYPES[k], f"out['{k}']")
+    for k, t in out.items():
+        for name, src in (("points", pts), ("pos", vp_), ("faces", fc)):
+            if _overlap(t, src):
+                raise _lib.FpAmdError(f"{what}: out['{k}'] overlaps {name}")
+        for k2, t2 in out.items():
+            if k2 < k and _overlap(t, t2):
+                raise _lib.FpAmdError(f"{what}: out['{k}'] overlaps out['{k2}']")
+    for k in names:
+        if k not in out:
+            out[k] = torch.empty(shapes[k], dtype=_MESH_DISTANCE_DTYPES[k], device=pts.device)
+    need = int(_lib.lib().fp_mesh_point_distance_workspace_bytes(Q))
+    ws = _workspace(need, pts.device)
+    _lib.check(_lib.lib().fp_mesh_point_distance(_ptr(vp_), Nv, _ptr(fc), F, _ptr(pts), Q, _ptr(out["dist2"]), _ptr(out.get("face")),
+                                                 _ptr(out.get("closest")), _ptr(ws), need, _stream(pts)), "fp_mesh_point_distance")
+    return {k: out[k] for k in names}
+
+
+class DistanceStats(NamedTuple):
+    """the distances of one mesh's surface samples to another mesh's surface, in the meshes' unit"""
+    mean: float
+    median: float
+    p99: float
+    max: float
+
+    @classmethod
+    def of(cls, d):
+        d = np.asarray(d, dtype=np.float64).reshape(-1)
+        if d.size == 0:
+            return cls(*(float("nan"),) * 4)
+        if not np.isfinite(d).all():                 # a sample that no triangle answered: no interpolation between +inf and +inf
+            return cls(float(np.mean(d)), float(np.median(d)), float(np.percentile(d, 99, method="higher")), float(np.max(d)))
+        return cls(float(np.mean(d)), float(np.median(d)), float(np.percentile(d, 99)), float(np.max(d)))
+
+
+class MeshComparison(NamedTuple):
+    """reconstruct.compare_meshes(a, b): how a mesh that was built (a) compares with its reference (b), from surface samples of both.
+    `accuracy`: the distances of a's samples to b's surface; `completeness`: those of b's samples to a's surface (DistanceStats);
+    `chamfer` the mean of the two means; `hausdorff` the larger of the two maxima (of the samples, so a lower bound of the surfaces');
+    per threshold: `precision` the fraction of a's samples within it of b, `recall` that of b's samples within it of a, `fscore`
+    their harmonic mean (0 when both are 0).  dist_a_to_b / dist_b_to_a: the two distance arrays where they were computed (device
+    tensors from compare_meshes)."""
+    accuracy: DistanceStats
+    completeness: DistanceStats
+    chamfer: float
+    hausdorff: float
+    thresholds: tuple
+    precision: tuple
+    recall: tuple
+    fscore: tuple
+    dist_a_to_b: object
+    dist_b_to_a: object
+
+    @classmethod
+    def from_distances(cls, d_ab, d_ba, thresholds):
+        """the report of two distance arrays (numpy, or device tensors: one device-to-host copy each); float64 on the host"""
+        host = lambda d: (d.detach().cpu().numpy() if torch.is_tensor(d) else np.asarray(d)).astype(np.float64).reshape(-1)   # noqa: E731
+        ha, hb = host(d_ab), host(d_ba)
+        thr = tuple(float(t) for t in thresholds)
+        acc, comp = DistanceStats.of(ha), DistanceStats.of(hb)
+        prec = tuple(float(np.mean(ha <= t)) if ha.size else float("nan") for t in thr)
+        rec = tuple(float(np.mean(hb <= t)) if hb.size else float("nan") for t in thr)
+        fs = tuple((2.0 * p * r / (p + r)) if p + r > 0 else 0.0 for p, r in zip(prec, rec))
+        return cls(acc, comp, 0.5 * (acc.mean + comp.mean), max(acc.max, comp.max), thr, prec, rec, fs, d_ab, d_ba)
+
+    def as_dict(self):
+        """what json.dumps takes: everything but the distance arrays"""
+        return dict(accuracy=self.accuracy._asdict(), completeness=self.completeness._asdict(), chamfer=self.chamfer,
+                    hausdorff=self.hausdorff, thresholds=list(self.thresholds), precision=list(self.precision),
+                    recall=list(self.recall), fscore=list(self.fscore), samples=[int(np.prod(tuple(self.dist_a_to_b.shape))),
+                                                                                 int(np.prod(tuple(self.dist_b_to_a.shape)))])
+
+
 BOP_TAUS = tuple(0.05 * k for k in range(1, 11))       # BOP's misalignment tolerances of VSD, in units of the object's diameter
 VSD_MAX_T = 16                                         # FP_VSD_MAX_T (include/fp_amd.h)
 _VSD_FAC = {}                                          # (K bytes, H, W, device) -> the depth-to-distance factor on the device
@@ -1939,6 +2063,7 @@ replicate_segments = _timed("fp_replicate_segments_f16", replicate_segments,
 mask_depth_stats = _timed("fp_mask_depth_stats", mask_depth_stats)
 depth_agreement = _timed("fp_depth_agreement", depth_agreement)
 pose_errors = _timed("fp_pose_errors", pose_errors)
+mesh_point_distance = _timed("fp_mesh_point_distance", mesh_point_distance)
 icp_point_plane = _timed("fp_icp_point_plane", icp_point_plane)
 tsdf_components = _timed("fp_tsdf_label_components", tsdf_components)
 vsd_counts = _timed("fp_vsd_counts", vsd_counts)

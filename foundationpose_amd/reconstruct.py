@@ -397,8 +397,8 @@ def reconstruct_object(rgbs, depths, masks, ob_in_cams, Ks, voxel=None, trunc=No
     "mesh" (the default) is the path described above.  keep_components ('largest', or the fewest triangles of a surface component
     that stays; None keeps all) drops floaters at every extraction of the call, those of the refine_poses rounds included
     (TsdfVolume.extract's keep): the mesh then carries components and dropped_triangles.  The volume is left as fused, so the
-    rounds of refine_against="volume" still see a floater.  ValueError, naming the cause, when there are no views, the
-    masks are empty or no surface was found."""
+    rounds of refine_against="volume" still see a floater.  The mesh carries the pitch it was fused at as mesh.voxel.
+    ValueError, naming the cause, when there are no views, the masks are empty or no surface was found."""
     what = "reconstruct_object"
     n = len(depths) if depths is not None else 0
     if n == 0:
@@ -452,4 +452,123 @@ def reconstruct_object(rgbs, depths, masks, ob_in_cams, Ks, voxel=None, trunc=No
         mesh.components, mesh.dropped_triangles = report
     if int(refine_poses) > 0:
         mesh.ob_in_cams = P.cpu().numpy()
+    mesh.voxel = voxel                                # the pitch it was fused at: the unit of compare_meshes' default thresholds
     return mesh, tensors
+
+
+# ------------------------------------------------------------------ how good is a mesh: surface samples and their exact distances
+_R2 = (0.7548776662466927, 0.5698402909980532)      # 1/g, 1/g^2 with g the plastic number: the R2 low-discrepancy sequence
+SEED_STRIDE = 7919                                  # seed s shifts the sequence's index by s * SEED_STRIDE
+DEFAULT_THRESHOLD_UNITS = (0.5, 1.0, 2.0, 4.0)      # compare_meshes' thresholds, in multiples of unit=
+
+
+def _surface_strata(pos, faces, n, seed):
+    """what sample_surface and its numpy stand-in share, float64 on the host (one order of summation): the cumulative face areas
+    (F,), the n area coordinates (i + 0.5) / n * total, and the (n,3) float32 barycentric weights of the points.  pos (Nv,3), faces
+    (F,3) host arrays.  A face whose area is not finite, or with an index outside the table, counts as 0."""
+    pos = np.asarray(pos, dtype=np.float64).reshape(-1, 3)
+    faces = np.asarray(faces, dtype=np.int64).reshape(-1, 3)
+    ok = ((faces >= 0) & (faces < len(pos))).all(axis=1)
+    fz = np.where(ok[:, None], faces, 0)
+    with np.errstate(all="ignore"):
+        a, b, c = (pos[fz[:, k]] for k in range(3)) if len(pos) else (np.zeros((len(faces), 3)),) * 3
+        area = 0.5 * np.sqrt((np.cross(b - a, c - a) ** 2).sum(axis=1))
+    area = np.where(ok & np.isfinite(area), area, 0.0)
+    cum = np.cumsum(area)
+    total = float(cum[-1]) if len(cum) else 0.0
+    if not total > 0.0:
+        raise ValueError("sample_surface: the mesh has no area (no face, or only degenerate ones)")
+    i = np.arange(n, dtype=np.float64)
+    target = (i + 0.5) / n * total
+    k = i + 1.0 + float(int(seed)) * SEED_STRIDE
+    r1, r2 = np.modf(0.5 + k * _R2[0])[0], np.modf(0.5 + k * _R2[1])[0]
+    su = np.sqrt(r1)                                 # uniform over the triangle: (1 - sqrt r1, sqrt r1 (1 - r2), sqrt r1 r2)
+    w = np.stack([1.0 - su, su * (1.0 - r2), su * r2], axis=1).astype(np.float32)
+    return cum, target, w
+
+
+def _mesh_arrays(m, device, what, name):
+    """a mesh-tensor dict (pos, faces on a device) or a SimpleMesh -> (pos (Nv,3) float32, faces (F,3) int32) device tensors"""
+    if isinstance(m, dict):
+        for k in ("pos", "faces"):
+            if k not in m:
+                raise ValueError(f"{what}: {name} has no '{k}'")
+        pos, faces = m["pos"], m["faces"]
+        if not (torch.is_tensor(pos) and torch.is_tensor(faces)):
+            raise ValueError(f"{what}: {name}'s pos and faces must be tensors")
+    elif hasattr(m, "vertices") and hasattr(m, "faces"):
+        pos, faces = torch.as_tensor(np.asarray(m.vertices, dtype=np.float32)), torch.as_tensor(np.asarray(m.faces).astype(np.int32))
+    else:
+        raise ValueError(f"{what}: {name} must be a mesh-tensor dict or a mesh with vertices and faces, got {type(m).__name__}")
+    if pos.dim() != 2 or int(pos.shape[1]) != 3 or faces.dim() != 2 or int(faces.shape[1]) != 3:
+        raise ValueError(f"{what}: {name} needs pos (Nv,3) and faces (F,3), got {tuple(pos.shape)} and {tuple(faces.shape)}")
+    if device is None:
+        device = pos.device
+    return pos.to(device=device, dtype=torch.float32).contiguous(), faces.to(device=device, dtype=torch.int32).contiguous()
+
+
+def _check_count(n, what, name):
+    if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or int(n) < 1:
+        raise ValueError(f"{what}: {name} must be an int >= 1, got {n!r}")
+    return int(n)
+
+
+def sample_surface(mesh_tensors, n, seed=0):
+    """n points on the surface of a mesh, area-weighted and reproducible -> (points (n,3) float32, face (n,) int64: the face of each),
+    on the device of the mesh.  mesh_tensors: a dict with pos (Nv,3) f32 and faces (F,3) int32 on a device, or a SimpleMesh (then on
+    the current device).  Stratified: point i sits at the area coordinate (i + 0.5) / n of the float64 cumulative face areas, found by
+    searchsorted, so face f gets n * area_f / total points to within one; inside its face the point has the barycentrics of the
+    R2 low-discrepancy pair at index i + 1 + seed * SEED_STRIDE, folded onto the triangle.  The area table and the weights are
+    made on the host in float64 (the one summation order the definition has; a setup call: it reads the mesh back once); the search,
+    the gather and the float32 combination (a*w0 + b*w1) + c*w2 run on the device in plain torch."""
+    what = "sample_surface"
+    n = _check_count(n, what, "n")
+    if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or int(seed) < 0:
+        raise ValueError(f"{what}: seed must be an int >= 0, got {seed!r}")
+    pos, faces = _mesh_arrays(mesh_tensors, None if isinstance(mesh_tensors, dict) else "cuda", what, "mesh_tensors")
+    cum, target, w = _surface_strata(pos.cpu().numpy(), faces.cpu().numpy(), n, seed)
+    dev = pos.device
+    f = torch.searchsorted(torch.as_tensor(cum, device=dev), torch.as_tensor(target, device=dev), right=True)
+    f = f.clamp_(max=int(faces.shape[0]) - 1)
+    idx = faces[f].long()
+    w = torch.as_tensor(w, device=dev)
+    a, b, c = pos[idx[:, 0]], pos[idx[:, 1]], pos[idx[:, 2]]
+    return ((a * w[:, 0:1] + b * w[:, 1:2]) + c * w[:, 2:3]).contiguous(), f
+
+
+def _thresholds(thresholds, unit, what):
+    if thresholds is None:
+        if unit is None:
+            raise ValueError(f"{what}: pass unit= (a length, for example the voxel pitch: the thresholds are "
+                             f"{DEFAULT_THRESHOLD_UNITS} times it) or thresholds=")
+        unit = float(unit)
+        if not (np.isfinite(unit) and unit > 0):
+            raise ValueError(f"{what}: unit must be a positive length, got {unit!r}")
+        return tuple(m * unit for m in DEFAULT_THRESHOLD_UNITS)
+    thr = tuple(float(t) for t in np.asarray(thresholds, dtype=np.float64).reshape(-1))
+    if not thr or not all(np.isfinite(t) and t >= 0 for t in thr):
+        raise ValueError(f"{what}: thresholds must be finite lengths >= 0, got {thresholds!r}")
+    return thr
+
+
+def compare_meshes(a, b, samples=100_000, thresholds=None, seed=0, unit=None, device=None):
+    """How good is mesh a (what was built) against mesh b (the reference) -> ops.MeshComparison: accuracy (the exact distances of
+    `samples` surface samples of a to the surface of b: mean / median / p99 / max), completeness (b's samples to a's surface), the
+    chamfer distance (the mean of the two means), the Hausdorff distance of the samples, and per threshold precision, recall and
+    F-score; the two distance arrays stay on the device.  a, b: mesh-tensor dicts (pos, faces) or SimpleMeshes, in one frame and one
+    unit.  thresholds: lengths; None: DEFAULT_THRESHOLD_UNITS times unit= (for example the voxel pitch of the fusion).  The samples
+    are sample_surface's (seed), the distances ops.mesh_point_distance's: brute force, samples x faces pair tests in each direction.
+    A setup / evaluation call, and it synchronises: sample_surface reads each mesh back once for its float64 area table, and the two
+    distance arrays are read once at the end for the statistics (float64 on the host)."""
+    what = "compare_meshes"
+    samples = _check_count(samples, what, "samples")
+    thr = _thresholds(thresholds, unit, what)
+    if device is None:
+        device = next((m["pos"].device for m in (a, b) if isinstance(m, dict) and torch.is_tensor(m.get("pos"))), "cuda")
+    ta, tb = (dict(zip(("pos", "faces"), _mesh_arrays(m, device, what, name))) for m, name in ((a, "a"), (b, "b")))
+    pa, _ = sample_surface(ta, samples, seed)
+    pb, _ = sample_surface(tb, samples, seed)
+    # the square root through float64: the correctly rounded float32 root whatever the device's float32 sqrt does in its last bit
+    d_ab = ops.mesh_point_distance(pa, tb, want=("dist2",))["dist2"].double().sqrt_().float()
+    d_ba = ops.mesh_point_distance(pb, ta, want=("dist2",))["dist2"].double().sqrt_().float()
+    return ops.MeshComparison.from_distances(d_ab, d_ba, thr)

@@ -96,8 +96,10 @@ const char* fp_last_error(void);
  *               as K or as Ks / view / V and the object as mesh_diameter or as diameters / obj / M (render: mesh or set) in one argument
  *               list.  REMOVED: fp_crop_windows_multi, fp_crop_windows_views, fp_render_crops_multi, fp_render_crops_views,
  *               fp_warp_crops_multi, fp_warp_crops_views, fp_pose_update_multi, fp_pose_update_views.  A caller of the four base names
- *               built against an older header passes the wrong arguments: gate on fp_version(). */
-#define FP_AMD_ABI_VERSION 230
+ *               built against an older header passes the wrong arguments: gate on fp_version().
+ *   230 -> 231: + fp_mesh_point_distance, fp_mesh_point_distance_workspace_bytes (additions only): the exact distance from points to
+ *               the surface of a triangle mesh, with the nearest face and the closest point. */
+#define FP_AMD_ABI_VERSION 231
 int fp_version(void);
 
 /* Utils.py:104-130 make_mesh_tensors: records caller-owned device tensors.
@@ -278,6 +280,49 @@ int fp_vsd_counts(const float* est /*dev N,h,w*/, const float* gt /*dev G,h,w*/,
 int fp_mspd(const float* model_pts /*dev P,3*/, int P, const double* sym_tfs /*dev S,16|NULL*/, int S, const float* poses /*dev N,16*/,
             const double* gt /*dev G,16*/, const int32_t* gt_index /*dev N|NULL*/, int G, int N, const float* K /*host 9*/,
             double* out /*dev N*/, void* stream);
+
+/* The exact distance from Q points to the surface of a triangle mesh: per query point the squared distance to the nearest point of any
+ * triangle, that triangle's index and that point.  Brute force over every (query, triangle) pair is the definition and the
+ * implementation.  Every operation below is one float32 operation (IEEE, round to nearest even), without contraction, in the order
+ * written; x - y, x * y and x / y on 3-vectors are per component;  dot(x, y) = (x0*y0 + x1*y1) + x2*y2.
+ * Candidate of query p for triangle f with vertices a = pos[faces[f][0]], b = pos[faces[f][1]], c = pos[faces[f][2]]: the closest
+ * point q of the closed triangle by the region walk of Ericson, Real-Time Collision Detection, 5.1.5.  The first test that holds
+ * gives q (a comparison with a NaN does not hold):
+ *   ab = b - a;  ac = c - a;  ap = p - a;  d1 = dot(ab, ap);  d2 = dot(ac, ap);
+ *     1. d1 <= 0 && d2 <= 0:                            q = a                                         (vertex a)
+ *   bp = p - b;  d3 = dot(ab, bp);  d4 = dot(ac, bp);
+ *     2. d3 >= 0 && d4 <= d3:                           q = b                                         (vertex b)
+ *   vc = d1*d4 - d3*d2;
+ *     3. vc <= 0 && d1 >= 0 && d3 <= 0:                 v = d1 / (d1 - d3);  q = a + v * ab           (edge ab)
+ *   cp = p - c;  d5 = dot(ab, cp);  d6 = dot(ac, cp);
+ *     4. d6 >= 0 && d5 <= d6:                           q = c                                         (vertex c)
+ *   vb = d5*d2 - d1*d6;
+ *     5. vb <= 0 && d2 >= 0 && d6 <= 0:                 w = d2 / (d2 - d6);  q = a + w * ac           (edge ac)
+ *   va = d3*d6 - d5*d4;  e = d4 - d3;  g = d5 - d6;
+ *     6. va <= 0 && e >= 0 && g >= 0:                   w = e / (e + g);  q = b + w * (c - b)         (edge bc)
+ *     7. otherwise:  denom = 1 / ((va + vb) + vc);  v = vb * denom;  w = vc * denom;  q = (a + v * ab) + w * ac    (interior)
+ *   dd = dot(p - q, p - q).
+ * The candidate counts only when dd <= FLT_MAX.  A triangle one of whose vertex indices is outside 0..Nv-1 has NaN vertices (nothing
+ * of pos is read for it), so it never counts; neither does one with a non-finite vertex that reaches dd, nor a degenerate one whose
+ * quotient is 0/0 (a degenerate triangle that an earlier vertex test answers does count: the walk is followed as written).
+ * The answer for p is the candidate with the smallest (dd, f) in lexicographic order: equal distances go to the smaller face index.
+ *   dist2[i] = dd,  face[i] = f,  closest[i] = q.   A query that no triangle answers (a NaN query, F == 0, every triangle skipped):
+ *   dist2[i] = +inf,  face[i] = -1,  closest[i] = (0, 0, 0).
+ * A minimum has no summation order, so each output has one value whatever the schedule: a query has the same bits alone, in a batch
+ * and on every replay.  face and closest may be NULL (not wanted).  One query per lane; the triangles pass through LDS in tiles and the
+ * grid runs over (256 queries) x (a chunk of faces), the partial minima merged with 64-bit integer atomic minima on the key
+ * (bits(dd) << 32) | f in the workspace -- non-negative floats order as their bits do; there are no floating-point atomics.  An init
+ * launch sets the keys, and a finish launch recomputes q for the winning face with the same arithmetic and writes the outputs.  Q * F pair
+ * tests of about 80 float32 operations each: the cost is the caller's to weigh (there is no grid or tree).  Q == 0 does nothing.
+ * No allocation, no host synchronisation (graph-capturable); nothing is written outside the outputs and the workspace
+ * (fp_mesh_point_distance_workspace_bytes(Q) bytes = 8 * Q, 8-byte aligned; 0 for Q <= 0).  Argument errors (FP_ERR_INVALID_ARG),
+ * before any launch: Q, F or Nv negative, Q or F above 2^30; NULL points / dist2 with Q > 0; NULL faces with F > 0 (and Q > 0); NULL pos
+ * with Nv > 0 and F > 0 (and Q > 0); a workspace that is NULL, too small or misaligned with Q > 0. */
+size_t fp_mesh_point_distance_workspace_bytes(int Q);
+int fp_mesh_point_distance(const float* pos /*dev Nv,3*/, int Nv, const int32_t* faces /*dev F,3*/, int F,
+                           const float* points /*dev Q,3*/, int Q,
+                           float* dist2 /*dev Q*/, int32_t* face /*dev Q|NULL*/, float* closest /*dev Q,3|NULL*/,
+                           void* workspace /*dev*/, size_t workspace_bytes, void* stream);
 
 /* An object's mesh from posed RGB-D reference views: truncated-signed-distance (TSDF) fusion into a caller-owned volume, then marching
  * tetrahedra.  The volume has nz x ny x nx voxels; voxel (ix, iy, iz) has the linear index i = (iz * ny + iy) * nx + ix and, in the

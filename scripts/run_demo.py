@@ -9,7 +9,10 @@ object's mesh from those reference views (foundationpose_amd/reconstruct.py) in 
 such a directory from the can first; `--ref_texture T` bakes a texture atlas of T x T texels a face onto that mesh from the same views;
 `--ref_keep_components largest|N` drops floaters from it (all but the largest surface component, or those under N triangles);
 `--save_mesh PATH` writes the mesh that was used: a PLY (positions, normals, vertex colours), or with a path ending in .obj an OBJ with
-its MTL and the texture as a PNG."""
+its MTL and the texture as a PNG; `--compare_mesh PATH` (with the reference views) compares the fused mesh with the mesh file PATH, in the
+frame of the views' poses -- `--compare_mesh synthetic` with --synthetic_ref_views takes the can the views were rendered from -- and
+prints the report (reconstruct.compare_meshes: accuracy, completeness, chamfer, Hausdorff, precision / recall / F-score at 0.5, 1, 2 and
+4 voxel pitches) as one JSON line {"compare_mesh": ...}."""
 import argparse
 import logging
 import os
@@ -101,6 +104,10 @@ def main(argv=None):
                     help="with --ref_views: drop floaters from the fused mesh: keep the surface component with the most triangles, or every "
                          "component of at least N triangles")
     ap.add_argument("--save_mesh", type=str, default=None, help="write the mesh that is used to this PLY (or .obj: OBJ + MTL + PNG)")
+    ap.add_argument("--compare_mesh", type=str, default=None, metavar="PATH",
+                    help="with --ref_views: compare the fused mesh with this mesh file (or 'synthetic': the can of --synthetic_ref_views) "
+                         "and print the report as one JSON line")
+    ap.add_argument("--compare_samples", type=int, default=100_000, help="surface samples per mesh for --compare_mesh")
     args = ap.parse_args(argv)
     logging.basicConfig(level=logging.INFO, format="[%(funcName)s()] %(message)s")
 
@@ -127,18 +134,30 @@ def main(argv=None):
         ap.error("--ref_refine_poses needs --ref_views (or --synthetic_ref_views N)")
     if args.ref_keep_components is not None and not args.ref_views:
         ap.error("--ref_keep_components needs --ref_views (or --synthetic_ref_views N)")
+    if args.compare_mesh and not args.ref_views:
+        ap.error("--compare_mesh needs --ref_views (or --synthetic_ref_views N)")
+    if args.compare_mesh == "synthetic" and not args.synthetic_ref_views:
+        ap.error("--compare_mesh synthetic needs --synthetic_ref_views N")
     if args.ref_views:
         from foundationpose_amd.reconstruct import reconstruct_object
         t0 = time.perf_counter()
-        mesh, _ = reconstruct_object(*read_ref_views(args.ref_views), device=dev, texture=args.ref_texture or None,
-                                     refine_poses=args.ref_refine_poses, refine_against=args.ref_refine_against,
-                                     keep_components=args.ref_keep_components)
+        mesh, fused = reconstruct_object(*read_ref_views(args.ref_views), device=dev, texture=args.ref_texture or None,
+                                         refine_poses=args.ref_refine_poses, refine_against=args.ref_refine_against,
+                                         keep_components=args.ref_keep_components)
         atlas = getattr(getattr(mesh.visual, "material", None), "image", None)
         logging.info(f"mesh from {args.ref_views}: {len(mesh.vertices)} vertices, {len(mesh.faces)} faces"
                      + ("" if atlas is None else f", atlas {atlas.shape[0]} x {atlas.shape[1]}")
                      + (f", view poses refined {args.ref_refine_poses} x" if args.ref_refine_poses else "")
                      + ("" if args.ref_keep_components is None else f", {len(mesh.components)} surface components, {mesh.dropped_triangles} triangles dropped")
                      + f" in {time.perf_counter() - t0:.2f} s")
+        if args.compare_mesh:
+            import json
+            from foundationpose_amd.mesh import make_can_mesh
+            from foundationpose_amd.reconstruct import compare_meshes
+            truth = make_can_mesh() if args.compare_mesh == "synthetic" else load_mesh(args.compare_mesh)
+            report = compare_meshes(fused, truth, samples=args.compare_samples, unit=mesh.voxel, device=dev).as_dict()
+            report.update(unit_m=mesh.voxel, faces=[len(mesh.faces), len(truth.faces)])
+            print(json.dumps({"compare_mesh": report}), flush=True)
     else:
         mesh = load_mesh(args.mesh_file)
     if args.ref_texture and not args.ref_views:
