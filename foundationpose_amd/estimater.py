@@ -99,11 +99,36 @@ class FoundationPose:
             t["pos"] = (t["pos"].double() - center).float()        # the host's float64 subtraction, rounded once
             t["_handle"] = mesh_handle_from_tensors(t)
             self.mesh_tensors = t
+        self.symmetries = None                            # the record of the last detect_symmetries (None: the table was given)
         if symmetry_tfs is None:
             self.symmetry_tfs = torch.eye(4, device=self.device).float()[None]
+        elif isinstance(symmetry_tfs, str):
+            if symmetry_tfs != "detect":
+                raise ValueError(f"symmetry_tfs must be None, a (S,4,4) table or 'detect', got {symmetry_tfs!r}")
+            self.detect_symmetries(rebuild_grid=False)    # the constructor builds the grid next; after reset_object it is the caller's
         else:
             self.symmetry_tfs = torch.as_tensor(symmetry_tfs, device=self.device, dtype=torch.float)
         logging.info("reset done")
+
+    def detect_symmetries(self, rebuild_grid=True, **kw):
+        """Find the mesh's rotational symmetries (reconstruct.detect_symmetries on the centred mesh; kw: its tol, max_order,
+        rot_angle_discrete, samples, n_axes), set self.symmetry_tfs from them, in the frame of the mesh handed to reset_object like a
+        table given by the caller, rebuild the rotation grid with them and return the record (symmetry.Symmetries, in the centred
+        frame; also kept as self.symmetries).  tol=None: for a mesh fused at a known pitch (from_reference_views) two voxels, otherwise
+        1 % of the mesh's extent.  Only geometry is considered: a can whose label is not symmetric is still reported as symmetric."""
+        from .reconstruct import detect_symmetries
+        if kw.get("tol") is None:
+            voxel = getattr(self.mesh_ori, "voxel", None)
+            kw["tol"] = 2.0 * float(voxel) if voxel else None
+        rec = detect_symmetries(dict(pos=self.mesh_tensors["pos"], faces=self.mesh_tensors["faces"]), **kw)
+        to_c, from_c = np.eye(4), np.eye(4)               # T(-model_center), T(+model_center): as _centred_frames, inverted
+        to_c[:3, 3] = -np.asarray(self.model_center, dtype=np.float64)
+        from_c[:3, 3] = np.asarray(self.model_center, dtype=np.float64)
+        self.symmetry_tfs = torch.as_tensor(from_c @ rec.tfs @ to_c, device=self.device, dtype=torch.float)
+        self.symmetries = rec
+        if rebuild_grid:
+            self.make_rotation_grid(min_n_views=40, inplane_step=60)
+        return rec
 
     def get_tf_to_centered_mesh(self):
         tf_to_center = torch.eye(4, dtype=torch.float, device=self.device)

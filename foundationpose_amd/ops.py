@@ -797,6 +797,20 @@ MESH_DISTANCE_OUTPUTS = ("dist2", "face", "closest")
 _MESH_DISTANCE_DTYPES = {"dist2": torch.float32, "face": torch.int32, "closest": torch.float32}
 
 
+def _mesh_pos_faces(what, mesh_tensors, pos, faces):
+    """the mesh of a call that takes mesh_tensors (a dict with pos and faces) or pos= and faces= themselves -> (pos, faces)"""
+    if mesh_tensors is not None:
+        if pos is not None or faces is not None:
+            raise _lib.FpAmdError(f"{what}: pass mesh_tensors or pos / faces, not both")
+        for k in ("pos", "faces"):
+            if k not in mesh_tensors:
+                raise _lib.FpAmdError(f"{what}: mesh_tensors has no '{k}'")
+        pos, faces = mesh_tensors["pos"], mesh_tensors["faces"]
+    if pos is None or faces is None:
+        raise _lib.FpAmdError(f"{what}: no mesh (pass mesh_tensors, or pos and faces)")
+    return pos, faces
+
+
 def mesh_point_distance(points, mesh_tensors=None, pos=None, faces=None, want=MESH_DISTANCE_OUTPUTS, out=None):
     """fp_mesh_point_distance: the exact distance from the points (Q,3) f32 to the surface of a triangle mesh -> dict of device tensors:
     `dist2` (Q,) f32 the squared distance to the nearest point of any triangle, `face` (Q,) int32 that triangle, `closest` (Q,3) f32
@@ -815,15 +829,7 @@ def mesh_point_distance(points, mesh_tensors=None, pos=None, faces=None, want=ME
     if not names:
         raise ValueError(f"{what}: want is empty")
     names = tuple(n for n in MESH_DISTANCE_OUTPUTS if n in names or n == "dist2")
-    if mesh_tensors is not None:
-        if pos is not None or faces is not None:
-            raise _lib.FpAmdError(f"{what}: pass mesh_tensors or pos / faces, not both")
-        for k in ("pos", "faces"):
-            if k not in mesh_tensors:
-                raise _lib.FpAmdError(f"{what}: mesh_tensors has no '{k}'")
-        pos, faces = mesh_tensors["pos"], mesh_tensors["faces"]
-    if pos is None or faces is None:
-        raise _lib.FpAmdError(f"{what}: no mesh (pass mesh_tensors, or pos and faces)")
+    pos, faces = _mesh_pos_faces(what, mesh_tensors, pos, faces)
     for name, t in (("points", points), ("pos", pos), ("faces", faces)):
         if not torch.is_tensor(t):
             raise _lib.FpAmdError(f"{what}: {name} must be a tensor, got {type(t).__name__}")
@@ -859,6 +865,92 @@ def mesh_point_distance(points, mesh_tensors=None, pos=None, faces=None, want=ME
     ws = _workspace(need, pts.device)
     _lib.check(_lib.lib().fp_mesh_point_distance(_ptr(vp_), Nv, _ptr(fc), F, _ptr(pts), Q, _ptr(out["dist2"]), _ptr(out.get("face")),
                                                  _ptr(out.get("closest")), _ptr(ws), need, _stream(pts)), "fp_mesh_point_distance")
+    return {k: out[k] for k in names}
+
+
+MESH_RESIDUAL_OUTPUTS = ("max_d2", "over", "dist2")
+_MESH_RESIDUAL_DTYPES = {"max_d2": torch.float32, "over": torch.int32, "dist2": torch.float32}
+MESH_RESIDUAL_MAX_THRESHOLDS = 4
+
+
+def mesh_transform_residuals(points, tfs, mesh_tensors=None, pos=None, faces=None, thresholds=None, want=("max_d2", "over"), out=None):
+    """fp_mesh_transform_residuals: how far each of the transforms tfs (T,4,4) f32 moves the points (Q,3) f32 (surface samples of the
+    mesh, as a rule) off the surface of the mesh -> dict of device tensors: `max_d2` (T,) f32 the largest squared distance of a
+    transformed point to the surface, `over` (T,L) int32 the number of points whose squared distance is strictly above each threshold
+    squared, `dist2` (T,Q) f32 the whole matrix (include/fp_amd.h has the definition: p' = ((r0*x + r1*y) + r2*z) + t per row in
+    float32, then fp_mesh_point_distance's dist2; +inf where no triangle answers).  The mesh is mesh_tensors or pos= and faces=, as
+    for mesh_point_distance.  thresholds: up to four lengths (a sequence of floats, or None for none); they are rounded to float32
+    and squared in float32 on the host (thr2 = f32(thr) * f32(thr), one rounding), and that table goes to the device.  want: names out
+    of "max_d2", "over", "dist2"; max_d2 is always computed and returned, over is left out when there is no threshold.  out: a dict of
+    caller-owned buffers for some of the wanted names.  The rows of tfs are used as given (row 3 is not read).  T x Q x F pair
+    tests.  The workspace (4 bytes a pair) is the library's per-stream scratch, or a fresh allocation inside a stream capture.  Wrong
+    shapes are refused first, then tensors that are not on the device, of another dtype or not contiguous, then buffers that overlap
+    an input or each other (FpAmdError)."""
+    what = "mesh_transform_residuals"
+    names = (want,) if isinstance(want, str) else tuple(want)
+    for w in names:
+        if w not in MESH_RESIDUAL_OUTPUTS:
+            raise ValueError(f"{what}: unknown name {w!r} in want (known: {list(MESH_RESIDUAL_OUTPUTS)})")
+    if not names:
+        raise ValueError(f"{what}: want is empty")
+    thr = np.zeros(0, np.float32) if thresholds is None else np.asarray(thresholds, dtype=np.float64).reshape(-1).astype(np.float32)
+    L = len(thr)
+    if L > MESH_RESIDUAL_MAX_THRESHOLDS:
+        raise ValueError(f"{what}: {L} thresholds (at most {MESH_RESIDUAL_MAX_THRESHOLDS})")
+    if L and not bool((thr >= 0).all()):
+        raise ValueError(f"{what}: thresholds must be lengths >= 0, got {thresholds!r}")
+    names = tuple(n for n in MESH_RESIDUAL_OUTPUTS if (n in names or n == "max_d2") and not (n == "over" and L == 0))
+    pos, faces = _mesh_pos_faces(what, mesh_tensors, pos, faces)
+    for name, t in (("points", points), ("pos", pos), ("faces", faces)):
+        if not torch.is_tensor(t):
+            raise _lib.FpAmdError(f"{what}: {name} must be a tensor, got {type(t).__name__}")
+        if t.dim() != 2 or int(t.shape[1]) != 3:
+            raise _lib.FpAmdError(f"{what}: {name} must be (n,3), got {tuple(t.shape)}")
+    if not torch.is_tensor(tfs):
+        raise _lib.FpAmdError(f"{what}: tfs must be a tensor, got {type(tfs).__name__}")
+    if tfs.dim() != 3 or tuple(tfs.shape[1:]) != (4, 4):
+        raise _lib.FpAmdError(f"{what}: tfs must be (T,4,4), got {tuple(tfs.shape)}")
+    Q, Nv, F, T = int(points.shape[0]), int(pos.shape[0]), int(faces.shape[0]), int(tfs.shape[0])
+    if T * Q > (1 << 30) or max(T, F) > (1 << 30):
+        raise _lib.FpAmdError(f"{what}: {T} transforms of {Q} points against {F} faces (at most 2^30 pairs, transforms or faces)")
+    out = dict(out or {})
+    shapes = {"max_d2": (T,), "over": (T, L), "dist2": (T, Q)}
+    for k, t in out.items():
+        if k not in names:
+            raise _lib.FpAmdError(f"{what}: out has '{k}', which is not among the wanted outputs {list(names)}")
+        if not torch.is_tensor(t) or tuple(t.shape) != shapes[k]:
+            raise _lib.FpAmdError(f"{what}: out['{k}'] must be a tensor of shape {shapes[k]}, got "
+                                  f"{tuple(t.shape) if torch.is_tensor(t) else type(t).__name__}")
+    pts = _dev(points, torch.float32, "points")
+    m = _dev(tfs, torch.float32, "tfs")
+    vp_ = _dev(pos, torch.float32, "pos")
+    fc = _dev(faces, torch.int32, "faces")
+    for k in list(out):
+        out[k] = _dev(out[k], _MESH_RESIDUAL_DTYPES[k], f"out['{k}']")
+    for k, t in out.items():
+        for name, src in (("points", pts), ("tfs", m), ("pos", vp_), ("faces", fc)):
+            if _overlap(t, src):
+                raise _lib.FpAmdError(f"{what}: out['{k}'] overlaps {name}")
+        for k2, t2 in out.items():
+            if k2 < k and _overlap(t, t2):
+                raise _lib.FpAmdError(f"{what}: out['{k}'] overlaps out['{k2}']")
+    for k in names:
+        if k not in out:
+            out[k] = torch.empty(shapes[k], dtype=_MESH_RESIDUAL_DTYPES[k], device=pts.device)
+    thr2 = None
+    if L:
+        sq = thr * thr                                                        # float32 * float32: one rounding, on the host
+        if torch.cuda.is_current_stream_capturing():                          # no host-to-device copy inside a capture: L fills
+            thr2 = torch.empty(L, dtype=torch.float32, device=pts.device)
+            for l in range(L):
+                thr2[l].fill_(float(sq[l]))
+        else:
+            thr2 = torch.as_tensor(sq, device=pts.device)
+    need = int(_lib.lib().fp_mesh_transform_residuals_workspace_bytes(T, Q))
+    ws = _workspace(need, pts.device)
+    _lib.check(_lib.lib().fp_mesh_transform_residuals(_ptr(vp_), Nv, _ptr(fc), F, _ptr(pts), Q, _ptr(m), T, _ptr(thr2), L,
+                                                      _ptr(out["max_d2"]), _ptr(out.get("over")), _ptr(out.get("dist2")), _ptr(ws), need,
+                                                      _stream(pts)), "fp_mesh_transform_residuals")
     return {k: out[k] for k in names}
 
 
@@ -2064,6 +2156,7 @@ mask_depth_stats = _timed("fp_mask_depth_stats", mask_depth_stats)
 depth_agreement = _timed("fp_depth_agreement", depth_agreement)
 pose_errors = _timed("fp_pose_errors", pose_errors)
 mesh_point_distance = _timed("fp_mesh_point_distance", mesh_point_distance)
+mesh_transform_residuals = _timed("fp_mesh_transform_residuals", mesh_transform_residuals)
 icp_point_plane = _timed("fp_icp_point_plane", icp_point_plane)
 tsdf_components = _timed("fp_tsdf_label_components", tsdf_components)
 vsd_counts = _timed("fp_vsd_counts", vsd_counts)

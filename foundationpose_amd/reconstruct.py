@@ -572,3 +572,48 @@ def compare_meshes(a, b, samples=100_000, thresholds=None, seed=0, unit=None, de
     d_ab = ops.mesh_point_distance(pa, tb, want=("dist2",))["dist2"].double().sqrt_().float()
     d_ba = ops.mesh_point_distance(pb, ta, want=("dist2",))["dist2"].double().sqrt_().float()
     return ops.MeshComparison.from_distances(d_ab, d_ba, thr)
+
+
+# ------------------------------------------------------------------ which rotations map a mesh onto itself
+def detect_symmetries(mesh_tensors, tol=None, max_order=6, rot_angle_discrete=5, samples=(64, 512), n_axes=800):
+    """The rotational symmetries of a mesh -> symmetry.Symmetries: tfs (S,4,4) float64 with the identity first (what the estimator's
+    symmetry_tfs, make_rotation_grid, pose_errors(want="sym"), MSSD, MSPD and cluster_poses take), the axes with their orders
+    (math.inf for a continuous one, which contributes a rotation every rot_angle_discrete degrees), tol and the residual of each
+    transform.  mesh_tensors: a dict with pos and faces on a device, or a SimpleMesh (then on the current device).  tol: how far a
+    symmetry may move the surface off itself, a length; None: 1 % of twice the largest vertex distance from the surface's centroid.
+    For a fused mesh give it the noise of the fusion: a couple of voxels.  samples: the numbers of surface samples of the coarse scan
+    (sample_surface, seed 1) and of the refinement and the final check (seed 0).  Only geometry is considered: a can whose label is
+    not symmetric is still reported as symmetric; only proper rotations are looked for.  symmetry.find_symmetries has the recipe; this
+    function binds its two callables to the device: ops.mesh_transform_residuals for the largest distance per candidate transform
+    (one call per order over all n_axes candidate axes) and ops.mesh_point_distance for the closest points of a refinement step.  A
+    setup call: it reads the mesh back once and synchronises at every step of the policy."""
+    from . import symmetry
+    what = "detect_symmetries"
+    pos, faces = _mesh_arrays(mesh_tensors, None if isinstance(mesh_tensors, dict) else "cuda", what, "mesh_tensors")
+    try:
+        n_coarse, n_fine = samples
+    except (TypeError, ValueError):
+        raise ValueError(f"{what}: samples must be two counts (coarse, fine), got {samples!r}") from None
+    n_coarse, n_fine = _check_count(n_coarse, what, "samples[0]"), _check_count(n_fine, what, "samples[1]")
+    centre, radius = symmetry.surface_centre(pos.cpu().numpy(), faces.cpu().numpy())
+    if tol is None:
+        tol = 0.01 * 2.0 * radius
+    tol = float(tol)
+    if not (np.isfinite(tol) and tol > 0):
+        raise ValueError(f"{what}: tol must be a positive length, got {tol!r}")
+    mesh = dict(pos=pos, faces=faces)
+    pts = {"coarse": sample_surface(mesh, n_coarse, seed=1)[0], "fine": sample_surface(mesh, n_fine, seed=0)[0]}
+    fine64 = pts["fine"].cpu().numpy().astype(np.float64)
+
+    def residuals(tfs, which):
+        m = torch.as_tensor(np.ascontiguousarray(tfs, dtype=np.float32), device=pos.device)
+        d2 = ops.mesh_transform_residuals(pts[which], m, mesh, want=("max_d2",))["max_d2"]
+        return np.sqrt(d2.cpu().numpy().astype(np.float64))
+
+    def closest(tf):
+        m = torch.as_tensor(np.ascontiguousarray(tf, dtype=np.float32), device=pos.device)
+        moved = (pts["fine"] @ m[:3, :3].T + m[:3, 3]).contiguous()
+        return fine64, ops.mesh_point_distance(moved, mesh, want=("closest",))["closest"].cpu().numpy().astype(np.float64)
+
+    return symmetry.find_symmetries(residuals, closest, centre, radius, tol, max_order=max_order, n_axes=n_axes,
+                                    rot_angle_discrete=rot_angle_discrete)

@@ -98,8 +98,10 @@ const char* fp_last_error(void);
  *               fp_warp_crops_multi, fp_warp_crops_views, fp_pose_update_multi, fp_pose_update_views.  A caller of the four base names
  *               built against an older header passes the wrong arguments: gate on fp_version().
  *   230 -> 231: + fp_mesh_point_distance, fp_mesh_point_distance_workspace_bytes (additions only): the exact distance from points to
- *               the surface of a triangle mesh, with the nearest face and the closest point. */
-#define FP_AMD_ABI_VERSION 231
+ *               the surface of a triangle mesh, with the nearest face and the closest point.
+ *   231 -> 232: + fp_mesh_transform_residuals, fp_mesh_transform_residuals_workspace_bytes (additions only): how far each of T
+ *               candidate transforms moves a mesh's surface samples off the surface, for detecting its rotational symmetries. */
+#define FP_AMD_ABI_VERSION 232
 int fp_version(void);
 
 /* Utils.py:104-130 make_mesh_tensors: records caller-owned device tensors.
@@ -323,6 +325,38 @@ int fp_mesh_point_distance(const float* pos /*dev Nv,3*/, int Nv, const int32_t*
                            const float* points /*dev Q,3*/, int Q,
                            float* dist2 /*dev Q*/, int32_t* face /*dev Q|NULL*/, float* closest /*dev Q,3|NULL*/,
                            void* workspace /*dev*/, size_t workspace_bytes, void* stream);
+
+/* How far does each of T candidate transforms move a mesh's surface off itself: the squared distances of Q transformed points (surface
+ * samples, as a rule) to the surface, reduced per transform on the chip.  Every operation is one float32 operation (IEEE, round to
+ * nearest even), without contraction, in the order written.
+ *  - Transformed point.  For transform t with rows r0, r1, r2 of tfs[t] (row-major 4x4; row 3 is never read) and point i = (x, y, z):
+ *      p'[k] = ((rk[0]*x + rk[1]*y) + rk[2]*z) + rk[3],  k = 0, 1, 2.
+ *    The rows are used as given: a matrix that is no rigid motion is not an error.
+ *  - Distance.  d2(t, i) is dist2 of fp_mesh_point_distance for the query p': the smallest dd over the triangles whose candidate
+ *    counts (dd <= FLT_MAX), by exactly that function's closest-point walk (one copy of the code, csrc/mesh_closest.h), and +inf
+ *    where no triangle answers: F == 0, every triangle skipped, or a p' that is not finite.  d2 is never NaN and never negative.
+ *  - Outputs.  max_d2[t] = the maximum over i of d2(t, i) (+inf if any sample is unanswered);  over[t*L + l] = the number of i with
+ *    d2(t, i) > thr2[l], strictly, so +inf counts unless thr2[l] is +inf, and a NaN threshold counts nothing;  dist2[t*Q + i] =
+ *    d2(t, i), where asked for.  over may be NULL when L == 0, dist2 may be NULL (not wanted).
+ *  - Empty inputs.  T == 0 does nothing.  With Q == 0 (and T > 0) max_d2[t] = 0 and over[t, l] = 0; dist2 has no element.
+ * Every reduction is a minimum, a maximum or an integer count, the first two taken on the bits of non-negative floats (which order as
+ * the floats do), so each output has one value whatever the schedule: a transform has the same bits alone, in a batch and on every
+ * replay.  Integer atomics only.  The grid runs over (256 (transform, sample) pairs, numbered t*Q + i, one per lane) x (a chunk of
+ * faces); the triangles pass through LDS in tiles; a lane merges its chunk's minimum into workspace[t*Q + i] with one 32-bit atomic
+ * minimum; an init launch sets the cells to the bits of +inf and a finish launch, one workgroup per transform, takes the maximum and
+ * the counts.  T * Q * F pair tests: the cost is the caller's to weigh.  No allocation, no host synchronisation (graph-capturable);
+ * nothing is written outside the outputs and the workspace (fp_mesh_transform_residuals_workspace_bytes(T, Q) bytes = 4 * T * Q,
+ * 4-byte aligned; 0 when T <= 0 or Q <= 0).  Argument errors (FP_ERR_INVALID_ARG), before any launch, each message beginning with
+ * the entry point's name: T, Q, F or Nv negative; T * Q, T or F above 2^30; L outside 0..4; and with T > 0: NULL max_d2; NULL thr2 or
+ * over with L > 0; with Q > 0 also NULL points or tfs, NULL faces with F > 0, NULL pos with Nv > 0 and F > 0, a workspace that is
+ * NULL, too small or misaligned. */
+size_t fp_mesh_transform_residuals_workspace_bytes(int T, int Q);
+int fp_mesh_transform_residuals(const float* pos /*dev Nv,3*/, int Nv, const int32_t* faces /*dev F,3*/, int F,
+                                const float* points /*dev Q,3*/, int Q,
+                                const float* tfs /*dev T,4,4 row-major; rows 0..2 are read*/, int T,
+                                const float* thr2 /*dev L | NULL when L == 0*/, int L /*0..4*/,
+                                float* max_d2 /*dev T*/, int32_t* over /*dev T,L|NULL*/, float* dist2 /*dev T,Q|NULL*/,
+                                void* workspace /*dev*/, size_t workspace_bytes, void* stream);
 
 /* An object's mesh from posed RGB-D reference views: truncated-signed-distance (TSDF) fusion into a caller-owned volume, then marching
  * tetrahedra.  The volume has nz x ny x nx voxels; voxel (ix, iy, iz) has the linear index i = (iz * ny + iy) * nx + ix and, in the

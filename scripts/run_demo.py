@@ -12,7 +12,8 @@ such a directory from the can first; `--ref_texture T` bakes a texture atlas of 
 its MTL and the texture as a PNG; `--compare_mesh PATH` (with the reference views) compares the fused mesh with the mesh file PATH, in the
 frame of the views' poses -- `--compare_mesh synthetic` with --synthetic_ref_views takes the can the views were rendered from -- and
 prints the report (reconstruct.compare_meshes: accuracy, completeness, chamfer, Hausdorff, precision / recall / F-score at 0.5, 1, 2 and
-4 voxel pitches) as one JSON line {"compare_mesh": ...}."""
+4 voxel pitches) as one JSON line {"compare_mesh": ...}; `--detect_symmetry` finds the rotational symmetries of the mesh that is used,
+registers with the rotation grid clustered by them and prints the axes as one JSON line {"detect_symmetry": ...}."""
 import argparse
 import logging
 import os
@@ -108,6 +109,9 @@ def main(argv=None):
                     help="with --ref_views: compare the fused mesh with this mesh file (or 'synthetic': the can of --synthetic_ref_views) "
                          "and print the report as one JSON line")
     ap.add_argument("--compare_samples", type=int, default=100_000, help="surface samples per mesh for --compare_mesh")
+    ap.add_argument("--detect_symmetry", action="store_true",
+                    help="find the mesh's rotational symmetries (FoundationPose.detect_symmetries), use them for the rotation grid and "
+                         "print the axes as one JSON line")
     args = ap.parse_args(argv)
     logging.basicConfig(level=logging.INFO, format="[%(funcName)s()] %(message)s")
 
@@ -173,6 +177,13 @@ def main(argv=None):
     glctx = dr.RasterizeCudaContext()
     est = FoundationPose(model_pts=mesh.vertices, model_normals=mesh.vertex_normals, mesh=mesh, scorer=scorer, refiner=refiner,
                          debug_dir=args.debug_dir, debug=args.debug, glctx=glctx, device=dev, track_graph=args.track_graph)
+    if args.detect_symmetry:
+        import json
+        import math
+        rec = est.detect_symmetries()                     # a fused mesh: within two voxels of its pitch; a CAD model: 1 % of its extent
+        print(json.dumps({"detect_symmetry": dict(
+            transforms=len(rec.tfs), hypotheses=len(est.rot_grid), tol_m=rec.tol, largest_residual_m=float(rec.residuals.max()),
+            axes=[dict(axis=[float(x) for x in a], order="continuous" if k == math.inf else int(k)) for a, k in rec.axes])}), flush=True)
     logging.info("estimator initialization done")
     reader = YcbineoatReader(video_dir=args.test_scene_dir, shorter_side=None, zfar=np.inf)
     times = []
