@@ -241,17 +241,28 @@ class FoundationPose:
         gt_c, sym_c = self._centred_frames(gt_pose)
         return ops.pose_errors(self.pts, poses, gt_c, symmetry_tfs=sym_c, want=want)
 
-    def compare_to_mesh(self, mesh, samples=100_000, thresholds=None, seed=0, unit=None):
+    def align_to_mesh(self, mesh, **kw):
+        """Register the estimator's mesh (as it was handed to reset_object, for example fused by from_reference_views in the frame of
+        the reference poses) onto `mesh` (a SimpleMesh or a mesh-tensor dict, for example the object's CAD model in its own frame)
+        -> ops.MeshAlignment (reconstruct.align_meshes; kw: its starts, samples, iterations, max_dist, min_overlap, init, seed).
+        Its transfer_pose turns a pose of the estimator's mesh into the pose of `mesh`'s frame; compare_to_mesh(mesh, tf=it) compares
+        in the aligned frame.  A setup call (it synchronises)."""
+        from .reconstruct import align_meshes
+        return align_meshes(self.mesh_ori, mesh, device=self.device, **kw)
+
+    def compare_to_mesh(self, mesh, samples=100_000, thresholds=None, seed=0, unit=None, tf=None):
         """How the estimator's mesh compares with `mesh` (a SimpleMesh or a mesh-tensor dict in the frame of the mesh handed to
         reset_object, for example the CAD model of an object whose estimator was made by from_reference_views) ->
         ops.MeshComparison (reconstruct.compare_meshes: accuracy = this estimator's mesh against `mesh`, completeness the other way,
         chamfer, Hausdorff, precision / recall / F-score per threshold).  The estimator's side is its mesh as it was handed over, not
         the centred one.  unit: the length the default thresholds are multiples of; None: the voxel pitch the mesh was fused at, for
-        an estimator made by from_reference_views (otherwise pass unit or thresholds).  An evaluation call (it synchronises)."""
+        an estimator made by from_reference_views (otherwise pass unit or thresholds).  tf: a (4,4) transform or an
+        ops.MeshAlignment (align_to_mesh) from the estimator's mesh into `mesh`'s frame, where the two are not in one frame already.
+        An evaluation call (it synchronises)."""
         from .reconstruct import compare_meshes
         if unit is None and thresholds is None:
             unit = getattr(self.mesh_ori, "voxel", None)
-        return compare_meshes(self.mesh_ori, mesh, samples=samples, thresholds=thresholds, seed=seed, unit=unit, device=self.device)
+        return compare_meshes(self.mesh_ori, mesh, samples=samples, thresholds=thresholds, seed=seed, unit=unit, device=self.device, tf=tf)
 
     # the depth maps bop_errors holds at a time: 48 MiB = 40 full 480 x 640 float32 frames.  Small against the 256 MiB last-level cache,
     # so a chunk's renders are still on the chip when the counting kernel reads them, and large enough that the raster launches of a

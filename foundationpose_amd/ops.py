@@ -1,6 +1,6 @@
 """torch-tensor front-end of the C ABI (device pointers + current HIP stream).  Plumbing only."""
 import ctypes as C
-from typing import NamedTuple
+from typing import NamedTuple, Optional
 
 import numpy as np
 import torch
@@ -952,6 +952,111 @@ def mesh_transform_residuals(points, tfs, mesh_tensors=None, pos=None, faces=Non
                                                       _ptr(out["max_d2"]), _ptr(out.get("over")), _ptr(out.get("dist2")), _ptr(ws), need,
                                                       _stream(pts)), "fp_mesh_transform_residuals")
     return {k: out[k] for k in names}
+
+
+MESH_ICP_OUTPUTS = ("dist2", "face")
+_MESH_ICP_DTYPES = {"tfs_out": torch.float32, "system": torch.float64, "dist2": torch.float32, "face": torch.int32}
+
+
+def mesh_icp_workspace(T, Q, device):
+    """the workspace of mesh_icp_step for T transforms of Q points (a captured graph owns its buffers)"""
+    nbytes = int(_lib.lib().fp_mesh_icp_workspace_bytes(int(T), int(Q)))
+    return torch.empty(((nbytes + 7) // 8,), dtype=torch.float64, device=device)
+
+
+def mesh_icp_step(points, tfs, mesh_tensors=None, pos=None, faces=None, *, max_dist, damping=1e-3, min_pairs=6, want=(), out=None,
+                  workspace=None):
+    """fp_mesh_icp_step: one Gauss-Newton step of point-to-plane ICP for each of the transforms tfs (T,4,4) f32 of the points (Q,3) f32
+    (surface samples of a mesh a) against the surface of a mesh b -> (tfs_out (T,4,4) f32, system (T,40) f64[, dict of `dist2` (T,Q)
+    f32 / `face` (T,Q) int32 for the names in want]) device tensors.  include/fp_amd.h has the definition: each transformed point is
+    paired with its exact closest point on b (fp_mesh_point_distance's) and that face's normal; pairs farther apart than max_dist are
+    dropped; damping scales diag(A); fewer than min_pairs pairs leave the transform as it is.  system has icp_point_plane's layout
+    (IcpStep.rows reads it) with [36] = the sum of the pairs' squared distances.  The mesh b is mesh_tensors or pos= and faces=, as
+    for mesh_point_distance.  out: a dict of caller-owned buffers out of "tfs_out", "system" and the wanted names; workspace:
+    mesh_icp_workspace (None: the library's per-stream scratch, or a fresh allocation inside a stream capture).  T x Q x F pair
+    tests.  Wrong shapes are refused first, then tensors that are not on the device, of another dtype or not contiguous, then
+    buffers that overlap an input or each other (FpAmdError)."""
+    what = "mesh_icp_step"
+    md, dmp, mp = _check_icp(max_dist, damping, min_pairs, what)
+    names = (want,) if isinstance(want, str) else tuple(want)
+    for w in names:
+        if w not in MESH_ICP_OUTPUTS:
+            raise ValueError(f"{what}: unknown name {w!r} in want (known: {list(MESH_ICP_OUTPUTS)})")
+    names = tuple(n for n in MESH_ICP_OUTPUTS if n in names)
+    pos, faces = _mesh_pos_faces(what, mesh_tensors, pos, faces)
+    for name, t in (("points", points), ("pos", pos), ("faces", faces)):
+        if not torch.is_tensor(t):
+            raise _lib.FpAmdError(f"{what}: {name} must be a tensor, got {type(t).__name__}")
+        if t.dim() != 2 or int(t.shape[1]) != 3:
+            raise _lib.FpAmdError(f"{what}: {name} must be (n,3), got {tuple(t.shape)}")
+    if not torch.is_tensor(tfs):
+        raise _lib.FpAmdError(f"{what}: tfs must be a tensor, got {type(tfs).__name__}")
+    if tfs.dim() != 3 or tuple(tfs.shape[1:]) != (4, 4):
+        raise _lib.FpAmdError(f"{what}: tfs must be (T,4,4), got {tuple(tfs.shape)}")
+    Q, Nv, F, T = int(points.shape[0]), int(pos.shape[0]), int(faces.shape[0]), int(tfs.shape[0])
+    if T * Q > (1 << 30) or max(T, F) > (1 << 30):
+        raise _lib.FpAmdError(f"{what}: {T} transforms of {Q} points against {F} faces (at most 2^30 pairs, transforms or faces)")
+    out = dict(out or {})
+    shapes = {"tfs_out": (T, 4, 4), "system": (T, 40), "dist2": (T, Q), "face": (T, Q)}
+    made = ("tfs_out", "system") + names
+    for k, t in out.items():
+        if k not in made:
+            raise _lib.FpAmdError(f"{what}: out has '{k}', which is not among the outputs {list(made)}")
+        if not torch.is_tensor(t) or tuple(t.shape) != shapes[k]:
+            raise _lib.FpAmdError(f"{what}: out['{k}'] must be a tensor of shape {shapes[k]}, got "
+                                  f"{tuple(t.shape) if torch.is_tensor(t) else type(t).__name__}")
+    pts = _dev(points, torch.float32, "points")
+    m = _dev(tfs, torch.float32, "tfs")
+    vp_ = _dev(pos, torch.float32, "pos")
+    fc = _dev(faces, torch.int32, "faces")
+    for k in list(out):
+        out[k] = _dev(out[k], _MESH_ICP_DTYPES[k], f"out['{k}']")
+    for k, t in out.items():
+        for name, src in (("points", pts), ("tfs", m), ("pos", vp_), ("faces", fc)):
+            if _overlap(t, src):
+                raise _lib.FpAmdError(f"{what}: out['{k}'] overlaps {name}")
+        for k2, t2 in out.items():
+            if k2 < k and _overlap(t, t2):
+                raise _lib.FpAmdError(f"{what}: out['{k}'] overlaps out['{k2}']")
+    need = int(_lib.lib().fp_mesh_icp_workspace_bytes(T, Q))
+    if workspace is None:
+        ws, ws_bytes = _workspace(need, pts.device), need
+    else:
+        if not (torch.is_tensor(workspace) and workspace.is_cuda and workspace.is_contiguous()):
+            raise _lib.FpAmdError(f"{what}: workspace must be a contiguous CUDA(HIP) tensor")
+        ws, ws_bytes = workspace, workspace.numel() * workspace.element_size()
+        if ws_bytes < need:
+            raise _lib.FpAmdError(f"{what}: workspace of {ws_bytes} bytes, {need} needed (mesh_icp_workspace)")
+        for k, t in out.items():
+            if _overlap(t, ws):
+                raise _lib.FpAmdError(f"{what}: out['{k}'] overlaps workspace")
+    for k in made:
+        if k not in out:
+            out[k] = torch.empty(shapes[k], dtype=_MESH_ICP_DTYPES[k], device=pts.device)
+    _lib.check(_lib.lib().fp_mesh_icp_step(_ptr(vp_), Nv, _ptr(fc), F, _ptr(pts), Q, _ptr(m), T, md, dmp, mp, _ptr(out["system"]),
+                                           _ptr(out["tfs_out"]), _ptr(out.get("dist2")), _ptr(out.get("face")), _ptr(ws), ws_bytes,
+                                           _stream(pts)), "fp_mesh_icp_step")
+    if names:
+        return out["tfs_out"], out["system"], {k: out[k] for k in names}
+    return out["tfs_out"], out["system"]
+
+
+class MeshAlignment(NamedTuple):
+    """a rigid registration of mesh a onto mesh b (reconstruct.align_meshes): `tf` (4,4) float64 maps a's coordinates into b's frame;
+    `mean_distance` / `rmse` the mean and the root mean square of the distances of a's samples to b's surface over the pairs, in the
+    meshes' unit; `overlap` the fraction of the samples that are pairs; `status` that of the last step at the winner (0 solved);
+    `runner_up` None, or a dict(tf, mean_distance, angle_deg) of the best other basin: its transform, its cost and its rotation angle
+    from the winner -- for a symmetric or nearly symmetric object its cost is the winner's, and the caller decides what that means."""
+    tf: np.ndarray
+    mean_distance: float
+    rmse: float
+    overlap: float
+    status: int
+    runner_up: Optional[dict]
+
+    def transfer_pose(self, ob_in_cam):
+        """the pose of b's frame given the pose(s) of a's frame ((4,4) or (n,4,4)): ob_in_cam @ inv(tf)"""
+        return np.asarray(ob_in_cam, dtype=np.float64) @ np.linalg.inv(self.tf)
 
 
 class DistanceStats(NamedTuple):
@@ -2157,6 +2262,7 @@ depth_agreement = _timed("fp_depth_agreement", depth_agreement)
 pose_errors = _timed("fp_pose_errors", pose_errors)
 mesh_point_distance = _timed("fp_mesh_point_distance", mesh_point_distance)
 mesh_transform_residuals = _timed("fp_mesh_transform_residuals", mesh_transform_residuals)
+mesh_icp_step = _timed("fp_mesh_icp_step", mesh_icp_step)
 icp_point_plane = _timed("fp_icp_point_plane", icp_point_plane)
 tsdf_components = _timed("fp_tsdf_label_components", tsdf_components)
 vsd_counts = _timed("fp_vsd_counts", vsd_counts)

@@ -551,7 +551,63 @@ def _thresholds(thresholds, unit, what):
     return thr
 
 
-def compare_meshes(a, b, samples=100_000, thresholds=None, seed=0, unit=None, device=None):
+def _rigid_tf(tf, what):
+    """tf= of compare_meshes: a (4,4) transform or an ops.MeshAlignment -> (4,4) float64"""
+    m = np.asarray(tf.tf if isinstance(tf, ops.MeshAlignment) else tf, dtype=np.float64)
+    if m.shape != (4, 4) or not np.isfinite(m).all():
+        raise ValueError(f"{what}: tf must be a finite (4,4) transform or a MeshAlignment, got shape {m.shape}")
+    return m
+
+
+def align_meshes(a, b, starts=300, samples=(128, 2048), iterations=(12, 20), max_dist=None, min_overlap=0.5, init=None, seed=0,
+                 device=None):
+    """Register mesh a onto mesh b with no initial guess -> ops.MeshAlignment: `tf` (4,4) float64 maps a's coordinates into b's frame
+    (one unit: no scale is estimated, and no reflection), with the mean and root-mean-square distance of a's samples to b's
+    surface, the fraction of them that found a pair, and `runner_up`, the best other basin (a symmetric or nearly symmetric object
+    has one of the same cost).  a, b: mesh-tensor dicts (pos, faces) or SimpleMeshes.  The direction is a's samples onto b's surface:
+    a fused mesh may lack its underside, a CAD model does not.  mesh_align.align has the recipe -- `starts` seeded rotations and the
+    identity, iterations[0] point-to-plane steps of all of them on samples[0] surface samples (sample_surface, seed + 1), the best
+    distinct basins refined by iterations[1] steps on samples[1] samples (seed) under a shrinking gate on the pair distance, never
+    above max_dist (None: no limit) -- and this function binds it to the device: every step of every candidate is one
+    ops.mesh_icp_step call (starts x samples x faces pair tests), the transforms ping-pong between two device tables and come back to
+    the host once per stage and per gate.  init: a (4,4) or (S,4,4) guess in the place of the starts (a local refinement).  A setup /
+    evaluation call: it reads the meshes back once and synchronises a handful of times."""
+    from . import mesh_align, symmetry
+    what = "align_meshes"
+    try:
+        n_coarse, n_fine = samples
+    except (TypeError, ValueError):
+        raise ValueError(f"{what}: samples must be two counts (coarse, fine), got {samples!r}") from None
+    n_coarse, n_fine = _check_count(n_coarse, what, "samples[0]"), _check_count(n_fine, what, "samples[1]")
+    if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or int(seed) < 0:
+        raise ValueError(f"{what}: seed must be an int >= 0, got {seed!r}")
+    if device is None:
+        device = next((m["pos"].device for m in (a, b) if isinstance(m, dict) and torch.is_tensor(m.get("pos"))), "cuda")
+    ta, tb = (dict(zip(("pos", "faces"), _mesh_arrays(m, device, what, name))) for m, name in ((a, "a"), (b, "b")))
+    pts = {"coarse": sample_surface(ta, n_coarse, int(seed) + 1)[0], "fine": sample_surface(ta, n_fine, int(seed))[0]}
+    centre_b, radius_b = symmetry.surface_centre(tb["pos"].cpu().numpy(), tb["faces"].cpu().numpy())
+    centre_a = pts["coarse"].double().mean(dim=0).cpu().numpy()
+    dev = tb["pos"].device
+
+    def steps(which, tfs, gate, n):
+        p = pts[which]
+        S, Q = len(tfs), int(p.shape[0])
+        cur = torch.as_tensor(np.ascontiguousarray(tfs, dtype=np.float32), device=dev)
+        nxt = torch.empty_like(cur)
+        system = torch.empty((S, 40), dtype=torch.float64, device=dev)
+        ws = ops.mesh_icp_workspace(S, Q, dev)
+        for _ in range(n):
+            ops.mesh_icp_step(p, cur, tb, max_dist=gate, out=dict(tfs_out=nxt, system=system), workspace=ws)
+            cur, nxt = nxt, cur
+        _, _, extra = ops.mesh_icp_step(p, cur, tb, max_dist=gate, want=("dist2",), out=dict(tfs_out=nxt, system=system), workspace=ws)
+        return cur.cpu().numpy().astype(np.float64), system.cpu().numpy(), extra["dist2"].cpu().numpy()
+
+    got = mesh_align.align(steps, centre_a, centre_b, radius_b, (n_coarse, n_fine), starts=starts, iterations=iterations,
+                           max_dist=max_dist, min_overlap=min_overlap, init=init, seed=int(seed))
+    return ops.MeshAlignment(*(got[k] for k in ops.MeshAlignment._fields))
+
+
+def compare_meshes(a, b, samples=100_000, thresholds=None, seed=0, unit=None, device=None, tf=None):
     """How good is mesh a (what was built) against mesh b (the reference) -> ops.MeshComparison: accuracy (the exact distances of
     `samples` surface samples of a to the surface of b: mean / median / p99 / max), completeness (b's samples to a's surface), the
     chamfer distance (the mean of the two means), the Hausdorff distance of the samples, and per threshold precision, recall and
@@ -559,13 +615,18 @@ def compare_meshes(a, b, samples=100_000, thresholds=None, seed=0, unit=None, de
     unit.  thresholds: lengths; None: DEFAULT_THRESHOLD_UNITS times unit= (for example the voxel pitch of the fusion).  The samples
     are sample_surface's (seed), the distances ops.mesh_point_distance's: brute force, samples x faces pair tests in each direction.
     A setup / evaluation call, and it synchronises: sample_surface reads each mesh back once for its float64 area table, and the two
-    distance arrays are read once at the end for the statistics (float64 on the host)."""
+    distance arrays are read once at the end for the statistics (float64 on the host).  tf: a (4,4) transform or an
+    ops.MeshAlignment (align_meshes) that takes a's coordinates into b's frame, applied to a's vertices (in float64, rounded once)
+    before anything is sampled; None: the meshes are in one frame already."""
     what = "compare_meshes"
     samples = _check_count(samples, what, "samples")
     thr = _thresholds(thresholds, unit, what)
     if device is None:
         device = next((m["pos"].device for m in (a, b) if isinstance(m, dict) and torch.is_tensor(m.get("pos"))), "cuda")
     ta, tb = (dict(zip(("pos", "faces"), _mesh_arrays(m, device, what, name))) for m, name in ((a, "a"), (b, "b")))
+    if tf is not None:
+        m = torch.as_tensor(_rigid_tf(tf, what), device=ta["pos"].device)
+        ta["pos"] = (ta["pos"].double() @ m[:3, :3].T + m[:3, 3]).float().contiguous()
     pa, _ = sample_surface(ta, samples, seed)
     pb, _ = sample_surface(tb, samples, seed)
     # the square root through float64: the correctly rounded float32 root whatever the device's float32 sqrt does in its last bit

@@ -100,8 +100,10 @@ const char* fp_last_error(void);
  *   230 -> 231: + fp_mesh_point_distance, fp_mesh_point_distance_workspace_bytes (additions only): the exact distance from points to
  *               the surface of a triangle mesh, with the nearest face and the closest point.
  *   231 -> 232: + fp_mesh_transform_residuals, fp_mesh_transform_residuals_workspace_bytes (additions only): how far each of T
- *               candidate transforms moves a mesh's surface samples off the surface, for detecting its rotational symmetries. */
-#define FP_AMD_ABI_VERSION 232
+ *               candidate transforms moves a mesh's surface samples off the surface, for detecting its rotational symmetries.
+ *   232 -> 233: + fp_mesh_icp_step, fp_mesh_icp_workspace_bytes (additions only): one Gauss-Newton step of point-to-plane ICP for each
+ *               of T candidate transforms of a mesh's surface samples against another mesh, for registering one onto the other. */
+#define FP_AMD_ABI_VERSION 233
 int fp_version(void);
 
 /* Utils.py:104-130 make_mesh_tensors: records caller-owned device tensors.
@@ -357,6 +359,51 @@ int fp_mesh_transform_residuals(const float* pos /*dev Nv,3*/, int Nv, const int
                                 const float* thr2 /*dev L | NULL when L == 0*/, int L /*0..4*/,
                                 float* max_d2 /*dev T*/, int32_t* over /*dev T,L|NULL*/, float* dist2 /*dev T,Q|NULL*/,
                                 void* workspace /*dev*/, size_t workspace_bytes, void* stream);
+
+/* Register one mesh onto another: ONE Gauss-Newton step of point-to-plane ICP for each of T candidate transforms of Q points (surface
+ * samples of a mesh a) against the surface of a triangle mesh b (pos, faces), in four launches.  Defined to the operation.
+ * Per pair (t, i), float32, one rounding per operation, without contraction, every 3-term sum as (a0*b0 + a1*b1) + a2*b2:
+ *   p = the point as fp_mesh_transform_residuals forms it: p[k] = ((rk[0]*x + rk[1]*y) + rk[2]*z) + rk[3] per row rk of tfs_in[t];
+ *       row 3 is not read;
+ *   (dd, f, q) = exactly fp_mesh_point_distance's dist2, face and closest for the query p: the smallest (dd, face) wins, by that
+ *       function's closest-point walk (one copy of the code, csrc/mesh_closest.h); (+inf, -1, -) where no triangle answers;
+ *   the normal of face f with ab = b - a, ac = c - a:  n = ab x ac = (ab1*ac2 - ab2*ac1, ab2*ac0 - ab0*ac2, ab0*ac1 - ab1*ac0) in
+ *       float32;  nn = (n0*n0 + n1*n1) + n2*n2 in float64 of the widened components;  m_k = (float)((double)n_k / sqrt(nn)) (the
+ *       float64 division and square root are correctly rounded);
+ *   e = q - p;   r = m.e;   a = p - c with c = (tfs_in[t][3], [7], [11]);
+ *   J = (a1*m2 - a2*m1, a2*m0 - a0*m2, a0*m1 - a1*m0, m0, m1, m2): the convention of fp_icp_point_plane, the step rotates about the
+ *       transform's own origin, p' = c + dR(w) (p - c) + v;
+ *   pair = f >= 0 && nn > 0 && m0, m1, m2 finite && dd <= max_dist * max_dist (the product in float32; it may be +inf).  A NaN
+ *       anywhere makes it no pair.
+ * dist2[t*Q + i] = dd and face[t*Q + i] = f, where asked for, are written for every (t, i), pair or not.
+ * Per transform, float64: the 28 sums of fp_icp_point_plane (A = sum J^T J, its 21 upper entries; b = sum J^T r; sum r*r), the pair
+ * count, and the sum of dd over the pairs (each dd widened), every term exact.  The sums run over chunks of 256 consecutive samples,
+ * inside a chunk over 4 waves of 64: within a wave by the xor tree (s += s of lane ^ 32, ^ 16, ^ 8, ^ 4, ^ 2, ^ 1; a sample that is no
+ * pair adds +0), the waves in index order, then the chunks in index order starting from +0 (one copy of the code with
+ * fp_icp_point_plane, csrc/icp_solve.h).  The order depends on Q alone and there are no floating-point atomics (the nearest face is
+ * merged with 64-bit integer atomic minima on (bits(dd) << 32) | f): row t has the same bits alone, in any batch, in any order of
+ * tfs_in, under any chunking of the faces and on every replay.
+ * Solve, status and update exactly as fp_icp_point_plane defines them, with tfs_in in the place of poses_in: damping on diag(A), LDL^T
+ * without pivoting, status 0 solved / 1 fewer than min_pairs pairs / 2 a non-finite tfs_in row (all 16), a pivot <= 0 or not finite
+ * or a non-finite x; Rodrigues in float64, R' = dR * R_in, t' = t_in + v, each rounded once to float32, row 3 copied; for status != 0,
+ * x = 0 and the tfs_out row is the tfs_in row bit for bit.
+ * system[t] (float64 x 40): fp_icp_point_plane's layout, [0..20] A's upper triangle row-major, [21..26] b, [27] sum r*r, [28] pairs,
+ * [29] status, [30..35] x, and [36] the sum of dd over the pairs, [37..39] 0.  The sums are reported whatever the status.
+ * tfs_out, dist2 and face may be NULL (not wanted); tfs_in and tfs_out must not overlap.  T == 0 does nothing.  Q == 0 or F == 0 gives
+ * zero sums and no pair (status 1, or 2 for a non-finite row) and tfs_out = tfs_in; with F == 0, dist2 = +inf and face = -1.
+ * T * Q * F pair tests: the cost is the caller's to weigh.  No allocation, no memset, no host synchronisation (graph-capturable);
+ * nothing is written outside the outputs and the workspace (fp_mesh_icp_workspace_bytes(T, Q) bytes = 8 * T * Q for the keys and 256
+ * per (transform, chunk of 256 samples), 8-byte aligned; 0 when T <= 0 or Q <= 0).  Argument errors (FP_ERR_INVALID_ARG), before
+ * any launch, each message beginning with the entry point's name: T, Q, F or Nv negative; T * Q, T or F above 2^30; max_dist or
+ * damping negative or not finite; min_pairs < 6; and with T > 0: NULL tfs_in or system; with Q > 0 also NULL points, NULL faces with
+ * F > 0, NULL pos with Nv > 0 and F > 0, a workspace that is NULL, too small or misaligned; tfs_in overlapping tfs_out. */
+size_t fp_mesh_icp_workspace_bytes(int T, int Q);
+int fp_mesh_icp_step(const float* pos /*dev Nv,3*/, int Nv, const int32_t* faces /*dev F,3*/, int F,
+                     const float* points /*dev Q,3*/, int Q,
+                     const float* tfs_in /*dev T,4,4 row-major*/, int T, float max_dist, double damping, int min_pairs,
+                     double* system /*dev T,40*/, float* tfs_out /*dev T,16|NULL*/,
+                     float* dist2 /*dev T,Q|NULL*/, int32_t* face /*dev T,Q|NULL*/,
+                     void* workspace /*dev*/, size_t workspace_bytes, void* stream);
 
 /* An object's mesh from posed RGB-D reference views: truncated-signed-distance (TSDF) fusion into a caller-owned volume, then marching
  * tetrahedra.  The volume has nz x ny x nx voxels; voxel (ix, iy, iz) has the linear index i = (iz * ny + iy) * nx + ix and, in the

@@ -12,7 +12,9 @@ such a directory from the can first; `--ref_texture T` bakes a texture atlas of 
 its MTL and the texture as a PNG; `--compare_mesh PATH` (with the reference views) compares the fused mesh with the mesh file PATH, in the
 frame of the views' poses -- `--compare_mesh synthetic` with --synthetic_ref_views takes the can the views were rendered from -- and
 prints the report (reconstruct.compare_meshes: accuracy, completeness, chamfer, Hausdorff, precision / recall / F-score at 0.5, 1, 2 and
-4 voxel pitches) as one JSON line {"compare_mesh": ...}; `--detect_symmetry` finds the rotational symmetries of the mesh that is used,
+4 voxel pitches) as one JSON line {"compare_mesh": ...}; `--align_mesh` with it registers the fused mesh onto that mesh first
+(reconstruct.align_meshes: the mesh file may then be in any frame of the same unit), prints the alignment as one JSON line
+{"align_mesh": ...} and compares in the aligned frame; `--detect_symmetry` finds the rotational symmetries of the mesh that is used,
 registers with the rotation grid clustered by them and prints the axes as one JSON line {"detect_symmetry": ...}."""
 import argparse
 import logging
@@ -109,10 +111,15 @@ def main(argv=None):
                     help="with --ref_views: compare the fused mesh with this mesh file (or 'synthetic': the can of --synthetic_ref_views) "
                          "and print the report as one JSON line")
     ap.add_argument("--compare_samples", type=int, default=100_000, help="surface samples per mesh for --compare_mesh")
+    ap.add_argument("--align_mesh", action="store_true",
+                    help="with --compare_mesh: register the fused mesh onto that mesh first (reconstruct.align_meshes: the two need not be "
+                         "in one frame), print the alignment as one JSON line and compare in the aligned frame")
     ap.add_argument("--detect_symmetry", action="store_true",
                     help="find the mesh's rotational symmetries (FoundationPose.detect_symmetries), use them for the rotation grid and "
                          "print the axes as one JSON line")
     args = ap.parse_args(argv)
+    if args.align_mesh and not args.compare_mesh:
+        ap.error("--align_mesh needs --compare_mesh PATH (the mesh to register onto)")
     logging.basicConfig(level=logging.INFO, format="[%(funcName)s()] %(message)s")
 
     from foundationpose_amd import dr
@@ -157,10 +164,21 @@ def main(argv=None):
         if args.compare_mesh:
             import json
             from foundationpose_amd.mesh import make_can_mesh
-            from foundationpose_amd.reconstruct import compare_meshes
+            from foundationpose_amd.reconstruct import align_meshes, compare_meshes
             truth = make_can_mesh() if args.compare_mesh == "synthetic" else load_mesh(args.compare_mesh)
-            report = compare_meshes(fused, truth, samples=args.compare_samples, unit=mesh.voxel, device=dev).as_dict()
+            alignment = None
+            if args.align_mesh:
+                alignment = align_meshes(fused, truth, device=dev)
+                ru = alignment.runner_up
+                print(json.dumps({"align_mesh": dict(
+                    tf=alignment.tf.tolist(), mean_distance_m=alignment.mean_distance, rmse_m=alignment.rmse, overlap=alignment.overlap,
+                    status=alignment.status, runner_up=None if ru is None else dict(
+                        tf=ru["tf"].tolist(), mean_distance_m=ru["mean_distance"], rmse_m=float(np.sqrt(ru["cost"])), angle_deg=ru["angle_deg"]))}),
+                      flush=True)
+            report = compare_meshes(fused, truth, samples=args.compare_samples, unit=mesh.voxel, device=dev, tf=alignment).as_dict()
             report.update(unit_m=mesh.voxel, faces=[len(mesh.faces), len(truth.faces)])
+            if alignment is not None:
+                report.update(aligned=True)
             print(json.dumps({"compare_mesh": report}), flush=True)
     else:
         mesh = load_mesh(args.mesh_file)
