@@ -10,7 +10,7 @@ import torch  # noqa: F401  (must precede CDLL: shares the HIP runtime with PyTo
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("FP_AMD_LIB") or os.path.join(_HERE, "csrc", "libfp_amd.so")   # FP_AMD_LIB: A/B builds
-ABI_VERSION = 233   # = FP_AMD_ABI_VERSION of include/fp_amd.h (tests/test_abi.py keeps the two in step)
+ABI_VERSION = 234   # = FP_AMD_ABI_VERSION of include/fp_amd.h (tests/test_abi.py keeps the two in step)
 _lib = None
 
 vp, ci, cf, cd, sz = C.c_void_p, C.c_int, C.c_float, C.c_double, C.c_size_t
@@ -45,6 +45,11 @@ SIGNATURES = {
     "fp_mesh_transform_residuals": (ci, [vp, ci, vp, ci, vp, ci, vp, ci, vp, ci, vp, vp, vp, vp, sz, vp]),
     "fp_mesh_icp_workspace_bytes": (sz, [ci, ci]),
     "fp_mesh_icp_step": (ci, [vp, ci, vp, ci, vp, ci, vp, ci, cf, cd, ci, vp, vp, vp, vp, vp, sz, vp]),
+    "fp_mesh_pseudonormals": (ci, [vp, ci, vp, ci, vp, vp, vp]),
+    "fp_mesh_signed_distance_workspace_bytes": (sz, [ci]),
+    "fp_mesh_signed_distance": (ci, [vp, ci, vp, ci, vp, vp, vp, ci, vp, vp, vp, vp, vp, vp, sz, vp]),
+    "fp_mesh_penetration_workspace_bytes": (sz, [ci, ci]),
+    "fp_mesh_penetration": (ci, [vp, ci, vp, ci, vp, vp, vp, ci, vp, ci, vp, vp, vp, vp, vp, vp, sz, vp]),
     "fp_tsdf_integrate": (ci, [vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, vp, cf, cf, cf, vp, vp, vp, vp, vp]),
     "fp_tsdf_count_triangles": (ci, [vp, vp, ci, ci, ci, cf, vp, vp]),
     "fp_tsdf_emit_triangles": (ci, [vp, vp, vp, vp, ci, ci, ci, vp, cf, cf, vp, C.c_longlong, vp, vp, vp, vp, vp]),

@@ -1,7 +1,8 @@
 // The closest point of a triangle to a point, and how a workgroup passes a mesh's triangles through LDS: the one copy that
-// mesh_distance.hip (fp_mesh_point_distance) and mesh_symmetry.hip (fp_mesh_transform_residuals) share.  The definition, down to the
-// float32 operation, is in include/fp_amd.h; both files are compiled with -ffp-contract=off (SRCS_EXACT), so the operations written
-// here are the ones executed and the two entry points give the same bits for the same (point, triangle) pair.
+// mesh_distance.hip (fp_mesh_point_distance), mesh_symmetry.hip (fp_mesh_transform_residuals), mesh_icp.hip (fp_mesh_icp_step) and
+// mesh_signed.hip (fp_mesh_signed_distance, fp_mesh_penetration) share.  The definition, down to the float32 operation, is in
+// include/fp_amd.h; the files are compiled with -ffp-contract=off (SRCS_EXACT), so the operations written here are the ones executed
+// and the entry points give the same bits for the same (point, triangle) pair.
 #pragma once
 #include "fp_common.h"
 
@@ -15,7 +16,13 @@ __device__ __forceinline__ float dot(const v3& a, const v3& b) { return (a.x * b
 // The closest point of triangle (a, b, c) to p and its squared distance: include/fp_amd.h, Ericson 5.1.5.  The region tests r1..r6
 // are the book's, each taken only when none before it held; one division serves whichever region was chosen (numerator and
 // denominator selected first), so every value that reaches the result is made by the operations the definition names.
-__device__ __forceinline__ float closest_point(const v3& p, const v3& a, const v3& b, const v3& c, const v3& ab, const v3& ac, v3& q) {
+// `feature` is the part of the triangle q lies on: 0, 1, 2 vertex a, b, c (r1, r2, r4); 3, 4, 5 edge ab, bc, ca (r3, r6, r5); 6 the
+// interior (r7).  It is selected from the region flags alone and takes part in no float operation: closest_point, which drops it,
+// and closest_point_feature give the same q and the same dd.
+constexpr int kFeatureInterior = 6;
+
+__device__ __forceinline__ float closest_point_feature(const v3& p, const v3& a, const v3& b, const v3& c, const v3& ab, const v3& ac,
+                                                       v3& q, int& feature) {
   const v3 ap = sub(p, a);
   const float d1 = dot(ab, ap), d2 = dot(ac, ap);
   const v3 bp = sub(p, b);
@@ -49,8 +56,19 @@ __device__ __forceinline__ float closest_point(const v3& p, const v3& a, const v
   const float w = vc * t;
   const v3 in{e1.x + w * ac.x, e1.y + w * ac.y, e1.z + w * ac.z};
   q = r1 ? a : r2 ? b : r4 ? c : r7 ? in : e1;
+  feature = r1 ? 0 : r2 ? 1 : r4 ? 2 : r3 ? 3 : r6 ? 4 : r5 ? 5 : kFeatureInterior;
   const v3 d = sub(p, q);
   return dot(d, d);
+}
+
+__device__ __forceinline__ float closest_point(const v3& p, const v3& a, const v3& b, const v3& c, const v3& ab, const v3& ac, v3& q) {
+  int feature;
+  return closest_point_feature(p, a, b, c, ab, ac, q, feature);
+}
+
+// ab x ac in float32, each component one difference of two products: (ab1*ac2 - ab2*ac1, ab2*ac0 - ab0*ac2, ab0*ac1 - ab1*ac0)
+__device__ __forceinline__ v3 cross(const v3& ab, const v3& ac) {
+  return v3{ab.y * ac.z - ab.z * ac.y, ab.z * ac.x - ab.x * ac.z, ab.x * ac.y - ab.y * ac.x};
 }
 
 __device__ __forceinline__ v3 load3(const float* p) { return v3{p[0], p[1], p[2]}; }
@@ -93,6 +111,36 @@ __device__ __forceinline__ float staged_distance2(const v3& p, const float4* __r
   v3 q;
   return closest_point(p, v3{t0.x, t0.y, t0.z}, v3{t0.w, t1.x, t1.y}, v3{t1.z, t1.w, t2.x}, v3{t2.y, t2.z, t2.w},
                        v3{t3.x, t3.y, t3.z}, q);
+}
+
+// The scan of one (lane tile, chunk of faces) workgroup, each lane holding its own query p: faces f0..f1-1 pass through LDS in tiles
+// of kTile (= the workgroup's size: one staging pass) and every lane keeps the smallest (dd, face) -- faces ascend, so `<` keeps the
+// smaller index on a tie.  best / best_f come in as +inf / -1.  Every thread of the workgroup calls it (barriers inside).
+template <int kTile>
+__device__ __forceinline__ void scan_chunk(const v3& p, float4* __restrict__ tile, const float* __restrict__ pos, int Nv,
+                                           const int32_t* __restrict__ faces, int f0, int f1, int tid, float& best, int& best_f) {
+  for (int base = f0; base < f1; base += kTile) {
+    const int cnt = min(kTile, f1 - base);
+    __syncthreads();                                  // the previous tile has been read by every wave
+    if (tid < cnt) stage_triangle(tile, tid, pos, Nv, faces, base + tid);
+    __syncthreads();
+    // (the loop vectoriser would pair two triangles into packed-fp32 instructions, which this library is built without: Makefile)
+#pragma clang loop vectorize(disable) interleave(disable) unroll_count(2)
+    for (int k = 0; k < cnt; ++k) {
+      const float dd = staged_distance2(p, tile, k);
+      // dd < best holds for no NaN and no +inf (best starts at +inf): exactly the candidates with dd <= FLT_MAX that improve
+      const bool better = dd < best;
+      best = better ? dd : best;
+      best_f = better ? base + k : best_f;
+    }
+  }
+}
+
+// the key of a lane's (dd, face): non-negative floats order as their bits do, so a 64-bit integer minimum picks the smallest (dd, face)
+constexpr unsigned long long kNoAnswer = ~0ull;
+__device__ __forceinline__ void merge_answer(unsigned long long* __restrict__ key, float best, int best_f) {
+  const unsigned long long k = ((unsigned long long)__float_as_uint(best) << 32) | (unsigned)best_f;
+  __hip_atomic_fetch_min(key, k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
 // faces per chunk for a grid of `tiles` lane tiles: a multiple of `tile`, at least `chunk_min`, and no smaller than what gives about

@@ -30,7 +30,6 @@ constexpr int kThreads = 256;          // queries per workgroup, one per lane
 constexpr int kTile = 256;             // triangles per LDS tile: 4 float4 each, 16 KiB
 constexpr int kChunkMin = 1024;        // the fewest faces a workgroup scans (unless the mesh has fewer)
 constexpr int kFillWorkgroups = 2048;  // workgroups wanted in flight (256 CUs x 8 of 4 waves)
-constexpr unsigned long long kNoAnswer = ~0ull;
 
 static_assert(kChunkMin % kTile == 0, "a chunk is whole tiles");
 static_assert(kTile == kThreads, "a tile is staged by one pass of the workgroup");
@@ -55,25 +54,8 @@ __global__ __launch_bounds__(kThreads) void k_md_scan(const float* __restrict__ 
   const int f1 = min(F, f0 + chunk);
   float best = __builtin_inff();
   int best_f = -1;
-  for (int base = f0; base < f1; base += kTile) {
-    const int cnt = min(kTile, f1 - base);
-    __syncthreads();                                  // the previous tile has been read by every wave
-    if (tid < cnt) stage_triangle(tile, tid, pos, Nv, faces, base + tid);
-    __syncthreads();
-    // (the loop vectoriser would pair two triangles into packed-fp32 instructions, which this library is built without: Makefile)
-#pragma clang loop vectorize(disable) interleave(disable) unroll_count(2)
-    for (int k = 0; k < cnt; ++k) {
-      const float dd = staged_distance2(p, tile, k);
-      // dd < best holds for no NaN and no +inf (best starts at +inf): exactly the candidates with dd <= FLT_MAX that improve
-      const bool better = dd < best;
-      best = better ? dd : best;
-      best_f = better ? base + k : best_f;
-    }
-  }
-  if (live && best_f >= 0) {
-    const unsigned long long key = ((unsigned long long)__float_as_uint(best) << 32) | (unsigned)best_f;
-    __hip_atomic_fetch_min(keys + i, key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
+  scan_chunk<kTile>(p, tile, pos, Nv, faces, f0, f1, tid, best, best_f);   // mesh_closest.h: the one copy
+  if (live && best_f >= 0) merge_answer(keys + i, best, best_f);
 }
 
 __global__ __launch_bounds__(kThreads) void k_md_finish(const float* __restrict__ pos, int Nv, const int32_t* __restrict__ faces,

@@ -94,7 +94,7 @@ class FoundationPose:
         if mesh_tensors is None:
             self.mesh_tensors = make_mesh_tensors(self.mesh, device=self.device)
         else:
-            t = {k: v.to(self.device) for k, v in mesh_tensors.items() if k != "_handle"}
+            t = {k: v.to(self.device) for k, v in mesh_tensors.items() if k not in ("_handle", "pseudonormals")}   # of the uncentred mesh
             center = torch.as_tensor(self.model_center, dtype=torch.float64, device=self.device)
             t["pos"] = (t["pos"].double() - center).float()        # the host's float64 subtraction, rounded once
             t["_handle"] = mesh_handle_from_tensors(t)
@@ -145,6 +145,7 @@ class FoundationPose:
             if torch.is_tensor(self.mesh_tensors[k]):
                 self.mesh_tensors[k] = self.mesh_tensors[k].to(s)
         self.mesh_tensors.pop("_handle", None)  # rebuilt lazily against the moved tensors
+        self.mesh_tensors.pop("pseudonormals", None)  # ops.mesh_pseudonormals' tables: made again on the new device when asked for
         if self.refiner is not None:
             self.refiner.model.to(s)
         if self.scorer is not None:
@@ -263,6 +264,34 @@ class FoundationPose:
         if unit is None and thresholds is None:
             unit = getattr(self.mesh_ori, "voxel", None)
         return compare_meshes(self.mesh_ori, mesh, samples=samples, thresholds=thresholds, seed=seed, unit=unit, device=self.device, tf=tf)
+
+    def penetration_into(self, other, poses=None, samples=2048, seed=0, allow_open=False):
+        """How far this object, at `poses`, reaches into the object of estimator `other` at other.pose_last (not in the reference)
+        -> ops.Penetration with one row per pose: `inside` the share of this object's `samples` surface samples (sample_surface,
+        seed) that lie inside other's mesh, `depth` the distance in metres of the deepest of them to other's surface (0 when none is
+        inside), `deepest` that sample in the frame of the mesh handed to this estimator's reset_object (NaN when none).  poses: (4,4)
+        or (N,4,4) in the centred-mesh frame like pose_last, for example the hypotheses of a registration; None: pose_last.  Both
+        poses are of centred meshes and both mesh tensors are centred, so the samples move by inv(other.pose_last) @ pose (float64 on
+        the host, rounded once) with no centring transform; the deepest sample alone is moved back by model_center.  One
+        ops.mesh_penetration call (N x samples x other's faces pair tests).  other's mesh must be closed (ops.mesh_pseudonormals,
+        computed once and kept in other.mesh_tensors) unless allow_open=True.  An evaluation call (it synchronises)."""
+        from .reconstruct import sample_surface
+        what = "penetration_into"
+        if not isinstance(other, FoundationPose):
+            raise ValueError(f"{what}: other must be a FoundationPose, got {type(other).__name__}")
+        if other.pose_last is None:
+            raise RuntimeError(f"{what}: the other estimator has no pose yet (register or track it first)")
+        if poses is None:
+            poses = self.pose_last
+            if poses is None:
+                raise RuntimeError(f"{what}: no pose yet (register or track first, or pass poses)")
+        host = lambda p: (p.detach().cpu().numpy() if torch.is_tensor(p) else np.asarray(p)).astype(np.float64).reshape(-1, 4, 4)   # noqa: E731
+        tfs = np.linalg.inv(host(other.pose_last)[0]) @ host(poses)
+        dev = other.mesh_tensors["pos"].device
+        pts, _ = sample_surface(dict(pos=self.mesh_tensors["pos"], faces=self.mesh_tensors["faces"]), samples, seed)
+        got = ops.mesh_penetration(pts.to(dev), torch.as_tensor(tfs.astype(np.float32), device=dev).contiguous(), other.mesh_tensors,
+                                   allow_open=allow_open)
+        return ops.Penetration.rows(got, pts, self.model_center)
 
     # the depth maps bop_errors holds at a time: 48 MiB = 40 full 480 x 640 float32 frames.  Small against the 256 MiB last-level cache,
     # so a chunk's renders are still on the chip when the counting kernel reads them, and large enough that the raster launches of a
@@ -623,6 +652,18 @@ def depth_polish(estimators, depths, Ks, views=None, iterations=3, max_dist=0.02
     for k, e in enumerate(ests):
         e.pose_last = out[k:k + 1]
     return ops.IcpStep.rows(system)
+
+
+def penetrations(estimators, samples=2048, seed=0, allow_open=False):
+    """penetration_into over every ordered pair of the estimators at their current pose_last -> {(i, j): ops.Penetration}: how far
+    object i reaches into object j.  Two objects tracked or registered into each other show up as a non-zero share in one direction
+    at least.  The estimators need not share a refiner; everybody needs a pose_last.  One ops.mesh_penetration call per pair."""
+    ests = list(estimators)
+    for i, e in enumerate(ests):
+        if e.pose_last is None:
+            raise RuntimeError(f"penetrations: estimator {i} has no pose yet (register or track it first)")
+    return {(i, j): a.penetration_into(b, samples=samples, seed=seed, allow_open=allow_open)
+            for i, a in enumerate(ests) for j, b in enumerate(ests) if i != j}
 
 
 def translation_from_stats(K, box, n, lo, hi):

@@ -1041,6 +1041,222 @@ def mesh_icp_step(points, tfs, mesh_tensors=None, pos=None, faces=None, *, max_d
     return out["tfs_out"], out["system"]
 
 
+MESH_REPORT_FIELDS = ("edges", "boundary", "nonmanifold", "inconsistent", "degenerate", "welded", "closed")
+
+
+class MeshPseudonormals(NamedTuple):
+    """fp_mesh_pseudonormals of a mesh: `vn` (Nv,3) f32 and `en` (F,3,3) f32 on the mesh's device, `report` (8,) int32 on the host
+    (MESH_REPORT_FIELDS, then a zero)."""
+    vn: torch.Tensor
+    en: torch.Tensor
+    report: np.ndarray
+
+    @property
+    def closed(self):
+        return bool(self.report[6])
+
+    def describe(self):
+        return ", ".join(f"{k}={int(v)}" for k, v in zip(MESH_REPORT_FIELDS, self.report))
+
+
+def mesh_pseudonormals(mesh_tensors=None, pos=None, faces=None):
+    """fp_mesh_pseudonormals: the angle-weighted pseudonormals of a mesh's vertices and face edges and the report of what keeps it from
+    being closed -> MeshPseudonormals (include/fp_amd.h has the definition; float64 on the host, adjacency by vertex position).  The
+    mesh is mesh_tensors (a dict with pos (Nv,3) f32 and faces (F,3) int32) or pos= and faces=, on any device; the tables come back on
+    that device.  A setup call: it copies the mesh to the host and synchronises.  With mesh_tensors the result is kept in the dict
+    under "pseudonormals" and returned from there the next time: the caller drops the key when pos or faces change."""
+    what = "mesh_pseudonormals"
+    if mesh_tensors is not None and pos is None and faces is None and isinstance(mesh_tensors.get("pseudonormals"), MeshPseudonormals):
+        return mesh_tensors["pseudonormals"]
+    pos, faces = _mesh_pos_faces(what, mesh_tensors, pos, faces)
+    for name, t, dt in (("pos", pos, torch.float32), ("faces", faces, torch.int32)):
+        if not torch.is_tensor(t):
+            raise _lib.FpAmdError(f"{what}: {name} must be a tensor, got {type(t).__name__}")
+        if t.dim() != 2 or int(t.shape[1]) != 3:
+            raise _lib.FpAmdError(f"{what}: {name} must be (n,3), got {tuple(t.shape)}")
+        if t.dtype != dt:
+            raise _lib.FpAmdError(f"{what}: {name} must be {dt}, got {t.dtype}")
+    Nv, F = int(pos.shape[0]), int(faces.shape[0])
+    if max(Nv, F) > (1 << 30):
+        raise _lib.FpAmdError(f"{what}: {Nv} vertices and {F} faces (at most 2^30 of either)")
+    hp = np.ascontiguousarray(pos.detach().cpu().numpy())
+    hf = np.ascontiguousarray(faces.detach().cpu().numpy())
+    vn, en, report = np.zeros((Nv, 3), np.float32), np.zeros((F, 3, 3), np.float32), np.zeros(8, np.int32)
+    _lib.check(_lib.lib().fp_mesh_pseudonormals(hp.ctypes.data if Nv else None, Nv, hf.ctypes.data if F else None, F,
+                                                vn.ctypes.data if Nv else None, en.ctypes.data if F else None, report.ctypes.data),
+               "fp_mesh_pseudonormals")
+    out = MeshPseudonormals(torch.from_numpy(vn).to(pos.device), torch.from_numpy(en).to(pos.device), report)
+    if mesh_tensors is not None:
+        mesh_tensors["pseudonormals"] = out
+    return out
+
+
+def _mesh_tables(what, mesh_tensors, pos, faces, tables, allow_open):
+    """the pseudonormal tables of a signed call (given, cached in mesh_tensors, or computed now), refused for a mesh that is not closed"""
+    if tables is None:
+        tables = mesh_pseudonormals(mesh_tensors) if mesh_tensors is not None else mesh_pseudonormals(pos=pos, faces=faces)
+    if not isinstance(tables, MeshPseudonormals):
+        raise _lib.FpAmdError(f"{what}: tables must be a MeshPseudonormals (mesh_pseudonormals), got {type(tables).__name__}")
+    if not tables.closed and not allow_open:
+        raise _lib.FpAmdError(f"{what}: the mesh is not closed ({tables.describe()}): inside and outside are not defined.  "
+                              f"allow_open=True gives the side of the nearest face instead")
+    return tables
+
+
+def _signed_call(what, known, dtypes, want, points, tfs, mesh_tensors, pos, faces, tables, allow_open, out, always):
+    """the argument checks that mesh_signed_distance and mesh_penetration share -> (names, pts, m, vp_, fc, vn, en, out, sizes)"""
+    names = (want,) if isinstance(want, str) else tuple(want)
+    for w in names:
+        if w not in known:
+            raise ValueError(f"{what}: unknown name {w!r} in want (known: {list(known)})")
+    names = tuple(n for n in known if n in names or n in always)
+    pos, faces = _mesh_pos_faces(what, mesh_tensors, pos, faces)
+    for name, t in (("points", points), ("pos", pos), ("faces", faces)):
+        if not torch.is_tensor(t):
+            raise _lib.FpAmdError(f"{what}: {name} must be a tensor, got {type(t).__name__}")
+        if t.dim() != 2 or int(t.shape[1]) != 3:
+            raise _lib.FpAmdError(f"{what}: {name} must be (n,3), got {tuple(t.shape)}")
+    T = None
+    if tfs is not None or what == "mesh_penetration":
+        if not torch.is_tensor(tfs):
+            raise _lib.FpAmdError(f"{what}: tfs must be a tensor, got {type(tfs).__name__}")
+        if tfs.dim() != 3 or tuple(tfs.shape[1:]) != (4, 4):
+            raise _lib.FpAmdError(f"{what}: tfs must be (T,4,4), got {tuple(tfs.shape)}")
+        T = int(tfs.shape[0])
+    Q, Nv, F = int(points.shape[0]), int(pos.shape[0]), int(faces.shape[0])
+    if (T or 1) * Q > (1 << 30) or max(T or 0, Q, F) > (1 << 30):
+        raise _lib.FpAmdError(f"{what}: {T or 1} x {Q} points against {F} faces (at most 2^30 pairs, transforms, points or faces)")
+    tables = _mesh_tables(what, mesh_tensors, pos if mesh_tensors is None else None, faces if mesh_tensors is None else None, tables,
+                          allow_open)
+    if tuple(tables.vn.shape) != (Nv, 3) or tuple(tables.en.shape) != (F, 3, 3):
+        raise _lib.FpAmdError(f"{what}: the tables are of another mesh: vn {tuple(tables.vn.shape)}, en {tuple(tables.en.shape)} for "
+                              f"{Nv} vertices and {F} faces")
+    shapes = ({"dist2": (Q,), "face": (Q,), "closest": (Q, 3), "feature": (Q,), "sign": (Q,)} if T is None else
+              {"inside": (T,), "depth2": (T,), "deepest": (T,), "sign": (T, Q), "dist2": (T, Q)})
+    out = dict(out or {})
+    for k, t in out.items():
+        if k not in names:
+            raise _lib.FpAmdError(f"{what}: out has '{k}', which is not among the wanted outputs {list(names)}")
+        if not torch.is_tensor(t) or tuple(t.shape) != shapes[k]:
+            raise _lib.FpAmdError(f"{what}: out['{k}'] must be a tensor of shape {shapes[k]}, got "
+                                  f"{tuple(t.shape) if torch.is_tensor(t) else type(t).__name__}")
+    pts = _dev(points, torch.float32, "points")
+    m = _dev(tfs, torch.float32, "tfs") if T is not None else None
+    vp_ = _dev(pos, torch.float32, "pos")
+    fc = _dev(faces, torch.int32, "faces")
+    vn = _dev(tables.vn, torch.float32, "tables.vn")
+    en = _dev(tables.en, torch.float32, "tables.en")
+    for k in list(out):
+        out[k] = _dev(out[k], dtypes[k], f"out['{k}']")
+    srcs = [("points", pts), ("pos", vp_), ("faces", fc), ("tables.vn", vn), ("tables.en", en)] + ([("tfs", m)] if m is not None else [])
+    for k, t in out.items():
+        for name, src in srcs:
+            if _overlap(t, src):
+                raise _lib.FpAmdError(f"{what}: out['{k}'] overlaps {name}")
+        for k2, t2 in out.items():
+            if k2 < k and _overlap(t, t2):
+                raise _lib.FpAmdError(f"{what}: out['{k}'] overlaps out['{k2}']")
+    return names, pts, m, vp_, fc, vn, en, out, shapes, (Q, Nv, F, T)
+
+
+MESH_SIGNED_OUTPUTS = ("dist2", "face", "closest", "feature", "sign")
+_MESH_SIGNED_DTYPES = {"dist2": torch.float32, "face": torch.int32, "closest": torch.float32, "feature": torch.int32, "sign": torch.int32}
+MESH_FEATURES = ("vertex a", "vertex b", "vertex c", "edge ab", "edge bc", "edge ca", "interior")
+
+
+def mesh_signed_distance(points, mesh_tensors=None, pos=None, faces=None, tables=None, want=("dist2", "sign"), out=None,
+                         allow_open=False):
+    """fp_mesh_signed_distance: mesh_point_distance and the side of the surface -> dict of device tensors: `dist2`, `face`, `closest`
+    as mesh_point_distance gives them (the same bits), `feature` (Q,) int32 the part of the nearest face the closest point lies on
+    (MESH_FEATURES; -1 without an answer), `sign` (Q,) int32: -1 inside, +1 outside or on the surface, 0 for a query that no triangle
+    answers.  The signed distance is sign * sqrt(dist2).  include/fp_amd.h has the definition: the sign of (p - closest) . n for the
+    angle-weighted pseudonormal n of that feature.  tables: mesh_pseudonormals of the mesh (None: taken from mesh_tensors, where it
+    is kept after the first call, or computed now -- a host computation that synchronises, so a caller that captures a graph or
+    passes pos= / faces= in a loop makes them beforehand).  The sign means inside / outside only for a closed, outward-oriented mesh
+    that does not cross itself: a mesh whose report is not closed is refused (FpAmdError) unless allow_open=True, and then the sign is
+    the side of the nearest face (a boundary edge carries its one face's normal).  want, out, the workspace and the order of the
+    refusals are mesh_point_distance's; dist2 is always computed and returned."""
+    what = "mesh_signed_distance"
+    names, pts, _, vp_, fc, vn, en, out, shapes, (Q, Nv, F, _) = _signed_call(
+        what, MESH_SIGNED_OUTPUTS, _MESH_SIGNED_DTYPES, want, points, None, mesh_tensors, pos, faces, tables, allow_open, out, ("dist2",))
+    for k in names:
+        if k not in out:
+            out[k] = torch.empty(shapes[k], dtype=_MESH_SIGNED_DTYPES[k], device=pts.device)
+    need = int(_lib.lib().fp_mesh_signed_distance_workspace_bytes(Q))
+    ws = _workspace(need, pts.device)
+    _lib.check(_lib.lib().fp_mesh_signed_distance(_ptr(vp_), Nv, _ptr(fc), F, _ptr(vn), _ptr(en), _ptr(pts), Q, _ptr(out["dist2"]),
+                                                  _ptr(out.get("face")), _ptr(out.get("closest")), _ptr(out.get("feature")),
+                                                  _ptr(out.get("sign")), _ptr(ws), need, _stream(pts)), "fp_mesh_signed_distance")
+    return {k: out[k] for k in names}
+
+
+MESH_PENETRATION_OUTPUTS = ("inside", "depth2", "deepest", "sign", "dist2")
+_MESH_PENETRATION_DTYPES = {"inside": torch.int32, "depth2": torch.float32, "deepest": torch.int32, "sign": torch.int32,
+                            "dist2": torch.float32}
+
+
+def mesh_penetration_workspace(T, Q, device):
+    """the workspace of mesh_penetration for T transforms of Q points (a captured graph owns its buffers)"""
+    nbytes = int(_lib.lib().fp_mesh_penetration_workspace_bytes(int(T), int(Q)))
+    return torch.empty(((nbytes + 7) // 8,), dtype=torch.int64, device=device)
+
+
+def mesh_penetration(points, tfs, mesh_tensors=None, pos=None, faces=None, tables=None, want=("inside", "depth2", "deepest"), out=None,
+                     workspace=None, allow_open=False):
+    """fp_mesh_penetration: how far each of the transforms tfs (T,4,4) f32 of the points (Q,3) f32 (surface samples of another object,
+    as a rule) reaches into the mesh -> dict of device tensors: `inside` (T,) int32 the number of transformed points inside, `depth2`
+    (T,) f32 the largest squared distance of one of those to the surface (0 when there is none), `deepest` (T,) int32 its index (the
+    smaller of equals; -1 when there is none), `sign` (T,Q) int32 and `dist2` (T,Q) f32 the whole matrices.  include/fp_amd.h has the
+    definition: the point as mesh_transform_residuals forms it, then mesh_signed_distance's dist2 and sign; a transform whose rows
+    0..2 are not finite moves every point to nowhere and has inside 0, depth2 0, deepest -1.  tables, allow_open and the refusal of a
+    mesh that is not closed are mesh_signed_distance's.  want: names out of MESH_PENETRATION_OUTPUTS; inside is always computed and
+    returned.  out: a dict of caller-owned buffers for some of the wanted names; workspace: mesh_penetration_workspace (None: the
+    library's per-stream scratch, or a fresh allocation inside a stream capture).  T x Q x F pair tests."""
+    what = "mesh_penetration"
+    names, pts, m, vp_, fc, vn, en, out, shapes, (Q, Nv, F, T) = _signed_call(
+        what, MESH_PENETRATION_OUTPUTS, _MESH_PENETRATION_DTYPES, want, points, tfs, mesh_tensors, pos, faces, tables, allow_open, out,
+        ("inside",))
+    need = int(_lib.lib().fp_mesh_penetration_workspace_bytes(T, Q))
+    if workspace is None:
+        ws, ws_bytes = _workspace(need, pts.device), need
+    else:
+        if not (torch.is_tensor(workspace) and workspace.is_cuda and workspace.is_contiguous()):
+            raise _lib.FpAmdError(f"{what}: workspace must be a contiguous CUDA(HIP) tensor")
+        ws, ws_bytes = workspace, workspace.numel() * workspace.element_size()
+        if ws_bytes < need:
+            raise _lib.FpAmdError(f"{what}: workspace of {ws_bytes} bytes, {need} needed (mesh_penetration_workspace)")
+        for k, t in out.items():
+            if _overlap(t, ws):
+                raise _lib.FpAmdError(f"{what}: out['{k}'] overlaps workspace")
+    for k in names:
+        if k not in out:
+            out[k] = torch.empty(shapes[k], dtype=_MESH_PENETRATION_DTYPES[k], device=pts.device)
+    _lib.check(_lib.lib().fp_mesh_penetration(_ptr(vp_), Nv, _ptr(fc), F, _ptr(vn), _ptr(en), _ptr(pts), Q, _ptr(m), T,
+                                              _ptr(out["inside"]), _ptr(out.get("depth2")), _ptr(out.get("deepest")),
+                                              _ptr(out.get("sign")), _ptr(out.get("dist2")), _ptr(ws), ws_bytes, _stream(pts)),
+               "fp_mesh_penetration")
+    return {k: out[k] for k in names}
+
+
+class Penetration(NamedTuple):
+    """FoundationPose.penetration_into: per pose, `inside` (N,) float64 the share of the object's surface samples inside the other
+    object, `depth` (N,) float64 the distance of the deepest of them to the other's surface (0 when none is inside), `deepest` (N,3)
+    float64 that sample in the object's own frame (NaN when none)."""
+    inside: np.ndarray
+    depth: np.ndarray
+    deepest: np.ndarray
+
+    @classmethod
+    def rows(cls, got, points, offset=(0.0, 0.0, 0.0)):
+        """of mesh_penetration's dict (inside, depth2, deepest), the points it was called with and the offset from their frame to the
+        object's own; float64 on the host (one device-to-host copy each)"""
+        pts = points.detach().cpu().numpy().astype(np.float64) + np.asarray(offset, dtype=np.float64).reshape(1, 3)
+        idx = got["deepest"].cpu().numpy()
+        deepest = np.where((idx >= 0)[:, None], pts[np.maximum(idx, 0)] if len(pts) else np.nan, np.nan)
+        return cls(got["inside"].cpu().numpy().astype(np.float64) / max(1, len(pts)), np.sqrt(got["depth2"].cpu().numpy().astype(np.float64)),
+                   deepest)
+
+
 class MeshAlignment(NamedTuple):
     """a rigid registration of mesh a onto mesh b (reconstruct.align_meshes): `tf` (4,4) float64 maps a's coordinates into b's frame;
     `mean_distance` / `rmse` the mean and the root mean square of the distances of a's samples to b's surface over the pairs, in the
@@ -1074,6 +1290,25 @@ class DistanceStats(NamedTuple):
         if not np.isfinite(d).all():                 # a sample that no triangle answered: no interpolation between +inf and +inf
             return cls(float(np.mean(d)), float(np.median(d)), float(np.percentile(d, 99, method="higher")), float(np.max(d)))
         return cls(float(np.mean(d)), float(np.median(d)), float(np.percentile(d, 99)), float(np.max(d)))
+
+
+class SignedStats(NamedTuple):
+    """reconstruct.signed_bias(a, b): the signed distances of a's surface samples to b's surface, negative inside b, in the meshes'
+    unit: `mean`, `inside` the share of the samples inside b, and the 5th, 50th and 95th percentiles.  A positive mean says a is
+    inflated against b, a negative one that it is shrunk."""
+    mean: float
+    inside: float
+    p5: float
+    p50: float
+    p95: float
+
+    @classmethod
+    def of(cls, d):
+        d = np.asarray(d, dtype=np.float64).reshape(-1)
+        if d.size == 0:
+            return cls(*(float("nan"),) * 5)
+        pct = dict(method="higher") if not np.isfinite(d).all() else {}
+        return cls(float(np.mean(d)), float(np.mean(d < 0)), *(float(x) for x in np.percentile(d, [5, 50, 95], **pct)))
 
 
 class MeshComparison(NamedTuple):

@@ -635,6 +635,58 @@ def compare_meshes(a, b, samples=100_000, thresholds=None, seed=0, unit=None, de
     return ops.MeshComparison.from_distances(d_ab, d_ba, thr)
 
 
+def _signed(points, mesh, what, allow_open):
+    """-> (sign (Q,) int32, dist (Q,) float32) device tensors of the points against a mesh-tensor dict or a SimpleMesh"""
+    if not torch.is_tensor(points):
+        points = torch.as_tensor(np.asarray(points, dtype=np.float32))
+    if points.dim() != 2 or int(points.shape[1]) != 3:
+        raise ValueError(f"{what}: points must be (Q,3), got {tuple(points.shape)}")
+    if isinstance(mesh, dict) and torch.is_tensor(mesh.get("pos")) and mesh["pos"].is_cuda and mesh["pos"].dtype == torch.float32 \
+            and torch.is_tensor(mesh.get("faces")) and mesh["faces"].dtype == torch.int32:
+        t = mesh                                       # the caller's dict as it is: its pseudonormal tables are kept in it
+    else:
+        t = dict(zip(("pos", "faces"), _mesh_arrays(mesh, points.device if points.is_cuda else "cuda", what, "mesh")))
+    pts = points.to(device=t["pos"].device, dtype=torch.float32).contiguous()
+    r = ops.mesh_signed_distance(pts, t, want=("dist2", "sign"), allow_open=allow_open)
+    # the square root through float64, as compare_meshes takes it
+    return r["sign"], r["dist2"].double().sqrt_().float()
+
+
+def signed_distance(points, mesh, allow_open=False):
+    """The signed distance of the points (Q,3) to the surface of a closed mesh -> (Q,) float32 on the mesh's device: negative inside,
+    positive outside, +0 on the surface; +inf for a point that no triangle answers (a NaN point).  mesh: a mesh-tensor dict (pos,
+    faces; the pseudonormal tables are computed at the first call and kept in it) or a SimpleMesh.  ops.mesh_signed_distance has the
+    definition, the cost (points x faces pair tests) and the refusal of a mesh that is not closed (allow_open=True: the side of the
+    nearest face)."""
+    sign, dist = _signed(points, mesh, "signed_distance", allow_open)
+    return torch.where(sign < 0, -dist, dist)
+
+
+def contains(points, mesh, allow_open=False):
+    """Is each of the points (Q,3) inside the closed mesh -> (Q,) bool on the mesh's device.  A point on the surface, and a point
+    that is not finite, is not inside.  See signed_distance."""
+    return _signed(points, mesh, "contains", allow_open)[0] < 0
+
+
+def signed_bias(a, b, samples=100_000, seed=0, tf=None, device=None, allow_open=False):
+    """On which side of mesh b (the reference, closed) does the surface of mesh a (what was built) lie -> ops.SignedStats: the mean
+    signed distance of `samples` surface samples of a to b's surface (negative inside b: a positive mean says a is inflated, a
+    negative one that it is shrunk), the share of the samples inside b, and the 5th, 50th and 95th percentiles.  The samples are
+    compare_meshes's accuracy samples (sample_surface, the same seed), so abs(mean) is at most that comparison's accuracy mean; a, b,
+    tf and device as there.  A setup / evaluation call: it synchronises."""
+    what = "signed_bias"
+    samples = _check_count(samples, what, "samples")
+    if device is None:
+        device = next((m["pos"].device for m in (a, b) if isinstance(m, dict) and torch.is_tensor(m.get("pos"))), "cuda")
+    ta, tb = (dict(zip(("pos", "faces"), _mesh_arrays(m, device, what, name))) for m, name in ((a, "a"), (b, "b")))
+    if tf is not None:
+        m = torch.as_tensor(_rigid_tf(tf, what), device=ta["pos"].device)
+        ta["pos"] = (ta["pos"].double() @ m[:3, :3].T + m[:3, 3]).float().contiguous()
+    pa, _ = sample_surface(ta, samples, seed)
+    sign, dist = _signed(pa, tb, what, allow_open)
+    return ops.SignedStats.of((sign.double() * dist.double()).cpu().numpy())
+
+
 # ------------------------------------------------------------------ which rotations map a mesh onto itself
 def detect_symmetries(mesh_tensors, tol=None, max_order=6, rot_angle_discrete=5, samples=(64, 512), n_axes=800):
     """The rotational symmetries of a mesh -> symmetry.Symmetries: tfs (S,4,4) float64 with the identity first (what the estimator's

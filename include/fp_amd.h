@@ -102,8 +102,11 @@ const char* fp_last_error(void);
  *   231 -> 232: + fp_mesh_transform_residuals, fp_mesh_transform_residuals_workspace_bytes (additions only): how far each of T
  *               candidate transforms moves a mesh's surface samples off the surface, for detecting its rotational symmetries.
  *   232 -> 233: + fp_mesh_icp_step, fp_mesh_icp_workspace_bytes (additions only): one Gauss-Newton step of point-to-plane ICP for each
- *               of T candidate transforms of a mesh's surface samples against another mesh, for registering one onto the other. */
-#define FP_AMD_ABI_VERSION 233
+ *               of T candidate transforms of a mesh's surface samples against another mesh, for registering one onto the other.
+ *   233 -> 234: + fp_mesh_pseudonormals, fp_mesh_signed_distance, fp_mesh_signed_distance_workspace_bytes, fp_mesh_penetration,
+ *               fp_mesh_penetration_workspace_bytes (additions only): which side of a closed mesh a point is on, and how far T
+ *               placements of a point set reach into it. */
+#define FP_AMD_ABI_VERSION 234
 int fp_version(void);
 
 /* Utils.py:104-130 make_mesh_tensors: records caller-owned device tensors.
@@ -404,6 +407,79 @@ int fp_mesh_icp_step(const float* pos /*dev Nv,3*/, int Nv, const int32_t* faces
                      double* system /*dev T,40*/, float* tfs_out /*dev T,16|NULL*/,
                      float* dist2 /*dev T,Q|NULL*/, int32_t* face /*dev T,Q|NULL*/,
                      void* workspace /*dev*/, size_t workspace_bytes, void* stream);
+
+/* Which side of a closed mesh: the angle-weighted pseudonormals of its vertices and edges (Baerentzen and Aanaes, Signed distance
+ * computation using the angle weighted pseudonormal, 2005), and a report of what keeps the mesh from being closed.  HOST pointers, no
+ * device, setup time (as fp_cluster_poses).  Every operation is float64 on the widened float32 coordinates, each output rounded once
+ * to float32; acos is the host libm's.
+ *  - Welding.  Adjacency goes by position, not by index (OBJ files repeat a vertex along UV seams): two indices whose three float32
+ *    coordinates compare equal (-0 == +0; a NaN equals nothing, itself included) are one vertex, named w(i) = the smallest such index.
+ *  - Faces.  Face f with a, b, c = pos[faces[f][0..2]]:  n = (b - a) x (c - a), len = sqrt((n0*n0 + n1*n1) + n2*n2), u_f = n / len.
+ *    The face is DEGENERATE when an index is outside 0..Nv-1 or len is not a finite number above 0; a degenerate face has no normal
+ *    and takes no part in anything below.
+ *  - vn[i] = the sum, over the non-degenerate faces f in index order and their corners j = 0, 1, 2 in order with w(faces[f][j]) = w(i),
+ *    of angle * u_f, where angle = acos(clamp(dot(e0, e1) / (|e0| * |e1|), -1, 1)) for the edges e0, e1 from corner j to the next and
+ *    to the previous corner.  Not normalised: only its direction is used.  An index that no such face uses has vn = 0.
+ *  - en[f][k], k = 0, 1, 2 for the edges ab, bc, ca of face f = the sum of u_g over the non-degenerate faces g, in index order, that have
+ *    an edge with the same unordered pair of welded end points.  For a face with an index outside the table it is 0; for any other
+ *    degenerate face it is that same sum (0 when no non-degenerate face has the edge).  A boundary edge carries its one face's normal.
+ *  - report[0] the distinct edges (unordered welded pairs) of the non-degenerate faces; [1] those with one face (boundary); [2] those
+ *    with more than two faces (non-manifold); [3] those with exactly two faces that both traverse it in the same direction
+ *    (inconsistently oriented); [4] the degenerate faces; [5] the indices i with w(i) != i (welded away); [6] closed: 1 when [0] > 0 and
+ *    [1] = [2] = [3] = 0, else 0; [7] 0.
+ * For a closed, consistently outward-oriented mesh that does not intersect itself, the sign of (p - q) . n with q the closest point of
+ * the surface to p and n the pseudonormal of the feature q lies on (vn at a vertex, en on an edge, u_f in a face) is negative exactly
+ * for p inside.  The report cannot see self-intersection, several shells or an inward orientation: those are the caller's to exclude.
+ * Argument errors (FP_ERR_INVALID_ARG): Nv or F outside 0..2^30, NULL report, NULL pos / vn with Nv > 0, NULL faces / en with F > 0. */
+int fp_mesh_pseudonormals(const float* pos /*host Nv,3*/, int Nv, const int32_t* faces /*host F,3*/, int F,
+                          float* vn /*host Nv,3*/, float* en /*host F,3,3*/, int32_t* report /*host 8*/);
+
+/* The signed distance from Q points to a mesh: fp_mesh_point_distance and the side.  dist2, face and closest are that function's, by
+ * the same launches on the same code (csrc/mesh_closest.h): the same bits for the same inputs.  vn and en are fp_mesh_pseudonormals'
+ * tables on the device.  For a query p that a triangle answers, with f its face, q its closest point and a, b, c, ab, ac as above:
+ *   feature[i] = where the walk found q: 0, 1, 2 vertex a, b, c (tests 1, 2, 4); 3, 4, 5 edge ab, bc, ca (tests 3, 6, 5); 6 interior (7);
+ *   n = vn[faces[f][feature]] for a vertex;  en[f][feature - 3] for an edge;  for the interior ab x ac in float32 =
+ *       (ab1*ac2 - ab2*ac1, ab2*ac0 - ab0*ac2, ab0*ac1 - ab1*ac0), each component one difference of two products;
+ *   s = dot(p - q, n) (float32, dot as above);  sign[i] = -1 when s < 0, else +1.
+ * So s = 0 (a point on the surface, a zero n), a NaN s and s > 0 are all outside.  The signed distance is sign * sqrt(dist2).
+ * A query that no triangle answers: dist2 = +inf, face = -1, closest = 0, feature = -1, sign = 0.
+ * face, closest, feature and sign may each be NULL (not wanted).  Three launches (init, scan, finish: the finish walks the winning face
+ * again); no allocation, no host synchronisation (graph-capturable); nothing is written outside the outputs and the workspace
+ * (fp_mesh_signed_distance_workspace_bytes(Q) bytes = 8 * Q, 8-byte aligned; 0 for Q <= 0).  Q == 0 does nothing.  Argument errors
+ * (FP_ERR_INVALID_ARG), before any launch, each message beginning with the entry point's name: fp_mesh_point_distance's, and with
+ * Q > 0 and F > 0 a NULL en, or a NULL vn with Nv > 0. */
+size_t fp_mesh_signed_distance_workspace_bytes(int Q);
+int fp_mesh_signed_distance(const float* pos /*dev Nv,3*/, int Nv, const int32_t* faces /*dev F,3*/, int F,
+                            const float* vn /*dev Nv,3*/, const float* en /*dev F,3,3*/, const float* points /*dev Q,3*/, int Q,
+                            float* dist2 /*dev Q*/, int32_t* face /*dev Q|NULL*/, float* closest /*dev Q,3|NULL*/,
+                            int32_t* feature /*dev Q|NULL*/, int32_t* sign /*dev Q|NULL*/,
+                            void* workspace /*dev*/, size_t workspace_bytes, void* stream);
+
+/* How far each of T placements of Q points reaches into a mesh.  The point of pair (t, i) is p' exactly as
+ * fp_mesh_transform_residuals forms it (rows 0..2 of tfs[t] as given, row 3 never read); (dd, sign) are fp_mesh_signed_distance's dist2
+ * and sign for the query p'.  Per transform t:
+ *   inside[t]  = the number of i with sign = -1;
+ *   depth2[t]  = the largest dd among them, 0 when there are none;
+ *   deepest[t] = the i of that dd, the smallest i among equal dd, -1 when there are none;
+ *   sign[t*Q + i], dist2[t*Q + i] = the pair's values, where asked for.
+ * A row 0..2 of tfs[t] with a non-finite element (or a product that overflows) makes p' non-finite, no triangle answers it, and so:
+ * sign = 0, dist2 = +inf, and a transform all of whose p' are such has inside = 0, depth2 = 0, deepest = -1.  The same holds with
+ * Q == 0 or F == 0.  T == 0 does nothing.  depth2, deepest, sign and dist2 may each be NULL (not wanted).
+ * The count is an integer sum and the deepest point a 64-bit integer maximum of (bits(dd) << 32) | ~i, both by LDS atomics in one
+ * workgroup per transform; the nearest face is merged with 64-bit integer atomic minima as in fp_mesh_point_distance: every output has
+ * one value whatever the schedule, and row t has the same bits alone, in any batch and on every replay.  Three launches; T * Q * F pair
+ * tests.  No allocation, no memset, no host synchronisation (graph-capturable); nothing is written outside the outputs and the
+ * workspace (fp_mesh_penetration_workspace_bytes(T, Q) bytes = 8 * T * Q, 8-byte aligned; 0 when T <= 0 or Q <= 0).  Argument errors
+ * (FP_ERR_INVALID_ARG), before any launch, each message beginning with the entry point's name: T, Q, F or Nv negative; T * Q, T or F
+ * above 2^30; and with T > 0: NULL inside; with Q > 0 also NULL points or tfs, NULL faces or en with F > 0, NULL pos or vn with Nv > 0
+ * and F > 0, a workspace that is NULL, too small or misaligned. */
+size_t fp_mesh_penetration_workspace_bytes(int T, int Q);
+int fp_mesh_penetration(const float* pos /*dev Nv,3*/, int Nv, const int32_t* faces /*dev F,3*/, int F,
+                        const float* vn /*dev Nv,3*/, const float* en /*dev F,3,3*/, const float* points /*dev Q,3*/, int Q,
+                        const float* tfs /*dev T,4,4 row-major; rows 0..2 are read*/, int T,
+                        int32_t* inside /*dev T*/, float* depth2 /*dev T|NULL*/, int32_t* deepest /*dev T|NULL*/,
+                        int32_t* sign /*dev T,Q|NULL*/, float* dist2 /*dev T,Q|NULL*/,
+                        void* workspace /*dev*/, size_t workspace_bytes, void* stream);
 
 /* An object's mesh from posed RGB-D reference views: truncated-signed-distance (TSDF) fusion into a caller-owned volume, then marching
  * tetrahedra.  The volume has nz x ny x nx voxels; voxel (ix, iy, iz) has the linear index i = (iz * ny + iy) * nx + ix and, in the

@@ -12,7 +12,9 @@ such a directory from the can first; `--ref_texture T` bakes a texture atlas of 
 its MTL and the texture as a PNG; `--compare_mesh PATH` (with the reference views) compares the fused mesh with the mesh file PATH, in the
 frame of the views' poses -- `--compare_mesh synthetic` with --synthetic_ref_views takes the can the views were rendered from -- and
 prints the report (reconstruct.compare_meshes: accuracy, completeness, chamfer, Hausdorff, precision / recall / F-score at 0.5, 1, 2 and
-4 voxel pitches) as one JSON line {"compare_mesh": ...}; `--align_mesh` with it registers the fused mesh onto that mesh first
+4 voxel pitches) as one JSON line {"compare_mesh": ...}, and with `--signed` a second line {"signed_bias": ...} that says on which side of
+that mesh the fused surface lies (reconstruct.signed_bias; a mesh that is not closed is reported as such and its sign is the side of
+the nearest face); `--align_mesh` with it registers the fused mesh onto that mesh first
 (reconstruct.align_meshes: the mesh file may then be in any frame of the same unit), prints the alignment as one JSON line
 {"align_mesh": ...} and compares in the aligned frame; `--detect_symmetry` finds the rotational symmetries of the mesh that is used,
 registers with the rotation grid clustered by them and prints the axes as one JSON line {"detect_symmetry": ...}."""
@@ -111,6 +113,9 @@ def main(argv=None):
                     help="with --ref_views: compare the fused mesh with this mesh file (or 'synthetic': the can of --synthetic_ref_views) "
                          "and print the report as one JSON line")
     ap.add_argument("--compare_samples", type=int, default=100_000, help="surface samples per mesh for --compare_mesh")
+    ap.add_argument("--signed", action="store_true",
+                    help="with --compare_mesh: also print on which side of that mesh the fused surface lies (reconstruct.signed_bias: "
+                         "the mean signed distance, negative inside, the share inside and three percentiles) as one JSON line")
     ap.add_argument("--align_mesh", action="store_true",
                     help="with --compare_mesh: register the fused mesh onto that mesh first (reconstruct.align_meshes: the two need not be "
                          "in one frame), print the alignment as one JSON line and compare in the aligned frame")
@@ -120,6 +125,8 @@ def main(argv=None):
     args = ap.parse_args(argv)
     if args.align_mesh and not args.compare_mesh:
         ap.error("--align_mesh needs --compare_mesh PATH (the mesh to register onto)")
+    if args.signed and not args.compare_mesh:
+        ap.error("--signed needs --compare_mesh PATH (the closed mesh whose sides are meant)")
     logging.basicConfig(level=logging.INFO, format="[%(funcName)s()] %(message)s")
 
     from foundationpose_amd import dr
@@ -164,7 +171,7 @@ def main(argv=None):
         if args.compare_mesh:
             import json
             from foundationpose_amd.mesh import make_can_mesh
-            from foundationpose_amd.reconstruct import align_meshes, compare_meshes
+            from foundationpose_amd.reconstruct import align_meshes, compare_meshes, signed_bias
             truth = make_can_mesh() if args.compare_mesh == "synthetic" else load_mesh(args.compare_mesh)
             alignment = None
             if args.align_mesh:
@@ -180,6 +187,14 @@ def main(argv=None):
             if alignment is not None:
                 report.update(aligned=True)
             print(json.dumps({"compare_mesh": report}), flush=True)
+            if args.signed:
+                from foundationpose_amd import ops
+                truth_t = dict(pos=torch.as_tensor(np.asarray(truth.vertices, dtype=np.float32), device=dev),
+                               faces=torch.as_tensor(np.asarray(truth.faces).astype(np.int32), device=dev))
+                tables = ops.mesh_pseudonormals(truth_t)
+                bias = signed_bias(fused, truth_t, samples=args.compare_samples, device=dev, tf=alignment, allow_open=True)
+                print(json.dumps({"signed_bias": dict(mean_m=bias.mean, inside=bias.inside, p5_m=bias.p5, p50_m=bias.p50, p95_m=bias.p95,
+                                                      closed=tables.closed, mesh_report=tables.describe())}), flush=True)
     else:
         mesh = load_mesh(args.mesh_file)
     if args.ref_texture and not args.ref_views:
