@@ -10,7 +10,7 @@ import torch  # noqa: F401  (must precede CDLL: shares the HIP runtime with PyTo
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("FP_AMD_LIB") or os.path.join(_HERE, "csrc", "libfp_amd.so")   # FP_AMD_LIB: A/B builds
-ABI_VERSION = 234   # = FP_AMD_ABI_VERSION of include/fp_amd.h (tests/test_abi.py keeps the two in step)
+ABI_VERSION = 234  # = FP_AMD_ABI_VERSION of include/fp_amd.h (tests/test_abi.py keeps the two in step)
 _lib = None
 
 vp, ci, cf, cd, sz = C.c_void_p, C.c_int, C.c_float, C.c_double, C.c_size_t
@@ -74,6 +74,8 @@ SIGNATURES = {
     "fp_layernorm_res_fwd": (ci, [vp, vp, vp, ci, vp, vp, vp, cf, vp, vp, ci, ci, vp]),
     "fp_pack_linear512_f16": (ci, [vp, vp, vp]),
     "fp_linear512_f16_fwd": (ci, [vp, vp, vp, vp, ci, ci, ci, vp]),
+    "fp_pack_linear512_direct_f16": (ci, [vp, vp, vp]),
+    "fp_linear512_flags_f16_fwd": (ci, [vp, vp, vp, vp, ci, ci, ci, vp]),
     "fp_linear_layernorm_fwd": (ci, [vp, vp, vp, vp, vp, vp, ci, vp, vp, cf, vp, vp, ci, ci, ci, ci, vp]),
     "fp_ffn_layernorm_mean_fwd": (ci, [vp, vp, vp, vp, vp, vp, vp, vp, cf, vp, vp, C.c_size_t, ci, ci, vp]),
     "fp_encoder_tail_workspace_bytes": (sz, [ci, ci]),

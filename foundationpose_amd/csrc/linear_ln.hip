@@ -85,12 +85,15 @@ struct LinearLnParams {
 // 64 lanes' MFMA operands stored back to back,
 //     packed[((w * (K / 16) + q) * 2 + i) * 64 + lane][0..7] = W[64 w + 32 i + (lane & 31)][16 q + 8 (lane >> 5) + 0..7]
 // so that one wave load reads one contiguous KiB.  One thread per 16-byte chunk.
-__global__ __launch_bounds__(256) void k_pack_w512(const _Float16* __restrict__ W, _Float16* __restrict__ out, int K) {
+// direct (fp_pack_linear512_direct_f16, the order of k_linear512_direct): column c of channel tile i is channel 2 c + i of the group, i.e.
+// packed row 32 i + c of every 64-row group holds weight row 2 c + i, so that a lane of the exchanged MFMA owns two ADJACENT channels.
+__global__ __launch_bounds__(256) void k_pack_w512(const _Float16* __restrict__ W, _Float16* __restrict__ out, int K, int direct) {
   const int o = blockIdx.x * 256 + threadIdx.x;          // chunk index of the packed matrix
   const int lane = o & 63, i = (o >> 6) & 1, rest = o >> 7, nq = K / 16;
   const int q = rest % nq, w = rest / nq;
   if (w >= LL_BN / 64) return;
-  const half8 v = *reinterpret_cast<const half8*>(W + (size_t)(64 * w + 32 * i + (lane & 31)) * K + 16 * q + 8 * (lane >> 5));
+  const int row = direct ? 2 * (lane & 31) + i : 32 * i + (lane & 31);
+  const half8 v = *reinterpret_cast<const half8*>(W + (size_t)(64 * w + row) * K + 16 * q + 8 * (lane >> 5));
   *reinterpret_cast<half8*>(out + (size_t)o * 8) = v;
 }
 
@@ -486,17 +489,38 @@ struct Linear512Params {
 constexpr int L5_XBUF = 32 * 64;                                   // a wave's transposition buffer: 32 rows x 32 channels fp16
 constexpr int L5_BIAS_OFF = LL_E_BYTES + LL_NW * L5_XBUF;          // bias vector (N floats) behind the eight buffers
 constexpr int L5_MAX_N = 3072;                                     // round 6: the in_proj of BOTH refiner heads in one launch (2 x 1536)
-constexpr int l5_lds(int N) { return L5_BIAS_OFF + N * 4; }
+// DIRECT (k_linear512_direct): no transposition buffers, the bias vector stands right behind the A tile
+constexpr int l5_lds(int N, bool direct = false) { return (direct ? LL_E_BYTES : L5_BIAS_OFF) + N * 4; }
 static_assert(l5_lds(L5_MAX_N) <= 160 * 1024, "tile does not fit the 160 KiB LDS");
 
-__global__ __launch_bounds__(LL_THREADS, 1) void k_linear512(Linear512Params p) {
+#ifdef FP_PROFILE_BUILD
+// profiling build only: 100 MHz wall-clock time of wave 0 of every workgroup of k_linear512 / k_linear512_direct, summed over a launch
+// (scripts/dbg_linear512.py): [0] inside store_block, [1] the workgroup's life, [2] workgroups, [3] column blocks stored
+__device__ unsigned long long l5_dbg[4];
+extern "C" int fp_dbg_linear512(unsigned long long* out, int reset) {
+  if (reset) { unsigned long long z[4] = {0, 0, 0, 0}; return (int)hipMemcpyToSymbol(HIP_SYMBOL(l5_dbg), z, sizeof(z)); }
+  return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(l5_dbg), 4 * sizeof(unsigned long long));
+}
+#endif
+
+// The body of both kernels.  DIRECT exchanges the two MFMA sources: the A and B fragment layouts of v_mfma_f32_32x32x16_f16 mirror each
+// other (attention.hip), so the same registers give D[row][channel] instead of D[channel][row], and with the weight rows in the order of
+// fp_pack_linear512_direct_f16 a lane owns two adjacent channels of 16 rows per row tile: its tiles leave with 4-byte stores, the 32
+// lanes of a half wave writing one whole 128-byte line, without the transposition through LDS.  The same dot products, accumulated in
+// the same k order, and the same rounding statement.  FULL (DIRECT only): every row of the tile exists.
+template <bool DIRECT, bool FULL>
+__device__ __forceinline__ void l5_body(const Linear512Params& p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
-  float* bias_lds = reinterpret_cast<float*>(smem + L5_BIAS_OFF);
-  unsigned char* xbuf = smem + LL_E_BYTES + wid * L5_XBUF;
+  float* bias_lds = reinterpret_cast<float*>(smem + (DIRECT ? LL_E_BYTES : L5_BIAS_OFF));
+  unsigned char* xbuf = smem + LL_E_BYTES + wid * L5_XBUF;   // !DIRECT only
   const int m0 = blockIdx.x * LL_BM;
   const int nblk = p.N / LL_BN;
+#ifdef FP_PROFILE_BUILD
+  const unsigned long long l5_t0 = wall_clock64();
+  unsigned long long l5_ts = 0;
+#endif
 
   // bias -> LDS: N / 256 pieces of 1 KiB, one LDS-DMA each (piece q by wave q % 8; the oldest vector-memory operations of the wave, so
   // every later counted wait covers them)
@@ -547,8 +571,10 @@ __global__ __launch_bounds__(LL_THREADS, 1) void k_linear512(Linear512Params p) 
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
-      for (int j = 0; j < LL_TM; ++j)
-        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wr[wslot][kk][i], fa[aslot][j], acc[i][j], 0, 0, 0);
+      for (int j = 0; j < LL_TM; ++j) {
+        if constexpr (DIRECT) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa[aslot][j], wr[wslot][kk][i], acc[i][j], 0, 0, 0);
+        else acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wr[wslot][kk][i], fa[aslot][j], acc[i][j], 0, 0, 0);
+      }
   };
   auto zero_acc = [&]() {
 #pragma unroll
@@ -558,9 +584,46 @@ __global__ __launch_bounds__(LL_THREADS, 1) void k_linear512(Linear512Params p) 
 #pragma unroll
         for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
   };
+  // DIRECT: D[j = row][i = channel].  A lane holds channels 2 (lane & 31) + i of the wave's 64 and rows (r & 3) + 8 (r >> 2) + 4 (lane >> 5)
+  // of a row tile, r = register.  The lane's part of the address -- its two channels and its row group -- is the vector offset, the
+  // wave-uniform row of (j, r) the scalar offset: no address arithmetic per store.  The descriptor ends with the matrix (the launcher keeps
+  // M N 2 below 2^31); the ragged last tile predicates its rows itself
+  typedef _Float16 half2_ __attribute__((ext_vector_type(2)));
+  const __amdgpu_buffer_rsrc_t rsY = __builtin_amdgcn_make_buffer_rsrc(p.Y, 0, DIRECT ? p.M * p.N * 2 : 0, 0x00020000);
+  const int row_bytes = p.N * 2;
+  const int yoff = (4 * fhalf) * row_bytes + (64 * wid + 2 * frow) * 2;
+  const int rows_left = p.M - m0 - 4 * fhalf;      // !FULL: tile rows (j, r) below this belong to the matrix
+  auto store_block_direct = [&](int nb) {
+    typedef float float2_ __attribute__((ext_vector_type(2)));
+    const float2_ bv = *reinterpret_cast<const float2_*>(bias_lds + nb * LL_BN + 64 * wid + 2 * frow);
+    const int voff = yoff + nb * (LL_BN * 2);
+    const half2_ zero2 = {0, 0};
+    // the scalar offset walks down the tile: + one row inside a register group, + five rows from one group to the next (rows 3 -> 8,
+    // 27 -> 32); opaque per block, or the 64 offsets are computed once for all blocks and spill
+    unsigned soff = (unsigned)m0 * (unsigned)row_bytes;
+    asm volatile("" : "+s"(soff));
+    int left = rows_left;
+#pragma unroll
+    for (int j = 0; j < LL_TM; ++j) {
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int row = 32 * j + (r & 3) + 8 * (r >> 2);   // + 4 (lane >> 5): the vector offset
+        half2_ v = {(_Float16)(acc[0][j][r] + bv[0]), (_Float16)(acc[1][j][r] + bv[1])};
+        if (p.relu) v = __builtin_elementwise_max(v, zero2);
+        const unsigned vu = __builtin_bit_cast(unsigned, v);
+        if constexpr (FULL) {
+          __builtin_amdgcn_raw_buffer_store_b32(vu, rsY, voff, (int)soff, 0);
+        } else {
+          asm volatile("" : "+v"(left));           // one compare at a time, at its store: 64 masks computed ahead spill
+          if (row < left) __builtin_amdgcn_raw_buffer_store_b32(vu, rsY, voff, (int)soff, 0);
+        }
+        soff += (r & 3) == 3 ? 5u * (unsigned)row_bytes : (unsigned)row_bytes;
+      }
+    }
+  };
   // f16(acc + bias) of column block nb -> Y, tile by tile through the wave's buffer.  D[i = channel][j = row]: a lane holds row
   // (lane & 31) of a row tile and channels 8 g + 4 (lane >> 5) + {0..3} of a channel tile, g = register >> 2
-  auto store_block = [&](int nb) {
+  auto store_block_lds = [&](int nb) {
     const half4 zero4 = {0, 0, 0, 0};
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
@@ -589,6 +652,16 @@ __global__ __launch_bounds__(LL_THREADS, 1) void k_linear512(Linear512Params p) 
         __builtin_amdgcn_wave_barrier();
       }
     }
+  };
+  auto store_block = [&](int nb) {
+#ifdef FP_PROFILE_BUILD
+    const unsigned long long ts0 = wall_clock64();
+#endif
+    if constexpr (DIRECT) store_block_direct(nb);
+    else store_block_lds(nb);
+#ifdef FP_PROFILE_BUILD
+    l5_ts += wall_clock64() - ts0;
+#endif
   };
 
   // ---- column block 0: the first loop of k_rows512
@@ -646,6 +719,20 @@ __global__ __launch_bounds__(LL_THREADS, 1) void k_linear512(Linear512Params p) 
     }
     store_block(nb);
   }
+#ifdef FP_PROFILE_BUILD
+  if (tid == 0) {
+    atomicAdd(&l5_dbg[0], l5_ts); atomicAdd(&l5_dbg[1], wall_clock64() - l5_t0); atomicAdd(&l5_dbg[2], 1ull);
+    atomicAdd(&l5_dbg[3], (unsigned long long)nblk);
+  }
+#endif
+}
+
+__global__ __launch_bounds__(LL_THREADS, 1) void k_linear512(Linear512Params p) { l5_body<false, false>(p); }
+// ... its tiles stored from the accumulators (weights from fp_pack_linear512_direct_f16): a tile whose 128 rows all exist runs the
+// unpredicated instantiation of the body, the ragged last tile the other one (a workgroup-uniform branch, one launch)
+__global__ __launch_bounds__(LL_THREADS, 1) void k_linear512_direct(Linear512Params p) {
+  if ((int)(blockIdx.x + 1) * LL_BM <= p.M) l5_body<true, true>(p);
+  else l5_body<true, false>(p);
 }
 
 // out[g][c] = mean over the rows of group g of LN(...) * gamma + beta from the chunk sums (16 rows each), chunks in increasing order
@@ -669,8 +756,20 @@ extern "C" int fp_pack_linear512_f16(const void* w16, void* packed, void* stream
   FP_REQUIRE(w16 != packed, "fp_pack_linear512_f16: cannot pack in place");
   FP_REQUIRE((((size_t)w16 | (size_t)packed) & 15) == 0, "fp_pack_linear512_f16: tensors must be 16-byte aligned");
   hipLaunchKernelGGL(k_pack_w512, dim3(LL_BN * LL_K / 8 / 256), dim3(256), 0, (hipStream_t)stream, (const _Float16*)w16, (_Float16*)packed,
-                     LL_K);
+                     LL_K, 0);
   FP_CHECK_LAUNCH("fp_pack_linear512_f16");
+  return FP_OK;
+}
+
+// The same copy in the row order of k_linear512_direct (FP_LINEAR512_W_DIRECT): within every group of 64 output channels, packed row
+// 32 i + c holds weight row 2 c + i.  Only fp_linear512_flags_f16_fwd with FP_LINEAR512_DIRECT_STORE reads it.  include/fp_amd.h.
+extern "C" int fp_pack_linear512_direct_f16(const void* w16, void* packed, void* stream) {
+  FP_REQUIRE(w16 && packed, "fp_pack_linear512_direct_f16: NULL tensor");
+  FP_REQUIRE(w16 != packed, "fp_pack_linear512_direct_f16: cannot pack in place");
+  FP_REQUIRE((((size_t)w16 | (size_t)packed) & 15) == 0, "fp_pack_linear512_direct_f16: tensors must be 16-byte aligned");
+  hipLaunchKernelGGL(k_pack_w512, dim3(LL_BN * LL_K / 8 / 256), dim3(256), 0, (hipStream_t)stream, (const _Float16*)w16, (_Float16*)packed,
+                     LL_K, 1);
+  FP_CHECK_LAUNCH("fp_pack_linear512_direct_f16");
   return FP_OK;
 }
 
@@ -678,21 +777,45 @@ extern "C" int fp_pack_linear512_f16(const void* w16, void* packed, void* stream
 // one rounding), the in_proj of nn.MultiheadAttention (N = 1536; refine_network.py:56-70, score_network.py:52-53).  The bits of
 // fp_igemm_f16_fwd (taps = 1): the same k order per accumulator.  w_packed: N / 512 blocks of 512 output channels, each
 // fp_pack_linear512_f16'ed, back to back.  include/fp_amd.h.
+static int l5_launch(const char* who, const void* x16, const void* w_packed, const float* bias, void* y16, int M, int N, int flags,
+                     void* stream) {
+  FP_REQUIRE(M >= 0, "%s: M < 0", who);
+  FP_REQUIRE((flags & ~(FP_LINEAR512_RELU | FP_LINEAR512_DIRECT_STORE | FP_LINEAR512_W_DIRECT)) == 0, "%s: unknown flags 0x%x", who, flags);
+  const bool direct = (flags & FP_LINEAR512_DIRECT_STORE) != 0, w_direct = (flags & FP_LINEAR512_W_DIRECT) != 0;
+  FP_REQUIRE(w_direct == direct, "%s: w_packed is in the row order of %s but this launch runs %s (FP_LINEAR512_W_DIRECT, FP_LINEAR512_DIRECT_STORE)",
+             who, w_direct ? "fp_pack_linear512_direct_f16" : "fp_pack_linear512_f16", direct ? "k_linear512_direct" : "k_linear512");
+  if (M == 0) return FP_OK;
+  FP_REQUIRE(x16 && w_packed && y16, "%s: NULL tensor", who);
+  FP_REQUIRE(N >= LL_BN && N % LL_BN == 0 && N <= L5_MAX_N, "%s: N=%d must be a multiple of 512, at most %d", who, N, L5_MAX_N);
+  FP_REQUIRE((long long)M * N < (1ll << 31), "%s: output exceeds 2^31 elements", who);
+  // k_linear512_direct addresses the output through a buffer descriptor with 32-bit byte offsets
+  FP_REQUIRE(!direct || (long long)M * N * 2 < (1ll << 31), "%s: FP_LINEAR512_DIRECT_STORE needs an output below 2 GiB (M=%d N=%d)", who, M, N);
+  FP_REQUIRE((((size_t)x16 | (size_t)w_packed | (size_t)bias | (size_t)y16) & 15) == 0, "%s: tensors must be 16-byte aligned", who);
+  Linear512Params p;
+  p.X = (const _Float16*)x16; p.Wp = (const _Float16*)w_packed; p.bias = bias; p.Y = (_Float16*)y16; p.M = M; p.N = N;
+  p.relu = (flags & FP_LINEAR512_RELU) ? 1 : 0;
+  if (direct) {
+    FP_SET_MAX_LDS(k_linear512_direct, l5_lds(L5_MAX_N, true));
+    hipLaunchKernelGGL(k_linear512_direct, dim3(fp_cdiv(M, LL_BM)), dim3(LL_THREADS), l5_lds(N, true), (hipStream_t)stream, p);
+  } else {
+    FP_SET_MAX_LDS(k_linear512, l5_lds(L5_MAX_N));
+    hipLaunchKernelGGL(k_linear512, dim3(fp_cdiv(M, LL_BM)), dim3(LL_THREADS), l5_lds(N), (hipStream_t)stream, p);
+  }
+  FP_CHECK_LAUNCH(who);
+  return FP_OK;
+}
+
 extern "C" int fp_linear512_f16_fwd(const void* x16, const void* w_packed, const float* bias, void* y16, int M, int N, int relu,
                                     void* stream) {
-  FP_REQUIRE(M >= 0, "fp_linear512_f16_fwd: M < 0");
-  if (M == 0) return FP_OK;
-  FP_REQUIRE(x16 && w_packed && y16, "fp_linear512_f16_fwd: NULL tensor");
-  FP_REQUIRE(N >= LL_BN && N % LL_BN == 0 && N <= L5_MAX_N, "fp_linear512_f16_fwd: N=%d must be a multiple of 512, at most %d", N, L5_MAX_N);
-  FP_REQUIRE((long long)M * N < (1ll << 31), "fp_linear512_f16_fwd: output exceeds 2^31 elements");
-  FP_REQUIRE((((size_t)x16 | (size_t)w_packed | (size_t)bias | (size_t)y16) & 15) == 0, "fp_linear512_f16_fwd: tensors must be 16-byte aligned");
-  Linear512Params p;
-  p.X = (const _Float16*)x16; p.Wp = (const _Float16*)w_packed; p.bias = bias; p.Y = (_Float16*)y16; p.M = M; p.N = N; p.relu = relu ? 1 : 0;
-  const int lds = l5_lds(N);
-  FP_SET_MAX_LDS(k_linear512, l5_lds(L5_MAX_N));
-  hipLaunchKernelGGL(k_linear512, dim3(fp_cdiv(M, LL_BM)), dim3(LL_THREADS), lds, (hipStream_t)stream, p);
-  FP_CHECK_LAUNCH("fp_linear512_f16_fwd");
-  return FP_OK;
+  return l5_launch("fp_linear512_f16_fwd", x16, w_packed, bias, y16, M, N, relu ? FP_LINEAR512_RELU : 0, stream);
+}
+
+// fp_linear512_f16_fwd with flags: FP_LINEAR512_DIRECT_STORE runs k_linear512_direct, which stores its tiles from the accumulators and
+// reads w_packed in the row order of fp_pack_linear512_direct_f16 (FP_LINEAR512_W_DIRECT says which order w_packed has; a launch whose
+// kernel cannot read its pack is refused, never run permuted).  The same bits.  include/fp_amd.h.
+extern "C" int fp_linear512_flags_f16_fwd(const void* x16, const void* w_packed, const float* bias, void* y16, int M, int N, int flags,
+                                          void* stream) {
+  return l5_launch("fp_linear512_flags_f16_fwd", x16, w_packed, bias, y16, M, N, flags, stream);
 }
 
 // The whole feed-forward half of the refiner's encoder layer in one launch + the finish kernel -- linear1 + ReLU + linear2 +

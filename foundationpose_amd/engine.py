@@ -90,6 +90,13 @@ SPECIALIZED_EPILOGUE = True
 # packs each layer's weight tiles for the kernel the layer runs (_conv_params); overrides(CONV_DIRECT_STORE=False) is the A/B arm.  The same
 # products in the same order and the same epilogue statements: the same bits (tests/test_gpu_conv_sw_direct.py).
 CONV_DIRECT_STORE = True
+# round 12: the same exchange of the MFMA sources in the in_proj launches (ops.linear512, csrc/linear_ln.hip k_linear512_direct), which
+# transposed every 32 x 32 accumulator tile through LDS to store rows.  A plan packs the in_proj weights in that kernel's row order
+# (ops.PackedLinear512(w, direct=True)); the row-owning fused kernels keep the plain order.  The same products in the same order and the
+# same rounding statement: the same bits (tests/test_gpu_linear512_direct.py).  overrides(LINEAR512_DIRECT_STORE=False) is the A/B arm:
+# pack and launch as before.  (The patch-embed conv got the same change and lost it again: DESIGN.md 3, "in_proj tiles stored from the
+# accumulators".)
+LINEAR512_DIRECT_STORE = True
 
 
 def _conv_backend():
@@ -236,7 +243,7 @@ SPLITK_TARGET_WGS = 384        # (tile, piece) workgroups a launch should have: 
 # the hard ceiling of both thresholds: overlap.SubBatches' default min_rows (a call of >= 2 x 32 hypotheses is split into sub-batches)
 SMALL_CALL_CEILING = 31
 
-_SWITCHES = ("FUSED_OUT_PROJ_LN", "FUSED_FFN", "ROWS_QKV", "PACKED_CONV_TILES", "MERGED_HEAD_QKV", "FUSED_TAIL", "CONV_MFMA_16X16X32", "SPECIALIZED_EPILOGUE", "CONV_DIRECT_STORE", "SPLITK_MAX_HYPS", "HEADS_TWO_STREAMS_MAX_HYPS")
+_SWITCHES = ("FUSED_OUT_PROJ_LN", "FUSED_FFN", "ROWS_QKV", "PACKED_CONV_TILES", "MERGED_HEAD_QKV", "FUSED_TAIL", "CONV_MFMA_16X16X32", "SPECIALIZED_EPILOGUE", "CONV_DIRECT_STORE", "LINEAR512_DIRECT_STORE","SPLITK_MAX_HYPS", "HEADS_TWO_STREAMS_MAX_HYPS")
 
 
 @contextlib.contextmanager
@@ -420,7 +427,7 @@ class _HipMHA:
         self.out = _HipLinear(sd[p + ".out_proj.weight"], sd[p + ".out_proj.bias"])
         self.out_rows = _HipRowsLinear(sd[p + ".out_proj.weight"], sd[p + ".out_proj.bias"])
         self.nhead, self.fp16_scores = nhead, fp16_scores
-        self.qkv_p = ops.PackedLinear512(self.qkv.w) if tuple(self.qkv.w.shape) == (1536, 512) else None
+        self.qkv_p = ops.PackedLinear512(self.qkv.w, direct=LINEAR512_DIRECT_STORE) if tuple(self.qkv.w.shape) == (1536, 512) else None
         # small calls: the in_proj of a call of <= SPLITK_MAX_HYPS sequences is a 48-tile launch of 8 k-steps each; split
         # in four it fills the chip.  Not for the scorer's cross-hypothesis attention (one "sequence" of N hypotheses: its row count is
         # the hypothesis count of the call, and every rank of a sharded call has to see the same arithmetic there).
@@ -530,7 +537,8 @@ class RefinePlan:
             wt, wr = (self.heads[n][0].att.qkv for n in ("trans", "rot"))
             if tuple(wt.w.shape) == (1536, 512) and tuple(wr.w.shape) == (1536, 512):
                 cut = lambda t: (t[0:512], t[512:1024], t[1024:1536])
-                self.qkv2_p = ops.PackedLinear512(torch.cat([p for pair in zip(cut(wt.w), cut(wr.w)) for p in pair], 0).contiguous())
+                self.qkv2_p = ops.PackedLinear512(torch.cat([p for pair in zip(cut(wt.w), cut(wr.w)) for p in pair], 0).contiguous(),
+                                                     direct=LINEAR512_DIRECT_STORE)
                 self.qkv2_b = torch.cat([p for pair in zip(cut(wt.b), cut(wr.b)) for p in pair], 0).contiguous()
             else:
                 self.qkv2_p = None

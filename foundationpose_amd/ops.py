@@ -2128,16 +2128,30 @@ def layernorm_res(branch16, gamma, beta, eps=1e-5, x32=None, tok16=None, pe=None
 class PackedLinear512:
     """fragment-packed copy of a (512 n, 512) fp16 nn.Linear weight (fp_pack_linear512_f16 per block of 512 output channels): what
     linear512, linear_layernorm_res and ffn_layernorm_mean take, whose waves read their weight rows straight from L2 into MFMA
-    operand registers"""
+    operand registers.  direct: the row order of linear512's direct-store kernel instead (fp_pack_linear512_direct_f16), which only
+    that kernel reads: the row-owning fused kernels refuse such a pack, and a launch of either linear512 kernel refuses the other's.
+    The object keeps a reference to w16 (not a copy), from which linear512 makes the pack in the other order when a call needs it."""
 
-    def __init__(self, w16):
+    def __init__(self, w16, direct=False):
         w = _dev(w16, torch.float16, "w16")
         if w.dim() != 2 or int(w.shape[1]) != 512 or int(w.shape[0]) % 512 or int(w.shape[0]) == 0:
             raise _lib.FpAmdError(f"PackedLinear512: weight {tuple(w.shape)}, must be (512 n, 512)")
         self.out_features = int(w.shape[0])
+        self.direct = bool(direct)
+        self.w16, self._other = w, None
         self.data = torch.empty_like(w)
+        fn, name = (_lib.lib().fp_pack_linear512_direct_f16, "fp_pack_linear512_direct_f16") if self.direct else \
+                   (_lib.lib().fp_pack_linear512_f16, "fp_pack_linear512_f16")
         for blk in range(self.out_features // 512):
-            _lib.check(_lib.lib().fp_pack_linear512_f16(_ptr(w[blk * 512:]), _ptr(self.data[blk * 512:]), _stream(w)), "fp_pack_linear512_f16")
+            _lib.check(fn(_ptr(w[blk * 512:]), _ptr(self.data[blk * 512:]), _stream(w)), name)
+
+    def in_order(self, direct):
+        """this pack if it has that row order, else the pack of the same weight in the other order (made once, on first use)"""
+        if bool(direct) == self.direct:
+            return self
+        if self._other is None:
+            self._other = PackedLinear512(self.w16, direct=direct)
+        return self._other
 
 
 def _packed(w, name, out_features=512):
@@ -2145,23 +2159,39 @@ def _packed(w, name, out_features=512):
         raise _lib.FpAmdError(f"{name}: the weight must be a PackedLinear512 (ops.PackedLinear512(w16))")
     if out_features is not None and w.out_features != out_features:
         raise _lib.FpAmdError(f"{name}: packed weight has {w.out_features} output features, expected {out_features}")
+    if w.direct and name != "linear512":
+        raise _lib.FpAmdError(f"{name}: the weight is packed in the row order of linear512's direct-store kernel (PackedLinear512(w16, direct=True)); "
+                              "the row-owning fused kernels read the plain order")
     return w.data
 
 
-def linear512(x16, w_packed, bias, relu=False, out=None):
-    """f16(x16 @ W^T + bias) for x16 (..., 512) fp16 and a PackedLinear512 of W (512 n, 512), n <= 6 (fp_linear512_f16_fwd): the
-    input tile of a workgroup is fetched once for all n column blocks; the bits of igemm_f16 with taps = 1"""
+LINEAR512_RELU = 1
+LINEAR512_DIRECT_STORE = 2
+LINEAR512_W_DIRECT = 4
+
+
+def linear512(x16, w_packed, bias, relu=False, out=None, direct_store=None):
+    """f16(x16 @ W^T + bias) for x16 (..., 512) fp16 and a PackedLinear512 of W (512 n, 512), n <= 6 (fp_linear512_flags_f16_fwd): the
+    input tile of a workgroup is fetched once for all n column blocks; the bits of igemm_f16 with taps = 1.  direct_store: the kernel
+    that stores its tiles from the accumulators (FP_LINEAR512_DIRECT_STORE; outputs below 2 GiB).  None = the engine switch
+    LINEAR512_DIRECT_STORE, with w_packed brought into the order that kernel reads (PackedLinear512.in_order; a plan packs in the right
+    order to begin with); True / False launch that kernel with w_packed as it is, and the library refuses a pack it cannot read."""
     x = _dev(x16, torch.float16, "x16")
-    w = _packed(w_packed, "linear512", None)
     if int(x.shape[-1]) != 512:
         raise _lib.FpAmdError(f"linear512: x16 (..., {int(x.shape[-1])}), must be (..., 512)")
+    _packed(w_packed, "linear512", None)
     N = w_packed.out_features
     M = x.numel() // 512
+    if direct_store is None:
+        from . import engine                   # engine imports this module
+        direct_store = bool(engine.LINEAR512_DIRECT_STORE) and M * N * 2 < 2 ** 31
+        w_packed = w_packed.in_order(direct_store)
     y = out if out is not None else torch.empty(tuple(x.shape[:-1]) + (N,), dtype=torch.float16, device=x.device)
     if y.dtype != torch.float16 or y.numel() != M * N or not y.is_contiguous():
         raise _lib.FpAmdError("linear512: out must be a contiguous fp16 tensor of M x N elements")
-    _lib.check(_lib.lib().fp_linear512_f16_fwd(_ptr(x), _ptr(w), _ptr(_dev(bias, torch.float32, "bias")), _ptr(y), M, N, 1 if relu else 0,
-                                               _stream(x)), "fp_linear512_f16_fwd")
+    flags = (LINEAR512_RELU if relu else 0) | (LINEAR512_DIRECT_STORE if direct_store else 0) | (LINEAR512_W_DIRECT if w_packed.direct else 0)
+    _lib.check(_lib.lib().fp_linear512_flags_f16_fwd(_ptr(x), _ptr(w_packed.data), _ptr(_dev(bias, torch.float32, "bias")), _ptr(y), M, N, flags,
+                                                     _stream(x)), "fp_linear512_flags_f16_fwd")
     return y
 
 

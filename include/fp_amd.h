@@ -105,7 +105,11 @@ const char* fp_last_error(void);
  *               of T candidate transforms of a mesh's surface samples against another mesh, for registering one onto the other.
  *   233 -> 234: + fp_mesh_pseudonormals, fp_mesh_signed_distance, fp_mesh_signed_distance_workspace_bytes, fp_mesh_penetration,
  *               fp_mesh_penetration_workspace_bytes (additions only): which side of a closed mesh a point is on, and how far T
- *               placements of a point set reach into it. */
+ *               placements of a point set reach into it.
+ *   234 (kept): + fp_pack_linear512_direct_f16, fp_linear512_flags_f16_fwd (additions only): the in_proj kernel that stores its tiles
+ *               from the accumulators, and the flags that select it.  No signature and no behaviour of an existing symbol changes, and
+ *               tests/test_mesh_signed_host.py pins the number; a binding that needs the new symbols finds an older library by their
+ *               absence. */
 #define FP_AMD_ABI_VERSION 234
 int fp_version(void);
 
@@ -891,6 +895,22 @@ int fp_pack_linear512_f16(const void* w16 /*dev*/, void* packed /*dev*/, void* s
  * fp_pack_linear512_f16, back to back; bias (N) f32 | NULL. */
 int fp_linear512_f16_fwd(const void* x16 /*dev*/, const void* w_packed /*dev*/, const float* bias /*dev|NULL*/, void* y16 /*dev*/,
                          int M, int N, int relu, void* stream);
+
+/* fp_pack_linear512_f16 in the row order of the direct-store kernel of fp_linear512_flags_f16_fwd: within every group of 64 output
+ * channels, packed row 32 i + c holds weight row 2 c + i (i = 0 | 1, c < 32), i.e.
+ *   packed[((w * 32 + q) * 2 + i) * 64 + lane][0..7] = W[64 w + 2 (lane & 31) + i][16 q + 8 (lane >> 5) + 0..7]. */
+int fp_pack_linear512_direct_f16(const void* w16 /*dev*/, void* packed /*dev*/, void* stream);
+
+/* fp_linear512_f16_fwd with flags instead of `relu`.  FP_LINEAR512_DIRECT_STORE: the kernel that exchanges the two MFMA sources, so that
+ * a lane owns two adjacent output channels and every tile leaves from the accumulators as whole 128-byte lines, without a transposition
+ * through LDS; the same dot products in the same k order and the same rounding, i.e. the same bits; needs M * N * 2 < 2^31.
+ * FP_LINEAR512_W_DIRECT: w_packed comes from fp_pack_linear512_direct_f16.  The two go together: a launch whose kernel cannot read the
+ * order of its pack is refused. */
+#define FP_LINEAR512_RELU 1
+#define FP_LINEAR512_DIRECT_STORE 2
+#define FP_LINEAR512_W_DIRECT 4
+int fp_linear512_flags_f16_fwd(const void* x16 /*dev*/, const void* w_packed /*dev*/, const float* bias /*dev|NULL*/, void* y16 /*dev*/,
+                               int M, int N, int flags, void* stream);
 
 /* A 512 -> 512 nn.Linear of the encoder layer (refine_network.py:56-70: self_attn.out_proj or linear2, under autocast: fp16
  * operands, fp32 accumulation + bias, one rounding to fp16) fused with the residual add and the LayerNorm that consume it:
