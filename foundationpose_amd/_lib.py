@@ -15,6 +15,16 @@ _lib = None
 
 vp, ci, cf, cd, sz = C.c_void_p, C.c_int, C.c_float, C.c_double, C.c_size_t
 
+
+
+class MeshGridStruct(C.Structure):
+    """fp_mesh_grid of include/fp_amd.h"""
+    _fields_ = [("lo", cf * 3), ("h", cf), ("n", C.c_int32 * 3), ("pad", cf), ("cell_start", vp), ("entries", vp), ("overflow", vp),
+                ("n_entries", C.c_int32), ("n_overflow", C.c_int32)]
+
+
+gp = C.POINTER(MeshGridStruct)
+
 # name -> (restype, argtypes); must list every symbol of include/fp_amd.h (checked by tests/test_abi.py)
 SIGNATURES = {
     "fp_last_error": (C.c_char_p, []),
@@ -50,6 +60,11 @@ SIGNATURES = {
     "fp_mesh_signed_distance": (ci, [vp, ci, vp, ci, vp, vp, vp, ci, vp, vp, vp, vp, vp, vp, sz, vp]),
     "fp_mesh_penetration_workspace_bytes": (sz, [ci, ci]),
     "fp_mesh_penetration": (ci, [vp, ci, vp, ci, vp, vp, vp, ci, vp, ci, vp, vp, vp, vp, vp, vp, sz, vp]),
+    "fp_mesh_grid_count": (ci, [vp, ci, vp, ci, gp, vp, vp]),
+    "fp_mesh_grid_fill_workspace_bytes": (sz, [gp]),
+    "fp_mesh_grid_fill": (ci, [vp, ci, vp, ci, gp, vp, vp, sz, vp]),
+    "fp_mesh_grid_point_distance": (ci, [vp, ci, vp, ci, gp, vp, ci, vp, vp, vp, vp, sz, vp]),
+    "fp_mesh_grid_signed_distance": (ci, [vp, ci, vp, ci, gp, vp, vp, vp, ci, vp, vp, vp, vp, vp, vp, sz, vp]),
     "fp_tsdf_integrate": (ci, [vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, vp, cf, cf, cf, vp, vp, vp, vp, vp]),
     "fp_tsdf_count_triangles": (ci, [vp, vp, ci, ci, ci, cf, vp, vp]),
     "fp_tsdf_emit_triangles": (ci, [vp, vp, vp, vp, ci, ci, ci, vp, cf, cf, vp, C.c_longlong, vp, vp, vp, vp, vp]),

@@ -18,9 +18,13 @@
 // A minimum commutes exactly, so the outputs have one value whatever the chunking and the arrival order: how the faces are cut into
 // chunks depends on Q and F only to fill the chip and never shows in a result.  Compiled with -ffp-contract=off (SRCS_EXACT): the
 // numpy restatement (tests/mesh_distance_model.py) computes the same bits.
+// fp_mesh_grid_point_distance is the same init and finish around k_md_grid_scan, where a lane walks the shells of a uniform grid around
+// its query instead (mesh_grid.h: the walk and why it skips no triangle that could win or tie); the keys are the interface, so every
+// output is made by k_md_finish as above.
 #include <float.h>
 #include "fp_common.h"
 #include "mesh_closest.h"
+#include "mesh_grid.h"
 
 namespace {
 
@@ -56,6 +60,18 @@ __global__ __launch_bounds__(kThreads) void k_md_scan(const float* __restrict__ 
   int best_f = -1;
   scan_chunk<kTile>(p, tile, pos, Nv, faces, f0, f1, tid, best, best_f);   // mesh_closest.h: the one copy
   if (live && best_f >= 0) merge_answer(keys + i, best, best_f);
+}
+
+// fp_mesh_grid_point_distance's scan in place of k_md_scan: a lane owns one query and walks the grid's shells around it (mesh_grid.h)
+__global__ __launch_bounds__(kThreads) void k_md_grid_scan(const float* __restrict__ pos, int Nv, const int32_t* __restrict__ faces, int F,
+                                                           mesh_grid::Grid g, mesh_grid::Tables t, const float* __restrict__ points,
+                                                           int Q, unsigned long long* __restrict__ keys) {
+  const int i = blockIdx.x * kThreads + threadIdx.x;
+  if (i >= Q) return;
+  float best = __builtin_inff();
+  int best_f = -1;
+  mesh_grid::walk(g, t, pos, Nv, faces, F, load3(points + (size_t)i * 3), best, best_f);
+  if (best_f >= 0) merge_answer(keys + i, best, best_f);
 }
 
 __global__ __launch_bounds__(kThreads) void k_md_finish(const float* __restrict__ pos, int Nv, const int32_t* __restrict__ faces,
@@ -111,5 +127,36 @@ extern "C" int fp_mesh_point_distance(const float* pos, int Nv, const int32_t* f
   }
   hipLaunchKernelGGL(k_md_finish, dim3(qtiles), dim3(kThreads), 0, st, pos, Nv, faces, points, Q, keys, dist2, face, closest);
   FP_CHECK_LAUNCH("fp_mesh_point_distance (finish)");
+  return FP_OK;
+}
+
+extern "C" int fp_mesh_grid_point_distance(const float* pos, int Nv, const int32_t* faces, int F, const fp_mesh_grid* grid,
+                                           const float* points, int Q, float* dist2, int32_t* face, float* closest, void* workspace,
+                                           size_t workspace_bytes, void* stream) {
+  const char* name = "fp_mesh_grid_point_distance";
+  FP_REQUIRE(Q >= 0 && Q <= (1 << 30), "%s: Q=%d outside 0..2^30", name, Q);
+  FP_REQUIRE(F >= 0 && F <= (1 << 30), "%s: F=%d outside 0..2^30", name, F);
+  FP_REQUIRE(Nv >= 0, "%s: Nv=%d is negative", name, Nv);
+  if (int st = mesh_grid::check_grid(name, grid)) return st;
+  if (Q == 0) return FP_OK;
+  FP_REQUIRE(points && dist2, "%s: NULL points or dist2", name);
+  FP_REQUIRE(F == 0 || faces, "%s: faces is NULL but F=%d", name, F);
+  FP_REQUIRE(F == 0 || Nv == 0 || pos, "%s: pos is NULL but Nv=%d", name, Nv);
+  const size_t need = fp_mesh_point_distance_workspace_bytes(Q);
+  FP_REQUIRE(workspace && workspace_bytes >= need && ((uintptr_t)workspace & 7) == 0,
+             "%s: workspace too small or not 8-byte aligned (%zu < %zu bytes, see fp_mesh_point_distance_workspace_bytes)", name,
+             workspace_bytes, need);
+  const hipStream_t st = (hipStream_t)stream;
+  unsigned long long* keys = (unsigned long long*)workspace;
+  const int qtiles = fp_cdiv(Q, kThreads);
+  hipLaunchKernelGGL(k_md_init, dim3(qtiles), dim3(kThreads), 0, st, keys, Q);
+  FP_CHECK_LAUNCH("fp_mesh_grid_point_distance (init)");
+  if (F > 0) {
+    hipLaunchKernelGGL(k_md_grid_scan, dim3(qtiles), dim3(kThreads), 0, st, pos, Nv, faces, F, mesh_grid::device_grid(grid),
+                       mesh_grid::device_tables(grid), points, Q, keys);
+    FP_CHECK_LAUNCH("fp_mesh_grid_point_distance (scan)");
+  }
+  hipLaunchKernelGGL(k_md_finish, dim3(qtiles), dim3(kThreads), 0, st, pos, Nv, faces, points, Q, keys, dist2, face, closest);
+  FP_CHECK_LAUNCH("fp_mesh_grid_point_distance (finish)");
   return FP_OK;
 }

@@ -16,11 +16,14 @@
 //     k_pn_finish  one workgroup per transform: each lane re-walks its pairs as k_sd_finish does, then the workgroup reduces in LDS
 //                  with integer atomics only: an add for the number of points inside, a 64-bit maximum on (bits(dd) << 32) | ~i for
 //                  the deepest of them (the larger dd, then the smaller i)
+//   fp_mesh_grid_signed_distance: k_sg_init, k_sd_grid_scan (a lane walks the shells of a uniform grid around its query: mesh_grid.h),
+//     and k_sd_finish unchanged
 // A minimum, a maximum and an integer count commute exactly: every output has one value whatever the chunking and the arrival order.
 // No allocation, no memset, no synchronisation.  Compiled with -ffp-contract=off (SRCS_EXACT): the numpy restatement
 // (tests/mesh_signed_model.py) computes the same bits.
 #include "fp_common.h"
 #include "mesh_closest.h"
+#include "mesh_grid.h"
 
 namespace {
 
@@ -89,6 +92,18 @@ __global__ __launch_bounds__(kThreads) void k_sd_scan(const float* __restrict__ 
   int best_f = -1;
   scan_chunk<kTile>(p, tile, pos, Nv, faces, f0, f1, tid, best, best_f);
   if (live && best_f >= 0) merge_answer(keys + i, best, best_f);
+}
+
+// fp_mesh_grid_signed_distance's scan in place of k_sd_scan: a lane owns one query and walks the grid's shells around it (mesh_grid.h)
+__global__ __launch_bounds__(kThreads) void k_sd_grid_scan(const float* __restrict__ pos, int Nv, const int32_t* __restrict__ faces, int F,
+                                                           mesh_grid::Grid g, mesh_grid::Tables t, const float* __restrict__ points,
+                                                           int Q, unsigned long long* __restrict__ keys) {
+  const int i = blockIdx.x * kThreads + threadIdx.x;
+  if (i >= Q) return;
+  float best = __builtin_inff();
+  int best_f = -1;
+  mesh_grid::walk(g, t, pos, Nv, faces, F, load3(points + (size_t)i * 3), best, best_f);
+  if (best_f >= 0) merge_answer(keys + i, best, best_f);
 }
 
 __global__ __launch_bounds__(kThreads) void k_sd_finish(const float* __restrict__ pos, int Nv, const int32_t* __restrict__ faces,
@@ -205,6 +220,40 @@ extern "C" int fp_mesh_signed_distance(const float* pos, int Nv, const int32_t* 
   hipLaunchKernelGGL(k_sd_finish, dim3(qtiles), dim3(kThreads), 0, st, pos, Nv, faces, vn, en, points, Q,
                      (const unsigned long long*)keys, dist2, face, closest, feature, sign);
   FP_CHECK_LAUNCH("fp_mesh_signed_distance (finish)");
+  return FP_OK;
+}
+
+extern "C" int fp_mesh_grid_signed_distance(const float* pos, int Nv, const int32_t* faces, int F, const fp_mesh_grid* grid, const float* vn,
+                                            const float* en, const float* points, int Q, float* dist2, int32_t* face, float* closest,
+                                            int32_t* feature, int32_t* sign, void* workspace, size_t workspace_bytes, void* stream) {
+  const char* name = "fp_mesh_grid_signed_distance";
+  FP_REQUIRE(Q >= 0 && Q <= (1 << 30), "%s: Q=%d outside 0..2^30", name, Q);
+  FP_REQUIRE(F >= 0 && F <= (1 << 30), "%s: F=%d outside 0..2^30", name, F);
+  FP_REQUIRE(Nv >= 0, "%s: Nv=%d is negative", name, Nv);
+  if (int st = mesh_grid::check_grid(name, grid)) return st;
+  if (Q == 0) return FP_OK;
+  FP_REQUIRE(points && dist2, "%s: NULL points or dist2", name);
+  FP_REQUIRE(F == 0 || faces, "%s: faces is NULL but F=%d", name, F);
+  FP_REQUIRE(F == 0 || Nv == 0 || pos, "%s: pos is NULL but Nv=%d", name, Nv);
+  FP_REQUIRE(F == 0 || Nv == 0 || vn, "%s: vn is NULL but Nv=%d", name, Nv);
+  FP_REQUIRE(F == 0 || en, "%s: en is NULL but F=%d", name, F);
+  const size_t need = fp_mesh_signed_distance_workspace_bytes(Q);
+  FP_REQUIRE(workspace && workspace_bytes >= need && ((uintptr_t)workspace & 7) == 0,
+             "%s: workspace too small or not 8-byte aligned (%zu < %zu bytes, see fp_mesh_signed_distance_workspace_bytes)", name,
+             workspace_bytes, need);
+  const hipStream_t st = (hipStream_t)stream;
+  unsigned long long* keys = (unsigned long long*)workspace;
+  const int qtiles = fp_cdiv(Q, kThreads);
+  hipLaunchKernelGGL(k_sg_init, dim3(qtiles), dim3(kThreads), 0, st, keys, Q);
+  FP_CHECK_LAUNCH("fp_mesh_grid_signed_distance (init)");
+  if (F > 0) {
+    hipLaunchKernelGGL(k_sd_grid_scan, dim3(qtiles), dim3(kThreads), 0, st, pos, Nv, faces, F, mesh_grid::device_grid(grid),
+                       mesh_grid::device_tables(grid), points, Q, keys);
+    FP_CHECK_LAUNCH("fp_mesh_grid_signed_distance (scan)");
+  }
+  hipLaunchKernelGGL(k_sd_finish, dim3(qtiles), dim3(kThreads), 0, st, pos, Nv, faces, vn, en, points, Q,
+                     (const unsigned long long*)keys, dist2, face, closest, feature, sign);
+  FP_CHECK_LAUNCH("fp_mesh_grid_signed_distance (finish)");
   return FP_OK;
 }
 

@@ -251,7 +251,7 @@ class FoundationPose:
         from .reconstruct import align_meshes
         return align_meshes(self.mesh_ori, mesh, device=self.device, **kw)
 
-    def compare_to_mesh(self, mesh, samples=100_000, thresholds=None, seed=0, unit=None, tf=None):
+    def compare_to_mesh(self, mesh, samples=100_000, thresholds=None, seed=0, unit=None, tf=None, accel=None):
         """How the estimator's mesh compares with `mesh` (a SimpleMesh or a mesh-tensor dict in the frame of the mesh handed to
         reset_object, for example the CAD model of an object whose estimator was made by from_reference_views) ->
         ops.MeshComparison (reconstruct.compare_meshes: accuracy = this estimator's mesh against `mesh`, completeness the other way,
@@ -259,11 +259,12 @@ class FoundationPose:
         the centred one.  unit: the length the default thresholds are multiples of; None: the voxel pitch the mesh was fused at, for
         an estimator made by from_reference_views (otherwise pass unit or thresholds).  tf: a (4,4) transform or an
         ops.MeshAlignment (align_to_mesh) from the estimator's mesh into `mesh`'s frame, where the two are not in one frame already.
-        An evaluation call (it synchronises)."""
+        accel="grid": the same report from far fewer pair tests (compare_meshes).  An evaluation call (it synchronises)."""
         from .reconstruct import compare_meshes
         if unit is None and thresholds is None:
             unit = getattr(self.mesh_ori, "voxel", None)
-        return compare_meshes(self.mesh_ori, mesh, samples=samples, thresholds=thresholds, seed=seed, unit=unit, device=self.device, tf=tf)
+        return compare_meshes(self.mesh_ori, mesh, samples=samples, thresholds=thresholds, seed=seed, unit=unit, device=self.device, tf=tf,
+                              accel=accel)
 
     def penetration_into(self, other, poses=None, samples=2048, seed=0, allow_open=False):
         """How far this object, at `poses`, reaches into the object of estimator `other` at other.pose_last (not in the reference)

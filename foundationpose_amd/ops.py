@@ -811,7 +811,7 @@ def _mesh_pos_faces(what, mesh_tensors, pos, faces):
     return pos, faces
 
 
-def mesh_point_distance(points, mesh_tensors=None, pos=None, faces=None, want=MESH_DISTANCE_OUTPUTS, out=None):
+def mesh_point_distance(points, mesh_tensors=None, pos=None, faces=None, want=MESH_DISTANCE_OUTPUTS, out=None, grid=None):
     """fp_mesh_point_distance: the exact distance from the points (Q,3) f32 to the surface of a triangle mesh -> dict of device tensors:
     `dist2` (Q,) f32 the squared distance to the nearest point of any triangle, `face` (Q,) int32 that triangle, `closest` (Q,3) f32
     that point (include/fp_amd.h has the definition: Ericson's region walk in float32, the smallest (dist2, face) wins; +inf / -1 /
@@ -820,7 +820,9 @@ def mesh_point_distance(points, mesh_tensors=None, pos=None, faces=None, want=ME
     dist2 is always computed and returned.  out: a dict of caller-owned buffers for some of the wanted names.  Brute force: Q x F pair
     tests.  The workspace (8 bytes a query) is the library's per-stream scratch, or a fresh allocation inside a stream capture.
     Wrong shapes are refused first, then tensors that are not on the device, of another dtype or not contiguous, then buffers that
-    overlap an input or each other (FpAmdError)."""
+    overlap an input or each other (FpAmdError).  grid: a MeshGrid of this mesh (mesh_grid_build) answers through
+    fp_mesh_grid_point_distance instead: the same bits from far fewer pair tests; a grid built for other pos / faces tensors is
+    refused."""
     what = "mesh_point_distance"
     names = (want,) if isinstance(want, str) else tuple(want)
     for w in names:
@@ -863,12 +865,181 @@ def mesh_point_distance(points, mesh_tensors=None, pos=None, faces=None, want=ME
             out[k] = torch.empty(shapes[k], dtype=_MESH_DISTANCE_DTYPES[k], device=pts.device)
     need = int(_lib.lib().fp_mesh_point_distance_workspace_bytes(Q))
     ws = _workspace(need, pts.device)
+    if grid is not None:
+        g = _grid_for(what, grid, vp_, fc)
+        _lib.check(_lib.lib().fp_mesh_grid_point_distance(_ptr(vp_), Nv, _ptr(fc), F, C.byref(g), _ptr(pts), Q, _ptr(out["dist2"]),
+                                                          _ptr(out.get("face")), _ptr(out.get("closest")), _ptr(ws), need, _stream(pts)),
+                   "fp_mesh_grid_point_distance")
+        return {k: out[k] for k in names}
     _lib.check(_lib.lib().fp_mesh_point_distance(_ptr(vp_), Nv, _ptr(fc), F, _ptr(pts), Q, _ptr(out["dist2"]), _ptr(out.get("face")),
                                                  _ptr(out.get("closest")), _ptr(ws), need, _stream(pts)), "fp_mesh_point_distance")
     return {k: out[k] for k in names}
 
 
-MESH_RESIDUAL_OUTPUTS = ("max_d2", "over", "dist2")
+MESH_GRID_MAX_CELLS = 1 << 21            # FP_MESH_GRID_MAX_CELLS
+MESH_GRID_DEFAULT_PAD = 2.0 ** -16       # of M, the grid box's largest coordinate; the library refuses less than 2^-20
+MESH_GRID_CELL_OVER_FACE = 2.0           # the default cell edge, in mean face box edges
+MESH_GRID_STATUS = {1: "the entries list was too small", 2: "the overflow list was too small",
+                    4: "more than 2^31 - 1 (cell, triangle) entries"}
+
+
+def mesh_grid_shape(pos, faces, cell=None, max_cells=MESH_GRID_MAX_CELLS, pad=None, lo=None, n=None):
+    """The grid mesh_grid_build lays over a mesh, from host arrays pos (Nv,3) f32 and faces (F,3) int -> (lo (3,) f32, h f32, n (3,)
+    int32, pad f32).  The box is that of the finite vertices of the faces whose three indices are valid (none: one unit cell at the
+    origin).  h = cell, or by default MESH_GRID_CELL_OVER_FACE times the mean over those faces (all vertices finite) of the longest
+    edge of the face's bounding box (the box's longest edge when that is zero), times 1.25 until the count fits; n_k = floor((hi_k -
+    lo_k) / h) + 1; a given cell that needs more than max_cells cells is refused.  pad defaults to 2^-16 * M, M = the largest
+    |coordinate| of the grid box in float32.  lo= and n= (with cell=) lay an explicit box instead: triangles outside it land in its
+    boundary cells."""
+    f32 = np.float32
+    pos = np.asarray(pos, f32).reshape(-1, 3)
+    faces = np.asarray(faces, np.int64).reshape(-1, 3)
+    max_cells = int(max_cells)
+    if not 1 <= max_cells <= MESH_GRID_MAX_CELLS:
+        raise _lib.FpAmdError(f"mesh_grid_build: max_cells={max_cells} outside 1..2^21")
+    if (lo is None) != (n is None) or (lo is not None and cell is None):
+        raise _lib.FpAmdError("mesh_grid_build: an explicit box needs lo=, n= and cell= together")
+    if cell is not None and not (np.isfinite(cell) and 2.0 ** -100 <= float(f32(cell)) <= 2.0 ** 100):
+        raise _lib.FpAmdError(f"mesh_grid_build: cell={cell} must be a positive finite length (2^-100..2^100)")
+    if lo is not None:
+        lo = np.asarray(lo, f32).reshape(3)
+        n = np.asarray(n, np.int64).reshape(3)
+        h = f32(cell)
+        if not np.isfinite(lo).all() or (n < 1).any() or int(n.prod()) > max_cells:
+            raise _lib.FpAmdError(f"mesh_grid_build: box lo={lo.tolist()} n={n.tolist()}: lo must be finite and 1 <= cells <= {max_cells}")
+    else:
+        ok = ((faces >= 0) & (faces < len(pos))).all(axis=1) if len(faces) else np.zeros(0, bool)
+        tri = pos[faces[ok]] if ok.any() else np.zeros((0, 3, 3), f32)
+        fin = np.isfinite(tri).all(axis=2)                              # (n, 3): per vertex
+        verts = tri[fin]
+        if len(verts) == 0:
+            lo, ext = np.zeros(3, f32), np.zeros(3)
+        else:
+            lo = verts.min(axis=0).astype(f32)
+            ext = verts.max(axis=0).astype(np.float64) - lo.astype(np.float64)
+        if cell is not None:
+            h = float(f32(cell))
+        else:
+            whole = tri[fin.all(axis=1)].astype(np.float64)
+            h = MESH_GRID_CELL_OVER_FACE * float((whole.max(axis=1) - whole.min(axis=1)).max(axis=1).mean()) if len(whole) else 0.0
+            if not (np.isfinite(h) and h > 0):
+                h = float(ext.max()) if ext.max() > 0 else 1.0
+            h = float(f32(min(max(h, 2.0 ** -100), 2.0 ** 100)))
+        while True:
+            cnt = np.floor(ext / h) + 1
+            if cnt.prod() <= max_cells:
+                break
+            if cell is not None:
+                raise _lib.FpAmdError(f"mesh_grid_build: cell={cell} needs {cnt.astype(np.int64).tolist()} cells, above max_cells={max_cells}")
+            h = float(f32(h * 1.25))
+        n, h = cnt.astype(np.int64), f32(h)
+    with np.errstate(all="ignore"):
+        M = f32(max(np.abs(lo).max(), np.abs(lo + n.astype(f32) * h).max()))
+    if not np.isfinite(M):
+        raise _lib.FpAmdError("mesh_grid_build: the grid's far corner is not finite")
+    pad = f32(MESH_GRID_DEFAULT_PAD) * M if pad is None else f32(pad)
+    if not (np.isfinite(pad) and pad >= f32(2.0 ** -20) * M):
+        raise _lib.FpAmdError(f"mesh_grid_build: pad={pad} is below 2^-20 of the grid's largest coordinate {M} (or not finite)")
+    return lo, h, n.astype(np.int32), f32(pad)
+
+
+class MeshGrid:
+    """A uniform grid over a mesh's triangles (mesh_grid_build): the shape (`lo`, `h`, `n`, `pad`: include/fp_amd.h), the device tables
+    `cell_start` (ncells + 1,), `entries` (n_entries,), `overflow` (n_overflow,) int32, and which pos / faces tensors it was built
+    for (data pointers and shapes: a grid is refused for any other pair)."""
+
+    def __init__(self, lo, h, n, pad, cell_start, entries, overflow, pos, faces):
+        self.lo, self.h, self.n, self.pad = np.asarray(lo, np.float32), np.float32(h), np.asarray(n, np.int32), np.float32(pad)
+        self.cell_start, self.entries, self.overflow = cell_start, entries, overflow
+        self.n_entries, self.n_overflow = int(entries.numel()), int(overflow.numel())
+        self.mesh_key = self.key_of(pos, faces)
+
+    @staticmethod
+    def key_of(pos, faces):
+        return (pos.data_ptr(), tuple(pos.shape), faces.data_ptr(), tuple(faces.shape))
+
+    @property
+    def ncells(self):
+        return int(self.n[0]) * int(self.n[1]) * int(self.n[2])
+
+    def struct(self, entries=None, overflow=None):
+        """the fp_mesh_grid of a call (entries / overflow: other lists than the grid's own, for the fill)"""
+        e = self.entries if entries is None else entries
+        o = self.overflow if overflow is None else overflow
+        g = _lib.MeshGridStruct()
+        g.lo[:] = [float(x) for x in self.lo]
+        g.n[:] = [int(x) for x in self.n]
+        g.h, g.pad = float(self.h), float(self.pad)
+        g.cell_start = self.cell_start.data_ptr()
+        g.entries = e.data_ptr() if e.numel() else None
+        g.overflow = o.data_ptr() if o.numel() else None
+        g.n_entries, g.n_overflow = int(e.numel()), int(o.numel())
+        return g
+
+
+def _grid_for(what, grid, pos, faces):
+    if not isinstance(grid, MeshGrid):
+        raise _lib.FpAmdError(f"{what}: grid must be a MeshGrid (mesh_grid_build), got {type(grid).__name__}")
+    if grid.mesh_key != MeshGrid.key_of(pos, faces):
+        raise _lib.FpAmdError(f"{what}: the grid was built for another mesh (other pos / faces tensors): build one for this mesh")
+    return grid.struct()
+
+
+def mesh_grid_build(mesh_tensors=None, pos=None, faces=None, cell=None, max_cells=MESH_GRID_MAX_CELLS, pad=None, lo=None, n=None):
+    """fp_mesh_grid_count + fp_mesh_grid_fill: a uniform grid over the triangles of a mesh -> MeshGrid, for
+    mesh_point_distance(grid=) and mesh_signed_distance(grid=), which then give the brute force's bits from a few dozen pair tests
+    a query near the surface (include/fp_amd.h has the definition and the proof).  The mesh is mesh_tensors (pos (Nv,3) f32, faces
+    (F,3) int32, on the device) or pos= and faces=.  cell: the cell edge; max_cells, pad, lo, n: mesh_grid_shape, which states the
+    default rule.  The sequence is count, one read of the header, the allocation of exactly n_entries and n_overflow slots, fill, and
+    a read of the status word, which raises FpAmdError when set.  Done once per mesh: it copies the mesh to the host for the box,
+    synchronises twice and allocates, so it is not capturable.  With mesh_tensors the grid is kept in the dict under "grid" and
+    returned from there the next time when every argument is a default: the caller drops the key when pos or faces change."""
+    what = "mesh_grid_build"
+    defaults = cell is None and pad is None and lo is None and n is None and int(max_cells) == MESH_GRID_MAX_CELLS
+    if mesh_tensors is not None and pos is None and faces is None and defaults and isinstance(mesh_tensors.get("grid"), MeshGrid):
+        g = mesh_tensors["grid"]
+        if g.mesh_key == MeshGrid.key_of(mesh_tensors["pos"], mesh_tensors["faces"]):
+            return g
+    pos, faces = _mesh_pos_faces(what, mesh_tensors, pos, faces)
+    for name, t in (("pos", pos), ("faces", faces)):
+        if not torch.is_tensor(t):
+            raise _lib.FpAmdError(f"{what}: {name} must be a tensor, got {type(t).__name__}")
+        if t.dim() != 2 or int(t.shape[1]) != 3:
+            raise _lib.FpAmdError(f"{what}: {name} must be (n,3), got {tuple(t.shape)}")
+    Nv, F = int(pos.shape[0]), int(faces.shape[0])
+    if F > (1 << 30):
+        raise _lib.FpAmdError(f"{what}: {F} faces (at most 2^30)")
+    vp_ = _dev(pos, torch.float32, "pos")
+    fc = _dev(faces, torch.int32, "faces")
+    glo, h, gn, gpad = mesh_grid_shape(vp_.detach().cpu().numpy(), fc.detach().cpu().numpy(), cell, max_cells, pad, lo, n)
+    dev = vp_.device
+    ncells = int(gn[0]) * int(gn[1]) * int(gn[2])
+    cell_start = torch.empty((ncells + 1,), dtype=torch.int32, device=dev)
+    header = torch.empty((4,), dtype=torch.int32, device=dev)
+    none = torch.empty((0,), dtype=torch.int32, device=dev)
+    grid = MeshGrid(glo, h, gn, gpad, cell_start, none, none, vp_, fc)
+    L = _lib.lib()
+    _lib.check(L.fp_mesh_grid_count(_ptr(vp_), Nv, _ptr(fc), F, C.byref(grid.struct()), _ptr(header), _stream(vp_)), "fp_mesh_grid_count")
+    n_entries, n_overflow, status, _ = (int(x) for x in header.cpu())
+    if status:
+        raise _lib.FpAmdError(f"{what}: {MESH_GRID_STATUS.get(status, status)}: use a larger cell")
+    entries = torch.empty((n_entries,), dtype=torch.int32, device=dev)
+    overflow = torch.empty((n_overflow,), dtype=torch.int32, device=dev)
+    g = grid.struct(entries, overflow)
+    need = int(L.fp_mesh_grid_fill_workspace_bytes(C.byref(g)))
+    ws = torch.empty(((need + 3) // 4,), dtype=torch.int32, device=dev)
+    _lib.check(L.fp_mesh_grid_fill(_ptr(vp_), Nv, _ptr(fc), F, C.byref(g), _ptr(header), _ptr(ws), need, _stream(vp_)), "fp_mesh_grid_fill")
+    status = int(header[2])
+    if status:
+        raise _lib.FpAmdError(f"{what}: fp_mesh_grid_fill: " + "; ".join(v for k, v in MESH_GRID_STATUS.items() if status & k)
+                              + " (did pos or faces change between the count and the fill?)")
+    grid = MeshGrid(glo, h, gn, gpad, cell_start, entries, overflow, vp_, fc)
+    if mesh_tensors is not None and defaults:
+        mesh_tensors["grid"] = grid
+    return grid
+
+
+MESH_RESIDUAL_OUTPUTS =("max_d2", "over", "dist2")
 _MESH_RESIDUAL_DTYPES = {"max_d2": torch.float32, "over": torch.int32, "dist2": torch.float32}
 MESH_RESIDUAL_MAX_THRESHOLDS = 4
 
@@ -1165,7 +1336,7 @@ MESH_FEATURES = ("vertex a", "vertex b", "vertex c", "edge ab", "edge bc", "edge
 
 
 def mesh_signed_distance(points, mesh_tensors=None, pos=None, faces=None, tables=None, want=("dist2", "sign"), out=None,
-                         allow_open=False):
+                         allow_open=False, grid=None):
     """fp_mesh_signed_distance: mesh_point_distance and the side of the surface -> dict of device tensors: `dist2`, `face`, `closest`
     as mesh_point_distance gives them (the same bits), `feature` (Q,) int32 the part of the nearest face the closest point lies on
     (MESH_FEATURES; -1 without an answer), `sign` (Q,) int32: -1 inside, +1 outside or on the surface, 0 for a query that no triangle
@@ -1175,7 +1346,8 @@ def mesh_signed_distance(points, mesh_tensors=None, pos=None, faces=None, tables
     passes pos= / faces= in a loop makes them beforehand).  The sign means inside / outside only for a closed, outward-oriented mesh
     that does not cross itself: a mesh whose report is not closed is refused (FpAmdError) unless allow_open=True, and then the sign is
     the side of the nearest face (a boundary edge carries its one face's normal).  want, out, the workspace and the order of the
-    refusals are mesh_point_distance's; dist2 is always computed and returned."""
+    refusals are mesh_point_distance's; dist2 is always computed and returned.  grid: a MeshGrid of this mesh (mesh_grid_build)
+    answers through fp_mesh_grid_signed_distance: the same bits from far fewer pair tests."""
     what = "mesh_signed_distance"
     names, pts, _, vp_, fc, vn, en, out, shapes, (Q, Nv, F, _) = _signed_call(
         what, MESH_SIGNED_OUTPUTS, _MESH_SIGNED_DTYPES, want, points, None, mesh_tensors, pos, faces, tables, allow_open, out, ("dist2",))
@@ -1184,6 +1356,13 @@ def mesh_signed_distance(points, mesh_tensors=None, pos=None, faces=None, tables
             out[k] = torch.empty(shapes[k], dtype=_MESH_SIGNED_DTYPES[k], device=pts.device)
     need = int(_lib.lib().fp_mesh_signed_distance_workspace_bytes(Q))
     ws = _workspace(need, pts.device)
+    if grid is not None:
+        g = _grid_for(what, grid, vp_, fc)
+        _lib.check(_lib.lib().fp_mesh_grid_signed_distance(_ptr(vp_), Nv, _ptr(fc), F, C.byref(g), _ptr(vn), _ptr(en), _ptr(pts), Q,
+                                                           _ptr(out["dist2"]), _ptr(out.get("face")), _ptr(out.get("closest")),
+                                                           _ptr(out.get("feature")), _ptr(out.get("sign")), _ptr(ws), need, _stream(pts)),
+                   "fp_mesh_grid_signed_distance")
+        return {k: out[k] for k in names}
     _lib.check(_lib.lib().fp_mesh_signed_distance(_ptr(vp_), Nv, _ptr(fc), F, _ptr(vn), _ptr(en), _ptr(pts), Q, _ptr(out["dist2"]),
                                                   _ptr(out.get("face")), _ptr(out.get("closest")), _ptr(out.get("feature")),
                                                   _ptr(out.get("sign")), _ptr(ws), need, _stream(pts)), "fp_mesh_signed_distance")

@@ -607,7 +607,16 @@ def align_meshes(a, b, starts=300, samples=(128, 2048), iterations=(12, 20), max
     return ops.MeshAlignment(*(got[k] for k in ops.MeshAlignment._fields))
 
 
-def compare_meshes(a, b, samples=100_000, thresholds=None, seed=0, unit=None, device=None, tf=None):
+def _accel_grid(accel, t, what):
+    """accel=None: no grid (brute force); "grid": ops.mesh_grid_build of the mesh-tensor dict t, kept in it under "grid" """
+    if accel is None:
+        return None
+    if accel != "grid":
+        raise ValueError(f"{what}: accel must be None or 'grid', got {accel!r}")
+    return ops.mesh_grid_build(t)
+
+
+def compare_meshes(a, b, samples=100_000, thresholds=None, seed=0, unit=None, device=None, tf=None, accel=None):
     """How good is mesh a (what was built) against mesh b (the reference) -> ops.MeshComparison: accuracy (the exact distances of
     `samples` surface samples of a to the surface of b: mean / median / p99 / max), completeness (b's samples to a's surface), the
     chamfer distance (the mean of the two means), the Hausdorff distance of the samples, and per threshold precision, recall and
@@ -617,7 +626,9 @@ def compare_meshes(a, b, samples=100_000, thresholds=None, seed=0, unit=None, de
     A setup / evaluation call, and it synchronises: sample_surface reads each mesh back once for its float64 area table, and the two
     distance arrays are read once at the end for the statistics (float64 on the host).  tf: a (4,4) transform or an
     ops.MeshAlignment (align_meshes) that takes a's coordinates into b's frame, applied to a's vertices (in float64, rounded once)
-    before anything is sampled; None: the meshes are in one frame already."""
+    before anything is sampled; None: the meshes are in one frame already.  accel="grid": the distances are answered through a
+    uniform grid over each mesh (ops.mesh_grid_build, built here once per mesh): the same report bit for bit, from far fewer pair
+    tests; None: brute force."""
     what = "compare_meshes"
     samples = _check_count(samples, what, "samples")
     thr = _thresholds(thresholds, unit, what)
@@ -630,12 +641,12 @@ def compare_meshes(a, b, samples=100_000, thresholds=None, seed=0, unit=None, de
     pa, _ = sample_surface(ta, samples, seed)
     pb, _ = sample_surface(tb, samples, seed)
     # the square root through float64: the correctly rounded float32 root whatever the device's float32 sqrt does in its last bit
-    d_ab = ops.mesh_point_distance(pa, tb, want=("dist2",))["dist2"].double().sqrt_().float()
-    d_ba = ops.mesh_point_distance(pb, ta, want=("dist2",))["dist2"].double().sqrt_().float()
+    d_ab = ops.mesh_point_distance(pa, tb, want=("dist2",), grid=_accel_grid(accel, tb, what))["dist2"].double().sqrt_().float()
+    d_ba = ops.mesh_point_distance(pb, ta, want=("dist2",), grid=_accel_grid(accel, ta, what))["dist2"].double().sqrt_().float()
     return ops.MeshComparison.from_distances(d_ab, d_ba, thr)
 
 
-def _signed(points, mesh, what, allow_open):
+def _signed(points, mesh, what, allow_open, accel=None):
     """-> (sign (Q,) int32, dist (Q,) float32) device tensors of the points against a mesh-tensor dict or a SimpleMesh"""
     if not torch.is_tensor(points):
         points = torch.as_tensor(np.asarray(points, dtype=np.float32))
@@ -647,33 +658,34 @@ def _signed(points, mesh, what, allow_open):
     else:
         t = dict(zip(("pos", "faces"), _mesh_arrays(mesh, points.device if points.is_cuda else "cuda", what, "mesh")))
     pts = points.to(device=t["pos"].device, dtype=torch.float32).contiguous()
-    r = ops.mesh_signed_distance(pts, t, want=("dist2", "sign"), allow_open=allow_open)
+    r = ops.mesh_signed_distance(pts, t, want=("dist2", "sign"), allow_open=allow_open, grid=_accel_grid(accel, t, what))
     # the square root through float64, as compare_meshes takes it
     return r["sign"], r["dist2"].double().sqrt_().float()
 
 
-def signed_distance(points, mesh, allow_open=False):
+def signed_distance(points, mesh, allow_open=False, accel=None):
     """The signed distance of the points (Q,3) to the surface of a closed mesh -> (Q,) float32 on the mesh's device: negative inside,
     positive outside, +0 on the surface; +inf for a point that no triangle answers (a NaN point).  mesh: a mesh-tensor dict (pos,
     faces; the pseudonormal tables are computed at the first call and kept in it) or a SimpleMesh.  ops.mesh_signed_distance has the
     definition, the cost (points x faces pair tests) and the refusal of a mesh that is not closed (allow_open=True: the side of the
-    nearest face)."""
-    sign, dist = _signed(points, mesh, "signed_distance", allow_open)
+    nearest face).  accel="grid": answered through a uniform grid over the mesh (ops.mesh_grid_build; built at the first call and kept
+    in a mesh-tensor dict beside the tables): the same bits from far fewer pair tests."""
+    sign, dist = _signed(points, mesh, "signed_distance", allow_open, accel)
     return torch.where(sign < 0, -dist, dist)
 
 
-def contains(points, mesh, allow_open=False):
+def contains(points, mesh, allow_open=False, accel=None):
     """Is each of the points (Q,3) inside the closed mesh -> (Q,) bool on the mesh's device.  A point on the surface, and a point
     that is not finite, is not inside.  See signed_distance."""
-    return _signed(points, mesh, "contains", allow_open)[0] < 0
+    return _signed(points, mesh, "contains", allow_open, accel)[0] < 0
 
 
-def signed_bias(a, b, samples=100_000, seed=0, tf=None, device=None, allow_open=False):
+def signed_bias(a, b, samples=100_000, seed=0, tf=None, device=None, allow_open=False, accel=None):
     """On which side of mesh b (the reference, closed) does the surface of mesh a (what was built) lie -> ops.SignedStats: the mean
     signed distance of `samples` surface samples of a to b's surface (negative inside b: a positive mean says a is inflated, a
     negative one that it is shrunk), the share of the samples inside b, and the 5th, 50th and 95th percentiles.  The samples are
     compare_meshes's accuracy samples (sample_surface, the same seed), so abs(mean) is at most that comparison's accuracy mean; a, b,
-    tf and device as there.  A setup / evaluation call: it synchronises."""
+    tf, device and accel as there.  A setup / evaluation call: it synchronises."""
     what = "signed_bias"
     samples = _check_count(samples, what, "samples")
     if device is None:
@@ -683,7 +695,7 @@ def signed_bias(a, b, samples=100_000, seed=0, tf=None, device=None, allow_open=
         m = torch.as_tensor(_rigid_tf(tf, what), device=ta["pos"].device)
         ta["pos"] = (ta["pos"].double() @ m[:3, :3].T + m[:3, 3]).float().contiguous()
     pa, _ = sample_surface(ta, samples, seed)
-    sign, dist = _signed(pa, tb, what, allow_open)
+    sign, dist = _signed(pa, tb, what, allow_open, accel)
     return ops.SignedStats.of((sign.double() * dist.double()).cpu().numpy())
 
 

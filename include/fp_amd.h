@@ -109,7 +109,10 @@ const char* fp_last_error(void);
  *   234 (kept): + fp_pack_linear512_direct_f16, fp_linear512_flags_f16_fwd (additions only): the in_proj kernel that stores its tiles
  *               from the accumulators, and the flags that select it.  No signature and no behaviour of an existing symbol changes, and
  *               tests/test_mesh_signed_host.py pins the number; a binding that needs the new symbols finds an older library by their
- *               absence. */
+ *               absence.
+ *   234 (kept): + fp_mesh_grid_count, fp_mesh_grid_fill, fp_mesh_grid_fill_workspace_bytes, fp_mesh_grid_point_distance,
+ *               fp_mesh_grid_signed_distance and the struct fp_mesh_grid (additions only): a uniform grid over a mesh's triangles and
+ *               the two point queries answered from it with the brute force's bits.  The number stays for the same reason. */
 #define FP_AMD_ABI_VERSION 234
 int fp_version(void);
 
@@ -324,7 +327,7 @@ int fp_mspd(const float* model_pts /*dev P,3*/, int P, const double* sym_tfs /*d
  * grid runs over (256 queries) x (a chunk of faces), the partial minima merged with 64-bit integer atomic minima on the key
  * (bits(dd) << 32) | f in the workspace -- non-negative floats order as their bits do; there are no floating-point atomics.  An init
  * launch sets the keys, and a finish launch recomputes q for the winning face with the same arithmetic and writes the outputs.  Q * F pair
- * tests of about 80 float32 operations each: the cost is the caller's to weigh (there is no grid or tree).  Q == 0 does nothing.
+ * tests of about 80 float32 operations each: the cost is the caller's to weigh (fp_mesh_grid_point_distance below answers from a uniform grid).  Q == 0 does nothing.
  * No allocation, no host synchronisation (graph-capturable); nothing is written outside the outputs and the workspace
  * (fp_mesh_point_distance_workspace_bytes(Q) bytes = 8 * Q, 8-byte aligned; 0 for Q <= 0).  Argument errors (FP_ERR_INVALID_ARG),
  * before any launch: Q, F or Nv negative, Q or F above 2^30; NULL points / dist2 with Q > 0; NULL faces with F > 0 (and Q > 0); NULL pos
@@ -484,6 +487,98 @@ int fp_mesh_penetration(const float* pos /*dev Nv,3*/, int Nv, const int32_t* fa
                         int32_t* inside /*dev T*/, float* depth2 /*dev T|NULL*/, int32_t* deepest /*dev T|NULL*/,
                         int32_t* sign /*dev T,Q|NULL*/, float* dist2 /*dev T,Q|NULL*/,
                         void* workspace /*dev*/, size_t workspace_bytes, void* stream);
+
+/* A uniform grid over a mesh's triangles, and fp_mesh_point_distance / fp_mesh_signed_distance answered from it: the same outputs, bit
+ * for bit, from a few dozen pair tests a query near the surface instead of F.  The answer is a minimum over (dd, f) keys, which
+ * commutes: which triangles are skipped never shows in a result as long as no skipped triangle could have won or tied, and the stop rule
+ * below is proved to skip only such triangles under one precondition on the float32 closest points (stated at the end).
+ *
+ * The grid (fp_mesh_grid, a host struct): an origin lo[3], a cell edge h, n[3] cells, a slack pad; all float32 / int32, chosen by the
+ * caller.  inv_h = 1.f / h.  M = max_k max(|lo_k|, |lo_k + float(n_k) * h|).  Refused (FP_ERR_INVALID_ARG): a non-finite lo, h or pad;
+ * h outside 2^-100..2^100 (so h <= 0 too); an n_k < 1; more than 2^21 cells; a non-finite M; pad < 2^-20 * M.
+ *   cell_k(x) = (int)clamp(floorf((x - lo_k) * inv_h), 0, n_k - 1), clamped in float before the conversion; cell (ix, iy, iz) has the
+ *   linear index (iz * n_1 + iy) * n_0 + ix.
+ * A triangle f, its vertices read as fp_mesh_point_distance reads them, is
+ *   dropped   when an index is outside 0..Nv-1 (it never counts in the brute force either);
+ *   overflow  when its indices are valid and a vertex coordinate is not finite, or its cell range below covers more than 4096 cells:
+ *             every query tests every triangle of this list (a triangle with an infinite vertex can give a finite dd);
+ *   stored    otherwise, in every cell of cell_k(tmin_k - pad) .. cell_k(tmax_k + pad) on each axis k (tmin, tmax its bounding box; the
+ *             clamp puts a triangle outside the grid's box into boundary cells).
+ * fp_mesh_grid_count zeroes cell_start, adds 1 to every cell of a stored triangle's range, takes the exclusive scan into
+ * cell_start[ncells + 1] and writes header[4] = {n_entries (= cell_start[ncells]), n_overflow, status, 0} on the device.
+ * fp_mesh_grid_fill, given that cell_start, entries[grid->n_entries] and overflow[grid->n_overflow] (the capacities) and a cursor
+ * workspace of (ncells + 1) int32, writes each stored triangle's index into a slot of each of its cells (an atomic cursor per cell: the
+ * order inside a cell is arbitrary and shows in no result) and the overflow list, by the same per-triangle decision (one device
+ * function).  It writes nothing past a capacity or past a cell's own slots: if one was too small it ORs FP_MESH_GRID_ENTRIES_TOO_SMALL
+ * / FP_MESH_GRID_OVERFLOW_TOO_SMALL into header[2] (count sets it to 0, or to FP_MESH_GRID_TOO_MANY_ENTRIES when the lists would hold
+ * more than 2^31 - 1 entries).  Both run on the caller's stream with integer atomics only, allocate nothing and do not synchronise;
+ * the caller reads the header between them to size the lists.
+ *
+ * The walk of a query p.  A non-finite p answers nothing (p - q has an infinite or NaN component for every q, so no dd counts) and
+ * walks nothing.  Otherwise c_k = cell_k(p_k), and for r = 0, 1, 2, ... the cells at Chebyshev distance r from c that are in the grid
+ * are visited; every entry f of a visited cell is tested -- dd exactly as above, on a, b, c, b - a, c - a -- and replaces the best
+ * when dd < best || (dd == best && f < best_f).  After shell r, for each axis k:
+ *   high side, when c_k + r < n_k - 1:  X = lo_k + (float)(c_k + r + 1) * h;  m_k+ = X - p_k
+ *   low side,  when c_k - r > 0:        X = lo_k + (float)(c_k - r) * h;      m_k- = p_k - X
+ * and m = the smallest of those that exist.  The walk stops when none exists (the block is the whole grid) or when m > 0 and
+ * best < m * m (strictly; one float32 product).  Then every triangle of the overflow list is tested the same way.
+ *
+ * Why no skipped triangle wins or ties (u = 2^-24; the high side of axis k, the low side mirrors it).  A stored triangle outside the
+ * block has, on some axis, i0 = cell_k(s) >= j = c_k + r + 1 with s = fl(tmin_k - pad), and j <= n_k - 1, so the clamp did not raise
+ * it: fl(fl(s - lo_k) * inv_h) >= j.  Three roundings (the difference, inv_h, the product) give s - lo_k >= j*h*(1 - 3u), and
+ * j*h <= 2M, so s >= (lo_k + j*h) - 6uM.  X = fl(lo_k + fl(j*h)) has two roundings, of a product <= 2M and of a sum <= M:
+ * X <= (lo_k + j*h) + 3uM.  s itself is one rounding of tmin_k - pad, at most 2uM when |tmin_k - pad| <= 2M (beyond 2M the triangle is
+ * farther than M past X and the claim is immediate).  Together tmin_k >= X + pad - 11uM(1 + O(u)).  With the precondition
+ * q_k >= tmin_k - pad / 4 and pad >= 2^-20 * M = 16uM:  q_k >= X + (12 - 11)uM > X, both float32 numbers, so by the monotonicity of
+ * rounding fl(q_k - p_k) >= fl(X - p_k) = m > 0.  In dd = dot(p - q, p - q) the component's square is then >= fl(m * m), every other
+ * term is >= 0 and adding a non-negative term never lowers a rounded sum: dd >= fl(m * m) > best.  Triangles clamped into boundary
+ * cells are covered because a side whose block touches the grid's end contributes no plane.
+ * THE PRECONDITION: for every (query, triangle) pair with dd <= FLT_MAX, the computed q lies within pad / 4 of the triangle's bounding
+ * box on each axis.  Under it, dist2, face, closest (and feature, sign) equal the brute-force entry points' bit for bit.  The walk's q
+ * is a vertex or a + s*dir (+ w*ac) with s, w in [0, 1] up to rounding, so it leaves the box by a few u of the triangle's largest
+ * coordinate (1.43 * 2^-24 of it is the largest measured over the generated cases); pad = 2^-16 * M, the default of the Python
+ * wrapper, allows 2^-18 * M = 64 u M, some 45 times that.  tests/test_mesh_grid_host.py checks the precondition for every case and grid it uses.
+ *
+ * fp_mesh_grid_point_distance and fp_mesh_grid_signed_distance: the parents' init launch, a scan of 256 queries a workgroup, one per
+ * lane, that walks as above and merges into the same 64-bit key, and the parents' finish kernels unchanged -- the keys workspace is the
+ * interface, so every output is made by the code that makes it today.  The workspace is the parent's (8 * Q bytes).  No allocation, no
+ * host synchronisation (graph-capturable).  grid->n_entries and grid->n_overflow are the lengths of the lists here; an entry outside
+ * 0..F-1 is ignored, and nothing outside the tables' lengths is read.  Argument errors: the parent's, each message beginning with the
+ * entry point's name, and the grid's refusals above, a NULL grid, a NULL cell_start, NULL entries / overflow with a length > 0, a
+ * negative length; for count and fill also a NULL header, and for fill a NULL or misaligned cursor workspace. */
+typedef struct fp_mesh_grid {
+  float lo[3];
+  float h;
+  int32_t n[3];
+  float pad;
+  int32_t* cell_start;   /* dev ncells + 1 */
+  int32_t* entries;      /* dev n_entries | NULL when 0 */
+  int32_t* overflow;     /* dev n_overflow | NULL when 0 */
+  int32_t n_entries;     /* fill: the capacity of entries; queries: its length */
+  int32_t n_overflow;    /* fill: the capacity of overflow; queries: its length */
+} fp_mesh_grid;
+#define FP_MESH_GRID_ENTRIES_TOO_SMALL 1
+#define FP_MESH_GRID_OVERFLOW_TOO_SMALL 2
+#define FP_MESH_GRID_TOO_MANY_ENTRIES 4
+#define FP_MESH_GRID_MAX_CELLS (1 << 21)
+#define FP_MESH_GRID_MAX_CELLS_PER_TRIANGLE 4096
+int fp_mesh_grid_count(const float* pos /*dev Nv,3*/, int Nv, const int32_t* faces /*dev F,3*/, int F,
+                       const fp_mesh_grid* grid /*host; cell_start is written, the lists are not read*/,
+                       int32_t* header /*dev 4*/, void* stream);
+size_t fp_mesh_grid_fill_workspace_bytes(const fp_mesh_grid* grid /*host*/);   /* 4 * (ncells + 1); 0 for a grid that is refused */
+int fp_mesh_grid_fill(const float* pos /*dev Nv,3*/, int Nv, const int32_t* faces /*dev F,3*/, int F,
+                      const fp_mesh_grid* grid /*host; entries and overflow are written*/,
+                      int32_t* header /*dev 4, as count left it*/, void* workspace /*dev*/, size_t workspace_bytes, void* stream);
+int fp_mesh_grid_point_distance(const float* pos /*dev Nv,3*/, int Nv, const int32_t* faces /*dev F,3*/, int F,
+                                const fp_mesh_grid* grid /*host*/, const float* points /*dev Q,3*/, int Q,
+                                float* dist2 /*dev Q*/, int32_t* face /*dev Q|NULL*/, float* closest /*dev Q,3|NULL*/,
+                                void* workspace /*dev*/, size_t workspace_bytes, void* stream);
+int fp_mesh_grid_signed_distance(const float* pos /*dev Nv,3*/, int Nv, const int32_t* faces /*dev F,3*/, int F,
+                                 const fp_mesh_grid* grid /*host*/, const float* vn /*dev Nv,3*/, const float* en /*dev F,3,3*/,
+                                 const float* points /*dev Q,3*/, int Q,
+                                 float* dist2 /*dev Q*/, int32_t* face /*dev Q|NULL*/, float* closest /*dev Q,3|NULL*/,
+                                 int32_t* feature /*dev Q|NULL*/, int32_t* sign /*dev Q|NULL*/,
+                                 void* workspace /*dev*/, size_t workspace_bytes, void* stream);
 
 /* An object's mesh from posed RGB-D reference views: truncated-signed-distance (TSDF) fusion into a caller-owned volume, then marching
  * tetrahedra.  The volume has nz x ny x nx voxels; voxel (ix, iy, iz) has the linear index i = (iz * ny + iy) * nx + ix and, in the

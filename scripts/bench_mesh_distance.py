@@ -7,7 +7,12 @@ one unfused operation per lane and instruction runs at half of it, 78.65e12 a se
 VALU_INSTR_PER_PAIR, the vector instructions the compiled inner loop holds per pair (271 in its two-pair body: the counted
 operations, 16 comparisons, 23 selects and the expansion of the one division), gives the time the issue of those instructions
 alone would take.  Every figure is the time of a call through the Python wrapper.  --host Q F also times the numpy restatement at
-a size it can finish.  Prints one JSON line (profiles/mesh_distance.json keeps a run under "bench")."""
+a size it can finish.  Prints one JSON line (profiles/mesh_distance.json keeps a run under "bench").
+
+--accel grid adds, per size, the same call answered through a uniform grid (ops.mesh_grid_build, then mesh_point_distance(grid=)):
+under "grid" the time of a build (the smaller of three, wall clock around a synchronised call: it reads the header back), the time of
+a query measured as above, the grid's shape and list lengths, and whether the three outputs equal the brute force's bit for bit;
+--out FILE also writes the JSON there (profiles/mesh_grid.json keeps a run)."""
 import argparse, json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -27,6 +32,8 @@ ap.add_argument("--queries", type=int, default=100_000)
 ap.add_argument("--window", type=float, default=0.5)
 ap.add_argument("--views", type=int, default=16)
 ap.add_argument("--host", type=int, nargs=2, default=(1000, 4900), metavar=("Q", "F"))
+ap.add_argument("--accel", choices=("grid",), default=None)
+ap.add_argument("--out", default=None)
 args = ap.parse_args()
 dev = torch.device("cuda:0")
 sc = bench.build_scene(dev, 0, 1)
@@ -76,6 +83,24 @@ with torch.inference_mode():
                                   valu_issue_fraction=valu_ms * VALU_INSTR_PER_PAIR / OPS_PER_PAIR / ms,
                                   pairs_per_s=args.queries * F / (ms * 1e-3),
                                   median_distance_m=float(bufs["dist2"].sqrt().median()))
+        if args.accel == "grid":
+            brute = {k: v.clone() for k, v in ops.mesh_point_distance(queries, t, out=bufs).items()}
+            builds = []
+            for _ in range(3):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                grid = ops.mesh_grid_build(pos=t["pos"], faces=t["faces"])
+                torch.cuda.synchronize()
+                builds.append((time.perf_counter() - t0) * 1e3)
+            g_runs = [timed(lambda: ops.mesh_point_distance(queries, t, out=bufs, grid=grid)) for _ in range(2)]
+            g_d2 = timed(lambda: ops.mesh_point_distance(queries, t, want=("dist2",), out=dict(dist2=bufs["dist2"]), grid=grid))[0]
+            got = ops.mesh_point_distance(queries, t, out=bufs, grid=grid)
+            g_ms = min(x[0] for x in g_runs)
+            out["sizes"][name]["grid"] = dict(
+                build_ms=min(builds), builds_ms=builds, query_ms=g_ms, runs_ms=[x[0] for x in g_runs], reps=g_runs[0][1], dist2_only_ms=g_d2,
+                brute_over_grid=ms / g_ms, cell_m=float(grid.h), cells=[int(x) for x in grid.n], pad_m=float(grid.pad),
+                n_entries=grid.n_entries, n_overflow=grid.n_overflow, entries_per_face=grid.n_entries / max(F, 1),
+                equal_bits=all(bool((got[k].view(torch.int32) == brute[k].view(torch.int32)).all()) for k in brute))
 # the restatement on the host, at a size it can finish
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import mesh_distance_model as mm
@@ -86,3 +111,7 @@ mm.mesh_point_distance(pos, faces, queries[:Qh].cpu().numpy())
 dt = time.perf_counter() - t0
 out["host_restatement"] = dict(Q=Qh, F=len(faces), seconds=dt, pairs_per_s=Qh * len(faces) / dt)
 print(json.dumps(out))
+if args.out:
+    with open(args.out, "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
