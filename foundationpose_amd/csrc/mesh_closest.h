@@ -1,8 +1,10 @@
-// The closest point of a triangle to a point, and how a workgroup passes a mesh's triangles through LDS: the one copy that
+// The device arithmetic of the mesh queries, one copy: the closest point of a triangle to a point, how a workgroup passes a mesh's
+// triangles through LDS, the transformed point of a (transform, point) pair, and the (dd, face) key a scan leaves for a finish.
+// mesh_scan.hip (the nearest face of every query, for all the entry points) and mesh_grid.h (the grid's walk) scan with it;
 // mesh_distance.hip (fp_mesh_point_distance), mesh_symmetry.hip (fp_mesh_transform_residuals), mesh_icp.hip (fp_mesh_icp_step) and
-// mesh_signed.hip (fp_mesh_signed_distance, fp_mesh_penetration) share.  The definition, down to the float32 operation, is in
-// include/fp_amd.h; the files are compiled with -ffp-contract=off (SRCS_EXACT), so the operations written here are the ones executed
-// and the entry points give the same bits for the same (point, triangle) pair.
+// mesh_signed.hip (fp_mesh_signed_distance, fp_mesh_penetration) finish with it.  The definition, down to the float32 operation, is
+// in include/fp_amd.h; the files are compiled with -ffp-contract=off (SRCS_EXACT), so the operations written here are the ones
+// executed and the entry points give the same bits for the same (point, triangle) pair.
 #pragma once
 #include "fp_common.h"
 
@@ -72,6 +74,13 @@ __device__ __forceinline__ v3 cross(const v3& ab, const v3& ac) {
 }
 
 __device__ __forceinline__ v3 load3(const float* p) { return v3{p[0], p[1], p[2]}; }
+
+// the point of a (transform, point) pair: rows 0..2 of the matrix as given; ((r0*x + r1*y) + r2*z) + t, one float32 operation each, in
+// this order
+__device__ __forceinline__ v3 transformed(const float* __restrict__ m, const v3& x) {
+  return v3{((m[0] * x.x + m[1] * x.y) + m[2] * x.z) + m[3], ((m[4] * x.x + m[5] * x.y) + m[6] * x.z) + m[7],
+            ((m[8] * x.x + m[9] * x.y) + m[10] * x.z) + m[11]};
+}
 
 // the vertices of face f, NaN when an index is outside 0..Nv-1
 __device__ __forceinline__ void face_vertices(const float* __restrict__ pos, int Nv, const int32_t* __restrict__ faces, int f, v3& a,
@@ -143,13 +152,15 @@ __device__ __forceinline__ void merge_answer(unsigned long long* __restrict__ ke
   __hip_atomic_fetch_min(key, k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-// faces per chunk for a grid of `tiles` lane tiles: a multiple of `tile`, at least `chunk_min`, and no smaller than what gives about
-// `fill` workgroups
-inline int chunk_faces(int tiles, int F, int tile, int chunk_min, int fill) {
-  const int want = tiles >= fill ? 1 : fp_cdiv(fill, tiles);   // chunks wanted
-  int chunk = fp_cdiv(F > 0 ? F : 1, want);
-  if (chunk < chunk_min) chunk = chunk_min;
-  return fp_cdiv(chunk, tile) * tile;
+// what a finish reads from a key: +inf and face -1 for a query that no triangle answered
+struct Nearest {
+  bool none;
+  int f;
+  float dd;
+};
+__device__ __forceinline__ Nearest nearest_of(unsigned long long key) {
+  const bool none = key == kNoAnswer;
+  return Nearest{none, none ? -1 : (int)(unsigned)(key & 0xffffffffull), none ? __builtin_inff() : __uint_as_float((unsigned)(key >> 32))};
 }
 
 }  // namespace mesh_closest

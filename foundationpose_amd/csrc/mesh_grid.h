@@ -1,6 +1,6 @@
 // A uniform grid over a mesh's triangles and the walk that answers a closest-point query from it: the one copy that mesh_grid.hip (the
-// build: fp_mesh_grid_count, fp_mesh_grid_fill), mesh_distance.hip (fp_mesh_grid_point_distance) and mesh_signed.hip
-// (fp_mesh_grid_signed_distance) share.  The definition -- the cell of a coordinate, the three classes of a triangle, the shells, the
+// build: fp_mesh_grid_count, fp_mesh_grid_fill) and mesh_scan.hip (the scan of fp_mesh_grid_point_distance and
+// fp_mesh_grid_signed_distance) share.  The definition -- the cell of a coordinate, the three classes of a triangle, the shells, the
 // stop rule and why a skipped triangle can neither win nor tie -- is in include/fp_amd.h.  Every pair test is mesh_closest.h's
 // closest_point on a, b, c, b - a, c - a, the operations the brute-force staging performs, so a (query, triangle) pair has the same dd
 // here as there; the files are compiled with -ffp-contract=off (SRCS_EXACT), which also keeps lo + (float)i * h two roundings.

@@ -1,13 +1,10 @@
 // One Gauss-Newton step of point-to-plane ICP for each of T candidate transforms of Q surface samples against a triangle mesh
 // (fp_mesh_icp_step; the definition, down to the operation, is in include/fp_amd.h): the hot path of a multi-start registration of
 // one mesh onto another.  Four launches on the caller's stream, no allocation, no memset, no synchronisation, integer atomics only:
-//   k_mi_init    keys[t * Q + i] = all ones ("no triangle answered yet")
-//   k_mi_scan    grid (tile of kThreads (transform, sample) pairs, chunk of faces), the pair tiling of k_ms_scan (mesh_symmetry.hip):
-//                the pairs are numbered n = t * Q + i and a lane owns one, so T transforms of a few samples still fill the chip.  The
-//                lane forms p = ((r0*x + r1*y) + r2*z) + t per row in registers; the chunk's triangles pass through LDS in tiles of
-//                kTile and are read by broadcast (mesh_closest.h: staging and the closest-point walk, one copy).  The lane keeps the
-//                smallest (dd, face) of its chunk -- faces ascend, `<` keeps the smaller index on a tie -- and merges it into keys[n]
-//                with one 64-bit atomic minimum on (bits(dd) << 32) | face, k_md_scan's key (mesh_distance.hip).
+//   init, scan   mesh_scan.hip's nearest_face_of_pairs: the (transform, sample) pairs are numbered n = t * Q + i and a lane owns one,
+//                so T transforms of a few samples still fill the chip.  The lane forms p = ((r0*x + r1*y) + r2*z) + t per row in
+//                registers and leaves keys[n] = the smallest (bits(dd) << 32) | face over the mesh's triangles (the smaller index on
+//                a tie), or all ones when no triangle answers
 //   k_mi_terms   one workgroup per (transform, chunk of 256 consecutive samples), one lane per sample: p again (the same operations:
 //                the same bits), the closest point q of the winning face recomputed as k_md_finish does, the face's unit normal, the
 //                float32 residual r and Jacobian row J of the pair (or nothing), then icp.hip's own sums (icp_solve.h): the 28
@@ -19,9 +16,8 @@
 // the order of every sum depends on Q alone, so row t has the same bits alone, in any batch, under any chunking of the faces and on
 // every replay.  Compiled with -ffp-contract=off (SRCS_EXACT): the float32 per-pair values are the ones the numpy restatement
 // (tests/mesh_icp_model.py) computes, bit for bit.
-#include "fp_common.h"
 #include "icp_solve.h"
-#include "mesh_closest.h"
+#include "mesh_scan.h"
 
 namespace {
 
@@ -30,46 +26,12 @@ using icp_solve::kRow;
 using icp_solve::kTerms;
 using icp_solve::kWaves;
 
-constexpr int kThreads = 256;          // (transform, sample) pairs per workgroup, one per lane
-constexpr int kTile = 256;             // triangles per LDS tile: 4 float4 each, 16 KiB -- as k_md_scan: 8 workgroups of 4 waves a CU
-constexpr int kChunkMin = 1024;        // the fewest faces a workgroup scans (unless the mesh has fewer)
-constexpr int kFillWorkgroups = 2048;  // workgroups wanted in flight (256 CUs x 8 of 4 waves)
+constexpr int kThreads = 256;          // samples per workgroup of the terms, one per lane
 constexpr int kStore = kTerms + 1;     // the 28 terms and the sum of dd
 constexpr int kCols = kStore + 1;      // + the pair count
 
-static_assert(kChunkMin % kTile == 0, "a chunk is whole tiles");
-static_assert(kTile == kThreads, "a tile is staged by one pass of the workgroup");
 static_assert(kThreads == icp_solve::kThreads, "a chunk of samples is one workgroup of the shared sums");
 static_assert(kCols <= kRow, "a partial row holds the sums and the count");
-
-// rows 0..2 of the matrix as given; ((r0*x + r1*y) + r2*z) + t, one float32 operation each, in this order (as k_ms_scan)
-__device__ __forceinline__ v3 transformed(const float* __restrict__ m, const v3& x) {
-  return v3{((m[0] * x.x + m[1] * x.y) + m[2] * x.z) + m[3], ((m[4] * x.x + m[5] * x.y) + m[6] * x.z) + m[7],
-            ((m[8] * x.x + m[9] * x.y) + m[10] * x.z) + m[11]};
-}
-
-__global__ __launch_bounds__(kThreads) void k_mi_init(unsigned long long* __restrict__ keys, int n_pairs) {
-  const int n = blockIdx.x * kThreads + threadIdx.x;
-  if (n < n_pairs) keys[n] = kNoAnswer;
-}
-
-__global__ __launch_bounds__(kThreads) void k_mi_scan(const float* __restrict__ pos, int Nv, const int32_t* __restrict__ faces, int F,
-                                                      const float* __restrict__ points, int Q, const float* __restrict__ tfs,
-                                                      int n_pairs, int chunk, unsigned long long* __restrict__ keys) {
-  __shared__ float4 tile[kTile * kTileFloat4];
-  const int tid = threadIdx.x;
-  const int n = blockIdx.x * kThreads + tid;          // n_pairs <= 2^30: no overflow
-  const bool live = n < n_pairs;
-  const int nn = live ? n : n_pairs - 1;
-  const int t = nn / Q, i = nn - t * Q;
-  const v3 p = transformed(tfs + (size_t)t * 16, load3(points + (size_t)i * 3));
-  const int f0 = blockIdx.y * chunk;                  // < F <= 2^30: no overflow in f0 + chunk
-  const int f1 = min(F, f0 + chunk);
-  float best = __builtin_inff();
-  int best_f = -1;
-  scan_chunk<kTile>(p, tile, pos, Nv, faces, f0, f1, tid, best, best_f);   // mesh_closest.h: the one copy
-  if (live && best_f >= 0) merge_answer(keys + n, best, best_f);
-}
 
 __global__ __launch_bounds__(kThreads) void k_mi_terms(const float* __restrict__ pos, int Nv, const int32_t* __restrict__ faces,
                                                        const float* __restrict__ points, int Q, const float* __restrict__ tfs, int C,
@@ -88,22 +50,20 @@ __global__ __launch_bounds__(kThreads) void k_mi_terms(const float* __restrict__
     const float* __restrict__ m = tfs + (size_t)t * 16;
     const v3 p = transformed(m, load3(points + (size_t)i * 3));
     const size_t n = (size_t)t * Q + i;
-    const unsigned long long key = keys[n];
-    const bool none = key == kNoAnswer;
-    const int f = none ? -1 : (int)(unsigned)(key & 0xffffffffull);
-    const float dd = none ? __builtin_inff() : __uint_as_float((unsigned)(key >> 32));
+    const Nearest k = nearest_of(keys[n]);
+    const float dd = k.dd;
     if (dist2) dist2[n] = dd;
-    if (face) face[n] = f;
-    if (!none) {
+    if (face) face[n] = k.f;
+    if (!k.none) {
       v3 a, b, cc, q;
-      face_vertices(pos, Nv, faces, f, a, b, cc);
+      face_vertices(pos, Nv, faces, k.f, a, b, cc);
       const v3 ab = sub(b, a), ac = sub(cc, a);
       closest_point(p, a, b, cc, ab, ac, q);
       // the face normal, n = ab x ac in float32, made a unit vector through float64 (division and square root correctly rounded)
-      const float n0 = ab.y * ac.z - ab.z * ac.y, n1 = ab.z * ac.x - ab.x * ac.z, n2 = ab.x * ac.y - ab.y * ac.x;
-      const double nn = icp_solve::dot3d((double)n0, (double)n0, (double)n1, (double)n1, (double)n2, (double)n2);
+      const v3 nf = cross(ab, ac);
+      const double nn = icp_solve::dot3d((double)nf.x, (double)nf.x, (double)nf.y, (double)nf.y, (double)nf.z, (double)nf.z);
       const double len = sqrt(nn);
-      const float m0 = (float)((double)n0 / len), m1 = (float)((double)n1 / len), m2 = (float)((double)n2 / len);
+      const float m0 = (float)((double)nf.x / len), m1 = (float)((double)nf.y / len), m2 = (float)((double)nf.z / len);
       pair = nn > 0.0 && __builtin_isfinite(m0) && __builtin_isfinite(m1) && __builtin_isfinite(m2) && dd <= md2;
       if (pair) {
         const v3 e = sub(q, p);
@@ -158,22 +118,17 @@ extern "C" int fp_mesh_icp_step(const float* pos, int Nv, const int32_t* faces, 
                                 int T, float max_dist, double damping, int min_pairs, double* system, float* tfs_out, float* dist2,
                                 int32_t* face, void* workspace, size_t workspace_bytes, void* stream) {
   const char* name = "fp_mesh_icp_step";
-  FP_REQUIRE(T >= 0 && Q >= 0, "%s: T=%d or Q=%d is negative", name, T, Q);
-  FP_REQUIRE((long long)T * (long long)Q <= (1ll << 30) && T <= (1 << 30), "%s: T=%d times Q=%d is above 2^30", name, T, Q);
-  FP_REQUIRE(F >= 0 && F <= (1 << 30), "%s: F=%d outside 0..2^30", name, F);
-  FP_REQUIRE(Nv >= 0, "%s: Nv=%d is negative", name, Nv);
+  if (int st = mesh_scan::check_pairs(name, T, Q, F, Nv)) return st;
   FP_REQUIRE(max_dist >= 0.f && __builtin_isfinite(max_dist), "%s: max_dist=%g must be finite and >= 0", name, (double)max_dist);
   FP_REQUIRE(damping >= 0.0 && __builtin_isfinite(damping), "%s: damping=%g must be finite and >= 0", name, damping);
   FP_REQUIRE(min_pairs >= 6, "%s: min_pairs=%d must be >= 6 (the unknowns of a step)", name, min_pairs);
   if (T == 0) return FP_OK;
   FP_REQUIRE(tfs_in && system, "%s: NULL tfs_in or system", name);
   FP_REQUIRE(Q == 0 || points, "%s: NULL points", name);
-  FP_REQUIRE(Q == 0 || F == 0 || faces, "%s: faces is NULL but F=%d", name, F);
-  FP_REQUIRE(Q == 0 || F == 0 || Nv == 0 || pos, "%s: pos is NULL but Nv=%d", name, Nv);
-  const size_t need = fp_mesh_icp_workspace_bytes(T, Q);
-  FP_REQUIRE(need == 0 || (workspace && workspace_bytes >= need && ((uintptr_t)workspace & 7) == 0),
-             "%s: workspace too small or not 8-byte aligned (%zu < %zu bytes, see fp_mesh_icp_workspace_bytes)", name, workspace_bytes,
-             need);
+  if (int st = mesh_scan::check_mesh(name, Q > 0, pos, Nv, faces, F)) return st;
+  if (int st = mesh_scan::check_workspace(name, workspace, workspace_bytes, fp_mesh_icp_workspace_bytes(T, Q), 8,
+                                          "fp_mesh_icp_workspace_bytes"))
+    return st;
   if (tfs_out) {   // the finish of one transform writes tfs_out while the terms of another still read tfs_in: no shared bytes
     const uintptr_t a = (uintptr_t)tfs_in, b = (uintptr_t)tfs_out, len = (uintptr_t)T * 16 * sizeof(float);
     FP_REQUIRE(a + len <= b || b + len <= a, "%s: tfs_in and tfs_out overlap", name);
@@ -181,23 +136,13 @@ extern "C" int fp_mesh_icp_step(const float* pos, int Nv, const int32_t* faces, 
   const hipStream_t st = (hipStream_t)stream;
   unsigned long long* keys = (unsigned long long*)workspace;
   double* partial = (double*)((char*)workspace + keys_bytes(T, Q));   // 8 * T * Q bytes on: still 8-byte aligned
-  const int n_pairs = T * Q;
   const int C = fp_cdiv(Q, kThreads);
-  if (n_pairs > 0) {
-    const int tiles = fp_cdiv(n_pairs, kThreads);
-    hipLaunchKernelGGL(k_mi_init, dim3(tiles), dim3(kThreads), 0, st, keys, n_pairs);
-    FP_CHECK_LAUNCH("fp_mesh_icp_step (init)");
-    if (F > 0) {
-      const int chunk = chunk_faces(tiles, F, kTile, kChunkMin, kFillWorkgroups);
-      hipLaunchKernelGGL(k_mi_scan, dim3(tiles, fp_cdiv(F, chunk)), dim3(kThreads), 0, st, pos, Nv, faces, F, points, Q, tfs_in, n_pairs,
-                         chunk, keys);
-      FP_CHECK_LAUNCH("fp_mesh_icp_step (scan)");
-    }
+  if (Q > 0) {
+    if (int e = mesh_scan::nearest_face_of_pairs(name, pos, Nv, faces, F, points, Q, tfs_in, T, keys, st)) return e;
     hipLaunchKernelGGL(k_mi_terms, dim3(T * C), dim3(kThreads), 0, st, pos, Nv, faces, points, Q, tfs_in, C, max_dist,
                        (const unsigned long long*)keys, partial, dist2, face);
-    FP_CHECK_LAUNCH("fp_mesh_icp_step (terms)");
+    if (int e = mesh_scan::launched(name, "terms")) return e;
   }
   hipLaunchKernelGGL(k_mi_finish, dim3(T), dim3(64), 0, st, (const double*)partial, C, tfs_in, damping, min_pairs, system, tfs_out);
-  FP_CHECK_LAUNCH("fp_mesh_icp_step (finish)");
-  return FP_OK;
+  return mesh_scan::launched(name, "finish");
 }

@@ -811,6 +811,132 @@ def _mesh_pos_faces(what, mesh_tensors, pos, faces):
     return pos, faces
 
 
+def _mesh_names(what, want, known, always=(), required=False):
+    """the outputs a mesh query makes, in the order of `known`: those named in want (a name or a sequence of names) and those in always"""
+    names = (want,) if isinstance(want, str) else tuple(want)
+    for w in names:
+        if w not in known:
+            raise ValueError(f"{what}: unknown name {w!r} in want (known: {list(known)})")
+    if required and not names:
+        raise ValueError(f"{what}: want is empty")
+    return tuple(n for n in known if n in names or n in always)
+
+
+def _mesh_n3(what, **tensors):
+    for name, t in tensors.items():
+        if not torch.is_tensor(t):
+            raise _lib.FpAmdError(f"{what}: {name} must be a tensor, got {type(t).__name__}")
+        if t.dim() != 2 or int(t.shape[1]) != 3:
+            raise _lib.FpAmdError(f"{what}: {name} must be (n,3), got {tuple(t.shape)}")
+
+
+# the sizes a mesh query refuses, each with its own words (T is None in a call without transforms) -> the message, or None
+def _mesh_limit_points(T, Q, F):
+    if max(Q, F) > (1 << 30):
+        return f"{Q} points against {F} faces (at most 2^30 of either)"
+    return None
+
+
+def _mesh_limit_pairs(T, Q, F):
+    if T * Q > (1 << 30) or max(T, F) > (1 << 30):
+        return f"{T} transforms of {Q} points against {F} faces (at most 2^30 pairs, transforms or faces)"
+    return None
+
+
+def _mesh_limit_signed(T, Q, F):
+    if (T or 1) * Q > (1 << 30) or max(T or 0, Q, F) > (1 << 30):
+        return f"{T or 1} x {Q} points against {F} faces (at most 2^30 pairs, transforms, points or faces)"
+    return None
+
+
+class _MeshCall(NamedTuple):
+    """_mesh_call's result: the checked device tensors (tfs is None without pairs, vn and en without signed), the out dict with every
+    output of the call in it, the workspace and its size, and the sizes (T is None without pairs)"""
+    points: torch.Tensor
+    tfs: Optional[torch.Tensor]
+    pos: torch.Tensor
+    faces: torch.Tensor
+    vn: Optional[torch.Tensor]
+    en: Optional[torch.Tensor]
+    out: dict
+    ws: torch.Tensor
+    ws_bytes: int
+    Q: int
+    Nv: int
+    F: int
+    T: Optional[int]
+
+
+def _mesh_call(what, points, tfs, mesh_tensors, pos, faces, out, *, names, dtypes, shapes_of, limit, workspace_bytes, pairs=False,
+               among="the wanted outputs", signed=None, workspace=None, workspace_maker=None):
+    """What the mesh queries do before they call the library, in the documented order of refusals: the mesh (mesh_tensors or pos /
+    faces); shapes: points, pos, faces (n,3) and, with pairs, tfs (T,4,4), the sizes `limit` refuses, with signed = (tables, allow_open)
+    the pseudonormal tables, the names and shapes (shapes_of(T, Q)) of the caller's out buffers; device, dtype and contiguity of
+    each; overlaps of an out buffer with an input or another; the caller's workspace (None: the per-stream scratch) against
+    workspace_bytes(T, Q) and the out buffers.  Then the outputs of `names` the caller did not give are allocated.
+    -> _MeshCall."""
+    pos, faces = _mesh_pos_faces(what, mesh_tensors, pos, faces)
+    _mesh_n3(what, points=points, pos=pos, faces=faces)
+    T = None
+    if pairs:
+        if not torch.is_tensor(tfs):
+            raise _lib.FpAmdError(f"{what}: tfs must be a tensor, got {type(tfs).__name__}")
+        if tfs.dim() != 3 or tuple(tfs.shape[1:]) != (4, 4):
+            raise _lib.FpAmdError(f"{what}: tfs must be (T,4,4), got {tuple(tfs.shape)}")
+        T = int(tfs.shape[0])
+    Q, Nv, F = int(points.shape[0]), int(pos.shape[0]), int(faces.shape[0])
+    too_large = limit(T, Q, F)
+    if too_large:
+        raise _lib.FpAmdError(f"{what}: {too_large}")
+    tables = None
+    if signed is not None:
+        tables = _mesh_tables(what, mesh_tensors, pos, faces, *signed)
+        if tuple(tables.vn.shape) != (Nv, 3) or tuple(tables.en.shape) != (F, 3, 3):
+            raise _lib.FpAmdError(f"{what}: the tables are of another mesh: vn {tuple(tables.vn.shape)}, en {tuple(tables.en.shape)} for "
+                                  f"{Nv} vertices and {F} faces")
+    shapes = shapes_of(T, Q)
+    out = dict(out or {})
+    for k, t in out.items():
+        if k not in names:
+            raise _lib.FpAmdError(f"{what}: out has '{k}', which is not among {among} {list(names)}")
+        if not torch.is_tensor(t) or tuple(t.shape) != shapes[k]:
+            raise _lib.FpAmdError(f"{what}: out['{k}'] must be a tensor of shape {shapes[k]}, got "
+                                  f"{tuple(t.shape) if torch.is_tensor(t) else type(t).__name__}")
+    pts = _dev(points, torch.float32, "points")
+    m = _dev(tfs, torch.float32, "tfs") if pairs else None
+    vp_ = _dev(pos, torch.float32, "pos")
+    fc = _dev(faces, torch.int32, "faces")
+    vn = _dev(tables.vn, torch.float32, "tables.vn") if signed is not None else None
+    en = _dev(tables.en, torch.float32, "tables.en") if signed is not None else None
+    for k in list(out):
+        out[k] = _dev(out[k], dtypes[k], f"out['{k}']")
+    srcs = [("points", pts), ("pos", vp_), ("faces", fc), ("tables.vn", vn), ("tables.en", en)]
+    srcs.insert(1 if signed is None else len(srcs), ("tfs", m))   # the signed calls test tfs last, the others after points
+    for k, t in out.items():
+        for name, src in srcs:
+            if _overlap(t, src):
+                raise _lib.FpAmdError(f"{what}: out['{k}'] overlaps {name}")
+        for k2, t2 in out.items():
+            if k2 < k and _overlap(t, t2):
+                raise _lib.FpAmdError(f"{what}: out['{k}'] overlaps out['{k2}']")
+    need = int(workspace_bytes(T, Q))
+    if workspace is None:
+        ws, ws_bytes = _workspace(need, pts.device), need
+    else:
+        if not (torch.is_tensor(workspace) and workspace.is_cuda and workspace.is_contiguous()):
+            raise _lib.FpAmdError(f"{what}: workspace must be a contiguous CUDA(HIP) tensor")
+        ws, ws_bytes = workspace, workspace.numel() * workspace.element_size()
+        if ws_bytes < need:
+            raise _lib.FpAmdError(f"{what}: workspace of {ws_bytes} bytes, {need} needed ({workspace_maker})")
+        for k, t in out.items():
+            if _overlap(t, ws):
+                raise _lib.FpAmdError(f"{what}: out['{k}'] overlaps workspace")
+    for k in names:
+        if k not in out:
+            out[k] = torch.empty(shapes[k], dtype=dtypes[k], device=pts.device)
+    return _MeshCall(pts, m, vp_, fc, vn, en, out, ws, ws_bytes, Q, Nv, F, T)
+
+
 def mesh_point_distance(points, mesh_tensors=None, pos=None, faces=None, want=MESH_DISTANCE_OUTPUTS, out=None, grid=None):
     """fp_mesh_point_distance: the exact distance from the points (Q,3) f32 to the surface of a triangle mesh -> dict of device tensors:
     `dist2` (Q,) f32 the squared distance to the nearest point of any triangle, `face` (Q,) int32 that triangle, `closest` (Q,3) f32
@@ -824,56 +950,19 @@ def mesh_point_distance(points, mesh_tensors=None, pos=None, faces=None, want=ME
     fp_mesh_grid_point_distance instead: the same bits from far fewer pair tests; a grid built for other pos / faces tensors is
     refused."""
     what = "mesh_point_distance"
-    names = (want,) if isinstance(want, str) else tuple(want)
-    for w in names:
-        if w not in MESH_DISTANCE_OUTPUTS:
-            raise ValueError(f"{what}: unknown name {w!r} in want (known: {list(MESH_DISTANCE_OUTPUTS)})")
-    if not names:
-        raise ValueError(f"{what}: want is empty")
-    names = tuple(n for n in MESH_DISTANCE_OUTPUTS if n in names or n == "dist2")
-    pos, faces = _mesh_pos_faces(what, mesh_tensors, pos, faces)
-    for name, t in (("points", points), ("pos", pos), ("faces", faces)):
-        if not torch.is_tensor(t):
-            raise _lib.FpAmdError(f"{what}: {name} must be a tensor, got {type(t).__name__}")
-        if t.dim() != 2 or int(t.shape[1]) != 3:
-            raise _lib.FpAmdError(f"{what}: {name} must be (n,3), got {tuple(t.shape)}")
-    Q, Nv, F = int(points.shape[0]), int(pos.shape[0]), int(faces.shape[0])
-    if max(Q, F) > (1 << 30):
-        raise _lib.FpAmdError(f"{what}: {Q} points against {F} faces (at most 2^30 of either)")
-    out = dict(out or {})
-    shapes = {"dist2": (Q,), "face": (Q,), "closest": (Q, 3)}
-    for k, t in out.items():
-        if k not in names:
-            raise _lib.FpAmdError(f"{what}: out has '{k}', which is not among the wanted outputs {list(names)}")
-        if not torch.is_tensor(t) or tuple(t.shape) != shapes[k]:
-            raise _lib.FpAmdError(f"{what}: out['{k}'] must be a tensor of shape {shapes[k]}, got "
-                                  f"{tuple(t.shape) if torch.is_tensor(t) else type(t).__name__}")
-    pts = _dev(points, torch.float32, "points")
-    vp_ = _dev(pos, torch.float32, "pos")
-    fc = _dev(faces, torch.int32, "faces")
-    for k in list(out):
-        out[k] = _dev(out[k], _MESH_DISTANCE_DTYPES[k], f"out['{k}']")
-    for k, t in out.items():
-        for name, src in (("points", pts), ("pos", vp_), ("faces", fc)):
-            if _overlap(t, src):
-                raise _lib.FpAmdError(f"{what}: out['{k}'] overlaps {name}")
-        for k2, t2 in out.items():
-            if k2 < k and _overlap(t, t2):
-                raise _lib.FpAmdError(f"{what}: out['{k}'] overlaps out['{k2}']")
-    for k in names:
-        if k not in out:
-            out[k] = torch.empty(shapes[k], dtype=_MESH_DISTANCE_DTYPES[k], device=pts.device)
-    need = int(_lib.lib().fp_mesh_point_distance_workspace_bytes(Q))
-    ws = _workspace(need, pts.device)
+    names = _mesh_names(what, want, MESH_DISTANCE_OUTPUTS, always=("dist2",), required=True)
+    c = _mesh_call(what, points, None, mesh_tensors, pos, faces, out, names=names, dtypes=_MESH_DISTANCE_DTYPES,
+                   shapes_of=lambda T, Q: {"dist2": (Q,), "face": (Q,), "closest": (Q, 3)}, limit=_mesh_limit_points,
+                   workspace_bytes=lambda T, Q: _lib.lib().fp_mesh_point_distance_workspace_bytes(Q))
+    outs = (_ptr(c.out["dist2"]), _ptr(c.out.get("face")), _ptr(c.out.get("closest")), _ptr(c.ws), c.ws_bytes, _stream(c.points))
     if grid is not None:
-        g = _grid_for(what, grid, vp_, fc)
-        _lib.check(_lib.lib().fp_mesh_grid_point_distance(_ptr(vp_), Nv, _ptr(fc), F, C.byref(g), _ptr(pts), Q, _ptr(out["dist2"]),
-                                                          _ptr(out.get("face")), _ptr(out.get("closest")), _ptr(ws), need, _stream(pts)),
+        g = _grid_for(what, grid, c.pos, c.faces)
+        _lib.check(_lib.lib().fp_mesh_grid_point_distance(_ptr(c.pos), c.Nv, _ptr(c.faces), c.F, C.byref(g), _ptr(c.points), c.Q, *outs),
                    "fp_mesh_grid_point_distance")
-        return {k: out[k] for k in names}
-    _lib.check(_lib.lib().fp_mesh_point_distance(_ptr(vp_), Nv, _ptr(fc), F, _ptr(pts), Q, _ptr(out["dist2"]), _ptr(out.get("face")),
-                                                 _ptr(out.get("closest")), _ptr(ws), need, _stream(pts)), "fp_mesh_point_distance")
-    return {k: out[k] for k in names}
+    else:
+        _lib.check(_lib.lib().fp_mesh_point_distance(_ptr(c.pos), c.Nv, _ptr(c.faces), c.F, _ptr(c.points), c.Q, *outs),
+                   "fp_mesh_point_distance")
+    return {k: c.out[k] for k in names}
 
 
 MESH_GRID_MAX_CELLS = 1 << 21            # FP_MESH_GRID_MAX_CELLS
@@ -1001,11 +1090,7 @@ def mesh_grid_build(mesh_tensors=None, pos=None, faces=None, cell=None, max_cell
         if g.mesh_key == MeshGrid.key_of(mesh_tensors["pos"], mesh_tensors["faces"]):
             return g
     pos, faces = _mesh_pos_faces(what, mesh_tensors, pos, faces)
-    for name, t in (("pos", pos), ("faces", faces)):
-        if not torch.is_tensor(t):
-            raise _lib.FpAmdError(f"{what}: {name} must be a tensor, got {type(t).__name__}")
-        if t.dim() != 2 or int(t.shape[1]) != 3:
-            raise _lib.FpAmdError(f"{what}: {name} must be (n,3), got {tuple(t.shape)}")
+    _mesh_n3(what, pos=pos, faces=faces)
     Nv, F = int(pos.shape[0]), int(faces.shape[0])
     if F > (1 << 30):
         raise _lib.FpAmdError(f"{what}: {F} faces (at most 2^30)")
@@ -1058,71 +1143,32 @@ def mesh_transform_residuals(points, tfs, mesh_tensors=None, pos=None, faces=Non
     shapes are refused first, then tensors that are not on the device, of another dtype or not contiguous, then buffers that overlap
     an input or each other (FpAmdError)."""
     what = "mesh_transform_residuals"
-    names = (want,) if isinstance(want, str) else tuple(want)
-    for w in names:
-        if w not in MESH_RESIDUAL_OUTPUTS:
-            raise ValueError(f"{what}: unknown name {w!r} in want (known: {list(MESH_RESIDUAL_OUTPUTS)})")
-    if not names:
-        raise ValueError(f"{what}: want is empty")
+    names = _mesh_names(what, want, MESH_RESIDUAL_OUTPUTS, always=("max_d2",), required=True)
     thr = np.zeros(0, np.float32) if thresholds is None else np.asarray(thresholds, dtype=np.float64).reshape(-1).astype(np.float32)
     L = len(thr)
     if L > MESH_RESIDUAL_MAX_THRESHOLDS:
         raise ValueError(f"{what}: {L} thresholds (at most {MESH_RESIDUAL_MAX_THRESHOLDS})")
     if L and not bool((thr >= 0).all()):
         raise ValueError(f"{what}: thresholds must be lengths >= 0, got {thresholds!r}")
-    names = tuple(n for n in MESH_RESIDUAL_OUTPUTS if (n in names or n == "max_d2") and not (n == "over" and L == 0))
-    pos, faces = _mesh_pos_faces(what, mesh_tensors, pos, faces)
-    for name, t in (("points", points), ("pos", pos), ("faces", faces)):
-        if not torch.is_tensor(t):
-            raise _lib.FpAmdError(f"{what}: {name} must be a tensor, got {type(t).__name__}")
-        if t.dim() != 2 or int(t.shape[1]) != 3:
-            raise _lib.FpAmdError(f"{what}: {name} must be (n,3), got {tuple(t.shape)}")
-    if not torch.is_tensor(tfs):
-        raise _lib.FpAmdError(f"{what}: tfs must be a tensor, got {type(tfs).__name__}")
-    if tfs.dim() != 3 or tuple(tfs.shape[1:]) != (4, 4):
-        raise _lib.FpAmdError(f"{what}: tfs must be (T,4,4), got {tuple(tfs.shape)}")
-    Q, Nv, F, T = int(points.shape[0]), int(pos.shape[0]), int(faces.shape[0]), int(tfs.shape[0])
-    if T * Q > (1 << 30) or max(T, F) > (1 << 30):
-        raise _lib.FpAmdError(f"{what}: {T} transforms of {Q} points against {F} faces (at most 2^30 pairs, transforms or faces)")
-    out = dict(out or {})
-    shapes = {"max_d2": (T,), "over": (T, L), "dist2": (T, Q)}
-    for k, t in out.items():
-        if k not in names:
-            raise _lib.FpAmdError(f"{what}: out has '{k}', which is not among the wanted outputs {list(names)}")
-        if not torch.is_tensor(t) or tuple(t.shape) != shapes[k]:
-            raise _lib.FpAmdError(f"{what}: out['{k}'] must be a tensor of shape {shapes[k]}, got "
-                                  f"{tuple(t.shape) if torch.is_tensor(t) else type(t).__name__}")
-    pts = _dev(points, torch.float32, "points")
-    m = _dev(tfs, torch.float32, "tfs")
-    vp_ = _dev(pos, torch.float32, "pos")
-    fc = _dev(faces, torch.int32, "faces")
-    for k in list(out):
-        out[k] = _dev(out[k], _MESH_RESIDUAL_DTYPES[k], f"out['{k}']")
-    for k, t in out.items():
-        for name, src in (("points", pts), ("tfs", m), ("pos", vp_), ("faces", fc)):
-            if _overlap(t, src):
-                raise _lib.FpAmdError(f"{what}: out['{k}'] overlaps {name}")
-        for k2, t2 in out.items():
-            if k2 < k and _overlap(t, t2):
-                raise _lib.FpAmdError(f"{what}: out['{k}'] overlaps out['{k2}']")
-    for k in names:
-        if k not in out:
-            out[k] = torch.empty(shapes[k], dtype=_MESH_RESIDUAL_DTYPES[k], device=pts.device)
+    if L == 0:
+        names = tuple(n for n in names if n != "over")
+    c = _mesh_call(what, points, tfs, mesh_tensors, pos, faces, out, pairs=True, names=names, dtypes=_MESH_RESIDUAL_DTYPES,
+                   shapes_of=lambda T, Q: {"max_d2": (T,), "over": (T, L), "dist2": (T, Q)}, limit=_mesh_limit_pairs,
+                   workspace_bytes=lambda T, Q: _lib.lib().fp_mesh_transform_residuals_workspace_bytes(T, Q))
     thr2 = None
     if L:
         sq = thr * thr                                                        # float32 * float32: one rounding, on the host
         if torch.cuda.is_current_stream_capturing():                          # no host-to-device copy inside a capture: L fills
-            thr2 = torch.empty(L, dtype=torch.float32, device=pts.device)
+            thr2 = torch.empty(L, dtype=torch.float32, device=c.points.device)
             for l in range(L):
                 thr2[l].fill_(float(sq[l]))
         else:
-            thr2 = torch.as_tensor(sq, device=pts.device)
-    need = int(_lib.lib().fp_mesh_transform_residuals_workspace_bytes(T, Q))
-    ws = _workspace(need, pts.device)
-    _lib.check(_lib.lib().fp_mesh_transform_residuals(_ptr(vp_), Nv, _ptr(fc), F, _ptr(pts), Q, _ptr(m), T, _ptr(thr2), L,
-                                                      _ptr(out["max_d2"]), _ptr(out.get("over")), _ptr(out.get("dist2")), _ptr(ws), need,
-                                                      _stream(pts)), "fp_mesh_transform_residuals")
-    return {k: out[k] for k in names}
+            thr2 = torch.as_tensor(sq, device=c.points.device)
+    _lib.check(_lib.lib().fp_mesh_transform_residuals(_ptr(c.pos), c.Nv, _ptr(c.faces), c.F, _ptr(c.points), c.Q, _ptr(c.tfs), c.T,
+                                                      _ptr(thr2), L, _ptr(c.out["max_d2"]), _ptr(c.out.get("over")),
+                                                      _ptr(c.out.get("dist2")), _ptr(c.ws), c.ws_bytes, _stream(c.points)),
+               "fp_mesh_transform_residuals")
+    return {k: c.out[k] for k in names}
 
 
 MESH_ICP_OUTPUTS = ("dist2", "face")
@@ -1149,64 +1195,16 @@ def mesh_icp_step(points, tfs, mesh_tensors=None, pos=None, faces=None, *, max_d
     buffers that overlap an input or each other (FpAmdError)."""
     what = "mesh_icp_step"
     md, dmp, mp = _check_icp(max_dist, damping, min_pairs, what)
-    names = (want,) if isinstance(want, str) else tuple(want)
-    for w in names:
-        if w not in MESH_ICP_OUTPUTS:
-            raise ValueError(f"{what}: unknown name {w!r} in want (known: {list(MESH_ICP_OUTPUTS)})")
-    names = tuple(n for n in MESH_ICP_OUTPUTS if n in names)
-    pos, faces = _mesh_pos_faces(what, mesh_tensors, pos, faces)
-    for name, t in (("points", points), ("pos", pos), ("faces", faces)):
-        if not torch.is_tensor(t):
-            raise _lib.FpAmdError(f"{what}: {name} must be a tensor, got {type(t).__name__}")
-        if t.dim() != 2 or int(t.shape[1]) != 3:
-            raise _lib.FpAmdError(f"{what}: {name} must be (n,3), got {tuple(t.shape)}")
-    if not torch.is_tensor(tfs):
-        raise _lib.FpAmdError(f"{what}: tfs must be a tensor, got {type(tfs).__name__}")
-    if tfs.dim() != 3 or tuple(tfs.shape[1:]) != (4, 4):
-        raise _lib.FpAmdError(f"{what}: tfs must be (T,4,4), got {tuple(tfs.shape)}")
-    Q, Nv, F, T = int(points.shape[0]), int(pos.shape[0]), int(faces.shape[0]), int(tfs.shape[0])
-    if T * Q > (1 << 30) or max(T, F) > (1 << 30):
-        raise _lib.FpAmdError(f"{what}: {T} transforms of {Q} points against {F} faces (at most 2^30 pairs, transforms or faces)")
-    out = dict(out or {})
-    shapes = {"tfs_out": (T, 4, 4), "system": (T, 40), "dist2": (T, Q), "face": (T, Q)}
-    made = ("tfs_out", "system") + names
-    for k, t in out.items():
-        if k not in made:
-            raise _lib.FpAmdError(f"{what}: out has '{k}', which is not among the outputs {list(made)}")
-        if not torch.is_tensor(t) or tuple(t.shape) != shapes[k]:
-            raise _lib.FpAmdError(f"{what}: out['{k}'] must be a tensor of shape {shapes[k]}, got "
-                                  f"{tuple(t.shape) if torch.is_tensor(t) else type(t).__name__}")
-    pts = _dev(points, torch.float32, "points")
-    m = _dev(tfs, torch.float32, "tfs")
-    vp_ = _dev(pos, torch.float32, "pos")
-    fc = _dev(faces, torch.int32, "faces")
-    for k in list(out):
-        out[k] = _dev(out[k], _MESH_ICP_DTYPES[k], f"out['{k}']")
-    for k, t in out.items():
-        for name, src in (("points", pts), ("tfs", m), ("pos", vp_), ("faces", fc)):
-            if _overlap(t, src):
-                raise _lib.FpAmdError(f"{what}: out['{k}'] overlaps {name}")
-        for k2, t2 in out.items():
-            if k2 < k and _overlap(t, t2):
-                raise _lib.FpAmdError(f"{what}: out['{k}'] overlaps out['{k2}']")
-    need = int(_lib.lib().fp_mesh_icp_workspace_bytes(T, Q))
-    if workspace is None:
-        ws, ws_bytes = _workspace(need, pts.device), need
-    else:
-        if not (torch.is_tensor(workspace) and workspace.is_cuda and workspace.is_contiguous()):
-            raise _lib.FpAmdError(f"{what}: workspace must be a contiguous CUDA(HIP) tensor")
-        ws, ws_bytes = workspace, workspace.numel() * workspace.element_size()
-        if ws_bytes < need:
-            raise _lib.FpAmdError(f"{what}: workspace of {ws_bytes} bytes, {need} needed (mesh_icp_workspace)")
-        for k, t in out.items():
-            if _overlap(t, ws):
-                raise _lib.FpAmdError(f"{what}: out['{k}'] overlaps workspace")
-    for k in made:
-        if k not in out:
-            out[k] = torch.empty(shapes[k], dtype=_MESH_ICP_DTYPES[k], device=pts.device)
-    _lib.check(_lib.lib().fp_mesh_icp_step(_ptr(vp_), Nv, _ptr(fc), F, _ptr(pts), Q, _ptr(m), T, md, dmp, mp, _ptr(out["system"]),
-                                           _ptr(out["tfs_out"]), _ptr(out.get("dist2")), _ptr(out.get("face")), _ptr(ws), ws_bytes,
-                                           _stream(pts)), "fp_mesh_icp_step")
+    names = _mesh_names(what, want, MESH_ICP_OUTPUTS)
+    c = _mesh_call(what, points, tfs, mesh_tensors, pos, faces, out, pairs=True, names=("tfs_out", "system") + names,
+                   among="the outputs", dtypes=_MESH_ICP_DTYPES,
+                   shapes_of=lambda T, Q: {"tfs_out": (T, 4, 4), "system": (T, 40), "dist2": (T, Q), "face": (T, Q)},
+                   limit=_mesh_limit_pairs, workspace_bytes=lambda T, Q: _lib.lib().fp_mesh_icp_workspace_bytes(T, Q),
+                   workspace=workspace, workspace_maker="mesh_icp_workspace")
+    out = c.out
+    _lib.check(_lib.lib().fp_mesh_icp_step(_ptr(c.pos), c.Nv, _ptr(c.faces), c.F, _ptr(c.points), c.Q, _ptr(c.tfs), c.T, md, dmp, mp,
+                                           _ptr(out["system"]), _ptr(out["tfs_out"]), _ptr(out.get("dist2")), _ptr(out.get("face")),
+                                           _ptr(c.ws), c.ws_bytes, _stream(c.points)), "fp_mesh_icp_step")
     if names:
         return out["tfs_out"], out["system"], {k: out[k] for k in names}
     return out["tfs_out"], out["system"]
@@ -1274,62 +1272,6 @@ def _mesh_tables(what, mesh_tensors, pos, faces, tables, allow_open):
     return tables
 
 
-def _signed_call(what, known, dtypes, want, points, tfs, mesh_tensors, pos, faces, tables, allow_open, out, always):
-    """the argument checks that mesh_signed_distance and mesh_penetration share -> (names, pts, m, vp_, fc, vn, en, out, sizes)"""
-    names = (want,) if isinstance(want, str) else tuple(want)
-    for w in names:
-        if w not in known:
-            raise ValueError(f"{what}: unknown name {w!r} in want (known: {list(known)})")
-    names = tuple(n for n in known if n in names or n in always)
-    pos, faces = _mesh_pos_faces(what, mesh_tensors, pos, faces)
-    for name, t in (("points", points), ("pos", pos), ("faces", faces)):
-        if not torch.is_tensor(t):
-            raise _lib.FpAmdError(f"{what}: {name} must be a tensor, got {type(t).__name__}")
-        if t.dim() != 2 or int(t.shape[1]) != 3:
-            raise _lib.FpAmdError(f"{what}: {name} must be (n,3), got {tuple(t.shape)}")
-    T = None
-    if tfs is not None or what == "mesh_penetration":
-        if not torch.is_tensor(tfs):
-            raise _lib.FpAmdError(f"{what}: tfs must be a tensor, got {type(tfs).__name__}")
-        if tfs.dim() != 3 or tuple(tfs.shape[1:]) != (4, 4):
-            raise _lib.FpAmdError(f"{what}: tfs must be (T,4,4), got {tuple(tfs.shape)}")
-        T = int(tfs.shape[0])
-    Q, Nv, F = int(points.shape[0]), int(pos.shape[0]), int(faces.shape[0])
-    if (T or 1) * Q > (1 << 30) or max(T or 0, Q, F) > (1 << 30):
-        raise _lib.FpAmdError(f"{what}: {T or 1} x {Q} points against {F} faces (at most 2^30 pairs, transforms, points or faces)")
-    tables = _mesh_tables(what, mesh_tensors, pos if mesh_tensors is None else None, faces if mesh_tensors is None else None, tables,
-                          allow_open)
-    if tuple(tables.vn.shape) != (Nv, 3) or tuple(tables.en.shape) != (F, 3, 3):
-        raise _lib.FpAmdError(f"{what}: the tables are of another mesh: vn {tuple(tables.vn.shape)}, en {tuple(tables.en.shape)} for "
-                              f"{Nv} vertices and {F} faces")
-    shapes = ({"dist2": (Q,), "face": (Q,), "closest": (Q, 3), "feature": (Q,), "sign": (Q,)} if T is None else
-              {"inside": (T,), "depth2": (T,), "deepest": (T,), "sign": (T, Q), "dist2": (T, Q)})
-    out = dict(out or {})
-    for k, t in out.items():
-        if k not in names:
-            raise _lib.FpAmdError(f"{what}: out has '{k}', which is not among the wanted outputs {list(names)}")
-        if not torch.is_tensor(t) or tuple(t.shape) != shapes[k]:
-            raise _lib.FpAmdError(f"{what}: out['{k}'] must be a tensor of shape {shapes[k]}, got "
-                                  f"{tuple(t.shape) if torch.is_tensor(t) else type(t).__name__}")
-    pts = _dev(points, torch.float32, "points")
-    m = _dev(tfs, torch.float32, "tfs") if T is not None else None
-    vp_ = _dev(pos, torch.float32, "pos")
-    fc = _dev(faces, torch.int32, "faces")
-    vn = _dev(tables.vn, torch.float32, "tables.vn")
-    en = _dev(tables.en, torch.float32, "tables.en")
-    for k in list(out):
-        out[k] = _dev(out[k], dtypes[k], f"out['{k}']")
-    srcs = [("points", pts), ("pos", vp_), ("faces", fc), ("tables.vn", vn), ("tables.en", en)] + ([("tfs", m)] if m is not None else [])
-    for k, t in out.items():
-        for name, src in srcs:
-            if _overlap(t, src):
-                raise _lib.FpAmdError(f"{what}: out['{k}'] overlaps {name}")
-        for k2, t2 in out.items():
-            if k2 < k and _overlap(t, t2):
-                raise _lib.FpAmdError(f"{what}: out['{k}'] overlaps out['{k2}']")
-    return names, pts, m, vp_, fc, vn, en, out, shapes, (Q, Nv, F, T)
-
-
 MESH_SIGNED_OUTPUTS = ("dist2", "face", "closest", "feature", "sign")
 _MESH_SIGNED_DTYPES = {"dist2": torch.float32, "face": torch.int32, "closest": torch.float32, "feature": torch.int32, "sign": torch.int32}
 MESH_FEATURES = ("vertex a", "vertex b", "vertex c", "edge ab", "edge bc", "edge ca", "interior")
@@ -1349,24 +1291,20 @@ def mesh_signed_distance(points, mesh_tensors=None, pos=None, faces=None, tables
     refusals are mesh_point_distance's; dist2 is always computed and returned.  grid: a MeshGrid of this mesh (mesh_grid_build)
     answers through fp_mesh_grid_signed_distance: the same bits from far fewer pair tests."""
     what = "mesh_signed_distance"
-    names, pts, _, vp_, fc, vn, en, out, shapes, (Q, Nv, F, _) = _signed_call(
-        what, MESH_SIGNED_OUTPUTS, _MESH_SIGNED_DTYPES, want, points, None, mesh_tensors, pos, faces, tables, allow_open, out, ("dist2",))
-    for k in names:
-        if k not in out:
-            out[k] = torch.empty(shapes[k], dtype=_MESH_SIGNED_DTYPES[k], device=pts.device)
-    need = int(_lib.lib().fp_mesh_signed_distance_workspace_bytes(Q))
-    ws = _workspace(need, pts.device)
+    names = _mesh_names(what, want, MESH_SIGNED_OUTPUTS, always=("dist2",))
+    c = _mesh_call(what, points, None, mesh_tensors, pos, faces, out, signed=(tables, allow_open), names=names,
+                   dtypes=_MESH_SIGNED_DTYPES,
+                   shapes_of=lambda T, Q: {"dist2": (Q,), "face": (Q,), "closest": (Q, 3), "feature": (Q,), "sign": (Q,)},
+                   limit=_mesh_limit_signed, workspace_bytes=lambda T, Q: _lib.lib().fp_mesh_signed_distance_workspace_bytes(Q))
+    rest = (_ptr(c.vn), _ptr(c.en), _ptr(c.points), c.Q, _ptr(c.out["dist2"]), _ptr(c.out.get("face")), _ptr(c.out.get("closest")),
+            _ptr(c.out.get("feature")), _ptr(c.out.get("sign")), _ptr(c.ws), c.ws_bytes, _stream(c.points))
     if grid is not None:
-        g = _grid_for(what, grid, vp_, fc)
-        _lib.check(_lib.lib().fp_mesh_grid_signed_distance(_ptr(vp_), Nv, _ptr(fc), F, C.byref(g), _ptr(vn), _ptr(en), _ptr(pts), Q,
-                                                           _ptr(out["dist2"]), _ptr(out.get("face")), _ptr(out.get("closest")),
-                                                           _ptr(out.get("feature")), _ptr(out.get("sign")), _ptr(ws), need, _stream(pts)),
+        g = _grid_for(what, grid, c.pos, c.faces)
+        _lib.check(_lib.lib().fp_mesh_grid_signed_distance(_ptr(c.pos), c.Nv, _ptr(c.faces), c.F, C.byref(g), *rest),
                    "fp_mesh_grid_signed_distance")
-        return {k: out[k] for k in names}
-    _lib.check(_lib.lib().fp_mesh_signed_distance(_ptr(vp_), Nv, _ptr(fc), F, _ptr(vn), _ptr(en), _ptr(pts), Q, _ptr(out["dist2"]),
-                                                  _ptr(out.get("face")), _ptr(out.get("closest")), _ptr(out.get("feature")),
-                                                  _ptr(out.get("sign")), _ptr(ws), need, _stream(pts)), "fp_mesh_signed_distance")
-    return {k: out[k] for k in names}
+    else:
+        _lib.check(_lib.lib().fp_mesh_signed_distance(_ptr(c.pos), c.Nv, _ptr(c.faces), c.F, *rest), "fp_mesh_signed_distance")
+    return {k: c.out[k] for k in names}
 
 
 MESH_PENETRATION_OUTPUTS = ("inside", "depth2", "deepest", "sign", "dist2")
@@ -1392,27 +1330,16 @@ def mesh_penetration(points, tfs, mesh_tensors=None, pos=None, faces=None, table
     returned.  out: a dict of caller-owned buffers for some of the wanted names; workspace: mesh_penetration_workspace (None: the
     library's per-stream scratch, or a fresh allocation inside a stream capture).  T x Q x F pair tests."""
     what = "mesh_penetration"
-    names, pts, m, vp_, fc, vn, en, out, shapes, (Q, Nv, F, T) = _signed_call(
-        what, MESH_PENETRATION_OUTPUTS, _MESH_PENETRATION_DTYPES, want, points, tfs, mesh_tensors, pos, faces, tables, allow_open, out,
-        ("inside",))
-    need = int(_lib.lib().fp_mesh_penetration_workspace_bytes(T, Q))
-    if workspace is None:
-        ws, ws_bytes = _workspace(need, pts.device), need
-    else:
-        if not (torch.is_tensor(workspace) and workspace.is_cuda and workspace.is_contiguous()):
-            raise _lib.FpAmdError(f"{what}: workspace must be a contiguous CUDA(HIP) tensor")
-        ws, ws_bytes = workspace, workspace.numel() * workspace.element_size()
-        if ws_bytes < need:
-            raise _lib.FpAmdError(f"{what}: workspace of {ws_bytes} bytes, {need} needed (mesh_penetration_workspace)")
-        for k, t in out.items():
-            if _overlap(t, ws):
-                raise _lib.FpAmdError(f"{what}: out['{k}'] overlaps workspace")
-    for k in names:
-        if k not in out:
-            out[k] = torch.empty(shapes[k], dtype=_MESH_PENETRATION_DTYPES[k], device=pts.device)
-    _lib.check(_lib.lib().fp_mesh_penetration(_ptr(vp_), Nv, _ptr(fc), F, _ptr(vn), _ptr(en), _ptr(pts), Q, _ptr(m), T,
-                                              _ptr(out["inside"]), _ptr(out.get("depth2")), _ptr(out.get("deepest")),
-                                              _ptr(out.get("sign")), _ptr(out.get("dist2")), _ptr(ws), ws_bytes, _stream(pts)),
+    names = _mesh_names(what, want, MESH_PENETRATION_OUTPUTS, always=("inside",))
+    c = _mesh_call(what, points, tfs, mesh_tensors, pos, faces, out, pairs=True, signed=(tables, allow_open), names=names,
+                   dtypes=_MESH_PENETRATION_DTYPES,
+                   shapes_of=lambda T, Q: {"inside": (T,), "depth2": (T,), "deepest": (T,), "sign": (T, Q), "dist2": (T, Q)},
+                   limit=_mesh_limit_signed, workspace_bytes=lambda T, Q: _lib.lib().fp_mesh_penetration_workspace_bytes(T, Q),
+                   workspace=workspace, workspace_maker="mesh_penetration_workspace")
+    out = c.out
+    _lib.check(_lib.lib().fp_mesh_penetration(_ptr(c.pos), c.Nv, _ptr(c.faces), c.F, _ptr(c.vn), _ptr(c.en), _ptr(c.points), c.Q,
+                                              _ptr(c.tfs), c.T, _ptr(out["inside"]), _ptr(out.get("depth2")), _ptr(out.get("deepest")),
+                                              _ptr(out.get("sign")), _ptr(out.get("dist2")), _ptr(c.ws), c.ws_bytes, _stream(c.points)),
                "fp_mesh_penetration")
     return {k: out[k] for k in names}
 

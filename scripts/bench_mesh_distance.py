@@ -24,7 +24,7 @@ from foundationpose_amd.reconstruct import reconstruct_object, sample_surface
 from foundationpose_amd.Utils import get_mesh_handle
 
 OPS_PER_PAIR = 81             # the float32 operations of the definition (include/fp_amd.h), a division counted as one
-VALU_INSTR_PER_PAIR = 135.5   # v_* instructions of k_md_scan's inner loop per pair (hipcc -S with the Makefile's flags)
+VALU_INSTR_PER_PAIR = 135.5   # v_* instructions of k_scan's inner loop (mesh_scan.hip) per pair (hipcc -S with the Makefile's flags)
 VALU_OPS_PER_S = 157.3e12 / 2   # one unfused float32 operation a lane and instruction
 
 ap = argparse.ArgumentParser()
