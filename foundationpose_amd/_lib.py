@@ -65,6 +65,9 @@ SIGNATURES = {
     "fp_mesh_grid_fill": (ci, [vp, ci, vp, ci, gp, vp, vp, sz, vp]),
     "fp_mesh_grid_point_distance": (ci, [vp, ci, vp, ci, gp, vp, ci, vp, vp, vp, vp, sz, vp]),
     "fp_mesh_grid_signed_distance": (ci, [vp, ci, vp, ci, gp, vp, vp, vp, ci, vp, vp, vp, vp, vp, vp, sz, vp]),
+    "fp_mesh_grid_transform_residuals": (ci, [vp, ci, vp, ci, gp, vp, ci, vp, ci, vp, ci, vp, vp, vp, vp, sz, vp]),
+    "fp_mesh_grid_icp_step": (ci, [vp, ci, vp, ci, gp, vp, ci, vp, ci, cf, cd, ci, vp, vp, vp, vp, vp, sz, vp]),
+    "fp_mesh_grid_penetration": (ci, [vp, ci, vp, ci, gp, vp, vp, vp, ci, vp, ci, vp, vp, vp, vp, vp, vp, sz, vp]),
     "fp_tsdf_integrate": (ci, [vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, vp, cf, cf, cf, vp, vp, vp, vp, vp]),
     "fp_tsdf_count_triangles": (ci, [vp, vp, ci, ci, ci, cf, vp, vp]),
     "fp_tsdf_emit_triangles": (ci, [vp, vp, vp, vp, ci, ci, ci, vp, cf, cf, vp, C.c_longlong, vp, vp, vp, vp, vp]),

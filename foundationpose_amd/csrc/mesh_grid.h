@@ -1,7 +1,8 @@
 // A uniform grid over a mesh's triangles and the walk that answers a closest-point query from it: the one copy that mesh_grid.hip (the
-// build: fp_mesh_grid_count, fp_mesh_grid_fill) and mesh_scan.hip (the scan of fp_mesh_grid_point_distance and
-// fp_mesh_grid_signed_distance) share.  The definition -- the cell of a coordinate, the three classes of a triangle, the shells, the
-// stop rule and why a skipped triangle can neither win nor tie -- is in include/fp_amd.h.  Every pair test is mesh_closest.h's
+// build: fp_mesh_grid_count, fp_mesh_grid_fill) and mesh_scan.hip (the scan of fp_mesh_grid_point_distance,
+// fp_mesh_grid_signed_distance, fp_mesh_grid_transform_residuals, fp_mesh_grid_icp_step and fp_mesh_grid_penetration) share.  The
+// definition -- the cell of a coordinate, the three classes of a triangle, the shells, the stop rule and why a skipped triangle can
+// neither win nor tie -- is in include/fp_amd.h.  Every pair test is mesh_closest.h's
 // closest_point on a, b, c, b - a, c - a, the operations the brute-force staging performs, so a (query, triangle) pair has the same dd
 // here as there; the files are compiled with -ffp-contract=off (SRCS_EXACT), which also keeps lo + (float)i * h two roundings.
 #pragma once
@@ -140,7 +141,7 @@ __device__ __forceinline__ void walk(const Grid& g, const Tables& t, const float
   for (int j = 0; j < t.n_overflow; ++j) test_face(p, pos, Nv, faces, F, t.overflow[j], best, best_f);
 }
 
-// ---- the host side: one check of a caller's fp_mesh_grid for the four entry points
+// ---- the host side: one check of a caller's fp_mesh_grid for every entry point that takes one
 inline long long cells_of(const fp_mesh_grid* g) { return (long long)g->n[0] * (long long)g->n[1] * (long long)g->n[2]; }
 
 inline int check_grid(const char* name, const fp_mesh_grid* g) {

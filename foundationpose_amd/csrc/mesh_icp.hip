@@ -16,6 +16,8 @@
 // the order of every sum depends on Q alone, so row t has the same bits alone, in any batch, under any chunking of the faces and on
 // every replay.  Compiled with -ffp-contract=off (SRCS_EXACT): the float32 per-pair values are the ones the numpy restatement
 // (tests/mesh_icp_model.py) computes, bit for bit.
+// fp_mesh_grid_icp_step is the same call with a grid: the scan then walks the shells of a uniform grid around each p (mesh_grid.h);
+// the keys are the interface, so the terms, the sums and the solve are the kernels above.
 #include "icp_solve.h"
 #include "mesh_scan.h"
 
@@ -107,18 +109,11 @@ __global__ __launch_bounds__(64) void k_mi_finish(const double* __restrict__ par
 inline size_t keys_bytes(int T, int Q) { return (size_t)T * (size_t)Q * sizeof(unsigned long long); }
 inline size_t workspace_of(int T, int Q) { return keys_bytes(T, Q) + (size_t)T * (size_t)fp_cdiv(Q, kThreads) * kRow * sizeof(double); }
 
-}  // namespace
-
-extern "C" size_t fp_mesh_icp_workspace_bytes(int T, int Q) {
-  if (T <= 0 || Q <= 0 || (long long)T * (long long)Q > (1ll << 30)) return 0;
-  return workspace_of(T, Q);
-}
-
-extern "C" int fp_mesh_icp_step(const float* pos, int Nv, const int32_t* faces, int F, const float* points, int Q, const float* tfs_in,
-                                int T, float max_dist, double damping, int min_pairs, double* system, float* tfs_out, float* dist2,
-                                int32_t* face, void* workspace, size_t workspace_bytes, void* stream) {
-  const char* name = "fp_mesh_icp_step";
-  if (int st = mesh_scan::check_pairs(name, T, Q, F, Nv)) return st;
+// fp_mesh_icp_step (gridded: no) and fp_mesh_grid_icp_step (gridded: yes) are one call, the scan exchanged
+int icp_step(const char* name, bool gridded, const float* pos, int Nv, const int32_t* faces, int F, const fp_mesh_grid* grid,
+             const float* points, int Q, const float* tfs_in, int T, float max_dist, double damping, int min_pairs, double* system,
+             float* tfs_out, float* dist2, int32_t* face, void* workspace, size_t workspace_bytes, void* stream) {
+  if (int st = mesh_scan::check_pairs(name, T, Q, F, Nv, gridded, grid)) return st;
   FP_REQUIRE(max_dist >= 0.f && __builtin_isfinite(max_dist), "%s: max_dist=%g must be finite and >= 0", name, (double)max_dist);
   FP_REQUIRE(damping >= 0.0 && __builtin_isfinite(damping), "%s: damping=%g must be finite and >= 0", name, damping);
   FP_REQUIRE(min_pairs >= 6, "%s: min_pairs=%d must be >= 6 (the unknowns of a step)", name, min_pairs);
@@ -138,11 +133,33 @@ extern "C" int fp_mesh_icp_step(const float* pos, int Nv, const int32_t* faces, 
   double* partial = (double*)((char*)workspace + keys_bytes(T, Q));   // 8 * T * Q bytes on: still 8-byte aligned
   const int C = fp_cdiv(Q, kThreads);
   if (Q > 0) {
-    if (int e = mesh_scan::nearest_face_of_pairs(name, pos, Nv, faces, F, points, Q, tfs_in, T, keys, st)) return e;
+    if (int e = mesh_scan::nearest_face_of_pairs(name, pos, Nv, faces, F, gridded ? grid : nullptr, points, Q, tfs_in, T, keys, st)) return e;
     hipLaunchKernelGGL(k_mi_terms, dim3(T * C), dim3(kThreads), 0, st, pos, Nv, faces, points, Q, tfs_in, C, max_dist,
                        (const unsigned long long*)keys, partial, dist2, face);
     if (int e = mesh_scan::launched(name, "terms")) return e;
   }
   hipLaunchKernelGGL(k_mi_finish, dim3(T), dim3(64), 0, st, (const double*)partial, C, tfs_in, damping, min_pairs, system, tfs_out);
   return mesh_scan::launched(name, "finish");
+}
+
+}  // namespace
+
+extern "C" size_t fp_mesh_icp_workspace_bytes(int T, int Q) {
+  if (T <= 0 || Q <= 0 || (long long)T * (long long)Q > (1ll << 30)) return 0;
+  return workspace_of(T, Q);
+}
+
+extern "C" int fp_mesh_icp_step(const float* pos, int Nv, const int32_t* faces, int F, const float* points, int Q, const float* tfs_in,
+                                int T, float max_dist, double damping, int min_pairs, double* system, float* tfs_out, float* dist2,
+                                int32_t* face, void* workspace, size_t workspace_bytes, void* stream) {
+  return icp_step("fp_mesh_icp_step", false, pos, Nv, faces, F, nullptr, points, Q, tfs_in, T, max_dist, damping, min_pairs, system,
+                  tfs_out, dist2, face, workspace, workspace_bytes, stream);
+}
+
+extern "C" int fp_mesh_grid_icp_step(const float* pos, int Nv, const int32_t* faces, int F, const fp_mesh_grid* grid, const float* points,
+                                     int Q, const float* tfs_in, int T, float max_dist, double damping, int min_pairs, double* system,
+                                     float* tfs_out, float* dist2, int32_t* face, void* workspace, size_t workspace_bytes,
+                                     void* stream) {
+  return icp_step("fp_mesh_grid_icp_step", true, pos, Nv, faces, F, grid, points, Q, tfs_in, T, max_dist, damping, min_pairs, system,
+                  tfs_out, dist2, face, workspace, workspace_bytes, stream);
 }

@@ -17,11 +17,11 @@ constexpr int kChunkMin = 1024;   // the fewest faces a workgroup scans (unless 
 // grid: NULL scans every face, a checked grid (mesh_grid::check_grid) walks its shells instead: the same keys.
 int nearest_face_of_points(const char* name, const float* pos, int Nv, const int32_t* faces, int F, const fp_mesh_grid* grid,
                            const float* points, int Q, unsigned long long* keys, hipStream_t st);
-int nearest_face_of_pairs(const char* name, const float* pos, int Nv, const int32_t* faces, int F, const float* points, int Q,
-                          const float* tfs, int T, unsigned long long* keys, hipStream_t st);
+int nearest_face_of_pairs(const char* name, const float* pos, int Nv, const int32_t* faces, int F, const fp_mesh_grid* grid,
+                          const float* points, int Q, const float* tfs, int T, unsigned long long* keys, hipStream_t st);
 // cell[n] is left as bits(dd) of the nearest face, or the bits of +inf
-int nearest_dist2_of_pairs(const char* name, const float* pos, int Nv, const int32_t* faces, int F, const float* points, int Q,
-                           const float* tfs, int T, unsigned* cell, hipStream_t st);
+int nearest_dist2_of_pairs(const char* name, const float* pos, int Nv, const int32_t* faces, int F, const fp_mesh_grid* grid,
+                           const float* points, int Q, const float* tfs, int T, unsigned* cell, hipStream_t st);
 
 // FP_CHECK_LAUNCH with the entry point's name at run time: a failed launch is reported as "<name> (<step>) launch failed: ..."
 static inline int launched(const char* name, const char* step) {
@@ -55,12 +55,15 @@ static inline int check_points(const char* name, const float* pos, int Nv, const
   return check_mesh(name, true, pos, Nv, faces, F);
 }
 
-// the sizes of a "pairs" call; the caller returns FP_OK at T == 0 once its own values are checked, then checks its pointers and check_mesh
-static inline int check_pairs(const char* name, int T, int Q, int F, int Nv) {
+// the sizes of a "pairs" call and the grid of one that takes one (gridded); the caller returns FP_OK at T == 0 once its own values
+// are checked, then checks its pointers and check_mesh
+static inline int check_pairs(const char* name, int T, int Q, int F, int Nv, bool gridded, const fp_mesh_grid* grid) {
   FP_REQUIRE(T >= 0 && Q >= 0, "%s: T=%d or Q=%d is negative", name, T, Q);
   FP_REQUIRE((long long)T * (long long)Q <= (1ll << 30) && T <= (1 << 30), "%s: T=%d times Q=%d is above 2^30", name, T, Q);
   FP_REQUIRE(F >= 0 && F <= (1 << 30), "%s: F=%d outside 0..2^30", name, F);
   FP_REQUIRE(Nv >= 0, "%s: Nv=%d is negative", name, Nv);
+  if (gridded)
+    if (int st = mesh_grid::check_grid(name, grid)) return st;
   return FP_OK;
 }
 

@@ -1,5 +1,5 @@
-// The nearest face of every query: the scan that fp_mesh_point_distance, fp_mesh_signed_distance, their grid forms,
-// fp_mesh_transform_residuals, fp_mesh_icp_step and fp_mesh_penetration all begin with (mesh_scan.h has the host functions; the
+// The nearest face of every query: the scan that fp_mesh_point_distance, fp_mesh_signed_distance, fp_mesh_transform_residuals,
+// fp_mesh_icp_step, fp_mesh_penetration and the grid form of each all begin with (mesh_scan.h has the host functions; the
 // definition, down to the float32 operation, is in include/fp_amd.h).  Two launches on the caller's stream, no allocation, no
 // synchronisation, integer atomics only:
 //   k_init       every cell of the workspace = "no triangle answered yet"
@@ -13,8 +13,9 @@
 //                of the selects into short exec-masked regions, skipped when no lane of the wave needs them; the values are the same).
 //                The lane keeps the smallest (dd, face) of its chunk -- faces ascend, so `<` keeps the smaller index on a tie -- and
 //                merges it into its cell with one atomic minimum.
-//   k_grid_scan  in place of k_scan: a lane owns one query and walks the shells of a uniform grid around it (mesh_grid.h: the walk and
-//                why it skips no triangle that could win or tie)
+//   k_grid_scan  in place of k_scan: a lane owns one query (a point, or a pair's p' formed as in k_scan) and walks the shells of a
+//                uniform grid around it (mesh_grid.h: the walk and why it skips no triangle that could win or tie; the proof is per
+//                query point, so p' needs nothing new)
 // The scans are templates over two things.  Where a lane's query comes from (kPairs): point n of `points`, or the pair n = t * Q + i,
 // p = ((r0*x + r1*y) + r2*z) + t per row of transform t, so that T transforms of a few samples still fill a workgroup.  And what the
 // lane leaves (Cells): a 64-bit minimum on (bits(dd) << 32) | face (FaceKeys: floats >= 0 order as their bits do), or, for the
@@ -112,7 +113,7 @@ __global__ __launch_bounds__(kThreads) void k_grid_scan(const float* __restrict_
 
 using mesh_scan::launched;
 
-// init, then if F > 0 the scan: over every face, or (points only) through the grid
+// init, then if F > 0 the scan: over every face, or through the grid
 template <bool kPairs, class Cells>
 int scan(const char* name, const float* pos, int Nv, const int32_t* faces, int F, const fp_mesh_grid* grid, const float* points, int Q,
          const float* tfs, int count, typename Cells::Cell* cells, hipStream_t st) {
@@ -120,12 +121,10 @@ int scan(const char* name, const float* pos, int Nv, const int32_t* faces, int F
   hipLaunchKernelGGL(k_init<Cells>, dim3(tiles), dim3(kThreads), 0, st, cells, count);
   if (int e = launched(name, "init")) return e;
   if (F == 0) return FP_OK;
-  if constexpr (!kPairs) {
-    if (grid) {
-      hipLaunchKernelGGL((k_grid_scan<kPairs, Cells>), dim3(tiles), dim3(kThreads), 0, st, pos, Nv, faces, F, mesh_grid::device_grid(grid),
-                         mesh_grid::device_tables(grid), points, Q, tfs, count, cells);
-      return launched(name, "scan");
-    }
+  if (grid) {
+    hipLaunchKernelGGL((k_grid_scan<kPairs, Cells>), dim3(tiles), dim3(kThreads), 0, st, pos, Nv, faces, F, mesh_grid::device_grid(grid),
+                       mesh_grid::device_tables(grid), points, Q, tfs, count, cells);
+    return launched(name, "scan");
   }
   const int chunk = chunk_faces(tiles, F);
   hipLaunchKernelGGL((k_scan<kPairs, Cells>), dim3(tiles, fp_cdiv(F, chunk)), dim3(kThreads), 0, st, pos, Nv, faces, F, points, Q, tfs,
@@ -142,14 +141,14 @@ int nearest_face_of_points(const char* name, const float* pos, int Nv, const int
   return scan<false, FaceKeys>(name, pos, Nv, faces, F, grid, points, Q, nullptr, Q, keys, st);
 }
 
-int nearest_face_of_pairs(const char* name, const float* pos, int Nv, const int32_t* faces, int F, const float* points, int Q,
-                          const float* tfs, int T, unsigned long long* keys, hipStream_t st) {
-  return scan<true, FaceKeys>(name, pos, Nv, faces, F, nullptr, points, Q, tfs, T * Q, keys, st);
+int nearest_face_of_pairs(const char* name, const float* pos, int Nv, const int32_t* faces, int F, const fp_mesh_grid* grid,
+                          const float* points, int Q, const float* tfs, int T, unsigned long long* keys, hipStream_t st) {
+  return scan<true, FaceKeys>(name, pos, Nv, faces, F, grid, points, Q, tfs, T * Q, keys, st);
 }
 
-int nearest_dist2_of_pairs(const char* name, const float* pos, int Nv, const int32_t* faces, int F, const float* points, int Q,
-                           const float* tfs, int T, unsigned* cell, hipStream_t st) {
-  return scan<true, Dist2Cells>(name, pos, Nv, faces, F, nullptr, points, Q, tfs, T * Q, cell, st);
+int nearest_dist2_of_pairs(const char* name, const float* pos, int Nv, const int32_t* faces, int F, const fp_mesh_grid* grid,
+                           const float* points, int Q, const float* tfs, int T, unsigned* cell, hipStream_t st) {
+  return scan<true, Dist2Cells>(name, pos, Nv, faces, F, grid, points, Q, tfs, T * Q, cell, st);
 }
 
 }  // namespace mesh_scan

@@ -15,6 +15,7 @@
 //                  the deepest of them (the larger dd, then the smaller i)
 //   fp_mesh_grid_signed_distance: fp_mesh_signed_distance with a grid: the scan walks the shells of a uniform grid around each query
 //     (mesh_grid.h), and k_sd_finish is unchanged
+//   fp_mesh_grid_penetration: fp_mesh_penetration with a grid: the same walk around each transformed point, and k_pn_finish unchanged
 // A minimum, a maximum and an integer count commute exactly: every output has one value whatever the chunking and the arrival order.
 // No allocation, no memset, no synchronisation.  Compiled with -ffp-contract=off (SRCS_EXACT): the numpy restatement
 // (tests/mesh_signed_model.py) computes the same bits.
@@ -142,6 +143,28 @@ int signed_distance(const char* name, bool gridded, const float* pos, int Nv, co
   return mesh_scan::launched(name, "finish");
 }
 
+// fp_mesh_penetration (gridded: no) and fp_mesh_grid_penetration (gridded: yes) are one call, the scan exchanged
+int penetration(const char* name, bool gridded, const float* pos, int Nv, const int32_t* faces, int F, const fp_mesh_grid* grid,
+                const float* vn, const float* en, const float* points, int Q, const float* tfs, int T, int32_t* inside, float* depth2,
+                int32_t* deepest, int32_t* sign, float* dist2, void* workspace, size_t workspace_bytes, void* stream) {
+  if (int st = mesh_scan::check_pairs(name, T, Q, F, Nv, gridded, grid)) return st;
+  if (T == 0) return FP_OK;
+  FP_REQUIRE(inside, "%s: NULL inside", name);
+  FP_REQUIRE(Q == 0 || (points && tfs), "%s: NULL points or tfs", name);
+  if (int st = mesh_scan::check_mesh(name, Q > 0, pos, Nv, faces, F)) return st;
+  if (int st = check_tables(name, Q > 0, vn, Nv, en, F)) return st;
+  if (int st = mesh_scan::check_workspace(name, workspace, workspace_bytes, fp_mesh_penetration_workspace_bytes(T, Q), 8,
+                                          "fp_mesh_penetration_workspace_bytes"))
+    return st;
+  const hipStream_t st = (hipStream_t)stream;
+  unsigned long long* keys = (unsigned long long*)workspace;
+  if (Q > 0)
+    if (int e = mesh_scan::nearest_face_of_pairs(name, pos, Nv, faces, F, gridded ? grid : nullptr, points, Q, tfs, T, keys, st)) return e;
+  hipLaunchKernelGGL(k_pn_finish, dim3(T), dim3(kThreads), 0, st, pos, Nv, faces, vn, en, points, Q, tfs,
+                     (const unsigned long long*)keys, inside, depth2, deepest, sign, dist2);
+  return mesh_scan::launched(name, "finish");
+}
+
 }  // namespace
 
 extern "C" size_t fp_mesh_signed_distance_workspace_bytes(int Q) { return Q > 0 ? (size_t)Q * sizeof(unsigned long long) : 0; }
@@ -169,21 +192,14 @@ extern "C" int fp_mesh_penetration(const float* pos, int Nv, const int32_t* face
                                    const float* points, int Q, const float* tfs, int T, int32_t* inside, float* depth2,
                                    int32_t* deepest, int32_t* sign, float* dist2, void* workspace, size_t workspace_bytes,
                                    void* stream) {
-  const char* name = "fp_mesh_penetration";
-  if (int st = mesh_scan::check_pairs(name, T, Q, F, Nv)) return st;
-  if (T == 0) return FP_OK;
-  FP_REQUIRE(inside, "%s: NULL inside", name);
-  FP_REQUIRE(Q == 0 || (points && tfs), "%s: NULL points or tfs", name);
-  if (int st = mesh_scan::check_mesh(name, Q > 0, pos, Nv, faces, F)) return st;
-  if (int st = check_tables(name, Q > 0, vn, Nv, en, F)) return st;
-  if (int st = mesh_scan::check_workspace(name, workspace, workspace_bytes, fp_mesh_penetration_workspace_bytes(T, Q), 8,
-                                          "fp_mesh_penetration_workspace_bytes"))
-    return st;
-  const hipStream_t st = (hipStream_t)stream;
-  unsigned long long* keys = (unsigned long long*)workspace;
-  if (Q > 0)
-    if (int e = mesh_scan::nearest_face_of_pairs(name, pos, Nv, faces, F, points, Q, tfs, T, keys, st)) return e;
-  hipLaunchKernelGGL(k_pn_finish, dim3(T), dim3(kThreads), 0, st, pos, Nv, faces, vn, en, points, Q, tfs,
-                     (const unsigned long long*)keys, inside, depth2, deepest, sign, dist2);
-  return mesh_scan::launched(name, "finish");
+  return penetration("fp_mesh_penetration", false, pos, Nv, faces, F, nullptr, vn, en, points, Q, tfs, T, inside, depth2, deepest, sign,
+                     dist2, workspace, workspace_bytes, stream);
+}
+
+extern "C" int fp_mesh_grid_penetration(const float* pos, int Nv, const int32_t* faces, int F, const fp_mesh_grid* grid, const float* vn,
+                                        const float* en, const float* points, int Q, const float* tfs, int T, int32_t* inside,
+                                        float* depth2, int32_t* deepest, int32_t* sign, float* dist2, void* workspace,
+                                        size_t workspace_bytes, void* stream) {
+  return penetration("fp_mesh_grid_penetration", true, pos, Nv, faces, F, grid, vn, en, points, Q, tfs, T, inside, depth2, deepest, sign,
+                     dist2, workspace, workspace_bytes, stream);
 }

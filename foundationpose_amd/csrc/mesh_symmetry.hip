@@ -11,6 +11,8 @@
 //                counts, reduced through LDS with integer atomics; dist2, where asked for, is the cells written out.
 // A minimum, a maximum and an integer count commute exactly, so the outputs have one value whatever the chunking and the arrival
 // order.  Compiled with -ffp-contract=off (SRCS_EXACT): the numpy restatement (tests/mesh_symmetry_model.py) computes the same bits.
+// fp_mesh_grid_transform_residuals is the same call with a grid: the scan then walks the shells of a uniform grid around each p'
+// (mesh_grid.h); the cells are the interface, so every output is made by k_ms_finish as above.
 #include "mesh_scan.h"
 
 namespace {
@@ -50,17 +52,11 @@ __global__ __launch_bounds__(kThreads) void k_ms_finish(const unsigned* __restri
   if (over && tid < L) over[(size_t)t * L + tid] = s_over[tid];
 }
 
-}  // namespace
-
-extern "C" size_t fp_mesh_transform_residuals_workspace_bytes(int T, int Q) {
-  return T > 0 && Q > 0 ? (size_t)T * (size_t)Q * sizeof(unsigned) : 0;
-}
-
-extern "C" int fp_mesh_transform_residuals(const float* pos, int Nv, const int32_t* faces, int F, const float* points, int Q,
-                                           const float* tfs, int T, const float* thr2, int L, float* max_d2, int32_t* over,
-                                           float* dist2, void* workspace, size_t workspace_bytes, void* stream) {
-  const char* name = "fp_mesh_transform_residuals";
-  if (int st = mesh_scan::check_pairs(name, T, Q, F, Nv)) return st;
+// fp_mesh_transform_residuals (gridded: no) and fp_mesh_grid_transform_residuals (gridded: yes) are one call, the scan exchanged
+int transform_residuals(const char* name, bool gridded, const float* pos, int Nv, const int32_t* faces, int F, const fp_mesh_grid* grid,
+                        const float* points, int Q, const float* tfs, int T, const float* thr2, int L, float* max_d2, int32_t* over,
+                        float* dist2, void* workspace, size_t workspace_bytes, void* stream) {
+  if (int st = mesh_scan::check_pairs(name, T, Q, F, Nv, gridded, grid)) return st;
   FP_REQUIRE(L >= 0 && L <= kMaxThresholds, "%s: L=%d outside 0..%d", name, L, kMaxThresholds);
   if (T == 0) return FP_OK;
   FP_REQUIRE(max_d2, "%s: NULL max_d2", name);
@@ -73,7 +69,28 @@ extern "C" int fp_mesh_transform_residuals(const float* pos, int Nv, const int32
   const hipStream_t st = (hipStream_t)stream;
   unsigned* cell = (unsigned*)workspace;
   if (Q > 0)
-    if (int e = mesh_scan::nearest_dist2_of_pairs(name, pos, Nv, faces, F, points, Q, tfs, T, cell, st)) return e;
+    if (int e = mesh_scan::nearest_dist2_of_pairs(name, pos, Nv, faces, F, gridded ? grid : nullptr, points, Q, tfs, T, cell, st)) return e;
   hipLaunchKernelGGL(k_ms_finish, dim3(T), dim3(kThreads), 0, st, cell, Q, thr2, L, max_d2, L > 0 ? over : nullptr, Q > 0 ? dist2 : nullptr);
   return mesh_scan::launched(name, "finish");
+}
+
+}  // namespace
+
+extern "C" size_t fp_mesh_transform_residuals_workspace_bytes(int T, int Q) {
+  return T > 0 && Q > 0 ? (size_t)T * (size_t)Q * sizeof(unsigned) : 0;
+}
+
+extern "C" int fp_mesh_transform_residuals(const float* pos, int Nv, const int32_t* faces, int F, const float* points, int Q,
+                                           const float* tfs, int T, const float* thr2, int L, float* max_d2, int32_t* over,
+                                           float* dist2, void* workspace, size_t workspace_bytes, void* stream) {
+  return transform_residuals("fp_mesh_transform_residuals", false, pos, Nv, faces, F, nullptr, points, Q, tfs, T, thr2, L, max_d2, over,
+                             dist2, workspace, workspace_bytes, stream);
+}
+
+extern "C" int fp_mesh_grid_transform_residuals(const float* pos, int Nv, const int32_t* faces, int F, const fp_mesh_grid* grid,
+                                                const float* points, int Q, const float* tfs, int T, const float* thr2, int L,
+                                                float* max_d2, int32_t* over, float* dist2, void* workspace, size_t workspace_bytes,
+                                                void* stream) {
+  return transform_residuals("fp_mesh_grid_transform_residuals", true, pos, Nv, faces, F, grid, points, Q, tfs, T, thr2, L, max_d2, over,
+                             dist2, workspace, workspace_bytes, stream);
 }

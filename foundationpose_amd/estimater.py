@@ -115,12 +115,17 @@ class FoundationPose:
         rot_angle_discrete, samples, n_axes), set self.symmetry_tfs from them, in the frame of the mesh handed to reset_object like a
         table given by the caller, rebuild the rotation grid with them and return the record (symmetry.Symmetries, in the centred
         frame; also kept as self.symmetries).  tol=None: for a mesh fused at a known pitch (from_reference_views) two voxels, otherwise
-        1 % of the mesh's extent.  Only geometry is considered: a can whose label is not symmetric is still reported as symmetric."""
+        1 % of the mesh's extent.  Only geometry is considered: a can whose label is not symmetric is still reported as symmetric.
+        accel="grid": the same record through a uniform grid, kept in self.mesh_tensors under "grid"; measured slower than the
+        default on every mesh size (reconstruct.detect_symmetries says why)."""
         from .reconstruct import detect_symmetries
         if kw.get("tol") is None:
             voxel = getattr(self.mesh_ori, "voxel", None)
             kw["tol"] = 2.0 * float(voxel) if voxel else None
-        rec = detect_symmetries(dict(pos=self.mesh_tensors["pos"], faces=self.mesh_tensors["faces"]), **kw)
+        mesh = dict(pos=self.mesh_tensors["pos"], faces=self.mesh_tensors["faces"])
+        if kw.get("accel") == "grid":
+            mesh["grid"] = ops.mesh_grid_build(self.mesh_tensors)     # kept with the estimator's tensors, found by detect_symmetries
+        rec = detect_symmetries(mesh, **kw)
         to_c, from_c = np.eye(4), np.eye(4)               # T(-model_center), T(+model_center): as _centred_frames, inverted
         to_c[:3, 3] = -np.asarray(self.model_center, dtype=np.float64)
         from_c[:3, 3] = np.asarray(self.model_center, dtype=np.float64)
@@ -245,7 +250,9 @@ class FoundationPose:
     def align_to_mesh(self, mesh, **kw):
         """Register the estimator's mesh (as it was handed to reset_object, for example fused by from_reference_views in the frame of
         the reference poses) onto `mesh` (a SimpleMesh or a mesh-tensor dict, for example the object's CAD model in its own frame)
-        -> ops.MeshAlignment (reconstruct.align_meshes; kw: its starts, samples, iterations, max_dist, min_overlap, init, seed).
+        -> ops.MeshAlignment (reconstruct.align_meshes; kw: its starts, samples, iterations, max_dist, min_overlap, init, seed, and
+        accel="grid" for the same alignment through a uniform grid over `mesh`: for a local refinement from a good init= against a
+        model of tens of thousands of faces; slower than the default from the default starts).
         Its transfer_pose turns a pose of the estimator's mesh into the pose of `mesh`'s frame; compare_to_mesh(mesh, tf=it) compares
         in the aligned frame.  A setup call (it synchronises)."""
         from .reconstruct import align_meshes
@@ -266,7 +273,7 @@ class FoundationPose:
         return compare_meshes(self.mesh_ori, mesh, samples=samples, thresholds=thresholds, seed=seed, unit=unit, device=self.device, tf=tf,
                               accel=accel)
 
-    def penetration_into(self, other, poses=None, samples=2048, seed=0, allow_open=False):
+    def penetration_into(self, other, poses=None, samples=2048, seed=0, allow_open=False, accel=None):
         """How far this object, at `poses`, reaches into the object of estimator `other` at other.pose_last (not in the reference)
         -> ops.Penetration with one row per pose: `inside` the share of this object's `samples` surface samples (sample_surface,
         seed) that lie inside other's mesh, `depth` the distance in metres of the deepest of them to other's surface (0 when none is
@@ -275,8 +282,13 @@ class FoundationPose:
         poses are of centred meshes and both mesh tensors are centred, so the samples move by inv(other.pose_last) @ pose (float64 on
         the host, rounded once) with no centring transform; the deepest sample alone is moved back by model_center.  One
         ops.mesh_penetration call (N x samples x other's faces pair tests).  other's mesh must be closed (ops.mesh_pseudonormals,
-        computed once and kept in other.mesh_tensors) unless allow_open=True.  An evaluation call (it synchronises)."""
-        from .reconstruct import sample_surface
+        computed once and kept in other.mesh_tensors) unless allow_open=True.  accel="grid": answered through a uniform grid over
+        other's mesh (ops.mesh_grid_build, built at the first call and kept in other.mesh_tensors under "grid"): the same rows bit for
+        bit.  It pays only where every sample is within about a cell of other's surface (twice its mean face edge) and other has
+        tens of thousands of faces; samples a few cells away already cost more than the brute force, and a pose that puts this object
+        far from other walks the whole grid and tests every stored triangle from global memory, minutes for milliseconds (DESIGN.md
+        section 6).  None: brute force, the default.  An evaluation call (it synchronises)."""
+        from .reconstruct import _accel_grid, sample_surface
         what = "penetration_into"
         if not isinstance(other, FoundationPose):
             raise ValueError(f"{what}: other must be a FoundationPose, got {type(other).__name__}")
@@ -288,10 +300,11 @@ class FoundationPose:
                 raise RuntimeError(f"{what}: no pose yet (register or track first, or pass poses)")
         host = lambda p: (p.detach().cpu().numpy() if torch.is_tensor(p) else np.asarray(p)).astype(np.float64).reshape(-1, 4, 4)   # noqa: E731
         tfs = np.linalg.inv(host(other.pose_last)[0]) @ host(poses)
+        grid = _accel_grid(accel, other.mesh_tensors, what)
         dev = other.mesh_tensors["pos"].device
         pts, _ = sample_surface(dict(pos=self.mesh_tensors["pos"], faces=self.mesh_tensors["faces"]), samples, seed)
         got = ops.mesh_penetration(pts.to(dev), torch.as_tensor(tfs.astype(np.float32), device=dev).contiguous(), other.mesh_tensors,
-                                   allow_open=allow_open)
+                                   allow_open=allow_open, grid=grid)
         return ops.Penetration.rows(got, pts, self.model_center)
 
     # the depth maps bop_errors holds at a time: 48 MiB = 40 full 480 x 640 float32 frames.  Small against the 256 MiB last-level cache,
@@ -655,15 +668,16 @@ def depth_polish(estimators, depths, Ks, views=None, iterations=3, max_dist=0.02
     return ops.IcpStep.rows(system)
 
 
-def penetrations(estimators, samples=2048, seed=0, allow_open=False):
+def penetrations(estimators, samples=2048, seed=0, allow_open=False, accel=None):
     """penetration_into over every ordered pair of the estimators at their current pose_last -> {(i, j): ops.Penetration}: how far
     object i reaches into object j.  Two objects tracked or registered into each other show up as a non-zero share in one direction
-    at least.  The estimators need not share a refiner; everybody needs a pose_last.  One ops.mesh_penetration call per pair."""
+    at least.  The estimators need not share a refiner; everybody needs a pose_last.  One ops.mesh_penetration call per pair; accel as
+    penetration_into takes it (one grid per estimator, kept in its mesh_tensors)."""
     ests = list(estimators)
     for i, e in enumerate(ests):
         if e.pose_last is None:
             raise RuntimeError(f"penetrations: estimator {i} has no pose yet (register or track it first)")
-    return {(i, j): a.penetration_into(b, samples=samples, seed=seed, allow_open=allow_open)
+    return {(i, j): a.penetration_into(b, samples=samples, seed=seed, allow_open=allow_open, accel=accel)
             for i, a in enumerate(ests) for j, b in enumerate(ests) if i != j}
 
 

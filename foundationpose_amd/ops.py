@@ -1076,9 +1076,10 @@ def _grid_for(what, grid, pos, faces):
 
 def mesh_grid_build(mesh_tensors=None, pos=None, faces=None, cell=None, max_cells=MESH_GRID_MAX_CELLS, pad=None, lo=None, n=None):
     """fp_mesh_grid_count + fp_mesh_grid_fill: a uniform grid over the triangles of a mesh -> MeshGrid, for
-    mesh_point_distance(grid=) and mesh_signed_distance(grid=), which then give the brute force's bits from a few dozen pair tests
-    a query near the surface (include/fp_amd.h has the definition and the proof).  The mesh is mesh_tensors (pos (Nv,3) f32, faces
-    (F,3) int32, on the device) or pos= and faces=.  cell: the cell edge; max_cells, pad, lo, n: mesh_grid_shape, which states the
+    mesh_point_distance(grid=), mesh_signed_distance(grid=) and the batched mesh_transform_residuals(grid=), mesh_icp_step(grid=) and
+    mesh_penetration(grid=), which then give the brute force's bits from a few dozen pair tests a query near the surface
+    (include/fp_amd.h has the definition and the proof).  The mesh is mesh_tensors (pos (Nv,3) f32, faces (F,3) int32, on the device)
+    or pos= and faces=.  cell: the cell edge; max_cells, pad, lo, n: mesh_grid_shape, which states the
     default rule.  The sequence is count, one read of the header, the allocation of exactly n_entries and n_overflow slots, fill, and
     a read of the status word, which raises FpAmdError when set.  Done once per mesh: it copies the mesh to the host for the box,
     synchronises twice and allocates, so it is not capturable.  With mesh_tensors the grid is kept in the dict under "grid" and
@@ -1129,7 +1130,8 @@ _MESH_RESIDUAL_DTYPES = {"max_d2": torch.float32, "over": torch.int32, "dist2": 
 MESH_RESIDUAL_MAX_THRESHOLDS = 4
 
 
-def mesh_transform_residuals(points, tfs, mesh_tensors=None, pos=None, faces=None, thresholds=None, want=("max_d2", "over"), out=None):
+def mesh_transform_residuals(points, tfs, mesh_tensors=None, pos=None, faces=None, thresholds=None, want=("max_d2", "over"), out=None,
+                             grid=None):
     """fp_mesh_transform_residuals: how far each of the transforms tfs (T,4,4) f32 moves the points (Q,3) f32 (surface samples of the
     mesh, as a rule) off the surface of the mesh -> dict of device tensors: `max_d2` (T,) f32 the largest squared distance of a
     transformed point to the surface, `over` (T,L) int32 the number of points whose squared distance is strictly above each threshold
@@ -1141,7 +1143,12 @@ def mesh_transform_residuals(points, tfs, mesh_tensors=None, pos=None, faces=Non
     caller-owned buffers for some of the wanted names.  The rows of tfs are used as given (row 3 is not read).  T x Q x F pair
     tests.  The workspace (4 bytes a pair) is the library's per-stream scratch, or a fresh allocation inside a stream capture.  Wrong
     shapes are refused first, then tensors that are not on the device, of another dtype or not contiguous, then buffers that overlap
-    an input or each other (FpAmdError)."""
+    an input or each other (FpAmdError).  grid: a MeshGrid of this mesh (mesh_grid_build) answers through
+    fp_mesh_grid_transform_residuals instead: the same bits; a grid built for other pos / faces tensors is refused, where
+    mesh_point_distance refuses it.  It pays only where the transformed points stay within about a cell of the surface of a mesh of tens
+    of thousands of faces or more (measured: 17.6 times at 401 672 faces, 3.7 times at 85 796, slower at 4 900); points a few cells
+    away already cost more than the brute force on every mesh, and a transformed point far from the mesh walks the whole grid and tests
+    every stored triangle from global memory, minutes for milliseconds."""
     what = "mesh_transform_residuals"
     names = _mesh_names(what, want, MESH_RESIDUAL_OUTPUTS, always=("max_d2",), required=True)
     thr = np.zeros(0, np.float32) if thresholds is None else np.asarray(thresholds, dtype=np.float64).reshape(-1).astype(np.float32)
@@ -1155,6 +1162,7 @@ def mesh_transform_residuals(points, tfs, mesh_tensors=None, pos=None, faces=Non
     c = _mesh_call(what, points, tfs, mesh_tensors, pos, faces, out, pairs=True, names=names, dtypes=_MESH_RESIDUAL_DTYPES,
                    shapes_of=lambda T, Q: {"max_d2": (T,), "over": (T, L), "dist2": (T, Q)}, limit=_mesh_limit_pairs,
                    workspace_bytes=lambda T, Q: _lib.lib().fp_mesh_transform_residuals_workspace_bytes(T, Q))
+    g = None if grid is None else _grid_for(what, grid, c.pos, c.faces)
     thr2 = None
     if L:
         sq = thr * thr                                                        # float32 * float32: one rounding, on the host
@@ -1164,10 +1172,13 @@ def mesh_transform_residuals(points, tfs, mesh_tensors=None, pos=None, faces=Non
                 thr2[l].fill_(float(sq[l]))
         else:
             thr2 = torch.as_tensor(sq, device=c.points.device)
-    _lib.check(_lib.lib().fp_mesh_transform_residuals(_ptr(c.pos), c.Nv, _ptr(c.faces), c.F, _ptr(c.points), c.Q, _ptr(c.tfs), c.T,
-                                                      _ptr(thr2), L, _ptr(c.out["max_d2"]), _ptr(c.out.get("over")),
-                                                      _ptr(c.out.get("dist2")), _ptr(c.ws), c.ws_bytes, _stream(c.points)),
-               "fp_mesh_transform_residuals")
+    rest = (_ptr(c.points), c.Q, _ptr(c.tfs), c.T, _ptr(thr2), L, _ptr(c.out["max_d2"]), _ptr(c.out.get("over")), _ptr(c.out.get("dist2")),
+            _ptr(c.ws), c.ws_bytes, _stream(c.points))
+    if g is not None:
+        _lib.check(_lib.lib().fp_mesh_grid_transform_residuals(_ptr(c.pos), c.Nv, _ptr(c.faces), c.F, C.byref(g), *rest),
+                   "fp_mesh_grid_transform_residuals")
+    else:
+        _lib.check(_lib.lib().fp_mesh_transform_residuals(_ptr(c.pos), c.Nv, _ptr(c.faces), c.F, *rest), "fp_mesh_transform_residuals")
     return {k: c.out[k] for k in names}
 
 
@@ -1182,7 +1193,7 @@ def mesh_icp_workspace(T, Q, device):
 
 
 def mesh_icp_step(points, tfs, mesh_tensors=None, pos=None, faces=None, *, max_dist, damping=1e-3, min_pairs=6, want=(), out=None,
-                  workspace=None):
+                  workspace=None, grid=None):
     """fp_mesh_icp_step: one Gauss-Newton step of point-to-plane ICP for each of the transforms tfs (T,4,4) f32 of the points (Q,3) f32
     (surface samples of a mesh a) against the surface of a mesh b -> (tfs_out (T,4,4) f32, system (T,40) f64[, dict of `dist2` (T,Q)
     f32 / `face` (T,Q) int32 for the names in want]) device tensors.  include/fp_amd.h has the definition: each transformed point is
@@ -1192,7 +1203,12 @@ def mesh_icp_step(points, tfs, mesh_tensors=None, pos=None, faces=None, *, max_d
     for mesh_point_distance.  out: a dict of caller-owned buffers out of "tfs_out", "system" and the wanted names; workspace:
     mesh_icp_workspace (None: the library's per-stream scratch, or a fresh allocation inside a stream capture).  T x Q x F pair
     tests.  Wrong shapes are refused first, then tensors that are not on the device, of another dtype or not contiguous, then
-    buffers that overlap an input or each other (FpAmdError)."""
+    buffers that overlap an input or each other (FpAmdError).  grid: a MeshGrid of mesh b (mesh_grid_build) answers through
+    fp_mesh_grid_icp_step instead: the same bits, float64 sums included; a grid built for other pos / faces tensors is refused, where
+    mesh_point_distance refuses it.  It pays only where the transformed points stay within about a cell of the surface of a mesh of tens
+    of thousands of faces or more (measured: 17.6 times at 401 672 faces, 3.7 times at 85 796, slower at 4 900); points a few cells
+    away already cost more than the brute force on every mesh, and a transformed point far from the mesh walks the whole grid and tests
+    every stored triangle from global memory, minutes for milliseconds."""
     what = "mesh_icp_step"
     md, dmp, mp = _check_icp(max_dist, damping, min_pairs, what)
     names = _mesh_names(what, want, MESH_ICP_OUTPUTS)
@@ -1202,9 +1218,13 @@ def mesh_icp_step(points, tfs, mesh_tensors=None, pos=None, faces=None, *, max_d
                    limit=_mesh_limit_pairs, workspace_bytes=lambda T, Q: _lib.lib().fp_mesh_icp_workspace_bytes(T, Q),
                    workspace=workspace, workspace_maker="mesh_icp_workspace")
     out = c.out
-    _lib.check(_lib.lib().fp_mesh_icp_step(_ptr(c.pos), c.Nv, _ptr(c.faces), c.F, _ptr(c.points), c.Q, _ptr(c.tfs), c.T, md, dmp, mp,
-                                           _ptr(out["system"]), _ptr(out["tfs_out"]), _ptr(out.get("dist2")), _ptr(out.get("face")),
-                                           _ptr(c.ws), c.ws_bytes, _stream(c.points)), "fp_mesh_icp_step")
+    rest = (_ptr(c.points), c.Q, _ptr(c.tfs), c.T, md, dmp, mp, _ptr(out["system"]), _ptr(out["tfs_out"]), _ptr(out.get("dist2")),
+            _ptr(out.get("face")), _ptr(c.ws), c.ws_bytes, _stream(c.points))
+    if grid is not None:
+        g = _grid_for(what, grid, c.pos, c.faces)
+        _lib.check(_lib.lib().fp_mesh_grid_icp_step(_ptr(c.pos), c.Nv, _ptr(c.faces), c.F, C.byref(g), *rest), "fp_mesh_grid_icp_step")
+    else:
+        _lib.check(_lib.lib().fp_mesh_icp_step(_ptr(c.pos), c.Nv, _ptr(c.faces), c.F, *rest), "fp_mesh_icp_step")
     if names:
         return out["tfs_out"], out["system"], {k: out[k] for k in names}
     return out["tfs_out"], out["system"]
@@ -1319,7 +1339,7 @@ def mesh_penetration_workspace(T, Q, device):
 
 
 def mesh_penetration(points, tfs, mesh_tensors=None, pos=None, faces=None, tables=None, want=("inside", "depth2", "deepest"), out=None,
-                     workspace=None, allow_open=False):
+                     workspace=None, allow_open=False, grid=None):
     """fp_mesh_penetration: how far each of the transforms tfs (T,4,4) f32 of the points (Q,3) f32 (surface samples of another object,
     as a rule) reaches into the mesh -> dict of device tensors: `inside` (T,) int32 the number of transformed points inside, `depth2`
     (T,) f32 the largest squared distance of one of those to the surface (0 when there is none), `deepest` (T,) int32 its index (the
@@ -1328,7 +1348,12 @@ def mesh_penetration(points, tfs, mesh_tensors=None, pos=None, faces=None, table
     0..2 are not finite moves every point to nowhere and has inside 0, depth2 0, deepest -1.  tables, allow_open and the refusal of a
     mesh that is not closed are mesh_signed_distance's.  want: names out of MESH_PENETRATION_OUTPUTS; inside is always computed and
     returned.  out: a dict of caller-owned buffers for some of the wanted names; workspace: mesh_penetration_workspace (None: the
-    library's per-stream scratch, or a fresh allocation inside a stream capture).  T x Q x F pair tests."""
+    library's per-stream scratch, or a fresh allocation inside a stream capture).  T x Q x F pair tests.  grid: a MeshGrid of this
+    mesh (mesh_grid_build) answers through fp_mesh_grid_penetration instead: the same bits; a grid built for other pos / faces
+    tensors is refused, where mesh_point_distance refuses it.  It pays only where the transformed points stay within about a cell of the
+    surface of a mesh of tens of thousands of faces or more; points a few cells away already cost more than the brute force on every
+    mesh, and a placement far from the mesh walks the whole grid and tests every stored triangle from global memory, minutes for
+    milliseconds."""
     what = "mesh_penetration"
     names = _mesh_names(what, want, MESH_PENETRATION_OUTPUTS, always=("inside",))
     c = _mesh_call(what, points, tfs, mesh_tensors, pos, faces, out, pairs=True, signed=(tables, allow_open), names=names,
@@ -1337,10 +1362,13 @@ def mesh_penetration(points, tfs, mesh_tensors=None, pos=None, faces=None, table
                    limit=_mesh_limit_signed, workspace_bytes=lambda T, Q: _lib.lib().fp_mesh_penetration_workspace_bytes(T, Q),
                    workspace=workspace, workspace_maker="mesh_penetration_workspace")
     out = c.out
-    _lib.check(_lib.lib().fp_mesh_penetration(_ptr(c.pos), c.Nv, _ptr(c.faces), c.F, _ptr(c.vn), _ptr(c.en), _ptr(c.points), c.Q,
-                                              _ptr(c.tfs), c.T, _ptr(out["inside"]), _ptr(out.get("depth2")), _ptr(out.get("deepest")),
-                                              _ptr(out.get("sign")), _ptr(out.get("dist2")), _ptr(c.ws), c.ws_bytes, _stream(c.points)),
-               "fp_mesh_penetration")
+    rest = (_ptr(c.vn), _ptr(c.en), _ptr(c.points), c.Q, _ptr(c.tfs), c.T, _ptr(out["inside"]), _ptr(out.get("depth2")),
+            _ptr(out.get("deepest")), _ptr(out.get("sign")), _ptr(out.get("dist2")), _ptr(c.ws), c.ws_bytes, _stream(c.points))
+    if grid is not None:
+        g = _grid_for(what, grid, c.pos, c.faces)
+        _lib.check(_lib.lib().fp_mesh_grid_penetration(_ptr(c.pos), c.Nv, _ptr(c.faces), c.F, C.byref(g), *rest), "fp_mesh_grid_penetration")
+    else:
+        _lib.check(_lib.lib().fp_mesh_penetration(_ptr(c.pos), c.Nv, _ptr(c.faces), c.F, *rest), "fp_mesh_penetration")
     return {k: out[k] for k in names}
 
 

@@ -560,7 +560,7 @@ def _rigid_tf(tf, what):
 
 
 def align_meshes(a, b, starts=300, samples=(128, 2048), iterations=(12, 20), max_dist=None, min_overlap=0.5, init=None, seed=0,
-                 device=None):
+                 device=None, accel=None):
     """Register mesh a onto mesh b with no initial guess -> ops.MeshAlignment: `tf` (4,4) float64 maps a's coordinates into b's frame
     (one unit: no scale is estimated, and no reflection), with the mean and root-mean-square distance of a's samples to b's
     surface, the fraction of them that found a pair, and `runner_up`, the best other basin (a symmetric or nearly symmetric object
@@ -571,7 +571,13 @@ def align_meshes(a, b, starts=300, samples=(128, 2048), iterations=(12, 20), max
     above max_dist (None: no limit) -- and this function binds it to the device: every step of every candidate is one
     ops.mesh_icp_step call (starts x samples x faces pair tests), the transforms ping-pong between two device tables and come back to
     the host once per stage and per gate.  init: a (4,4) or (S,4,4) guess in the place of the starts (a local refinement).  A setup /
-    evaluation call: it reads the meshes back once and synchronises a handful of times."""
+    evaluation call: it reads the meshes back once and synchronises a handful of times.  accel="grid": every step is answered through
+    a uniform grid over mesh b (ops.mesh_grid_build, built here once and kept in b under "grid" when b is a dict of device tensors):
+    the same alignment bit for bit.  It pays only for samples within about a cell of b's surface and a b of tens of thousands of
+    faces or more: a local refinement from a good init= (the fine stage's step then took 0.9 ms against 16 ms at 401 672 faces).
+    The default policy's starts put most samples several cells from b, where every measured size was 9 to 15 times slower through
+    the grid, and a start that puts a far from b walks the whole grid and tests every stored triangle from global memory (DESIGN.md
+    section 6): those stay on None, brute force, the default."""
     from . import mesh_align, symmetry
     what = "align_meshes"
     try:
@@ -588,6 +594,7 @@ def align_meshes(a, b, starts=300, samples=(128, 2048), iterations=(12, 20), max
     centre_b, radius_b = symmetry.surface_centre(tb["pos"].cpu().numpy(), tb["faces"].cpu().numpy())
     centre_a = pts["coarse"].double().mean(dim=0).cpu().numpy()
     dev = tb["pos"].device
+    grid = _accel_grid(accel, tb, what, keep=b)
 
     def steps(which, tfs, gate, n):
         p = pts[which]
@@ -597,9 +604,10 @@ def align_meshes(a, b, starts=300, samples=(128, 2048), iterations=(12, 20), max
         system = torch.empty((S, 40), dtype=torch.float64, device=dev)
         ws = ops.mesh_icp_workspace(S, Q, dev)
         for _ in range(n):
-            ops.mesh_icp_step(p, cur, tb, max_dist=gate, out=dict(tfs_out=nxt, system=system), workspace=ws)
+            ops.mesh_icp_step(p, cur, tb, max_dist=gate, out=dict(tfs_out=nxt, system=system), workspace=ws, grid=grid)
             cur, nxt = nxt, cur
-        _, _, extra = ops.mesh_icp_step(p, cur, tb, max_dist=gate, want=("dist2",), out=dict(tfs_out=nxt, system=system), workspace=ws)
+        _, _, extra = ops.mesh_icp_step(p, cur, tb, max_dist=gate, want=("dist2",), out=dict(tfs_out=nxt, system=system), workspace=ws,
+                                        grid=grid)
         return cur.cpu().numpy().astype(np.float64), system.cpu().numpy(), extra["dist2"].cpu().numpy()
 
     got = mesh_align.align(steps, centre_a, centre_b, radius_b, (n_coarse, n_fine), starts=starts, iterations=iterations,
@@ -607,12 +615,15 @@ def align_meshes(a, b, starts=300, samples=(128, 2048), iterations=(12, 20), max
     return ops.MeshAlignment(*(got[k] for k in ops.MeshAlignment._fields))
 
 
-def _accel_grid(accel, t, what):
-    """accel=None: no grid (brute force); "grid": ops.mesh_grid_build of the mesh-tensor dict t, kept in it under "grid" """
+def _accel_grid(accel, t, what, keep=None):
+    """accel=None: no grid (brute force); "grid": ops.mesh_grid_build of the mesh-tensor dict t, kept in it under "grid" -- or in
+    keep, the caller's own dict that t was made from, where t holds that dict's very tensors"""
     if accel is None:
         return None
     if accel != "grid":
         raise ValueError(f"{what}: accel must be None or 'grid', got {accel!r}")
+    if isinstance(keep, dict) and ops.MeshGrid.key_of(keep["pos"], keep["faces"]) == ops.MeshGrid.key_of(t["pos"], t["faces"]):
+        return ops.mesh_grid_build(keep)
     return ops.mesh_grid_build(t)
 
 
@@ -700,7 +711,7 @@ def signed_bias(a, b, samples=100_000, seed=0, tf=None, device=None, allow_open=
 
 
 # ------------------------------------------------------------------ which rotations map a mesh onto itself
-def detect_symmetries(mesh_tensors, tol=None, max_order=6, rot_angle_discrete=5, samples=(64, 512), n_axes=800):
+def detect_symmetries(mesh_tensors, tol=None, max_order=6, rot_angle_discrete=5, samples=(64, 512), n_axes=800, accel=None):
     """The rotational symmetries of a mesh -> symmetry.Symmetries: tfs (S,4,4) float64 with the identity first (what the estimator's
     symmetry_tfs, make_rotation_grid, pose_errors(want="sym"), MSSD, MSPD and cluster_poses take), the axes with their orders
     (math.inf for a continuous one, which contributes a rotation every rot_angle_discrete degrees), tol and the residual of each
@@ -711,7 +722,12 @@ def detect_symmetries(mesh_tensors, tol=None, max_order=6, rot_angle_discrete=5,
     not symmetric is still reported as symmetric; only proper rotations are looked for.  symmetry.find_symmetries has the recipe; this
     function binds its two callables to the device: ops.mesh_transform_residuals for the largest distance per candidate transform
     (one call per order over all n_axes candidate axes) and ops.mesh_point_distance for the closest points of a refinement step.  A
-    setup call: it reads the mesh back once and synchronises at every step of the policy."""
+    setup call: it reads the mesh back once and synchronises at every step of the policy.  accel="grid": both callables are answered
+    through a uniform grid over the mesh (ops.mesh_grid_build, built here once and kept in mesh_tensors under "grid" when that is a
+    dict of device tensors): the same record bit for bit.  Measured, it does not pay here: a candidate rotation that is no symmetry
+    puts the samples several cells from the surface, and the coarse scan's call was 9 to 13 times slower through the grid at 4 900
+    to 401 672 faces (the grid is for samples within about a cell of the surface, and a transformed sample far
+    from the mesh walks the whole grid and tests every stored triangle from global memory).  None: brute force, the default."""
     from . import symmetry
     what = "detect_symmetries"
     pos, faces = _mesh_arrays(mesh_tensors, None if isinstance(mesh_tensors, dict) else "cuda", what, "mesh_tensors")
@@ -729,16 +745,17 @@ def detect_symmetries(mesh_tensors, tol=None, max_order=6, rot_angle_discrete=5,
     mesh = dict(pos=pos, faces=faces)
     pts = {"coarse": sample_surface(mesh, n_coarse, seed=1)[0], "fine": sample_surface(mesh, n_fine, seed=0)[0]}
     fine64 = pts["fine"].cpu().numpy().astype(np.float64)
+    grid = _accel_grid(accel, mesh, what, keep=mesh_tensors)
 
     def residuals(tfs, which):
         m = torch.as_tensor(np.ascontiguousarray(tfs, dtype=np.float32), device=pos.device)
-        d2 = ops.mesh_transform_residuals(pts[which], m, mesh, want=("max_d2",))["max_d2"]
+        d2 = ops.mesh_transform_residuals(pts[which], m, mesh, want=("max_d2",), grid=grid)["max_d2"]
         return np.sqrt(d2.cpu().numpy().astype(np.float64))
 
     def closest(tf):
         m = torch.as_tensor(np.ascontiguousarray(tf, dtype=np.float32), device=pos.device)
         moved = (pts["fine"] @ m[:3, :3].T + m[:3, 3]).contiguous()
-        return fine64, ops.mesh_point_distance(moved, mesh, want=("closest",))["closest"].cpu().numpy().astype(np.float64)
+        return fine64, ops.mesh_point_distance(moved, mesh, want=("closest",), grid=grid)["closest"].cpu().numpy().astype(np.float64)
 
     return symmetry.find_symmetries(residuals, closest, centre, radius, tol, max_order=max_order, n_axes=n_axes,
                                     rot_angle_discrete=rot_angle_discrete)

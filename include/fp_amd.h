@@ -112,7 +112,10 @@ const char* fp_last_error(void);
  *               absence.
  *   234 (kept): + fp_mesh_grid_count, fp_mesh_grid_fill, fp_mesh_grid_fill_workspace_bytes, fp_mesh_grid_point_distance,
  *               fp_mesh_grid_signed_distance and the struct fp_mesh_grid (additions only): a uniform grid over a mesh's triangles and
- *               the two point queries answered from it with the brute force's bits.  The number stays for the same reason. */
+ *               the two point queries answered from it with the brute force's bits.  The number stays for the same reason.
+ *   234 (kept): + fp_mesh_grid_transform_residuals, fp_mesh_grid_icp_step, fp_mesh_grid_penetration (additions only): the three
+ *               batched transform queries answered from the same grid with the brute force's bits.  The number stays for the same
+ *               reason: tests/test_mesh_signed_host.py pins it, and a binding finds an older library by the symbols' absence. */
 #define FP_AMD_ABI_VERSION 234
 int fp_version(void);
 
@@ -545,7 +548,23 @@ int fp_mesh_penetration(const float* pos /*dev Nv,3*/, int Nv, const int32_t* fa
  * host synchronisation (graph-capturable).  grid->n_entries and grid->n_overflow are the lengths of the lists here; an entry outside
  * 0..F-1 is ignored, and nothing outside the tables' lengths is read.  Argument errors: the parent's, each message beginning with the
  * entry point's name, and the grid's refusals above, a NULL grid, a NULL cell_start, NULL entries / overflow with a length > 0, a
- * negative length; for count and fill also a NULL header, and for fill a NULL or misaligned cursor workspace. */
+ * negative length; for count and fill also a NULL header, and for fill a NULL or misaligned cursor workspace.
+ *
+ * fp_mesh_grid_transform_residuals, fp_mesh_grid_icp_step and fp_mesh_grid_penetration: fp_mesh_transform_residuals, fp_mesh_icp_step
+ * and fp_mesh_penetration with the grid after F, each to its parent what fp_mesh_grid_point_distance is to fp_mesh_point_distance.  The
+ * parent's init launch; a scan of 256 (transform, sample) pairs a workgroup, numbered t*Q + i, one per lane, in which the lane forms
+ * p' = ((rk[0]*x + rk[1]*y) + rk[2]*z) + rk[3] exactly as the parent does and walks as above for the query p', merging into the
+ * parent's cell (the 32-bit bits(dd) of the residuals, the 64-bit key of the other two); then the parent's finish kernels unchanged.
+ * The proof of the stop rule above is per query point: it uses p only as a float32 point whose cell and plane distances the walk
+ * computes from it, so it holds unchanged for p', however p' was formed, and a non-finite p' walks nothing and answers nothing, as in
+ * the brute force.  Every output -- max_d2, over, dist2; system with its float64 sums, tfs_out, dist2, face; inside, depth2, deepest,
+ * sign, dist2 -- has the parent's bits under the precondition above.  The workspace is the parent's, sized by the parent's
+ * *_workspace_bytes function.  No allocation, no memset, no host synchronisation (graph-capturable), integer atomics only.  The cost
+ * is per pair: a p' within about a cell of the surface tests a few dozen triangles; a p' a few cells away tests hundreds, each a gather
+ * from global memory that only its lane wants, and is already slower than the brute force's LDS tiles; a p' far from the mesh walks
+ * shell after shell until the whole grid is visited and tests every stored triangle -- the grid form is for samples near the surface.
+ * Argument errors, before any launch, each message beginning with the new entry point's name: the parent's, and, after the parent's
+ * checks of T, Q, F and Nv, the grid's refusals as listed above. */
 typedef struct fp_mesh_grid {
   float lo[3];
   float h;
@@ -579,6 +598,25 @@ int fp_mesh_grid_signed_distance(const float* pos /*dev Nv,3*/, int Nv, const in
                                  float* dist2 /*dev Q*/, int32_t* face /*dev Q|NULL*/, float* closest /*dev Q,3|NULL*/,
                                  int32_t* feature /*dev Q|NULL*/, int32_t* sign /*dev Q|NULL*/,
                                  void* workspace /*dev*/, size_t workspace_bytes, void* stream);
+int fp_mesh_grid_transform_residuals(const float* pos /*dev Nv,3*/, int Nv, const int32_t* faces /*dev F,3*/, int F,
+                                     const fp_mesh_grid* grid /*host*/, const float* points /*dev Q,3*/, int Q,
+                                     const float* tfs /*dev T,4,4 row-major; rows 0..2 are read*/, int T,
+                                     const float* thr2 /*dev L | NULL when L == 0*/, int L /*0..4*/,
+                                     float* max_d2 /*dev T*/, int32_t* over /*dev T,L|NULL*/, float* dist2 /*dev T,Q|NULL*/,
+                                     void* workspace /*dev*/, size_t workspace_bytes, void* stream);
+int fp_mesh_grid_icp_step(const float* pos /*dev Nv,3*/, int Nv, const int32_t* faces /*dev F,3*/, int F,
+                          const fp_mesh_grid* grid /*host*/, const float* points /*dev Q,3*/, int Q,
+                          const float* tfs_in /*dev T,4,4 row-major*/, int T, float max_dist, double damping, int min_pairs,
+                          double* system /*dev T,40*/, float* tfs_out /*dev T,16|NULL*/,
+                          float* dist2 /*dev T,Q|NULL*/, int32_t* face /*dev T,Q|NULL*/,
+                          void* workspace /*dev*/, size_t workspace_bytes, void* stream);
+int fp_mesh_grid_penetration(const float* pos /*dev Nv,3*/, int Nv, const int32_t* faces /*dev F,3*/, int F,
+                             const fp_mesh_grid* grid /*host*/, const float* vn /*dev Nv,3*/, const float* en /*dev F,3,3*/,
+                             const float* points /*dev Q,3*/, int Q,
+                             const float* tfs /*dev T,4,4 row-major; rows 0..2 are read*/, int T,
+                             int32_t* inside /*dev T*/, float* depth2 /*dev T|NULL*/, int32_t* deepest /*dev T|NULL*/,
+                             int32_t* sign /*dev T,Q|NULL*/, float* dist2 /*dev T,Q|NULL*/,
+                             void* workspace /*dev*/, size_t workspace_bytes, void* stream);
 
 /* An object's mesh from posed RGB-D reference views: truncated-signed-distance (TSDF) fusion into a caller-owned volume, then marching
  * tetrahedra.  The volume has nz x ny x nx voxels; voxel (ix, iy, iz) has the linear index i = (iz * ny + iy) * nx + ix and, in the

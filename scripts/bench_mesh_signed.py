@@ -6,8 +6,16 @@ the table read and one dot product a pair -- and, for the penetration, 64-bit ke
 cells.  The two of a pair are timed in turns (--rounds of signed, sibling, signed, sibling, ...), each turn HIP events around warm
 back-to-back calls that fill --window seconds; the figure is the median of the turns, the spread their (max - min) / median.  Every
 figure is the time of a call through the Python wrapper.  Prints one JSON line and writes it into --out (profiles/mesh_signed.json)
-under "bench", keeping what else the file holds."""
-import argparse, json, os, sys
+under "bench", keeping what else the file holds.
+
+--accel grid adds, per mesh, the same penetration call answered through a uniform grid (ops.mesh_grid_build, then
+mesh_penetration(grid=)) in the same run: under "grid" the time of a build (the smallest of three, wall clock around a synchronised
+call), the time of a call (the median of --rounds turns), this run's brute-force time over it, the grid's shape and whether inside,
+depth2 and deepest equal the brute force's bit for bit; and under "far" the same call with every placement moved three extents of the
+mesh away from it, where each lane walks the whole grid and tests every stored triangle: the brute-force time, and the grid's unless
+its time, estimated from the first four placements, is above --far_limit times the brute force's (then `skipped` says so).  It also
+adds the can fused at the default pitch (128 voxels, about 400 k faces) to the meshes.  Without the flag the output is what it was."""
+import argparse, json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import numpy as np
@@ -26,6 +34,8 @@ ap.add_argument("--rounds", type=int, default=3)
 ap.add_argument("--views", type=int, default=16)
 ap.add_argument("--fused_faces", type=int, default=1, help="0: leave the fused can out")
 ap.add_argument("--out", type=str, default=os.path.join(ROOT, "profiles", "mesh_signed.json"), help="'' writes no file")
+ap.add_argument("--accel", choices=("grid",), default=None)
+ap.add_argument("--far_limit", type=float, default=2000.0, help="the far placements through the grid may take this many brute-force calls")
 args = ap.parse_args()
 dev = torch.device("cuda:0")
 sc = bench.build_scene(dev, 0, 1)
@@ -95,7 +105,55 @@ def case(name, mesh):
     pen = in_turns(lambda: ops.mesh_penetration(pts, tfs, mesh, out=o_p, workspace=ws, allow_open=True),
                    lambda: ops.mesh_transform_residuals(pts, tfs, mesh, want=("max_d2",), out=o_r))
     pen.update(T=T, Q=Q, inside_share=float(o_p["inside"].float().mean() / Q))
-    return dict(name=name, faces=F, closed=tables.closed, distance=dist, penetration=pen)
+    row = dict(name=name, faces=F, closed=tables.closed, distance=dist, penetration=pen)
+    if args.accel == "grid":
+        builds = []
+        for _ in range(3):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            grid = ops.mesh_grid_build(pos=mesh["pos"], faces=mesh["faces"])
+            torch.cuda.synchronize()
+            builds.append((time.perf_counter() - t0) * 1e3)
+        call = lambda m, g, o=o_p, w=ws: ops.mesh_penetration(pts, m, mesh, out=o, workspace=w, allow_open=True, grid=g)   # noqa: E731
+        brute = {k: v.clone() for k, v in call(tfs, None).items()}
+        got = {k: v.clone() for k, v in call(tfs, grid).items()}
+        for _ in range(3):
+            call(tfs, grid)
+        runs = [timed(lambda: call(tfs, grid)) for _ in range(args.rounds)]
+        g_ms = float(np.median(runs))
+        row["grid"] = dict(build_ms=min(builds), builds_ms=builds, query_ms=g_ms, runs_ms=runs, brute_ms=pen["signed_ms"],
+                           brute_over_grid=pen["signed_ms"] / g_ms, cell_m=float(grid.h), cells=[int(x) for x in grid.n],
+                           n_entries=grid.n_entries, n_overflow=grid.n_overflow,
+                           equal_bits=all(bool((got[k].view(torch.int32) == brute[k].view(torch.int32)).all()) for k in brute))
+        # every placement three extents away along x: each lane walks every shell and tests every stored triangle from global memory
+        far = tfs.clone()
+        far[:, 0, 3] += 3.0 * float((hi - lo).max())
+        b_ms = float(np.median([timed(lambda: call(far, None)) for _ in range(args.rounds)]))
+        few = far[:min(4, T)].contiguous()
+        o4 = {k: v[:min(4, T)].clone() for k, v in o_p.items()}
+        call(few, grid, o4, ws)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        call(few, grid, o4, ws)
+        torch.cuda.synchronize()
+        estimate = (time.perf_counter() - t0) * 1e3 * max(1.0, T / 4)
+        row["far"] = dict(offset_m=3.0 * float((hi - lo).max()), brute_ms=b_ms, estimate_ms=estimate, limit_ms=args.far_limit * b_ms)
+        if estimate > args.far_limit * b_ms:
+            row["far"]["skipped"] = "the estimate from four placements is above the limit"
+        else:
+            brute = {k: v.clone() for k, v in call(far, None).items()}
+            got = {k: v.clone() for k, v in call(far, grid).items()}
+            torch.cuda.synchronize()
+            times = []
+            for _ in range(args.rounds):                                  # single calls: one may take seconds
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                call(far, grid)
+                torch.cuda.synchronize()
+                times.append((time.perf_counter() - t0) * 1e3)
+            row["far"].update(query_ms=float(np.median(times)), runs_ms=times, grid_over_brute=float(np.median(times)) / b_ms,
+                              equal_bits=all(bool((got[k].view(torch.int32) == brute[k].view(torch.int32)).all()) for k in brute))
+    return row
 
 
 out = {"metric": "ms per call, signed against unsigned sibling in turns: ops.mesh_signed_distance (all five outputs) / ops.mesh_point_distance "
@@ -110,6 +168,9 @@ with torch.inference_mode():
         Ks = np.tile(np.asarray(sc["K"], np.float64)[None], (V, 1, 1))
         mesh, t = reconstruct_object(rgb, depth, (depth > 0).to(torch.uint8), P, Ks, voxel=0.0025, device=dev, keep_components="largest")
         out["cases"].append(case("can fused at 2.5 mm", t))
+        if args.accel == "grid":
+            mesh, t = reconstruct_object(rgb, depth, (depth > 0).to(torch.uint8), P, Ks, voxel=None, device=dev, keep_components="largest")
+            out["cases"].append(case("can fused at 128 voxels", t))
 print(json.dumps(out))
 if args.out:
     doc = json.load(open(args.out)) if os.path.exists(args.out) else {}
