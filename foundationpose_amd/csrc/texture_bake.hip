@@ -6,6 +6,8 @@
 //                    L1 hits.  The V views are visited inside the kernel in index order: one summation order, no atomics, nothing to
 //                    clear.  A view's pose and intrinsics are wave-uniform (scalar) loads; depth / mask / rgb are gathers at the
 //                    texel's pixel, which the texels of a block share or neighbour.
+// The views are recon_common.h's ViewStack and the walk over them its load_view, to_camera and pixel_of, the ones k_tsdf_integrate
+// calls: which views are skipped and which pixel a point falls on is decided there, the facing test between them here.
 // Compiled with -ffp-contract=off (SRCS_EXACT): every float32 value is the one the numpy restatement (tests/texture_bake_model.py)
 // computes.  Not a tuned path: baking is a setup call (three IEEE divisions and three dependent gathers per texel and view, as the
 // fusion has per voxel and view).  Times: scripts/bench_reconstruct.py.
@@ -13,25 +15,14 @@
 
 #include <math.h>
 
+#include "recon_common.h"
+
 namespace {
 
 constexpr int kThreads = 256;
 
-__device__ __forceinline__ bool finite4(float a, float b, float c, float d) {
-  return isfinite(a) && isfinite(b) && isfinite(c) && isfinite(d);
-}
-
-struct Views {
-  const float* depth;
-  const float* rgb;
-  const uint8_t* masks;
-  const float* poses;
-  const double* Ks;
-  int V, H, W;
-};
-
 __global__ __launch_bounds__(kThreads) void k_texture_bake(const float* __restrict__ pos, int Nv, const int32_t* __restrict__ faces, int F,
-                                                           const float* __restrict__ vcol, Views in, int T, int Bx, size_t ntexels,
+                                                           const float* __restrict__ vcol, recon::ViewStack in, int T, int Bx, size_t ntexels,
                                                            float tol, float min_cos2, float min_depth, float* __restrict__ tex,
                                                            uint8_t* __restrict__ coverage) {
   const size_t g = (size_t)blockIdx.x * kThreads + threadIdx.x;
@@ -91,18 +82,12 @@ __global__ __launch_bounds__(kThreads) void k_texture_bake(const float* __restri
     const float nz = e1x * e2y - e1y * e2x;
     const float nn = (nx * nx + ny * ny) + nz * nz;
     if (nn > 0.f && nn < INFINITY) {
-      const float Wf = (float)in.W, Hf = (float)in.H;
       for (int v = 0; v < in.V; ++v) {
-        const float* M = in.poses + (size_t)v * 16;
-        const double* Kd = in.Ks + (size_t)v * 9;
-        const float fx = (float)Kd[0], skew = (float)Kd[1], cx = (float)Kd[2], fy = (float)Kd[4], cy = (float)Kd[5];
-        bool ok = finite4(fx, fy, cx, cy) && skew == 0.f;
-#pragma unroll
-        for (int k = 0; k < 16; k += 4) ok = ok && finite4(M[k], M[k + 1], M[k + 2], M[k + 3]);
-        if (!ok) continue;   // wave-uniform
-        const float X = ((M[0] * px + M[1] * py) + M[2] * pz) + M[3];
-        const float Y = ((M[4] * px + M[5] * py) + M[6] * pz) + M[7];
-        const float Z = ((M[8] * px + M[9] * py) + M[10] * pz) + M[11];
+        const float* M;
+        recon::Pinhole cam;
+        if (!recon::load_view(in, v, M, cam)) continue;   // wave-uniform
+        float X, Y, Z;
+        recon::to_camera(M, px, py, pz, X, Y, Z);
         if (!(Z > 0.f)) continue;
         const float Nx = (M[0] * nx + M[1] * ny) + M[2] * nz;
         const float Ny = (M[4] * nx + M[5] * ny) + M[6] * nz;
@@ -112,9 +97,8 @@ __global__ __launch_bounds__(kThreads) void k_texture_bake(const float* __restri
         const float rr = (X * X + Y * Y) + Z * Z;
         const float w = (d * d) / (NN * rr);   // cos^2 of the angle between the face's normal and the ray
         if (!(d < 0.f && w >= min_cos2)) continue;
-        const float uf = floorf(((fx * X) / Z + cx) + 0.5f), vf = floorf(((fy * Y) / Z + cy) + 0.5f);
-        if (!(uf >= 0.f && uf < Wf && vf >= 0.f && vf < Hf)) continue;
-        const size_t p = ((size_t)v * in.H + (size_t)(int)vf) * in.W + (size_t)(int)uf;
+        size_t p;
+        if (!recon::pixel_of(in, v, cam, X, Y, Z, p)) continue;
         if (in.masks && in.masks[p] == 0) continue;
         const float dz = in.depth[p];
         if (!(dz >= min_depth)) continue;
@@ -142,22 +126,20 @@ extern "C" int fp_texture_bake(const float* pos, int Nv, const int32_t* faces, i
   const char* who = "fp_texture_bake";
   FP_REQUIRE(F >= 0 && F <= (1 << 24), "%s: F=%d outside 0..2^24 faces", who, F);
   FP_REQUIRE(Nv >= 0, "%s: Nv=%d must be >= 0", who, Nv);
-  FP_REQUIRE(V >= 0 && V <= 4096, "%s: V=%d outside 0..4096", who, V);
-  FP_REQUIRE(H >= 1 && W >= 1, "%s: H=%d W=%d must be >= 1", who, H, W);
-  FP_REQUIRE((long long)H * W <= (1ll << 28), "%s: more than 2^28 pixels (%d x %d)", who, H, W);
+  if (int st = recon::check_view_stack(who, V, H, W, "")) return st;
   FP_REQUIRE(T >= 2 && T <= FP_TEXTURE_BAKE_MAX_TEXELS, "%s: T=%d outside 2..%d texels a block side", who, T, FP_TEXTURE_BAKE_MAX_TEXELS);
   FP_REQUIRE(Bx >= 1, "%s: Bx=%d must be >= 1", who, Bx);
   const long long Wt = (long long)Bx * T, rows = ((long long)F + Bx - 1) / Bx, Ht = rows * T;
   FP_REQUIRE(Wt <= FP_TEXTURE_BAKE_MAX_SIDE && Ht <= FP_TEXTURE_BAKE_MAX_SIDE, "%s: an atlas of %lld x %lld texels (Ht x Wt), at most %d a side",
              who, Ht, Wt, FP_TEXTURE_BAKE_MAX_SIDE);
   FP_REQUIRE(isfinite(tol) && tol >= 0.f, "%s: tol=%g must be finite and >= 0", who, (double)tol);
-  FP_REQUIRE(isfinite(min_depth) && min_depth >= 0.f, "%s: min_depth=%g must be finite and >= 0", who, (double)min_depth);
+  if (int st = recon::check_min_depth(who, min_depth)) return st;
   FP_REQUIRE(min_cos > 0.f && min_cos <= 1.f, "%s: min_cos=%g must be in (0, 1]", who, (double)min_cos);
   if (F == 0) return FP_OK;
   FP_REQUIRE(pos && faces && tex && coverage, "%s: NULL pos / faces / tex / coverage", who);
   FP_REQUIRE(V == 0 || (depth && rgb && ob_in_cams && Ks), "%s: NULL depth / rgb / ob_in_cams / Ks", who);
   const size_t ntexels = (size_t)(rows * Bx) * (size_t)(T * T);
-  const Views in{depth, rgb, masks, ob_in_cams, Ks, V, H, W};
+  const recon::ViewStack in{depth, rgb, masks, ob_in_cams, Ks, V, H, W};
   hipLaunchKernelGGL(k_texture_bake, dim3((unsigned)((ntexels + kThreads - 1) / kThreads)), dim3(kThreads), 0, (hipStream_t)stream, pos, Nv,
                      faces, F, vertex_color, in, T, Bx, ntexels, tol, min_cos * min_cos, min_depth, tex, coverage);
   FP_CHECK_LAUNCH(who);

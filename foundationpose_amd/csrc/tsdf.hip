@@ -10,6 +10,9 @@
 //                      by the caller), so the order of the output is cube, tetrahedron, table order, whatever the scheduling.
 // A triangle corner depends only on the grid edge it lies on (interpolated from the end with the smaller linear index), so every
 // tetrahedron around an edge writes the same bits and the caller welds by the edge key.
+// recon_common.h holds what is shared with texture_bake.hip, tsdf_raycast.hip and tsdf_components.hip: the walk over the posed views
+// (load_view, to_camera, pixel_of), Grid, axis_gradient, lerp_from_a and the checks of the grid, the origin, the view stack, min_depth
+// and min_weight.  Here: the three kernels, the corner, and the entry points with the checks of their own arguments.
 // Compiled with -ffp-contract=off (SRCS_EXACT): every float32 value is the one the numpy restatement (tests/tsdf_model.py) computes.
 // Not a tuned path: reconstruction is a setup call.  Fusion costs several times the volume's own traffic (three IEEE divisions and
 // three dependent gathers per voxel and view).  The emit kernel runs one lane per cube, writes 3 x 44 bytes per triangle scattered,
@@ -19,27 +22,20 @@
 
 #include <math.h>
 
+#include "recon_common.h"
 #include "tsdf_tables.h"
 
 namespace {
 
+using recon::Grid;
+using recon::axis_gradient;
+using recon::lerp_from_a;
+
 constexpr int kThreads = 256;
 
-struct Grid {
-  int nz, ny, nx;
-  float ox, oy, oz, s;
-};
-
-__device__ __forceinline__ bool finite4(float a, float b, float c, float d) {
-  return isfinite(a) && isfinite(b) && isfinite(c) && isfinite(d);
-}
-
-__global__ __launch_bounds__(kThreads) void k_tsdf_integrate(const float* __restrict__ depth, const float* __restrict__ rgb,
-                                                             const uint8_t* __restrict__ masks, const float* __restrict__ poses,
-                                                             const double* __restrict__ Ks, int V, int H, int W, Grid g, size_t nvox,
-                                                             float trunc, float min_depth, float* __restrict__ tsdf,
-                                                             float* __restrict__ weight, float* __restrict__ color,
-                                                             float* __restrict__ color_weight) {
+__global__ __launch_bounds__(kThreads) void k_tsdf_integrate(recon::ViewStack in, Grid g, size_t nvox, float trunc, float min_depth,
+                                                             float* __restrict__ tsdf, float* __restrict__ weight,
+                                                             float* __restrict__ color, float* __restrict__ color_weight) {
   const size_t i = (size_t)blockIdx.x * kThreads + threadIdx.x;
   if (i >= nvox) return;
   const int ix = (int)(i % (size_t)g.nx);
@@ -48,26 +44,19 @@ __global__ __launch_bounds__(kThreads) void k_tsdf_integrate(const float* __rest
   const float px = g.ox + (float)ix * g.s, py = g.oy + (float)iy * g.s, pz = g.oz + (float)iz * g.s;
   float f = tsdf[i], w = weight[i], cw = color_weight[i];
   float c0 = color[3 * i], c1 = color[3 * i + 1], c2 = color[3 * i + 2];
-  const float Wf = (float)W, Hf = (float)H;
-  for (int v = 0; v < V; ++v) {
-    const float* T = poses + (size_t)v * 16;
-    const double* Kd = Ks + (size_t)v * 9;
-    const float fx = (float)Kd[0], skew = (float)Kd[1], cx = (float)Kd[2], fy = (float)Kd[4], cy = (float)Kd[5];
-    bool ok = finite4(fx, fy, cx, cy) && skew == 0.f;
-#pragma unroll
-    for (int k = 0; k < 16; k += 4) ok = ok && finite4(T[k], T[k + 1], T[k + 2], T[k + 3]);
-    if (!ok) continue;   // wave-uniform
-    const float X = ((T[0] * px + T[1] * py) + T[2] * pz) + T[3];
-    const float Y = ((T[4] * px + T[5] * py) + T[6] * pz) + T[7];
-    const float Z = ((T[8] * px + T[9] * py) + T[10] * pz) + T[11];
+  for (int v = 0; v < in.V; ++v) {
+    const float* T;
+    recon::Pinhole cam;
+    if (!recon::load_view(in, v, T, cam)) continue;   // wave-uniform
+    float X, Y, Z;
+    recon::to_camera(T, px, py, pz, X, Y, Z);
     if (!(Z > 0.f)) continue;
-    const float uf = floorf(((fx * X) / Z + cx) + 0.5f), vf = floorf(((fy * Y) / Z + cy) + 0.5f);
-    if (!(uf >= 0.f && uf < Wf && vf >= 0.f && vf < Hf)) continue;
-    const size_t p = ((size_t)v * H + (size_t)(int)vf) * W + (size_t)(int)uf;
-    const bool object = masks ? masks[p] != 0 : true;
+    size_t p;
+    if (!recon::pixel_of(in, v, cam, X, Y, Z, p)) continue;
+    const bool object = in.masks ? in.masks[p] != 0 : true;
     float obs = 1.f, sdf = 0.f;
     if (object) {
-      const float d = depth[p];
+      const float d = in.depth[p];
       if (!(d >= min_depth)) continue;
       sdf = d - Z;
       if (sdf < -trunc) continue;
@@ -77,7 +66,7 @@ __global__ __launch_bounds__(kThreads) void k_tsdf_integrate(const float* __rest
     f = (f * w + obs) / (w + 1.f);
     w = w + 1.f;
     if (object && fabsf(sdf) <= trunc) {
-      const float* c = rgb + 3 * p;
+      const float* c = in.rgb + 3 * p;
       const float d1 = cw + 1.f;
       c0 = (c0 * cw + c[0]) / d1;
       c1 = (c1 * cw + c[1]) / d1;
@@ -105,15 +94,6 @@ struct Outputs {
   float* col;
   float* nrm;
 };
-
-// the gradient of tsdf along one axis at voxel `at` (coordinate c of n along it, n >= 2, `stride` voxels apart)
-__device__ __forceinline__ float axis_gradient(const float* __restrict__ f, size_t at, size_t stride, int c, int n) {
-  if (c == 0) return f[at + stride] - f[at];
-  if (c == n - 1) return f[at] - f[at - stride];
-  return 0.5f * (f[at + stride] - f[at - stride]);
-}
-
-__device__ __forceinline__ float lerp_from_a(float a, float b, float t) { return a + t * (b - a); }
 
 // one triangle corner: on the grid edge between voxel (ax, ay, az) and voxel (bx, by, bz), the first with the smaller linear index
 __device__ __forceinline__ void emit_corner(const Grid& g, const Fields& in, const Outputs& out, size_t row, int ax, int ay, int az, int bx,
@@ -199,41 +179,25 @@ __global__ __launch_bounds__(kThreads) void k_tsdf_cubes(const float* __restrict
   if (!kEmit) counts[c] = n;
 }
 
-int check_grid(const char* who, int nz, int ny, int nx) {
-  FP_REQUIRE(nz >= 1 && ny >= 1 && nx >= 1 && nz <= FP_TSDF_MAX_DIM && ny <= FP_TSDF_MAX_DIM && nx <= FP_TSDF_MAX_DIM,
-             "%s: volume %d x %d x %d (nz, ny, nx) has a dimension outside 1..%d", who, nz, ny, nx, FP_TSDF_MAX_DIM);
-  FP_REQUIRE((long long)nz * ny * nx <= (1ll << 30), "%s: volume %d x %d x %d has more than 2^30 voxels", who, nz, ny, nx);
-  return FP_OK;
-}
-
-int check_origin(const char* who, const float* origin, float voxel) {
-  FP_REQUIRE(origin, "%s: NULL origin", who);
-  FP_REQUIRE(isfinite(origin[0]) && isfinite(origin[1]) && isfinite(origin[2]), "%s: origin (%g, %g, %g) is not finite", who,
-             (double)origin[0], (double)origin[1], (double)origin[2]);
-  FP_REQUIRE(isfinite(voxel) && voxel > 0.f, "%s: voxel=%g must be finite and > 0", who, (double)voxel);
-  return FP_OK;
-}
-
 }  // namespace
 
 extern "C" int fp_tsdf_integrate(const float* depth, const float* rgb, const uint8_t* masks, const float* ob_in_cams, const double* Ks, int V,
                                  int H, int W, int nz, int ny, int nx, const float* origin, float voxel, float trunc, float min_depth,
                                  float* tsdf, float* weight, float* color, float* color_weight, void* stream) {
   const char* who = "fp_tsdf_integrate";
-  FP_REQUIRE(V >= 0 && V <= 4096, "%s: V=%d outside 0..4096 (fuse the views in several calls)", who, V);
-  FP_REQUIRE(H >= 1 && W >= 1, "%s: H=%d W=%d must be >= 1", who, H, W);
-  FP_REQUIRE((long long)H * W <= (1ll << 28), "%s: more than 2^28 pixels (%d x %d)", who, H, W);
-  if (int st = check_grid(who, nz, ny, nx)) return st;
-  if (int st = check_origin(who, origin, voxel)) return st;
+  if (int st = recon::check_view_stack(who, V, H, W, " (fuse the views in several calls)")) return st;
+  if (int st = recon::check_grid(who, nz, ny, nx)) return st;
+  if (int st = recon::check_origin(who, origin, voxel)) return st;
   FP_REQUIRE(isfinite(trunc) && trunc > 0.f, "%s: trunc=%g must be finite and > 0", who, (double)trunc);
-  FP_REQUIRE(isfinite(min_depth) && min_depth >= 0.f, "%s: min_depth=%g must be finite and >= 0", who, (double)min_depth);
+  if (int st = recon::check_min_depth(who, min_depth)) return st;
   FP_REQUIRE(tsdf && weight && color && color_weight, "%s: NULL volume array", who);
   if (V == 0) return FP_OK;
   FP_REQUIRE(depth && rgb && ob_in_cams && Ks, "%s: NULL depth / rgb / ob_in_cams / Ks", who);
   const size_t nvox = (size_t)nz * ny * nx;
   const Grid g{nz, ny, nx, origin[0], origin[1], origin[2], voxel};
-  hipLaunchKernelGGL(k_tsdf_integrate, dim3((unsigned)((nvox + kThreads - 1) / kThreads)), dim3(kThreads), 0, (hipStream_t)stream, depth, rgb,
-                     masks, ob_in_cams, Ks, V, H, W, g, nvox, trunc, min_depth, tsdf, weight, color, color_weight);
+  const recon::ViewStack in{depth, rgb, masks, ob_in_cams, Ks, V, H, W};
+  hipLaunchKernelGGL(k_tsdf_integrate, dim3((unsigned)((nvox + kThreads - 1) / kThreads)), dim3(kThreads), 0, (hipStream_t)stream, in, g, nvox,
+                     trunc, min_depth, tsdf, weight, color, color_weight);
   FP_CHECK_LAUNCH(who);
   return FP_OK;
 }
@@ -241,8 +205,8 @@ extern "C" int fp_tsdf_integrate(const float* depth, const float* rgb, const uin
 extern "C" int fp_tsdf_count_triangles(const float* tsdf, const float* weight, int nz, int ny, int nx, float min_weight, int32_t* counts,
                                        void* stream) {
   const char* who = "fp_tsdf_count_triangles";
-  if (int st = check_grid(who, nz, ny, nx)) return st;
-  FP_REQUIRE(isfinite(min_weight), "%s: min_weight=%g must be finite", who, (double)min_weight);
+  if (int st = recon::check_grid(who, nz, ny, nx)) return st;
+  if (int st = recon::check_min_weight(who, min_weight)) return st;
   const size_t ncubes = (size_t)(nz - 1) * (ny - 1) * (nx - 1);
   if (ncubes == 0) return FP_OK;
   FP_REQUIRE(tsdf && weight && counts, "%s: NULL tsdf / weight / counts", who);
@@ -258,9 +222,9 @@ extern "C" int fp_tsdf_emit_triangles(const float* tsdf, const float* weight, co
                                       int nx, const float* origin, float voxel, float min_weight, const int64_t* offsets, long long total,
                                       int64_t* keys, float* pos, float* col, float* nrm, void* stream) {
   const char* who = "fp_tsdf_emit_triangles";
-  if (int st = check_grid(who, nz, ny, nx)) return st;
-  if (int st = check_origin(who, origin, voxel)) return st;
-  FP_REQUIRE(isfinite(min_weight), "%s: min_weight=%g must be finite", who, (double)min_weight);
+  if (int st = recon::check_grid(who, nz, ny, nx)) return st;
+  if (int st = recon::check_origin(who, origin, voxel)) return st;
+  if (int st = recon::check_min_weight(who, min_weight)) return st;
   FP_REQUIRE(total >= 0 && total <= (1ll << 29), "%s: total=%lld outside 0..2^29 triangles", who, total);
   const size_t ncubes = (size_t)(nz - 1) * (ny - 1) * (nx - 1);
   if (ncubes == 0 || total == 0) return FP_OK;

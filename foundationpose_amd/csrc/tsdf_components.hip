@@ -16,7 +16,9 @@
 // agent-scope atomic loads, never with plain loads the compiler could hoist out of a loop.
 // Times, also of builds without the ballot and without the wave sum (both slower, so neither was kept as an option):
 // scripts/bench_tsdf_components.py, profiles/tsdf_components.json, DESIGN.md section 1.
+// The volume's dimensions are checked by recon_common.h's check_grid, as in tsdf.hip and tsdf_raycast.hip.
 #include "fp_common.h"
+#include "recon_common.h"
 
 namespace {
 
@@ -116,9 +118,7 @@ __global__ __launch_bounds__(kThreads) void k_tc_flatten(const int32_t* __restri
 
 extern "C" int fp_tsdf_label_components(const int32_t* counts, int nz, int ny, int nx, int32_t* labels, int32_t* sizes, void* stream) {
   const char* who = "fp_tsdf_label_components";
-  FP_REQUIRE(nz >= 1 && ny >= 1 && nx >= 1 && nz <= FP_TSDF_MAX_DIM && ny <= FP_TSDF_MAX_DIM && nx <= FP_TSDF_MAX_DIM,
-             "%s: volume %d x %d x %d (nz, ny, nx) has a dimension outside 1..%d", who, nz, ny, nx, FP_TSDF_MAX_DIM);
-  FP_REQUIRE((long long)nz * ny * nx <= (1ll << 30), "%s: volume %d x %d x %d has more than 2^30 voxels", who, nz, ny, nx);
+  if (int st = recon::check_grid(who, nz, ny, nx)) return st;
   const Cubes g{nx - 1, ny - 1, nz - 1, (nz - 1) * (ny - 1) * (nx - 1)};
   if (g.n == 0) return FP_OK;
   FP_REQUIRE(counts && labels && sizes, "%s: NULL counts / labels / sizes", who);

@@ -10,13 +10,20 @@
 //                    below 0 after a known one at or above 0 is the hit; the surface is the zero of the chord between the two.
 // No atomics, no workspace, no allocation, no synchronisation; every output element is written exactly once (0 on a miss).  The march
 // is divergent by nature: a wave runs as long as its longest ray, which the box clip bounds by the box's diagonal over step.
+// The volume's Grid, the extraction's axis_gradient and lerp_from_a, and the checks of the grid, the origin and min_weight are
+// recon_common.h's; trilinear and dot3f, which only the rays use, are here.
 // Compiled with -ffp-contract=off (SRCS_EXACT): every float32 value is the one the numpy restatement (tests/tsdf_raycast_model.py)
 // computes, bit for bit.  Times: scripts/bench_tsdf_raycast.py, DESIGN.md section 1.
 #include "fp_common.h"
 
 #include <math.h>
 
+#include "recon_common.h"
+
 namespace {
+
+using recon::axis_gradient;
+using recon::lerp_from_a;
 
 constexpr int kThreads = 256;
 constexpr int kBlockSide = 16;    // pixels a workgroup covers per axis: 2 x 2 wave tiles of 8 x 8
@@ -26,8 +33,7 @@ struct Volume {
   const float* weight;
   const float* color;
   const float* color_weight;
-  int nz, ny, nx;
-  float ox, oy, oz, s;
+  recon::Grid g;
 };
 
 struct Camera {      // one host K9 (view == NULL, Ks == NULL) or the fp_views table
@@ -49,8 +55,6 @@ __device__ __forceinline__ float dot3f(float a0, float b0, float a1, float b1, f
   return (a0 * b0 + a1 * b1) + a2 * b2;
 }
 
-__device__ __forceinline__ float lerp_from_a(float a, float b, float t) { return a + t * (b - a); }
-
 // the value at (fx, fy, fz) inside a cell from its corners v[dx + 2 dy + 4 dz]: along x, then y, then z
 __device__ __forceinline__ float trilinear(const float v[8], float fx, float fy, float fz) {
   const float c00 = lerp_from_a(v[0], v[1], fx), c10 = lerp_from_a(v[2], v[3], fx);
@@ -58,18 +62,12 @@ __device__ __forceinline__ float trilinear(const float v[8], float fx, float fy,
   return lerp_from_a(lerp_from_a(c00, c10, fy), lerp_from_a(c01, c11, fy), fz);
 }
 
-// the gradient of tsdf along one axis at voxel `at` (coordinate c of n along it, n >= 2, `stride` voxels apart): fp_tsdf_emit_triangles'
-__device__ __forceinline__ float axis_gradient(const float* __restrict__ f, size_t at, size_t stride, int c, int n) {
-  if (c == 0) return f[at + stride] - f[at];
-  if (c == n - 1) return f[at] - f[at - stride];
-  return 0.5f * (f[at + stride] - f[at - stride]);
-}
-
-__global__ __launch_bounds__(kThreads) void k_tsdf_raycast(Volume g, float min_weight, const float* __restrict__ poses, Camera cam,
+__global__ __launch_bounds__(kThreads) void k_tsdf_raycast(Volume vol, float min_weight, const float* __restrict__ poses, Camera cam,
                                                            const float* __restrict__ bbox2d, int H, int W, int oh, int ow, float step,
                                                            float z_near, float z_far, int tiles_x, RayOut out) {
   __shared__ float row[kRowFloats];
   __shared__ int row_ok;
+  const recon::Grid& g = vol.g;
   const int n = blockIdx.y;
   if (threadIdx.x == 0) {
     const float* T = poses + (size_t)n * 16;
@@ -158,8 +156,8 @@ __global__ __launch_bounds__(kThreads) void k_tsdf_raycast(Volume g, float min_w
 #pragma unroll
         for (int q = 0; q < 8; ++q) {
           const size_t at = base + (q & 1) + (q >> 1 & 1) * sy + (q >> 2) * sz;
-          known = known && g.weight[at] >= min_weight;
-          val[q] = g.tsdf[at];
+          known = known && vol.weight[at] >= min_weight;
+          val[q] = vol.tsdf[at];
         }
         f = trilinear(val, fr[0], fr[1], fr[2]);
       }
@@ -209,9 +207,9 @@ __global__ __launch_bounds__(kThreads) void k_tsdf_raycast(Volume g, float min_w
       for (int q = 0; q < 8; ++q) {
         const int dx = q & 1, dy = q >> 1 & 1, dz = q >> 2;
         const size_t at = base + dx + dy * sy + dz * sz;
-        gx[q] = axis_gradient(g.tsdf, at, 1, ci[0] + dx, g.nx);
-        gy[q] = axis_gradient(g.tsdf, at, sy, ci[1] + dy, g.ny);
-        gz[q] = axis_gradient(g.tsdf, at, sz, ci[2] + dz, g.nz);
+        gx[q] = axis_gradient(vol.tsdf, at, 1, ci[0] + dx, g.nx);
+        gy[q] = axis_gradient(vol.tsdf, at, sy, ci[1] + dy, g.ny);
+        gz[q] = axis_gradient(vol.tsdf, at, sz, ci[2] + dz, g.nz);
       }
       const float n0 = trilinear(gx, fr[0], fr[1], fr[2]), n1 = trilinear(gy, fr[0], fr[1], fr[2]), n2 = trilinear(gz, fr[0], fr[1], fr[2]);
       const float len = sqrtf((n0 * n0 + n1 * n1) + n2 * n2);
@@ -227,10 +225,10 @@ __global__ __launch_bounds__(kThreads) void k_tsdf_raycast(Volume g, float min_w
       for (int q = 0; q < 8; ++q) {
         const int dx = q & 1, dy = q >> 1 & 1, dz = q >> 2;
         const size_t at = base + dx + dy * sy + dz * sz;
-        if (g.color_weight[at] > 0.f) {
+        if (vol.color_weight[at] > 0.f) {
           const float w = ((dx ? fr[0] : 1.f - fr[0]) * (dy ? fr[1] : 1.f - fr[1])) * (dz ? fr[2] : 1.f - fr[2]);
 #pragma unroll
-          for (int k = 0; k < 3; ++k) acc[k] = acc[k] + w * g.color[3 * at + k];
+          for (int k = 0; k < 3; ++k) acc[k] = acc[k] + w * vol.color[3 * at + k];
           accw = accw + w;
         }
       }
@@ -258,17 +256,12 @@ extern "C" int fp_tsdf_raycast(const float* tsdf, const float* weight, const flo
   FP_REQUIRE((long long)oh * ow <= (1 << 20), "%s: crop %dx%d has more than 2^20 pixels", who, oh, ow);
   FP_REQUIRE(bbox2d || (oh == H && ow == W), "%s: without bbox2d the crop is the frame: oh x ow = %d x %d but H x W = %d x %d", who, oh, ow,
              H, W);
-  FP_REQUIRE(nz >= 1 && ny >= 1 && nx >= 1 && nz <= FP_TSDF_MAX_DIM && ny <= FP_TSDF_MAX_DIM && nx <= FP_TSDF_MAX_DIM,
-             "%s: volume %d x %d x %d (nz, ny, nx) has a dimension outside 1..%d", who, nz, ny, nx, FP_TSDF_MAX_DIM);
-  FP_REQUIRE((long long)nz * ny * nx <= (1ll << 30), "%s: volume %d x %d x %d has more than 2^30 voxels", who, nz, ny, nx);
-  FP_REQUIRE(origin, "%s: NULL origin", who);
-  FP_REQUIRE(isfinite(origin[0]) && isfinite(origin[1]) && isfinite(origin[2]), "%s: origin (%g, %g, %g) is not finite", who,
-             (double)origin[0], (double)origin[1], (double)origin[2]);
-  FP_REQUIRE(isfinite(voxel) && voxel > 0.f, "%s: voxel=%g must be finite and > 0", who, (double)voxel);
+  if (int st = recon::check_grid(who, nz, ny, nx)) return st;
+  if (int st = recon::check_origin(who, origin, voxel)) return st;
   FP_REQUIRE(isfinite(step) && step > 0.f, "%s: step=%g must be finite and > 0", who, (double)step);
   FP_REQUIRE(isfinite(z_near) && z_near >= 0.f, "%s: z_near=%g must be finite and >= 0", who, (double)z_near);
   FP_REQUIRE(isfinite(z_far) && z_far >= z_near, "%s: z_far=%g must be finite and >= z_near=%g", who, (double)z_far, (double)z_near);
-  FP_REQUIRE(isfinite(min_weight), "%s: min_weight=%g must be finite", who, (double)min_weight);
+  if (int st = recon::check_min_weight(who, min_weight)) return st;
   {
     const double ex = nx - 1, ey = ny - 1, ez = nz - 1;
     const double samples = sqrt(ex * ex + ey * ey + ez * ez) * (double)voxel / (double)step;
@@ -293,9 +286,9 @@ extern "C" int fp_tsdf_raycast(const float* tsdf, const float* weight, const flo
   }
   if (N == 0) return FP_OK;
   FP_REQUIRE(poses, "%s: NULL poses", who);
-  const Volume g{tsdf, weight, color, color_weight, nz, ny, nx, origin[0], origin[1], origin[2], voxel};
+  const Volume vol{tsdf, weight, color, color_weight, recon::Grid{nz, ny, nx, origin[0], origin[1], origin[2], voxel}};
   const int tiles_x = fp_cdiv(ow, kBlockSide), tiles_y = fp_cdiv(oh, kBlockSide);
-  hipLaunchKernelGGL(k_tsdf_raycast, dim3((unsigned)(tiles_x * tiles_y), (unsigned)N), dim3(kThreads), 0, (hipStream_t)stream, g, min_weight,
+  hipLaunchKernelGGL(k_tsdf_raycast, dim3((unsigned)(tiles_x * tiles_y), (unsigned)N), dim3(kThreads), 0, (hipStream_t)stream, vol, min_weight,
                      poses, cam, bbox2d, H, W, oh, ow, step, z_near, z_far, tiles_x, RayOut{depth, xyz, normal, out_color});
   FP_CHECK_LAUNCH(who);
   return FP_OK;

@@ -1629,6 +1629,67 @@ def mspd(model_pts, poses, gt, K, gt_index=None, symmetry_tfs=None, out=None):
 TSDF_MAX_DIM = 4096                                    # FP_TSDF_MAX_DIM (include/fp_amd.h)
 
 
+def _metres(what, name, x, positive=True):
+    """x as a float that is finite and > 0 (positive) or >= 0, and still so once rounded to float32; ValueError otherwise"""
+    v = float(x)
+    if not (np.isfinite(np.float32(v)) and (np.float32(v) > 0 if positive else v >= 0)):
+        raise ValueError(f"{what}: {name} must be finite and {'> 0' if positive else '>= 0'} (metres), got {x!r}")
+    return v
+
+
+def _tensors_nd(what, *named):
+    """each (name, t, nd) is a tensor of nd dimensions, refused in the order given"""
+    for name, t, nd in named:
+        if not torch.is_tensor(t):
+            raise _lib.FpAmdError(f"{what}: {name} must be a tensor, got {type(t).__name__}")
+        if t.dim() != nd:
+            raise _lib.FpAmdError(f"{what}: {name} must have {nd} dimensions, got {tuple(t.shape)}")
+
+
+def _view_stack(what, depth, rgb, masks, ob_in_cams, too_many=""):
+    """the shapes of a stack of posed views (tensors of the right ndim: _tensors_nd) -> (V, H, W); too_many ends the refusal of V > 4096"""
+    V, H, W = (int(x) for x in depth.shape)
+    if V > 4096:
+        raise _lib.FpAmdError(f"{what}: {V} views in one call, at most 4096{too_many}")
+    if H < 1 or W < 1 or H * W > 1 << 28:
+        raise _lib.FpAmdError(f"{what}: frames of {H} x {W} pixels (1 .. 2^28 pixels are supported)")
+    if tuple(rgb.shape) != (V, H, W, 3):
+        raise _lib.FpAmdError(f"{what}: rgb must be ({V},{H},{W},3) like depth, got {tuple(rgb.shape)}")
+    if masks is not None and (not torch.is_tensor(masks) or tuple(masks.shape) != (V, H, W)):
+        raise _lib.FpAmdError(f"{what}: masks must be a ({V},{H},{W}) tensor like depth or None")
+    if tuple(ob_in_cams.shape) != (V, 4, 4):
+        raise _lib.FpAmdError(f"{what}: ob_in_cams must be ({V},4,4), got {tuple(ob_in_cams.shape)}")
+    return V, H, W
+
+
+def _view_Ks(what, Ks, V, no_skew):
+    """a (V,3,3) device tensor, taken as is, or V host matrices, each checked (_hostK33; no_skew: why a skew is refused) and returned as
+    one (V,3,3) float64 array: the caller uploads it once nothing can be refused any more (torch.as_tensor passes a device tensor on)"""
+    if torch.is_tensor(Ks) and Ks.is_cuda:
+        if tuple(Ks.shape) != (V, 3, 3):
+            raise _lib.FpAmdError(f"{what}: device Ks must be ({V},3,3), got {tuple(Ks.shape)}")
+        return Ks
+    Kh = [_hostK33(K, what, no_skew) for K in Ks]
+    if len(Kh) != V:
+        raise _lib.FpAmdError(f"{what}: {len(Kh)} intrinsic matrices for {V} views")
+    return np.asarray(Kh, dtype=np.float64).reshape(V, 3, 3)
+
+
+def _view_stack_dev(depth, rgb, masks, ob_in_cams, K):
+    """the views (K: _view_Ks') as device tensors of their dtypes, contiguous -> (depth, rgb, masks | None, ob_in_cams, K)"""
+    return (_dev(depth, torch.float32, "depth"), _dev(rgb, torch.float32, "rgb"), _dev(masks, torch.uint8, "masks"),
+            _dev(ob_in_cams, torch.float32, "ob_in_cams"), _dev(K, torch.float64, "Ks") if torch.is_tensor(K) else K)
+
+
+def _volume_dev(tsdf, weight, color, color_weight):
+    return [_dev(t, torch.float32, name) for name, t in (("tsdf", tsdf), ("weight", weight), ("color", color), ("color_weight", color_weight))]
+
+
+def _check_volume_dims(what, dims):
+    if min(dims) < 1 or max(dims) > TSDF_MAX_DIM or dims[0] * dims[1] * dims[2] > 1 << 30:
+        raise _lib.FpAmdError(f"{what}: a volume of {dims} voxels; every dimension must be 1..{TSDF_MAX_DIM} and their product <= 2^30")
+
+
 def _tsdf_grid(what, tsdf, weight, color, color_weight, origin, voxel):
     """shapes and values of a TSDF volume's arrays -> ((nz, ny, nx), origin as 3 float32 on the host, voxel); nothing about devices"""
     for name, t in (("tsdf", tsdf), ("weight", weight), ("color", color), ("color_weight", color_weight)):
@@ -1637,8 +1698,7 @@ def _tsdf_grid(what, tsdf, weight, color, color_weight, origin, voxel):
     if tsdf.dim() != 3:
         raise _lib.FpAmdError(f"{what}: tsdf must be (nz,ny,nx), got {tuple(tsdf.shape)}")
     dims = tuple(int(x) for x in tsdf.shape)
-    if min(dims) < 1 or max(dims) > TSDF_MAX_DIM or dims[0] * dims[1] * dims[2] > 1 << 30:
-        raise _lib.FpAmdError(f"{what}: a volume of {dims} voxels; every dimension must be 1..{TSDF_MAX_DIM} and their product <= 2^30")
+    _check_volume_dims(what, dims)
     for name, t, shape in (("weight", weight, dims), ("color", color, dims + (3,)), ("color_weight", color_weight, dims)):
         if tuple(t.shape) != shape:
             raise _lib.FpAmdError(f"{what}: {name} must be {shape} like tsdf, got {tuple(t.shape)}")
@@ -1648,10 +1708,7 @@ def _tsdf_grid(what, tsdf, weight, color, color_weight, origin, voxel):
         raise ValueError(f"{what}: origin must be 3 numbers, got {origin!r}") from None
     if o.size != 3 or not np.isfinite(o).all() or not np.isfinite(o.astype(np.float32)).all():
         raise ValueError(f"{what}: origin must be 3 finite numbers (metres), got {origin!r}")
-    s = float(voxel)
-    if not (np.isfinite(s) and s > 0 and np.isfinite(np.float32(s)) and np.float32(s) > 0):
-        raise ValueError(f"{what}: voxel must be finite and > 0 (metres), got {voxel!r}")
-    return dims, np.ascontiguousarray(o.astype(np.float32)), s
+    return dims, np.ascontiguousarray(o.astype(np.float32)), _metres(what, "voxel", voxel)
 
 
 def tsdf_integrate(tsdf, weight, color, color_weight, depth, rgb, masks, ob_in_cams, Ks, origin, voxel, trunc, min_depth=0.001):
@@ -1666,47 +1723,17 @@ def tsdf_integrate(tsdf, weight, color, color_weight, depth, rgb, masks, ob_in_c
     several calls, with the bits of one call.  Wrong shapes and values are refused first, then tensors that are not on the device, of
     another dtype or not contiguous, then the volume's arrays."""
     what = "tsdf_integrate"
-    for name, t, nd in (("depth", depth, 3), ("rgb", rgb, 4), ("ob_in_cams", ob_in_cams, 3)):
-        if not torch.is_tensor(t):
-            raise _lib.FpAmdError(f"{what}: {name} must be a tensor, got {type(t).__name__}")
-        if t.dim() != nd:
-            raise _lib.FpAmdError(f"{what}: {name} must have {nd} dimensions, got {tuple(t.shape)}")
-    V, H, W = (int(x) for x in depth.shape)
-    if V > 4096:
-        raise _lib.FpAmdError(f"{what}: {V} views in one call, at most 4096 (fuse them in several calls)")
-    if H < 1 or W < 1 or H * W > 1 << 28:
-        raise _lib.FpAmdError(f"{what}: frames of {H} x {W} pixels (1 .. 2^28 pixels are supported)")
-    if tuple(rgb.shape) != (V, H, W, 3):
-        raise _lib.FpAmdError(f"{what}: rgb must be ({V},{H},{W},3) like depth, got {tuple(rgb.shape)}")
-    if masks is not None and (not torch.is_tensor(masks) or tuple(masks.shape) != (V, H, W)):
-        raise _lib.FpAmdError(f"{what}: masks must be a ({V},{H},{W}) tensor like depth or None")
-    if tuple(ob_in_cams.shape) != (V, 4, 4):
-        raise _lib.FpAmdError(f"{what}: ob_in_cams must be ({V},4,4), got {tuple(ob_in_cams.shape)}")
+    _tensors_nd(what, ("depth", depth, 3), ("rgb", rgb, 4), ("ob_in_cams", ob_in_cams, 3))
+    V, H, W = _view_stack(what, depth, rgb, masks, ob_in_cams, " (fuse them in several calls)")
     dims, o, s = _tsdf_grid(what, tsdf, weight, color, color_weight, origin, voxel)
-    tr, md = float(trunc), float(min_depth)
-    if not (np.isfinite(tr) and tr > 0 and np.isfinite(np.float32(tr)) and np.float32(tr) > 0):
-        raise ValueError(f"{what}: trunc must be finite and > 0 (metres), got {trunc!r}")
-    if not (np.isfinite(md) and md >= 0):
-        raise ValueError(f"{what}: min_depth must be finite and >= 0 (metres), got {min_depth!r}")
-    K_dev = None
-    if torch.is_tensor(Ks) and Ks.is_cuda:
-        if tuple(Ks.shape) != (V, 3, 3):
-            raise _lib.FpAmdError(f"{what}: device Ks must be ({V},3,3), got {tuple(Ks.shape)}")
-        K_dev = Ks
-    else:
-        Kh = [_hostK33(K, what, "the projection of a voxel is defined without one") for K in Ks]
-        if len(Kh) != V:
-            raise _lib.FpAmdError(f"{what}: {len(Kh)} intrinsic matrices for {V} views")
-    d = _dev(depth, torch.float32, "depth")
-    c = _dev(rgb, torch.float32, "rgb")
-    m = _dev(masks, torch.uint8, "masks")
-    P = _dev(ob_in_cams, torch.float32, "ob_in_cams")
-    K_dev = _dev(K_dev, torch.float64, "Ks")
-    vol = [_dev(t, torch.float32, name) for name, t in (("tsdf", tsdf), ("weight", weight), ("color", color), ("color_weight", color_weight))]
+    tr = _metres(what, "trunc", trunc)
+    md = _metres(what, "min_depth", min_depth, positive=False)
+    K = _view_Ks(what, Ks, V, "the projection of a voxel is defined without one")
+    d, c, m, P, K = _view_stack_dev(depth, rgb, masks, ob_in_cams, K)
+    vol = _volume_dev(tsdf, weight, color, color_weight)
     if V == 0:
         return
-    if K_dev is None:
-        K_dev = torch.as_tensor(np.stack(Kh), device=d.device)
+    K_dev = torch.as_tensor(K, device=d.device)
     _lib.check(_lib.lib().fp_tsdf_integrate(_ptr(d), _ptr(c), _ptr(m), _ptr(P), _ptr(K_dev), V, H, W, dims[0], dims[1], dims[2],
                                             o.ctypes.data_as(C.c_void_p), s, tr, md, _ptr(vol[0]), _ptr(vol[1]), _ptr(vol[2]), _ptr(vol[3]),
                                             _stream(d)), "fp_tsdf_integrate")
@@ -1723,8 +1750,7 @@ def tsdf_components(counts, dims):
         nz, ny, nx = (int(n) for n in dims)
     except (TypeError, ValueError):
         raise ValueError(f"{what}: dims must be (nz, ny, nx), got {dims!r}") from None
-    if min(nz, ny, nx) < 1 or max(nz, ny, nx) > TSDF_MAX_DIM or nz * ny * nx > 1 << 30:
-        raise _lib.FpAmdError(f"{what}: a volume of {(nz, ny, nx)} voxels; every dimension must be 1..{TSDF_MAX_DIM} and their product <= 2^30")
+    _check_volume_dims(what, (nz, ny, nx))
     if not torch.is_tensor(counts):
         raise _lib.FpAmdError(f"{what}: counts must be a tensor, got {type(counts).__name__}")
     shape = (nz - 1, ny - 1, nx - 1)
@@ -1762,6 +1788,23 @@ def _component_report(what, labels, sizes, keep):
     return sorted((int(x) for x in host), reverse=True), kept
 
 
+def _min_weight(what, min_weight):
+    mw = float(min_weight)
+    if not np.isfinite(mw):
+        raise ValueError(f"{what}: min_weight must be finite, got {min_weight!r}")
+    return mw
+
+
+def tsdf_count_triangles(tsdf, weight, dims, min_weight):
+    """fp_tsdf_count_triangles on a volume of dims = (nz, ny, nx) voxels (tsdf, weight: float32 device tensors; the caller has checked
+    them, and that min_weight is a finite float) -> the cubes' triangle counts, int32 (nz-1)(ny-1)(nx-1), x fastest.  One launch."""
+    nz, ny, nx = dims
+    counts = torch.empty(((nz - 1) * (ny - 1) * (nx - 1),), dtype=torch.int32, device=tsdf.device)
+    _lib.check(_lib.lib().fp_tsdf_count_triangles(_ptr(tsdf), _ptr(weight), nz, ny, nx, min_weight, _ptr(counts), _stream(tsdf)),
+               "fp_tsdf_count_triangles")
+    return counts
+
+
 def tsdf_extract(tsdf, weight, color, color_weight, origin, voxel, min_weight=1.0, keep=None):
     """The surface of a TSDF volume (arrays, origin and voxel as in tsdf_integrate) as a welded triangle mesh on the device, by
     marching tetrahedra over the cubes whose corners all have weight >= min_weight (fp_tsdf_count_triangles -> torch.cumsum -> one
@@ -1778,18 +1821,15 @@ def tsdf_extract(tsdf, weight, color, color_weight, origin, voxel, min_weight=1.
     Refusals in tsdf_integrate's order."""
     what = "tsdf_extract"
     dims, o, s = _tsdf_grid(what, tsdf, weight, color, color_weight, origin, voxel)
-    mw = float(min_weight)
-    if not np.isfinite(mw):
-        raise ValueError(f"{what}: min_weight must be finite, got {min_weight!r}")
+    mw = _min_weight(what, min_weight)
     keep = _check_keep(what, keep)
-    f, w, c, cw = [_dev(t, torch.float32, name) for name, t in (("tsdf", tsdf), ("weight", weight), ("color", color), ("color_weight", color_weight))]
+    f, w, c, cw = _volume_dev(tsdf, weight, color, color_weight)
     dev, L, st = f.device, _lib.lib(), _stream(f)
     nz, ny, nx = dims
     ncubes = (nz - 1) * (ny - 1) * (nx - 1)
     total = 0
     if ncubes > 0:
-        counts = torch.empty((ncubes,), dtype=torch.int32, device=dev)
-        _lib.check(L.fp_tsdf_count_triangles(_ptr(f), _ptr(w), nz, ny, nx, mw, _ptr(counts), st), "fp_tsdf_count_triangles")
+        counts = tsdf_count_triangles(f, w, dims, mw)
         ends = torch.cumsum(counts, 0, dtype=torch.int64)
         total = int(ends[-1].item())
     report = {} if keep is None else dict(components=[], dropped_triangles=0)
@@ -1869,20 +1909,16 @@ def tsdf_raycast(tsdf, weight, color, color_weight, origin, voxel, poses, K, H, 
     want = tuple(want)
     if not want or any(w not in RAYCAST_OUTPUTS for w in want):
         raise ValueError(f"{what}: want must name at least one of {RAYCAST_OUTPUTS}, got {want!r}")
-    st = s if step is None else float(step)
-    if not (np.isfinite(st) and st > 0 and np.isfinite(np.float32(st)) and np.float32(st) > 0):
-        raise ValueError(f"{what}: step must be finite and > 0 (metres), got {step!r}")
+    st = s if step is None else _metres(what, "step", step)
     diag = float(np.sqrt(sum((n - 1.0) ** 2 for n in dims))) * s
     if diag / st > TSDF_RAYCAST_MAX_SAMPLES - 2:
         raise ValueError(f"{what}: step={st!r} gives {diag / st:.0f} samples along the volume's diagonal, more than "
                          f"{TSDF_RAYCAST_MAX_SAMPLES - 2}: use a longer step")
-    zn, zf, mw = float(z_near), RAYCAST_NO_Z_FAR if z_far is None else float(z_far), float(min_weight)
-    if not (np.isfinite(zn) and zn >= 0):
-        raise ValueError(f"{what}: z_near must be finite and >= 0 (metres), got {z_near!r}")
+    zn = _metres(what, "z_near", z_near, positive=False)
+    zf = RAYCAST_NO_Z_FAR if z_far is None else float(z_far)
     if not (np.isfinite(zf) and zf >= zn):
         raise ValueError(f"{what}: z_far must be finite and >= z_near (metres; None for no limit), got {z_far!r}")
-    if not np.isfinite(mw):
-        raise ValueError(f"{what}: min_weight must be finite, got {min_weight!r}")
+    mw = _min_weight(what, min_weight)
     K9 = vt = None
     if views is not None:
         vt = _views(views, what, N)
@@ -1897,7 +1933,7 @@ def tsdf_raycast(tsdf, weight, color, color_weight, origin, voxel, poses, K, H, 
             raise _lib.FpAmdError(f"{what}: out['{name}'] must be a {shapes[name]} tensor")
     P = _dev(poses, torch.float32, "poses")
     bb = _dev(bbox2d, torch.float32, "bbox2d")
-    f, w, c, cw = [_dev(t, torch.float32, name) for name, t in (("tsdf", tsdf), ("weight", weight), ("color", color), ("color_weight", color_weight))]
+    f, w, c, cw = _volume_dev(tsdf, weight, color, color_weight)
     res = {}
     for name in RAYCAST_OUTPUTS:
         if name in want:
@@ -1966,59 +2002,30 @@ def texture_bake(pos, faces, vertex_color, depth, rgb, masks, ob_in_cams, Ks, to
     ray.  Face f owns the texels x texels block (f % Bx, f / Bx); Bx=None: ceil(sqrt(F)).  One launch, no synchronisation: with device
     Ks capturable in a graph (the outputs are allocated before it).  Refusals in tsdf_integrate's order."""
     what = "texture_bake"
-    for name, t, nd in (("pos", pos, 2), ("faces", faces, 2), ("depth", depth, 3), ("rgb", rgb, 4), ("ob_in_cams", ob_in_cams, 3)):
-        if not torch.is_tensor(t):
-            raise _lib.FpAmdError(f"{what}: {name} must be a tensor, got {type(t).__name__}")
-        if t.dim() != nd:
-            raise _lib.FpAmdError(f"{what}: {name} must have {nd} dimensions, got {tuple(t.shape)}")
+    _tensors_nd(what, ("pos", pos, 2), ("faces", faces, 2), ("depth", depth, 3), ("rgb", rgb, 4), ("ob_in_cams", ob_in_cams, 3))
     if pos.shape[1] != 3 or faces.shape[1] != 3:
         raise _lib.FpAmdError(f"{what}: pos must be (Nv,3) and faces (F,3), got {tuple(pos.shape)} and {tuple(faces.shape)}")
     Nv, F = int(pos.shape[0]), int(faces.shape[0])
     if vertex_color is not None and (not torch.is_tensor(vertex_color) or tuple(vertex_color.shape) != (Nv, 3)):
         raise _lib.FpAmdError(f"{what}: vertex_color must be a ({Nv},3) tensor like pos or None")
-    V, H, W = (int(x) for x in depth.shape)
-    if V > 4096:
-        raise _lib.FpAmdError(f"{what}: {V} views in one call, at most 4096")
-    if H < 1 or W < 1 or H * W > 1 << 28:
-        raise _lib.FpAmdError(f"{what}: frames of {H} x {W} pixels (1 .. 2^28 pixels are supported)")
-    if tuple(rgb.shape) != (V, H, W, 3):
-        raise _lib.FpAmdError(f"{what}: rgb must be ({V},{H},{W},3) like depth, got {tuple(rgb.shape)}")
-    if masks is not None and (not torch.is_tensor(masks) or tuple(masks.shape) != (V, H, W)):
-        raise _lib.FpAmdError(f"{what}: masks must be a ({V},{H},{W}) tensor like depth or None")
-    if tuple(ob_in_cams.shape) != (V, 4, 4):
-        raise _lib.FpAmdError(f"{what}: ob_in_cams must be ({V},4,4), got {tuple(ob_in_cams.shape)}")
+    V, H, W = _view_stack(what, depth, rgb, masks, ob_in_cams)
     Bx, Ht, Wt = texture_atlas_layout(F, texels, Bx)
-    tl, mc, md = float(tol), float(min_cos), float(min_depth)
-    if not (np.isfinite(tl) and tl >= 0 and np.isfinite(np.float32(tl))):
-        raise ValueError(f"{what}: tol must be finite and >= 0 (metres), got {tol!r}")
+    tl = _metres(what, "tol", tol, positive=False)
+    mc = float(min_cos)
     if not (0 < np.float32(mc) <= 1):
         raise ValueError(f"{what}: min_cos must be in (0, 1], got {min_cos!r}")
-    if not (np.isfinite(md) and md >= 0):
-        raise ValueError(f"{what}: min_depth must be finite and >= 0 (metres), got {min_depth!r}")
-    K_dev = None
-    if torch.is_tensor(Ks) and Ks.is_cuda:
-        if tuple(Ks.shape) != (V, 3, 3):
-            raise _lib.FpAmdError(f"{what}: device Ks must be ({V},3,3), got {tuple(Ks.shape)}")
-        K_dev = Ks
-    else:
-        Kh = [_hostK33(K, what, "the projection of a texel is defined without one") for K in Ks]
-        if len(Kh) != V:
-            raise _lib.FpAmdError(f"{what}: {len(Kh)} intrinsic matrices for {V} views")
+    md = _metres(what, "min_depth", min_depth, positive=False)
+    K = _view_Ks(what, Ks, V, "the projection of a texel is defined without one")
     p = _dev(pos, torch.float32, "pos")
     fc = _dev(faces, torch.int32, "faces")
     vc = _dev(vertex_color, torch.float32, "vertex_color")
-    d = _dev(depth, torch.float32, "depth")
-    c = _dev(rgb, torch.float32, "rgb")
-    m = _dev(masks, torch.uint8, "masks")
-    P = _dev(ob_in_cams, torch.float32, "ob_in_cams")
-    K_dev = _dev(K_dev, torch.float64, "Ks")
+    d, c, m, P, K = _view_stack_dev(depth, rgb, masks, ob_in_cams, K)
     tex = torch.empty((Ht, Wt, 3), dtype=torch.float32, device=p.device)
     coverage = torch.empty((Ht, Wt), dtype=torch.uint8, device=p.device)
     uv, uv_idx = texture_atlas_uv(F, texels, Bx, p.device)
     if F == 0:
         return tex, coverage, uv, uv_idx
-    if K_dev is None and V > 0:
-        K_dev = torch.as_tensor(np.stack(Kh), device=p.device)
+    K_dev = torch.as_tensor(K, device=p.device) if V > 0 else None
     _lib.check(_lib.lib().fp_texture_bake(_ptr(p), Nv, _ptr(fc), F, _ptr(vc), _ptr(d), _ptr(c), _ptr(m), _ptr(P), _ptr(K_dev), V, H, W,
                                           int(texels), Bx, tl, mc, md, _ptr(tex), _ptr(coverage), _stream(p)), "fp_texture_bake")
     return tex, coverage, uv, uv_idx

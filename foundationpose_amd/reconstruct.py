@@ -8,7 +8,7 @@ as a floater can be dropped from the mesh at extraction (keep= / keep_components
 import numpy as np
 import torch
 
-from . import _lib, ops
+from . import ops
 from .mesh import SimpleMesh
 
 PAD_VOXELS = 3          # voxels kept free around the observed points, so that the surface closes inside the volume
@@ -51,6 +51,18 @@ def _views_in(rgbs, depths, masks, ob_in_cams, Ks, device, what):
         raise ValueError(f"{what}: Ks must be ({V},3,3) or one (3,3) matrix, got {K.shape}")
     return (_upload(d, torch.float32, device), _upload(c, torch.float32, device), _upload(m, torch.uint8, device),
             _upload(P, torch.float32, device), K)
+
+
+def _masked_xyz(d, m, K):
+    """-> (the views' table: view v for row v, the views' masked depth back-projected unfiltered: (V,H,W,3), camera frame)"""
+    vt = ops.Views(list(K), np.arange(int(d.shape[0])), d.device)
+    return vt, ops.depth_to_xyz_frames(torch.where(m != 0, d, torch.zeros_like(d)).contiguous(), vt)
+
+
+def _check_mesh_tensors(mesh_tensors, what):
+    for k in ("pos", "faces", "vnormals"):
+        if k not in mesh_tensors:
+            raise ValueError(f"{what}: mesh_tensors has no '{k}'")
 
 
 class TsdfVolume:
@@ -101,15 +113,10 @@ class TsdfVolume:
         setup call (it synchronises)."""
         nz, ny, nx = self.dims
         shape = (max(nz - 1, 0), max(ny - 1, 0), max(nx - 1, 0))
-        mw = float(min_weight)
-        if not np.isfinite(mw):
-            raise ValueError(f"TsdfVolume.components: min_weight must be finite, got {min_weight!r}")
+        mw = ops._min_weight("TsdfVolume.components", min_weight)
         if 0 in shape:
             return dict(labels=torch.empty(shape, dtype=torch.int32, device=self.device), components=[])
-        counts = torch.empty(shape, dtype=torch.int32, device=self.device)
-        _lib.check(_lib.lib().fp_tsdf_count_triangles(ops._ptr(self.tsdf), ops._ptr(self.weight), nz, ny, nx, mw, ops._ptr(counts),
-                                                      ops._stream(self.tsdf)), "fp_tsdf_count_triangles")
-        labels, sizes = ops.tsdf_components(counts, self.dims)
+        labels, sizes = ops.tsdf_components(ops.tsdf_count_triangles(self.tsdf, self.weight, self.dims, mw), self.dims)
         sizes = sizes[sizes > 0].cpu().numpy()
         return dict(labels=labels, components=sorted((int(x) for x in sizes), reverse=True))
 
@@ -165,8 +172,7 @@ class TsdfVolume:
         V, H, W = (int(x) for x in d.shape)
         if H < 2 or W < 2:
             raise ValueError(f"{what}: frames of {H} x {W} pixels (at least 2 x 2)")
-        vt = ops.Views(list(K), np.arange(V), self.device)
-        xyz = ops.depth_to_xyz_frames(torch.where(m != 0, d, torch.zeros_like(d)).contiguous(), vt)
+        vt, xyz = _masked_xyz(d, m, K)
         r = ops.tsdf_raycast(*self.arrays(), self.origin, self.voxel, P.contiguous(), None, H, W, want=("depth",), views=vt)
         # the window that is the frame: crop pixel (i, j) reads texel (i, j)
         tf = torch.tensor([[W / (W - 1.0), 0.0, -0.5], [0.0, H / (H - 1.0), -0.5], [0.0, 0.0, 1.0]], dtype=torch.float32, device=self.device)
@@ -222,9 +228,7 @@ def bake_texture(mesh_tensors, rgbs, depths, masks, ob_in_cams, Ks, texels=4, to
         raise ValueError(f"{what}: tol is required (metres; about twice the voxel pitch the mesh was fused at)")
     if rgbs is None:
         raise ValueError(f"{what}: rgbs are required")
-    for k in ("pos", "faces", "vnormals"):
-        if k not in mesh_tensors:
-            raise ValueError(f"{what}: mesh_tensors has no '{k}'")
+    _check_mesh_tensors(mesh_tensors, what)
     dev = mesh_tensors["pos"].device
     return _bake(mesh_tensors, *_views_in(rgbs, depths, masks, ob_in_cams, Ks, dev, what), texels, tol, min_cos, min_depth)
 
@@ -299,9 +303,7 @@ def refine_view_poses(mesh_tensors, depths, masks, ob_in_cams, Ks, iterations=3,
         raise ValueError(f"{what}: masks are required")
     iterations = _check_iterations(iterations, what)
     ops._check_icp(max_dist, 1e-3, 64, what)
-    for k in ("pos", "faces", "vnormals"):
-        if k not in mesh_tensors:
-            raise ValueError(f"{what}: mesh_tensors has no '{k}'")
+    _check_mesh_tensors(mesh_tensors, what)
     d, _, m, P, K = _views_in(None, depths, masks, ob_in_cams, Ks, mesh_tensors["pos"].device, what)
     return _refine_views(mesh_tensors, d, m, P, K, iterations, max_dist)
 
@@ -311,8 +313,7 @@ def _refine_views(t, d, m, P, K, iterations, max_dist):
     from .Utils import get_mesh_handle
     dev = d.device
     V, H, W = (int(x) for x in d.shape)
-    vt = ops.Views(list(K), np.arange(V), dev)
-    xyz = ops.depth_to_xyz_frames(torch.where(m != 0, d, torch.zeros_like(d)).contiguous(), vt)
+    vt, xyz = _masked_xyz(d, m, K)
     mset = ops.MeshSet([get_mesh_handle(t)])
     diam = ops.object_diameters([2.0 * float(t["pos"].norm(dim=1).max())], dev)
     oh, ow = ICP_CROP
@@ -332,10 +333,8 @@ class _AlignSide:
 
     def __init__(self, vol, d, m, K):
         dev = d.device
-        V = int(d.shape[0])
         self.vol, self.H, self.W = vol, int(d.shape[1]), int(d.shape[2])
-        self.vt = ops.Views(list(K), np.arange(V), dev)
-        self.xyz = ops.depth_to_xyz_frames(torch.where(m != 0, d, torch.zeros_like(d)).contiguous(), self.vt)
+        self.vt, self.xyz = _masked_xyz(d, m, K)
         nz, ny, nx = vol.dims
         hi = vol.origin + (np.asarray([nx, ny, nz], dtype=np.float64) - 1.0) * vol.voxel
         self.diam = ops.object_diameters([2.0 * float(np.linalg.norm(np.maximum(np.abs(vol.origin), np.abs(hi))))], dev)
