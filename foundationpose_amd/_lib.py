@@ -51,6 +51,8 @@ SIGNATURES = {
     "fp_mspd": (ci, [vp, ci, vp, ci, vp, vp, vp, ci, ci, vp, vp, vp]),
     "fp_mesh_point_distance_workspace_bytes": (sz, [ci]),
     "fp_mesh_point_distance": (ci, [vp, ci, vp, ci, vp, ci, vp, vp, vp, vp, sz, vp]),
+    "fp_mesh_ray_cast_workspace_bytes": (sz, [ci]),
+    "fp_mesh_ray_cast": (ci, [vp, ci, vp, ci, vp, vp, ci, cf, cf, ci, vp, vp, vp, vp, vp, sz, vp]),
     "fp_mesh_transform_residuals_workspace_bytes": (sz, [ci, ci]),
     "fp_mesh_transform_residuals": (ci, [vp, ci, vp, ci, vp, ci, vp, ci, vp, ci, vp, vp, vp, vp, sz, vp]),
     "fp_mesh_icp_workspace_bytes": (sz, [ci, ci]),

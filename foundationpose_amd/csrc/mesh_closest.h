@@ -2,7 +2,8 @@
 // triangles through LDS, the transformed point of a (transform, point) pair, and the (dd, face) key a scan leaves for a finish.
 // mesh_scan.hip (the nearest face of every query, for all the entry points) and mesh_grid.h (the grid's walk) scan with it;
 // mesh_distance.hip (fp_mesh_point_distance), mesh_symmetry.hip (fp_mesh_transform_residuals), mesh_icp.hip (fp_mesh_icp_step) and
-// mesh_signed.hip (fp_mesh_signed_distance, fp_mesh_penetration) finish with it.  The definition, down to the float32 operation, is
+// mesh_signed.hip (fp_mesh_signed_distance, fp_mesh_penetration) finish with it; mesh_ray.hip (fp_mesh_ray_cast) passes its rays
+// through the same tiles and keys with an intersection test of its own.  The definition, down to the float32 operation, is
 // in include/fp_amd.h; the files are compiled with -ffp-contract=off (SRCS_EXACT), so the operations written here are the ones
 // executed and the entry points give the same bits for the same (point, triangle) pair.
 #pragma once
@@ -122,11 +123,19 @@ __device__ __forceinline__ float staged_distance2(const v3& p, const float4* __r
                        v3{t3.x, t3.y, t3.z}, q);
 }
 
-// The scan of one (lane tile, chunk of faces) workgroup, each lane holding its own query p: faces f0..f1-1 pass through LDS in tiles
-// of kTile (= the workgroup's size: one staging pass) and every lane keeps the smallest (dd, face) -- faces ascend, so `<` keeps the
-// smaller index on a tie.  best / best_f come in as +inf / -1.  Every thread of the workgroup calls it (barriers inside).
-template <int kTile>
-__device__ __forceinline__ void scan_chunk(const v3& p, float4* __restrict__ tile, const float* __restrict__ pos, int Nv,
+// What a lane of the scan holds in registers: a query type with `candidate(tile, k)`, the value the triangle staged in slot k offers
+// it (smaller wins), or NaN / +inf when that triangle does not answer.  A point offers its squared distance; mesh_ray.hip's ray offers
+// the t of its intersection.
+struct PointQuery {
+  v3 p;
+  __device__ __forceinline__ float candidate(const float4* __restrict__ tile, int k) const { return staged_distance2(p, tile, k); }
+};
+
+// The scan of one (lane tile, chunk of faces) workgroup, each lane holding its own query: faces f0..f1-1 pass through LDS in tiles
+// of kTile (= the workgroup's size: one staging pass) and every lane keeps the smallest (value, face) -- faces ascend, so `<` keeps
+// the smaller index on a tie.  best / best_f come in as +inf / -1.  Every thread of the workgroup calls it (barriers inside).
+template <int kTile, class Query>
+__device__ __forceinline__ void scan_chunk(const Query& q, float4* __restrict__ tile, const float* __restrict__ pos, int Nv,
                                            const int32_t* __restrict__ faces, int f0, int f1, int tid, float& best, int& best_f) {
   for (int base = f0; base < f1; base += kTile) {
     const int cnt = min(kTile, f1 - base);
@@ -136,7 +145,7 @@ __device__ __forceinline__ void scan_chunk(const v3& p, float4* __restrict__ til
     // (the loop vectoriser would pair two triangles into packed-fp32 instructions, which this library is built without: Makefile)
 #pragma clang loop vectorize(disable) interleave(disable) unroll_count(2)
     for (int k = 0; k < cnt; ++k) {
-      const float dd = staged_distance2(p, tile, k);
+      const float dd = q.candidate(tile, k);
       // dd < best holds for no NaN and no +inf (best starts at +inf): exactly the candidates with dd <= FLT_MAX that improve
       const bool better = dd < best;
       best = better ? dd : best;

@@ -10,6 +10,17 @@ namespace mesh_scan {
 // on these boundaries
 constexpr int kTile = 256;        // triangles per LDS tile: 4 float4 each, 16 KiB: 8 workgroups of 4 waves a CU
 constexpr int kChunkMin = 1024;   // the fewest faces a workgroup scans (unless the mesh has fewer)
+constexpr int kFillWorkgroups = 2048;  // workgroups wanted in flight (256 CUs x 8 of 4 waves)
+static_assert(kChunkMin % kTile == 0, "a chunk is whole tiles");
+
+// faces per chunk for a grid of `tiles` lane tiles (mesh_scan.hip's scans and mesh_ray.hip's): a multiple of kTile, at least
+// kChunkMin, and no smaller than what gives about kFillWorkgroups workgroups
+inline int chunk_faces(int tiles, int F) {
+  const int want = tiles >= kFillWorkgroups ? 1 : fp_cdiv(kFillWorkgroups, tiles);   // chunks wanted
+  int chunk = fp_cdiv(F > 0 ? F : 1, want);
+  if (chunk < kChunkMin) chunk = kChunkMin;
+  return fp_cdiv(chunk, kTile) * kTile;
+}
 
 // ---- mesh_scan.hip.  Each issues the init launch and, if F > 0, the scan launch on `st`, and reports a failure as "<name> (init)" or
 // "<name> (scan)".  n = Q queries (points) or T * Q pairs numbered t * Q + i (pairs: p = transformed(tfs + 16 t, points[i])), n > 0.

@@ -31,19 +31,9 @@ using namespace mesh_closest;
 constexpr int kThreads = 256;          // queries, or (transform, point) pairs, per workgroup: one per lane
 using mesh_scan::kTile;                // triangles per LDS tile, and
 using mesh_scan::kChunkMin;            // the fewest faces a workgroup scans: mesh_scan.h
-constexpr int kFillWorkgroups = 2048;  // workgroups wanted in flight (256 CUs x 8 of 4 waves)
+using mesh_scan::chunk_faces;
 
-static_assert(kChunkMin % kTile == 0, "a chunk is whole tiles");
 static_assert(kTile == kThreads, "a tile is staged by one pass of the workgroup");
-
-// faces per chunk for a grid of `tiles` lane tiles: a multiple of kTile, at least kChunkMin, and no smaller than what gives about
-// kFillWorkgroups workgroups
-inline int chunk_faces(int tiles, int F) {
-  const int want = tiles >= kFillWorkgroups ? 1 : fp_cdiv(kFillWorkgroups, tiles);   // chunks wanted
-  int chunk = fp_cdiv(F > 0 ? F : 1, want);
-  if (chunk < kChunkMin) chunk = kChunkMin;
-  return fp_cdiv(chunk, kTile) * kTile;
-}
 
 // ---- where query n comes from (n < count <= 2^30: no overflow): point n, or with kPairs the pair n = t * Q + i (count = T * Q)
 template <bool kPairs>
@@ -94,7 +84,7 @@ __global__ __launch_bounds__(kThreads) void k_scan(const float* __restrict__ pos
   const int f1 = min(F, f0 + chunk);
   float best = __builtin_inff();
   int best_f = -1;
-  scan_chunk<kTile>(p, tile, pos, Nv, faces, f0, f1, tid, best, best_f);
+  scan_chunk<kTile>(PointQuery{p}, tile, pos, Nv, faces, f0, f1, tid, best, best_f);
   if (live) Cells::merge(cells + n, best, best_f);
 }
 

@@ -64,6 +64,9 @@ class FoundationPose:
         mesh, tensors = reconstruct_object(rgbs, depths, masks, ob_in_cams, Ks, voxel=voxel, **args)
         est = cls(model_pts=mesh.vertices, model_normals=mesh.vertex_normals, mesh=mesh, mesh_tensors=tensors, **kwargs)
         est.ref_ob_in_cams = getattr(mesh, "ob_in_cams", None)
+        # what view_coverage() reports on without arguments: the views the mesh was fused from (their polished poses where there are)
+        est.ref_views = dict(ob_in_cams=est.ref_ob_in_cams if est.ref_ob_in_cams is not None else ob_in_cams, Ks=Ks,
+                             hw=tuple(int(x) for x in np.shape(depths)[-2:]))
         return est
 
     # ------------------------------------------------------------------ estimater.py:44-78
@@ -272,6 +275,25 @@ class FoundationPose:
             unit = getattr(self.mesh_ori, "voxel", None)
         return compare_meshes(self.mesh_ori, mesh, samples=samples, thresholds=thresholds, seed=seed, unit=unit, device=self.device, tf=tf,
                               accel=accel)
+
+    def view_coverage(self, ob_in_cams=None, Ks=None, hw=None, **kw):
+        """What of the estimator's mesh (as it was handed to reset_object, not the centred one) the views saw -> ops.ViewCoverage
+        (reconstruct.view_coverage: the fraction of the surface seen by at least one view, by each view, the unseen area, and per
+        surface sample the number of views that see it).  ob_in_cams (V,4,4), Ks and hw = (height, width) in that mesh's frame;
+        with none of them, the reference views of an estimator made by from_reference_views: where the next reference view is
+        needed.  kw: samples, seed, rel_tol, min_cos.  An evaluation call (it synchronises)."""
+        from .reconstruct import view_coverage
+        if ob_in_cams is None and Ks is None and hw is None:
+            views = getattr(self, "ref_views", None)
+            if views is None:
+                raise RuntimeError("view_coverage: no reference views (the estimator was not made by from_reference_views): pass "
+                                   "ob_in_cams, Ks and hw")
+            ob_in_cams, Ks, hw = views["ob_in_cams"], views["Ks"], views["hw"]
+        elif ob_in_cams is None or Ks is None or hw is None:
+            raise ValueError("view_coverage: pass ob_in_cams, Ks and hw together (or none of them: the reference views)")
+        pos, faces = (torch.as_tensor(np.ascontiguousarray(x, dtype=dt), device=self.device)
+                      for x, dt in ((self.mesh_ori.vertices, np.float32), (self.mesh_ori.faces, np.int32)))
+        return view_coverage(dict(pos=pos, faces=faces), ob_in_cams, Ks, hw, **kw)
 
     def penetration_into(self, other, poses=None, samples=2048, seed=0, allow_open=False, accel=None):
         """How far this object, at `poses`, reaches into the object of estimator `other` at other.pose_last (not in the reference)

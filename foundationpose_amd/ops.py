@@ -868,15 +868,15 @@ class _MeshCall(NamedTuple):
 
 
 def _mesh_call(what, points, tfs, mesh_tensors, pos, faces, out, *, names, dtypes, shapes_of, limit, workspace_bytes, pairs=False,
-               among="the wanted outputs", signed=None, workspace=None, workspace_maker=None):
+               among="the wanted outputs", signed=None, workspace=None, workspace_maker=None, points_name="points"):
     """What the mesh queries do before they call the library, in the documented order of refusals: the mesh (mesh_tensors or pos /
     faces); shapes: points, pos, faces (n,3) and, with pairs, tfs (T,4,4), the sizes `limit` refuses, with signed = (tables, allow_open)
     the pseudonormal tables, the names and shapes (shapes_of(T, Q)) of the caller's out buffers; device, dtype and contiguity of
     each; overlaps of an out buffer with an input or another; the caller's workspace (None: the per-stream scratch) against
-    workspace_bytes(T, Q) and the out buffers.  Then the outputs of `names` the caller did not give are allocated.
-    -> _MeshCall."""
+    workspace_bytes(T, Q) and the out buffers (points_name: what the messages call `points`).  Then the outputs of `names` the
+    caller did not give are allocated.  -> _MeshCall."""
     pos, faces = _mesh_pos_faces(what, mesh_tensors, pos, faces)
-    _mesh_n3(what, points=points, pos=pos, faces=faces)
+    _mesh_n3(what, **{points_name: points}, pos=pos, faces=faces)
     T = None
     if pairs:
         if not torch.is_tensor(tfs):
@@ -902,7 +902,7 @@ def _mesh_call(what, points, tfs, mesh_tensors, pos, faces, out, *, names, dtype
         if not torch.is_tensor(t) or tuple(t.shape) != shapes[k]:
             raise _lib.FpAmdError(f"{what}: out['{k}'] must be a tensor of shape {shapes[k]}, got "
                                   f"{tuple(t.shape) if torch.is_tensor(t) else type(t).__name__}")
-    pts = _dev(points, torch.float32, "points")
+    pts = _dev(points, torch.float32, points_name)
     m = _dev(tfs, torch.float32, "tfs") if pairs else None
     vp_ = _dev(pos, torch.float32, "pos")
     fc = _dev(faces, torch.int32, "faces")
@@ -910,7 +910,7 @@ def _mesh_call(what, points, tfs, mesh_tensors, pos, faces, out, *, names, dtype
     en = _dev(tables.en, torch.float32, "tables.en") if signed is not None else None
     for k in list(out):
         out[k] = _dev(out[k], dtypes[k], f"out['{k}']")
-    srcs = [("points", pts), ("pos", vp_), ("faces", fc), ("tables.vn", vn), ("tables.en", en)]
+    srcs = [(points_name, pts), ("pos", vp_), ("faces", fc), ("tables.vn", vn), ("tables.en", en)]
     srcs.insert(1 if signed is None else len(srcs), ("tfs", m))   # the signed calls test tfs last, the others after points
     for k, t in out.items():
         for name, src in srcs:
@@ -963,6 +963,76 @@ def mesh_point_distance(points, mesh_tensors=None, pos=None, faces=None, want=ME
         _lib.check(_lib.lib().fp_mesh_point_distance(_ptr(c.pos), c.Nv, _ptr(c.faces), c.F, _ptr(c.points), c.Q, *outs),
                    "fp_mesh_point_distance")
     return {k: c.out[k] for k in names}
+
+
+MESH_RAY_OUTPUTS = ("t", "face", "bary", "hit")
+_MESH_RAY_DTYPES = {"t": torch.float32, "face": torch.int32, "bary": torch.float32, "hit": torch.float32}
+MESH_RAY_CULL = {"none": 0, "back": 1, "front": 2}
+
+
+def _mesh_ray_cull(what, cull):
+    if cull not in MESH_RAY_CULL:
+        raise ValueError(f"{what}: cull must be one of {list(MESH_RAY_CULL)}, got {cull!r}")
+    return MESH_RAY_CULL[cull]
+
+
+def mesh_ray_cast(origins, dirs, mesh_tensors=None, *, pos=None, faces=None, t_min=0.0, t_max=float("inf"), cull="none",
+                  want=MESH_RAY_OUTPUTS, out=None):
+    """fp_mesh_ray_cast: what the rays origins[i] + t * dirs[i] ((R,3) f32 each; dirs need not be unit vectors, t is in units of them)
+    hit first on a triangle mesh -> dict of device tensors: `t` (R,) f32 the smallest t in t_min..t_max (both inclusive) at which the
+    ray meets a triangle, `face` (R,) int32 that triangle, `bary` (R,2) f32 the hit's weights of the face's second and third vertex,
+    `hit` (R,3) f32 the point origin + t * dir (include/fp_amd.h has the definition: Moeller-Trumbore in float32 without an epsilon,
+    the smallest (t, face) wins; +inf / -1 / NaN / NaN for a ray that hits nothing).  cull: "none" keeps both sides of a face, "back"
+    drops the hits on back faces (the ray runs along the face's normal ab x ac), "front" drops those on front faces.  The test is not
+    watertight: a ray through an edge or a vertex that two faces share can miss both.  The mesh, want (t is always computed and
+    returned), out, the workspace (8 bytes a ray) and the refusals are mesh_point_distance's.  Brute force: R x F pair tests."""
+    what = "mesh_ray_cast"
+    names = _mesh_names(what, want, MESH_RAY_OUTPUTS, always=("t",), required=True)
+    code = _mesh_ray_cull(what, cull)
+    t_min, t_max = float(t_min), float(t_max)
+    if not 0.0 <= t_min <= t_max:
+        raise ValueError(f"{what}: 0 <= t_min <= t_max is required, got t_min={t_min}, t_max={t_max}")
+    _mesh_n3(what, origins=origins, dirs=dirs)
+    if tuple(dirs.shape) != tuple(origins.shape):
+        raise _lib.FpAmdError(f"{what}: dirs must be {tuple(origins.shape)} like origins, got {tuple(dirs.shape)}")
+    c = _mesh_call(what, origins, None, mesh_tensors, pos, faces, out, names=names, dtypes=_MESH_RAY_DTYPES,
+                   shapes_of=lambda T, R: {"t": (R,), "face": (R,), "bary": (R, 2), "hit": (R, 3)}, limit=_mesh_limit_points,
+                   workspace_bytes=lambda T, R: _lib.lib().fp_mesh_ray_cast_workspace_bytes(R), points_name="origins")
+    d = _dev(dirs, torch.float32, "dirs")
+    for k in names:
+        if _overlap(c.out[k], d):
+            raise _lib.FpAmdError(f"{what}: out['{k}'] overlaps dirs")
+    _lib.check(_lib.lib().fp_mesh_ray_cast(_ptr(c.pos), c.Nv, _ptr(c.faces), c.F, _ptr(c.points), _ptr(d), c.Q, t_min, t_max, code,
+                                           _ptr(c.out["t"]), _ptr(c.out.get("face")), _ptr(c.out.get("bary")), _ptr(c.out.get("hit")),
+                                           _ptr(c.ws), c.ws_bytes, _stream(c.points)), "fp_mesh_ray_cast")
+    return {k: c.out[k] for k in names}
+
+
+def _check_rel_tol(what, rel_tol):
+    rel_tol = float(rel_tol)
+    if not 0.0 <= rel_tol < 1.0:
+        raise ValueError(f"{what}: rel_tol must be in [0, 1), got {rel_tol!r}")
+    return rel_tol
+
+
+def mesh_visibility(points, eyes, mesh_tensors=None, rel_tol=1e-4, cull="none", *, pos=None, faces=None):
+    """Which of the points (Q,3) f32 each of the eyes (E,3) f32 sees past a mesh -> (E,Q) bool on the device, True where nothing of the
+    mesh lies between.  Segment (e, q) is the ray from eyes[e] with the direction points[q] - eyes[e] (one float32 subtraction), and
+    it is blocked when mesh_ray_cast with t_min = 0 and t_max = 1 - rel_tol answers with a face.  rel_tol is relative to the distance
+    from the eye to the point: the last rel_tol of the segment is not tested, so a point on the mesh's own surface is not blocked by
+    the face it lies on (1e-4 is 30-100 micrometres at the 0.3-1 m a camera stands from a hand-sized object), and whatever lies
+    nearer to the point than that does not block it either.  A segment that is not finite is not blocked.  cull as mesh_ray_cast's.
+    Brute force: E x Q x F pair tests, and 32 bytes of temporaries a segment."""
+    what = "mesh_visibility"
+    rel_tol = _check_rel_tol(what, rel_tol)
+    _mesh_ray_cull(what, cull)
+    _mesh_n3(what, points=points, eyes=eyes)
+    p, e = _dev(points, torch.float32, "points"), _dev(eyes, torch.float32, "eyes")
+    E, Q = int(e.shape[0]), int(p.shape[0])
+    origins = e[:, None, :].expand(E, Q, 3).reshape(E * Q, 3).contiguous()
+    dirs = (p[None, :, :] - e[:, None, :]).reshape(E * Q, 3).contiguous()
+    got = mesh_ray_cast(origins, dirs, mesh_tensors, pos=pos, faces=faces, t_min=0.0, t_max=1.0 - rel_tol, cull=cull, want=("t", "face"))
+    return (got["face"] < 0).reshape(E, Q)
 
 
 MESH_GRID_MAX_CELLS = 1 << 21            # FP_MESH_GRID_MAX_CELLS
@@ -1451,7 +1521,8 @@ class MeshComparison(NamedTuple):
     `chamfer` the mean of the two means; `hausdorff` the larger of the two maxima (of the samples, so a lower bound of the surfaces');
     per threshold: `precision` the fraction of a's samples within it of b, `recall` that of b's samples within it of a, `fscore`
     their harmonic mean (0 when both are 0).  dist_a_to_b / dist_b_to_a: the two distance arrays where they were computed (device
-    tensors from compare_meshes)."""
+    tensors from compare_meshes).  `coverage`: None, or with compare_meshes(seen_from=) the fraction of b's samples that a view saw
+    and that completeness, recall and b's side of chamfer and hausdorff are taken over."""
     accuracy: DistanceStats
     completeness: DistanceStats
     chamfer: float
@@ -1462,6 +1533,7 @@ class MeshComparison(NamedTuple):
     fscore: tuple
     dist_a_to_b: object
     dist_b_to_a: object
+    coverage: Optional[float] = None
 
     @classmethod
     def from_distances(cls, d_ab, d_ba, thresholds):
@@ -1477,10 +1549,54 @@ class MeshComparison(NamedTuple):
 
     def as_dict(self):
         """what json.dumps takes: everything but the distance arrays"""
-        return dict(accuracy=self.accuracy._asdict(), completeness=self.completeness._asdict(), chamfer=self.chamfer,
-                    hausdorff=self.hausdorff, thresholds=list(self.thresholds), precision=list(self.precision),
-                    recall=list(self.recall), fscore=list(self.fscore), samples=[int(np.prod(tuple(self.dist_a_to_b.shape))),
-                                                                                 int(np.prod(tuple(self.dist_b_to_a.shape)))])
+        d = dict(accuracy=self.accuracy._asdict(), completeness=self.completeness._asdict(), chamfer=self.chamfer,
+                 hausdorff=self.hausdorff, thresholds=list(self.thresholds), precision=list(self.precision),
+                 recall=list(self.recall), fscore=list(self.fscore), samples=[int(np.prod(tuple(self.dist_a_to_b.shape))),
+                                                                              int(np.prod(tuple(self.dist_b_to_a.shape)))])
+        if self.coverage is not None:
+            d["coverage"] = self.coverage
+        return d
+
+
+class ViewCoverage(NamedTuple):
+    """reconstruct.view_coverage(mesh, views): what of a mesh's surface a set of views saw, from area-stratified surface samples (a
+    fraction of the samples is a fraction of the area).  `seen` (n,) int32 on the device: the number of views that see each sample;
+    `points` (n,3) f32 and `face` (n,) the samples and their faces (sample_surface's); `fraction` the share of the samples that at
+    least one view sees; `per_view` (V,) the share each view sees; `unseen_area` the area no view sees, in the mesh's unit squared;
+    `area` the mesh's area.  The statistics are float64 on the host."""
+    seen: object
+    points: object
+    face: object
+    fraction: float
+    per_view: tuple
+    unseen_area: float
+    area: float
+
+    @classmethod
+    def from_seen(cls, seen_by_view, points, face, area):
+        """the report of the (V,n) bool table "view v sees sample i" (numpy, or a device tensor: one device-to-host copy)"""
+        if torch.is_tensor(seen_by_view):
+            seen = seen_by_view.sum(dim=0, dtype=torch.int32)
+            table = seen_by_view.detach().cpu().numpy()
+        else:
+            table = np.asarray(seen_by_view, dtype=bool)
+            seen = table.sum(axis=0, dtype=np.int32)
+        V, n = table.shape
+        fraction = float(np.mean(table.any(axis=0))) if V and n else 0.0
+        per_view = tuple(float(np.mean(row)) if n else 0.0 for row in table)
+        return cls(seen, points, face, fraction, per_view, (1.0 - fraction) * float(area), float(area))
+
+    def describe(self):
+        """one line for a log"""
+        worst = min(self.per_view) if self.per_view else float("nan")
+        best = max(self.per_view) if self.per_view else float("nan")
+        return (f"{len(self.per_view)} views see {100.0 * self.fraction:.1f} % of the surface ({self.unseen_area:.6g} of {self.area:.6g} "
+                f"unit^2 unseen); a view sees {100.0 * worst:.1f} % to {100.0 * best:.1f} %")
+
+    def as_dict(self):
+        """what json.dumps takes: everything but the arrays"""
+        return dict(fraction=self.fraction, per_view=list(self.per_view), unseen_area=self.unseen_area, area=self.area,
+                    samples=int(np.prod(tuple(self.seen.shape))))
 
 
 BOP_TAUS = tuple(0.05 * k for k in range(1, 11))       # BOP's misalignment tolerances of VSD, in units of the object's diameter
@@ -2667,6 +2783,7 @@ mask_depth_stats = _timed("fp_mask_depth_stats", mask_depth_stats)
 depth_agreement = _timed("fp_depth_agreement", depth_agreement)
 pose_errors = _timed("fp_pose_errors", pose_errors)
 mesh_point_distance = _timed("fp_mesh_point_distance", mesh_point_distance)
+mesh_ray_cast = _timed("fp_mesh_ray_cast", mesh_ray_cast)
 mesh_transform_residuals = _timed("fp_mesh_transform_residuals", mesh_transform_residuals)
 mesh_icp_step = _timed("fp_mesh_icp_step", mesh_icp_step)
 icp_point_plane = _timed("fp_icp_point_plane", icp_point_plane)

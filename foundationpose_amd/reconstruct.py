@@ -525,6 +525,12 @@ def sample_surface(mesh_tensors, n, seed=0):
     if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or int(seed) < 0:
         raise ValueError(f"{what}: seed must be an int >= 0, got {seed!r}")
     pos, faces = _mesh_arrays(mesh_tensors, None if isinstance(mesh_tensors, dict) else "cuda", what, "mesh_tensors")
+    return _sample_surface_area(pos, faces, n, seed)[:2]
+
+
+def _sample_surface_area(pos, faces, n, seed):
+    """sample_surface on checked device tensors -> (points, face, the mesh's area: the total of the float64 table the strata are cut
+    from), from the one read of the mesh"""
     cum, target, w = _surface_strata(pos.cpu().numpy(), faces.cpu().numpy(), n, seed)
     dev = pos.device
     f = torch.searchsorted(torch.as_tensor(cum, device=dev), torch.as_tensor(target, device=dev), right=True)
@@ -532,7 +538,7 @@ def sample_surface(mesh_tensors, n, seed=0):
     idx = faces[f].long()
     w = torch.as_tensor(w, device=dev)
     a, b, c = pos[idx[:, 0]], pos[idx[:, 1]], pos[idx[:, 2]]
-    return ((a * w[:, 0:1] + b * w[:, 1:2]) + c * w[:, 2:3]).contiguous(), f
+    return ((a * w[:, 0:1] + b * w[:, 1:2]) + c * w[:, 2:3]).contiguous(), f, float(cum[-1])
 
 
 def _thresholds(thresholds, unit, what):
@@ -626,7 +632,92 @@ def _accel_grid(accel, t, what, keep=None):
     return ops.mesh_grid_build(t)
 
 
-def compare_meshes(a, b, samples=100_000, thresholds=None, seed=0, unit=None, device=None, tf=None, accel=None):
+def _coverage_views(ob_in_cams, Ks, hw, rel_tol, min_cos, what):
+    """the views of view_coverage and its numpy stand-in, checked, float64 on the host -> (P (V,4,4), K (V,3,3), eyes (V,3) float32:
+    -R^T t of each pose taken through float64 and rounded once, (H, W), rel_tol, min_cos)"""
+    P = np.asarray(_host(ob_in_cams), dtype=np.float64)
+    if P.ndim != 3 or P.shape[1:] != (4, 4) or not np.isfinite(P).all():
+        raise ValueError(f"{what}: ob_in_cams must be finite (V,4,4) poses, got shape {P.shape}")
+    K = np.asarray(_host(Ks), dtype=np.float64)
+    if K.shape == (3, 3):
+        K = np.broadcast_to(K, (len(P), 3, 3))
+    if K.shape != (len(P), 3, 3) or not np.isfinite(K).all():
+        raise ValueError(f"{what}: Ks must be finite (3,3) or (V,3,3) intrinsics for {len(P)} views, got shape {K.shape}")
+    try:
+        H, W = (int(x) for x in hw)
+    except (TypeError, ValueError):
+        raise ValueError(f"{what}: hw must be (height, width), got {hw!r}") from None
+    if H < 1 or W < 1:
+        raise ValueError(f"{what}: hw must be (height, width) >= 1, got {hw!r}")
+    rel_tol, min_cos = ops._check_rel_tol(what, rel_tol), float(min_cos)
+    if not 0.0 <= min_cos < 1.0:
+        raise ValueError(f"{what}: min_cos must be in [0, 1), got {min_cos!r}")
+    eyes = (-np.einsum("vji,vj->vi", P[:, :3, :3], P[:, :3, 3])).astype(np.float32)
+    return P, np.ascontiguousarray(K), eyes, (H, W), rel_tol, min_cos
+
+
+def _in_frame_and_facing(xp, p, n, P, K, eyes, hw, min_cos):
+    """what view_coverage and its numpy stand-in share, float64, one order of operations: (V,n) bool, sample i projects inside view
+    v's frame at positive depth and its face looks at the eye.  xp: torch or numpy; p (n,3) the samples and n (n,3) their faces'
+    normals ab x ac, P (V,4,4), K (V,3,3), eyes (V,3), all float64 arrays of xp.  The pixel of a projection is floor(u + 0.5), as
+    everywhere in the library; facing is cos > min_cos on the face normal, for min_cos = 0 the sign of a dot product."""
+    H, W = hw
+    x, y, z = (p[None, :, k] for k in range(3))
+    cam = [((P[:, k, 0, None] * x + P[:, k, 1, None] * y) + P[:, k, 2, None] * z) + P[:, k, 3, None] for k in range(3)]
+    Z = cam[2]
+    front = Z > 0
+    Zs = xp.where(front, Z, xp.ones_like(Z))
+    u = xp.floor(((K[:, 0, 0, None] * cam[0]) / Zs + K[:, 0, 2, None]) + 0.5)
+    v = xp.floor(((K[:, 1, 1, None] * cam[1]) / Zs + K[:, 1, 2, None]) + 0.5)
+    inside = front & (u >= 0) & (u <= W - 1) & (v >= 0) & (v <= H - 1)
+    view = [eyes[:, k, None] - p[None, :, k] for k in range(3)]
+    dotv = (n[None, :, 0] * view[0] + n[None, :, 1] * view[1]) + n[None, :, 2] * view[2]
+    if min_cos == 0.0:
+        return inside & (dotv > 0)
+    nn = (n[:, 0] * n[:, 0] + n[:, 1] * n[:, 1]) + n[:, 2] * n[:, 2]
+    vv = (view[0] * view[0] + view[1] * view[1]) + view[2] * view[2]
+    return inside & (dotv > min_cos * xp.sqrt(nn[None, :] * vv))
+
+
+def view_coverage(mesh, ob_in_cams, Ks, hw, samples=100_000, seed=0, rel_tol=1e-4, min_cos=0.0, accel=None):
+    """What of a mesh's surface did a set of views see -> ops.ViewCoverage: per surface sample the number of views that see it (`seen`,
+    on the device), the fraction of the surface that at least one view sees, the fraction each view sees, and the unseen area.
+    mesh: a mesh-tensor dict (pos, faces) or a SimpleMesh; ob_in_cams (V,4,4) the object's pose in each camera, Ks (3,3) or (V,3,3),
+    hw = (height, width) of the views' frames, all in the mesh's frame and unit.  The samples are sample_surface's (area-stratified,
+    so a fraction of samples is a fraction of area; seed).  View v sees sample i when the sample projects inside the frame at
+    positive depth, its face looks at the eye (cos > min_cos on the face normal ab x ac: the texture bake's facing test), and
+    ops.mesh_visibility from the view's eye (-R^T t, through float64, rounded once) says no face of the mesh lies between; rel_tol
+    is relative to the distance from the eye to the sample (ops.mesh_visibility).  Brute force: V x samples x faces pair tests, a
+    setup / evaluation call, and it synchronises (the mesh is read back once by the sampler, and the table once for the statistics,
+    float64 on the host).  accel must be None: answering the rays through the uniform grid (a 3D-DDA walk) is not built yet."""
+    what = "view_coverage"
+    samples = _check_count(samples, what, "samples")
+    if accel is not None:
+        if accel == "grid":
+            raise NotImplementedError(f"{what}: accel='grid' is not built yet: ray queries through the uniform grid (a 3D-DDA walk with "
+                                      f"a float32 proof of its own) are the follow-up; pass accel=None (brute force)")
+        raise ValueError(f"{what}: accel must be None, got {accel!r}")
+    views = _coverage_views(ob_in_cams, Ks, hw, rel_tol, min_cos, what)
+    t = dict(zip(("pos", "faces"), _mesh_arrays(mesh, None if isinstance(mesh, dict) else "cuda", what, "mesh")))
+    return _coverage_of_samples(t, *_sample_surface_area(t["pos"], t["faces"], samples, seed), *views)
+
+
+def _coverage_of_samples(t, pts, f, area, P, K, eyes, hw, rel_tol, min_cos):
+    """view_coverage of the samples (pts, f) of the mesh-tensor dict t, whose area is `area`, from checked views (_coverage_views)"""
+    dev = pts.device
+    idx = t["faces"][f].long()
+    a, b, c = (t["pos"][idx[:, k]].double() for k in range(3))
+    ab, ac = b - a, c - a
+    n = torch.stack([ab[:, 1] * ac[:, 2] - ab[:, 2] * ac[:, 1], ab[:, 2] * ac[:, 0] - ab[:, 0] * ac[:, 2],
+                     ab[:, 0] * ac[:, 1] - ab[:, 1] * ac[:, 0]], dim=1)
+    eyes_d = torch.as_tensor(eyes, device=dev)
+    table = _in_frame_and_facing(torch, pts.double(), n, torch.as_tensor(P, device=dev), torch.as_tensor(K, device=dev),
+                                 eyes_d.double(), hw, min_cos)
+    table &= ops.mesh_visibility(pts, eyes_d, t, rel_tol=rel_tol)
+    return ops.ViewCoverage.from_seen(table, pts, f, area)
+
+
+def compare_meshes(a, b, samples=100_000, thresholds=None, seed=0, unit=None, device=None, tf=None, accel=None, seen_from=None):
     """How good is mesh a (what was built) against mesh b (the reference) -> ops.MeshComparison: accuracy (the exact distances of
     `samples` surface samples of a to the surface of b: mean / median / p99 / max), completeness (b's samples to a's surface), the
     chamfer distance (the mean of the two means), the Hausdorff distance of the samples, and per threshold precision, recall and
@@ -638,10 +729,21 @@ def compare_meshes(a, b, samples=100_000, thresholds=None, seed=0, unit=None, de
     ops.MeshAlignment (align_meshes) that takes a's coordinates into b's frame, applied to a's vertices (in float64, rounded once)
     before anything is sampled; None: the meshes are in one frame already.  accel="grid": the distances are answered through a
     uniform grid over each mesh (ops.mesh_grid_build, built here once per mesh): the same report bit for bit, from far fewer pair
-    tests; None: brute force."""
+    tests; None: brute force.  seen_from: a dict(ob_in_cams=, Ks=, hw=) of views in b's frame (and rel_tol= / min_cos=, as
+    view_coverage takes them): b's samples are restricted to those view_coverage reports seen by at least one of the views, so that
+    completeness, recall and b's side of chamfer and hausdorff no longer charge a for what no view could see (the underside of an
+    object fused from a ring of views); the report's `coverage` is the fraction of b's samples kept; views that see none of
+    them are refused.  None: every sample of b."""
     what = "compare_meshes"
     samples = _check_count(samples, what, "samples")
     thr = _thresholds(thresholds, unit, what)
+    views = None
+    if seen_from is not None:
+        if not isinstance(seen_from, dict) or not {"ob_in_cams", "Ks", "hw"} <= set(seen_from) <= {"ob_in_cams", "Ks", "hw", "rel_tol",
+                                                                                                  "min_cos"}:
+            raise ValueError(f"{what}: seen_from must be a dict with ob_in_cams, Ks, hw (and rel_tol, min_cos), got {seen_from!r}")
+        views = _coverage_views(seen_from["ob_in_cams"], seen_from["Ks"], seen_from["hw"], seen_from.get("rel_tol", 1e-4),
+                                seen_from.get("min_cos", 0.0), f"{what}: seen_from")
     if device is None:
         device = next((m["pos"].device for m in (a, b) if isinstance(m, dict) and torch.is_tensor(m.get("pos"))), "cuda")
     ta, tb = (dict(zip(("pos", "faces"), _mesh_arrays(m, device, what, name))) for m, name in ((a, "a"), (b, "b")))
@@ -649,11 +751,19 @@ def compare_meshes(a, b, samples=100_000, thresholds=None, seed=0, unit=None, de
         m = torch.as_tensor(_rigid_tf(tf, what), device=ta["pos"].device)
         ta["pos"] = (ta["pos"].double() @ m[:3, :3].T + m[:3, 3]).float().contiguous()
     pa, _ = sample_surface(ta, samples, seed)
-    pb, _ = sample_surface(tb, samples, seed)
+    pb, fb, area_b = _sample_surface_area(tb["pos"], tb["faces"], samples, seed)      # sample_surface(tb, samples, seed), and b's area
+    coverage = None
+    if views is not None:
+        cov = _coverage_of_samples(tb, pb, fb, area_b, *views)
+        if cov.fraction == 0.0:
+            raise ValueError(f"{what}: seen_from: none of b's {samples} samples is seen by any of the {len(cov.per_view)} views (are the "
+                             f"poses in b's frame and unit?): completeness over nothing is not a figure")
+        pb, coverage = pb[cov.seen > 0].contiguous(), cov.fraction
     # the square root through float64: the correctly rounded float32 root whatever the device's float32 sqrt does in its last bit
     d_ab = ops.mesh_point_distance(pa, tb, want=("dist2",), grid=_accel_grid(accel, tb, what))["dist2"].double().sqrt_().float()
     d_ba = ops.mesh_point_distance(pb, ta, want=("dist2",), grid=_accel_grid(accel, ta, what))["dist2"].double().sqrt_().float()
-    return ops.MeshComparison.from_distances(d_ab, d_ba, thr)
+    report = ops.MeshComparison.from_distances(d_ab, d_ba, thr)
+    return report if coverage is None else report._replace(coverage=coverage)
 
 
 def _signed(points, mesh, what, allow_open, accel=None):

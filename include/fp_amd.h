@@ -115,7 +115,9 @@ const char* fp_last_error(void);
  *               the two point queries answered from it with the brute force's bits.  The number stays for the same reason.
  *   234 (kept): + fp_mesh_grid_transform_residuals, fp_mesh_grid_icp_step, fp_mesh_grid_penetration (additions only): the three
  *               batched transform queries answered from the same grid with the brute force's bits.  The number stays for the same
- *               reason: tests/test_mesh_signed_host.py pins it, and a binding finds an older library by the symbols' absence. */
+ *               reason: tests/test_mesh_signed_host.py pins it, and a binding finds an older library by the symbols' absence.
+ *   234 (kept): + fp_mesh_ray_cast, fp_mesh_ray_cast_workspace_bytes (additions only): what a ray hits first on a triangle mesh, by
+ *               brute force on the scan's own tile.  The number stays for the same reason. */
 #define FP_AMD_ABI_VERSION 234
 int fp_version(void);
 
@@ -340,6 +342,45 @@ int fp_mesh_point_distance(const float* pos /*dev Nv,3*/, int Nv, const int32_t*
                            const float* points /*dev Q,3*/, int Q,
                            float* dist2 /*dev Q*/, int32_t* face /*dev Q|NULL*/, float* closest /*dev Q,3|NULL*/,
                            void* workspace /*dev*/, size_t workspace_bytes, void* stream);
+
+/* What R rays hit first on a triangle mesh: per ray the parameter t of the first intersection, that triangle's index, the barycentric
+ * coordinates of the hit and the hit point.  Brute force over every (ray, triangle) pair is the definition and the implementation.
+ * Every operation below is one float32 operation (IEEE, round to nearest even), without contraction, in the order written;
+ * dot(x, y) = (x0*y0 + x1*y1) + x2*y2;  x cross y = (x1*y2 - x2*y1, x2*y0 - x0*y2, x0*y1 - x1*y0), each component one difference of
+ * two products.  Ray i is o + t d with o = origins[i], d = dirs[i]; d need not be a unit vector, and t is in units of d.
+ * Candidate of the ray for triangle f with vertices a, b, c read as fp_mesh_point_distance reads them (Moeller and Trumbore, Fast,
+ * Minimum Storage Ray/Triangle Intersection, 1997), ab = b - a, ac = c - a:
+ *   pvec = d cross ac;  det = dot(ab, pvec);  tvec = o - a;  un = dot(tvec, pvec);
+ *   qvec = tvec cross ab;  vn = dot(d, qvec);  tn = dot(ac, qvec);
+ *   s = det < 0 ? -1 : +1;  D = |det|;  U = s*un;  V = s*vn;  T = s*tn   (exact sign changes);   t = T / D
+ *   hit  <=>  D > 0  &&  U >= 0  &&  V >= 0  &&  (U + V) <= D  &&  t_min <= t <= t_max  &&  t <= FLT_MAX
+ * cull: 0 keeps both sides of a face, 1 only det > 0 (the ray meets the face against its normal ab cross ac: back faces are
+ * dropped), 2 only det < 0.  There is no epsilon anywhere: a degenerate triangle and a ray in a triangle's plane have det == 0 and
+ * never answer; a comparison with a NaN does not hold, so a NaN or infinite vertex that reaches a test, an index outside 0..Nv-1 (NaN
+ * vertices; nothing of pos is read for it), a non-finite ray and a zero direction never answer either.  The t of a hit that compares
+ * equal to 0 is recorded as +0.
+ * The answer of a ray is the candidate with the smallest (t, f) in lexicographic order: equal t go to the smaller face index.
+ *   t[i] = t,  face[i] = f,  bary[i] = (U / D, V / D),  hit[i] = (o.x + t*d.x, o.y + t*d.y, o.z + t*d.z)
+ * (the hit is a + bary.u * ab + bary.v * ac up to rounding).  A ray that nothing answers: t[i] = +inf, face[i] = -1, bary and hit NaN.
+ * The intersection is NOT watertight: each triangle is tested with its own roundings, so a ray through an edge or a vertex that two
+ * faces share can miss both, and where it hits both with equal t the smaller face answers.  Callers that need "is the segment
+ * blocked" keep the segment's end out of the range (t_max < 1) and so do not depend on the end's own face.
+ * A minimum has no summation order, so each output has one value whatever the schedule: a ray has the same bits alone, in a batch and
+ * on every replay.  face, bary and hit may be NULL (not wanted).  One ray per lane; the triangles pass through the LDS tile of
+ * fp_mesh_point_distance, whose a, b - a and c - a are the operands above, and the grid runs over (256 rays) x (a chunk of faces), the
+ * partial minima merged with 64-bit integer atomic minima on the key (bits(t) << 32) | f in the workspace.  An init launch sets the
+ * keys, and a finish launch recomputes U, V, D for the winning face with the same arithmetic and writes the outputs.  R * F pair tests;
+ * R == 0 does nothing.  No allocation, no host synchronisation (graph-capturable); nothing is written outside the outputs and the
+ * workspace (fp_mesh_ray_cast_workspace_bytes(R) bytes = 8 * R, 8-byte aligned; 0 for R <= 0).  Argument errors
+ * (FP_ERR_INVALID_ARG), before any launch, in this order: R, F or Nv negative, R or F above 2^30; not 0 <= t_min <= t_max (t_max may
+ * be +inf; a NaN is refused); cull outside 0..2; then with R > 0: NULL origins, dirs or t; NULL faces with F > 0; NULL pos with Nv > 0
+ * and F > 0; a workspace that is NULL, too small or misaligned. */
+size_t fp_mesh_ray_cast_workspace_bytes(int R);
+int fp_mesh_ray_cast(const float* pos /*dev Nv,3*/, int Nv, const int32_t* faces /*dev F,3*/, int F,
+                     const float* origins /*dev R,3*/, const float* dirs /*dev R,3*/, int R,
+                     float t_min, float t_max, int cull /*0 none, 1 back faces, 2 front faces*/,
+                     float* t /*dev R*/, int32_t* face /*dev R|NULL*/, float* bary /*dev R,2|NULL*/, float* hit /*dev R,3|NULL*/,
+                     void* workspace /*dev*/, size_t workspace_bytes, void* stream);
 
 /* How far does each of T candidate transforms move a mesh's surface off itself: the squared distances of Q transformed points (surface
  * samples, as a rule) to the surface, reduced per transform on the chip.  Every operation is one float32 operation (IEEE, round to

@@ -8,6 +8,8 @@ Without a CAD model: `--ref_views DIR` (a directory in the same layout whose fra
 object's mesh from those reference views (foundationpose_amd/reconstruct.py) in place of --mesh_file; `--synthetic_ref_views N` writes
 such a directory from the can first; `--ref_texture T` bakes a texture atlas of T x T texels a face onto that mesh from the same views;
 `--ref_keep_components largest|N` drops floaters from it (all but the largest surface component, or those under N triangles);
+`--ref_coverage` prints what of the fused surface the reference views saw (reconstruct.view_coverage) as one JSON line
+{"ref_coverage": ...};
 `--save_mesh PATH` writes the mesh that was used: a PLY (positions, normals, vertex colours), or with a path ending in .obj an OBJ with
 its MTL and the texture as a PNG; `--compare_mesh PATH` (with the reference views) compares the fused mesh with the mesh file PATH, in the
 frame of the views' poses -- `--compare_mesh synthetic` with --synthetic_ref_views takes the can the views were rendered from -- and
@@ -112,7 +114,10 @@ def main(argv=None):
     ap.add_argument("--compare_mesh", type=str, default=None, metavar="PATH",
                     help="with --ref_views: compare the fused mesh with this mesh file (or 'synthetic': the can of --synthetic_ref_views) "
                          "and print the report as one JSON line")
-    ap.add_argument("--compare_samples", type=int, default=100_000, help="surface samples per mesh for --compare_mesh")
+    ap.add_argument("--compare_samples", type=int, default=100_000, help="surface samples per mesh for --compare_mesh and --ref_coverage")
+    ap.add_argument("--ref_coverage", action="store_true",
+                    help="with --ref_views: print what of the fused mesh's surface the reference views saw (reconstruct.view_coverage: "
+                         "the fraction seen by any view and by each, the unseen area) as one JSON line")
     ap.add_argument("--signed", action="store_true",
                     help="with --compare_mesh: also print on which side of that mesh the fused surface lies (reconstruct.signed_bias: "
                          "the mean signed distance, negative inside, the share inside and three percentiles) as one JSON line")
@@ -152,6 +157,8 @@ def main(argv=None):
         ap.error("--ref_refine_poses needs --ref_views (or --synthetic_ref_views N)")
     if args.ref_keep_components is not None and not args.ref_views:
         ap.error("--ref_keep_components needs --ref_views (or --synthetic_ref_views N)")
+    if args.ref_coverage and not args.ref_views:
+        ap.error("--ref_coverage needs --ref_views (or --synthetic_ref_views N)")
     if args.compare_mesh and not args.ref_views:
         ap.error("--compare_mesh needs --ref_views (or --synthetic_ref_views N)")
     if args.compare_mesh == "synthetic" and not args.synthetic_ref_views:
@@ -159,7 +166,8 @@ def main(argv=None):
     if args.ref_views:
         from foundationpose_amd.reconstruct import reconstruct_object
         t0 = time.perf_counter()
-        mesh, fused = reconstruct_object(*read_ref_views(args.ref_views), device=dev, texture=args.ref_texture or None,
+        ref = read_ref_views(args.ref_views)
+        mesh, fused = reconstruct_object(*ref, device=dev, texture=args.ref_texture or None,
                                          refine_poses=args.ref_refine_poses, refine_against=args.ref_refine_against,
                                          keep_components=args.ref_keep_components)
         atlas = getattr(getattr(mesh.visual, "material", None), "image", None)
@@ -168,6 +176,13 @@ def main(argv=None):
                      + (f", view poses refined {args.ref_refine_poses} x" if args.ref_refine_poses else "")
                      + ("" if args.ref_keep_components is None else f", {len(mesh.components)} surface components, {mesh.dropped_triangles} triangles dropped")
                      + f" in {time.perf_counter() - t0:.2f} s")
+        if args.ref_coverage:
+            import json
+            from foundationpose_amd.reconstruct import view_coverage
+            poses = getattr(mesh, "ob_in_cams", None)                      # the polished poses of --ref_refine_poses
+            cov = view_coverage(fused, ref[3] if poses is None else poses, ref[4], ref[1].shape[-2:], samples=args.compare_samples)
+            logging.info(cov.describe())
+            print(json.dumps({"ref_coverage": cov.as_dict()}), flush=True)
         if args.compare_mesh:
             import json
             from foundationpose_amd.mesh import make_can_mesh
